@@ -12,6 +12,8 @@ inside the library (the north-star partition).  `python bench.py --gpus N` start
 running under torch.distributed.run.
 `--workload C4opt` is the optimiser's inner loop instead (opt.cpp:441-482): one step = loose_function value + gradient of
 the three density-matrix elements of a 2-state system (2 real + 1 complex GP, N = 4096, 5N extra points each).
+A plain run sets up, warms up, times --steps steps and prints the result line; `--full` adds what the headline figure does not need
+(the pruned-predict leg and the CPU baseline).  `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (float64).
 """
 import argparse
 import ctypes as C
@@ -294,6 +296,48 @@ def emit(result):
     OUT.flush()
 
 
+DUMP_BUDGET = 64 * 10**6  # bytes: all files of one --dump-outputs together
+DUMP_SEED = 20240607
+
+
+def dump_outputs(out_dir, arrays, points=None):
+    """--dump-outputs: one out_dir/<name>.npy (float64) per array of the last timed step.  When the arrays exceed DUMP_BUDGET, those whose
+    first axis runs over the `points` grid points keep one fixed, seeded sample of the points (the same for every array, its indices saved
+    as sample_index); the sample depends only on the sizes, so two builds of the project dump the same points."""
+    arrays = {k: np.ascontiguousarray(np.asarray(v, dtype=np.float64)) for k, v in arrays.items()}
+    size = lambda: sum(a.nbytes + 256 for a in arrays.values())  # 256: room for the .npy header of each file
+    if size() > DUMP_BUDGET and points:
+        per_grid = [k for k, a in arrays.items() if a.ndim and a.shape[0] == points]
+        per_point = sum(arrays[k].nbytes // points for k in per_grid)
+        keep = (DUMP_BUDGET - 256 - (size() - per_point * points)) // (per_point + 8)
+        idx = np.sort(np.random.Generator(np.random.PCG64(DUMP_SEED)).choice(points, keep, replace=False))
+        arrays.update({k: np.ascontiguousarray(arrays[k][idx]) for k in per_grid})
+        arrays["sample_index"] = idx.astype(np.float64)
+    total = size()
+    if total > DUMP_BUDGET:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the budget of {DUMP_BUDGET}")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
+def grid_outputs(out, cplx, prefix=""):
+    """the (rows, M) buffer of a grid predict as the caller sees it: mean, variance, cut-off per point (complex: (re, im) pairs)"""
+    o = out.cpu().numpy()
+    M = o.shape[1]
+    if cplx:
+        return {prefix + "mean": o[0:2].reshape(M, 2), prefix + "variance": o[2], prefix + "cutoff": o[3:5].reshape(M, 2)}
+    return {prefix + "mean": o[0], prefix + "variance": o[1], prefix + "cutoff": o[2]}
+
+
+def scalar_vector(s):
+    """the fit-scalars fields a fit with error + averages computes, in declaration order, as one float64 vector (the *_derivative fields
+    stay unwritten without a derivative request, and info is a status)"""
+    from gaussian_process_liouville_equation_amd import _capi
+    return np.concatenate([np.ravel(np.asarray(v, dtype=np.float64)) for k, v in _capi.scalars_to_dict(s).items()
+                           if not k.endswith("_derivative") and k != "info"])
+
+
 OUT = sys.stdout
 
 
@@ -304,7 +348,12 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="C4r", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the library's default (pruned) predict timed after the full one "
+                         "(grid workloads on one GPU) and the CPU baseline (grid and NLML workloads on one GPU)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float64, at most 64 MB: a fixed sample of the grid above that)")
     ap.add_argument("--prune", action="store_true",
                     help="time the library's default predict (far grid rows not contracted) as `value` instead of the full contraction")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
@@ -528,6 +577,8 @@ def main():
     if tuple(full.shape) != (rows, M) or not bool(torch.isfinite(full).all()):
         raise RuntimeError("gathered prediction has the wrong shape or contains non-finite values")
     ms_per_step = 1e3 * elapsed / args.steps
+    if args.dump_outputs and rank == 0:  # before the --full leg below reuses the buffers
+        dump_outputs(args.dump_outputs, dict(grid_outputs(full, cplx), fit_scalars=scalar_vector(sc)), points=M)
 
     _, fit_total, fit_cnt = api.timing(0)
     _, pred_total, pred_cnt = api.timing(1)
@@ -595,7 +646,7 @@ def main():
                                              "note": "per-rank step of the sharded predict on ONE GPU (fit + this rank's blocks + unpack; stand-in transport): a proxy, not a judged value"}
     if last.get("recovered"):
         result["recovered_from_give_up"] = last["recovered"]
-    if world == 1 and not args.prune and emu is None:
+    if args.full and world == 1 and not args.prune and emu is None:
         full_out = last["full"].clone()
         predict_mode["flag"] = 0
         api.prune_stats(reset=True)
@@ -613,7 +664,7 @@ def main():
                             "bit_identical_to_full": bool(torch.equal(full_out, last["full"])),
                             "note": "the library's default predict: grid rows with |k*|^2 < 2^-56 sf^2 sn^2 k(x*,x*) are not contracted "
                                     "(k(x*,x*) - k* K^-1 k*^T rounds to k(x*,x*) either way; blocks_* count live / all rows in units of 128); not the judged value"}
-    if rank == 0 and not args.no_cpu_baseline and world == 1 and emu is None:
+    if args.full and rank == 0 and not args.no_cpu_baseline and world == 1 and emu is None:
         result["cpu_baseline"] = cpu_baseline(args.workload, N, G, kernel, X, y, grid, theta)
     if rank == 0:
         emit(result)
@@ -760,6 +811,11 @@ def elements_step(args, pkg, c, parallel, torch, dist, rank, world, dev):
     if not bool(torch.isfinite(last["scalars"]).all()):
         raise RuntimeError("non-finite element scalars")
     ms = 1e3 * elapsed / args.steps
+    if args.dump_outputs and rank == 0:
+        arrays = {"element_scalars": last["scalars"].cpu().numpy()}
+        for e, o in enumerate(last["outs"]):
+            arrays.update(grid_outputs(o, data[e]["cplx"], prefix=f"element{e}_"))
+        dump_outputs(args.dump_outputs, arrays, points=M)
     _, fit_total, fit_cnt = api.timing(0)
     _, pk_total, pk_cnt = api.timing(2)
     # contraction flops this rank executed per step: its share of every element (complex: 2 typed rows per point against the 2N x 2N factor)
@@ -849,6 +905,14 @@ def step_loop(args, pkg, torch, dist, rank, world, dev):
     if not np.isfinite(pop):
         raise RuntimeError("non-finite population after the tick")
     ms = 1e3 * elapsed / args.steps
+    if args.dump_outputs and rank == 0:  # the tick's results: the evolved points and labels of every element, the refitted population
+        arrays = {"population": [pop]}
+        for k, e in enumerate(order):
+            for tag, (Xk, yk) in (("density", state["d"][e]), ("extra", state["x"][e])):
+                yk = np.asarray(yk)
+                arrays[f"{tag}{k}_x"] = Xk
+                arrays[f"{tag}{k}_y"] = np.stack([yk.real, yk.imag], axis=-1) if np.iscomplexobj(yk) else yk
+        dump_outputs(args.dump_outputs, arrays)
     # contraction flops of the batched predicts of one tick: every element is asked at NE branches of the (N + 5N) points of each of the NE
     # elements (two levels: 8 of the 9 — the exact density stands in for one); complex: 2 typed rows, n = 2N
     NE = len(order)
@@ -925,6 +989,8 @@ def nlml_step(args, pkg, c, torch, dist, rank, world, dev):
     if not (np.isfinite(val.value) and np.all(np.isfinite(grad)) and bool(torch.isfinite(dmean).all())):
         raise RuntimeError("non-finite NLML value, gradient or prediction")
     ms = 1e3 * elapsed / args.steps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"nlml_value": [val.value], "nlml_gradient": grad, "mean": dmean.cpu().numpy()}, points=M)
     _, f_total, f_cnt = api.timing(0)  # HIP events around chol_inverse_factor: L = chol(K) and T = L^-1 (two per step)
     _, p_total, p_cnt = api.timing(1)  # around the prediction kernels
     n = -(-N // 256) * 256
@@ -947,7 +1013,7 @@ def nlml_step(args, pkg, c, torch, dist, rank, world, dev):
         "exp_rate": round(float(M) * N / (p_ms * 1e-3), 1) if p_ms > 0 else None,
         "nlml": {"value": val.value, "gradient": [float(g) for g in grad]},
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import binding
         ora = binding.load()
         t0 = time.perf_counter()
@@ -1034,6 +1100,8 @@ def opt_loop(args, pkg, c, parallel, torch, dist, rank, world, dev):
     if not bool(torch.isfinite(allv).all()):
         raise RuntimeError("non-finite objective value or gradient")
     ms = 1e3 * elapsed / args.steps
+    if args.dump_outputs and rank == 0:  # per element: the objective value, then its gradient (zero-padded to 8)
+        dump_outputs(args.dump_outputs, {"objective": allv.cpu().numpy()})
     # derivative GEMMs dK * K^-1 (kernel.cpp:354): HIP events of the library around each launch; 2 n^3 flops each
     gemm_ms, gemm_cnt, gemm_flops, per_elem = 0.0, 0, 0.0, {}
     for slot, i in enumerate(mine):
