@@ -206,6 +206,7 @@ GPLE_SYMBOLS = [
     "real_fit_create", "real_fit_get_scalars", "real_fit_retain", "real_fit_release", "real_fit_size", "real_fit_get", "real_predict",
     "complex_fit_create", "complex_fit_get_scalars", "complex_fit_retain", "complex_fit_release", "complex_fit_size", "complex_fit_get",
     "complex_predict", "loose_function", "objective_create", "objective_eval", "objective_eval_part", "objective_release", "minimize_neldermead", "objective_minimize_neldermead", "minimize_direct_l", "objective_minimize_direct_l", "minimize_auglag_eq", "pes_adiabatic", "evolve", "evolve_n", "pes_adiabatic_n", "markov_chain", "markov_chain_trace", "nlml", "nlml_predict", "nlml_cross", "nlml_cross_predict",
+    "dvr_hamiltonian", "dvr_propagate", "wigner",
 ]
 
 
@@ -492,6 +493,51 @@ class Api:
                 NAC[:, k, l], NAC[:, l, k] = out[:, num_pes + ne + e], -out[:, num_pes + ne + e]
                 e += 1
         return E, F, NAC
+
+    # ---- exact DVR dynamics (schrodinger_equation/ of the reference; gple_dvr_* / gple_wigner) ----------------------------------------------
+    DVR_REFLECTIVE, DVR_PERIODIC = 0, 1
+
+    def dvr_hamiltonian(self, num_pes, model, boundary, x_first, dx, n_grids, mass, want_h=True, want_states=True):
+        """gple_dvr_hamiltonian: (H (dim, dim) or None, energies (n, num_pes) or None, basis (n, num_pes, num_pes) or None, columns = states)"""
+        dim = num_pes * n_grids
+        H = np.empty((dim, dim)) if want_h else None
+        E = np.empty((n_grids, num_pes)) if want_states else None
+        B = np.empty((n_grids, num_pes, num_pes)) if want_states else None
+        f = self.lib.gple_dvr_hamiltonian
+        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_size_t, C.c_double, C.c_uint, _dp, _dp, _dp]
+        self._check(f(self.ctx, int(num_pes), int(model), int(boundary), float(x_first), float(dx), int(n_grids), float(mass), 0, _ptr(H), _ptr(E), _ptr(B)))
+        return H, E, B
+
+    def dvr_propagate(self, num_pes, n_grids, eigvec, eigval, psi0, times, basis=None, from_psi0=True):
+        """gple_dvr_propagate: psi(t) = C exp(-i E t) C^T psi0 at every time (from_psi0=False: psi0 already holds c0 = C^T psi0);
+        eigvec[r, k] = component r of eigenvector k (numpy.linalg.eigh); basis (n, num_pes, num_pes): adiabatic output.  -> (T, dim) complex"""
+        eigvec, eigval, times = _f64(eigvec), _f64(eigval), _f64(np.atleast_1d(times))
+        psi0 = _cplx(psi0)
+        dim = num_pes * n_grids
+        if eigvec.shape != (dim, dim) or eigval.shape != (dim,) or psi0.shape != (dim,):
+            raise ValueError("eigvec (dim, dim), eigval (dim,) and psi0 (dim,) with dim = num_pes * n_grids")
+        basis = None if basis is None else _f64(basis)
+        out = np.empty((len(times), dim), dtype=np.complex128)
+        f = self.lib.gple_dvr_propagate
+        f.argtypes = [C.c_void_p, C.c_int, C.c_size_t, _dp, _dp, _dp, _dp, C.c_size_t, _dp, C.c_uint, _dp]
+        self._check(f(self.ctx, int(num_pes), int(n_grids), _ptr(eigvec), _ptr(eigval), _ptr(psi0.view(np.float64)), _ptr(times), len(times), _ptr(basis),
+                      0x800 if from_psi0 else 0, _ptr(out.view(np.float64))))
+        return out
+
+    def wigner(self, num_pes, boundary, x_first, dx, p, psi, energies=None, mass=0.0, phase=True, averages=False):
+        """gple_wigner on psi (T, num_pes * n) complex: (P (T, num_pes, num_pes, n, n_p) complex or None, averages (T, 3) = (E, x, p) or None)"""
+        p = _f64(p)
+        psi = _cplx(np.atleast_2d(psi))
+        T = psi.shape[0]
+        n = psi.shape[1] // num_pes
+        P = np.empty((T, num_pes, num_pes, n, len(p)), dtype=np.complex128) if phase else None
+        av = np.empty((T, 3)) if averages else None
+        en = None if energies is None else _f64(energies)
+        f = self.lib.gple_wigner
+        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_double, C.c_double, _dp, C.c_size_t, _dp, C.c_size_t, _dp, C.c_double, C.c_uint, _dp, _dp]
+        self._check(f(self.ctx, int(num_pes), int(boundary), n, float(x_first), float(dx), _ptr(p), len(p), _ptr(psi.view(np.float64)), T, _ptr(en),
+                      float(mass), 0, None if P is None else _ptr(P.view(np.float64)), _ptr(av)))
+        return P, av
 
     def evolve_n(self, num_pes, fits, model, mass, dt, density, new_points=False):
         """gple_evolve_n: one tick for an N-level system; fits and density in the packing order (0,0), (1,0), (1,1), (2,0), ...;

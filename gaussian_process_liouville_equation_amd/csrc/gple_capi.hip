@@ -2510,6 +2510,155 @@ extern "C"
 		return GPLE_OK;
 	}
 
+	/* ---- exact DVR dynamics (gple_dvr.hip; schrodinger_equation/general.cpp of the reference) ---------------------------------------------- */
+	static bool dvr_model_ok(int num_pes, int model) { return (num_pes == 2 || num_pes == 3) && model >= 0 && model <= (num_pes == 3 ? 3 : 2); }
+	static bool dvr_grid_ok(size_t n_grids, double dx) { return n_grids >= 2 && n_grids <= (1u << 16) && dx > 0.0 && std::isfinite(dx); }
+
+	int gple_dvr_hamiltonian(gple_ctx* ctx, int num_pes, int model, int boundary, double x_first, double dx, size_t n_grids, double mass, unsigned flags,
+		double* H, double* energies, double* basis)
+	{
+		if (!ctx || !dvr_model_ok(num_pes, model) || (boundary != GPLE_DVR_REFLECTIVE && boundary != GPLE_DVR_PERIODIC) || !dvr_grid_ok(n_grids, dx) ||
+			!std::isfinite(x_first) || !(mass > 0.0))
+			return GPLE_ERR_BAD_ARG;
+		GPLE_OPEN(ctx);
+		const bool dev = flags & GPLE_IO_DEVICE;
+		const int n = static_cast<int>(n_grids);
+		const size_t dim = static_cast<size_t>(num_pes) * n_grids;
+		std::lock_guard<std::mutex> lk(ctx->call_mu);
+		GPLE_HIP(ctx, hipSetDevice(ctx->device));
+		hipStream_t st = ctx->stream;
+		Scratch hd(ctx), ed(ctx), bd(ctx), sw(ctx);
+		double* h = H;
+		double* e = energies;
+		double* b = basis;
+		if (!dev)
+		{
+			if (H) GPLE_HIP(ctx, hd.get(dim * dim));
+			if (energies) GPLE_HIP(ctx, ed.get(n_grids * num_pes));
+			if (basis) GPLE_HIP(ctx, bd.get(n_grids * num_pes * num_pes));
+			h = hd.p, e = ed.p, b = bd.p;
+		}
+		if (h) GPLE_HIP(ctx, launch_dvr_hamiltonian(st, num_pes, model, boundary, x_first, dx, n, mass, h));
+		if (e || b)
+		{
+			GPLE_HIP(ctx, sw.get(dvr_states_work_doubles(num_pes, n)));
+			GPLE_HIP(ctx, launch_dvr_states(st, num_pes, model, x_first, dx, n, e, b, sw.p));
+		}
+		if (!dev)
+		{
+			if (H) GPLE_HIP(ctx, copy_out(st, H, hd.p, dim * dim, false));
+			if (energies) GPLE_HIP(ctx, copy_out(st, energies, ed.p, n_grids * num_pes, false));
+			if (basis) GPLE_HIP(ctx, copy_out(st, basis, bd.p, n_grids * num_pes * num_pes, false));
+			GPLE_HIP(ctx, hipStreamSynchronize(st));
+		}
+		return GPLE_OK;
+	}
+
+	int gple_dvr_propagate(gple_ctx* ctx, int num_pes, size_t n_grids, const double* eigvec, const double* eigval, const double* psi0_or_c0, const double* times,
+		size_t T, const double* basis, unsigned flags, double* psi)
+	{
+		if (!ctx || (num_pes != 2 && num_pes != 3) || !dvr_grid_ok(n_grids, 1.0) || T > 4096 || (T && (!eigvec || !eigval || !psi0_or_c0 || !times || !psi)))
+			return GPLE_ERR_BAD_ARG;
+		GPLE_OPEN(ctx);
+		if (T == 0) return GPLE_OK;
+		const bool dev = flags & GPLE_IO_DEVICE;
+		const int n = static_cast<int>(n_grids);
+		const size_t dim = static_cast<size_t>(num_pes) * n_grids, ld = round_up(dim, 64);
+		std::lock_guard<std::mutex> lk(ctx->call_mu);
+		GPLE_HIP(ctx, hipSetDevice(ctx->device));
+		hipStream_t st = ctx->stream;
+		Scratch work(ctx), ev(ctx), vin(ctx), tm(ctx), bs(ctx), out(ctx);
+		GPLE_HIP(ctx, work.get(dvr_propagate_work_doubles(num_pes, n, static_cast<int>(T))));
+		// C into the zero-padded ld x ld block
+		GPLE_HIP(ctx, hipMemsetAsync(work.p, 0, ld * ld * sizeof(double), st));
+		GPLE_HIP(ctx, hipMemcpy2DAsync(work.p, ld * sizeof(double), eigvec, dim * sizeof(double), dim * sizeof(double), dim,
+			dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+		const double *e = eigval, *v = psi0_or_c0, *t = times, *b = basis;
+		double* o = psi;
+		if (!dev)
+		{
+			GPLE_HIP(ctx, ev.get(dim));
+			GPLE_HIP(ctx, vin.get(2 * dim));
+			GPLE_HIP(ctx, tm.get(T));
+			GPLE_HIP(ctx, out.get(2 * dim * T));
+			GPLE_HIP(ctx, copy_in(st, ev.p, eigval, dim, false));
+			GPLE_HIP(ctx, copy_in(st, vin.p, psi0_or_c0, 2 * dim, false));
+			GPLE_HIP(ctx, copy_in(st, tm.p, times, T, false));
+			e = ev.p, v = vin.p, t = tm.p, o = out.p;
+			if (basis)
+			{
+				GPLE_HIP(ctx, bs.get(n_grids * num_pes * num_pes));
+				GPLE_HIP(ctx, copy_in(st, bs.p, basis, n_grids * num_pes * num_pes, false));
+				b = bs.p;
+			}
+		}
+		GPLE_HIP(ctx, launch_dvr_propagate(st, num_pes, n, e, v, t, static_cast<int>(T), b, (flags & GPLE_DVR_PSI0) != 0, work.p, o));
+		if (!dev)
+		{
+			GPLE_HIP(ctx, copy_out(st, psi, out.p, 2 * dim * T, false));
+			GPLE_HIP(ctx, hipStreamSynchronize(st));
+		}
+		return GPLE_OK;
+	}
+
+	int gple_wigner(gple_ctx* ctx, int num_pes, int boundary, size_t n_grids, double x_first, double dx, const double* p, size_t n_p, const double* psi,
+		size_t T, const double* energies, double mass, unsigned flags, double* phase, double* averages)
+	{
+		if (!ctx || (num_pes != 2 && num_pes != 3) || (boundary != GPLE_DVR_REFLECTIVE && boundary != GPLE_DVR_PERIODIC) || !dvr_grid_ok(n_grids, dx) ||
+			!std::isfinite(x_first) || n_p < 2 || n_p > (1u << 16) || T * num_pes * (num_pes + 1) / 2 > 65535 || (T && (!p || !psi)) ||
+			(averages && (!energies || !(mass > 0.0))))
+			return GPLE_ERR_BAD_ARG;
+		GPLE_OPEN(ctx);
+		if (T == 0 || (!phase && !averages)) return GPLE_OK;
+		const bool dev = flags & GPLE_IO_DEVICE;
+		const int n = static_cast<int>(n_grids), np = static_cast<int>(n_p);
+		const size_t dim = static_cast<size_t>(num_pes) * n_grids, pdoubles = 2 * T * num_pes * num_pes * n_grids * n_p;
+		std::lock_guard<std::mutex> lk(ctx->call_mu);
+		GPLE_HIP(ctx, hipSetDevice(ctx->device));
+		hipStream_t st = ctx->stream;
+		Scratch table(ctx), pd(ctx), psd(ctx), Pd(ctx), ed(ctx), avw(ctx), avd(ctx);
+		GPLE_HIP(ctx, table.get(wigner_table_doubles(boundary, n, np)));
+		const double *pp = p, *ps = psi, *en = energies;
+		double* P = phase;
+		double* av = averages;
+		if (!dev)
+		{
+			GPLE_HIP(ctx, pd.get(n_p));
+			GPLE_HIP(ctx, psd.get(2 * dim * T));
+			GPLE_HIP(ctx, copy_in(st, pd.p, p, n_p, false));
+			GPLE_HIP(ctx, copy_in(st, psd.p, psi, 2 * dim * T, false));
+			pp = pd.p, ps = psd.p;
+			if (averages)
+			{
+				GPLE_HIP(ctx, ed.get(n_grids * num_pes));
+				GPLE_HIP(ctx, avd.get(3 * T));
+				GPLE_HIP(ctx, copy_in(st, ed.p, energies, n_grids * num_pes, false));
+				en = ed.p, av = avd.p;
+			}
+		}
+		if (!dev || !phase)
+		{
+			GPLE_HIP(ctx, Pd.get(pdoubles));
+			P = Pd.p;
+		}
+		GPLE_HIP(ctx, launch_wigner_table(st, boundary, n, pp, np, dx, table.p));
+		timer_start(ctx, GPLE_TIMER_WIGNER);
+		GPLE_HIP(ctx, launch_wigner(st, num_pes, boundary, n, dx, table.p, np, ps, static_cast<int>(T), P));
+		timer_stop(ctx, GPLE_TIMER_WIGNER);
+		if (averages)
+		{
+			GPLE_HIP(ctx, avw.get(wigner_avg_work_doubles(num_pes, static_cast<int>(T))));
+			GPLE_HIP(ctx, launch_wigner_averages(st, num_pes, n, x_first, dx, pp, np, en, mass, P, static_cast<int>(T), avw.p, av));
+		}
+		if (!dev)
+		{
+			if (phase) GPLE_HIP(ctx, copy_out(st, phase, P, pdoubles, false));
+			if (averages) GPLE_HIP(ctx, copy_out(st, averages, avd.p, 3 * T, false));
+			GPLE_HIP(ctx, hipStreamSynchronize(st));
+		}
+		return GPLE_OK;
+	}
+
 	int gple_markov_chain(gple_ctx* ctx, const gple_element* element, size_t num_steps, double max_displacement, unsigned long long seed, double* r,
 		size_t n, double* accept_ratio)
 	{

@@ -247,4 +247,22 @@ namespace gple
 		double* const* q, int new_points);
 	hipError_t launch_evolve_combine_n(hipStream_t s, int num_pes, const double* r_new, const double* rho_old, const int* n, double mass, double dt, int model,
 		const double* const* pred, double* rho_new, int new_points);
+	// ---- exact DVR dynamics (gple_dvr.hip): num_pes = 2 or 3, dim = num_pes n, boundary = gple_dvr_boundary ---------------------------
+	// H: dim x dim (symmetric); energies: n x num_pes; basis: n x num_pes x num_pes (columns = adiabatic states); either may be null
+	hipError_t launch_dvr_hamiltonian(hipStream_t s, int num_pes, int model, int boundary, double x_first, double dx, int n, double mass, double* H);
+	size_t dvr_states_work_doubles(int num_pes, int n);
+	hipError_t launch_dvr_states(hipStream_t s, int num_pes, int model, double x_first, double dx, int n, double* energies, double* basis, double* work);
+	// work layout (doubles, ld = dim rounded up to 64): C (ld x ld, row-major, zero padded) | Z, Y (ld x round_up(2T, 64) each) | input (ld x 64:
+	// v = psi0 or c0 (dim (re, im) pairs) split into columns re, im) | c0 (ld x 64).  psi: T x dim (re, im) pairs, adiabatic when basis != null
+	size_t dvr_propagate_work_doubles(int num_pes, int n, int T);
+	hipError_t launch_dvr_propagate(hipStream_t s, int num_pes, int n, const double* eigval, const double* v, const double* times, int T, const double* basis,
+		bool from_psi0, double* work, double* psi);
+	// Wigner transform: table = exp(2 i p y / hbar) (wigner_table_doubles), P: T x num_pes^2 x n x np (re, im) pairs, p fastest
+	int wigner_half_range(int boundary, int n);
+	size_t wigner_table_doubles(int boundary, int n, int np);
+	hipError_t launch_wigner_table(hipStream_t s, int boundary, int n, const double* p, int np, double dx, double* table);
+	hipError_t launch_wigner(hipStream_t s, int num_pes, int boundary, int n, double dx, const double* table, int np, const double* psi, int T, double* P);
+	size_t wigner_avg_work_doubles(int num_pes, int T);
+	hipError_t launch_wigner_averages(hipStream_t s, int num_pes, int n, double x_first, double dx, const double* p, int np, const double* energies,
+		double mass, const double* P, int T, double* work, double* averages);
 } // namespace gple

@@ -1,0 +1,214 @@
+"""Exact DVR wavepacket dynamics: the reference's schrodinger_equation/main.cpp for the reflective and periodic boundaries, restated on the
+library's device entry points (gple_dvr_hamiltonian, gple_dvr_propagate, gple_wigner).
+
+    setup()            main.cpp:41-146 with the defaults of schrodinger_equation/input.py
+    initial_adiabatic_psi(), to_diabatic()  general.cpp:70-103 (Gaussian on the lowest adiabatic surface) taken to the diabatic basis (main.cpp:158-161)
+    run()              the output loop of main.cpp:210-298: propagate, adiabatic psi, populations (general.cpp:480-495), <E> <x> <p> from psi
+                       (general.cpp:443-478), the Wigner transform and its averages (general.cpp:324-411), the stop criteria (main.cpp:256-294)
+    writers            x.txt, p.txt, t.txt, psi.txt, phase.txt, averages.txt in the reference's line layout; numbers as %g (output.py)
+
+The Hamiltonian is diagonalised once per run with numpy.linalg.eigh on the host (set-up, not the hot path: DESIGN.md §11).
+"""
+import math
+import os
+import time
+
+import numpy as np
+
+HBAR = 1.0                 # general.h:35
+CHANGE_LIM = 1e-5  # general.h:46 (PplLim, :45, applies to the absorbing boundary only)
+SAC, DAC, ECR, TSAC = 0, 1, 2, 3
+REFLECTIVE, PERIODIC = 0, 1
+
+
+def cutoff(val):
+    """The power of two <= val (general.cpp:33-36)."""
+    return 2.0 ** int(math.floor(math.log2(val)))
+
+
+def output_time_cutoff(x):
+    """input.py's rounding of the output time to 1eN / 2eN / 5eN / 10eN (int() truncates towards zero, as there)."""
+    logx = np.log10(x)
+    n = int(logx)
+    powx = np.power(10.0, n)
+    resume = logx - n
+    if resume < 0.3:
+        return 2 * powx
+    if resume < 0.7:
+        return 5 * powx
+    return 10 * powx
+
+
+def setup(ln_energy=0.0, mass=2000.0, x0=-8.0, xmin=-15.0, xmax=15.0, dx_max=0.1, number_of_output=50, p0=None, sigma_p=None, output_time=None, dx=None):
+    """The run's constants: input.py's defaults (p0 = sqrt(2 m e^lnE), sigma_p = p0 / 20, output time from the 1-2-5 rounding) then main.cpp:52-146.
+    dx (optional) replaces the grid spacing main.cpp:74 derives (coarse grids for tests and probes)."""
+    if p0 is None:
+        p0 = float(np.sqrt(2.0 * mass * np.exp(ln_energy)))
+    if sigma_p is None:
+        sigma_p = p0 / 20.0
+    if output_time is None:
+        output_time = float(output_time_cutoff((-x0 - x0) / (p0 / mass) / number_of_output))
+    sigma_x = HBAR / 2.0 / sigma_p                                   # main.cpp:59
+    p0max = p0 + 3.0 * sigma_p                                       # main.cpp:66
+    if dx is None:
+        dx = cutoff(min(dx_max, 2 * math.pi * HBAR / p0max / 5.0))   # main.cpp:74
+    n_grids = int((xmax - xmin) / dx) + 1                            # main.cpp:76, 95 (no absorbing region)
+    pmin, pmax = p0 - math.pi * HBAR / dx / 2.0, p0 + math.pi * HBAR / dx / 2.0  # main.cpp:103-104
+    i = np.arange(n_grids)
+    x = xmin + dx * i                                                # main.cpp:108
+    p = ((n_grids - 1 - i) * pmin + i * pmax) / (n_grids - 1)        # main.cpp:109
+    total_time = (xmax - xmin) / (p0 / mass) * 2.0                   # main.cpp:127
+    dt = output_time                                                 # main.cpp:130-140 (no absorbing boundary)
+    return dict(mass=mass, x0=x0, p0=p0, sigma_p=sigma_p, sigma_x=sigma_x, xmin=xmin, xmax=xmax, dx=dx, n_grids=n_grids, x=x, p=p,
+                total_time=total_time, output_time=output_time, dt=dt, total_step=int(total_time / dt), output_step=int(output_time / dt))
+
+
+def initial_adiabatic_psi(x, x0, p0, sigma_x, num_pes):
+    """wavefunction_initialization (general.cpp:75-104): a Gaussian on the lowest surface, normalised on the grid."""
+    n = len(x)
+    dx = (x[n - 1] - x[0]) / (n - 1)
+    psi = np.zeros(num_pes * n, dtype=np.complex128)
+    psi[:n] = np.exp(-((x - x0) / 2 / sigma_x) ** 2 + 1j * (p0 * x / HBAR)) / math.sqrt(math.sqrt(2.0 * math.pi) * sigma_x)
+    psi[:n] /= math.sqrt(np.vdot(psi, psi).real * dx)
+    return psi
+
+
+def to_diabatic(psi_adia, basis):
+    """psi_dia[j n + a] = sum_k C_a(j, k) psi_adia[k n + a] (main.cpp:160-161, pes.cpp:96-120)."""
+    n, num_pes = basis.shape[0], basis.shape[1]
+    return np.einsum("ajk,...ka->...ja", basis, psi_adia.reshape(psi_adia.shape[:-1] + (num_pes, n))).reshape(psi_adia.shape)
+
+
+def to_adiabatic(psi_dia, basis):
+    """psi_adia = basis^T psi_dia per grid point (main.cpp:221)."""
+    n, num_pes = basis.shape[0], basis.shape[1]
+    return np.einsum("ajk,...ja->...ka", basis, psi_dia.reshape(psi_dia.shape[:-1] + (num_pes, n))).reshape(psi_dia.shape)
+
+
+def derivative_matrix(n, dx):
+    """The first-derivative DVR matrix of general.cpp:417-436 on one surface: (-1)^(j-k) / dx / (j - k) off the diagonal."""
+    j = np.arange(n)
+    d = j[:, None] - j[None, :]
+    with np.errstate(divide="ignore"):
+        D = np.where(d == 0, 0.0, np.where(d % 2 == 0, 1.0, -1.0) / dx / np.where(d == 0, 1, d))
+    return D
+
+
+def populations(psi_adia, n, dx, num_pes):
+    """calculate_population (general.cpp:480-495)."""
+    return np.array([np.vdot(psi_adia[m * n:(m + 1) * n], psi_adia[m * n:(m + 1) * n]).real * dx for m in range(num_pes)])
+
+
+def psi_averages(psi_dia, H, D, x, dx, num_pes):
+    """calculate_average (general.cpp:443-478): <E> = psi^H H psi dx, <x> = sum x |psi|^2 dx, <p> = psi^H (-i hbar D) psi dx."""
+    n = len(x)
+    E = np.vdot(psi_dia, H @ psi_dia).real * dx
+    X = float(sum(np.dot(x, np.abs(psi_dia[m * n:(m + 1) * n]) ** 2) for m in range(num_pes))) * dx
+    Dpsi = np.concatenate([D @ psi_dia[m * n:(m + 1) * n] for m in range(num_pes)])
+    P = np.vdot(psi_dia, -1j * HBAR * Dpsi).real * dx
+    return E, X, P
+
+
+def fmt(v):
+    return "%g" % v
+
+
+def write_grid(path, values):
+    """x.txt / p.txt / t.txt: one number per line (main.cpp:112-121, 219)."""
+    with open(path, "w") as f:
+        f.write("".join(fmt(v) + "\n" for v in values))
+
+
+def psi_line(psi_adia):
+    """output_grided_population (general.cpp:281-288): ' |psi_i|^2' for every entry, then a newline."""
+    return "".join(" " + fmt(v) for v in (psi_adia * np.conj(psi_adia)).real) + "\n"
+
+
+def phase_block(P):
+    """One output time of phase.txt (general.cpp:384-409): a line per element (i, j) row-major with ' re im' per (x, p), p fastest, then a
+    blank line.  P: (num_pes, num_pes, n, n_p) complex."""
+    num_pes = P.shape[0]
+    lines = []
+    for i in range(num_pes):
+        for j in range(num_pes):
+            v = P[i, j].reshape(-1)
+            pairs = np.empty(2 * len(v))
+            pairs[0::2], pairs[1::2] = v.real, v.imag
+            lines.append("".join(" " + fmt(u) for u in pairs) + "\n")
+    return "".join(lines) + "\n"
+
+
+def averages_line(t, E, X, P, pops, phase_avg):
+    """One line of averages.txt (main.cpp:245-253): t <E> <x> <p> populations <E> <x> <p> of the Wigner function."""
+    return " ".join(fmt(v) for v in [t, E, X, P, *pops, *phase_avg]) + "\n"
+
+
+def run(api, model=DAC, num_pes=2, boundary=PERIODIC, ln_energy=0.0, out_dir=None, write_phase="text", max_outputs=None, chunk_bytes=1 << 30,
+        p_grid=None, log=None, **setup_kw):
+    """The loop of main.cpp:210-298 for a non-absorbing boundary.  write_phase: "text" (phase.txt), "npy" (phase_<k>.npy per output time) or None;
+    out_dir None writes no file.  max_outputs caps the output times.  Returns a dict with the setup, per-output records and the final stdout line."""
+    s = setup(ln_energy, **setup_kw)
+    n, dx, x, mass = s["n_grids"], s["dx"], s["x"], s["mass"]
+    p = s["p"] if p_grid is None else np.asarray(p_grid, dtype=np.float64)
+    say = log or (lambda *_: None)
+    t0 = time.perf_counter()
+    H, energies, basis = api.dvr_hamiltonian(num_pes, model, boundary, x[0], dx, n, mass)
+    t_h = time.perf_counter()
+    eigval, eigvec = np.linalg.eigh(H)
+    t_eigh = time.perf_counter() - t_h
+    say(f"dx = {dx:g}, {n} grids from {x[0]:g} to {x[-1]:g}; dt = {s['dt']:g}, {s['total_step']} steps; eigh of {num_pes * n} x {num_pes * n}: {t_eigh:.2f} s")
+    psi0 = to_diabatic(initial_adiabatic_psi(x, s["x0"], s["p0"], s["sigma_x"], num_pes), basis)
+    D = derivative_matrix(n, dx)
+    steps = [k for k in range(s["total_step"] + 1) if k % s["output_step"] == 0]
+    if max_outputs is not None:
+        steps = steps[:max_outputs]
+    per_time = 16 * num_pes * num_pes * n * len(p) + 64 * num_pes * n
+    chunk = max(1, min(64, int(chunk_bytes // per_time)))
+    files = {}
+    if out_dir is not None:
+        os.makedirs(out_dir, exist_ok=True)
+        write_grid(os.path.join(out_dir, "x.txt"), x)
+        write_grid(os.path.join(out_dir, "p.txt"), p)
+        for name in ("t.txt", "psi.txt", "averages.txt") + (("phase.txt",) if write_phase == "text" else ()):
+            files[name] = open(os.path.join(out_dir, name), "w")
+    records, stop, last_x, old_pop, pops = [], None, s["x0"], np.zeros(num_pes), None
+    t_loop = time.perf_counter()
+    try:
+        for c0 in range(0, len(steps), chunk):
+            times = np.array([k * s["dt"] for k in steps[c0:c0 + chunk]])
+            psi_dia = api.dvr_propagate(num_pes, n, eigvec, eigval, psi0, times)
+            psi_adia = to_adiabatic(psi_dia, basis)
+            P, wav = api.wigner(num_pes, boundary, x[0], dx, p, psi_adia, energies=energies, mass=mass, phase=write_phase is not None, averages=True)
+            for q, t in enumerate(times):
+                pops = populations(psi_adia[q], n, dx, num_pes)
+                E, X, Pm = psi_averages(psi_dia[q], H, D, x, dx, num_pes)
+                records.append(dict(t=t, E=E, x=X, p=Pm, populations=pops, phase_averages=wav[q].copy()))
+                if files:
+                    files["t.txt"].write(fmt(t) + "\n")
+                    files["psi.txt"].write(psi_line(psi_adia[q]))
+                    files["averages.txt"].write(averages_line(t, E, X, Pm, pops, wav[q]))
+                    if write_phase == "text":
+                        files["phase.txt"].write(phase_block(P[q]))
+                    elif write_phase == "npy":
+                        np.save(os.path.join(out_dir, f"phase_{len(records) - 1}.npy"), P[q])
+                if X > 0.0:  # main.cpp:256-287
+                    if X > -s["x0"]:
+                        stop = f"GET OUT OF INTERACTING REGION, STOP EVOLVING AT {t:g}"
+                    elif (X - last_x) * s["p0"] < 0:
+                        stop = f"DIRECTION REVERSED DUE TO REFLECTION / PBC, STOP EVOLVING AT {t:g}"
+                    elif np.all(np.abs(pops - old_pop) < CHANGE_LIM):
+                        stop = f"POPULATION ON EACH PES IS STABLE. STOP EVOLVING AT {t:g}"
+                    if stop:
+                        break
+                last_x, old_pop = X, pops
+            if stop:
+                break
+    finally:
+        for f in files.values():
+            f.close()
+    t_end = time.perf_counter()
+    head = math.log(s["p0"] ** 2 / 2.0 / mass) if model == DAC else s["p0"]  # main.cpp:308-321
+    final_line = " ".join(fmt(v) for v in [head, *pops])
+    say(stop or "FINISHED ALL OUTPUT TIMES")
+    return dict(setup=s, records=records, stop=stop, final_line=final_line, eigh_seconds=t_eigh, total_seconds=t_end - t0,
+                seconds_per_output=(t_end - t_loop) / max(1, len(records)), stop_time=records[-1]["t"] if records else None)

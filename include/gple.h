@@ -147,7 +147,8 @@ typedef enum gple_timer {
 	GPLE_TIMER_FIT = 0,            /* whole *_fit_create call (device side)                 */
 	GPLE_TIMER_PREDICT = 1,        /* whole *_predict call (device side)                    */
 	GPLE_TIMER_PREDICT_KERNEL = 2, /* the MFMA row-norm kernel of *_predict alone; count = its launches */
-	GPLE_TIMER_DERIV_GEMM = 3      /* the dK * K^-1 MFMA GEMM of a GPLE_CALC_DERIVATIVE fit (kernel.cpp:354); count = its launches */
+	GPLE_TIMER_DERIV_GEMM = 3,     /* the dK * K^-1 MFMA GEMM of a GPLE_CALC_DERIVATIVE fit (kernel.cpp:354); count = its launches */
+	GPLE_TIMER_WIGNER = 4          /* the MFMA kernel of gple_wigner alone (all T output times of a call); count = its launches */
 } gple_timer;
 int gple_ctx_enable_timing(gple_ctx* ctx, int on);
 /* Synchronises the stream, then: last = milliseconds of the most recent interval; total / count = accumulated since
@@ -365,6 +366,39 @@ int gple_evolve_n(gple_ctx* ctx, int num_pes, const gple_element* elements, int 
 /* adiabatic_potential / adiabatic_force / adiabatic_coupling (pes.cpp:98-155) for num_pes levels at M positions:
  * out[(num_pes + 2 NE) i + ...] = E (num_pes, ascending) | F lower-packed (NE) | NAC lower-packed (NE; NAC(j, k) = F(j, k) / (E_j - E_k), j > k). */
 int gple_pes_adiabatic_n(gple_ctx* ctx, int num_pes, int model, const double* x, size_t M, unsigned flags, double* out);
+
+/* ---- exact DVR dynamics (schrodinger_equation/ of the reference) ------------------------------------------------------- */
+/* The reference's exact quantum dynamics of the same models, for the non-absorbing boundaries.  num_pes = 2 or 3, models as gple_evolve_n
+ * (TSAC = 3 only at three levels); wavefunctions are num_pes n_grids (re, im) pairs with the index m n_grids + a (general.cpp:126, 137);
+ * grid x_a = x_first + dx a (main.cpp:108). */
+typedef enum gple_dvr_boundary
+{
+	GPLE_DVR_REFLECTIVE = 0, /* general.h:92; Colbert-Miller kinetic energy, general.cpp:154-175 */
+	GPLE_DVR_PERIODIC = 1    /* general.h:91 (the reference's default); general.cpp:176-198. The absorbing boundary is not provided */
+} gple_dvr_boundary;
+/* Hamiltonian_construction (general.cpp:106-200) without the absorbing term: H (dim x dim, dim = num_pes n_grids, real symmetric) holds the
+ * diabatic potential on the diagonal grid blocks and the kinetic energy on the diagonal surface blocks, every entry in the reference's
+ * operation order.  energies (n_grids x num_pes, ascending) and basis (n_grids x num_pes x num_pes, columns = adiabatic states) are the
+ * adiabatic states per grid point (adiabatic_energy general.cpp:296-309, diabatic_to_adiabatic pes.cpp:96-120) exactly as
+ * gple_pes_adiabatic_n forms them.  Each output is nullable.  n_grids >= 2, dx > 0, mass > 0. */
+int gple_dvr_hamiltonian(gple_ctx* ctx, int num_pes, int model, int boundary, double x_first, double dx, size_t n_grids, double mass,
+	unsigned flags, double* H, double* energies, double* basis);
+/* Evolution::evolve without ABC (general.cpp:205-252) at T times: psi(t) = C (exp(-i E t / hbar) o c0) with C = eigvec (dim x dim row-major,
+ * eigvec[r dim + k] = component r of eigenvector k, what numpy.linalg.eigh returns) and E = eigval (dim).  psi0_or_c0 (dim (re, im) pairs)
+ * is c0 = C^T psi0, or psi0 itself with GPLE_DVR_PSI0 (general.cpp:225).  basis (nullable, as gple_dvr_hamiltonian returns it): psi is
+ * returned in the adiabatic representation, basis^T psi per grid point (main.cpp:221).  psi: T x dim (re, im) pairs. */
+#define GPLE_DVR_PSI0 0x800u
+int gple_dvr_propagate(gple_ctx* ctx, int num_pes, size_t n_grids, const double* eigvec, const double* eigval, const double* psi0_or_c0,
+	const double* times, size_t T, const double* basis, unsigned flags, double* psi);
+/* output_phase_space_distribution (general.cpp:324-411) of T wavefunctions psi (T x num_pes n_grids (re, im) pairs, in the representation
+ * the caller wants transformed: the reference passes the adiabatic one, main.cpp:225-232) on the momentum grid p (n_p >= 2 values):
+ *   P_ij(x_a, p_b) = dx / (pi hbar) sum_k exp(2 i p_b k dx / hbar) psi_i[a - k] conj(psi_j[a + k]),
+ * |k| <= min(a, n_grids - 1 - a) (reflective) or |k| <= n_grids / 3 with indices mod n_grids (periodic).  phase (nullable): the phase.txt
+ * layout, T x num_pes^2 (i, j row-major) x n_grids x n_p (re, im) pairs.  averages (nullable, T x 3): (E, x, p) of general.cpp:393-410 from
+ * the diagonal elements, E weighted by energies (n_grids x num_pes, the adiabatic energies of gple_dvr_hamiltonian; needed with averages)
+ * and p^2 / 2 mass; two calls on the same input return the same bits.  Only the elements j <= i are summed, P_ji = conj(P_ij). */
+int gple_wigner(gple_ctx* ctx, int num_pes, int boundary, size_t n_grids, double x_first, double dx, const double* p, size_t n_p,
+	const double* psi, size_t T, const double* energies, double mass, unsigned flags, double* phase, double* averages);
 
 /* generate_markov_chain (mc.cpp:118-165) for n walkers at once on the fitted distribution |cut-off prediction| of `element`:
  * num_steps Metropolis steps with uniform displacements in [-max_displacement, max_displacement) per dimension; r (2n) holds

@@ -1,0 +1,223 @@
+"""GPU: exact DVR dynamics (gple_dvr_hamiltonian, gple_dvr_propagate, gple_wigner; csrc/gple_dvr.hip) against the numpy restatement of the
+reference's schrodinger_equation/general.cpp (tests/dvr_numpy.py), and the driver exact.run against a numpy restatement of its loop."""
+import ctypes as C
+import math
+
+import numpy as np
+import pytest
+
+from oracle import evolve_oracle_n as ON
+from tests import dvr_numpy as DN
+
+pytestmark = pytest.mark.gpu
+EPS = np.finfo(np.float64).eps
+IO_DEVICE = 0x100
+BAD_ARG = 1
+MODELS = [(2, 0), (2, 1), (2, 2), (3, 0), (3, 1), (3, 2), (3, 3)]
+dp = lambda t: C.cast(t.data_ptr(), C.POINTER(C.c_double))
+
+
+@pytest.mark.parametrize("num_pes, model", MODELS)
+def test_hamiltonian_and_states(gpu, num_pes, model):
+    for boundary in (DN.REFLECTIVE, DN.PERIODIC):
+        for n in (64, 301):
+            x_first, dx, mass = -7.5, 15.0 / (n - 1), 2000.0
+            H, E, B = gpu.dvr_hamiltonian(num_pes, model, boundary, x_first, dx, n, mass)
+            ref = DN.hamiltonian(num_pes, model, boundary, x_first, dx, n, mass)
+            assert np.array_equal(H, H.T)
+            # the potential entries carry the device's exp / tanh and the library's fma contraction of the potentials (gple_pes_n.h):
+            # a few ulps of the entry on top of the kinetic energy's 4 eps of the row
+            row = np.abs(ref).max(axis=1, keepdims=True)
+            V = np.zeros_like(ref)
+            Vd, _ = ON.diabatic(x_first + dx * np.arange(n), model, num_pes)
+            for m in range(num_pes):
+                for mm in range(num_pes):
+                    V[m * n + np.arange(n), mm * n + np.arange(n)] = Vd[:, m, mm]
+            assert (np.abs(H - ref) <= 4 * EPS * row + 16 * EPS * np.abs(V)).all(), (boundary, n, np.abs(H - ref).max())
+            # the adiabatic states: the bits of gple_pes_adiabatic_n, orthonormal, the oracle's eigenvectors in the library's sign convention
+            x = x_first + dx * np.arange(n)
+            Ep, _, _ = gpu.pes_adiabatic_n(num_pes, model, x)
+            assert np.array_equal(E, Ep)
+            assert np.abs(np.einsum("aji,ajk->aik", B, B) - np.eye(num_pes)).max() <= 1e-14
+            Eo, Co, _, _ = ON.adiabatic(x, model, num_pes)
+            assert np.abs(E - Eo).max() <= 1e-14
+            # columns up to their sign: where a coupling underflows to ~1e-26 (SAC far from the crossing) the sign of the tiny component that
+            # the convention keys on is rounding in either solver; the library's own convention holds on B
+            col = np.minimum(np.abs(B - Co).max(axis=1), np.abs(B + Co).max(axis=1))
+            assert col.max() <= 1e-10
+            for k in range(num_pes):
+                last = np.array([v[np.nonzero(v)[0][-1]] for v in B[:, :, k]])
+                assert (last > 0).all()
+
+
+@pytest.mark.parametrize("num_pes, model, boundary, n", [(2, 1, DN.PERIODIC, 150), (3, 3, DN.REFLECTIVE, 120), (2, 0, DN.REFLECTIVE, 97)])
+def test_propagation_against_expm(gpu, num_pes, model, boundary, n):
+    from scipy.linalg import expm
+
+    x_first, dx, mass = -10.0, 20.0 / (n - 1), 2000.0
+    H, E, B = gpu.dvr_hamiltonian(num_pes, model, boundary, x_first, dx, n, mass)
+    lam, U = np.linalg.eigh(H)
+    x = x_first + dx * np.arange(n)
+    g = DN.gaussian(x, -2.0, 15.0, 0.7)
+    psi0 = np.concatenate([B[:, j, 0] * g for j in range(num_pes)])
+    times = np.array([0.0, 1.0, 10.0, 100.0, 333.3, 1000.0, 2500.0])
+    psi = gpu.dvr_propagate(num_pes, n, U, lam, psi0, times)
+    nrm = np.linalg.norm(psi0)
+    for t, v in zip(times, psi):
+        assert np.linalg.norm(v - expm(-1j * H * t) @ psi0) <= 1e-10 * nrm, t
+    assert np.abs(np.linalg.norm(psi, axis=1) - nrm).max() <= 1e-12 * nrm
+    c0 = U.T @ psi0
+    e_spec = dx * np.sum(np.abs(c0) ** 2 * lam)
+    assert abs(e_spec - np.vdot(psi0, H @ psi0).real * dx) <= 1e-12 * abs(e_spec)
+    # c0 given directly, and the adiabatic representation (basis^T psi per grid point)
+    assert np.abs(gpu.dvr_propagate(num_pes, n, U, lam, c0, times, from_psi0=False) - psi).max() <= 1e-13 * nrm
+    ad = gpu.dvr_propagate(num_pes, n, U, lam, psi0, times, basis=B)
+    ref = np.einsum("ajk,tja->tka", B, psi.reshape(len(times), num_pes, n)).reshape(psi.shape)
+    assert np.abs(ad - ref).max() <= 1e-13 * nrm
+
+
+WIGNER_CASES = [(47, 47, 2, DN.REFLECTIVE), (47, 29, 3, DN.PERIODIC), (96, 131, 3, DN.REFLECTIVE), (96, 96, 2, DN.PERIODIC),
+                (301, 257, 2, DN.PERIODIC), (301, 200, 2, DN.REFLECTIVE)]
+
+
+@pytest.mark.parametrize("n, n_p, num_pes, boundary", WIGNER_CASES)
+def test_wigner_against_restatement(gpu, n, n_p, num_pes, boundary):
+    rng = np.random.default_rng(n * 7 + n_p + num_pes)
+    T, dx = 3, 0.1
+    psi = rng.normal(size=(T, num_pes * n)) + 1j * rng.normal(size=(T, num_pes * n))
+    p = np.linspace(-4.0, 7.0, n_p)
+    P, _ = gpu.wigner(num_pes, boundary, -3.0, dx, p, psi)
+    K = 2 * DN.half_range(boundary, n) + 1
+    for t in range(T):
+        ref, bound = DN.wigner(psi[t], num_pes, boundary, dx, p)
+        tol = 4 * K * EPS * (dx / math.pi) * bound[:, :, :, None]
+        err = np.abs((P[t] - ref).astype(np.clongdouble))
+        assert (err <= tol).all(), (t, (err / np.maximum(tol, 1e-300)).max())
+
+
+def _gaussian_case(num_pes=2):
+    from gaussian_process_liouville_equation_amd import exact
+
+    s = exact.setup(-4.0)  # n = 481
+    x0 = 1.5
+    psi = np.zeros(num_pes * s["n_grids"], dtype=complex)
+    psi[:s["n_grids"]] = DN.gaussian(s["x"], x0, s["p0"], s["sigma_x"])
+    return s, x0, psi
+
+
+def test_wigner_known_answer(gpu):
+    s, x0, psi = _gaussian_case()
+    n = s["n_grids"]
+    W = DN.analytic_wigner(s["x"], s["p"], x0, s["p0"], s["sigma_x"])
+    P, _ = gpu.wigner(2, DN.REFLECTIVE, s["x"][0], s["dx"], s["p"], psi)
+    assert np.abs(P[0, 0, 0] - W).max() <= 1e-10 * W.max()
+    for i, j in ((0, 1), (1, 0), (1, 1)):  # the empty surface
+        assert not P[0, i, j].any()
+    P, _ = gpu.wigner(2, DN.PERIODIC, s["x"][0], s["dx"], s["p"], psi)
+    K = DN.half_range(DN.PERIODIC, n)
+    assert np.abs(P[0, 0, 0] - W)[K:n - K].max() <= 1e-10 * W.max()  # rows whose k-range stays inside the box (tests/test_dvr_host.py)
+    assert not P[0, 1].any() and not P[0, 0, 1].any()
+
+
+def test_wigner_averages(gpu):
+    s, x0, psi = _gaussian_case()
+    n, dx, x, p, mass = s["n_grids"], s["dx"], s["x"], s["p"], s["mass"]
+    _, E, _ = gpu.dvr_hamiltonian(2, 1, DN.REFLECTIVE, x[0], dx, n, mass, want_h=False)
+    rng = np.random.default_rng(5)
+    psis = np.stack([psi, psi * np.exp(0.3j), psi + 0.1 * (rng.normal(size=psi.shape) + 1j * rng.normal(size=psi.shape))])
+    P, av = gpu.wigner(2, DN.REFLECTIVE, x[0], dx, p, psis, energies=E, mass=mass, averages=True)
+    for t in range(len(psis)):
+        ref = DN.wigner_averages(P[t], x, p, E, mass, dx)
+        assert np.abs(av[t] - ref).max() <= 1e-12 * np.abs(ref).max(), (t, av[t], ref)
+    # the Wigner <x> of the Gaussian is psi's <x>
+    x_psi = np.dot(x, np.abs(psi[:n]) ** 2) * dx
+    assert abs(av[0, 1] - x_psi) <= 1e-8 * abs(x_psi)
+
+
+def test_wigner_determinism_and_device_pointers(gpu):
+    import torch
+
+    s, _, psi = _gaussian_case(3)
+    n, dx, x, mass = s["n_grids"], s["dx"], s["x"], s["mass"]
+    _, E, _ = gpu.dvr_hamiltonian(3, 3, DN.PERIODIC, x[0], dx, n, mass, want_h=False)
+    psis = np.stack([psi, np.roll(psi, 300) * 0.5 + psi])
+    p = np.linspace(s["p"][0], s["p"][-1], 333)
+    P1, a1 = gpu.wigner(3, DN.PERIODIC, x[0], dx, p, psis, energies=E, mass=mass, averages=True)
+    P2, a2 = gpu.wigner(3, DN.PERIODIC, x[0], dx, p, psis, energies=E, mass=mass, averages=True)
+    assert np.array_equal(P1.view(np.float64), P2.view(np.float64)) and np.array_equal(a1, a2)
+    dev = torch.device("cuda", 0)
+    tp = torch.from_numpy(p).to(dev)
+    tpsi = torch.from_numpy(np.ascontiguousarray(psis).view(np.float64)).to(dev)
+    tE = torch.from_numpy(np.ascontiguousarray(E)).to(dev)
+    tP = torch.empty(P1.size * 2, dtype=torch.float64, device=dev)
+    tav = torch.empty(6, dtype=torch.float64, device=dev)
+    torch.cuda.synchronize()
+    f = gpu.lib.gple_wigner
+    st = f(gpu.ctx, 3, DN.PERIODIC, n, float(x[0]), float(dx), dp(tp), len(p), dp(tpsi), 2, dp(tE), float(mass), IO_DEVICE, dp(tP), dp(tav))
+    assert st == 0
+    gpu.lib.gple_ctx_synchronize(gpu.ctx)
+    assert np.array_equal(tP.cpu().numpy(), P1.reshape(-1).view(np.float64))
+    assert np.array_equal(tav.cpu().numpy(), a1.reshape(-1))
+    # the same through the propagation and the Hamiltonian
+    H, Eh, B = gpu.dvr_hamiltonian(2, 1, DN.PERIODIC, -5.0, 0.1, 101, mass)
+    tH = torch.empty(202 * 202, dtype=torch.float64, device=dev)
+    fh = gpu.lib.gple_dvr_hamiltonian
+    assert fh(gpu.ctx, 2, 1, DN.PERIODIC, -5.0, 0.1, 101, mass, IO_DEVICE, dp(tH), None, None) == 0
+    gpu.lib.gple_ctx_synchronize(gpu.ctx)
+    assert np.array_equal(tH.cpu().numpy(), H.reshape(-1))
+    lam, U = np.linalg.eigh(H)
+    psi0 = np.concatenate([np.exp(-(np.arange(101) - 50.0) ** 2 / 50 + 0.5j * np.arange(101)), np.zeros(101)])
+    times = np.array([0.0, 50.0, 500.0])
+    ref = gpu.dvr_propagate(2, 101, U, lam, psi0, times)
+    assert np.array_equal(ref.view(np.float64), gpu.dvr_propagate(2, 101, U, lam, psi0, times).view(np.float64))
+    tU, tl, tv, tt = (torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (U, lam, psi0.view(np.float64), times))
+    tout = torch.empty(ref.size * 2, dtype=torch.float64, device=dev)
+    torch.cuda.synchronize()
+    fp = gpu.lib.gple_dvr_propagate
+    assert fp(gpu.ctx, 2, 101, dp(tU), dp(tl), dp(tv), dp(tt), 3, None, IO_DEVICE | 0x800, dp(tout)) == 0
+    gpu.lib.gple_ctx_synchronize(gpu.ctx)
+    assert np.array_equal(tout.cpu().numpy(), ref.reshape(-1).view(np.float64))
+
+
+def test_invalid_arguments(gpu):
+    fh, fp, fw = gpu.lib.gple_dvr_hamiltonian, gpu.lib.gple_dvr_propagate, gpu.lib.gple_wigner
+    gpu.dvr_hamiltonian(2, 1, 0, -5.0, 0.1, 11, 2000.0)  # declares the argument types
+    gpu.dvr_propagate(2, 2, np.eye(4), np.zeros(4), np.zeros(4), [0.0])
+    gpu.wigner(2, 0, -5.0, 0.1, np.linspace(0, 1, 3), np.zeros((1, 8)))
+    H = np.empty(64 * 64)
+    ptr = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+    for num_pes, model, boundary, n in ((2, 1, 2, 16), (1, 1, 0, 16), (4, 1, 0, 16), (2, 3, 0, 16), (2, 1, -1, 16), (2, 1, 0, 1), (3, 4, 1, 16)):
+        assert fh(gpu.ctx, num_pes, model, boundary, -1.0, 0.1, n, 2000.0, 0, ptr(H), None, None) == BAD_ARG, (num_pes, model, boundary, n)
+    assert fh(gpu.ctx, 2, 1, 0, -1.0, 0.1, 16, 0.0, 0, ptr(H), None, None) == BAD_ARG  # mass
+    assert fh(gpu.ctx, 2, 1, 0, -1.0, 0.0, 16, 2000.0, 0, ptr(H), None, None) == BAD_ARG  # dx
+    U, v, t, out = np.eye(8), np.zeros(16), np.zeros(1), np.zeros(16)
+    for num_pes, n in ((1, 8), (4, 2), (2, 1)):
+        assert fp(gpu.ctx, num_pes, n, ptr(U), ptr(v), ptr(v), ptr(t), 1, None, 0, ptr(out)) == BAD_ARG, (num_pes, n)
+    p, psi, Ph, av = np.linspace(0, 1, 4), np.zeros(32), np.zeros(2 * 4 * 8 * 4), np.zeros(3)
+    for num_pes, boundary, n in ((2, 2, 8), (1, 0, 8), (4, 0, 4), (2, 0, 1)):
+        assert fw(gpu.ctx, num_pes, boundary, n, -1.0, 0.1, ptr(p), 4, ptr(psi), 1, None, 0.0, 0, ptr(Ph), None) == BAD_ARG, (num_pes, boundary, n)
+    assert fw(gpu.ctx, 2, 0, 8, -1.0, 0.1, ptr(p), 1, ptr(psi), 1, None, 0.0, 0, ptr(Ph), None) == BAD_ARG  # n_p < 2
+    assert fw(gpu.ctx, 2, 0, 8, -1.0, 0.1, ptr(p), 4, ptr(psi), 1, None, 2000.0, 0, ptr(Ph), ptr(av)) == BAD_ARG  # averages need energies
+
+
+def test_exact_run_against_restated_loop(gpu, tmp_path):
+    from gaussian_process_liouville_equation_amd import exact
+
+    res = exact.run(gpu, model=exact.DAC, num_pes=2, boundary=exact.PERIODIC, ln_energy=-1.0, dx=0.125, max_outputs=10, out_dir=str(tmp_path),
+                    write_phase="text")
+    s = res["setup"]
+    assert s["n_grids"] == 241
+    _, E, B = gpu.dvr_hamiltonian(2, exact.DAC, exact.PERIODIC, s["x"][0], s["dx"], s["n_grids"], s["mass"], want_h=False)
+    ref = DN.run_loop(2, exact.DAC, exact.PERIODIC, s, 10, (E, B))
+    assert len(res["records"]) == len(ref) and res["stop_time"] == ref[-1]["t"]
+    for a, b in zip(res["records"], ref):
+        assert a["t"] == b["t"]
+        assert np.abs(a["populations"] - b["populations"]).max() <= 1e-9
+        for k in ("E", "x", "p"):
+            assert abs(a[k] - b[k]) <= 1e-9 * max(1.0, abs(b[k])), (k, a[k], b[k])
+        assert (np.abs(a["phase_averages"] - b["phase_averages"]) <= 1e-9 * np.maximum(1.0, np.abs(b["phase_averages"]))).all()
+    # the six files
+    for name, lines in (("x.txt", 241), ("p.txt", 241), ("t.txt", len(ref)), ("psi.txt", len(ref)), ("averages.txt", len(ref))):
+        assert len(open(tmp_path / name).read().splitlines()) == lines, name
+    assert len(open(tmp_path / "phase.txt").read().split("\n")) == 5 * len(ref) + 1
+    assert len(res["final_line"].split()) == 3
