@@ -8,7 +8,7 @@
 //     contraction (M N^2 flops) whose result is a sum of squares (no cancellation inside the quadratic form);
 //   * kstar_gen_kernel writes one bounded chunk of K* (<= PREDICT_SCRATCH_BYTES, column-major chunk_rows x n) to a
 //     rolling HBM scratch and reduces the mean on the way (pure VALU: one exp per element, once);
-//   * rownorm_kernel streams that chunk and T through LDS into v_mfma_f64_16x16x4_f64 and keeps only the squared
+//   * rownormp_kernel streams that chunk and T through LDS into v_mfma_f64_16x16x4_f64 and keeps only the squared
 //     row norms.
 // Why two kernels (measured on MI355X, see profiles/ and probes/): fp64 MFMA and fp64 VALU share one pipe, every
 // VALU instruction of a co-resident wave adds ~4.4 cycles to the MFMA stream, and a fused kernel has to re-generate
@@ -16,18 +16,13 @@
 // Fused variants (lock-step, interleaved, wave-specialised ping-pong) all stalled at 52 TFLOP/s at N=4096; the plain
 // lock-step MFMA loop with LDS operand reads sustains 72.6 TFLOP/s on its own.
 //
-// The contraction kernels, oldest first — all on the same 128 x 256 tile, K advancing 16 per barrier, the same virtual-group sums, the newer ones
-// bit-identical to their predecessor with the same blocking: rownorm_kernel (round 1; GPLE_ROWNORM_VARIANT=0), rownorm2_kernel (round 2: 4 x 4 / 2 x 8
-// fragments per wave, slabs by LDS-DMA; GPLE_ROWNORM_PIPE=0), rownormp_kernel (round 4, the default: the k-steps of a unit as one pipeline pinned
-// around the barrier), rownorm3_kernel (n <= 512 with few row blocks) and predict_fused256_kernel (round 4: the whole predict of a real fit with
-// N <= 256 in one launch, K* generated inside).
-//
-// rownorm_kernel: one workgroup = 8 waves owns 128 test rows and loops over 256-wide N-tiles of T; K advances 16 per
-// step through a double-buffered LDS stage (global -> registers -> LDS, loads issued before the MFMAs of the current
-// step).  Every wave owns 16 rows x all 256 columns (16 accumulator tiles), so the all-zero blocks of T (k > n) are
-// skipped by all waves alike; the skipping is expressed as consecutive loops with a compile-time block range because
-// any branch that merges around the accumulators makes hipcc spill hundreds of VGPRs.  The result rows sit on n and
-// the result columns (lane & 15) on the test row m, so the squared row sums stay lane-local.
+// The contraction kernels — all on the same 128 x 256 tile, K advancing 16 per barrier, the same virtual-group sums, bit-identical to each other
+// with the same blocking: rownorm2_kernel (round 2: 4 x 4 / 2 x 8 fragments per wave, slabs by LDS-DMA; gple_debug_predict_knobs pipe = 0),
+// rownormp_kernel (round 4, the default: the k-steps of a unit as one pipeline pinned around the barrier), rownorm3_kernel (n <= 512 with few
+// row blocks) and predict_fused256_kernel (round 4: the whole predict of a real fit with N <= 256 in one launch, K* generated inside).
+// A workgroup = 8 waves owns 128 test rows and loops over 256-wide N-tiles of T.  The all-zero blocks of T (k > n) are skipped with
+// compile-time block ranges because any branch that merges around the accumulators makes hipcc spill hundreds of VGPRs.  The result rows
+// sit on n and the result columns (lane & 15) on the test row m, so the squared row sums stay lane-local.
 //
 // "Typed" rows/columns implement the complex GP as a real GP on [Re; Im] (see gple_kernels.h, SEParamSet).
 #include <algorithm>
@@ -73,7 +68,6 @@ namespace gple
 			const int r = blockIdx.x * 128 + threadIdx.x; // row inside the chunk
 			int gm = row0 + r;                             // row of the typed test set
 			int type_m = (row0 + blockIdx.x * 128) >= a.m_split; // MODE 0, 1: uniform per block (m_split multiple of 128)
-			// MODE 3: K* of the rows [row0, row0 + rows) and nothing else (a generation beside the fit: its weights do not exist yet)
 			if constexpr (MODE == 2)
 			{
 				const int nl = *n_live;
@@ -114,7 +108,7 @@ namespace gple
 					const double g = exp_nonpos(__dmul_rn(-0.5, fma(d0, d0, __dmul_rn(d1, d1))));
 					const double delta = (xm == xk && pm == pkv) ? n2 : 0.0; // delta_kernel: exact equality, kernel.cpp:26
 					const double val = valid ? __dmul_rn(amp, g + delta) : 0.0;
-					if constexpr (MODE != 2 && MODE != 3) mu = fma(val, a.v[k], mu);
+					if constexpr (MODE != 2) mu = fma(val, a.v[k], mu);
 					if constexpr (MODE == 1) nrm = fma(val, val, nrm);
 					if constexpr (DERIV == 2)
 					{
@@ -145,19 +139,11 @@ namespace gple
 				}
 				out += 4L * rows;
 			}
-			if constexpr (MODE != 2 && MODE != 3) mu_part[static_cast<long>(blockIdx.y) * a.m_rows + gm] = mu;
+			if constexpr (MODE != 2) mu_part[static_cast<long>(blockIdx.y) * a.m_rows + gm] = mu;
 			if constexpr (MODE == 1) nrm_part[static_cast<long>(blockIdx.y) * a.m_rows + gm] = nrm;
 			if constexpr (DERIV != 0)
 #pragma unroll
 				for (int ip = 0; ip < NACC; ++ip) mu_part[(static_cast<long>(ip + 1) * ksplit + blockIdx.y) * a.m_rows + gm] = dacc[ip];
-		}
-
-		// the k-steps that cross the diagonal 256-block of an N-tile: step D starts at k = n0 + KB D, where the column blocks
-		// j < KB D / 16 are identically zero
-		template <int KB, class Step, int... D>
-		__device__ __forceinline__ void diag_steps(Step& kstep, int nd, std::integer_sequence<int, D...>)
-		{
-			(kstep(std::integral_constant<int, (D * KB) / 16>{}, nd + D), ...);
 		}
 
 		// Rows whose K* is so small that the contraction cannot move the variance: q = k*^T K^-1 k* <= |k*|^2 / lambda_min(K) and
@@ -178,13 +164,6 @@ namespace gple
 			const int* n_live; // device: number of live rows (the compacted list's length)
 			int row0;          // offset of this chunk in the compacted list
 			int nblocks, G;    // row blocks of the chunk (upper bound: the live ones are the first ceil((n_live - row0) / 128)), tile groups
-			// A contraction in two launches (rownormp_kernel only; launch_predict_overlapped): the N-tiles [jt_lo, jt_hi) of every unit (jt_hi = 0: all of them).
-			// A virtual group's sum runs over tiles of both launches, lane by lane, before anything is reduced — so the first launch SAVES the per-lane
-			// partial sums of every group (state_mode 1: [row block][VG][wave][fragment][lane], nothing is written to q) and the second STARTS from them
-			// (state_mode 2; a group has saved sums iff it owns a tile below jt_lo, i.e. iff vg < jt_lo): the bits of the unsplit launch.
-			int jt_lo = 0, jt_hi = 0;
-			double* state = nullptr;
-			int state_mode = 0;
 		};
 		// the unit this workgroup works on next: false when there is none (queue mode: the counter ran past the last unit;
 		// static mode: the one unit of the workgroup is done)
@@ -294,133 +273,10 @@ namespace gple
 			q[row] = v;
 		}
 
-		// q[row] = sum_n ( sum_{k <= n} K*(row, k) T(n, k) )^2 for one chunk of rows.
-		// WAVES waves x 16 rows per workgroup, K advances KB per barrier.  <8, 16> (the one launched): one workgroup fills a CU
-		// (2 waves per SIMD).  GPLE_ROWNORM_VARIANT selects between this kernel and rownorm2_kernel for A/B runs (launch_predict_q).
-		template <int WAVES, int KB, bool QUEUE>
-		__global__ void __launch_bounds__(WAVES * 64, 8 / WAVES) rownorm_kernel(const double* __restrict__ Ks, int rows, const double* __restrict__ T,
-			long ldt, int n_total, double* __restrict__ q, long qstride, const Prune pr)
-		{
-			constexpr int TM = WAVES * 16, NT = WAVES * 64;
-			constexpr int ASr = TM + 16;
-			constexpr int ASL = KB * ASr, BSL = KB * BS;
-			constexpr int NA = TM * KB / 2 / NT, NBv = BN * KB / 2 / NT; // double2 per thread and slab
-			static_assert(NA >= 1 && NBv >= 1, "tile too small for the thread count");
-			__shared__ __attribute__((aligned(16))) double lds[2 * ASL + 2 * BSL];
-			double* const As = lds;
-			double* const Bs = lds + 2 * ASL;
-			const int t = threadIdx.x, lane = t & 63, w = __builtin_amdgcn_readfirstlane(t >> 6);
-			const int fk = lane >> 4, fr = lane & 15;
-			int m0 = 0; // row block of the current unit (the loaders below read it)
-			const int ntiles = n_total / BN;
-			double rsq = 0.0;
-
-			d2 areg[NA], breg[NBv];
-			auto load_ab = [&](int n0, int k0) {
-				const double* __restrict__ abase = Ks + m0 + static_cast<long>(k0) * rows;
-#pragma unroll
-				for (int qq = 0; qq < NA; ++qq)
-				{
-					const int i = t + NT * qq;
-					const int r2 = (i % (TM / 2)) * 2, k = i / (TM / 2);
-					areg[qq] = *reinterpret_cast<const d2*>(abase + r2 + static_cast<long>(k) * rows);
-				}
-				const double* __restrict__ bbase = T + n0 + static_cast<long>(k0) * ldt;
-#pragma unroll
-				for (int qq = 0; qq < NBv; ++qq)
-				{
-					const int i = t + NT * qq;
-					const int r2 = (i & 127) * 2, k = i >> 7;
-					breg[qq] = *reinterpret_cast<const d2*>(bbase + r2 + static_cast<long>(k) * ldt);
-				}
-			};
-			auto store_ab = [&](int buf) {
-				double* __restrict__ sa = As + buf * ASL;
-#pragma unroll
-				for (int qq = 0; qq < NA; ++qq)
-				{
-					const int i = t + NT * qq;
-					const int r2 = (i % (TM / 2)) * 2, k = i / (TM / 2);
-					*reinterpret_cast<d2*>(sa + k * ASr + r2) = areg[qq];
-				}
-				double* __restrict__ sb = Bs + buf * BSL;
-#pragma unroll
-				for (int qq = 0; qq < NBv; ++qq)
-				{
-					const int i = t + NT * qq;
-					const int r2 = (i & 127) * 2, k = i >> 7;
-					*reinterpret_cast<d2*>(sb + k * BS + r2) = breg[qq];
-				}
-			};
-
-			// gridDim.y > 1 splits the N-tiles of one row block over several workgroups (few row blocks: fill the chip anyway).
-			// N-tile jt costs jt + 1 units, so the tiles are dealt out in snake order: group g of G takes the tiles whose
-			// position in a period of 2 G is g or 2 G - 1 - g.
-			int mblock, g, G;
-			for (int it = 0; next_unit<QUEUE>(pr, it, mblock, g, G); ++it)
-			{
-			m0 = mblock * TM;
-			for (int vg = 0; vg < VG; ++vg)
-			{
-			if (snake(vg, G) != g) continue; // uniform
-			rsq = 0.0;
-			for (int jt = 0; jt < ntiles; ++jt)
-			{
-				if (snake(jt, VG) != vg) continue; // uniform; no accumulator is live here
-				const int n0 = jt * BN;
-				const int nk = (n0 + BN) / KB; // T(n,k) = 0 for k > n: k-slabs beyond the N-tile's last column are skipped
-				d4 acc[16];
-#pragma unroll
-				for (int j = 0; j < 16; ++j) acc[j] = (d4){0.0, 0.0, 0.0, 0.0};
-
-				__syncthreads(); // the previous tile's last MFMAs have finished reading the stage
-				load_ab(n0, 0);
-				store_ab(0);
-				__syncthreads();
-
-				// one k-step: prefetch slab s + 1, MFMAs of slab s against the column blocks j >= JMIN, commit the prefetch
-				auto kstep = [&](auto jmin_tag, int s) {
-					constexpr int JMIN = decltype(jmin_tag)::value;
-					if (s + 1 < nk) load_ab(n0, (s + 1) * KB);
-					const double* __restrict__ pa = As + (s & 1) * ASL + w * 16 + fr;
-					const double* __restrict__ pb = Bs + (s & 1) * BSL + fr;
-#pragma unroll
-					for (int kk = 0; kk < KB; kk += 4)
-					{
-						const double af = pa[(kk + fk) * ASr];
-						double bf[16];
-#pragma unroll
-						for (int j = JMIN; j < 16; ++j) bf[j] = pb[(kk + fk) * BS + j * 16];
-#pragma unroll
-						for (int j = JMIN; j < 16; ++j) acc[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(bf[j], af, acc[j], 0, 0, 0);
-					}
-					if (s + 1 < nk) store_ab((s + 1) & 1);
-					__syncthreads();
-				};
-				// k-slabs below the diagonal N-tile see every column block; inside the diagonal 256-block the column blocks left
-				// of the current k (T(n,k) = 0 for k > n) drop out one at a time: 16 columns per 16 k
-				const int nd = n0 / KB;
-				int s = 0;
-				for (; s < nd; ++s) kstep(std::integral_constant<int, 0>{}, s);
-				diag_steps<KB>(kstep, nd, std::make_integer_sequence<int, BN / KB>{});
-
-				// result element [n = 16 j + fk + 4 r][m = 16 w + fr]: the row index m is lane-local
-#pragma unroll
-				for (int j = 0; j < 16; ++j)
-#pragma unroll
-					for (int r = 0; r < 4; ++r) rsq = fma(acc[j][r], acc[j][r], rsq);
-			}
-			rsq += __shfl_xor(rsq, 16);
-			rsq += __shfl_xor(rsq, 32);
-			if (lane < 16) q[static_cast<long>(vg) * qstride + m0 + w * 16 + lane] = rsq; // partial sums of virtual group vg
-			}
-			}
-		}
-
-		// ---- register-blocked variant ------------------------------------------------------------------------------------
-		// rownorm_kernel gives every wave 16 rows x all 256 columns: 1 + 16 operand fragments from LDS per 16 MFMAs.  The bare
+		// ---- q[row] = sum_n ( sum_{k <= n} K*(row, k) T(n, k) )^2 for one chunk of rows, register-blocked -------------------------
+		// A wave that owns 16 rows x all 256 columns (round 1) reads 1 + 16 operand fragments from LDS per 16 MFMAs.  The bare
 		// MFMA loop with that operand pattern sustains 72.6 TFLOP/s against 78.4 from registers (probes/mfma_f64_sustained):
-		// the LDS operand reads cost ~8 %.  Here a wave owns AF x BF fragments (AF * BF = 16 accumulators as before): AF + BF
+		// the LDS operand reads cost ~8 %.  Here a wave owns AF x BF fragments (AF * BF = 16 accumulators): AF + BF
 		// reads per 16 MFMAs — 8 for 4 x 4, 10 for 2 x 8.  The 8 waves form a (128 / (16 AF)) x WN grid over the same 128 x 256
 		// workgroup tile; a wave's BF column blocks are interleaved (block wn + WN t), so that inside the diagonal 256-block,
 		// where the column blocks left of k drop out one per k-step, all waves keep the same number of live blocks (+-1).
@@ -603,7 +459,7 @@ namespace gple
 		constexpr int TL_MAX = 256; // N-tiles of a factor (n <= 65536)
 		template <int AF, int BF, int WNI>
 		__device__ __forceinline__ void rownormp_unit(const double* __restrict__ Ks, int rows, const double* __restrict__ T, long ldt, double* lds,
-			const int* tl, int ntl, double* __restrict__ q, long qstride, int m0, int wm, double* __restrict__ su, int mode, int jlo)
+			const int* tl, int ntl, double* __restrict__ q, long qstride, int m0, int wm)
 		{
 			constexpr int KB = 16, WN = 16 / BF, ASr = BM + 16;
 			constexpr int ASL = KB * ASr, BSL = KB * BS;
@@ -669,14 +525,9 @@ namespace gple
 				for (int j = 0; j < BF; ++j) bf[j] = pb[(kk + fk) * BS + j * (16 * WN)];
 			};
 			read_ops(0, 0, cA, cB);
-			// su: this unit's saved per-lane sums (Prune::state), entry (vg, wave, fragment, lane)
-			auto su_at = [&](int vg, int i) { return su + ((static_cast<long>(vg) * 8 + w) * AF + i) * 64 + lane; };
 			double rsq[AF];
-			{
-				const int vg0 = tile_vg(0);
 #pragma unroll
-				for (int i = 0; i < AF; ++i) rsq[i] = (mode == 2 && vg0 < jlo) ? *su_at(vg0, i) : 0.0;
-			}
+			for (int i = 0; i < AF; ++i) rsq[i] = 0.0;
 			for (int ti = 0; ti < ntl; ++ti)
 			{
 				const int n0 = tile_n0(ti) * BN, vg = tile_vg(ti);
@@ -770,33 +621,24 @@ namespace gple
 				// the last tile of a virtual group: its plane of partial sums (the WN column groups meet in LDS, beside the stage)
 				if (ti + 1 == ntl || tile_vg(ti + 1) != vg)
 				{
-					const int vgn = ti + 1 < ntl ? tile_vg(ti + 1) : VG; // the next group of this unit
-					if (mode == 1) // the early tiles: the group's sums wait, lane by lane, for its late tiles
+#pragma unroll
+					for (int i = 0; i < AF; ++i)
 					{
-#pragma unroll
-						for (int i = 0; i < AF; ++i) *su_at(vg, i) = rsq[i], rsq[i] = 0.0;
+						double v = rsq[i];
+						v += __shfl_xor(v, 16);
+						v += __shfl_xor(v, 32);
+						if (lane < 16) red[WNI * BM + wm * (16 * AF) + 16 * i + lane] = v;
+						rsq[i] = 0.0;
 					}
-					else
+					__syncthreads();
+					if (threadIdx.x < BM)
 					{
+						double v = 0.0;
 #pragma unroll
-						for (int i = 0; i < AF; ++i)
-						{
-							double v = rsq[i];
-							v += __shfl_xor(v, 16);
-							v += __shfl_xor(v, 32);
-							if (lane < 16) red[WNI * BM + wm * (16 * AF) + 16 * i + lane] = v;
-							rsq[i] = (mode == 2 && vgn < jlo) ? *su_at(vgn, i) : 0.0;
-						}
-						__syncthreads();
-						if (threadIdx.x < BM)
-						{
-							double v = 0.0;
-#pragma unroll
-							for (int c = 0; c < WN; ++c) v += red[c * BM + threadIdx.x];
-							q[static_cast<long>(vg) * qstride + m0 + threadIdx.x] = v;
-						}
-						__syncthreads();
+						for (int c = 0; c < WN; ++c) v += red[c * BM + threadIdx.x];
+						q[static_cast<long>(vg) * qstride + m0 + threadIdx.x] = v;
 					}
+					__syncthreads();
 				}
 			}
 			asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the two requests past the end
@@ -817,7 +659,6 @@ namespace gple
 			const int simd = w & 3, half = w >> 2;
 			const int wm = WN == 4 ? half : simd, wn = WN == 4 ? (half ? 3 - simd : simd) : (half ^ (simd & 1));
 			const int ntiles = n_total / BN;
-			const int jlo = pr.jt_lo, jhi = pr.jt_hi > 0 ? pr.jt_hi : ntiles; // the N-tiles of this launch
 			int mblock, g, G;
 			for (int it = 0; next_unit<QUEUE>(pr, it, mblock, g, G); ++it)
 			{
@@ -830,59 +671,29 @@ namespace gple
 					for (int vg = 0; vg < VG; ++vg)
 					{
 						if (snake(vg, G) != g) continue;
-						for (int jt = jlo; jt < jhi; ++jt)
+						for (int jt = 0; jt < ntiles; ++jt)
 							if (snake(jt, VG) == vg) tl[c++] = jt | (vg << 16);
 					}
 					tl[c] = -1, tl[c + 1] = -1;
 					s_ntl = c;
 				}
-				// a virtual group without a tile in this launch still owns its plane of the partial sums: zero (n < 2048: it has no tile at all), or —
-				// the late launch of a split contraction — its saved sums, reduced here.  (The early launch writes no plane.)
-				double* const su = pr.state ? pr.state + static_cast<long>(mblock) * (VG * 8 * AF * 64) : nullptr;
-				for (int vg = 0; vg < VG; ++vg)
-				{
-					if (snake(vg, G) != g) continue; // uniform
-					bool has = false;
-					for (int jt = jlo; jt < jhi; ++jt) has = has || snake(jt, VG) == vg;
-					if (has || pr.state_mode == 1) continue;
-					if (pr.state_mode == 2 && vg < jlo)
-					{
-						double* const red = lds + 2 * KB * ASr + 2 * KB * BS;
-						const int lane = threadIdx.x & 63;
-#pragma unroll
-						for (int i = 0; i < AF; ++i)
-						{
-							double v = su[((static_cast<long>(vg) * 8 + w) * AF + i) * 64 + lane];
-							v += __shfl_xor(v, 16);
-							v += __shfl_xor(v, 32);
-							if (lane < 16) red[wn * BM + wm * (16 * AF) + 16 * i + lane] = v;
-						}
-						__syncthreads();
-						if (threadIdx.x < BM)
-						{
-							double v = 0.0;
-#pragma unroll
-							for (int c = 0; c < WN; ++c) v += red[c * BM + threadIdx.x];
-							q[static_cast<long>(vg) * qstride + m0 + threadIdx.x] = v;
-						}
-						__syncthreads();
-					}
-					else if (threadIdx.x < BM) q[static_cast<long>(vg) * qstride + m0 + threadIdx.x] = 0.0;
-				}
+				// a virtual group without a tile (n < 2048) still owns its plane of the partial sums
+				for (int vg = ntiles; vg < VG; ++vg)
+					if (snake(vg, G) == g && threadIdx.x < BM) q[static_cast<long>(vg) * qstride + m0 + threadIdx.x] = 0.0;
 				__syncthreads();
 				const int ntl = __builtin_amdgcn_readfirstlane(s_ntl);
 				if (ntl == 0) continue; // uniform
 				if constexpr (WN == 4)
 				{
-					if (wn == 0) rownormp_unit<AF, BF, 0>(Ks, rows, T, ldt, lds, tl, ntl, q, qstride, m0, wm, su, pr.state_mode, jlo);
-					else if (wn == 1) rownormp_unit<AF, BF, 1>(Ks, rows, T, ldt, lds, tl, ntl, q, qstride, m0, wm, su, pr.state_mode, jlo);
-					else if (wn == 2) rownormp_unit<AF, BF, 2>(Ks, rows, T, ldt, lds, tl, ntl, q, qstride, m0, wm, su, pr.state_mode, jlo);
-					else rownormp_unit<AF, BF, 3>(Ks, rows, T, ldt, lds, tl, ntl, q, qstride, m0, wm, su, pr.state_mode, jlo);
+					if (wn == 0) rownormp_unit<AF, BF, 0>(Ks, rows, T, ldt, lds, tl, ntl, q, qstride, m0, wm);
+					else if (wn == 1) rownormp_unit<AF, BF, 1>(Ks, rows, T, ldt, lds, tl, ntl, q, qstride, m0, wm);
+					else if (wn == 2) rownormp_unit<AF, BF, 2>(Ks, rows, T, ldt, lds, tl, ntl, q, qstride, m0, wm);
+					else rownormp_unit<AF, BF, 3>(Ks, rows, T, ldt, lds, tl, ntl, q, qstride, m0, wm);
 				}
 				else
 				{
-					if (wn == 0) rownormp_unit<AF, BF, 0>(Ks, rows, T, ldt, lds, tl, ntl, q, qstride, m0, wm, su, pr.state_mode, jlo);
-					else rownormp_unit<AF, BF, 1>(Ks, rows, T, ldt, lds, tl, ntl, q, qstride, m0, wm, su, pr.state_mode, jlo);
+					if (wn == 0) rownormp_unit<AF, BF, 0>(Ks, rows, T, ldt, lds, tl, ntl, q, qstride, m0, wm);
+					else rownormp_unit<AF, BF, 1>(Ks, rows, T, ldt, lds, tl, ntl, q, qstride, m0, wm);
 				}
 			}
 		}
@@ -1328,8 +1139,8 @@ namespace gple
 			if (threadIdx.x == 0) q[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 		}
 
-		// Few test rows (the extra-point sets of the objective, opt.cpp:441-482; single-point lookups): rownorm_kernel
-		// gives every 128 rows to one workgroup that walks its share of T, at best 1/8 of it (rownorm_split) — with a
+		// Few test rows (the extra-point sets of the objective, opt.cpp:441-482; single-point lookups): the streaming kernels
+		// give every 128 rows to one workgroup that walks its share of T, at best 1/8 of it (rownorm_split) — with a
 		// handful of row blocks that still leaves most CUs idle.  There the contraction is spread over (n/64) x (rows/64)
 		// tiles instead: Z = T K*^T by the triangular-K GEMM, then column sums of squares.  Measured crossover
 		// (probes/predict_path_crossover.py): about 4096 rows at N = 1024, 2048 rows at N = 4096.
@@ -1342,11 +1153,6 @@ namespace gple
 		int rownorm_split(int m_rows, int n_total)
 		{
 			const long blocks = m_rows / BM, ntiles = n_total / BN;
-			static const int forced = [] {
-				const char* e = getenv("GPLE_ROWNORM_SPLIT"); // A/B: groups per row block whatever the model says (must leave every group a snake pair)
-				return e ? atoi(e) : 0;
-			}();
-			if (forced > 0 && (forced == 1 || 4 * forced <= 2 * ntiles) && forced <= ROWNORM_SPLIT_MAX) return forced;
 			int best = 1;
 			double best_cost = 1e300;
 			for (int g = 1; g <= ROWNORM_SPLIT_MAX; g *= 2)
@@ -1428,181 +1234,22 @@ namespace gple
 		return hipGetLastError();
 	}
 
-	// ---- part of a predict beside the fit it follows ------------------------------------------------------------------------------------------
-	// The contraction needs T, the fit's last product but for its first rows: T(0 .. early_rows, .) is final at the first fork of the factorisation
-	// (chol_inverse_factor), a third of the way into a fit at n = 4096, and the fit hardly uses the chip from there on (a latency-bound spine, GEMMs
-	// on a side stream).  Here, on a stream of the context's own: K* of the rows (store only: the mean needs v, the fit's LAST product) as soon as
-	// the points are there, then — behind the fork's event — rownormp_kernel over the N-tiles below early_rows as a work queue of FEWER workgroups
-	// than CUs (a contraction workgroup shares its CU with nothing: the CUs it leaves out are the fit's), saving every virtual group's per-lane sums.
-	// On the main stream, behind the fit: the means (the generation pass without the store), then the late tiles on all CUs, starting from the saved
-	// sums: bit for bit the unsplit contraction (Prune::state).  Buffers of its own (the pooled scratch is ordered by the main stream).
-	// GPLE_PREDICT_OVERLAP=1 switches it on; GPLE_PREDICT_OVERLAP_CUS = CUs left to the fit (64).  DEFAULT OFF, because it does not pay: measured on the
-	// per-rank proxy (probes/overlap_sweep.sh, N = 4096, an eighth of the 512 x 512 grid) the step is 9.41 ms in turn and 9.46 ... 17 ms overlapped — the
-	// one-launch factorisation slows by 0.3 - 1.0 ms beside ANY early work (its GEMMs and tile tasks want the CUs the early part holds), which is
-	// more than the early part saves (profiles/r04_notes.md).  Kept as a tested, bit-exact experiment for a fit that tolerates company.
-	namespace
-	{
-		__global__ void set_int2_kernel(int* p, int a, int b) { p[0] = a, p[1] = b; }
-		struct OverlapBuffers
-		{
-			double *Ks, *state, *qpart, *mu_part, *nrm_part, *xs;
-			int* counters; // [0] n_live (= rows: every row is live), [1] the work queue's counter
-			size_t bytes;
-		};
-		OverlapBuffers overlap_layout(char* base, const PredictArgs& a, size_t xs_doubles)
-		{
-			OverlapBuffers b{};
-			const size_t ksplit = gen_ksplit(a.m_rows), nblk = a.m_rows / BM;
-			size_t off = 0;
-			auto take = [&](size_t doubles) {
-				double* p = base ? reinterpret_cast<double*>(base + off) : nullptr;
-				off += (doubles * sizeof(double) + 255) / 256 * 256;
-				return p;
-			};
-			b.Ks = take(static_cast<size_t>(a.m_rows) * a.n_total);
-			b.state = take(nblk * (VG * 8 * 4 * 64));
-			b.qpart = take(static_cast<size_t>(VG) * a.m_rows);
-			b.mu_part = take(ksplit * a.m_rows);
-			b.nrm_part = take(ksplit * a.m_rows);
-			b.xs = take(xs_doubles);
-			b.counters = reinterpret_cast<int*>(take(32));
-			b.bytes = off;
-			return b;
-		}
-	} // namespace
-	bool predict_overlap_enabled()
-	{
-		static const bool on = [] {
-			const char* e = getenv("GPLE_PREDICT_OVERLAP");
-			return e != nullptr && atoi(e) != 0;
-		}();
-		return on;
-	}
-	// can this predict start beside the fit whose first early_rows rows of T are final early?  (one chunk, the full contraction on rownormp_kernel<4,4>,
-	// no derivative pass, at least two N-tiles on either side of the split)
-	bool predict_overlap_applicable(const Ctx* ctx, const PredictArgs& a, int early_rows)
-	{
-		if (!predict_overlap_enabled() || early_rows < 2 * BN || a.dv || a.mean_only || a.cut_thr > 0.0 || a.prune_thr > 0.0) return false;
-		if (a.m_rows % BM || a.n_total % BN || a.n_total / BN < 8 || a.n_total / BN > TL_MAX || early_rows / BN > a.n_total / BN - 2) return false;
-		if (static_cast<size_t>(a.m_rows) * a.n_total * sizeof(double) > PREDICT_SCRATCH_BYTES) return false; // one chunk
-		if (ctx->rownorm_pipe == 0) return false;
-		return !small_m(a) && a.m_rows / BM >= 16;
-	}
-	// the stream, events and buffers of the early work (sized for `a` and xs_doubles of test-point storage); *xs: where a caller may put the points
-	hipError_t predict_overlap_prepare(Ctx* ctx, const PredictArgs& a, size_t xs_doubles, double** xs)
-	{
-		hipError_t e;
-		if (!ctx->early_stream)
-		{
-			if ((e = hipStreamCreateWithFlags(&ctx->early_stream, hipStreamNonBlocking)) != hipSuccess) return e;
-			for (hipEvent_t* ev : {&ctx->early_points, &ctx->early_done, &ctx->early_free})
-				if ((e = hipEventCreateWithFlags(ev, hipEventDisableTiming)) != hipSuccess) return e;
-		}
-		const OverlapBuffers need = overlap_layout(nullptr, a, xs_doubles);
-		if (need.bytes > ctx->early_bytes)
-		{
-			if ((e = hipDeviceSynchronize()) != hipSuccess) return e; // (rare: the buffers only grow)
-			if (ctx->early_buf) (void)hipFree(ctx->early_buf);
-			ctx->early_buf = nullptr, ctx->early_bytes = 0, ctx->early_free_pending = false;
-			if ((e = hipMalloc(&ctx->early_buf, need.bytes)) != hipSuccess) return e;
-			ctx->early_bytes = need.bytes;
-		}
-		// the early stream may touch the buffers once the previous predict's main-stream part is through with them
-		if (ctx->early_free_pending && (e = hipStreamWaitEvent(ctx->early_stream, ctx->early_free, 0)) != hipSuccess) return e;
-		ctx->early_free_pending = false;
-		*xs = overlap_layout(static_cast<char*>(ctx->early_buf), a, xs_doubles).xs;
-		return hipSuccess;
-	}
-	// a.Xs must be readable on the early stream: now, or — points_ready, an event recorded on it — behind work already enqueued there; fills a.q and a.mu like launch_predict_q
-	hipError_t launch_predict_overlapped(Ctx* ctx, hipStream_t s, const PredictArgs& a, size_t xs_doubles, int early_rows, hipEvent_t t_early, hipEvent_t points_ready)
-	{
-		hipStream_t E = ctx->early_stream;
-		const OverlapBuffers b = overlap_layout(static_cast<char*>(ctx->early_buf), a, xs_doubles);
-		if (!E || b.bytes > ctx->early_bytes) return hipErrorInvalidValue;
-		static const int fit_cus = [] {
-			const char* e = getenv("GPLE_PREDICT_OVERLAP_CUS");
-			return e ? atoi(e) : 64;
-		}();
-		// GPLE_PREDICT_OVERLAP_TILES: at most that many N-tiles go early (the early part should end with the fit, not after it);
-		// GPLE_PREDICT_OVERLAP_KSTAR_LATE=1: the generation waits for the early rows too (it disturbs the factorisation's first launch otherwise)
-		static const int max_tiles = [] {
-			const char* e = getenv("GPLE_PREDICT_OVERLAP_TILES");
-			return e ? atoi(e) : 1 << 20;
-		}();
-		static const bool kstar_late = [] {
-			const char* e = getenv("GPLE_PREDICT_OVERLAP_KSTAR_LATE");
-			return e != nullptr && atoi(e) != 0;
-		}();
-		const int ksplit = gen_ksplit(a.m_rows), ntiles = a.n_total / BN, jt_split = std::max(2, std::min(early_rows / BN, max_tiles)), nblocks = a.m_rows / BM;
-		const int* none = nullptr;
-		hipError_t e;
-		// early stream: K*, store only
-		if (kstar_late && (e = hipStreamWaitEvent(E, t_early, 0)) != hipSuccess) return e;
-		hipLaunchKernelGGL((kstar_gen_kernel<0, 3>), dim3(a.m_rows / 128, ksplit), dim3(128), 0, E, a, 0, a.m_rows, b.Ks, static_cast<double*>(nullptr), static_cast<double*>(nullptr), none, none);
-		hipLaunchKernelGGL(set_int2_kernel, dim3(1), dim3(1), 0, E, b.counters, a.m_rows, 0);
-		if ((e = hipStreamWaitEvent(E, t_early, 0)) != hipSuccess) return e;
-		{
-			// the tiles below the split: one virtual group per unit (the finest units), fewer resident workgroups than CUs
-			int G = 1;
-			while (2 * G <= ROWNORM_SPLIT_MAX && 4 * (2 * G) <= 2 * ntiles) G *= 2;
-			Prune pr{b.counters + 1, b.counters, 0, nblocks, G};
-			pr.jt_lo = 0, pr.jt_hi = jt_split, pr.state = b.state, pr.state_mode = 1;
-			const int wgs = std::max(16, std::min(device_cu_count() - fit_cus, nblocks * G));
-			hipLaunchKernelGGL((rownormp_kernel<4, 4, true>), dim3(wgs), dim3(NTHREADS), 0, E, b.Ks, a.m_rows, a.T, a.ldt, a.n_total, b.qpart, static_cast<long>(a.m_rows), pr);
-		}
-		if ((e = hipEventRecord(ctx->early_done, E)) != hipSuccess) return e;
-		// main stream (behind the fit): the means, then the late tiles from the saved sums
-		if (points_ready && (e = hipStreamWaitEvent(s, points_ready, 0)) != hipSuccess) return e;
-		hipLaunchKernelGGL((kstar_gen_kernel<0, 1>), dim3(a.m_rows / 128, ksplit), dim3(128), 0, s, a, 0, a.m_rows, b.Ks, b.mu_part, b.nrm_part, none, none);
-		if ((e = hipStreamWaitEvent(s, ctx->early_done, 0)) != hipSuccess) return e;
-		{
-			Prune pr{};
-			pr.jt_lo = jt_split, pr.jt_hi = ntiles, pr.state = b.state, pr.state_mode = 2;
-			const int split = rownorm_split(a.m_rows, a.n_total);
-			chunk_timer_start(ctx);
-			ctx->last_contraction = "rownormp_kernel<4,4,false>";
-			hipLaunchKernelGGL((rownormp_kernel<4, 4, false>), dim3(nblocks, split), dim3(NTHREADS), 0, s, b.Ks, a.m_rows, a.T, a.ldt, a.n_total, b.qpart, static_cast<long>(a.m_rows), pr);
-			chunk_timer_stop(ctx);
-		}
-		hipLaunchKernelGGL(sum_mu_kernel, dim3((a.m_rows + 255) / 256, 1), dim3(256), 0, s, b.qpart, a.m_rows, VG, a.q);
-		hipLaunchKernelGGL(sum_mu_kernel, dim3((a.m_rows + 255) / 256, 1), dim3(256), 0, s, b.mu_part, a.m_rows, ksplit, a.mu);
-		if ((e = hipEventRecord(ctx->early_free, s)) != hipSuccess) return e;
-		ctx->early_free_pending = true;
-		ctx->overlapped_predicts += 1;
-		return hipGetLastError();
-	}
-
 	hipError_t launch_predict_q(Ctx* ctx, hipStream_t s, const PredictArgs& a, double* scratch, int chunk_rows, bool few_rows, bool* finished)
 	{
 		if (finished) *finished = false;
 		if (a.M <= 0) return hipSuccess;
 		if (a.m_rows % BM || a.n_total % BN || a.m_split % BM || a.n_split % BN || chunk_rows % BM || chunk_rows <= 0)
 			return hipErrorInvalidValue;
-		// 0: 8 waves x (16 rows x 256 columns); 2 / 3: 8 waves x (4 x 4) / (2 x 8) fragments.  Measured at C2 / C4r (TFLOP/s, same
-		// box): 60.1 / 65.07, 59.6 / 65.78, 60.4 / 65.75 (two more shapes — 4 waves with BK 8, and 4 waves on a 128 x 128 tile, both
-		// with two workgroups per CU — were 61 and 64.0 at C4r and are gone; profiles/r02_notes.md).  Default: 2 from eight N-tiles
-		// on (+1.1 % at C4r), else 0.
-		static const int forced = [] {
-			const char* e = getenv("GPLE_ROWNORM_VARIANT");
-			return e ? atoi(e) : -1;
-		}();
-		// Round 2: with the LDS-DMA staging the 2 x 8 blocking led below eight N-tiles (C2: 64.3 vs 62.9 / 61.2 TFLOP/s).  Round 4, rownormp_kernel: 4 x 4 leads at
-		// C2 too (three same-box pairs: 0.835 / 0.841 / 0.846 of the peak against 0.830 / 0.838 / 0.836); one and two N-tiles stay on 2 x 8, the arithmetic of
-		// rownorm3_kernel and predict_fused256_kernel (the same rows come out bit for bit whichever of the three a call gets)
-		const int variant = forced >= 0 ? forced : (a.n_total / BN >= 3 ? 2 : 3);
-		// short factors with few row blocks (C1): 64-row workgroups with three slabs in flight (rownorm3_kernel; same bits as <2,8>).  GPLE_ROWNORM_SHORT=0: A/B
-		static const bool short_ok = [] {
-			const char* e = getenv("GPLE_ROWNORM_SHORT");
-			return e == nullptr || atoi(e) != 0;
-		}();
-		// the k-steps of a unit as one pipeline (rownormp_kernel; same bits).  GPLE_ROWNORM_PIPE=0: rownorm2_kernel, A/B
-		static const bool pipe_env = [] {
-			const char* e = getenv("GPLE_ROWNORM_PIPE");
-			return (e == nullptr || atoi(e) != 0);
-		}();
-		const bool pipe = ctx->rownorm_pipe < 0 ? pipe_env : ctx->rownorm_pipe != 0;
+		// Fragments per wave: 4 x 4 or 2 x 8.  Round 2: with the LDS-DMA staging the 2 x 8 blocking led below eight N-tiles (C2: 64.3 vs 62.9 / 61.2
+		// TFLOP/s).  Round 4, rownormp_kernel: 4 x 4 leads at C2 too (three same-box pairs: 0.835 / 0.841 / 0.846 of the peak against 0.830 / 0.838 /
+		// 0.836); one and two N-tiles stay on 2 x 8, the arithmetic of rownorm3_kernel and predict_fused256_kernel (the same rows come out bit for bit
+		// whichever of the three a call gets)
+		const bool b4x4 = a.n_total / BN >= 3;
+		// the k-steps of a unit as one pipeline (rownormp_kernel; same bits as rownorm2_kernel, which gple_debug_predict_knobs can select)
+		const bool pipe = ctx->rownorm_pipe != 0;
 		if (a.n_total / BN > TL_MAX) return hipErrorInvalidValue;
-		const bool short_factor = short_ok && variant == 3 && a.n_total / BN <= 2 && a.m_rows / BM <= 2 * device_cu_count();
+		// short factors with few row blocks (C1): 64-row workgroups with three slabs in flight (rownorm3_kernel; same bits as <2,8>)
+		const bool short_factor = !b4x4 && a.n_total / BN <= 2 && a.m_rows / BM <= 2 * device_cu_count();
 		double* Ks = scratch;
 		double* mu_part = scratch + static_cast<size_t>(chunk_rows) * a.n_total;
 		const bool small = few_rows && chunk_rows == a.m_rows;
@@ -1628,12 +1275,8 @@ namespace gple
 			return hipGetLastError();
 		}
 		// the real GP with one N-tile (N <= 256): generation, contraction and both sums in one launch, whatever the number of rows; a pruned request
-		// contracts every row there (same bits, cheaper than the statistics pass).  GPLE_PREDICT_FUSED_SMALL=0: the separate kernels, A/B
-		static const bool fused_env = [] {
-			const char* e = getenv("GPLE_PREDICT_FUSED_SMALL");
-			return e == nullptr || atoi(e) != 0;
-		}();
-		if ((ctx->fused_small < 0 ? fused_env : ctx->fused_small != 0) && a.n_total == BN && a.m_split == a.m_rows && !a.dv && !(a.cut_thr > 0.0))
+		// contracts every row there (same bits, cheaper than the statistics pass)
+		if (ctx->fused_small != 0 && a.n_total == BN && a.m_split == a.m_rows && !a.dv && !(a.cut_thr > 0.0))
 		{
 			chunk_timer_start(ctx);
 			ctx->last_contraction = "predict_fused256_kernel";
@@ -1651,11 +1294,10 @@ namespace gple
 				if (queue_mode) hipLaunchKernelGGL(queue_kernel, grid, dim3(NTHREADS), 0, s, Ks, rows, a.T, a.ldt, a.n_total, qdst, static_cast<long>(a.m_rows), pr);
 				else hipLaunchKernelGGL(full_kernel, grid, dim3(NTHREADS), 0, s, Ks, rows, a.T, a.ldt, a.n_total, qdst, static_cast<long>(a.m_rows), pr);
 			};
-			if (variant == 3 && pipe) { launch(rownormp_kernel<2, 8, false>, rownormp_kernel<2, 8, true>); ctx->last_contraction = queue_mode ? "rownormp_kernel<2,8,true>" : "rownormp_kernel<2,8,false>"; }
-			else if (variant == 2 && pipe) { launch(rownormp_kernel<4, 4, false>, rownormp_kernel<4, 4, true>); ctx->last_contraction = queue_mode ? "rownormp_kernel<4,4,true>" : "rownormp_kernel<4,4,false>"; }
-			else if (variant == 3) { launch(rownorm2_kernel<2, 8, false>, rownorm2_kernel<2, 8, true>); ctx->last_contraction = queue_mode ? "rownorm2_kernel<2,8,true>" : "rownorm2_kernel<2,8,false>"; }
-			else if (variant == 2) { launch(rownorm2_kernel<4, 4, false>, rownorm2_kernel<4, 4, true>); ctx->last_contraction = queue_mode ? "rownorm2_kernel<4,4,true>" : "rownorm2_kernel<4,4,false>"; }
-			else { launch(rownorm_kernel<8, 16, false>, rownorm_kernel<8, 16, true>); ctx->last_contraction = queue_mode ? "rownorm_kernel<8,16,true>" : "rownorm_kernel<8,16,false>"; }
+			if (!b4x4 && pipe) { launch(rownormp_kernel<2, 8, false>, rownormp_kernel<2, 8, true>); ctx->last_contraction = queue_mode ? "rownormp_kernel<2,8,true>" : "rownormp_kernel<2,8,false>"; }
+			else if (pipe) { launch(rownormp_kernel<4, 4, false>, rownormp_kernel<4, 4, true>); ctx->last_contraction = queue_mode ? "rownormp_kernel<4,4,true>" : "rownormp_kernel<4,4,false>"; }
+			else if (!b4x4) { launch(rownorm2_kernel<2, 8, false>, rownorm2_kernel<2, 8, true>); ctx->last_contraction = queue_mode ? "rownorm2_kernel<2,8,true>" : "rownorm2_kernel<2,8,false>"; }
+			else { launch(rownorm2_kernel<4, 4, false>, rownorm2_kernel<4, 4, true>); ctx->last_contraction = queue_mode ? "rownorm2_kernel<4,4,true>" : "rownorm2_kernel<4,4,false>"; }
 		};
 		if (prune || cut_only)
 		{
@@ -1686,12 +1328,8 @@ namespace gple
 			// the number of live row blocks is only known on the device: the finest units (most groups per block that still hold a snake pair
 			// of N-tiles each) keep the last round of the queue short whatever it turns out to be — 93 live blocks in 2 groups fill 186 of 256
 			// CUs once, in 8 groups they make 2.9 rounds of an eighth
-			static const int queue_split = [] {
-				const char* e = getenv("GPLE_PREDICT_QUEUE_SPLIT"); // 0: the split of the full launch (>= 2), as before
-				return e ? atoi(e) : ROWNORM_SPLIT_MAX;
-			}();
 			if (split < 2 && a.n_total / BN >= 4) split = 2;
-			for (int g = split * 2; g <= queue_split && 4 * g <= 2 * (a.n_total / BN); g *= 2) split = g;
+			for (int g = split * 2; g <= ROWNORM_SPLIT_MAX && 4 * g <= 2 * (a.n_total / BN); g *= 2) split = g;
 			for (int c0 = 0; c0 < a.m_rows; c0 += chunk_rows)
 			{
 				const int rows = a.m_rows - c0 < chunk_rows ? a.m_rows - c0 : chunk_rows;

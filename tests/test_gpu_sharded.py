@@ -19,14 +19,24 @@ pytestmark = pytest.mark.gpu
 _dp = C.POINTER(C.c_double)
 
 
-def _sharded(api, fit, Xs, rank, world, comm, cplx):
+def _sharded(api, fit, Xs, rank, world, comm, cplx, device=False):
+    """device: points and outputs as torch tensors on the GPU (GPLE_IO_DEVICE) instead of host arrays"""
     M = len(Xs)
     ow = 2 if cplx else 1
-    mean, var, cut = np.empty(ow * M), np.empty(M), np.empty(ow * M)
     fn = api.lib.gple_complex_predict_sharded if cplx else api.lib.gple_real_predict_sharded
     fn.argtypes = [C.c_void_p, C.c_void_p, _dp, C.c_size_t, C.c_uint, C.c_int, C.c_int, C.c_void_p, _dp, _dp, _dp]
     Xs = np.ascontiguousarray(Xs)
-    st = fn(api.ctx, fit.handle, Xs.ctypes.data_as(_dp), M, 0, rank, world, comm, mean.ctypes.data_as(_dp), var.ctypes.data_as(_dp), cut.ctypes.data_as(_dp))
+    if device:
+        import torch
+        xs, out = torch.tensor(Xs, device="cuda"), [torch.full((n,), float("nan"), dtype=torch.float64, device="cuda") for n in (ow * M, M, ow * M)]
+        ptr = lambda t: C.cast(t.data_ptr(), _dp)
+        torch.cuda.synchronize()  # the context's stream is not torch's
+        st = fn(api.ctx, fit.handle, ptr(xs), M, c.IO_DEVICE, rank, world, comm, *(ptr(t) for t in out))
+        torch.cuda.synchronize()
+        mean, var, cut = (t.cpu().numpy() for t in out)
+    else:
+        mean, var, cut = np.empty(ow * M), np.empty(M), np.empty(ow * M)
+        st = fn(api.ctx, fit.handle, Xs.ctypes.data_as(_dp), M, 0, rank, world, comm, mean.ctypes.data_as(_dp), var.ctypes.data_as(_dp), cut.ctypes.data_as(_dp))
     assert st == 0, (st, api.lib.gple_ctx_last_error(api.ctx))
     return (mean.view(np.complex128), var, cut.view(np.complex128)) if cplx else (mean, var, cut)
 
@@ -65,8 +75,9 @@ def test_sharded_predict_with_real_rccl_single_rank(gpu):
     rccl.ncclCommDestroy(comm)
 
 
-@pytest.mark.parametrize("world,cplx", [(2, False), (3, False), (2, True)])
-def test_sharded_predict_between_threads(gpu, world, cplx):
+@pytest.mark.parametrize("world,cplx,device", [pytest.param(w, x, d, id=f"{w}-{x}" + ("-device" if d else ""))
+                                               for d in (False, True) for w, x in [(2, False), (3, False), (2, True)]])
+def test_sharded_predict_between_threads(gpu, world, cplx, device):
     so = os.path.join(ROOT, "tests", "cpp", "libfake_allgather.so")
     if not os.path.exists(so):
         pytest.fail("tests/cpp/libfake_allgather.so missing: run __graft_entry__.build()")
@@ -103,7 +114,7 @@ def test_sharded_predict_between_threads(gpu, world, cplx):
                 api = pkg.open_api(0)  # one context (= stream) per rank, the fit replicated like on a real node
                 fit = (api.complex_fit if cplx else api.real_fit)(theta, X, y, 0)
                 comm = fake.fake_comm_create(group, r)
-                out[r] = _sharded(api, fit, Xs, r, world, comm, cplx)
+                out[r] = _sharded(api, fit, Xs, r, world, comm, cplx, device)
                 fake.fake_comm_destroy(comm)
                 api.close()
             except Exception as e:  # pragma: no cover
