@@ -207,6 +207,7 @@ GPLE_SYMBOLS = [
     "complex_fit_create", "complex_fit_get_scalars", "complex_fit_retain", "complex_fit_release", "complex_fit_size", "complex_fit_get",
     "complex_predict", "loose_function", "objective_create", "objective_eval", "objective_eval_part", "objective_release", "minimize_neldermead", "objective_minimize_neldermead", "minimize_direct_l", "objective_minimize_direct_l", "minimize_auglag_eq", "pes_adiabatic", "evolve", "evolve_n", "pes_adiabatic_n", "markov_chain", "markov_chain_trace", "nlml", "nlml_predict", "nlml_cross", "nlml_cross_predict",
     "dvr_hamiltonian", "dvr_propagate", "wigner",
+    "mqcl_transform", "mqcl_evolve", "mqcl_observe",
 ]
 
 
@@ -538,6 +539,85 @@ class Api:
         self._check(f(self.ctx, int(num_pes), int(boundary), n, float(x_first), float(dx), _ptr(p), len(p), _ptr(psi.view(np.float64)), T, _ptr(en),
                       float(mass), 0, None if P is None else _ptr(P.view(np.float64)), _ptr(av)))
         return P, av
+
+    # ---- exact MQCLE dynamics (liouville_equation/ of the reference; gple_mqcl_*) -------------------------------------------------------------
+    MQCL_DIABATIC, MQCL_ADIABATIC, MQCL_FORCE = 0, 1, 2
+
+    @staticmethod
+    def _mqcl_io(*arrays):
+        """numpy arrays -> (host pointers, 0); torch tensors on the GPU (contiguous, float64 / complex128) -> (device pointers, IO_DEVICE)"""
+        dev = [a is not None and hasattr(a, "data_ptr") and a.is_cuda for a in arrays]
+        if any(dev):
+            if not all(d or a is None for a, d in zip(arrays, dev)):
+                raise ValueError("either every array is a device tensor or none is")
+            for a in arrays:
+                if a is not None and not a.is_contiguous():
+                    raise ValueError("device tensors must be contiguous")
+            return [None if a is None else C.cast(a.data_ptr(), _dp) for a in arrays], IO_DEVICE
+        return [None if a is None else a.ctypes.data_as(_dp) for a in arrays], 0
+
+    @staticmethod
+    def _mqcl_rho(rho, num_pes, n):
+        if hasattr(rho, "data_ptr"):
+            if tuple(rho.shape) != (num_pes, num_pes, n, n) or str(rho.dtype) != "torch.complex128":
+                raise ValueError("rho must be a complex128 tensor of shape (num_pes, num_pes, n, n)")
+            return rho
+        rho = np.ascontiguousarray(rho, dtype=np.complex128)
+        if rho.shape != (num_pes, num_pes, n, n):
+            raise ValueError("rho must have shape (num_pes, num_pes, n, n)")
+        return rho
+
+    @staticmethod
+    def _mqcl_grid(v):
+        return v if hasattr(v, "data_ptr") else _f64(v)
+
+    def mqcl_transform(self, num_pes, model, x, rho, frm, to, out=None):
+        """gple_mqcl_transform: basis_transform[frm][to] of rho (num_pes, num_pes, n, n) complex; numpy in -> new numpy array out, device tensors
+        in -> written into `out` (a tensor like rho; rho itself when None)"""
+        x = self._mqcl_grid(x)
+        n = int(x.shape[0])
+        rho = self._mqcl_rho(rho, num_pes, n)
+        if out is None:
+            out = rho if hasattr(rho, "data_ptr") else np.empty_like(rho)
+        (px, pi, po), flags = self._mqcl_io(x, rho, out)
+        f = self.lib.gple_mqcl_transform
+        f.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, C.c_size_t, C.c_int, C.c_int, C.c_uint, _dp, _dp]
+        self._check(f(self.ctx, int(num_pes), int(model), px, n, int(frm), int(to), flags, pi, po))
+        return out
+
+    def mqcl_evolve(self, num_pes, model, x, p, rho, mass, length_x, length_p, dt, n_steps):
+        """gple_mqcl_evolve: n_steps Trotter steps on the diabatic rho (num_pes, num_pes, n, n) complex.  numpy: returns the evolved copy;
+        device tensors: evolves rho in place (asynchronously on the context's stream) and returns it"""
+        x, p = self._mqcl_grid(x), self._mqcl_grid(p)
+        n = int(x.shape[0])
+        rho = self._mqcl_rho(rho, num_pes, n)
+        if not hasattr(rho, "data_ptr"):
+            rho = rho.copy()
+        (px, pp, pr), flags = self._mqcl_io(x, p, rho)
+        f = self.lib.gple_mqcl_evolve
+        f.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.c_size_t, C.c_double, C.c_double, C.c_double, C.c_double, C.c_size_t, C.c_uint, _dp]
+        self._check(f(self.ctx, int(num_pes), int(model), px, pp, n, float(mass), float(length_x), float(length_p), float(dt), int(n_steps), flags, pr))
+        return rho
+
+    def mqcl_observe(self, num_pes, model, x, p, rho_dia, mass, dx, dp, adiabatic=True):
+        """gple_mqcl_observe: (rho_adia (num_pes, num_pes, n, n) or None, averages (E, x, p), populations (num_pes,)); with device tensors the
+        three outputs are device tensors"""
+        x, p = self._mqcl_grid(x), self._mqcl_grid(p)
+        n = int(x.shape[0])
+        rho_dia = self._mqcl_rho(rho_dia, num_pes, n)
+        if hasattr(rho_dia, "data_ptr"):
+            import torch
+            adia = torch.empty_like(rho_dia) if adiabatic else None
+            av = torch.empty(3, dtype=torch.float64, device=rho_dia.device)
+            pops = torch.empty(num_pes, dtype=torch.float64, device=rho_dia.device)
+        else:
+            adia = np.empty_like(rho_dia) if adiabatic else None
+            av, pops = np.empty(3), np.empty(num_pes)
+        (px, pp, pr, pa, pav, ppo), flags = self._mqcl_io(x, p, rho_dia, adia, av, pops)
+        f = self.lib.gple_mqcl_observe
+        f.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.c_size_t, C.c_double, C.c_double, C.c_double, C.c_uint, _dp, _dp, _dp, _dp]
+        self._check(f(self.ctx, int(num_pes), int(model), px, pp, n, float(mass), float(dx), float(dp), flags, pr, pa, pav, ppo))
+        return adia, av, pops
 
     def evolve_n(self, num_pes, fits, model, mass, dt, density, new_points=False):
         """gple_evolve_n: one tick for an N-level system; fits and density in the packing order (0,0), (1,0), (1,1), (2,0), ...;

@@ -2603,6 +2603,147 @@ extern "C"
 		return GPLE_OK;
 	}
 
+	/* ---- exact MQCLE dynamics (gple_mqcl.hip; liouville_equation/ of the reference) ------------------------------------------------------ */
+	static bool mqcl_size_ok(int num_pes, int model, size_t n) { return dvr_model_ok(num_pes, model) && n >= 4 && n <= 4096; }
+
+	// the per-x tables of gple_mqcl.hip from host or device x (tq: the time of one Q step, spectral: the FFT tables too)
+	static int mqcl_tables(gple_ctx* ctx, hipStream_t st, int num_pes, int model, const double* x, int n, bool dev, double tq, bool spectral, Scratch& xs,
+		Scratch& tables)
+	{
+		const double* xd = x;
+		if (!dev)
+		{
+			GPLE_HIP(ctx, xs.get(n));
+			GPLE_HIP(ctx, copy_in(st, xs.p, x, n, false));
+			xd = xs.p;
+		}
+		GPLE_HIP(ctx, tables.get(mqcl_table_doubles(num_pes, n)));
+		GPLE_HIP(ctx, launch_mqcl_tables(st, num_pes, model, xd, n, tq, spectral, tables.p));
+		return GPLE_OK;
+	}
+
+	int gple_mqcl_transform(gple_ctx* ctx, int num_pes, int model, const double* x, size_t n_grids, int from, int to, unsigned flags, const double* rho_in,
+		double* rho_out)
+	{
+		if (!ctx || !mqcl_size_ok(num_pes, model, n_grids) || from < 0 || from > 2 || to < 0 || to > 2 || !x || !rho_in || !rho_out) return GPLE_ERR_BAD_ARG;
+		GPLE_OPEN(ctx);
+		const bool dev = flags & GPLE_IO_DEVICE;
+		const int n = static_cast<int>(n_grids);
+		const size_t doubles = 2 * static_cast<size_t>(num_pes) * num_pes * n_grids * n_grids;
+		std::lock_guard<std::mutex> lk(ctx->call_mu);
+		GPLE_HIP(ctx, hipSetDevice(ctx->device));
+		hipStream_t st = ctx->stream;
+		Scratch xs(ctx), tables(ctx), rin(ctx), rout(ctx);
+		GPLE_TRY(mqcl_tables(ctx, st, num_pes, model, x, n, dev, 0.0, false, xs, tables));
+		const double* ri = rho_in;
+		double* ro = rho_out;
+		if (!dev)
+		{
+			GPLE_HIP(ctx, rin.get(doubles));
+			GPLE_HIP(ctx, rout.get(doubles));
+			GPLE_HIP(ctx, copy_in(st, rin.p, rho_in, doubles, false));
+			ri = rin.p, ro = rout.p;
+		}
+		GPLE_HIP(ctx, launch_mqcl_transform(st, num_pes, n, from, to, tables.p, ri, ro));
+		if (!dev)
+		{
+			GPLE_HIP(ctx, copy_out(st, rho_out, ro, doubles, false));
+			GPLE_HIP(ctx, hipStreamSynchronize(st));
+		}
+		return GPLE_OK;
+	}
+
+	int gple_mqcl_evolve(gple_ctx* ctx, int num_pes, int model, const double* x, const double* p, size_t n_grids, double mass, double length_x,
+		double length_p, double dt, size_t n_steps, unsigned flags, double* rho)
+	{
+		if (!ctx || !mqcl_size_ok(num_pes, model, n_grids) || !x || !p || !rho || !(mass > 0.0) || !std::isfinite(mass) || !(length_x > 0.0) ||
+			!std::isfinite(length_x) || !(length_p > 0.0) || !std::isfinite(length_p) || !std::isfinite(dt) || n_steps > (1ul << 40))
+			return GPLE_ERR_BAD_ARG;
+		GPLE_OPEN(ctx);
+		if (n_steps == 0) return GPLE_OK;
+		const bool dev = flags & GPLE_IO_DEVICE;
+		const int n = static_cast<int>(n_grids);
+		const size_t plane = n_grids * n_grids, doubles = 2 * static_cast<size_t>(num_pes) * num_pes * plane;
+		std::lock_guard<std::mutex> lk(ctx->call_mu);
+		GPLE_HIP(ctx, hipSetDevice(ctx->device));
+		hipStream_t st = ctx->stream;
+		Scratch xs(ctx), tables(ctx), pd(ctx), rd(ctx), tr(ctx);
+		GPLE_TRY(mqcl_tables(ctx, st, num_pes, model, x, n, dev, dt / 2.0, true, xs, tables));
+		GPLE_HIP(ctx, tr.get(2 * plane * (num_pes * (num_pes + 1) / 2)));
+		const double* pp = p;
+		double* r = rho;
+		if (!dev)
+		{
+			GPLE_HIP(ctx, pd.get(n_grids));
+			GPLE_HIP(ctx, rd.get(doubles));
+			GPLE_HIP(ctx, copy_in(st, pd.p, p, n_grids, false));
+			GPLE_HIP(ctx, copy_in(st, rd.p, rho, doubles, false));
+			pp = pd.p, r = rd.p;
+		}
+		MqclEvolveArgs g{};
+		g.num_pes = num_pes, g.n = n, g.n_steps = static_cast<long>(n_steps), g.rho = r, g.transposed = tr.p, g.table = tables.p, g.p = pp;
+		g.mass = mass, g.length_x = length_x, g.length_p = length_p, g.dt = dt;
+		timer_start(ctx, GPLE_TIMER_MQCL);
+		GPLE_HIP(ctx, launch_mqcl_evolve(st, g));
+		timer_stop(ctx, GPLE_TIMER_MQCL);
+		GPLE_HIP(ctx, launch_mqcl_lower(st, num_pes, n, r));
+		if (!dev)
+		{
+			GPLE_HIP(ctx, copy_out(st, rho, r, doubles, false));
+			GPLE_HIP(ctx, hipStreamSynchronize(st));
+		}
+		return GPLE_OK;
+	}
+
+	int gple_mqcl_observe(gple_ctx* ctx, int num_pes, int model, const double* x, const double* p, size_t n_grids, double mass, double dx, double dp,
+		unsigned flags, const double* rho_dia, double* rho_adia, double* averages, double* populations)
+	{
+		if (!ctx || !mqcl_size_ok(num_pes, model, n_grids) || !x || !p || !rho_dia || !averages || !populations || !(mass > 0.0) || !std::isfinite(mass) ||
+			!std::isfinite(dx) || !std::isfinite(dp))
+			return GPLE_ERR_BAD_ARG;
+		GPLE_OPEN(ctx);
+		const bool dev = flags & GPLE_IO_DEVICE;
+		const int n = static_cast<int>(n_grids);
+		const size_t doubles = 2 * static_cast<size_t>(num_pes) * num_pes * n_grids * n_grids;
+		std::lock_guard<std::mutex> lk(ctx->call_mu);
+		GPLE_HIP(ctx, hipSetDevice(ctx->device));
+		hipStream_t st = ctx->stream;
+		Scratch xs(ctx), tables(ctx), pd(ctx), rd(ctx), ad(ctx), work(ctx), outd(ctx);
+		GPLE_TRY(mqcl_tables(ctx, st, num_pes, model, x, n, dev, 0.0, false, xs, tables));
+		const double *pp = p, *r = rho_dia;
+		double* a = rho_adia;
+		if (!dev)
+		{
+			GPLE_HIP(ctx, pd.get(n_grids));
+			GPLE_HIP(ctx, rd.get(doubles));
+			GPLE_HIP(ctx, copy_in(st, pd.p, p, n_grids, false));
+			GPLE_HIP(ctx, copy_in(st, rd.p, rho_dia, doubles, false));
+			pp = pd.p, r = rd.p;
+			if (rho_adia)
+			{
+				GPLE_HIP(ctx, ad.get(doubles));
+				a = ad.p;
+			}
+		}
+		GPLE_HIP(ctx, work.get(mqcl_observe_work_doubles(num_pes, n)));
+		GPLE_HIP(ctx, outd.get(3 + num_pes));
+		const double* xd = dev ? x : xs.p;
+		GPLE_HIP(ctx, launch_mqcl_observe(st, num_pes, n, tables.p, xd, pp, mass, dx * dp, r, a, work.p, outd.p));
+		if (dev)
+		{
+			GPLE_HIP(ctx, hipMemcpyAsync(averages, outd.p, 3 * sizeof(double), hipMemcpyDeviceToDevice, st));
+			GPLE_HIP(ctx, hipMemcpyAsync(populations, outd.p + 3, num_pes * sizeof(double), hipMemcpyDeviceToDevice, st));
+			return GPLE_OK;
+		}
+		double h[6];
+		GPLE_HIP(ctx, hipMemcpyAsync(h, outd.p, (3 + num_pes) * sizeof(double), hipMemcpyDeviceToHost, st));
+		if (rho_adia) GPLE_HIP(ctx, copy_out(st, rho_adia, a, doubles, false));
+		GPLE_HIP(ctx, hipStreamSynchronize(st));
+		for (int k = 0; k < 3; ++k) averages[k] = h[k];
+		for (int k = 0; k < num_pes; ++k) populations[k] = h[3 + k];
+		return GPLE_OK;
+	}
+
 	int gple_markov_chain(gple_ctx* ctx, const gple_element* element, size_t num_steps, double max_displacement, unsigned long long seed, double* r,
 		size_t n, double* accept_ratio)
 	{

@@ -259,4 +259,26 @@ namespace gple
 	size_t wigner_avg_work_doubles(int num_pes, int T);
 	hipError_t launch_wigner_averages(hipStream_t s, int num_pes, int n, double x_first, double dx, const double* p, int np, const double* energies,
 		double mass, const double* P, int T, double* work, double* averages);
+	// ---- exact MQCLE dynamics (gple_mqcl.hip): num_pes = 2 or 3, 4 <= n <= 4096, rho: num_pes^2 x n x n (re, im) pairs, x major ------------
+	// tables (mqcl_table_doubles): per x C | E | U | lambda | Q phases of one Q(tq), then (spectral) chirp (n), twiddles (M / 2), chirp spectrum (M)
+	int mqcl_fft_length(int n);
+	size_t mqcl_table_doubles(int num_pes, int n);
+	hipError_t launch_mqcl_tables(hipStream_t s, int num_pes, int model, const double* x, int n, double tq, bool spectral, double* tables);
+	struct MqclEvolveArgs
+	{
+		int num_pes, n, M;
+		long n_steps;
+		double* rho;        // the caller's full layout, in place (only the planes a <= b are read)
+		double* transposed; // num_pes (num_pes + 1) / 2 x n x n (re, im) pairs
+		const double* table;
+		const double* p;
+		const double *chirp, *tw, *bhat; // filled by launch_mqcl_evolve from table
+		double mass, length_x, length_p, dt;
+	};
+	hipError_t launch_mqcl_evolve(hipStream_t s, const MqclEvolveArgs& g);
+	hipError_t launch_mqcl_lower(hipStream_t s, int num_pes, int n, double* rho);
+	hipError_t launch_mqcl_transform(hipStream_t s, int num_pes, int n, int from, int to, const double* tables, const double* in, double* out);
+	size_t mqcl_observe_work_doubles(int num_pes, int n);
+	hipError_t launch_mqcl_observe(hipStream_t s, int num_pes, int n, const double* tables, const double* x, const double* p, double mass, double dxdp,
+		const double* rho, double* adia, double* work, double* out);
 } // namespace gple

@@ -148,7 +148,8 @@ typedef enum gple_timer {
 	GPLE_TIMER_PREDICT = 1,        /* whole *_predict call (device side)                    */
 	GPLE_TIMER_PREDICT_KERNEL = 2, /* the MFMA row-norm kernel of *_predict alone; count = its launches */
 	GPLE_TIMER_DERIV_GEMM = 3,     /* the dK * K^-1 MFMA GEMM of a GPLE_CALC_DERIVATIVE fit (kernel.cpp:354); count = its launches */
-	GPLE_TIMER_WIGNER = 4          /* the MFMA kernel of gple_wigner alone (all T output times of a call); count = its launches */
+	GPLE_TIMER_WIGNER = 4,         /* the MFMA kernel of gple_wigner alone (all T output times of a call); count = its launches */
+	GPLE_TIMER_MQCL = 5            /* the step kernels of one gple_mqcl_evolve call (all its steps, no set-up); count = its calls */
 } gple_timer;
 int gple_ctx_enable_timing(gple_ctx* ctx, int on);
 /* Synchronises the stream, then: last = milliseconds of the most recent interval; total / count = accumulated since
@@ -399,6 +400,32 @@ int gple_dvr_propagate(gple_ctx* ctx, int num_pes, size_t n_grids, const double*
  * and p^2 / 2 mass; two calls on the same input return the same bits.  Only the elements j <= i are summed, P_ji = conj(P_ij). */
 int gple_wigner(gple_ctx* ctx, int num_pes, int boundary, size_t n_grids, double x_first, double dx, const double* p, size_t n_p,
 	const double* psi, size_t T, const double* energies, double mass, unsigned flags, double* phase, double* averages);
+
+/* ---- exact MQCLE dynamics (liouville_equation/ of the reference) ------------------------------------------------------- */
+/* The mixed quantum-classical Liouville equation on the square (x, p) grid of n points per axis, evolved in the diabatic basis
+ * (main.cpp:153).  num_pes = 2 or 3, models as gple_evolve_n (TSAC = 3 only at three levels), 4 <= n <= 4096.  rho: the phase.txt layout,
+ * num_pes^2 elements (a, b) row-major, each n x n (re, im) pairs with x major and p fastest.  Only the elements a <= b are read; every
+ * output has rho_ba = conj(rho_ab) and diagonal imaginary parts exactly zero.  x, p: the n grid values.  Adiabatic states: the convention
+ * of gple_evolve_n (the reference takes dsyev's raw signs); force basis: eigenvectors of the diabatic force (their signs cancel). */
+typedef enum gple_mqcl_basis
+{
+	GPLE_MQCL_DIABATIC = 0,  /* Representation::Diabatic (general.h) */
+	GPLE_MQCL_ADIABATIC = 1, /* Representation::Adiabatic */
+	GPLE_MQCL_FORCE = 2      /* Representation::ForceBasis */
+} gple_mqcl_basis;
+/* basis_transform[from][to] (pes.cpp:360-700): through the diabatic basis, every rotation hermitised.  rho_in and rho_out may alias. */
+int gple_mqcl_transform(gple_ctx* ctx, int num_pes, int model, const double* x, size_t n, int from, int to, unsigned flags,
+	const double* rho_in, double* rho_out);
+/* n_steps Trotter steps Q(dt/2) R(dt/2) P(dt) R(dt/2) Q(dt/2) (main.cpp:192-260) in place on the diabatic rho, every launch on the context's
+ * stream.  R shifts along x over the length length_x (xmax - xmin), P along p over length_p (pmax - pmin), with the reference's frequency map
+ * (bin k -> k for k < n / 2, else k - n) and the hermitisation after every shift.  mass > 0, dt finite. */
+int gple_mqcl_evolve(gple_ctx* ctx, int num_pes, int model, const double* x, const double* p, size_t n, double mass, double length_x, double length_p,
+	double dt, size_t n_steps, unsigned flags, double* rho);
+/* The adiabatic rho of the diabatic rho_dia (rho_adia, nullable) and calculate_average / calculate_population of it (general.cpp:108-164):
+ * averages = (E, x, p) with E weighted by the adiabatic energy plus p^2 / 2 mass, populations (num_pes), all times dx dp.  Two calls on the
+ * same input return the same bits. */
+int gple_mqcl_observe(gple_ctx* ctx, int num_pes, int model, const double* x, const double* p, size_t n, double mass, double dx, double dp,
+	unsigned flags, const double* rho_dia, double* rho_adia, double* averages, double* populations);
 
 /* generate_markov_chain (mc.cpp:118-165) for n walkers at once on the fitted distribution |cut-off prediction| of `element`:
  * num_steps Metropolis steps with uniform displacements in [-max_displacement, max_displacement) per dimension; r (2n) holds
