@@ -1334,14 +1334,6 @@ extern "C"
 		if (want_deriv)
 			for (int ip = 0; ip < (cplx ? 8 : 4); ++ip) scalars->error_derivative[ip] = ctx->host_scalars[HS_PRED_DERIV + ip];
 	}
-	static bool predict_pruning()
-	{
-		static const bool on = [] {
-			const char* e = getenv("GPLE_PREDICT_PRUNE");
-			return !e || atoi(e) != 0;
-		}();
-		return on;
-	}
 	static int predict_pass(gple_ctx* ctx, const FitCommon* f, const double* Xs, size_t M, unsigned flags, const double* labels,
 		double* prediction, double* variance, double* cutoff_prediction, gple_predict_scalars* scalars, bool* repeat);
 	static int predict_common(gple_ctx* ctx, const FitCommon* f, const double* Xs, size_t M, unsigned flags, const double* labels,
@@ -1397,7 +1389,7 @@ extern "C"
 		a.Xs = xs_dev, a.M = Mi, a.m_rows = m_rows, a.m_split = cplx ? Mh : m_rows;
 		a.Xt = f->Xt, a.N = f->N, a.n_total = f->n_total, a.n_split = cplx ? f->Np : f->n_total;
 		a.T = f->T, a.ldt = f->n_total, a.v = f->v, a.q = q.p, a.mu = mu.p, a.ps = f->ps;
-		if (!(flags & GPLE_PREDICT_FULL) && predict_pruning())
+		if (!(flags & GPLE_PREDICT_FULL))
 		{
 			// |k*|^2 below this cannot move the variance (gple_predict.hip, Prune): lambda_min(K) >= amp n2, k(x*,x*) = self.
 			// Complex GP in its [Re; Im] embedding: the covariance is a valid (positive semi-definite) cross-covariance of two
@@ -1418,15 +1410,11 @@ extern "C"
 			a.complex_deriv = cplx ? 1 : 0;
 			if (cplx) std::memcpy(a.dspec, f->dspec, sizeof(a.dspec));
 		}
-		// How much of the variance contraction the caller's outputs need (GPLE_PREDICT_SKIP=0: always all of it, for A/B runs).  The objective
+		// How much of the variance contraction the caller's outputs need.  The objective
 		// of opt.cpp:441-482 asks for Error (+ ErrorDerivatives) only: Error uses the UNCUT mean (kernel.cpp:522) — no contraction at all, every
 		// value-only evaluation of the derivative-free searches; ErrorDerivatives use the cut one (:527), where the variance only decides the
 		// cut-off factor — and a point with |mu|^2 >= 4 k(x*,x*) >= 4 var has factor 1 (kernel.h:301-332) whatever q is.
-		static const bool skip_ok = [] {
-			const char* e = getenv("GPLE_PREDICT_SKIP");
-			return e == nullptr || atoi(e) != 0;
-		}();
-		if (skip_ok && !variance && !cutoff_prediction)
+		if (!variance && !cutoff_prediction)
 		{
 			if (!want_deriv) a.mean_only = 1;
 			else
@@ -1612,21 +1600,13 @@ extern "C"
 			f->point_cv.notify_all();
 		}
 	}
-	static bool point_combining()
-	{
-		static const bool on = [] {
-			const char* e = getenv("GPLE_POINT_COMBINE");
-			return !e || atoi(e) != 0;
-		}();
-		return on;
-	}
 
 	int gple_real_predict(gple_ctx* ctx, const gple_real_fit* fit, const double* Xs, size_t M, unsigned flags, const double* labels,
 		double* prediction, double* variance, double* cutoff_prediction, gple_predict_scalars* scalars)
 	{
 		if (!ctx || !fit || (M && !Xs)) return GPLE_ERR_BAD_ARG;
 		GPLE_OPEN(ctx);
-		if (M == 1 && !labels && !(flags & GPLE_IO_DEVICE) && point_combining())
+		if (M == 1 && !labels && !(flags & GPLE_IO_DEVICE))
 		{
 			if (scalars)
 			{
@@ -1868,7 +1848,7 @@ extern "C"
 	{
 		if (!ctx || !fit || (M && !Xs)) return GPLE_ERR_BAD_ARG;
 		GPLE_OPEN(ctx);
-		if (M == 1 && !labels && !(flags & GPLE_IO_DEVICE) && point_combining())
+		if (M == 1 && !labels && !(flags & GPLE_IO_DEVICE))
 		{
 			if (scalars)
 			{
@@ -3076,38 +3056,6 @@ extern "C"
 		unsigned flags, double* mean)
 	{
 		return nlml_predict_impl(ctx, x, 5, X, y, N, Xs, M, flags, mean);
-	}
-
-	/* gple_debug.h (not part of include/gple.h): instrumented launch of the diagonal-block kernel for probes/diag_probe.py.
-	 * A: 64 x 64 column-major SPD block (host); T out: inv(chol(A)) (host); stamps: 16 cycle-counter values (host). */
-	int gple_debug_potrf_diag(gple_ctx* ctx, const double* A, double* T, long long* stamps, int reps, float* ms_per_launch)
-	{
-		if (!ctx || !A || !T || !stamps) return GPLE_ERR_BAD_ARG;
-		GPLE_OPEN(ctx);
-		std::lock_guard<std::mutex> lk(ctx->call_mu);
-		GPLE_HIP(ctx, hipSetDevice(ctx->device));
-		hipStream_t st = ctx->stream;
-		Scratch a(ctx), t(ctx), aux(ctx);
-		GPLE_HIP(ctx, a.get(64 * 64));
-		GPLE_HIP(ctx, t.get(64 * 64));
-		GPLE_HIP(ctx, aux.get(32));
-		GPLE_HIP(ctx, hipMemsetAsync(aux.p, 0, 32 * 8, st));
-		GPLE_HIP(ctx, copy_in(st, a.p, A, 64 * 64, false));
-		hipEvent_t e0, e1;
-		GPLE_HIP(ctx, hipEventCreate(&e0));
-		GPLE_HIP(ctx, hipEventCreate(&e1));
-		GPLE_HIP(ctx, debug_potrf_diag(st, a.p, t.p, reinterpret_cast<int*>(aux.p), reinterpret_cast<long long*>(aux.p + 8)));
-		GPLE_HIP(ctx, hipEventRecord(e0, st));
-		for (int i = 0; i < reps; ++i) GPLE_HIP(ctx, debug_potrf_diag(st, a.p, t.p, reinterpret_cast<int*>(aux.p), reinterpret_cast<long long*>(aux.p + 8)));
-		GPLE_HIP(ctx, hipEventRecord(e1, st));
-		GPLE_HIP(ctx, hipStreamSynchronize(st));
-		float ms = 0.f;
-		GPLE_HIP(ctx, hipEventElapsedTime(&ms, e0, e1));
-		if (ms_per_launch) *ms_per_launch = reps > 0 ? ms / reps : 0.f;
-		(void)hipEventDestroy(e0), (void)hipEventDestroy(e1);
-		GPLE_HIP(ctx, hipMemcpy(T, t.p, 64 * 64 * 8, hipMemcpyDeviceToHost));
-		GPLE_HIP(ctx, hipMemcpy(stamps, aux.p + 8, 16 * 8, hipMemcpyDeviceToHost));
-		return GPLE_OK;
 	}
 
 	/* gple_debug.h: the layout the factorisation of an n-column matrix will use (host logic only, no device call): outer block bounds

@@ -38,7 +38,7 @@ namespace gple
 			return fma(r, e * fma(0.375, e, 0.5), r);
 		}
 
-		// ---- diagonal-block kernel: L_jj = chol(A_jj), T_jj = L_jj^-1 and the panel rows below, one launch ----------------------
+		// ---- the diagonal block of a panel: L_jj = chol(A_jj), T_jj = L_jj^-1 (potrf_step_kernel, potrf_dag_kernel) ----------------
 		// The panel step is the critical path of the fit.  Its first form (rounds 1-2: one sweep over the diagonal block and the rows
 		// below it, the scaled column published through LDS with a barrier per column) took ~320 ns per column, 20 us per panel.
 		// Here the 64 x 64 diagonal block is factored 16 columns at a time by ONE wave with a matrix row per lane and no LDS or
@@ -284,167 +284,17 @@ namespace gple
 				for (int c = 0; c < 16; ++c) Trow[c] = c < i ? nri * acc[c] : (c == i ? ri : 0.0);
 			}
 		}
-		// A points at block (j0, j0) of the working matrix (column-major, lower part valid); T_jj (ldt) receives inv(L_jj) as a full
-		// 64 x 64 block (zeros above the diagonal).  L_jj itself is not kept: nothing downstream reads a diagonal block of the factor.
-		// Every workgroup factors and inverts the diagonal block for itself (no workgroup ever waits for another) and then turns
-		// its own 64 rows of the panel below, P = A(j0 + 64 + 64 b .., j0 .. j0 + 63), into L21 = P T_jj^T in place; the rows are
-		// requested from HBM before the factorisation starts.  Workgroup 0 also stores T_jj.
-		template <bool PROBE>
-		__global__ void __launch_bounds__(256) potrf_diag_kernel(const double* __restrict__ A, long lda, double* __restrict__ T, long ldt, int* __restrict__ info,
-			int j0, long long* __restrict__ stamps, double* __restrict__ P, int below, double* __restrict__ uvec)
-		{
-			int stamp_i = 0;
-			auto stamp = [&]() {
-				if constexpr (PROBE)
-					if (threadIdx.x == 0) stamps[stamp_i++] = static_cast<long long>(__builtin_readcyclecounter());
-			};
-			stamp();
-			__shared__ __attribute__((aligned(16))) double S[NB * DLS];  // A_jj -> L_jj (strictly lower tiles); later the panel rows
-			__shared__ __attribute__((aligned(16))) double TI[NB * DLS]; // T_jj; tile (i, b), b < i, holds V(i, b) until T(i, b) replaces it
-			__shared__ double rinv[NB];
-			const int t = threadIdx.x, lane = t & 63, w = __builtin_amdgcn_readfirstlane(t >> 6);
-			{
-				const int r = t & 63;
-#pragma unroll
-				for (int q = 0; q < 16; ++q)
-				{
-					const int c = (t >> 6) + 4 * q;
-					S[r * DLS + c] = A[r + static_cast<long>(c) * lda];
-				}
-			}
-			const bool has_rows = static_cast<int>(blockIdx.x) * NB < below; // uniform
-			double* const Pb = P + static_cast<long>(blockIdx.x) * NB;
-			double prow[16];
-			if (has_rows)
-			{
-				const int r = t & 63;
-#pragma unroll
-				for (int q = 0; q < 16; ++q) prow[q] = Pb[r + static_cast<long>((t >> 6) + 4 * q) * lda];
-			}
-			int first_bad = 0;
-			auto Sx = [&](int ti, int tj) { return S + ti * 16 * DLS + tj * 16; };
-			auto Tx = [&](int ti, int tj) { return TI + ti * 16 * DLS + tj * 16; };
-			// trailing tile (ti, tj) -= L(ti, sp) L(tj, sp)^T
-			auto upd = [&](int ti, int tj, int sp) {
-				d4v acc = tile_load(Sx(ti, tj), lane);
-				acc = tile_mac<true, true, 16>(acc, Sx(ti, sp), Sx(tj, sp), lane);
-				tile_store(Sx(ti, tj), acc, lane);
-			};
-			// V(i, b) (+)= L(i, k) T(k, b), kept in TI's tile (i, b)
-			auto v_acc = [&](int i, int b, int k, bool first) {
-				d4v acc = {0.0, 0.0, 0.0, 0.0};
-				if (!first) acc = tile_load(Tx(i, b), lane);
-				acc = tile_mac<false, false, 16>(acc, Sx(i, k), Tx(k, b), lane);
-				tile_store(Tx(i, b), acc, lane);
-			};
-			// T(i, b) = -T(i, i) V(i, b), in place
-			auto t_fin = [&](int i, int b) {
-				d4v acc = {0.0, 0.0, 0.0, 0.0};
-				acc = tile_mac<false, true, 16>(acc, Tx(i, i), Tx(i, b), lane);
-				tile_store(Tx(i, b), acc, lane);
-			};
-			__syncthreads();
-			stamp();
-			if (w == 0) diag_chain<0>(S, rinv, lane, first_bad);
-			__syncthreads();
-			stamp();
-			if (w == 0) upd(1, 1, 0);
-			else if (w == 1) upd(2, 1, 0);
-			else if (w == 2) upd(3, 1, 0);
-			else upd(2, 2, 0);
-			__syncthreads();
-			stamp();
-			if (w == 0) diag_chain<1>(S, rinv, lane, first_bad);
-			else if (w == 1) diag_inv16(S, rinv, TI, 0, lane);
-			else if (w == 2) upd(3, 2, 0);
-			else upd(3, 3, 0);
-			__syncthreads();
-			stamp();
-			if (w == 0) upd(2, 2, 1);
-			else if (w == 1) upd(3, 2, 1);
-			else if (w == 2) upd(3, 3, 1);
-			else v_acc(1, 0, 0, true);
-			__syncthreads();
-			stamp();
-			if (w == 0) diag_chain<2>(S, rinv, lane, first_bad);
-			else if (w == 1) diag_inv16(S, rinv, TI, 1, lane);
-			else if (w == 2) v_acc(2, 0, 0, true);
-			else v_acc(3, 0, 0, true);
-			__syncthreads();
-			stamp();
-			if (w == 0) upd(3, 3, 2);
-			else if (w == 1) t_fin(1, 0);
-			else if (w == 2) v_acc(2, 1, 1, true);
-			else v_acc(3, 1, 1, true);
-			__syncthreads();
-			stamp();
-			if (w == 0) diag_chain<3>(S, rinv, lane, first_bad);
-			else if (w == 1) diag_inv16(S, rinv, TI, 2, lane);
-			else if (w == 2) v_acc(2, 0, 1, false);
-			else v_acc(3, 0, 1, false);
-			__syncthreads();
-			stamp();
-			if (w == 0) diag_inv16(S, rinv, TI, 3, lane);
-			else if (w == 1) t_fin(2, 0), v_acc(3, 0, 2, false); // LDS operations of one wave complete in order
-			else if (w == 2) t_fin(2, 1), v_acc(3, 1, 2, false);
-			else v_acc(3, 2, 2, true);
-			__syncthreads();
-			stamp();
-			if (w < 3) t_fin(3, w);
-			if (has_rows) // L_jj is dead since the last barrier: the panel rows take its place
-			{
-				const int r = t & 63;
-#pragma unroll
-				for (int q = 0; q < 16; ++q) S[r * DLS + (t >> 6) + 4 * q] = prow[q];
-			}
-			__syncthreads();
-			stamp();
-			if (blockIdx.x == 0)
-			{
-				const int r = t & 63;
-#pragma unroll
-				for (int q = 0; q < 16; ++q)
-				{
-					const int c = (t >> 6) + 4 * q;
-					T[r + static_cast<long>(c) * ldt] = c <= r ? TI[r * DLS + c] : 0.0;
-					if (j0 & NB) T[r - NB + static_cast<long>(c) * ldt] = 0.0; // see potrf_step_kernel
-				}
-				if (first_bad != 0 && t == 0) atomicCAS(info, 0, j0 + first_bad); // info starts at 0
-			}
-			stamp();
-			if (has_rows)
-			{
-				// L21(16 w .. 16 w + 15, 16 j ..) = sum_{k <= 16 j + 15} P(., k) T_jj(16 j .., k): wave w owns row tile w of the 64 rows
-				d4v out[4];
-				out[0] = tile_mac<true, false, 16>((d4v){0.0, 0.0, 0.0, 0.0}, S + w * 16 * DLS, TI, lane);
-				out[1] = tile_mac<true, false, 32>((d4v){0.0, 0.0, 0.0, 0.0}, S + w * 16 * DLS, TI + 16 * DLS, lane);
-				out[2] = tile_mac<true, false, 48>((d4v){0.0, 0.0, 0.0, 0.0}, S + w * 16 * DLS, TI + 32 * DLS, lane);
-				out[3] = tile_mac<true, false, 64>((d4v){0.0, 0.0, 0.0, 0.0}, S + w * 16 * DLS, TI + 48 * DLS, lane);
-				// the wave's own rows of S are dead once its MFMAs have read them: reuse them to transpose the result for coalesced stores
-#pragma unroll
-				for (int j = 0; j < 4; ++j) tile_store(S + w * 16 * DLS + j * 16, out[j], lane);
-				__syncthreads();
-				const int r = t & 63;
-#pragma unroll
-				for (int q = 0; q < 16; ++q)
-				{
-					const int c = (t >> 6) + 4 * q;
-					Pb[r + static_cast<long>(c) * lda] = S[r * DLS + c];
-				}
-				// the label row carried below the matrix (chol_inverse_factor, `uvec`): its factor entries are u = L^-1 y, 64 per panel
-				if (uvec != nullptr && blockIdx.x == gridDim.x - 1 && t < NB) uvec[j0 + t] = S[t];
-			}
-			stamp();
-		}
 
 		// ---- the whole panel step in one launch ----------------------------------------------------------------------------------
-		// potrf_diag_kernel followed by the rank-64 update of the block column's strip is two dependent launches per panel: the
+		// A launch for the panel followed by the rank-64 update of the block column's strip is two dependent launches per panel: the
 		// update (5 us, latency-bound) sits on the critical path only because the NEXT panel's own 64 columns are among what it
 		// updates.  Here the panel applies the previous panel's update to its own columns itself (left-looking by exactly one
 		// step: diagonal block before the chain starts, its 64 rows below on four extra waves while wave 0 runs the first two
 		// chains), and the rest of that update — every column right of this panel — is done by further workgroups of the SAME
 		// launch, next to the panel workgroups instead of in front of them.  One launch per panel; no workgroup waits for another:
-		//   workgroups [0, ndt):      panel j0 (as potrf_diag_kernel), `pend`: first subtract L_prev(rows) L_prev(diag rows)^T
+		//   workgroups [0, ndt):      panel j0: each factors and inverts the diagonal block for itself, then turns its own 64 rows of the
+		//                              panel below, P, into L21 = P T_jj^T in place; workgroup 0 also stores T_jj (a full 64 x 64 block,
+		//                              zeros above the diagonal; L_jj itself is not kept).  `pend`: first subtract L_prev(rows) L_prev(diag rows)^T
 		//   workgroups [ndt, ndt + .): four 64 x 64 tiles (r >= c) each of  A(c0 + 64 r .., c0 + 64 c ..) -= L_prev(rows r) L_prev(rows c)^T,
 		//                              c0 = j0 + 64, L_prev = A(., j0 - 64 .. j0 - 1); straight from L2 into MFMA fragments, no LDS
 		// 8 waves: waves 4-7 hold the panel rows as MFMA accumulators from the start (no register copy of them on the chain wave)
@@ -803,7 +653,7 @@ namespace gple
 		// rehearsal — the first give-up seen outside the tests that force one.  A wait is better than a give-up while the other side makes progress.)
 		constexpr int DAG_POLL_LIMIT_DEFAULT = 1 << 23;
 		// the ticket floor of a launch is (epoch * DAG_MAX_LAUNCHES + launch number) << 32: a factorisation may have up to DAG_MAX_LAUNCHES launches
-		// (n = 8192: 12; more than 64, the packing of round 3, from n ~ 29k on or with GPLE_CHOL_OUTER=256 above n = 16384 — launch 64 of epoch e then
+		// (n = 8192: 12; more than 64, the packing of round 3, from n ~ 29k on or with equal 256-wide outer blocks above n = 16384 — launch 64 of epoch e then
 		// had the floor of launch 0 of epoch e + 1), and epochs stay below 2^31 / DAG_MAX_LAUNCHES (dag_state)
 		constexpr unsigned long long DAG_MAX_LAUNCHES = 4096;
 #ifndef DAG_POLL_SLEEP
@@ -1604,52 +1454,33 @@ namespace gple
 	// 8 n^3 / (3 * 64) bytes in total, 2.9 GB at n = 4096 — the K = 64 updates run at HBM speed, not MFMA speed.  With outer blocks
 	// the panel steps only update the rest of their own block (a strip), and the matrix right of the block gets ONE update with
 	// K = the block's width per outer block.  In the one-launch panel step the strip's tiles run beside the panel workgroups for
-	// free as long as they are done before the panel is (~14 us: about GPLE_CHOL_TILE_BUDGET = 800 tiles of 2-3 us on the CUs the
+	// free as long as they are done before the panel is (~14 us: a budget of about 800 tiles of 2-3 us on the CUs the
 	// panel leaves idle), so every outer block is made as wide as that budget allows at its first panel — the blocks widen as the
 	// trailing matrix shrinks (n = 4096: 832 + 1088 + 2176; below n ~ 2400 the whole matrix is one block), which also makes the
-	// K of the separate updates large.  GPLE_CHOL_OUTER = <width> forces equal blocks (0: a single one) for A/B runs.
+	// K of the separate updates large.
 	static const std::vector<int>& chol_block_bounds(int n)
 	{
-		static const int forced = [] {
-			const char* e = getenv("GPLE_CHOL_OUTER");
-			return e ? atoi(e) : -1;
-		}();
-		static const int budget_env = [] {
-			const char* e = getenv("GPLE_CHOL_TILE_BUDGET");
-			return e && atoi(e) > 0 ? atoi(e) : 0;
-		}();
 		// one launch per outer block: the tile tasks of a block are not bound to a panel's duration, wider blocks save trailing updates
 		// (n = 4096: 1.88 / 1.75 / 1.80 ms with 800 / 1600 / 2000; n = 8192: 8.80 / 8.43 / 8.57; one block up to n = 3648)
-		const int budget = budget_env ? budget_env : (chol_dag_scheme() ? 1600 : 800);
-		static const bool fused = [] {
-			const char* e = getenv("GPLE_CHOL_FUSED");
-			return e == nullptr || atoi(e) != 0;
-		}();
+		const int budget = chol_dag_scheme() ? 1600 : 800;
 		static std::mutex mu;
 		static std::map<long, std::vector<int>> cache;
 		std::lock_guard<std::mutex> lk(mu);
 		auto it = cache.find(layout_key(n));
 		if (it != cache.end()) return it->second;
 		std::vector<int> b{0};
-		if (forced >= 0 || !fused)
+		for (int J0 = 0; J0 < n;)
 		{
-			const int OB = forced >= NB ? forced / NB * NB : (forced < 0 && n >= 2048 ? 256 : 0);
-			if (OB)
-				for (int j = OB; j < n; j += OB) b.push_back(j);
+			// widest block whose first strip (nc column blocks right of the panel, nr row blocks below it) stays within the budget
+			const int nr = (n - J0) / NB - 1;
+			int nc = 0;
+			while (nc < nr && (nc + 1) * nr - (nc + 1) * nc / 2 <= budget) ++nc;
+			int w = (nc + 1) * NB;
+			if (w < 256) w = 256;
+			if (n - (J0 + w) < 256) w = n - J0; // no sliver at the end
+			J0 += w;
+			if (J0 < n) b.push_back(J0);
 		}
-		else
-			for (int J0 = 0; J0 < n;)
-			{
-				// widest block whose first strip (nc column blocks right of the panel, nr row blocks below it) stays within the budget
-				const int nr = (n - J0) / NB - 1;
-				int nc = 0;
-				while (nc < nr && (nc + 1) * nr - (nc + 1) * nc / 2 <= budget) ++nc;
-				int w = (nc + 1) * NB;
-				if (w < 256) w = 256;
-				if (n - (J0 + w) < 256) w = n - J0; // no sliver at the end
-				J0 += w;
-				if (J0 < n) b.push_back(J0);
-			}
 		b.push_back(n);
 		return cache.emplace(layout_key(n), std::move(b)).first->second;
 	}
@@ -1686,8 +1517,6 @@ namespace gple
 	static int chol_dag_max_blocks()
 	{
 		static const int v = [] {
-			if (const char* e = getenv("GPLE_CHOL_DAG_BLOCKS"))
-				if (atoi(e) >= 2) return atoi(e);
 			int dev = 0, cus = 0;
 			if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 2) cus = 64;
 			return cus; // one workgroup per CU: more would only queue behind the resident ones (the ticket order needs no particular number resident)
@@ -1764,10 +1593,6 @@ namespace gple
 			// n = 4096, 12.25 vs 11.16 at 8192; K = 256 is too short for that kernel's two-slab pipeline)
 			return launch_gemm(s, g, gemm_pick_tile(m, ncols, 1, true));
 		};
-		static const bool fused = [] {
-			const char* e = getenv("GPLE_CHOL_FUSED");
-			return e == nullptr || atoi(e) != 0;
-		}();
 		if (dag != nullptr)
 		{
 			// outer block by outer block — the marks are block boundaries too, so that a launch never continues sums another launch began —:
@@ -1792,13 +1617,11 @@ namespace gple
 				g.seq = static_cast<int>(bi);
 				// once the side stream is at work (from the first mark on) the launch leaves part of the chip to its GEMMs: a workgroup of this kernel
 				// holds 70 KB of LDS on its CU whether it works or waits, which halves the GEMM workgroups that fit beside it
-				static const int late_blocks = [] {
-					const char* e = getenv("GPLE_CHOL_DAG_LATE_BLOCKS");
-					return e ? atoi(e) : 64; // 0: no limit.  n = 4096: 1.85 / 1.85 / 1.79 / 1.81 ms with 256 / 128 / 64 / 32 workgroups
-				}();
+				// (n = 4096: 1.85 / 1.85 / 1.79 / 1.81 ms with 256 / 128 / 64 / 32 workgroups)
+				constexpr int LATE_BLOCKS = 64;
 				const bool side_busy = marks != nullptr && !marks->empty() && J0 >= marks->front();
 				const int all_blocks = dag->max_blocks >= 2 ? dag->max_blocks : chol_dag_max_blocks();
-				const int max_blocks = side_busy && late_blocks >= 2 ? std::min(late_blocks, all_blocks) : all_blocks;
+				const int max_blocks = side_busy ? std::min(LATE_BLOCKS, all_blocks) : all_blocks;
 				const int helpers = std::min(max_blocks - 1, g.nunits);
 				constexpr int LAST_STAMP = 11;
 				static const bool want_stamps = getenv("GPLE_CHOL_DAG_STAMPS") != nullptr;
@@ -1850,7 +1673,7 @@ namespace gple
 			}
 			return hipGetLastError();
 		}
-		bool pend = false; // the rank-64 update by the previous panel has not been applied yet (fused scheme: it rides in the next launch)
+		bool pend = false; // the rank-64 update by the previous panel has not been applied yet (it rides in the next launch)
 		for (int j0 = j_begin; j0 < j_end; j0 += NB)
 		{
 			size_t bi = 0;
@@ -1861,43 +1684,22 @@ namespace gple
 			const int below = m - NB;
 			const int ndt = below > 0 ? below / NB : 1;
 			const int strip = Jend - (j0 + NB); // columns of this block column right of the panel
-			if (fused)
+			// one launch: the panel (with the previous panel's update of its own columns, if pending) + the rest of that update
+			const int sy_nc = pend ? strip / NB : 0, sy_nr = pend ? below / NB : 0;
+			const int ntiles = sy_nc * sy_nr - sy_nc * (sy_nc - 1) / 2;
+			hipLaunchKernelGGL(potrf_step_kernel<false>, dim3(ndt + (ntiles + 3) / 4), dim3(512), 0, s, A, lda, T, ldt, info, j0, below, ndt, pend ? 1 : 0, sy_nc, sy_nr, uvec,
+				static_cast<long long*>(nullptr));
+			if (marks && std::find(marks->begin(), marks->end(), j0 + NB) != marks->end())
 			{
-				// one launch: the panel (with the previous panel's update of its own columns, if pending) + the rest of that update
-				const int sy_nc = pend ? strip / NB : 0, sy_nr = pend ? below / NB : 0;
-				const int ntiles = sy_nc * sy_nr - sy_nc * (sy_nc - 1) / 2;
-				hipLaunchKernelGGL(potrf_step_kernel<false>, dim3(ndt + (ntiles + 3) / 4), dim3(512), 0, s, A, lda, T, ldt, info, j0, below, ndt, pend ? 1 : 0, sy_nc, sy_nr, uvec,
-					static_cast<long long*>(nullptr));
-				if (marks && std::find(marks->begin(), marks->end(), j0 + NB) != marks->end())
-				{
-					const hipError_t e = (*on_final)(j0 + NB);
-					if (e != hipSuccess) return e;
-				}
-				pend = strip > 0;
-				if (pend && j0 + NB >= j_end) // nobody comes after this panel in this call: apply its update now
-				{
-					const hipError_t e = syrk_update(j0 + NB, below, strip, j0, NB);
-					if (e != hipSuccess) return e;
-					pend = false;
-				}
+				const hipError_t e = (*on_final)(j0 + NB);
+				if (e != hipSuccess) return e;
 			}
-			else
+			pend = strip > 0;
+			if (pend && j0 + NB >= j_end) // nobody comes after this panel in this call: apply its update now
 			{
-				// diagonal block + the rows below it: one launch, one workgroup per 64 panel rows (each re-does the diagonal block)
-				double* Tjj = T + j0 + static_cast<long>(j0) * ldt;
-				hipLaunchKernelGGL(potrf_diag_kernel<false>, dim3(ndt), dim3(256), 0, s, at(j0, j0), lda, Tjj, ldt, info, j0, static_cast<long long*>(nullptr),
-					at(j0 + (below > 0 ? NB : 0), j0), below, uvec);
-				if (marks && std::find(marks->begin(), marks->end(), j0 + NB) != marks->end())
-				{
-					const hipError_t e = (*on_final)(j0 + NB);
-					if (e != hipSuccess) return e;
-				}
-				// the rest of this block column: rows j0 + NB .. n, columns j0 + NB .. Jend
-				if (strip > 0)
-				{
-					const hipError_t e = syrk_update(j0 + NB, below, strip, j0, NB);
-					if (e != hipSuccess) return e;
-				}
+				const hipError_t e = syrk_update(j0 + NB, below, strip, j0, NB);
+				if (e != hipSuccess) return e;
+				pend = false;
 			}
 			// last panel of an outer block: everything right of the block column, once, with K = the block's width
 			if (j0 + NB == Jend && n - Jend > 0)
@@ -1906,13 +1708,6 @@ namespace gple
 				if (e != hipSuccess) return e;
 			}
 		}
-		return hipGetLastError();
-	}
-
-	// probe entry (probes/diag_probe.py): one instrumented launch of the diagonal-block kernel on device buffers
-	hipError_t debug_potrf_diag(hipStream_t s, const double* A, double* T, int* info, long long* stamps)
-	{
-		hipLaunchKernelGGL(potrf_diag_kernel<true>, dim3(1), dim3(256), 0, s, A, 64L, T, 64L, info, 0, stamps, const_cast<double*>(A), 0, static_cast<double*>(nullptr));
 		return hipGetLastError();
 	}
 
@@ -2025,14 +1820,7 @@ namespace gple
 	}
 
 	// Smallest n for which the inverse runs beside the factorisation on the side stream (an event hand-over costs the main stream ~6 us)
-	static int chol_overlap_min_n()
-	{
-		static const int v = [] {
-			const char* e = getenv("GPLE_CHOL_OVERLAP_MIN_N");
-			return e ? atoi(e) : 1024;
-		}();
-		return v;
-	}
+	constexpr int CHOL_OVERLAP_MIN_N = 1024;
 	// The inverse by block rows, beside the factorisation.  T = L^-1 row block by row block: once the panels of the column range
 	// [g0, g1) are done, everything its row block of T needs is final — T_gg from the merge tree over its diagonal blocks, then
 	// T(g, 0..g0) = -T_gg (L(g, 0..g0) T(0..g0, 0..g0)), two triangular-k GEMMs — so the side stream of the context works through the row
@@ -2076,9 +1864,9 @@ namespace gple
 	// Workspace of chol_inverse_factor, from the fork list actually in use (GPLE_CHOL_FORKS may put the forks anywhere): W = L(g, 0..g0) T(0..g0)
 	// of the widest row block product, the merge tree of the widest side job, the merge tree of the last row block (a tree over b columns needs
 	// b^2 / 4 doubles: count * s1 * s2 per level); the unsplit path uses one tree of n^2 / 4 at the front
-	// The row blocks of the inverse = where the side stream is handed finished columns: the fork points (GPLE_CHOL_MARKS=cuts: every outer block
-	// boundary of the one-launch scheme as well — a launch ends there anyway —, measured slower: the side stream's GEMMs run at a fraction of
-	// their speed beside a panel launch, and more, smaller ones do worse).  Empty: no overlap (small matrices).
+	// The row blocks of the inverse = where the side stream is handed finished columns: the fork points (adding every outer block boundary of
+	// the one-launch scheme — a launch ends there anyway — measured slower: 1.86 vs 1.83 ms at n = 4096, 9.15 vs 8.91 at 8192; the side stream's
+	// GEMMs run at a fraction of their speed beside a panel launch, and more, smaller ones do worse).  Empty: no overlap (small matrices).
 	static const std::vector<int>& chol_marks(int n)
 	{
 		static std::mutex mu;
@@ -2088,24 +1876,7 @@ namespace gple
 		if (it != cache.end()) return it->second;
 		std::vector<int> m;
 		const std::vector<int>& forks = chol_fork_points(n);
-		if (!chol_dag_inverse_inside(n) && n >= chol_overlap_min_n() && n / NB >= 4 && !forks.empty())
-		{
-			m = forks;
-			static const bool all_cuts = [] {
-				const char* e = getenv("GPLE_CHOL_MARKS"); // "cuts": every outer block boundary as well (A/B: 1.86 vs 1.83 ms at n = 4096, 9.15 vs 8.91 at 8192)
-				return e != nullptr && std::string(e) == "cuts";
-			}();
-			if (chol_dag_scheme() && all_cuts)
-			{
-				for (int b : chol_block_bounds(n))
-				{
-					bool keep = b > 0 && b < n;
-					for (int f : forks) keep = keep && std::abs(b - f) >= 256;
-					if (keep) m.push_back(b);
-				}
-				std::sort(m.begin(), m.end());
-			}
-		}
+		if (!chol_dag_inverse_inside(n) && n >= CHOL_OVERLAP_MIN_N && n / NB >= 4) m = forks;
 		return cache.emplace(layout_key(n), std::move(m)).first->second;
 	}
 	struct InvWork
@@ -2186,14 +1957,8 @@ namespace gple
 	{
 		// the side stream's GEMMs fill whatever the panel launches leave idle and must not be dispatched ahead of them: lowest priority
 		static const int side_prio = [] {
-			const char* ev = getenv("GPLE_CHOL_SIDE_PRIORITY"); // 0: default priority (A/B)
 			int lo = 0, hi = 0;
-			if ((ev && atoi(ev) == 0) || hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess) return 0;
-			return lo;
-		}();
-		static const bool probe = [] {
-			const char* ev = getenv("GPLE_CHOL_SIDE_PROBE"); // 0: take the first stream whatever queue it is on (A/B)
-			return ev == nullptr || atoi(ev) != 0;
+			return hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess ? lo : 0;
 		}();
 		constexpr int MAX_CANDIDATES = 8;
 		constexpr long long SPIN_TICKS = 10000; // 100 us of the 100 MHz wall clock
@@ -2208,11 +1973,6 @@ namespace gple
 			hipStream_t cand = nullptr;
 			if ((e = hipStreamCreateWithPriority(&cand, hipStreamNonBlocking, side_prio)) != hipSuccess) break;
 			ctx->side_attempts = attempt + 1;
-			if (!probe)
-			{
-				chosen = cand;
-				break;
-			}
 			// both spins start at ev[0]; ev[1] / ev[2] close the main / the candidate's one
 			float t_main = 0.f, t_side = 0.f, t_ref = 0.f;
 			bool ok = hipEventRecord(ev[0], main_stream) == hipSuccess && hipStreamWaitEvent(cand, ev[0], 0) == hipSuccess;

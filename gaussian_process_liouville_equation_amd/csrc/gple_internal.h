@@ -158,7 +158,7 @@ namespace gple
 	// diagonal are overwritten by the factor; the CHOL_NB diagonal blocks of A keep their (updated, unfactored) contents — every
 	// workgroup of a panel step reads its diagonal block, none may overwrite it — and the upper part is not referenced.  The
 	// diagonal blocks of the factor are never stored: on return T (n x n, ldt) holds inv(L_jj) in every diagonal block (full
-	// 64 x 64 blocks, zeros above the diagonal), i.e. the diagonal blocks of T = L^-1 (potrf_diag_kernel).  info (device int): 0 or 1 + index of the
+	// 64 x 64 blocks, zeros above the diagonal), i.e. the diagonal blocks of T = L^-1.  info (device int): 0 or 1 + index of the
 	// first non-positive pivot.
 	// the scheme of the factorisations this host thread issues while the object lives (scheme < 0: unchanged)
 	struct CholSchemeScope
@@ -170,7 +170,6 @@ namespace gple
 	};
 	hipError_t potrf_lower(hipStream_t s, double* A, long lda, int n, double* T, long ldt, int* info, double* uvec = nullptr, Ctx* ctx = nullptr,
 		double* tt = nullptr, double* pa = nullptr); // pa: 64 n doubles of scratch (without: a launch per panel); tt: n * n doubles — the launch also completes T = L^-1
-	hipError_t debug_potrf_diag(hipStream_t s, const double* A, double* T, int* info, long long* stamps);
 	void chol_layout(int n, std::vector<int>& bounds, std::vector<int>& forks, size_t& work_doubles);
 	hipError_t debug_potrf_step(hipStream_t s, double* A, long lda, double* T, long ldt, int* info, long long* stamps, int pend, int below);
 	// Completes T = L^-1 (lower) given its diagonal blocks; work: at least n*n/4 doubles.

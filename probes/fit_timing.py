@@ -1,5 +1,5 @@
 """Device time of one fit (GPLE_TIMER_FIT) at the sizes of the BASELINE configs; A/B knobs through the environment
-(GPLE_CHOL_OUTER=0|128|256|512, GPLE_CHOL_OVERLAP_MIN_N=...).  usage: python probes/fit_timing.py [real|complex|both] [N ...]"""
+(GPLE_CHOL_SCHEME=step, GPLE_CHOL_FORKS=...).  usage: python probes/fit_timing.py [real|complex|both] [N ...]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np

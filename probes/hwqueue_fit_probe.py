@@ -1,7 +1,7 @@
 """The fit's side stream and HIP's hardware queues (round 3).  Streams are bound to a small set of hardware queues (GPU_MAX_HW_QUEUES, default 4)
 in creation order; when the context's side stream lands on the queue of its main stream the block-row inverse no longer runs beside the panels
 — and with a low-priority side stream the fit at N = 4096 took 3.85 ms instead of 2.0 ms once an RCCL communicator had been created first.
-usage: python probes/hwqueue_fit_probe.py <streams created (and used) before the context> <comm: 0|1>   (env: GPLE_CHOL_SIDE_PRIORITY, GPU_MAX_HW_QUEUES)"""
+usage: python probes/hwqueue_fit_probe.py <streams created (and used) before the context> <comm: 0|1>   (env: GPU_MAX_HW_QUEUES)"""
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -41,5 +41,5 @@ for N in (1024, 4096):
         vals.append(api.timing(0)[0])
     out[N] = float(np.median(vals))
     api.close()
-sys.stderr.write(f"pre_streams={pre} comm={comm_on} side_prio={os.environ.get('GPLE_CHOL_SIDE_PRIORITY', 'low')} hwq={os.environ.get('GPU_MAX_HW_QUEUES', 'default')}: "
+sys.stderr.write(f"pre_streams={pre} comm={comm_on} hwq={os.environ.get('GPU_MAX_HW_QUEUES', 'default')}: "
                  f"fit N=1024 {out[1024]:.3f} ms, N=4096 {out[4096]:.3f} ms\n")

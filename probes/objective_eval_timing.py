@@ -1,5 +1,5 @@
 """One evaluation of the resident objective (opt.cpp:441-482: fit + predict of the 5N extra points) with and without gradient, real and complex,
-at the sizes of the configs.  GPLE_PREDICT_SKIP=0 restores the full contraction for the A/B.  usage: python probes/objective_eval_timing.py [N ...]"""
+at the sizes of the configs.  usage: python probes/objective_eval_timing.py [N ...]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np

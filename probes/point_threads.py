@@ -1,5 +1,5 @@
 """One-point predicts from several host threads on one fit (what the reference's TBB workers do, evolve.cpp:392-420): calls per
-second with 1, 4, 16 threads, with and without the combining front end (GPLE_POINT_COMBINE=0)."""
+second with 1, 4, 16 threads (one-point host predicts are combined across threads)."""
 import os, sys, threading, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np

@@ -1,6 +1,7 @@
-"""GPU: the diagonal-block kernel of the Cholesky panel step (csrc/gple_chol.hip, potrf_diag_kernel) on its own, through the
-library's diagnostic entry gple_debug_potrf_diag (not part of include/gple.h; probes/diag_probe.py prints its stage timings):
-T = inv(chol(A)) for one 64 x 64 block against numpy.  The kernel is otherwise covered through every fit (a6, a12)."""
+"""GPU: the Cholesky panel step (csrc/gple_chol.hip, potrf_step_kernel) on its own, through the library's diagnostic entry
+gple_debug_potrf_step (not part of include/gple.h; probes/step_probe.py prints its stage timings): T = inv(chol(A)) for one 64 x 64 block
+against numpy, one panel step of a larger matrix, a non-positive pivot; then the whole factorisation — its layouts, its two schemes, its
+side stream, and a give-up of the one-launch scheme.  The kernels are otherwise covered through every fit (a6, a12)."""
 import ctypes
 
 import numpy as np
@@ -10,22 +11,28 @@ pytestmark = pytest.mark.gpu
 
 
 def _run(gpu, A):
+    """inv(chol(A)) of a 64 x 64 block by one panel step (pend = 0, below = 0): A is block (1, 1) of a 128 x 128 matrix whose factored block
+    column 0 is [I; 0], so block (1, 1) of T is inv(chol(A))"""
     lib = gpu.lib
-    if not hasattr(lib, "gple_debug_potrf_diag"):
-        pytest.fail("libgple_hip.so lacks gple_debug_potrf_diag")
-    lib.gple_debug_potrf_diag.restype = ctypes.c_int
-    Af = np.asfortranarray(A, dtype=np.float64)
-    T = np.zeros((64, 64), order="F")
-    stamps = np.zeros(16, dtype=np.int64)
+    if not hasattr(lib, "gple_debug_potrf_step"):
+        pytest.fail("libgple_hip.so lacks gple_debug_potrf_step")
+    lib.gple_debug_potrf_step.restype = ctypes.c_int
+    K = np.zeros((128, 128), order="F")
+    K[:64, :64] = np.eye(64)
+    K[64:, 64:] = A
+    T = np.zeros((128, 128), order="F")
+    stamps = np.zeros(24, dtype=np.int64)
     ms = ctypes.c_float()
-    rc = lib.gple_debug_potrf_diag(gpu.ctx, Af.ctypes.data_as(ctypes.c_void_p), T.ctypes.data_as(ctypes.c_void_p),
-                                   stamps.ctypes.data_as(ctypes.c_void_p), 1, ctypes.byref(ms))
+    rc = lib.gple_debug_potrf_step(gpu.ctx, K.ctypes.data_as(ctypes.c_void_p), T.ctypes.data_as(ctypes.c_void_p), 0, 0,
+                                   stamps.ctypes.data_as(ctypes.c_void_p), 0, ctypes.byref(ms))
     assert rc == 0
-    return T
+    assert stamps[23] == 0  # info: every pivot positive
+    return T[64:, 64:]
 
 
 @pytest.mark.parametrize("seed,ridge", [(0, 0.5), (1, 1e-2), (2, 1e-6)])
-def test_diag_block_inverse_factor(gpu, seed, ridge):
+def test_diag_block_inverse_factor_by_the_panel_step(gpu, seed, ridge):
+    """T_jj = inv(chol(A_jj)) of one 64 x 64 block, as the panel step leaves it in T, against numpy"""
     rng = np.random.default_rng(seed)
     B = rng.standard_normal((64, 96))
     A = B @ B.T / 96 + ridge * np.eye(64)
@@ -39,7 +46,7 @@ def test_diag_block_inverse_factor(gpu, seed, ridge):
     assert np.abs(T - ref).max() <= 1e-10 * np.abs(ref).max() * max(1.0, np.linalg.cond(L) * 1e-4)
 
 
-def test_diag_block_of_a_gram_matrix(gpu):
+def test_diag_block_of_a_gram_matrix_by_the_panel_step(gpu):
     """the kind of block a fit hands over: squared-exponential Gram block with the sigma_n^2 ridge"""
     rng = np.random.default_rng(5)
     X = rng.normal(size=(64, 2)) * [0.7, 0.7]
@@ -217,11 +224,25 @@ def test_one_launch_per_outer_block_against_one_launch_per_panel():
         assert abs(a["e%d" % N] - b["e%d" % N]) <= 1e-7 * b["e%d" % N], N
 
 
-def test_work_queue_makes_progress_with_one_worker_workgroup():
+def test_work_queue_makes_progress_with_one_worker_workgroup(gpu):
     """the tile tasks of potrf_dag_kernel are handed out in dependency order from one counter, so the launch must complete with ANY number of its
-    workgroups running (the situation of a chip shared with other work): here one worker workgroup beside the spine (GPLE_CHOL_DAG_BLOCKS=2) —
-    4096 / 64 = 64 panels, four launches, about 60 ms instead of 2"""
-    _fit_in_own_process({"GPLE_CHOL_DAG_BLOCKS": "2"}, (1024, 4096))
+    workgroups running (the situation of a chip shared with other work): here one worker workgroup beside the spine (gple_debug_chol_knobs,
+    dag_blocks = 2) — 4096 / 64 = 64 panels, four launches, about 60 ms instead of 2"""
+    from gaussian_process_liouville_equation_amd import _capi as c
+    from tests import parity
+    _knobs(gpu, scheme=1, dag_blocks=2)
+    try:
+        for N in (1024, 4096):
+            X, y, _ = parity.synthetic_real(N, 8, 4242 + N)
+            fit = gpu.real_fit([1.0, 0.7086, 0.7056, 1e-2], X, y, 3)
+            assert fit.scalars["info"] == 0
+            K, W, v, ys = fit.get(c.R_KERNEL), fit.get(c.R_INVERSE), fit.get(c.R_INVLBL), fit.get(c.R_LABEL)
+            n1 = lambda A: np.abs(A).sum(axis=0).max()
+            assert n1(K @ W - np.eye(N)) <= 50 * N * parity.EPS * n1(K) * n1(W)
+            assert np.abs(K @ v - ys).max() <= 50 * N * parity.EPS * (n1(K) * np.abs(v).max() + np.abs(ys).max())
+            fit.release()
+    finally:
+        _knobs(gpu, scheme=2, dag_blocks=0)
 
 
 def test_repeated_fits_agree_bit_for_bit(gpu):
