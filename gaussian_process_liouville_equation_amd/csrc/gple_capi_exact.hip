@@ -1,0 +1,210 @@
+// gple_capi_exact.hip — C-ABI entry points of include/gple.h: the exact DVR and MQCLE solvers and the Wigner transform.
+#include <algorithm>
+#include <cmath>
+
+#include "gple_capi.h"
+
+extern "C"
+{
+	/* ---- exact DVR dynamics (gple_dvr.hip; schrodinger_equation/general.cpp of the reference) ---------------------------------------------- */
+	static bool dvr_model_ok(int num_pes, int model) { return (num_pes == 2 || num_pes == 3) && model >= 0 && model <= (num_pes == 3 ? 3 : 2); }
+	static bool dvr_grid_ok(size_t n_grids, double dx) { return n_grids >= 2 && n_grids <= (1u << 16) && dx > 0.0 && std::isfinite(dx); }
+
+	int gple_dvr_hamiltonian(gple_ctx* ctx, int num_pes, int model, int boundary, double x_first, double dx, size_t n_grids, double mass, unsigned flags,
+		double* H, double* energies, double* basis)
+	{
+		if (!ctx || !dvr_model_ok(num_pes, model) || (boundary != GPLE_DVR_REFLECTIVE && boundary != GPLE_DVR_PERIODIC) || !dvr_grid_ok(n_grids, dx) ||
+			!std::isfinite(x_first) || !(mass > 0.0))
+			return GPLE_ERR_BAD_ARG;
+		GPLE_OPEN(ctx);
+		const bool dev = flags & GPLE_IO_DEVICE;
+		const int n = static_cast<int>(n_grids);
+		const size_t dim = static_cast<size_t>(num_pes) * n_grids;
+		GPLE_CALL(ctx);
+		hipStream_t st = ctx->stream;
+		Staged h(ctx, dev), e(ctx, dev), b(ctx, dev);
+		Scratch sw(ctx);
+		GPLE_HIP(ctx, h.out(H, dim * dim));
+		GPLE_HIP(ctx, e.out(energies, n_grids * num_pes));
+		GPLE_HIP(ctx, b.out(basis, n_grids * num_pes * num_pes));
+		if (h.p) GPLE_HIP(ctx, launch_dvr_hamiltonian(st, num_pes, model, boundary, x_first, dx, n, mass, h.p));
+		if (e.p || b.p)
+		{
+			GPLE_HIP(ctx, sw.get(dvr_states_work_doubles(num_pes, n)));
+			GPLE_HIP(ctx, launch_dvr_states(st, num_pes, model, x_first, dx, n, e.p, b.p, sw.p));
+		}
+		for (Staged* o : {&h, &e, &b}) GPLE_HIP(ctx, o->back());
+		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
+		return GPLE_OK;
+	}
+
+	int gple_dvr_propagate(gple_ctx* ctx, int num_pes, size_t n_grids, const double* eigvec, const double* eigval, const double* psi0_or_c0, const double* times,
+		size_t T, const double* basis, unsigned flags, double* psi)
+	{
+		if (!ctx || (num_pes != 2 && num_pes != 3) || !dvr_grid_ok(n_grids, 1.0) || T > 4096 || (T && (!eigvec || !eigval || !psi0_or_c0 || !times || !psi)))
+			return GPLE_ERR_BAD_ARG;
+		GPLE_OPEN(ctx);
+		if (T == 0) return GPLE_OK;
+		const bool dev = flags & GPLE_IO_DEVICE;
+		const int n = static_cast<int>(n_grids);
+		const size_t dim = static_cast<size_t>(num_pes) * n_grids, ld = round_up(dim, 64);
+		GPLE_CALL(ctx);
+		hipStream_t st = ctx->stream;
+		Scratch work(ctx);
+		Staged e(ctx, dev), v(ctx, dev), t(ctx, dev), b(ctx, dev), o(ctx, dev);
+		GPLE_HIP(ctx, work.get(dvr_propagate_work_doubles(num_pes, n, static_cast<int>(T))));
+		// C into the zero-padded ld x ld block
+		GPLE_HIP(ctx, hipMemsetAsync(work.p, 0, ld * ld * sizeof(double), st));
+		GPLE_HIP(ctx, hipMemcpy2DAsync(work.p, ld * sizeof(double), eigvec, dim * sizeof(double), dim * sizeof(double), dim,
+			dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+		GPLE_HIP(ctx, e.in(eigval, dim));
+		GPLE_HIP(ctx, v.in(psi0_or_c0, 2 * dim));
+		GPLE_HIP(ctx, t.in(times, T));
+		GPLE_HIP(ctx, b.in(basis, n_grids * num_pes * num_pes));
+		GPLE_HIP(ctx, o.out(psi, 2 * dim * T));
+		GPLE_HIP(ctx, launch_dvr_propagate(st, num_pes, n, e.p, v.p, t.p, static_cast<int>(T), b.p, (flags & GPLE_DVR_PSI0) != 0, work.p, o.p));
+		GPLE_HIP(ctx, o.back());
+		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
+		return GPLE_OK;
+	}
+
+	int gple_wigner(gple_ctx* ctx, int num_pes, int boundary, size_t n_grids, double x_first, double dx, const double* p, size_t n_p, const double* psi,
+		size_t T, const double* energies, double mass, unsigned flags, double* phase, double* averages)
+	{
+		if (!ctx || (num_pes != 2 && num_pes != 3) || (boundary != GPLE_DVR_REFLECTIVE && boundary != GPLE_DVR_PERIODIC) || !dvr_grid_ok(n_grids, dx) ||
+			!std::isfinite(x_first) || n_p < 2 || n_p > (1u << 16) || T * num_pes * (num_pes + 1) / 2 > 65535 || (T && (!p || !psi)) ||
+			(averages && (!energies || !(mass > 0.0))))
+			return GPLE_ERR_BAD_ARG;
+		GPLE_OPEN(ctx);
+		if (T == 0 || (!phase && !averages)) return GPLE_OK;
+		const bool dev = flags & GPLE_IO_DEVICE;
+		const int n = static_cast<int>(n_grids), np = static_cast<int>(n_p);
+		const size_t dim = static_cast<size_t>(num_pes) * n_grids, pdoubles = 2 * T * num_pes * num_pes * n_grids * n_p;
+		GPLE_CALL(ctx);
+		hipStream_t st = ctx->stream;
+		Scratch table(ctx), avw(ctx), only_avg(ctx);
+		Staged pp(ctx, dev), ps(ctx, dev), en(ctx, dev), av(ctx, dev), P(ctx, dev);
+		GPLE_HIP(ctx, table.get(wigner_table_doubles(boundary, n, np)));
+		GPLE_HIP(ctx, pp.in(p, n_p));
+		GPLE_HIP(ctx, ps.in(psi, 2 * dim * T));
+		GPLE_HIP(ctx, en.in(averages ? energies : nullptr, n_grids * num_pes));
+		GPLE_HIP(ctx, av.out(averages, 3 * T));
+		GPLE_HIP(ctx, P.out(phase, pdoubles));
+		if (!phase) GPLE_HIP(ctx, only_avg.get(pdoubles)); // the averages alone: the distribution is formed all the same
+		double* const Pd = phase ? P.p : only_avg.p;
+		GPLE_HIP(ctx, launch_wigner_table(st, boundary, n, pp.p, np, dx, table.p));
+		timer_start(ctx, GPLE_TIMER_WIGNER);
+		GPLE_HIP(ctx, launch_wigner(st, num_pes, boundary, n, dx, table.p, np, ps.p, static_cast<int>(T), Pd));
+		timer_stop(ctx, GPLE_TIMER_WIGNER);
+		if (averages)
+		{
+			GPLE_HIP(ctx, avw.get(wigner_avg_work_doubles(num_pes, static_cast<int>(T))));
+			GPLE_HIP(ctx, launch_wigner_averages(st, num_pes, n, x_first, dx, pp.p, np, en.p, mass, Pd, static_cast<int>(T), avw.p, av.p));
+		}
+		GPLE_HIP(ctx, P.back());
+		GPLE_HIP(ctx, av.back());
+		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
+		return GPLE_OK;
+	}
+
+	/* ---- exact MQCLE dynamics (gple_mqcl.hip; liouville_equation/ of the reference) ------------------------------------------------------ */
+	static bool mqcl_size_ok(int num_pes, int model, size_t n) { return dvr_model_ok(num_pes, model) && n >= 4 && n <= 4096; }
+
+	// the per-x tables of gple_mqcl.hip from host or device x (tq: the time of one Q step, spectral: the FFT tables too)
+	static int mqcl_tables(gple_ctx* ctx, hipStream_t st, int num_pes, int model, const double* x, int n, double tq, bool spectral, Staged& xs,
+		Scratch& tables)
+	{
+		GPLE_HIP(ctx, xs.in(x, n));
+		GPLE_HIP(ctx, tables.get(mqcl_table_doubles(num_pes, n)));
+		GPLE_HIP(ctx, launch_mqcl_tables(st, num_pes, model, xs.p, n, tq, spectral, tables.p));
+		return GPLE_OK;
+	}
+
+	int gple_mqcl_transform(gple_ctx* ctx, int num_pes, int model, const double* x, size_t n_grids, int from, int to, unsigned flags, const double* rho_in,
+		double* rho_out)
+	{
+		if (!ctx || !mqcl_size_ok(num_pes, model, n_grids) || from < 0 || from > 2 || to < 0 || to > 2 || !x || !rho_in || !rho_out) return GPLE_ERR_BAD_ARG;
+		GPLE_OPEN(ctx);
+		const bool dev = flags & GPLE_IO_DEVICE;
+		const int n = static_cast<int>(n_grids);
+		const size_t doubles = 2 * static_cast<size_t>(num_pes) * num_pes * n_grids * n_grids;
+		GPLE_CALL(ctx);
+		hipStream_t st = ctx->stream;
+		Staged xs(ctx, dev), ri(ctx, dev), ro(ctx, dev);
+		Scratch tables(ctx);
+		GPLE_TRY(mqcl_tables(ctx, st, num_pes, model, x, n, 0.0, false, xs, tables));
+		GPLE_HIP(ctx, ri.in(rho_in, doubles));
+		GPLE_HIP(ctx, ro.out(rho_out, doubles));
+		GPLE_HIP(ctx, launch_mqcl_transform(st, num_pes, n, from, to, tables.p, ri.p, ro.p));
+		GPLE_HIP(ctx, ro.back());
+		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
+		return GPLE_OK;
+	}
+
+	int gple_mqcl_evolve(gple_ctx* ctx, int num_pes, int model, const double* x, const double* p, size_t n_grids, double mass, double length_x,
+		double length_p, double dt, size_t n_steps, unsigned flags, double* rho)
+	{
+		if (!ctx || !mqcl_size_ok(num_pes, model, n_grids) || !x || !p || !rho || !(mass > 0.0) || !std::isfinite(mass) || !(length_x > 0.0) ||
+			!std::isfinite(length_x) || !(length_p > 0.0) || !std::isfinite(length_p) || !std::isfinite(dt) || n_steps > (1ul << 40))
+			return GPLE_ERR_BAD_ARG;
+		GPLE_OPEN(ctx);
+		if (n_steps == 0) return GPLE_OK;
+		const bool dev = flags & GPLE_IO_DEVICE;
+		const int n = static_cast<int>(n_grids);
+		const size_t plane = n_grids * n_grids, doubles = 2 * static_cast<size_t>(num_pes) * num_pes * plane;
+		GPLE_CALL(ctx);
+		hipStream_t st = ctx->stream;
+		Staged xs(ctx, dev), pp(ctx, dev), r(ctx, dev);
+		Scratch tables(ctx), tr(ctx);
+		GPLE_TRY(mqcl_tables(ctx, st, num_pes, model, x, n, dt / 2.0, true, xs, tables));
+		GPLE_HIP(ctx, tr.get(2 * plane * (num_pes * (num_pes + 1) / 2)));
+		GPLE_HIP(ctx, pp.in(p, n_grids));
+		GPLE_HIP(ctx, r.inout(rho, doubles));
+		MqclEvolveArgs g{};
+		g.num_pes = num_pes, g.n = n, g.n_steps = static_cast<long>(n_steps), g.rho = r.p, g.transposed = tr.p, g.table = tables.p, g.p = pp.p;
+		g.mass = mass, g.length_x = length_x, g.length_p = length_p, g.dt = dt;
+		timer_start(ctx, GPLE_TIMER_MQCL);
+		GPLE_HIP(ctx, launch_mqcl_evolve(st, g));
+		timer_stop(ctx, GPLE_TIMER_MQCL);
+		GPLE_HIP(ctx, launch_mqcl_lower(st, num_pes, n, r.p));
+		GPLE_HIP(ctx, r.back());
+		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
+		return GPLE_OK;
+	}
+
+	int gple_mqcl_observe(gple_ctx* ctx, int num_pes, int model, const double* x, const double* p, size_t n_grids, double mass, double dx, double dp,
+		unsigned flags, const double* rho_dia, double* rho_adia, double* averages, double* populations)
+	{
+		if (!ctx || !mqcl_size_ok(num_pes, model, n_grids) || !x || !p || !rho_dia || !averages || !populations || !(mass > 0.0) || !std::isfinite(mass) ||
+			!std::isfinite(dx) || !std::isfinite(dp))
+			return GPLE_ERR_BAD_ARG;
+		GPLE_OPEN(ctx);
+		const bool dev = flags & GPLE_IO_DEVICE;
+		const int n = static_cast<int>(n_grids);
+		const size_t doubles = 2 * static_cast<size_t>(num_pes) * num_pes * n_grids * n_grids;
+		GPLE_CALL(ctx);
+		hipStream_t st = ctx->stream;
+		Staged xs(ctx, dev), pp(ctx, dev), r(ctx, dev), a(ctx, dev);
+		Scratch tables(ctx), work(ctx), outd(ctx);
+		GPLE_TRY(mqcl_tables(ctx, st, num_pes, model, x, n, 0.0, false, xs, tables));
+		GPLE_HIP(ctx, pp.in(p, n_grids));
+		GPLE_HIP(ctx, r.in(rho_dia, doubles));
+		GPLE_HIP(ctx, a.out(rho_adia, doubles));
+		GPLE_HIP(ctx, work.get(mqcl_observe_work_doubles(num_pes, n)));
+		GPLE_HIP(ctx, outd.get(3 + num_pes));
+		GPLE_HIP(ctx, launch_mqcl_observe(st, num_pes, n, tables.p, xs.p, pp.p, mass, dx * dp, r.p, a.p, work.p, outd.p));
+		if (dev)
+		{
+			GPLE_HIP(ctx, hipMemcpyAsync(averages, outd.p, 3 * sizeof(double), hipMemcpyDeviceToDevice, st));
+			GPLE_HIP(ctx, hipMemcpyAsync(populations, outd.p + 3, num_pes * sizeof(double), hipMemcpyDeviceToDevice, st));
+			return GPLE_OK;
+		}
+		double h[6];
+		GPLE_HIP(ctx, hipMemcpyAsync(h, outd.p, (3 + num_pes) * sizeof(double), hipMemcpyDeviceToHost, st));
+		GPLE_HIP(ctx, a.back());
+		GPLE_HIP(ctx, hipStreamSynchronize(st));
+		for (int k = 0; k < 3; ++k) averages[k] = h[k];
+		for (int k = 0; k < num_pes; ++k) populations[k] = h[3 + k];
+		return GPLE_OK;
+	}
+}

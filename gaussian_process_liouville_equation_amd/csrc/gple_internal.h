@@ -23,12 +23,12 @@ namespace gple
 
 	// ---- error plumbing ------------------------------------------------------------------------------------
 	struct Ctx;
-	int record_hip_error(Ctx* ctx, hipError_t e, const char* what, int line);
+	int record_hip_error(Ctx* ctx, hipError_t e, const char* what, const char* file, int line);
 #define GPLE_HIP(ctx, expr)                                                        \
 	do                                                                             \
 	{                                                                              \
 		hipError_t gple_e_ = (expr);                                               \
-		if (gple_e_ != hipSuccess) return gple::record_hip_error((ctx), gple_e_, #expr, __LINE__); \
+		if (gple_e_ != hipSuccess) return gple::record_hip_error((ctx), gple_e_, #expr, __FILE_NAME__, __LINE__); \
 	} while (0)
 #define GPLE_TRY(expr)                        \
 	do                                        \

@@ -28,7 +28,7 @@ namespace gple
 		const double a = abs_pred / sqrt(var);
 		return (3.0 * 2.0 - 2.0 * a - 1.0) * ((a - 1.0) * (a - 1.0)) / 1.0;
 	}
-	// the factorisation's info word in the fit's scalar block (gple_capi.hip, SDEV_INFO): negative = the one-launch scheme gave up, everything derived
+	// the factorisation's info word in the fit's scalar block (gple_capi.h, SDEV_INFO): negative = the one-launch scheme gave up, everything derived
 	// from the factor is NaN until the host has repeated it
 	__device__ __forceinline__ bool fit_gave_up(const double* s_dev) { return *reinterpret_cast<const int*>(s_dev + 31) < 0; }
 	// exp(x) for finite x <= 0 (the argument of a squared-exponential kernel), fp64, < 1 ulp:

@@ -321,7 +321,7 @@ namespace gple
 			}
 		}
 
-		// the fit's scalar block: [0] rescale factor, [31] info of the factorisation (an int in the double's slot; gple_capi.hip SDEV_INFO)
+		// the fit's scalar block: [0] rescale factor, [31] info of the factorisation (an int in the double's slot; gple_capi.h SDEV_INFO)
 		// PredictiveKernel epilogue (kernel.cpp:496-522)
 		__global__ void __launch_bounds__(256) predict_finish_real_kernel(const double* __restrict__ q, const double* __restrict__ mu, int M,
 			double self, const double* __restrict__ s_dev, const double* __restrict__ labels, double* __restrict__ mean,

@@ -129,7 +129,7 @@ def allgather_element_scalars(values, n_elements, width, group=None, device="cpu
 #     T_rank = sum over elements with weight > 0 of fit_ms(e) + sum over elements of predict_ms(e) * share(e, rank) + E * gather_ms
 # and the step takes max over ranks.  plan_elements builds three candidates and keeps the one with the smallest modelled step.
 
-DEAL_BLOCK = 128    # SHARD_BLOCK of csrc/gple_capi.hip
+DEAL_BLOCK = 128    # SHARD_BLOCK of csrc/gple_capi_sharded.hip
 DEAL_CYCLE = 64     # blocks per cycle of a hybrid plan's weights (8192 grid points: fine against a 512 x 512 grid's 2048 blocks)
 # measured on MI355X: fit(error + averages) by padded matrix size n, contraction rate of rownorm2_kernel, K* generation bandwidth
 FIT_MS_BY_N = {256: 0.093, 1024: 0.274, 2048: 0.536, 4096: 1.6, 8192: 8.35, 16384: 58.0}
@@ -156,7 +156,7 @@ def model_costs(kind, N, M):
 
 
 def deal_shares(M, weights, block=DEAL_BLOCK):
-    """points of every rank under the weighted deal of gple_*_predict_dealt (host arithmetic of deal_counts in csrc/gple_capi.hip)"""
+    """points of every rank under the weighted deal of gple_*_predict_dealt (host arithmetic of deal_counts in csrc/gple_capi_sharded.hip)"""
     w = [int(x) for x in weights]
     S = sum(w)
     nblocks = (M + block - 1) // block

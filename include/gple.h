@@ -36,12 +36,13 @@ extern "C" {
 #define GPLE_ERR_COLLECTIVE 5 /* RCCL could not be resolved or a collective failed (gple_ctx_last_error has the text) */
 #define GPLE_ERR_STATE 4 /* e.g. derivative output requested from a fit built without GPLE_CALC_DERIVATIVE; call on a destroyed context */
 /* The factorisation of a fit runs as ONE launch per block of panels whose workgroups hand tiles to each other through flags; every wait is bounded
- * (about a second), and a wave that gives up leaves the launch unfinished.  That never yields a wrong number: on the device everything derived
- * from the unfinished factor becomes NaN, and the first call on the fit that drains the stream (*_fit_create with a scalars struct,
- * *_fit_get_scalars, *_fit_get, a predict with host pointers or labels, the objective and NLML entry points) notices, repeats the
- * factorisation with one launch per panel (no waits between workgroups) and returns the correct result — the caller sees nothing but the delay.
- * GPLE_ERR_TIMEOUT is returned only (a) by such a draining call when OTHER calls had been enqueued on the fit before it (device pointers, no labels:
- * those never drain the stream) — their outputs are NaN, the fit is valid from here on, gple_ctx_last_error says how many to repeat; or
+ * (2^23 polls, about 5-8 s per waiting launch: gple_chol.hip), and a wave that gives up leaves the launch unfinished.  That never yields a wrong
+ * number: on the device everything derived from the unfinished factor becomes NaN, and the first call on the fit that drains the stream
+ * (*_fit_create with a scalars struct, *_fit_get_scalars, *_fit_get, a predict with host pointers or labels, the objective and NLML entry points)
+ * notices, repeats the factorisation with one launch per panel (no waits between workgroups) and returns the correct result — the caller sees
+ * nothing but the delay.  GPLE_ERR_TIMEOUT is returned only (a) by such a draining call when OTHER calls had been enqueued on the fit before it
+ * (device pointers, no labels: those never drain the stream) — the call's own outputs are correct, theirs are NaN, the fit is valid from here on,
+ * gple_ctx_last_error says how many to repeat; or
  * (b) when the repetition failed as well (it cannot give up: it has no waits). */
 #define GPLE_ERR_TIMEOUT 6
 

@@ -347,11 +347,13 @@ def test_a_give_up_of_the_one_launch_factorisation_is_recovered_bit_for_bit(cplx
         bad_api.close()
 
 
-def test_work_enqueued_before_the_give_up_was_noticed_is_nan_and_reported():
+@pytest.mark.parametrize("noticer", ["get_scalars", "host_predict", "fit_get", "predict_batch"])
+def test_work_enqueued_before_the_give_up_was_noticed_is_nan_and_reported(noticer):
     """A fit created without a scalars struct and a predict with DEVICE pointers only enqueue work: nobody has looked at the factorisation when the
     predict runs.  If it had given up, the predict's outputs must be NaN (never numbers from the unfinished factor), the next draining call on the fit
-    (gple_real_fit_get_scalars) must recover the fit AND say that earlier work has to be repeated (GPLE_ERR_TIMEOUT), and the repeated predict must
-    then equal the launch-per-panel result bit for bit."""
+    (`noticer`: gple_real_fit_get_scalars, a predict with host pointers, gple_real_fit_get, gple_predict_batch) must recover the fit, return its own outputs from the good
+    fit AND say that earlier work has to be repeated (GPLE_ERR_TIMEOUT), and the repeated predict must then equal the launch-per-panel result bit for
+    bit."""
     import torch
 
     import gaussian_process_liouville_equation_amd as pkg
@@ -379,9 +381,30 @@ def test_work_enqueued_before_the_give_up_was_noticed_is_nan_and_reported():
         api.synchronize()
         assert bool(torch.isnan(out).all()), "a predict on a given-up factor returned numbers"
         sc = c.RealFitScalars()
-        st = api.lib.gple_real_fit_get_scalars(f.handle, ctypes.byref(sc))
+        hp = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+        if noticer == "get_scalars":
+            st = api.lib.gple_real_fit_get_scalars(f.handle, ctypes.byref(sc))
+            own = {"info": sc.info, "error": sc.error, "purity": sc.purity}
+            want = {"info": 0, "error": ref["error"], "purity": ref["purity"]}
+        elif noticer == "host_predict":
+            mean, var, cut = np.empty(M), np.empty(M), np.empty(M)
+            st = api.lib.gple_real_predict(api.ctx, f.handle, hp(Xs), M, 0, None, hp(mean), hp(var), hp(cut), ctypes.byref(ps))
+            own = {"mean": mean.tobytes(), "var": var.tobytes(), "cut": cut.tobytes()}
+            want = {k: ref[k] for k in own}
+        elif noticer == "predict_batch":  # host points, every request of the one element: the whole batch is filled, then the status reports
+            rf = ref_api.real_fit(THETA_R, X, y, 3)
+            want = {"cut": ref_api.predict_batch([rf], Xs, np.zeros(M, dtype=np.int32)).tobytes()}
+            rf.release()
+            el, idx, res = c.Element(f.handle.value, None), np.zeros(M, dtype=np.int32), np.empty(2 * M)
+            st = api.lib.gple_predict_batch(api.ctx, ctypes.byref(el), 1, hp(Xs), idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), M, hp(res))
+            own = {"cut": res.tobytes()}
+        else:
+            v = np.empty(N)
+            st = api.lib.gple_real_fit_get(f.handle, c.R_INVLBL, 0, hp(v))
+            own, want = {"v": v.tobytes()}, {"v": ref["v"]}
         assert st == c.GPLE_ERR_TIMEOUT, st
         assert b"repeat" in api.lib.gple_ctx_last_error(api.ctx)
+        assert own == want  # the noticing call's own outputs: those of the recovered fit
         assert api.lib.gple_real_fit_get_scalars(f.handle, ctypes.byref(sc)) == 0  # the fit itself is good now
         assert sc.info == 0 and sc.error == ref["error"] and sc.purity == ref["purity"]
         assert predict() == 0
