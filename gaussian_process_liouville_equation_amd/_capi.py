@@ -163,6 +163,11 @@ class Points(C.Structure):
     _fields_ = [("r", C.POINTER(C.c_double)), ("rho", C.POINTER(C.c_double)), ("n", C.c_size_t)]
 
 
+class ReconPlane(C.Structure):
+    """gple_recon_plane: kernel, training points and weights K^-1 y of one real plane (N = 0: predicted as exactly 0)"""
+    _fields_ = [("x", C.c_double * 4), ("X", C.POINTER(C.c_double)), ("b", C.POINTER(C.c_double)), ("N", C.c_size_t)]
+
+
 class PredictScalars(C.Structure):
     _fields_ = [("error", C.c_double), ("error_derivative", C.c_double * 8)]
 
@@ -208,6 +213,7 @@ GPLE_SYMBOLS = [
     "complex_predict", "loose_function", "objective_create", "objective_eval", "objective_eval_part", "objective_release", "minimize_neldermead", "objective_minimize_neldermead", "minimize_direct_l", "objective_minimize_direct_l", "minimize_auglag_eq", "pes_adiabatic", "evolve", "evolve_n", "pes_adiabatic_n", "markov_chain", "markov_chain_trace", "nlml", "nlml_predict", "nlml_cross", "nlml_cross_predict",
     "dvr_hamiltonian", "dvr_propagate", "wigner",
     "mqcl_transform", "mqcl_evolve", "mqcl_observe",
+    "nlml_weights", "grid_survey", "grid_select", "grid_reconstruct",
 ]
 
 
@@ -383,7 +389,8 @@ class Api:
         self._check(self.lib.gple_ctx_enable_timing(self.ctx, int(on)))
 
     def timing(self, which):
-        """(last_ms, total_ms, count) of timer 0 = fit, 1 = predict call, 2 = fused predict kernel."""
+        """(last_ms, total_ms, count) of a gple_timer: 0 = fit, 1 = predict call, 2 = fused predict kernel, 3 = derivative GEMM, 4 = Wigner kernel, 5 = MQCLE
+        steps, 6 = the device work of the reconstruction entry points."""
         last, total, count = C.c_double(), C.c_double(), C.c_long()
         self.lib.gple_ctx_get_timing.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                                  C.POINTER(C.c_long)]
@@ -618,6 +625,105 @@ class Api:
         f.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.c_size_t, C.c_double, C.c_double, C.c_double, C.c_uint, _dp, _dp, _dp, _dp]
         self._check(f(self.ctx, int(num_pes), int(model), px, pp, n, float(mass), float(dx), float(dp), flags, pr, pa, pav, ppo))
         return adia, av, pops
+
+    # ---- reconstruction of a gridded density with the NLML GP (test/main_evolve.cpp; gple_nlml_weights / gple_grid_*) -------------------------
+    SURVEY_FIELDS = ("max", "min", "weight", "argmax", "population", "potential", "kinetic")
+
+    @staticmethod
+    def _grid_rho(rho, num_pes):
+        if hasattr(rho, "data_ptr"):
+            if rho.dim() != 4 or tuple(rho.shape[:2]) != (num_pes, num_pes) or str(rho.dtype) != "torch.complex128":
+                raise ValueError("rho must be a complex128 tensor of shape (num_pes, num_pes, nx, np)")
+            return rho
+        rho = np.ascontiguousarray(rho, dtype=np.complex128)
+        if rho.ndim != 4 or rho.shape[:2] != (num_pes, num_pes):
+            raise ValueError("rho must have shape (num_pes, num_pes, nx, np)")
+        return rho
+
+    def _like(self, ref, shape):
+        """an empty float64 output on the side `ref` lives on"""
+        if hasattr(ref, "data_ptr"):
+            import torch
+            return torch.empty(shape, dtype=torch.float64, device=ref.device)
+        return np.empty(shape)
+
+    def nlml_weights(self, x, X, y):
+        """gple_nlml_weights: b = K^-1 y of the NOCROSS kernel x = (w_d, w_g, a_x, a_p); numpy in -> numpy out, device tensors in -> device tensor out"""
+        x = _f64(x)
+        assert len(x) == 4
+        if not hasattr(X, "data_ptr"):
+            X, y = _points(X), _f64(y)
+        N = int(X.shape[0])
+        b = self._like(X, N)
+        (pX, py, pb), flags = self._mqcl_io(X, y, b)
+        f = self.lib.gple_nlml_weights
+        f.argtypes = [C.c_void_p, _dp, _dp, _dp, C.c_size_t, C.c_uint, _dp]
+        self._check(f(self.ctx, _ptr(x), pX, py, N, flags, pb))
+        return b
+
+    def grid_survey(self, num_pes, model, rho, x, p, mass, dx, dp):
+        """gple_grid_survey: (num_pes^2, 8) per real plane q = row * num_pes + col: max, min, sum |v|, row-major index of the first maximum above 0
+        (-1: none), and on diagonal planes population, potential and kinetic energy from the grid (SURVEY_FIELDS)"""
+        rho, x, p = self._grid_rho(rho, num_pes), self._mqcl_grid(x), self._mqcl_grid(p)
+        out = self._like(rho, (num_pes * num_pes, 8))
+        (pr, px, pp, po), flags = self._mqcl_io(rho, x, p, out)
+        f = self.lib.gple_grid_survey
+        f.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.c_size_t, _dp, C.c_size_t, C.c_double, C.c_double, C.c_double, C.c_uint, _dp]
+        self._check(f(self.ctx, int(num_pes), int(model), pr, px, int(x.shape[0]), pp, int(p.shape[0]), float(mass), float(dx), float(dp), flags, po))
+        return out
+
+    def grid_select(self, num_pes, rho, x, p, q, n_select, seed, uniform=False):
+        """gple_grid_select for plane q: (cells (n_select, 2) int32, X (n_select, 2), y (n_select,), K draws); device tensors in -> device tensors out"""
+        rho, x, p = self._grid_rho(rho, num_pes), self._mqcl_grid(x), self._mqcl_grid(p)
+        n_select = int(n_select)
+        X, y = self._like(rho, (n_select, 2)), self._like(rho, n_select)
+        if hasattr(rho, "data_ptr"):
+            import torch
+            cells = torch.empty((n_select, 2), dtype=torch.int32, device=rho.device)
+            pc = C.cast(cells.data_ptr(), C.POINTER(C.c_int))
+        else:
+            cells = np.empty((n_select, 2), dtype=np.int32)
+            pc = cells.ctypes.data_as(C.POINTER(C.c_int))
+        (pr, px, pp, pX, py), flags = self._mqcl_io(rho, x, p, X, y)
+        K = C.c_size_t(0)
+        f = self.lib.gple_grid_select
+        f.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.c_size_t, _dp, C.c_size_t, C.c_int, C.c_int, C.c_size_t, C.c_ulonglong, C.c_uint, C.POINTER(C.c_int), _dp, _dp,
+                      C.POINTER(C.c_size_t)]
+        self._check(f(self.ctx, int(num_pes), pr, px, int(x.shape[0]), pp, int(p.shape[0]), int(q), int(bool(uniform)), n_select, int(seed), flags, pc, pX, py,
+                      C.byref(K)))
+        return cells, X, y, K.value
+
+    def grid_reconstruct(self, num_pes, model, rho, x, p, mass, dx, dp, planes, scale=None, want_pred=True):
+        """gple_grid_reconstruct: planes = num_pes^2 entries (x (4,), X (N, 2), b (N,)) or None (the plane is predicted as 0), on the side rho lives
+        on; scale: num_pes^2 factors or None.  -> (pred (num_pes^2, nx, np) or None, sums (num_pes^2, 6): sum (c mu - v)^2, population, potential and
+        kinetic energy of c mu on diagonal planes, sum (c mu)^2, sum c mu v)"""
+        rho, x, p = self._grid_rho(rho, num_pes), self._mqcl_grid(x), self._mqcl_grid(p)
+        nq = num_pes * num_pes
+        if len(planes) != nq:
+            raise ValueError("planes needs num_pes^2 entries")
+        pred = self._like(rho, (nq, int(x.shape[0]), int(p.shape[0]))) if want_pred else None
+        sums = self._like(rho, (nq, 6))
+        arr, keep = (ReconPlane * nq)(), []
+        for k, pl in enumerate(planes):
+            if pl is None:
+                continue
+            xk, Xk, bk = pl
+            if not hasattr(Xk, "data_ptr"):
+                Xk, bk = _points(Xk), _f64(bk)
+            (pX, pb, _), _ = self._mqcl_io(Xk, bk, rho)  # raises unless the plane's arrays live where rho does
+            keep.append((Xk, bk))
+            arr[k].x = (C.c_double * 4)(*[float(v) for v in xk])
+            arr[k].X, arr[k].b, arr[k].N = pX, pb, int(Xk.shape[0])
+        sc = None if scale is None else _f64(scale)
+        if sc is not None and sc.shape != (nq,):
+            raise ValueError("scale needs num_pes^2 entries")
+        (pr, px, pp, ppred, ps), flags = self._mqcl_io(rho, x, p, pred, sums)
+        f = self.lib.gple_grid_reconstruct
+        f.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.c_size_t, _dp, C.c_size_t, C.c_double, C.c_double, C.c_double, C.POINTER(ReconPlane), _dp, C.c_uint,
+                      _dp, _dp]
+        self._check(f(self.ctx, int(num_pes), int(model), pr, px, int(x.shape[0]), pp, int(p.shape[0]), float(mass), float(dx), float(dp), arr, _ptr(sc), flags,
+                      ppred, ps))
+        return pred, sums
 
     def evolve_n(self, num_pes, fits, model, mass, dt, density, new_points=False):
         """gple_evolve_n: one tick for an N-level system; fits and density in the packing order (0,0), (1,0), (1,1), (2,0), ...;

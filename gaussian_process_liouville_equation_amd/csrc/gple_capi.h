@@ -261,4 +261,9 @@ namespace gple
 	// give-up bookkeeping of the one-launch factorisation (fits and the NLML path): a give-up noticed on `attempt` (0: the first factorisation,
 	// 1: its repetition with a launch per panel) is counted; GPLE_OK: repeat with a launch per panel, GPLE_ERR_TIMEOUT: the repetition gave up too
 	int note_give_up(gple_ctx* ctx, int attempt);
+	// the NLML path's shared front (gple_capi_objective.hip): Gram of x = (w_d, w_g, a, c, b), Cholesky, inverse factor and bvec = K^-1 y, enqueued;
+	// X / y are device arrays with dev.  nlml_gave_up: after the caller's synchronisation, with the info word copied to host_scalars[HS_NLML + 8]
+	int nlml_solve(gple_ctx* ctx, const double x[5], const double* X, const double* y, size_t N, Scratch& Xt, Scratch& yd, Scratch& T, Scratch& bvec,
+		Scratch& info, int* n_out, bool dev = false);
+	int nlml_gave_up(gple_ctx* ctx, int attempt, bool* again);
 } // namespace gple

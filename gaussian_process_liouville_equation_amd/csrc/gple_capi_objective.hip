@@ -159,12 +159,16 @@ extern "C"
 		return GPLE_OK;
 	}
 
+}
+
+namespace gple
+{
 	// ---- negative_log_marginal_likelihood / predict_phase (test/gpr.cpp:499-532, 654-706) -------------------------------
 	// shared: Gram, Cholesky, inverse factor, b = K^-1 y (labels are NOT rescaled on this path).  Enqueue only; `info` (device, one double's
 	// slot) receives the factorisation's info word and a negative one turns b into NaN (colpass_kernel), so that nothing derived from an
 	// unfinished factor looks like a number; the callers read the word back with their results and repeat the call with one launch per panel.
-	static int nlml_solve(gple_ctx* ctx, const double x[5], const double* X, const double* y, size_t N, Scratch& Xt, Scratch& yd, Scratch& T,
-		Scratch& bvec, Scratch& info, int* n_out)
+	int nlml_solve(gple_ctx* ctx, const double x[5], const double* X, const double* y, size_t N, Scratch& Xt, Scratch& yd, Scratch& T, Scratch& bvec,
+		Scratch& info, int* n_out, bool dev)
 	{
 		hipStream_t st = ctx->stream;
 		const int n = static_cast<int>(round_up(N, NPAD));
@@ -186,8 +190,8 @@ extern "C"
 		// (unlike a fit's, this T is cleared: trmv_lower below walks whole 256-column chunks of a row, the blocks above the diagonal 64-blocks
 		// included — a fit gets u = L^-1 y from the label row of its factorisation instead; 30 us at n = 4096)
 		GPLE_HIP(ctx, hipMemsetAsync(T.p, 0, static_cast<size_t>(n) * n * 8, st));
-		GPLE_HIP(ctx, copy_in(st, Xt.p, X, 2 * N, false));
-		GPLE_HIP(ctx, copy_in(st, yd.p, y, N, false));
+		GPLE_HIP(ctx, copy_in(st, Xt.p, X, 2 * N, dev));
+		GPLE_HIP(ctx, copy_in(st, yd.p, y, N, dev));
 		GPLE_HIP(ctx, launch_nlml_gram(st, Xt.p, static_cast<int>(N), n, x, L.p));
 		timer_start(ctx, GPLE_TIMER_FIT); // the factorisation + inverse factor: what the NLML workloads of bench.py price against the fp64 MFMA peak
 		GPLE_HIP(ctx, chol_inverse_factor(ctx, st, L.p, n, n, T.p, n, reinterpret_cast<int*>(info.p), work.p));
@@ -197,14 +201,17 @@ extern "C"
 		return GPLE_OK;
 	}
 	// after the caller's synchronisation: did the factorisation of this attempt give up?  (the word was copied to host_scalars[HS_NLML + 8])
-	static int nlml_gave_up(gple_ctx* ctx, int attempt, bool* again)
+	int nlml_gave_up(gple_ctx* ctx, int attempt, bool* again)
 	{
 		int info_i;
 		std::memcpy(&info_i, ctx->host_scalars + HS_NLML + 8, sizeof(int));
 		*again = info_i < 0;
 		return *again ? note_give_up(ctx, attempt) : GPLE_OK;
 	}
+} // namespace gple
 
+extern "C"
+{
 	// n = 4: (w_d, w_g, a_x, a_p), the NOCROSS build; n = 5: (w_d, w_g, a, c, b), the default build's lower-triangular weight matrix
 	static void nlml_params(const double* x, size_t n, double x5[5])
 	{

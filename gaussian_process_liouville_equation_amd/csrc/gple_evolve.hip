@@ -9,6 +9,7 @@
 // per Monte-Carlo step one proposal kernel (counter-based Philox4x32-10 stream: the reference's clock-seeded, thread-shared
 // mt19937 of mc.cpp:17 is not reproducible), one batched predict, one accept kernel.
 #include "gple_kernels.h"
+#include "gple_philox.h"
 
 namespace gple
 {
@@ -285,23 +286,6 @@ namespace gple
 			out[6 * i] = a.e0, out[6 * i + 1] = a.e1, out[6 * i + 2] = a.f00, out[6 * i + 3] = a.f10, out[6 * i + 4] = a.f11, out[6 * i + 5] = a.nac01;
 		}
 
-		// ---- Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11) -------------------
-		__device__ __forceinline__ void philox4x32(unsigned (&c)[4], unsigned k0, unsigned k1)
-		{
-#pragma unroll
-			for (int round = 0; round < 10; ++round)
-			{
-				const unsigned long long p0 = 0xD2511F53ull * c[0], p1 = 0xCD9E8D57ull * c[2];
-				const unsigned hi0 = static_cast<unsigned>(p0 >> 32), lo0 = static_cast<unsigned>(p0), hi1 = static_cast<unsigned>(p1 >> 32), lo1 = static_cast<unsigned>(p1);
-				const unsigned n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
-				c[0] = n0, c[1] = lo1, c[2] = n2, c[3] = lo0;
-				k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
-			}
-		}
-		__device__ __forceinline__ double unit53(unsigned hi, unsigned lo)
-		{
-			return static_cast<double>(((static_cast<unsigned long long>(hi) << 32) | lo) >> 11) * (1.0 / 9007199254740992.0);
-		}
 		// three uniforms in [0, 1) for (walker, step): counter (walker, step, block, 0), key = seed
 		__device__ __forceinline__ void philox_uniform3(unsigned walker, unsigned step, unsigned long long seed, double& u0, double& u1, double& u2)
 		{

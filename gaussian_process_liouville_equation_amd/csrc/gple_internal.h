@@ -105,10 +105,10 @@ namespace gple
 		bool timing = false;
 		std::vector<hipEvent_t> ev_free;
 		std::vector<TimedSpan> pending;
-		static constexpr int NTIMERS = 6; // gple_timer
+		static constexpr int NTIMERS = 7; // gple_timer
 		TimedSpan open_span[NTIMERS] = {};
-		double t_last[NTIMERS] = {0, 0, 0, 0, 0, 0}, t_total[NTIMERS] = {0, 0, 0, 0, 0, 0};
-		long t_count[NTIMERS] = {0, 0, 0, 0, 0, 0};
+		double t_last[NTIMERS] = {}, t_total[NTIMERS] = {};
+		long t_count[NTIMERS] = {};
 	};
 	// one interval per contraction launch (GPLE_TIMER_PREDICT_KERNEL)
 	void chunk_timer_start(Ctx* c);

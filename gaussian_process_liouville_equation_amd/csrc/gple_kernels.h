@@ -281,4 +281,49 @@ namespace gple
 	size_t mqcl_observe_work_doubles(int num_pes, int n);
 	hipError_t launch_mqcl_observe(hipStream_t s, int num_pes, int n, const double* tables, const double* x, const double* p, double mass, double dxdp,
 		const double* rho, double* adia, double* work, double* out);
+
+	// ---- reconstruction of a gridded density (gple_recon.hip; test/gpr.cpp): num_pes = 2 or 3, rho: num_pes^2 x nx x np (re, im) ----
+	constexpr int RECON_SURVEY_BLOCKS = 64, RECON_SURVEY_VALUES = 7; // row blocks of the survey, values per plane and block
+	constexpr int RECON_MAX_PLANES = 9, RECON_MAX_N = 4096, RECON_SUMS = 6;
+	constexpr int RECON_SCAN_CHUNK = 4096; // cells per workgroup of the selection's running sum
+	size_t recon_survey_work_doubles(int num_pes);
+	hipError_t launch_recon_survey(hipStream_t s, int num_pes, int model, const double* rho, const double* x, int nx, const double* p, int np, double mass,
+		double dxdp, double* work, double* out);
+	// selection: running sum of |v| of plane q (within[c]: inclusive within its chunk; offsets[k]: sum of the chunks before k, offsets[nchunks] = W;
+	// counts[nchunks]: cells of non-zero weight), the draws [k0, k0 + nk) with first-occurrence marking in mark (cells ints, INT_MAX = never drawn),
+	// the count (state: [0] distinct cells so far, [1] K or 0; chosen: the first n_select distinct cells in draw order) and the gather
+	long recon_scan_chunks(long cells);
+	hipError_t launch_recon_scan(hipStream_t s, int num_pes, const double* rho, long cells, int q, double* within, double* offsets, long long* count);
+	hipError_t launch_recon_draw(hipStream_t s, const double* within, const double* offsets, long cells, int nx, int np, int q, int uniform,
+		unsigned long long seed, unsigned k0, unsigned nk, int* draw_cell, int* mark);
+	hipError_t launch_recon_count(hipStream_t s, const int* draw_cell, const int* mark, unsigned k0, unsigned nk, int n_select, int* state, int* chosen);
+	hipError_t launch_recon_gather(hipStream_t s, int num_pes, const double* rho, const double* x, int nx, const double* p, int np, int q, const int* chosen,
+		int n_select, int* cells, double* X, double* y);
+	// reconstruction: the two tables of every plane, the MFMA contraction with its epilogue (one record per tile) and the final sum
+	struct ReconPlane
+	{
+		const double* X; // 2 N interleaved
+		const double* b; // N
+		double* Ax;      // rows_x x Npad, k contiguous
+		double* Ep;      // rows_p x Npad
+		double coef, ax, ap; // c w_g^2, a_x, a_p
+		int N, Npad;
+	};
+	struct ReconArgs
+	{
+		ReconPlane plane[RECON_MAX_PLANES];
+		const double* rho;
+		const double* x;
+		const double* p;
+		double* energy; // nx x num_pes adiabatic energies
+		double* pred;   // nullable
+		double* records;
+		double* sums;
+		double mass, dxdp;
+		int num_pes, model, nx, np, rows_x, rows_p;
+	};
+	size_t recon_record_doubles(int num_pes, int nx, int np);
+	hipError_t launch_recon_tables(hipStream_t s, const ReconArgs& g);
+	hipError_t launch_recon_contract(hipStream_t s, const ReconArgs& g);
+	hipError_t launch_recon_final(hipStream_t s, const ReconArgs& g);
 } // namespace gple

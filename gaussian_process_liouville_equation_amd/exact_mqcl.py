@@ -87,9 +87,11 @@ def stop_criterion(x_bar, last_x, p0, x0):
     return x_bar > 0 and ((x_bar - last_x) * p0 < 0 or x_bar > -x0)
 
 
-def run(api, model=DAC, num_pes=2, ln_energy=0.0, out_dir=None, write_phase="text", max_outputs=None, log=None, **setup_kw):
+def run(api, model=DAC, num_pes=2, ln_energy=0.0, out_dir=None, write_phase="text", max_outputs=None, log=None, on_output=None, **setup_kw):
     """The loop of main.cpp:117-337.  write_phase: "text" (phase.txt), "npy" (phase_<k>.npy per output time) or None; out_dir None writes no
-    file.  max_outputs caps the output times after t = 0.  Returns a dict with the setup, per-output records, the final state and the final line."""
+    file.  max_outputs caps the output times after t = 0.  on_output(t, rho_adia) (optional) is called at every output time, t = 0 included, with
+    the adiabatic state that phase.txt holds (reconstruct.run_mqcl hangs the GP reconstruction on it).  Returns a dict with the setup,
+    per-output records, the final state and the final line."""
     s = setup(ln_energy, **setup_kw)
     n, x, p, mass, dx, dp = s["n_grids"], s["x"], s["p"], s["mass"], s["dx"], s["dp"]
     say = log or (lambda *_: None)
@@ -117,10 +119,15 @@ def run(api, model=DAC, num_pes=2, ln_energy=0.0, out_dir=None, write_phase="tex
         elif write_phase == "npy":
             np.save(os.path.join(out_dir, f"phase_{len(records) - 1}.npy"), adia)
 
+    def emit_and_tell(t, adia, av, pops):
+        emit(t, adia, av, pops)
+        if on_output is not None:
+            on_output(t, adia)
+
     stopped = False
     try:
         av, pops = host_observe(rho, energies, x, p, mass, dx, dp)
-        emit(0.0, rho, av, pops)
+        emit_and_tell(0.0, rho, av, pops)
         last_x = av[1]
         rho = api.mqcl_transform(num_pes, model, x, rho, ADIABATIC, DIABATIC)       # main.cpp:185
         n_out = s["total_step"] // s["output_step"]
@@ -131,7 +138,7 @@ def run(api, model=DAC, num_pes=2, ln_energy=0.0, out_dir=None, write_phase="tex
             rho = api.mqcl_evolve(num_pes, model, x, p, rho, mass, s["length_x"], s["length_p"], s["dt"], s["output_step"])
             t = k * s["output_step"] * s["dt"]                                        # main.cpp:265
             adia, av, pops = api.mqcl_observe(num_pes, model, x, p, rho, mass, dx, dp)
-            emit(t, adia, av, pops)
+            emit_and_tell(t, adia, av, pops)
             if stop_criterion(av[1], last_x, s["p0"], s["x0"]):
                 stopped = True
                 rho = adia                                                            # the loop breaks with rho adiabatic (main.cpp:266, 305)

@@ -1,0 +1,339 @@
+"""Reconstruction of an exact phase-space density with the NLML GP: the loop body of the reference's test/main_evolve.cpp:56-179 for one
+state, on the library's device entry points (gple_grid_survey, gple_grid_select, gple_nlml, gple_nlml_weights, gple_grid_reconstruct;
+DESIGN.md §13).
+
+    set_initial_value()           gpr.cpp:113-195: bounds and start values of the hyper-parameters (w_d, w_g, a_x, a_p) of every plane
+    is_small()                    gpr.cpp:197-210 on the survey's max / min
+    optimize()                    gpr.cpp:535-643: Nelder-Mead on the NLML value, then one projected-BFGS pass on value + gradient
+    population_from_gpr() ...     gpr.cpp:715-911 (NOCROSS branches), host numpy on b = K^-1 y
+    obey_conservation()           gpr.cpp:913-992: the factors of the diagonal planes
+    reconstruct()                 survey -> is_small -> select -> optimise -> weights -> reconstruct -> obey_conservation -> reconstruct(scale)
+    run_mqcl()                    the exact MQCLE run of exact_mqcl.run with a reconstruction at every output time; log.txt, choose.txt, sim.txt
+
+The state is num_pes^2 real planes (SuperMatrix, test/io.cpp:25-72): plane q = row * num_pes + col is Re rho_ii, Re rho_ij (row < col) or
+Im rho_ij (row > col)."""
+import ctypes as C
+import math
+import os
+import time
+
+import numpy as np
+
+from . import _capi, exact_mqcl
+from .exact import DAC, fmt
+
+SMALL = 1e-2                       # is_very_small_everywhere, gpr.cpp:200
+DIAG_MIN, DIAG_MAX = 1e-8, 1e-5    # gpr.cpp:138-139
+GAUSS_MIN, GAUSS_MAX = 1e-4, 1.0   # gpr.cpp:140-141
+XTOL_ABS, INITIAL_STEP = 1e-10, 0.5  # gpr.cpp:592-596
+DBL_MAX = float(np.finfo(np.float64).max)
+
+
+class State:
+    """What stays the same from one output time to the next: the grid, the model, dx and dp as the experiment defines them
+    ((x[nx - 1] - x[0]) / nx, main_evolve.cpp:23) and the device copies of the grid for states that live on the device"""
+
+    def __init__(self, api, num_pes, model, x, p, mass):
+        self.num_pes, self.model, self.mass = int(num_pes), int(model), float(mass)
+        self.x, self.p = np.ascontiguousarray(x, dtype=np.float64), np.ascontiguousarray(p, dtype=np.float64)
+        self.dx, self.dp = (self.x[-1] - self.x[0]) / len(self.x), (self.p[-1] - self.p[0]) / len(self.p)
+        self._dev = None
+
+    def grid_like(self, rho):
+        """(x, p) on the side rho lives on"""
+        if not hasattr(rho, "data_ptr"):
+            return self.x, self.p
+        if self._dev is None:
+            import torch
+            self._dev = (torch.from_numpy(self.x).to(rho.device), torch.from_numpy(self.p).to(rho.device))
+        return self._dev
+
+
+def _host(api, a):
+    """a result on the host; device results are complete once the context's stream has drained (the library's calls with device pointers are
+    asynchronous on its own stream, which torch's copies do not wait for)"""
+    if not hasattr(a, "data_ptr"):
+        return np.asarray(a)
+    api.synchronize()
+    return a.cpu().numpy()
+
+
+def is_small(survey):
+    """gpr.cpp:197-210: max < 1e-2 and min > -1e-2, per plane"""
+    return (survey[:, 0] < SMALL) & (survey[:, 1] > -SMALL)
+
+
+def set_initial_value(survey, x, p, num_pes):
+    """gpr.cpp:113-195 -> (lower, upper, start), each (num_pes^2, 4) in the order (w_d, w_g, a_x, a_p): sigma_p = p[argmax of plane 0] / 20,
+    sigma_x = 0.5 / sigma_p; the ARD weights start at the inverse widths and are bounded below by the inverse box lengths, unbounded above"""
+    arg = int(survey[0, 3])
+    if arg < 0:
+        raise ValueError("plane (0, 0) has no value above 0: the reference's start values are undefined there (gpr.cpp:119-136)")
+    sigma_p = p[arg % len(p)] / 20.0
+    sigma_x = 0.5 / sigma_p
+    nq = num_pes * num_pes
+    lower = np.tile([DIAG_MIN, GAUSS_MIN, 1.0 / (x.max() - x.min()), 1.0 / (p.max() - p.min())], (nq, 1))
+    upper = np.tile([DIAG_MAX, GAUSS_MAX, DBL_MAX, DBL_MAX], (nq, 1))
+    start = np.tile([DIAG_MIN, GAUSS_MAX, 1.0 / sigma_x, 1.0 / sigma_p], (nq, 1))
+    return lower, upper, start
+
+
+def _options(maxeval):
+    # NLopt with set_xtol_abs alone (gpr.cpp:592-596): every other tolerance off
+    return _capi.OptOptions(0.0, 0.0, XTOL_ABS, 0.0, INITIAL_STEP, int(maxeval or 0))
+
+
+def optimize(api, X, y, start, lower, upper, maxeval=0):
+    """gpr.cpp:535-643 for one plane: the library's Nelder-Mead on the NLML value, then its augmented-Lagrangian search without constraints
+    (one projected-BFGS pass) on value + gradient, from the first search's minimiser.  gple_nlml keeps the reference's half gradient on the two
+    kernel weights (gpr.cpp:425, 432): they are doubled here.  -> (hyper-parameters, NLML there, evaluations)"""
+    lib = api.lib
+    dp_ = _capi._dp
+    count = [0]
+
+    def value(xs, want_grad):
+        count[0] += 1
+        v, g = api.nlml(np.array(xs), X, y, want_grad=want_grad)
+        if not math.isfinite(v):
+            v = DBL_MAX
+        if g is not None:
+            g = np.where(np.isfinite(g), g, 0.0)
+            g[:2] *= 2.0
+        return v, g
+
+    def f_cb(n, xp, gp, data):
+        v, g = value([xp[i] for i in range(n)], bool(gp))
+        if gp:
+            for i in range(n):
+                gp[i] = g[i]
+        return v
+
+    cb = _capi.OBJECTIVE_FN(f_cb)
+    hc = _capi.CONSTRAINT_FN(lambda m, rp, n, xp, gp, data: None)
+    xv, lb, ub = _capi._f64(start).copy(), _capi._f64(lower), _capi._f64(upper)
+    f, ne = C.c_double(), C.c_int()
+    opt = _options(maxeval)
+    lib.gple_minimize_neldermead.argtypes = [_capi.OBJECTIVE_FN, C.c_void_p, C.c_uint, dp_, dp_, C.POINTER(_capi.OptOptions), dp_, dp_, C.POINTER(C.c_int)]
+    st = lib.gple_minimize_neldermead(cb, None, 4, _capi._ptr(lb), _capi._ptr(ub), C.byref(opt), _capi._ptr(xv), C.cast(C.byref(f), dp_), C.byref(ne))
+    if st != _capi.GPLE_OK:
+        raise _capi.GpleError(f"gple_minimize_neldermead: status {st}")
+    lib.gple_minimize_auglag_eq.argtypes = [_capi.OBJECTIVE_FN, C.c_void_p, _capi.CONSTRAINT_FN, C.c_void_p, C.c_uint, C.c_uint, dp_, dp_,
+                                            C.POINTER(_capi.OptOptions), dp_, dp_, C.POINTER(C.c_int)]
+    st = lib.gple_minimize_auglag_eq(cb, None, hc, None, 0, 4, _capi._ptr(lb), _capi._ptr(ub), C.byref(opt), _capi._ptr(xv), C.cast(C.byref(f), dp_), C.byref(ne))
+    if st != _capi.GPLE_OK:
+        raise _capi.GpleError(f"gple_minimize_auglag_eq: status {st}")
+    return xv, value(xv, False)[0], count[0]  # "Best Combination": the value once more at the result (gpr.cpp:633)
+
+
+def population_from_gpr(hyper, b):
+    """gpr.cpp:715-762, NOCROSS: (2 pi)^Dim w_g^2 / (a_x a_p) sum b, Dim = 1"""
+    return 2.0 * math.pi * hyper[1] ** 2 / (hyper[2] * hyper[3]) * float(np.sum(b))
+
+
+def kinetic_energy_from_gpr(hyper, X, b, mass):
+    """gpr.cpp:853-911, NOCROSS: the same coefficient times sum (P_i^2 + a_p^-2) b_i / 2 mass"""
+    return 2.0 * math.pi * hyper[1] ** 2 / (hyper[2] * hyper[3]) * float(np.dot(X[:, 1] ** 2 + hyper[3] ** -2, b)) / 2.0 / mass
+
+
+def potential_energy_from_gpr(api, num_pes, model, level, hyper, X, b, step_divisor=16):
+    """gpr.cpp:765-841: the integral of E_level(x) rho(x) with rho(x) = w_g^2 sqrt(2 pi) / a_p sum b_i exp(-(a_x (x - X_i))^2 / 2).  The reference
+    integrates with Boost's Bulirsch-Stoer after x = (1 - t) / t; here: the trapezoid rule on a uniform grid of step 1 / (step_divisor a_x) — never
+    above 1 / step_divisor, so that a kernel much wider than the potential's features does not under-sample the energy — over
+    [min X - 40 / a_x, max X + 40 / a_x], beyond which every term is below exp(-800).  The rule converges geometrically for this integrand."""
+    ax = float(hyper[2])
+    h = min(1.0 / (step_divisor * ax), 1.0 / step_divisor)
+    lo, hi = float(X[:, 0].min()) - 40.0 / ax, float(X[:, 0].max()) + 40.0 / ax
+    n = int(math.ceil((hi - lo) / h)) + 1
+    xs = lo + h * np.arange(n)
+    energy = api.pes_adiabatic_n(num_pes, model, xs)[0][:, level]
+    total = 0.0
+    for i0 in range(0, n, 8192):  # bounded memory: 8192 x N exponentials at a time
+        d = ax * (xs[i0:i0 + 8192, None] - X[None, :, 0])
+        total += float(np.dot(energy[i0:i0 + 8192], np.exp(-0.5 * d * d) @ b))
+    return hyper[1] ** 2 * math.sqrt(2.0 * math.pi) / hyper[3] * total * h
+
+
+def obey_conservation(population, energy, small_diag, initial_energy):
+    """gpr.cpp:913-992 on the from-parameters population and energy of the diagonal planes (arrays over the levels; small_diag: the levels
+    that are 0 everywhere): one level -> 1 / population; more -> the 2 x 2 system [sum population; sum energy] of the first half and the second
+    half of the non-small levels = [1; initial energy].  -> (factor per level, singular); a singular system leaves every factor at 1"""
+    levels = [i for i in range(len(population)) if not small_diag[i]]
+    factors = np.ones(len(population))
+    if not levels:
+        return factors, False
+    if len(levels) == 1:
+        if population[levels[0]] == 0.0 or not math.isfinite(population[levels[0]]):
+            return factors, True
+        factors[levels[0]] = 1.0 / population[levels[0]]
+        return factors, False
+    half = len(levels) // 2
+    A = np.zeros((2, 2))
+    for k, i in enumerate(levels):
+        A[0, 0 if k < half else 1] += population[i]
+        A[1, 0 if k < half else 1] += energy[i]
+    det = A[0, 0] * A[1, 1] - A[0, 1] * A[1, 0]
+    if not np.all(np.isfinite(A)) or abs(det) <= 1e-14 * (abs(A[0, 0] * A[1, 1]) + abs(A[0, 1] * A[1, 0])):
+        return factors, True
+    c = np.linalg.solve(A, np.array([1.0, initial_energy]))
+    for k, i in enumerate(levels):
+        factors[i] = c[0 if k < half else 1]
+    return factors, False
+
+
+def reconstruct(api, state, rho, n_points=200, seed=0, maxeval=0, start=None, initial_energy=None, keep_pred=False, log=None):
+    """One pass of main_evolve.cpp:56-179 on the adiabatic state rho ((num_pes, num_pes, nx, np) complex; numpy, or a torch tensor on the
+    GPU, which then never leaves it).  start: the previous output time's hyper-parameters (main_evolve.cpp:94), default set_initial_value;
+    initial_energy: the conserved energy (main_evolve.cpp:48), default this state's own; maxeval caps each of the two searches (0: the
+    library's defaults).  Returns the record of log.txt and more: nlml, hyper (nq, 4), mse_before / mse_after (nq), factors (nq), singular,
+    is_small (nq), per level exact / grid / gpr population, potential and kinetic energy before and after, features / labels / cells per
+    plane, draws, sums_before / sums_after (nq, 6), seconds per phase, and with keep_pred the two predictions (nq, nx, np) on the host."""
+    num_pes, model, mass, dx, dp = state.num_pes, state.model, state.mass, state.dx, state.dp
+    nq = num_pes * num_pes
+    x, p = state.grid_like(rho)
+    say = log or (lambda *_: None)
+    clock = {}
+    t0 = time.perf_counter()
+    survey = _host(api, api.grid_survey(num_pes, model, rho, x, p, mass, dx, dp))
+    small = is_small(survey)
+    lower, upper, first = set_initial_value(survey, state.x, state.p, num_pes)
+    hyper = np.array(first if start is None else start, dtype=np.float64).reshape(nq, 4).copy()
+    diag = [i * num_pes + i for i in range(num_pes)]
+    exact = {"population": survey[diag, 4], "potential": survey[diag, 5], "kinetic": survey[diag, 6]}
+    if initial_energy is None:
+        initial_energy = float(exact["potential"].sum() + exact["kinetic"].sum())
+    clock["survey"] = time.perf_counter() - t0
+
+    t0 = time.perf_counter()
+    chosen = [api.grid_select(num_pes, rho, x, p, q, n_points, seed, uniform=bool(small[q])) for q in range(nq)]
+    cells, features, labels = [_host(api, c[0]) for c in chosen], [_host(api, c[1]) for c in chosen], [_host(api, c[2]) for c in chosen]
+    draws = [c[3] for c in chosen]
+    clock["select"] = time.perf_counter() - t0
+
+    t0 = time.perf_counter()
+    nlml, evals = 0.0, 0
+    for q in range(nq):
+        if small[q]:
+            continue  # "0 everywhere": no optimisation, the hyper-parameters stay (gpr.cpp:575-579)
+        hyper[q], value, n = optimize(api, features[q], labels[q], hyper[q], lower[q], upper[q], maxeval)
+        nlml, evals = nlml + value, evals + n
+        say(f"  plane {q}: NLML {value:.6g} at {np.array2string(hyper[q], precision=5)} after {n} evaluations")
+    clock["optimize"] = time.perf_counter() - t0
+
+    t0 = time.perf_counter()
+    weights = [None if small[q] else api.nlml_weights(hyper[q], features[q], labels[q]) for q in range(nq)]
+    on_device = hasattr(rho, "data_ptr")
+
+    def planes():
+        out = []
+        for q in range(nq):
+            if small[q]:
+                out.append(None)
+                continue
+            Xq, bq = features[q], weights[q]
+            if on_device:
+                import torch
+                Xq, bq = torch.from_numpy(Xq).to(rho.device), torch.from_numpy(bq).to(rho.device)
+            out.append((hyper[q], Xq, bq))
+        return out
+
+    plane_args = planes()
+    pred_b, sums_b = api.grid_reconstruct(num_pes, model, rho, x, p, mass, dx, dp, plane_args, None, want_pred=keep_pred)
+    sums_b = _host(api, sums_b)
+
+    def from_gpr(factor):
+        pop, pot, kin = np.zeros(num_pes), np.zeros(num_pes), np.zeros(num_pes)
+        for i, q in enumerate(diag):
+            if small[q]:
+                continue
+            b = weights[q] * factor[i]  # K^-1 (c y) = c K^-1 y: the scaled labels' weights (gpr.cpp:952-955, 986-989)
+            pop[i] = population_from_gpr(hyper[q], b)
+            pot[i] = potential_energy_from_gpr(api, num_pes, model, i, hyper[q], features[q], b)
+            kin[i] = kinetic_energy_from_gpr(hyper[q], features[q], b, mass)
+        return pop, pot, kin
+
+    pop_b, pot_b, kin_b = from_gpr(np.ones(num_pes))
+    level_factor, singular = obey_conservation(pop_b, pot_b + kin_b, small[diag], initial_energy)
+    factors = np.ones(nq)
+    factors[diag] = level_factor
+    pop_a, pot_a, kin_a = from_gpr(level_factor)
+    pred_a, sums_a = api.grid_reconstruct(num_pes, model, rho, x, p, mass, dx, dp, plane_args, factors, want_pred=keep_pred)
+    sums_a = _host(api, sums_a)
+    clock["reconstruct"] = time.perf_counter() - t0
+
+    rec = dict(nlml=nlml, hyper=hyper, evaluations=evals, is_small=small, factors=factors, singular=singular, initial_energy=initial_energy,
+               mse_before=sums_b[:, 0].copy(), mse_after=sums_a[:, 0].copy(), sums_before=sums_b, sums_after=sums_a, survey=survey,
+               cells=cells, features=features, labels=[labels[q] * factors[q] for q in range(nq)], draws=draws, seconds=clock)
+    for name, ex, gb, ga, k in (("population", exact["population"], pop_b, pop_a, 1), ("potential", exact["potential"], pot_b, pot_a, 2),
+                                ("kinetic", exact["kinetic"], kin_b, kin_a, 3)):
+        rec[f"{name}_exact"] = ex
+        rec[f"{name}_grid_before"], rec[f"{name}_grid_after"] = sums_b[diag, k], sums_a[diag, k]
+        rec[f"{name}_gpr_before"], rec[f"{name}_gpr_after"] = gb, ga
+    if keep_pred:
+        rec["pred_before"], rec["pred_after"] = _host(api, pred_b), _host(api, pred_a)
+    return rec
+
+
+def log_line(t, rec):
+    """One line of log.txt (main_evolve.cpp:135-178): t, NLML sum, the hyper-parameters, per plane MSE without / with the constraints, per level
+    exact / grid / parameters population, potential and kinetic energy without and with the constraints"""
+    v = [t, rec["nlml"], *rec["hyper"].ravel()]
+    for q in range(len(rec["mse_before"])):
+        v += [rec["mse_before"][q], rec["mse_after"][q]]
+    for i in range(len(rec["population_exact"])):
+        for name in ("population", "potential", "kinetic"):
+            v += [rec[f"{name}_exact"][i], rec[f"{name}_grid_before"][i], rec[f"{name}_gpr_before"][i], rec[f"{name}_grid_after"][i], rec[f"{name}_gpr_after"][i]]
+    return " ".join("%.16g" % a for a in v) + "\n"
+
+
+def choose_block(rec):
+    """print_point (io.cpp:74-92): per plane one line ' x p x p ...', then an empty line"""
+    return "".join("".join(f" {fmt(a)} {fmt(b)}" for a, b in f) + "\n" for f in rec["features"]) + "\n"
+
+
+def sim_block(pred):
+    """main_evolve.cpp:145-160: per plane one line of the nx * np predicted values, then an empty line"""
+    return "".join("".join(" " + fmt(v) for v in plane.ravel()) + "\n" for plane in pred) + "\n"
+
+
+def run_mqcl(api, out_dir=None, model=DAC, num_pes=2, ln_energy=0.0, n_points=200, seed=0, maxeval=0, write_sim=False, max_outputs=None, log=None,
+             **setup_kw):
+    """The exact MQCLE run of exact_mqcl.run with the reconstruction of main_evolve.cpp at every output time.  Each output's state is moved to
+    the device once and the four reconstruction entry points work on that resident copy.  Writes log.txt, choose.txt and (write_sim) sim.txt
+    in the reference's layouts next to exact_mqcl.run's files (phase.txt is not written: it is what this run replaces).  Returns exact_mqcl.run's
+    dict with the reconstruction records under "reconstructions"."""
+    import torch
+    say = log or (lambda *_: None)
+    files, recs, carry = {}, [], {}
+    if out_dir is not None:
+        os.makedirs(out_dir, exist_ok=True)
+        for name in ("log.txt", "choose.txt") + (("sim.txt",) if write_sim else ()):
+            files[name] = open(os.path.join(out_dir, name), "w")
+
+    def on_output(t, adia):
+        if "state" not in carry:
+            s = exact_mqcl.setup(ln_energy, **setup_kw)
+            carry["state"] = State(api, num_pes, model, s["x"], s["p"], s["mass"])
+        dev = torch.from_numpy(np.ascontiguousarray(adia)).cuda()
+        rec = reconstruct(api, carry["state"], dev, n_points=n_points, seed=seed + len(recs), maxeval=maxeval, start=carry.get("hyper"),
+                          initial_energy=carry.get("energy"), keep_pred=write_sim, log=log)
+        carry["hyper"] = rec["hyper"]
+        carry.setdefault("energy", rec["initial_energy"])
+        rec["t"] = t
+        say(f"T = {t:g}: NLML {rec['nlml']:.6g}, MSE {np.array2string(rec['mse_before'], precision=3)} -> {np.array2string(rec['mse_after'], precision=3)}, "
+            + ", ".join(f"{k} {1e3 * v:.1f} ms" for k, v in rec["seconds"].items()))
+        if files:
+            files["log.txt"].write(log_line(t, rec))
+            files["choose.txt"].write(choose_block(rec))
+            if write_sim:
+                files["sim.txt"].write(sim_block(rec["pred_after"]))
+        rec.pop("pred_before", None), rec.pop("pred_after", None)
+        recs.append(rec)
+
+    try:
+        res = exact_mqcl.run(api, model=model, num_pes=num_pes, ln_energy=ln_energy, out_dir=out_dir, write_phase=None, max_outputs=max_outputs, log=log,
+                             on_output=on_output, **setup_kw)
+    finally:
+        for f in files.values():
+            f.close()
+    res["reconstructions"] = recs
+    return res

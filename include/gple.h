@@ -150,7 +150,8 @@ typedef enum gple_timer {
 	GPLE_TIMER_PREDICT_KERNEL = 2, /* the MFMA row-norm kernel of *_predict alone; count = its launches */
 	GPLE_TIMER_DERIV_GEMM = 3,     /* the dK * K^-1 MFMA GEMM of a GPLE_CALC_DERIVATIVE fit (kernel.cpp:354); count = its launches */
 	GPLE_TIMER_WIGNER = 4,         /* the MFMA kernel of gple_wigner alone (all T output times of a call); count = its launches */
-	GPLE_TIMER_MQCL = 5            /* the step kernels of one gple_mqcl_evolve call (all its steps, no set-up); count = its calls */
+	GPLE_TIMER_MQCL = 5,           /* the step kernels of one gple_mqcl_evolve call (all its steps, no set-up); count = its calls */
+	GPLE_TIMER_RECON = 6           /* the device work of one gple_nlml_weights / gple_grid_survey / gple_grid_select / gple_grid_reconstruct call; count = calls */
 } gple_timer;
 int gple_ctx_enable_timing(gple_ctx* ctx, int on);
 /* Synchronises the stream, then: last = milliseconds of the most recent interval; total / count = accumulated since
@@ -459,6 +460,55 @@ int gple_nlml_predict(gple_ctx* ctx, const double x[4], const double* X, const d
 int gple_nlml_cross(gple_ctx* ctx, const double x[5], const double* X, const double* y, size_t N, double* value, double* grad);
 int gple_nlml_cross_predict(gple_ctx* ctx, const double x[5], const double* X, const double* y, size_t N, const double* Xs,
 	size_t M, unsigned flags, double* mean);
+
+/* ---- reconstruction of a gridded density with the NLML GP (test/main_evolve.cpp:56-179, test/gpr.cpp) ------------------- */
+/* The experiment the reference runs on the exact solvers' phase.txt: pick points of every density-matrix element weighted by |rho|, fit the
+ * NOCROSS kernel of gple_nlml, predict the element back on the whole grid and compare.  rho is the phase.txt layout of gple_wigner /
+ * gple_mqcl_observe: num_pes^2 elements (i, j) row-major, each nx x np (x major, p fastest) (re, im) pairs; num_pes = 2 or 3; nx, np >= 2 and
+ * independent; only the elements i <= j are read.  The state is seen as num_pes^2 REAL planes (SuperMatrix, test/io.cpp:25-72): plane
+ * q = row num_pes + col is Re rho_ii (row == col = i), Re rho_ij (row = i < col = j) or Im rho_ij (row = j > col = i).  read_density's
+ * averaging with the transposed block (io.cpp:62-66) is not restated. */
+/* b = K^-1 y (N values) of the kernel x = (w_d, w_g, a_x, a_p): the KInvLbl of predict_phase and of the three calculate_*_from_gpr
+ * (test/gpr.cpp:692, 736, 788, 874) — the Gram, factorisation and solve gple_nlml_predict runs internally.  1 <= N <= 4096. */
+int gple_nlml_weights(gple_ctx* ctx, const double x[4], const double* X, const double* y, size_t N, unsigned flags, double* b);
+/* One pass over the elements i <= j; out[8 q + ...] per plane q: [0] max, [1] min, [2] sum |v| (the `weight` of gpr.cpp:247), [3] row-major
+ * index a np + b of the first strict maximum above 0.0 (set_initial_value, gpr.cpp:119-135) as a double, -1 if none; diagonal planes also
+ * [4] sum v dx dp, [5] sum_a rowsum_a E_i(x_a) dx dp, [6] sum_b colsum_b p_b^2 / (2 mass) dx dp (calculate_{population, potential_energy,
+ * kinetic_energy}_from_grid, gpr.cpp:42-82; zeros off the diagonal); [7] = 0.  E_i: the adiabatic energies of gple_pes_adiabatic_n, rho in the
+ * adiabatic representation.  dx, dp are arguments because the reference uses (x[nx - 1] - x[0]) / nx here (main_evolve.cpp:23).  Two calls on
+ * the same input return the same bits. */
+#define GPLE_SURVEY_STRIDE 8
+int gple_grid_survey(gple_ctx* ctx, int num_pes, int model, const double* rho, const double* x, size_t nx, const double* p, size_t np, double mass,
+	double dx, double dp, unsigned flags, double* out);
+/* generate_training_set (gpr.cpp:215-291) for plane q.  Draw k = 0, 1, ... takes the uniforms u, u' = unit53 of words (0, 1) and (2, 3) of
+ * Philox4x32-10 with counter (k, q, 0x5E1EC7, 0) and key = seed.  uniform == 0 (gpr.cpp:243-265): u_k = u W with W = sum |v| as the device's
+ * own blocked running sum ends (u_k >= W by rounding is taken one ulp down), the draw selects the first cell in row-major order whose running
+ * sum exceeds u_k — never a cell of zero weight.  uniform != 0 (gpr.cpp:232-240): cell (floor(u nx), floor(u' np)).  The result is the set of
+ * distinct cells among the first K draws, K the smallest count that yields n_select of them, in ascending (ix, ip) order: cells (2 n_select
+ * ints), X (2 n_select: x[ix], p[ip] interleaved), y (n_select plane values), *n_draws = K (host pointer always).  n_select must not exceed
+ * the number of cells (weighted: of cells with |v| > 0) nor 4096, else GPLE_ERR_BAD_ARG.  The reference seeds from the clock: no draw stream
+ * of it exists to match. */
+int gple_grid_select(gple_ctx* ctx, int num_pes, const double* rho, const double* x, size_t nx, const double* p, size_t np, int q, int uniform,
+	size_t n_select, unsigned long long seed, unsigned flags, int* cells, double* X, double* y, size_t* n_draws);
+/* predict_phase + mean_squared_error + calculate_*_from_grid (gpr.cpp:654-706, 994-1005, 42-82) of all planes in one pass.  planes[q]: the
+ * kernel x = (w_d, w_g, a_x, a_p) (host values), the N training points X (2 N) and the weights b (N, gple_nlml_weights) of plane q; N = 0: the
+ * plane is predicted as exactly 0 (gpr.cpp:671-681); 1 <= N <= 4096 otherwise.  scale (nullable = 1; host values): c_q multiplies the
+ * prediction (obey_conservation's factor, gpr.cpp:949, 983).  The prediction on the tensor grid is the product of two tables,
+ * mu(x_a, p_b) = sum_i [c w_g^2 b_i exp(-(a_x (x_a - X_i))^2 / 2)] [exp(-(a_p (p_b - P_i))^2 / 2)], on the fp64 MFMA — a product of two
+ * exponentials where gple_nlml_predict takes one exponential of the summed argument.  pred (nullable): the num_pes^2 real planes, nx x np each.
+ * sums[6 q + ...]: [0] sum (c mu - v)^2 (mean_squared_error: a sum, not a mean), diagonal planes [1] sum c mu dx dp, [2] sum c mu E_i(x_a) dx dp,
+ * [3] sum c mu p_b^2 / (2 mass) dx dp (zeros off the diagonal), [4] sum (c mu)^2, [5] sum c mu v.  No floating-point atomics: two calls on the
+ * same input return the same bits, with or without pred. */
+typedef struct gple_recon_plane
+{
+	double x[4];
+	const double* X;
+	const double* b;
+	size_t N;
+} gple_recon_plane;
+#define GPLE_RECON_SUMS 6
+int gple_grid_reconstruct(gple_ctx* ctx, int num_pes, int model, const double* rho, const double* x, size_t nx, const double* p, size_t np, double mass,
+	double dx, double dp, const gple_recon_plane* planes, const double* scale, unsigned flags, double* pred, double* sums);
 
 #ifdef __cplusplus
 }
