@@ -29,9 +29,11 @@ def load_library():
             raise ImportError(f"{LIB_PATH} not found: the HIP extension is not built "
                               "(run `python -c 'import __graft_entry__ as g; g.build()'`); there is no CPU fallback")
         try:
-            _lib = ctypes.CDLL(LIB_PATH)
+            lib = ctypes.CDLL(LIB_PATH)
         except OSError as e:  # pragma: no cover
             raise ImportError(f"cannot load {LIB_PATH}: {e}; there is no CPU fallback") from e
+        _capi.declare(lib, "gple_")  # callers of the raw library (the searches, tests) get the signatures of include/gple.h without an Api
+        _lib = lib
     return _lib
 
 

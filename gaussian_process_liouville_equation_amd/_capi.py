@@ -71,24 +71,35 @@ def _opt_options(maxeval=0, initial_step=0.5):
     return OptOptions(1e-5, 1e-5, 1e-15, 1e-15, initial_step, int(maxeval or 0))
 
 
-def minimize_neldermead(lib, fun, x0, lb, ub, maxeval=0):
-    """the library's own Nelder-Mead (gple_minimize_neldermead) on a Python objective fun(x list) -> float; (x, f, n_eval)"""
-    n = len(x0)
-    cb = OBJECTIVE_FN(lambda nn, xp, gp, data: float(fun([xp[i] for i in range(nn)])))
+def _search(lib, name, head, x0, lb, ub, maxeval, options, is_log=()):
+    """The part every gple_*minimize_* call shares: `head` (callbacks and their data, or handles, then the counts) is followed by the box,
+    the options (None: the reference's tolerances with this maxeval), the start point / minimiser, the minimum and the evaluation count.
+    `head` keeps the callback objects referenced until the call returns.  -> (x, f, n_eval)"""
     x, lbv, ubv = _f64(x0).copy(), _f64(lb), _f64(ub)
     f, ne = C.c_double(), C.c_int()
-    lib.gple_minimize_neldermead.argtypes = [OBJECTIVE_FN, C.c_void_p, C.c_uint, _dp, _dp, C.POINTER(OptOptions), _dp, _dp, C.POINTER(C.c_int)]
-    st = lib.gple_minimize_neldermead(cb, None, n, _ptr(lbv), _ptr(ubv), C.byref(_opt_options(maxeval)), _ptr(x), C.cast(C.byref(f), _dp), C.byref(ne))
+    opt = _opt_options(maxeval) if options is None else options
+    st = getattr(lib, "gple_" + name)(*head, _ptr(lbv), _ptr(ubv), *is_log, C.byref(opt), _ptr(x), C.byref(f), C.byref(ne))
     if st != GPLE_OK:
-        raise GpleError(f"gple_minimize_neldermead: status {st}")
+        raise GpleError(f"gple_{name}: status {st}")
     return list(x), f.value, ne.value
 
 
-def minimize_auglag_eq(lib, fun, constraint, m, x0, lb, ub, maxeval=0):
+def _value_callback(fun):
+    return OBJECTIVE_FN(lambda nn, xp, gp, data: float(fun([xp[i] for i in range(nn)])))
+
+
+def _handles(objectives):
+    return (C.c_void_p * len(objectives))(*[o.handle.value for o in objectives])
+
+
+def minimize_neldermead(lib, fun, x0, lb, ub, maxeval=0, options=None):
+    """the library's own Nelder-Mead (gple_minimize_neldermead) on a Python objective fun(x list) -> float; (x, f, n_eval)"""
+    return _search(lib, "minimize_neldermead", (_value_callback(fun), None, len(x0)), x0, lb, ub, maxeval, options)
+
+
+def minimize_auglag_eq(lib, fun, constraint, m, x0, lb, ub, maxeval=0, options=None):
     """the library's augmented-Lagrangian search: fun(x, want_grad) -> (f, grad or None); constraint(x, want_grad) ->
     (h (m,), grad (m*n,) row-major or None); returns (x, f, n_eval)"""
-    n = len(x0)
-
     def f_cb(nn, xp, gp, data):
         v, g = fun([xp[i] for i in range(nn)], bool(gp))
         if gp:
@@ -104,58 +115,25 @@ def minimize_auglag_eq(lib, fun, constraint, m, x0, lb, ub, maxeval=0):
             for i in range(mm * nn):
                 gp[i] = g[i]
 
-    fc, hc = OBJECTIVE_FN(f_cb), CONSTRAINT_FN(h_cb)
-    x, lbv, ubv = _f64(x0).copy(), _f64(lb), _f64(ub)
-    f, ne = C.c_double(), C.c_int()
-    lib.gple_minimize_auglag_eq.argtypes = [OBJECTIVE_FN, C.c_void_p, CONSTRAINT_FN, C.c_void_p, C.c_uint, C.c_uint, _dp, _dp, C.POINTER(OptOptions), _dp, _dp,
-                                            C.POINTER(C.c_int)]
-    st = lib.gple_minimize_auglag_eq(fc, None, hc, None, m, n, _ptr(lbv), _ptr(ubv), C.byref(_opt_options(maxeval)), _ptr(x), C.cast(C.byref(f), _dp), C.byref(ne))
-    if st != GPLE_OK:
-        raise GpleError(f"gple_minimize_auglag_eq: status {st}")
-    return list(x), f.value, ne.value
+    return _search(lib, "minimize_auglag_eq", (OBJECTIVE_FN(f_cb), None, CONSTRAINT_FN(h_cb), None, m, len(x0)), x0, lb, ub, maxeval, options)
 
 
-def objective_minimize_neldermead(lib, objectives, x0, lb, ub, maxeval=0):
+def objective_minimize_neldermead(lib, objectives, x0, lb, ub, maxeval=0, options=None):
     """gple_objective_minimize_neldermead over resident objectives (same data, different contexts): vertices evaluated concurrently"""
-    n = len(x0)
-    arr = (C.c_void_p * len(objectives))(*[o.handle.value for o in objectives])
-    x, lbv, ubv = _f64(x0).copy(), _f64(lb), _f64(ub)
-    f, ne = C.c_double(), C.c_int()
-    lib.gple_objective_minimize_neldermead.argtypes = [C.POINTER(C.c_void_p), C.c_size_t, C.c_size_t, _dp, _dp, C.POINTER(OptOptions), _dp, _dp, C.POINTER(C.c_int)]
-    st = lib.gple_objective_minimize_neldermead(arr, len(objectives), n, _ptr(lbv), _ptr(ubv), C.byref(_opt_options(maxeval)), _ptr(x), C.cast(C.byref(f), _dp), C.byref(ne))
-    if st != GPLE_OK:
-        raise GpleError(f"gple_objective_minimize_neldermead: status {st}")
-    return list(x), f.value, ne.value
+    return _search(lib, "objective_minimize_neldermead", (_handles(objectives), len(objectives), len(x0)), x0, lb, ub, maxeval, options)
 
 
-def minimize_direct_l(lib, fun, x0, lb, ub, maxeval=0):
+def minimize_direct_l(lib, fun, x0, lb, ub, maxeval=0, options=None):
     """the library's DIRECT-L (gple_minimize_direct_l, the GN_DIRECT_L stand-in) on a Python objective fun(x list) -> float; (x, f, n_eval)"""
-    n = len(x0)
-    cb = OBJECTIVE_FN(lambda nn, xp, gp, data: float(fun([xp[i] for i in range(nn)])))
-    x, lbv, ubv = _f64(x0).copy(), _f64(lb), _f64(ub)
-    f, ne = C.c_double(), C.c_int()
-    lib.gple_minimize_direct_l.argtypes = [OBJECTIVE_FN, C.c_void_p, C.c_uint, _dp, _dp, C.POINTER(OptOptions), _dp, _dp, C.POINTER(C.c_int)]
-    st = lib.gple_minimize_direct_l(cb, None, n, _ptr(lbv), _ptr(ubv), C.byref(_opt_options(maxeval)), _ptr(x), C.cast(C.byref(f), _dp), C.byref(ne))
-    if st != GPLE_OK:
-        raise GpleError(f"gple_minimize_direct_l: status {st}")
-    return list(x), f.value, ne.value
+    return _search(lib, "minimize_direct_l", (_value_callback(fun), None, len(x0)), x0, lb, ub, maxeval, options)
 
 
-def objective_minimize_direct_l(lib, objectives, x0, lb, ub, is_log=None, maxeval=0):
+def objective_minimize_direct_l(lib, objectives, x0, lb, ub, is_log=None, maxeval=0, options=None):
     """gple_objective_minimize_direct_l over resident objectives (same data, different contexts): the new rectangle centres of an iteration
     are evaluated concurrently; is_log flags the coordinates that are logarithms of their parameter (the global tier's reparametrisation)"""
     n = len(x0)
-    arr = (C.c_void_p * len(objectives))(*[o.handle.value for o in objectives])
-    x, lbv, ubv = _f64(x0).copy(), _f64(lb), _f64(ub)
     flags = (C.c_ubyte * n)(*[1 if (is_log is not None and is_log[i]) else 0 for i in range(n)])
-    f, ne = C.c_double(), C.c_int()
-    lib.gple_objective_minimize_direct_l.argtypes = [C.POINTER(C.c_void_p), C.c_size_t, C.c_size_t, _dp, _dp, C.POINTER(C.c_ubyte), C.POINTER(OptOptions), _dp, _dp,
-                                                     C.POINTER(C.c_int)]
-    st = lib.gple_objective_minimize_direct_l(arr, len(objectives), n, _ptr(lbv), _ptr(ubv), flags, C.byref(_opt_options(maxeval)), _ptr(x), C.cast(C.byref(f), _dp),
-                                              C.byref(ne))
-    if st != GPLE_OK:
-        raise GpleError(f"gple_objective_minimize_direct_l: status {st}")
-    return list(x), f.value, ne.value
+    return _search(lib, "objective_minimize_direct_l", (_handles(objectives), len(objectives), n), x0, lb, ub, maxeval, options, is_log=(flags,))
 
 
 class Points(C.Structure):
@@ -204,17 +182,156 @@ def _cplx(y):
     return np.ascontiguousarray(y, dtype=np.complex128)
 
 
+def _on_device(a):
+    return hasattr(a, "data_ptr")
+
+
+def _io(*arrays):
+    """numpy arrays -> (host pointers, 0); torch tensors on the GPU (contiguous) -> (device pointers, IO_DEVICE).  The one place that turns an
+    array argument into a pointer for the entry points that take either side"""
+    dev = [a is not None and _on_device(a) and a.is_cuda for a in arrays]
+    if any(dev):
+        if not all(d or a is None for a, d in zip(arrays, dev)):
+            raise ValueError("either every array is a device tensor or none is")
+        for a in arrays:
+            if a is not None and not a.is_contiguous():
+                raise ValueError("device tensors must be contiguous")
+        return [None if a is None else C.cast(a.data_ptr(), _dp) for a in arrays], IO_DEVICE
+    return [None if a is None else a.ctypes.data_as(_dp) for a in arrays], 0
+
+
+def _axis(v):
+    """grid values: a device tensor as it is, anything else as a float64 array"""
+    return v if _on_device(v) else _f64(v)
+
+
+def _rho(rho, num_pes, n=None):
+    """a density in the phase.txt layout, complex128 (num_pes, num_pes, nx, np) — (num_pes, num_pes, n, n) when the square grid's n is given:
+    a device tensor as it is, anything else as a contiguous array"""
+    if not _on_device(rho):
+        rho = np.ascontiguousarray(rho, dtype=np.complex128)
+    shape = tuple(rho.shape)
+    if len(shape) != 4 or shape[:2] != (num_pes, num_pes) or (n is not None and shape[2:] != (n, n)):
+        raise ValueError(f"rho must have shape (num_pes, num_pes, {'nx, np' if n is None else 'n, n'})")
+    if _on_device(rho) and str(rho.dtype) != "torch.complex128":
+        raise ValueError("rho must be a complex128 tensor")
+    return rho
+
+
+def _like(ref, shape, dtype=np.float64):
+    """an empty output on the side `ref` lives on"""
+    if _on_device(ref):
+        import torch
+        return torch.empty(shape, dtype=getattr(torch, np.dtype(dtype).name), device=ref.device)
+    return np.empty(shape, dtype=dtype)
+
+
+# ---- the signatures of include/gple.h, written once ------------------------------------------------------------------------------------------
+# name without prefix -> (result type, argument types).  CTX stands for the leading gple_ctx* and FL for the `unsigned flags` argument that the
+# CPU oracle's mirror of the interface (prefix "oracle_", with_ctx=False) does not have; a flags argument the oracle keeps is a plain `u`.
+# Handles are void*, so that a c_void_p, its integer value and None all pass.  tests/test_capi_symbols.py checks every row against the header.
+CTX, FL = "ctx", "fl"
+
+
+def _signatures():
+    st, i, u, sz, d, vp, ull, ip = C.c_int, C.c_int, C.c_uint, C.c_size_t, C.c_double, C.c_void_p, C.c_ulonglong, C.POINTER(C.c_int)
+    szp, el, pts, opt = C.POINTER(C.c_size_t), C.POINTER(Element), C.POINTER(Points), C.POINTER(OptOptions)
+    predict = [CTX, vp, _dp, sz, u, _dp, _dp, _dp, _dp, C.POINTER(PredictScalars)]
+    sharded = [CTX, vp, _dp, sz, u, i, i, vp, _dp, _dp, _dp]
+    dealt = [CTX, vp, _dp, sz, u, i, i, ip, vp, _dp, _dp, _dp]
+    search = [_dp, _dp, opt, _dp, _dp, ip]  # lb, ub, options, x, fmin, n_eval
+    return {
+        # context and tracing
+        "ctx_create": (st, [i, vp, C.POINTER(vp)]),
+        "ctx_destroy": (st, [CTX]),
+        "ctx_synchronize": (st, [CTX]),
+        "ctx_trim": (st, [CTX, szp]),
+        "status_string": (C.c_char_p, [i]),
+        "ctx_last_error": (C.c_char_p, [CTX]),
+        "ctx_enable_timing": (st, [CTX, i]),
+        "ctx_get_timing": (st, [CTX, i, _dp, _dp, C.POINTER(C.c_long)]),
+        "ctx_get_prune_stats": (st, [CTX, C.POINTER(ull), C.POINTER(ull), i]),
+        # kernels, fits and predicts
+        "real_gram": (st, [CTX, _dp, _dp, sz, _dp, sz, i, FL, _dp, _dp]),
+        "complex_gram": (st, [CTX, _dp, _dp, sz, _dp, sz, i, FL, _dp, _dp, _dp, _dp]),
+        "cutoff_factor": (st, [CTX, _dp, i, _dp, sz, FL, _dp]),
+        "real_fit_create": (st, [CTX, _dp, _dp, _dp, i, sz, u, C.POINTER(RealFitScalars), C.POINTER(vp)]),
+        "real_fit_get_scalars": (st, [vp, C.POINTER(RealFitScalars)]),
+        "real_fit_retain": (st, [vp]),
+        "real_fit_release": (st, [vp]),
+        "real_fit_size": (sz, [vp]),
+        "real_fit_get": (st, [vp, i, FL, _dp]),
+        "real_predict": (st, predict),
+        "complex_fit_create": (st, [CTX, _dp, _dp, _dp, sz, u, C.POINTER(ComplexFitScalars), C.POINTER(vp)]),
+        "complex_fit_get_scalars": (st, [vp, C.POINTER(ComplexFitScalars)]),
+        "complex_fit_retain": (st, [vp]),
+        "complex_fit_release": (st, [vp]),
+        "complex_fit_size": (sz, [vp]),
+        "complex_fit_get": (st, [vp, i, FL, _dp]),
+        "complex_predict": (st, predict),
+        "predict_batch": (st, [CTX, el, sz, _dp, ip, sz, _dp]),
+        # the grid-sharded predicts
+        "shard_bounds": (st, [sz, i, i, szp, szp, szp]),
+        "set_allgather_function": (st, [vp]),
+        "real_predict_sharded": (st, sharded),
+        "complex_predict_sharded": (st, sharded),
+        "real_predict_dealt": (st, dealt),
+        "complex_predict_dealt": (st, dealt),
+        "deal_share": (st, [sz, i, i, ip, szp, szp, szp]),
+        # the objective and the searches
+        "loose_function": (st, [CTX, _dp, sz, _dp, _dp, sz, _dp, _dp, sz, _dp, _dp]),
+        "objective_create": (st, [CTX, _dp, _dp, sz, _dp, _dp, sz, C.POINTER(vp)]),
+        "objective_eval": (st, [vp, _dp, sz, _dp, _dp]),
+        "objective_eval_part": (st, [vp, _dp, sz, i, i, _dp, _dp]),
+        "objective_release": (st, [vp]),
+        "minimize_neldermead": (st, [OBJECTIVE_FN, vp, u] + search),
+        "objective_minimize_neldermead": (st, [C.POINTER(vp), sz, sz] + search),
+        "minimize_direct_l": (st, [OBJECTIVE_FN, vp, u] + search),
+        "objective_minimize_direct_l": (st, [C.POINTER(vp), sz, sz, _dp, _dp, C.POINTER(C.c_ubyte)] + search[2:]),
+        "minimize_auglag_eq": (st, [OBJECTIVE_FN, vp, CONSTRAINT_FN, vp, u, u] + search),
+        # the step loop
+        "pes_adiabatic": (st, [CTX, i, _dp, sz, u, _dp]),
+        "evolve": (st, [CTX, el, i, d, d, pts, u]),
+        "evolve_n": (st, [CTX, i, el, i, d, d, pts, u]),
+        "pes_adiabatic_n": (st, [CTX, i, i, _dp, sz, u, _dp]),
+        "markov_chain": (st, [CTX, el, sz, d, ull, _dp, sz, _dp]),
+        "markov_chain_trace": (st, [CTX, el, sz, d, ull, _dp, sz, _dp, _dp]),
+        # the NLML GP of test/gpr.cpp
+        "nlml": (st, [CTX, _dp, _dp, _dp, sz, _dp, _dp]),
+        "nlml_predict": (st, [CTX, _dp, _dp, _dp, sz, _dp, sz, FL, _dp]),
+        "nlml_cross": (st, [CTX, _dp, _dp, _dp, sz, _dp, _dp]),
+        "nlml_cross_predict": (st, [CTX, _dp, _dp, _dp, sz, _dp, sz, FL, _dp]),
+        # exact DVR and MQCLE dynamics
+        "dvr_hamiltonian": (st, [CTX, i, i, i, d, d, sz, d, u, _dp, _dp, _dp]),
+        "dvr_propagate": (st, [CTX, i, sz, _dp, _dp, _dp, _dp, sz, _dp, u, _dp]),
+        "wigner": (st, [CTX, i, i, sz, d, d, _dp, sz, _dp, sz, _dp, d, u, _dp, _dp]),
+        "mqcl_transform": (st, [CTX, i, i, _dp, sz, i, i, u, _dp, _dp]),
+        "mqcl_evolve": (st, [CTX, i, i, _dp, _dp, sz, d, d, d, d, sz, u, _dp]),
+        "mqcl_observe": (st, [CTX, i, i, _dp, _dp, sz, d, d, d, u, _dp, _dp, _dp, _dp]),
+        # reconstruction of a gridded density
+        "nlml_weights": (st, [CTX, _dp, _dp, _dp, sz, u, _dp]),
+        "grid_survey": (st, [CTX, i, i, _dp, _dp, sz, _dp, sz, d, d, d, u, _dp]),
+        "grid_select": (st, [CTX, i, _dp, _dp, sz, _dp, sz, i, i, sz, ull, u, ip, _dp, _dp, szp]),
+        "grid_reconstruct": (st, [CTX, i, i, _dp, _dp, sz, _dp, sz, d, d, d, C.POINTER(ReconPlane), _dp, u, _dp, _dp]),
+        # csrc/gple_debug.h: the one debug entry point the binding itself calls
+        "debug_last_contraction_kernel": (C.c_char_p, [CTX]),
+    }
+
+
+SIGNATURES = _signatures()
 # every symbol include/gple.h declares (checked by tests/test_capi_symbols.py)
-GPLE_SYMBOLS = [
-    "ctx_create", "ctx_destroy", "ctx_synchronize", "ctx_trim", "status_string", "ctx_last_error", "ctx_enable_timing", "ctx_get_timing", "ctx_get_prune_stats",
-    "real_gram", "complex_gram", "cutoff_factor", "predict_batch", "shard_bounds", "set_allgather_function", "real_predict_sharded", "complex_predict_sharded", "real_predict_dealt", "complex_predict_dealt", "deal_share",
-    "real_fit_create", "real_fit_get_scalars", "real_fit_retain", "real_fit_release", "real_fit_size", "real_fit_get", "real_predict",
-    "complex_fit_create", "complex_fit_get_scalars", "complex_fit_retain", "complex_fit_release", "complex_fit_size", "complex_fit_get",
-    "complex_predict", "loose_function", "objective_create", "objective_eval", "objective_eval_part", "objective_release", "minimize_neldermead", "objective_minimize_neldermead", "minimize_direct_l", "objective_minimize_direct_l", "minimize_auglag_eq", "pes_adiabatic", "evolve", "evolve_n", "pes_adiabatic_n", "markov_chain", "markov_chain_trace", "nlml", "nlml_predict", "nlml_cross", "nlml_cross_predict",
-    "dvr_hamiltonian", "dvr_propagate", "wigner",
-    "mqcl_transform", "mqcl_evolve", "mqcl_observe",
-    "nlml_weights", "grid_survey", "grid_select", "grid_reconstruct",
-]
+GPLE_SYMBOLS = [name for name in SIGNATURES if not name.startswith("debug_")]
+
+
+def declare(lib, prefix, with_ctx=True):
+    """Give every table row whose symbol `lib` exports under `prefix` its argtypes and restype, with the markers resolved: the oracle's mirror
+    (with_ctx=False) has neither contexts nor the FL flags.  Declarations belong to the loaded library and are made once, when it is loaded or
+    bound: no call site assigns them again."""
+    filled = {CTX: [C.c_void_p], FL: [C.c_uint]} if with_ctx else {CTX: [], FL: []}
+    for name, (restype, args) in SIGNATURES.items():
+        f = getattr(lib, prefix + name, None)
+        if f is not None:
+            f.restype, f.argtypes = restype, [t for a in args for t in filled.get(a, [a])]
 
 
 class _Fit:
@@ -235,7 +352,7 @@ class _Fit:
 
     def release(self):
         if self.handle:
-            getattr(self.api.lib, f"{self.api.prefix}{self.kind}_fit_release")(self.handle)
+            self.api._fn(f"{self.kind}_fit_release")(self.handle)
             self.handle = None
 
     def __del__(self):
@@ -272,21 +389,19 @@ class _Objective:
                                                  len(Xe), C.byref(self.handle)))
         api._fits.add(self)  # released with the context, like the fits
 
-    def __call__(self, x, want_grad=True):
+    def _eval(self, name, x, split, want_grad):
         x = _f64(x)
         val = C.c_double()
         grad = np.empty(len(x)) if want_grad else None
-        self.api._check(self.api.lib.gple_objective_eval(self.handle, _ptr(x), len(x), C.cast(C.byref(val), _dp), _ptr(grad)))
+        self.api._check(self.api._fn(name)(self.handle, _ptr(x), len(x), *split, C.byref(val), _ptr(grad)))
         return val.value, grad
+
+    def __call__(self, x, want_grad=True):
+        return self._eval("objective_eval", x, (), want_grad)
 
     def part(self, x, part, nparts, want_grad=True):
         """gple_objective_eval_part: this rank's share of the value and gradient (sum over the parts = the whole; make_normal after the sum)"""
-        x = _f64(x)
-        val = C.c_double()
-        grad = np.empty(len(x)) if want_grad else None
-        self.api.lib.gple_objective_eval_part.argtypes = [C.c_void_p, _dp, C.c_size_t, C.c_int, C.c_int, _dp, _dp]
-        self.api._check(self.api.lib.gple_objective_eval_part(self.handle, _ptr(x), len(x), int(part), int(nparts), C.cast(C.byref(val), _dp), _ptr(grad)))
-        return val.value, grad
+        return self._eval("objective_eval_part", x, (int(part), int(nparts)), want_grad)
 
     def release(self):
         if self.handle:
@@ -305,7 +420,7 @@ class Api:
         self.lib, self.prefix, self.with_ctx = lib, prefix, with_ctx
         self.ctx = None
         self._fits = weakref.WeakSet()  # a context must outlive its fit handles: close() releases them first
-        self._declare()
+        declare(lib, prefix, with_ctx)
         if with_ctx:
             ctx = C.c_void_p()
             self._check(lib.gple_ctx_create(int(device), C.c_void_p(stream), C.byref(ctx)))
@@ -314,47 +429,6 @@ class Api:
     # ---- plumbing --------------------------------------------------------------------------------------------
     def _fn(self, name):
         return getattr(self.lib, self.prefix + name)
-
-    def _declare(self):
-        ctx = [C.c_void_p] if self.with_ctx else []
-        fl = [C.c_uint] if self.with_ctx else []  # the oracle has no flags on gram/cutoff/get
-        sz, vp, ci = C.c_size_t, C.c_void_p, C.c_int
-        sig = {
-            "real_gram": ctx + [_dp, _dp, sz, _dp, sz, ci] + fl + [_dp, _dp],
-            "complex_gram": ctx + [_dp, _dp, sz, _dp, sz, ci] + fl + [_dp, _dp, _dp, _dp],
-            "cutoff_factor": ctx + [_dp, ci, _dp, sz] + fl + [_dp],
-            "real_fit_create": ctx + [_dp, _dp, _dp, ci, sz, C.c_uint, C.POINTER(RealFitScalars), C.POINTER(vp)],
-            "real_fit_release": [vp],
-            "real_fit_get": [vp, ci] + fl + [_dp],
-            "real_predict": ctx + [vp, _dp, sz, C.c_uint, _dp, _dp, _dp, _dp, C.POINTER(PredictScalars)],
-            "complex_fit_create": ctx + [_dp, _dp, _dp, sz, C.c_uint, C.POINTER(ComplexFitScalars), C.POINTER(vp)],
-            "complex_fit_release": [vp],
-            "complex_fit_get": [vp, ci] + fl + [_dp],
-            "complex_predict": ctx + [vp, _dp, sz, C.c_uint, _dp, _dp, _dp, _dp, C.POINTER(PredictScalars)],
-            "loose_function": ctx + [_dp, sz, _dp, _dp, sz, _dp, _dp, sz, _dp, _dp],
-            "nlml": ctx + [_dp, _dp, _dp, sz, _dp, _dp],
-            "nlml_predict": ctx + [_dp, _dp, _dp, sz, _dp, sz] + fl + [_dp],
-            "nlml_cross": ctx + [_dp, _dp, _dp, sz, _dp, _dp],
-            "nlml_cross_predict": ctx + [_dp, _dp, _dp, sz, _dp, sz] + fl + [_dp],
-        }
-        for name, argtypes in sig.items():
-            f = self._fn(name)
-            f.argtypes, f.restype = argtypes, C.c_int
-        if self.with_ctx:
-            for kind, st in (("real", RealFitScalars), ("complex", ComplexFitScalars)):
-                f = self._fn(f"{kind}_fit_get_scalars")
-                f.argtypes, f.restype = [vp, C.POINTER(st)], C.c_int
-            self.lib.gple_predict_batch.argtypes = [vp, C.POINTER(Element), sz, _dp, C.POINTER(ci), sz, _dp]
-            self.lib.gple_predict_batch.restype = C.c_int
-            self.lib.gple_objective_create.argtypes = [vp, _dp, _dp, sz, _dp, _dp, sz, C.POINTER(vp)]
-            self.lib.gple_objective_eval.argtypes = [vp, _dp, sz, _dp, _dp]
-            self.lib.gple_objective_release.argtypes = [vp]
-            self.lib.gple_ctx_create.argtypes = [C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]
-            self.lib.gple_ctx_destroy.argtypes = [C.c_void_p]
-            self.lib.gple_ctx_synchronize.argtypes = [C.c_void_p]
-            self.lib.gple_ctx_trim.argtypes = [C.c_void_p, C.POINTER(C.c_size_t)]
-            self.lib.gple_status_string.argtypes, self.lib.gple_status_string.restype = [C.c_int], C.c_char_p
-            self.lib.gple_ctx_last_error.argtypes, self.lib.gple_ctx_last_error.restype = [C.c_void_p], C.c_char_p
 
     def trim(self):
         """Free the pooled device buffers no live fit owns; returns the number of bytes released."""
@@ -385,23 +459,18 @@ class Api:
             self.ctx = None
 
     def enable_timing(self, on=True):
-        self.lib.gple_ctx_enable_timing.argtypes = [C.c_void_p, C.c_int]
         self._check(self.lib.gple_ctx_enable_timing(self.ctx, int(on)))
 
     def timing(self, which):
         """(last_ms, total_ms, count) of a gple_timer: 0 = fit, 1 = predict call, 2 = fused predict kernel, 3 = derivative GEMM, 4 = Wigner kernel, 5 = MQCLE
         steps, 6 = the device work of the reconstruction entry points."""
         last, total, count = C.c_double(), C.c_double(), C.c_long()
-        self.lib.gple_ctx_get_timing.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
-                                                 C.POINTER(C.c_long)]
         self._check(self.lib.gple_ctx_get_timing(self.ctx, which, C.byref(last), C.byref(total), C.byref(count)))
         return last.value, total.value, count.value
 
     def last_contraction_kernel(self):
         """Name of the kernel this context's last predict ran its variance contraction on (csrc/gple_debug.h; the roofline label of bench.py)."""
-        fn = self.lib.gple_debug_last_contraction_kernel
-        fn.argtypes, fn.restype = [C.c_void_p], C.c_char_p
-        return (fn(self.ctx) or b"").decode()
+        return (self.lib.gple_debug_last_contraction_kernel(self.ctx) or b"").decode()
 
     def prune_stats(self, reset=False):
         """(contracted, seen) test rows of the pruned predicts in units of 128 rows since creation / the last reset."""
@@ -445,14 +514,10 @@ class Api:
 
     def predict_batch(self, elements, points, element_of_request):
         """gple_predict_batch: elements = list of _Fit or None; points (n,2); element_of_request (n,) ints -> complex (n,)"""
-        arr = (Element * max(1, len(elements)))()
-        for i, f in enumerate(elements):
-            if f is not None:
-                setattr(arr[i], "real" if f.kind == "real" else "cplx", f.handle.value)
         pts = _points(points)
         idx = np.ascontiguousarray(element_of_request, dtype=np.int32)
         out = np.empty(2 * len(pts))
-        self._check(self.lib.gple_predict_batch(self.ctx, arr, len(elements), _ptr(pts), idx.ctypes.data_as(C.POINTER(C.c_int)), len(pts), _ptr(out)))
+        self._check(self.lib.gple_predict_batch(self.ctx, self._elements(elements), len(elements), _ptr(pts), idx.ctypes.data_as(C.POINTER(C.c_int)), len(pts), _ptr(out)))
         return out.view(np.complex128)
 
     def _elements(self, fits):
@@ -466,7 +531,6 @@ class Api:
         """(M, 6): E0, E1, F00, F10, F11, NAC01 of Tully's model `model` (0 SAC, 1 DAC, 2 ECR) at positions x"""
         x = _f64(x)
         out = np.empty(6 * len(x))
-        self.lib.gple_pes_adiabatic.argtypes = [C.c_void_p, C.c_int, _dp, C.c_size_t, C.c_uint, _dp]
         self._check(self.lib.gple_pes_adiabatic(self.ctx, int(model), _ptr(x), len(x), 0, _ptr(out)))
         return out.reshape(-1, 6)
 
@@ -475,13 +539,16 @@ class Api:
         -> the same structure one tick later.  new_points: new_point_predict (evolve.cpp:425-443) at the given points instead — they
         stay where they are and rho becomes what the back-propagation predicts there from the fits alone (0 where uncoupled)."""
         order = [(0, 0), (1, 0), (1, 1)]
-        rs = [np.ascontiguousarray(np.asarray(density[e][0], dtype=np.float64).reshape(-1, 2)).copy() for e in order]
-        rhos = [np.ascontiguousarray(np.asarray(density[e][1], dtype=np.complex128)).copy() for e in order]
-        pts = (Points * 3)()
-        for k in range(3):
+        return self._tick("evolve", (), order, [density[e] for e in order], fits, model, mass, dt, new_points)
+
+    def _tick(self, name, head, order, pairs, fits, model, mass, dt, new_points):
+        """gple_evolve / gple_evolve_n on copies of the (r, rho) pairs of the elements in `order`"""
+        rs = [np.ascontiguousarray(np.asarray(pair[0], dtype=np.float64).reshape(-1, 2)).copy() for pair in pairs]
+        rhos = [np.ascontiguousarray(np.asarray(pair[1], dtype=np.complex128)).copy() for pair in pairs]
+        pts = (Points * len(order))()
+        for k in range(len(order)):
             pts[k].r, pts[k].rho, pts[k].n = _ptr(rs[k]), _ptr(rhos[k].view(np.float64)), len(rs[k])
-        self.lib.gple_evolve.argtypes = [C.c_void_p, C.POINTER(Element), C.c_int, C.c_double, C.c_double, C.POINTER(Points), C.c_uint]
-        self._check(self.lib.gple_evolve(self.ctx, self._elements(fits), int(model), float(mass), float(dt), pts, EVOLVE_NEW_POINTS if new_points else 0))
+        self._check(self._fn(name)(self.ctx, *head, self._elements(fits), int(model), float(mass), float(dt), pts, EVOLVE_NEW_POINTS if new_points else 0))
         return {e: (rs[k], rhos[k]) for k, e in enumerate(order)}
 
     def pes_adiabatic_n(self, num_pes, model, x):
@@ -490,7 +557,6 @@ class Api:
         ne = num_pes * (num_pes + 1) // 2
         w = num_pes + 2 * ne
         out = np.empty(w * len(x))
-        self.lib.gple_pes_adiabatic_n.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, C.c_size_t, C.c_uint, _dp]
         self._check(self.lib.gple_pes_adiabatic_n(self.ctx, int(num_pes), int(model), _ptr(x), len(x), 0, _ptr(out)))
         out = out.reshape(-1, w)
         E, F, NAC = out[:, :num_pes].copy(), np.zeros((len(x), num_pes, num_pes)), np.zeros((len(x), num_pes, num_pes))
@@ -511,9 +577,8 @@ class Api:
         H = np.empty((dim, dim)) if want_h else None
         E = np.empty((n_grids, num_pes)) if want_states else None
         B = np.empty((n_grids, num_pes, num_pes)) if want_states else None
-        f = self.lib.gple_dvr_hamiltonian
-        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_size_t, C.c_double, C.c_uint, _dp, _dp, _dp]
-        self._check(f(self.ctx, int(num_pes), int(model), int(boundary), float(x_first), float(dx), int(n_grids), float(mass), 0, _ptr(H), _ptr(E), _ptr(B)))
+        self._check(self.lib.gple_dvr_hamiltonian(self.ctx, int(num_pes), int(model), int(boundary), float(x_first), float(dx), int(n_grids), float(mass), 0, _ptr(H), _ptr(E),
+                                                  _ptr(B)))
         return H, E, B
 
     def dvr_propagate(self, num_pes, n_grids, eigvec, eigval, psi0, times, basis=None, from_psi0=True):
@@ -526,10 +591,8 @@ class Api:
             raise ValueError("eigvec (dim, dim), eigval (dim,) and psi0 (dim,) with dim = num_pes * n_grids")
         basis = None if basis is None else _f64(basis)
         out = np.empty((len(times), dim), dtype=np.complex128)
-        f = self.lib.gple_dvr_propagate
-        f.argtypes = [C.c_void_p, C.c_int, C.c_size_t, _dp, _dp, _dp, _dp, C.c_size_t, _dp, C.c_uint, _dp]
-        self._check(f(self.ctx, int(num_pes), int(n_grids), _ptr(eigvec), _ptr(eigval), _ptr(psi0.view(np.float64)), _ptr(times), len(times), _ptr(basis),
-                      0x800 if from_psi0 else 0, _ptr(out.view(np.float64))))
+        self._check(self.lib.gple_dvr_propagate(self.ctx, int(num_pes), int(n_grids), _ptr(eigvec), _ptr(eigval), _ptr(psi0.view(np.float64)), _ptr(times),
+                                                len(times), _ptr(basis), 0x800 if from_psi0 else 0, _ptr(out.view(np.float64))))
         return out
 
     def wigner(self, num_pes, boundary, x_first, dx, p, psi, energies=None, mass=0.0, phase=True, averages=False):
@@ -541,188 +604,113 @@ class Api:
         P = np.empty((T, num_pes, num_pes, n, len(p)), dtype=np.complex128) if phase else None
         av = np.empty((T, 3)) if averages else None
         en = None if energies is None else _f64(energies)
-        f = self.lib.gple_wigner
-        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_double, C.c_double, _dp, C.c_size_t, _dp, C.c_size_t, _dp, C.c_double, C.c_uint, _dp, _dp]
-        self._check(f(self.ctx, int(num_pes), int(boundary), n, float(x_first), float(dx), _ptr(p), len(p), _ptr(psi.view(np.float64)), T, _ptr(en),
-                      float(mass), 0, None if P is None else _ptr(P.view(np.float64)), _ptr(av)))
+        self._check(self.lib.gple_wigner(self.ctx, int(num_pes), int(boundary), n, float(x_first), float(dx), _ptr(p), len(p), _ptr(psi.view(np.float64)), T,
+                                         _ptr(en), float(mass), 0, None if P is None else _ptr(P.view(np.float64)), _ptr(av)))
         return P, av
 
     # ---- exact MQCLE dynamics (liouville_equation/ of the reference; gple_mqcl_*) -------------------------------------------------------------
     MQCL_DIABATIC, MQCL_ADIABATIC, MQCL_FORCE = 0, 1, 2
 
-    @staticmethod
-    def _mqcl_io(*arrays):
-        """numpy arrays -> (host pointers, 0); torch tensors on the GPU (contiguous, float64 / complex128) -> (device pointers, IO_DEVICE)"""
-        dev = [a is not None and hasattr(a, "data_ptr") and a.is_cuda for a in arrays]
-        if any(dev):
-            if not all(d or a is None for a, d in zip(arrays, dev)):
-                raise ValueError("either every array is a device tensor or none is")
-            for a in arrays:
-                if a is not None and not a.is_contiguous():
-                    raise ValueError("device tensors must be contiguous")
-            return [None if a is None else C.cast(a.data_ptr(), _dp) for a in arrays], IO_DEVICE
-        return [None if a is None else a.ctypes.data_as(_dp) for a in arrays], 0
-
-    @staticmethod
-    def _mqcl_rho(rho, num_pes, n):
-        if hasattr(rho, "data_ptr"):
-            if tuple(rho.shape) != (num_pes, num_pes, n, n) or str(rho.dtype) != "torch.complex128":
-                raise ValueError("rho must be a complex128 tensor of shape (num_pes, num_pes, n, n)")
-            return rho
-        rho = np.ascontiguousarray(rho, dtype=np.complex128)
-        if rho.shape != (num_pes, num_pes, n, n):
-            raise ValueError("rho must have shape (num_pes, num_pes, n, n)")
-        return rho
-
-    @staticmethod
-    def _mqcl_grid(v):
-        return v if hasattr(v, "data_ptr") else _f64(v)
-
     def mqcl_transform(self, num_pes, model, x, rho, frm, to, out=None):
         """gple_mqcl_transform: basis_transform[frm][to] of rho (num_pes, num_pes, n, n) complex; numpy in -> new numpy array out, device tensors
         in -> written into `out` (a tensor like rho; rho itself when None)"""
-        x = self._mqcl_grid(x)
+        x = _axis(x)
         n = int(x.shape[0])
-        rho = self._mqcl_rho(rho, num_pes, n)
+        rho = _rho(rho, num_pes, n)
         if out is None:
-            out = rho if hasattr(rho, "data_ptr") else np.empty_like(rho)
-        (px, pi, po), flags = self._mqcl_io(x, rho, out)
-        f = self.lib.gple_mqcl_transform
-        f.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, C.c_size_t, C.c_int, C.c_int, C.c_uint, _dp, _dp]
-        self._check(f(self.ctx, int(num_pes), int(model), px, n, int(frm), int(to), flags, pi, po))
+            out = rho if _on_device(rho) else np.empty_like(rho)
+        (px, pi, po), flags = _io(x, rho, out)
+        self._check(self.lib.gple_mqcl_transform(self.ctx, int(num_pes), int(model), px, n, int(frm), int(to), flags, pi, po))
         return out
 
     def mqcl_evolve(self, num_pes, model, x, p, rho, mass, length_x, length_p, dt, n_steps):
         """gple_mqcl_evolve: n_steps Trotter steps on the diabatic rho (num_pes, num_pes, n, n) complex.  numpy: returns the evolved copy;
         device tensors: evolves rho in place (asynchronously on the context's stream) and returns it"""
-        x, p = self._mqcl_grid(x), self._mqcl_grid(p)
+        x, p = _axis(x), _axis(p)
         n = int(x.shape[0])
-        rho = self._mqcl_rho(rho, num_pes, n)
-        if not hasattr(rho, "data_ptr"):
+        rho = _rho(rho, num_pes, n)
+        if not _on_device(rho):
             rho = rho.copy()
-        (px, pp, pr), flags = self._mqcl_io(x, p, rho)
-        f = self.lib.gple_mqcl_evolve
-        f.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.c_size_t, C.c_double, C.c_double, C.c_double, C.c_double, C.c_size_t, C.c_uint, _dp]
-        self._check(f(self.ctx, int(num_pes), int(model), px, pp, n, float(mass), float(length_x), float(length_p), float(dt), int(n_steps), flags, pr))
+        (px, pp, pr), flags = _io(x, p, rho)
+        self._check(self.lib.gple_mqcl_evolve(self.ctx, int(num_pes), int(model), px, pp, n, float(mass), float(length_x), float(length_p), float(dt), int(n_steps),
+                                              flags, pr))
         return rho
 
     def mqcl_observe(self, num_pes, model, x, p, rho_dia, mass, dx, dp, adiabatic=True):
         """gple_mqcl_observe: (rho_adia (num_pes, num_pes, n, n) or None, averages (E, x, p), populations (num_pes,)); with device tensors the
         three outputs are device tensors"""
-        x, p = self._mqcl_grid(x), self._mqcl_grid(p)
+        x, p = _axis(x), _axis(p)
         n = int(x.shape[0])
-        rho_dia = self._mqcl_rho(rho_dia, num_pes, n)
-        if hasattr(rho_dia, "data_ptr"):
-            import torch
-            adia = torch.empty_like(rho_dia) if adiabatic else None
-            av = torch.empty(3, dtype=torch.float64, device=rho_dia.device)
-            pops = torch.empty(num_pes, dtype=torch.float64, device=rho_dia.device)
-        else:
-            adia = np.empty_like(rho_dia) if adiabatic else None
-            av, pops = np.empty(3), np.empty(num_pes)
-        (px, pp, pr, pa, pav, ppo), flags = self._mqcl_io(x, p, rho_dia, adia, av, pops)
-        f = self.lib.gple_mqcl_observe
-        f.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.c_size_t, C.c_double, C.c_double, C.c_double, C.c_uint, _dp, _dp, _dp, _dp]
-        self._check(f(self.ctx, int(num_pes), int(model), px, pp, n, float(mass), float(dx), float(dp), flags, pr, pa, pav, ppo))
+        rho_dia = _rho(rho_dia, num_pes, n)
+        adia = _like(rho_dia, rho_dia.shape, np.complex128) if adiabatic else None
+        av, pops = _like(rho_dia, 3), _like(rho_dia, num_pes)
+        (px, pp, pr, pa, pav, ppo), flags = _io(x, p, rho_dia, adia, av, pops)
+        self._check(self.lib.gple_mqcl_observe(self.ctx, int(num_pes), int(model), px, pp, n, float(mass), float(dx), float(dp), flags, pr, pa, pav, ppo))
         return adia, av, pops
 
     # ---- reconstruction of a gridded density with the NLML GP (test/main_evolve.cpp; gple_nlml_weights / gple_grid_*) -------------------------
     SURVEY_FIELDS = ("max", "min", "weight", "argmax", "population", "potential", "kinetic")
 
-    @staticmethod
-    def _grid_rho(rho, num_pes):
-        if hasattr(rho, "data_ptr"):
-            if rho.dim() != 4 or tuple(rho.shape[:2]) != (num_pes, num_pes) or str(rho.dtype) != "torch.complex128":
-                raise ValueError("rho must be a complex128 tensor of shape (num_pes, num_pes, nx, np)")
-            return rho
-        rho = np.ascontiguousarray(rho, dtype=np.complex128)
-        if rho.ndim != 4 or rho.shape[:2] != (num_pes, num_pes):
-            raise ValueError("rho must have shape (num_pes, num_pes, nx, np)")
-        return rho
-
-    def _like(self, ref, shape):
-        """an empty float64 output on the side `ref` lives on"""
-        if hasattr(ref, "data_ptr"):
-            import torch
-            return torch.empty(shape, dtype=torch.float64, device=ref.device)
-        return np.empty(shape)
-
     def nlml_weights(self, x, X, y):
         """gple_nlml_weights: b = K^-1 y of the NOCROSS kernel x = (w_d, w_g, a_x, a_p); numpy in -> numpy out, device tensors in -> device tensor out"""
         x = _f64(x)
         assert len(x) == 4
-        if not hasattr(X, "data_ptr"):
+        if not _on_device(X):
             X, y = _points(X), _f64(y)
         N = int(X.shape[0])
-        b = self._like(X, N)
-        (pX, py, pb), flags = self._mqcl_io(X, y, b)
-        f = self.lib.gple_nlml_weights
-        f.argtypes = [C.c_void_p, _dp, _dp, _dp, C.c_size_t, C.c_uint, _dp]
-        self._check(f(self.ctx, _ptr(x), pX, py, N, flags, pb))
+        b = _like(X, N)
+        (pX, py, pb), flags = _io(X, y, b)
+        self._check(self.lib.gple_nlml_weights(self.ctx, _ptr(x), pX, py, N, flags, pb))
         return b
 
     def grid_survey(self, num_pes, model, rho, x, p, mass, dx, dp):
         """gple_grid_survey: (num_pes^2, 8) per real plane q = row * num_pes + col: max, min, sum |v|, row-major index of the first maximum above 0
         (-1: none), and on diagonal planes population, potential and kinetic energy from the grid (SURVEY_FIELDS)"""
-        rho, x, p = self._grid_rho(rho, num_pes), self._mqcl_grid(x), self._mqcl_grid(p)
-        out = self._like(rho, (num_pes * num_pes, 8))
-        (pr, px, pp, po), flags = self._mqcl_io(rho, x, p, out)
-        f = self.lib.gple_grid_survey
-        f.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.c_size_t, _dp, C.c_size_t, C.c_double, C.c_double, C.c_double, C.c_uint, _dp]
-        self._check(f(self.ctx, int(num_pes), int(model), pr, px, int(x.shape[0]), pp, int(p.shape[0]), float(mass), float(dx), float(dp), flags, po))
+        rho, x, p = _rho(rho, num_pes), _axis(x), _axis(p)
+        out = _like(rho, (num_pes * num_pes, 8))
+        (pr, px, pp, po), flags = _io(rho, x, p, out)
+        self._check(self.lib.gple_grid_survey(self.ctx, int(num_pes), int(model), pr, px, int(x.shape[0]), pp, int(p.shape[0]), float(mass), float(dx), float(dp),
+                                              flags, po))
         return out
 
     def grid_select(self, num_pes, rho, x, p, q, n_select, seed, uniform=False):
         """gple_grid_select for plane q: (cells (n_select, 2) int32, X (n_select, 2), y (n_select,), K draws); device tensors in -> device tensors out"""
-        rho, x, p = self._grid_rho(rho, num_pes), self._mqcl_grid(x), self._mqcl_grid(p)
+        rho, x, p = _rho(rho, num_pes), _axis(x), _axis(p)
         n_select = int(n_select)
-        X, y = self._like(rho, (n_select, 2)), self._like(rho, n_select)
-        if hasattr(rho, "data_ptr"):
-            import torch
-            cells = torch.empty((n_select, 2), dtype=torch.int32, device=rho.device)
-            pc = C.cast(cells.data_ptr(), C.POINTER(C.c_int))
-        else:
-            cells = np.empty((n_select, 2), dtype=np.int32)
-            pc = cells.ctypes.data_as(C.POINTER(C.c_int))
-        (pr, px, pp, pX, py), flags = self._mqcl_io(rho, x, p, X, y)
+        cells, X, y = _like(rho, (n_select, 2), np.int32), _like(rho, (n_select, 2)), _like(rho, n_select)
+        (pr, px, pp, pc, pX, py), flags = _io(rho, x, p, cells, X, y)
         K = C.c_size_t(0)
-        f = self.lib.gple_grid_select
-        f.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.c_size_t, _dp, C.c_size_t, C.c_int, C.c_int, C.c_size_t, C.c_ulonglong, C.c_uint, C.POINTER(C.c_int), _dp, _dp,
-                      C.POINTER(C.c_size_t)]
-        self._check(f(self.ctx, int(num_pes), pr, px, int(x.shape[0]), pp, int(p.shape[0]), int(q), int(bool(uniform)), n_select, int(seed), flags, pc, pX, py,
-                      C.byref(K)))
+        self._check(self.lib.gple_grid_select(self.ctx, int(num_pes), pr, px, int(x.shape[0]), pp, int(p.shape[0]), int(q), int(bool(uniform)), n_select, int(seed),
+                                              flags, C.cast(pc, C.POINTER(C.c_int)), pX, py, C.byref(K)))
         return cells, X, y, K.value
 
     def grid_reconstruct(self, num_pes, model, rho, x, p, mass, dx, dp, planes, scale=None, want_pred=True):
         """gple_grid_reconstruct: planes = num_pes^2 entries (x (4,), X (N, 2), b (N,)) or None (the plane is predicted as 0), on the side rho lives
         on; scale: num_pes^2 factors or None.  -> (pred (num_pes^2, nx, np) or None, sums (num_pes^2, 6): sum (c mu - v)^2, population, potential and
         kinetic energy of c mu on diagonal planes, sum (c mu)^2, sum c mu v)"""
-        rho, x, p = self._grid_rho(rho, num_pes), self._mqcl_grid(x), self._mqcl_grid(p)
+        rho, x, p = _rho(rho, num_pes), _axis(x), _axis(p)
         nq = num_pes * num_pes
         if len(planes) != nq:
             raise ValueError("planes needs num_pes^2 entries")
-        pred = self._like(rho, (nq, int(x.shape[0]), int(p.shape[0]))) if want_pred else None
-        sums = self._like(rho, (nq, 6))
+        pred = _like(rho, (nq, int(x.shape[0]), int(p.shape[0]))) if want_pred else None
+        sums = _like(rho, (nq, 6))
         arr, keep = (ReconPlane * nq)(), []
         for k, pl in enumerate(planes):
             if pl is None:
                 continue
             xk, Xk, bk = pl
-            if not hasattr(Xk, "data_ptr"):
+            if not _on_device(Xk):
                 Xk, bk = _points(Xk), _f64(bk)
-            (pX, pb, _), _ = self._mqcl_io(Xk, bk, rho)  # raises unless the plane's arrays live where rho does
+            (pX, pb, _), _ = _io(Xk, bk, rho)  # raises unless the plane's arrays live where rho does
             keep.append((Xk, bk))
             arr[k].x = (C.c_double * 4)(*[float(v) for v in xk])
             arr[k].X, arr[k].b, arr[k].N = pX, pb, int(Xk.shape[0])
         sc = None if scale is None else _f64(scale)
         if sc is not None and sc.shape != (nq,):
             raise ValueError("scale needs num_pes^2 entries")
-        (pr, px, pp, ppred, ps), flags = self._mqcl_io(rho, x, p, pred, sums)
-        f = self.lib.gple_grid_reconstruct
-        f.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.c_size_t, _dp, C.c_size_t, C.c_double, C.c_double, C.c_double, C.POINTER(ReconPlane), _dp, C.c_uint,
-                      _dp, _dp]
-        self._check(f(self.ctx, int(num_pes), int(model), pr, px, int(x.shape[0]), pp, int(p.shape[0]), float(mass), float(dx), float(dp), arr, _ptr(sc), flags,
-                      ppred, ps))
+        (pr, px, pp, ppred, ps), flags = _io(rho, x, p, pred, sums)
+        self._check(self.lib.gple_grid_reconstruct(self.ctx, int(num_pes), int(model), pr, px, int(x.shape[0]), pp, int(p.shape[0]), float(mass), float(dx), float(dp),
+                                                   arr, _ptr(sc), flags, ppred, ps))
         return pred, sums
 
     def evolve_n(self, num_pes, fits, model, mass, dt, density, new_points=False):
@@ -730,29 +718,19 @@ class Api:
         density = {(i, j): (r (n, 2), rho (n,))} -> the same structure one tick later"""
         order = [(i, j) for i in range(num_pes) for j in range(i + 1)]
         empty = (np.zeros((0, 2)), np.zeros(0, dtype=complex))
-        rs = [np.ascontiguousarray(np.asarray(density.get(e, empty)[0], dtype=np.float64).reshape(-1, 2)).copy() for e in order]
-        rhos = [np.ascontiguousarray(np.asarray(density.get(e, empty)[1], dtype=np.complex128)).copy() for e in order]
-        pts = (Points * len(order))()
-        for k in range(len(order)):
-            pts[k].r, pts[k].rho, pts[k].n = _ptr(rs[k]), _ptr(rhos[k].view(np.float64)), len(rs[k])
-        self.lib.gple_evolve_n.argtypes = [C.c_void_p, C.c_int, C.POINTER(Element), C.c_int, C.c_double, C.c_double, C.POINTER(Points), C.c_uint]
-        self._check(self.lib.gple_evolve_n(self.ctx, int(num_pes), self._elements(fits), int(model), float(mass), float(dt), pts,
-                                           EVOLVE_NEW_POINTS if new_points else 0))
-        return {e: (rs[k], rhos[k]) for k, e in enumerate(order)}
+        return self._tick("evolve_n", (int(num_pes),), order, [density.get(e, empty) for e in order], fits, model, mass, dt, new_points)
 
     def markov_chain(self, fit, num_steps, max_displacement, seed, r, want_chain=False):
         """Metropolis chains of all walkers on |cut-off prediction| of `fit`: (last points (n,2), acceptance ratio (n,)); with
         want_chain also the whole chains (num_steps + 1, n, 2)"""
         r = np.ascontiguousarray(np.asarray(r, dtype=np.float64).reshape(-1, 2)).copy()
         acc = np.empty(len(r))
+        args = (self.ctx, self._elements([fit]), int(num_steps), float(max_displacement), int(seed), _ptr(r), len(r), _ptr(acc))
         if want_chain:
             chain = np.empty((int(num_steps) + 1, len(r), 2))
-            self.lib.gple_markov_chain_trace.argtypes = [C.c_void_p, C.POINTER(Element), C.c_size_t, C.c_double, C.c_ulonglong, _dp, C.c_size_t, _dp, _dp]
-            self._check(self.lib.gple_markov_chain_trace(self.ctx, self._elements([fit]), int(num_steps), float(max_displacement), int(seed), _ptr(r), len(r),
-                                                         _ptr(acc), _ptr(chain)))
+            self._check(self.lib.gple_markov_chain_trace(*args, _ptr(chain)))
             return r, acc, chain
-        self.lib.gple_markov_chain.argtypes = [C.c_void_p, C.POINTER(Element), C.c_size_t, C.c_double, C.c_ulonglong, _dp, C.c_size_t, _dp]
-        self._check(self.lib.gple_markov_chain(self.ctx, self._elements([fit]), int(num_steps), float(max_displacement), int(seed), _ptr(r), len(r), _ptr(acc)))
+        self._check(self.lib.gple_markov_chain(*args))
         return r, acc
 
     def cutoff_factor(self, prediction, variance):
@@ -763,55 +741,49 @@ class Api:
         self._check(self._fn("cutoff_factor")(*self._c(), _ptr(p), int(is_c), _ptr(var), len(var), *self._fl(), _ptr(out)))
         return out
 
-    # ---- TrainingKernel / PredictiveKernel -------------------------------------------------------------------
-    def real_fit(self, theta, X, y, flags, defer_scalars=False):
+    # ---- TrainingKernel / PredictiveKernel, TrainingComplexKernel / PredictiveComplexKernel ---------------------------------------------------
+    def _fit(self, kind, theta, X, yy, y_is_complex, flags, defer_scalars):
+        """yy: the labels as doubles; y_is_complex: the argument only gple_real_fit_create has, as a tuple (empty for the complex kernel)"""
         defer_scalars = defer_scalars and self.with_ctx  # the oracle computes everything at once
         theta, X = _f64(theta), _points(X)
-        is_c = np.iscomplexobj(y)
-        yy = _cplx(y).view(np.float64) if is_c else _f64(y)
-        sc, h = RealFitScalars(), C.c_void_p()
-        self._check(self._fn("real_fit_create")(*self._c(), _ptr(theta), _ptr(X), _ptr(yy), int(is_c), len(X), flags,
-                                                None if defer_scalars else C.byref(sc), C.byref(h)))
-        return _Fit(self, h, "real", len(X), None if defer_scalars else scalars_to_dict(sc))
+        sc, h = (RealFitScalars if kind == "real" else ComplexFitScalars)(), C.c_void_p()
+        self._check(self._fn(kind + "_fit_create")(*self._c(), _ptr(theta), _ptr(X), _ptr(yy), *y_is_complex, len(X), flags,
+                                                   None if defer_scalars else C.byref(sc), C.byref(h)))
+        return _Fit(self, h, kind, len(X), None if defer_scalars else scalars_to_dict(sc))
 
-    def real_predict(self, fit, Xs, flags=0, labels=None, want=("prediction", "variance", "cutoff")):
+    def _predict(self, kind, fit, Xs, flags, labels, want):
+        """labels, prediction and cutoff are M doubles for the real kernel and M (re, im) pairs for the complex one"""
+        cplx = kind == "complex"
         Xs = _points(Xs)
         M = len(Xs)
-        lab = None if labels is None else _f64(labels)
-        pred = np.empty(M) if "prediction" in want else None
+        wide = 2 * M if cplx else M
+        lab = None if labels is None else (_cplx(labels).view(np.float64) if cplx else _f64(labels))
+        pred = np.empty(wide) if "prediction" in want else None
         var = np.empty(M) if "variance" in want else None
-        cut = np.empty(M) if "cutoff" in want else None
+        cut = np.empty(wide) if "cutoff" in want else None
         ps = PredictScalars()
-        self._check(self._fn("real_predict")(*self._c(), fit.handle, _ptr(Xs), M, flags, _ptr(lab), _ptr(pred), _ptr(var),
-                                             _ptr(cut), C.byref(ps)))
+        self._check(self._fn(kind + "_predict")(*self._c(), fit.handle, _ptr(Xs), M, flags, _ptr(lab), _ptr(pred), _ptr(var), _ptr(cut), C.byref(ps)))
         d = scalars_to_dict(ps)
-        d["error_derivative"] = d["error_derivative"][:4]
+        if cplx:
+            pred, cut = (None if a is None else a.view(np.complex128) for a in (pred, cut))
+        else:
+            d["error_derivative"] = d["error_derivative"][:4]
         d.update(prediction=pred, variance=var, cutoff=cut)
         return d
 
-    # ---- TrainingComplexKernel / PredictiveComplexKernel ------------------------------------------------------
+    def real_fit(self, theta, X, y, flags, defer_scalars=False):
+        is_c = np.iscomplexobj(y)
+        yy = _cplx(y).view(np.float64) if is_c else _f64(y)
+        return self._fit("real", theta, X, yy, (int(is_c),), flags, defer_scalars)
+
+    def real_predict(self, fit, Xs, flags=0, labels=None, want=("prediction", "variance", "cutoff")):
+        return self._predict("real", fit, Xs, flags, labels, want)
+
     def complex_fit(self, theta, X, y, flags, defer_scalars=False):
-        defer_scalars = defer_scalars and self.with_ctx
-        theta, X, yy = _f64(theta), _points(X), _cplx(y).view(np.float64)
-        sc, h = ComplexFitScalars(), C.c_void_p()
-        self._check(self._fn("complex_fit_create")(*self._c(), _ptr(theta), _ptr(X), _ptr(yy), len(X), flags,
-                                                   None if defer_scalars else C.byref(sc), C.byref(h)))
-        return _Fit(self, h, "complex", len(X), None if defer_scalars else scalars_to_dict(sc))
+        return self._fit("complex", theta, X, _cplx(y).view(np.float64), (), flags, defer_scalars)
 
     def complex_predict(self, fit, Xs, flags=0, labels=None, want=("prediction", "variance", "cutoff")):
-        Xs = _points(Xs)
-        M = len(Xs)
-        lab = None if labels is None else _cplx(labels).view(np.float64)
-        pred = np.empty(2 * M) if "prediction" in want else None
-        var = np.empty(M) if "variance" in want else None
-        cut = np.empty(2 * M) if "cutoff" in want else None
-        ps = PredictScalars()
-        self._check(self._fn("complex_predict")(*self._c(), fit.handle, _ptr(Xs), M, flags, _ptr(lab), _ptr(pred),
-                                                _ptr(var), _ptr(cut), C.byref(ps)))
-        d = scalars_to_dict(ps)
-        d.update(prediction=None if pred is None else pred.view(np.complex128), variance=var,
-                 cutoff=None if cut is None else cut.view(np.complex128))
-        return d
+        return self._predict("complex", fit, Xs, flags, labels, want)
 
     # ---- objective / NLML ------------------------------------------------------------------------------------
     def loose_function(self, x, X, y, X_extra, y_extra, want_grad=True):
@@ -820,7 +792,7 @@ class Api:
         val = C.c_double()
         grad = np.empty(len(x)) if want_grad else None
         self._check(self._fn("loose_function")(*self._c(), _ptr(x), len(x), _ptr(X), _ptr(yy), len(X), _ptr(Xe), _ptr(ye),
-                                               len(Xe), C.cast(C.byref(val), _dp), _ptr(grad)))
+                                               len(Xe), C.byref(val), _ptr(grad)))
         return val.value, grad
 
     def objective(self, X, y, X_extra, y_extra):
@@ -839,7 +811,7 @@ class Api:
         assert len(x) in (4, 5)
         val = C.c_double()
         grad = np.empty(len(x)) if want_grad else None
-        self._check(self._fn("nlml" if len(x) == 4 else "nlml_cross")(*self._c(), _ptr(x), _ptr(X), _ptr(y), len(X), C.cast(C.byref(val), _dp), _ptr(grad)))
+        self._check(self._fn("nlml" if len(x) == 4 else "nlml_cross")(*self._c(), _ptr(x), _ptr(X), _ptr(y), len(X), C.byref(val), _ptr(grad)))
         return val.value, grad
 
     def nlml_predict(self, x, X, y, Xs):

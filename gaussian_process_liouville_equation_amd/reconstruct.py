@@ -12,7 +12,6 @@ DESIGN.md §13).
 
 The state is num_pes^2 real planes (SuperMatrix, test/io.cpp:25-72): plane q = row * num_pes + col is Re rho_ii, Re rho_ij (row < col) or
 Im rho_ij (row > col)."""
-import ctypes as C
 import math
 import os
 import time
@@ -87,8 +86,6 @@ def optimize(api, X, y, start, lower, upper, maxeval=0):
     """gpr.cpp:535-643 for one plane: the library's Nelder-Mead on the NLML value, then its augmented-Lagrangian search without constraints
     (one projected-BFGS pass) on value + gradient, from the first search's minimiser.  gple_nlml keeps the reference's half gradient on the two
     kernel weights (gpr.cpp:425, 432): they are doubled here.  -> (hyper-parameters, NLML there, evaluations)"""
-    lib = api.lib
-    dp_ = _capi._dp
     count = [0]
 
     def value(xs, want_grad):
@@ -101,27 +98,10 @@ def optimize(api, X, y, start, lower, upper, maxeval=0):
             g[:2] *= 2.0
         return v, g
 
-    def f_cb(n, xp, gp, data):
-        v, g = value([xp[i] for i in range(n)], bool(gp))
-        if gp:
-            for i in range(n):
-                gp[i] = g[i]
-        return v
-
-    cb = _capi.OBJECTIVE_FN(f_cb)
-    hc = _capi.CONSTRAINT_FN(lambda m, rp, n, xp, gp, data: None)
-    xv, lb, ub = _capi._f64(start).copy(), _capi._f64(lower), _capi._f64(upper)
-    f, ne = C.c_double(), C.c_int()
     opt = _options(maxeval)
-    lib.gple_minimize_neldermead.argtypes = [_capi.OBJECTIVE_FN, C.c_void_p, C.c_uint, dp_, dp_, C.POINTER(_capi.OptOptions), dp_, dp_, C.POINTER(C.c_int)]
-    st = lib.gple_minimize_neldermead(cb, None, 4, _capi._ptr(lb), _capi._ptr(ub), C.byref(opt), _capi._ptr(xv), C.cast(C.byref(f), dp_), C.byref(ne))
-    if st != _capi.GPLE_OK:
-        raise _capi.GpleError(f"gple_minimize_neldermead: status {st}")
-    lib.gple_minimize_auglag_eq.argtypes = [_capi.OBJECTIVE_FN, C.c_void_p, _capi.CONSTRAINT_FN, C.c_void_p, C.c_uint, C.c_uint, dp_, dp_,
-                                            C.POINTER(_capi.OptOptions), dp_, dp_, C.POINTER(C.c_int)]
-    st = lib.gple_minimize_auglag_eq(cb, None, hc, None, 0, 4, _capi._ptr(lb), _capi._ptr(ub), C.byref(opt), _capi._ptr(xv), C.cast(C.byref(f), dp_), C.byref(ne))
-    if st != _capi.GPLE_OK:
-        raise _capi.GpleError(f"gple_minimize_auglag_eq: status {st}")
+    xv, _, _ = _capi.minimize_neldermead(api.lib, lambda xs: value(xs, False)[0], start, lower, upper, options=opt)
+    xv, _, _ = _capi.minimize_auglag_eq(api.lib, value, lambda xs, want_grad: ((), ()), 0, xv, lower, upper, options=opt)
+    xv = np.array(xv)
     return xv, value(xv, False)[0], count[0]  # "Best Combination": the value once more at the result (gpr.cpp:633)
 
 

@@ -64,7 +64,6 @@ def main():
     api = pkg.open_api(0)
     api.enable_timing(True)
     lib = api.lib
-    lib.gple_nlml_predict.argtypes = [C.c_void_p, _capi._dp, _capi._dp, _capi._dp, C.c_size_t, _capi._dp, C.c_size_t, C.c_uint, _capi._dp]
     print("| n | N | reconstruct + pred ms | reconstruct ms | nlml_predict route ms | old / new | bound | share of bound (with pred) |")
     print("|---|---|---|---|---|---|---|---|")
     for n in [int(v) for v in a.sizes.split(",")]:

@@ -19,13 +19,59 @@ def test_header_and_binding_agree():
     assert sorted("gple_" + n for n in _capi.GPLE_SYMBOLS) == names
 
 
+def header_prototypes():
+    """{name: (result type, [argument declarations])} of every function include/gple.h declares"""
+    text = open(os.path.join(ROOT, "include", "gple.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    found = re.findall(r"^[ \t]*((?:const\s+)?\w+(?:\s+\w+)*\s*\**)\s*\b(gple_\w+)\s*\(([^()]*)\)\s*;", text, flags=re.M)
+    enums = set(re.findall(r"typedef\s+enum\s+(\w+)", text))
+    return {name: (" ".join(res.split()), [" ".join(a.split()) for a in args.split(",")]) for res, name, args in found}, enums
+
+
+INTEGER_TYPES = {"int", "unsigned", "long", "size_t", "unsigned long long", "unsigned char"}
+
+
+def c_class(declaration, enums):
+    """pointer / integer / double of one C parameter declaration `type name`; enums and size_t / unsigned long long are integers, every other
+    type name that is not double (handles, structs, the callback typedefs) is a pointer"""
+    if "*" in declaration or "[" in declaration:
+        return "pointer"
+    type_name = " ".join(w for w in declaration.split()[:-1] if w != "const")
+    return "double" if type_name == "double" else "integer" if type_name in INTEGER_TYPES | enums else "pointer"
+
+
+def ctypes_class(t):
+    if t is ctypes.c_double:
+        return "double"
+    if t in (ctypes.c_int, ctypes.c_uint, ctypes.c_long, ctypes.c_size_t, ctypes.c_ulonglong):
+        return "integer"
+    assert t in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(t, (ctypes._Pointer, ctypes._CFuncPtr)), t
+    return "pointer"
+
+
+def test_declared_signatures_match_the_header():
+    """Every function of include/gple.h carries, once the library is loaded, as many argument types as its prototype has parameters, each of
+    the prototype's class (pointer / integer / double), and the prototype's result type"""
+    import gaussian_process_liouville_equation_amd as pkg
+
+    prototypes, enums = header_prototypes()
+    assert sorted(prototypes) == declared_functions()
+    lib = pkg.load_library()
+    results = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "const char*": ctypes.c_char_p}
+    for name, (result, params) in prototypes.items():
+        f = getattr(lib, name)
+        assert f.restype is results[result.replace(" *", "*")], name
+        assert f.argtypes is not None and len(f.argtypes) == len(params), (name, f.argtypes, params)
+        for k, (t, declaration) in enumerate(zip(f.argtypes, params)):
+            assert ctypes_class(t) == c_class(declaration, enums), (name, k, t, declaration)
+
+
 def test_hip_library_exports_every_declared_symbol():
     import gaussian_process_liouville_equation_amd as pkg
 
     lib = pkg.load_library()  # no HIP call happens at load time, so this works on a CPU-only machine
     for name in declared_functions():
         assert hasattr(lib, name), name
-    lib.gple_status_string.restype = ctypes.c_char_p
     assert lib.gple_status_string(0) == b"ok"
 
 

@@ -107,7 +107,6 @@ def test_weighted_deal_host_mirror_matches_the_library():
     import ctypes as C
     import gaussian_process_liouville_equation_amd as pkg
     lib = pkg.load_library()
-    lib.gple_deal_share.argtypes = [C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_int)] + [C.POINTER(C.c_size_t)] * 3
     for M in (1, 127, 128, 129, 1000, 8192 + 77, 65537):
         for weights in ([1], [1, 1], [1, 1, 1], [3, 0, 5], [0, 0, 64], [27, 27, 10, 0, 0, 0, 0, 0], [0, 44, 20, 0]):
             world = len(weights)

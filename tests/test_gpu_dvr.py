@@ -181,9 +181,6 @@ def test_wigner_determinism_and_device_pointers(gpu):
 
 def test_invalid_arguments(gpu):
     fh, fp, fw = gpu.lib.gple_dvr_hamiltonian, gpu.lib.gple_dvr_propagate, gpu.lib.gple_wigner
-    gpu.dvr_hamiltonian(2, 1, 0, -5.0, 0.1, 11, 2000.0)  # declares the argument types
-    gpu.dvr_propagate(2, 2, np.eye(4), np.zeros(4), np.zeros(4), [0.0])
-    gpu.wigner(2, 0, -5.0, 0.1, np.linspace(0, 1, 3), np.zeros((1, 8)))
     H = np.empty(64 * 64)
     ptr = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
     for num_pes, model, boundary, n in ((2, 1, 2, 16), (1, 1, 0, 16), (4, 1, 0, 16), (2, 3, 0, 16), (2, 1, -1, 16), (2, 1, 0, 1), (3, 4, 1, 16)):

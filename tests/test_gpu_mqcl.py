@@ -156,7 +156,6 @@ def test_bad_arguments(gpu):
     rho = np.zeros(2 * 9 * n * n)
     px, pr = x.ctypes.data_as(dp_), rho.ctypes.data_as(dp_)
     ev = lib.gple_mqcl_evolve
-    ev.argtypes = [C.c_void_p, C.c_int, C.c_int, dp_, dp_, C.c_size_t, C.c_double, C.c_double, C.c_double, C.c_double, C.c_size_t, C.c_uint, dp_]
     assert ev(ctx, 2, 1, px, px, n, 2000.0, 2.0, 2.0, 0.1, 1, 0, pr) == 0
     assert ev(ctx, 4, 1, px, px, n, 2000.0, 2.0, 2.0, 0.1, 1, 0, pr) == BAD_ARG       # num_pes 4
     assert ev(ctx, 2, 3, px, px, n, 2000.0, 2.0, 2.0, 0.1, 1, 0, pr) == BAD_ARG       # TSAC at two levels
@@ -166,14 +165,12 @@ def test_bad_arguments(gpu):
     assert ev(ctx, 2, 1, px, px, n, 0.0, 2.0, 2.0, 0.1, 1, 0, pr) == BAD_ARG          # mass <= 0
     assert ev(ctx, 2, 1, px, px, n, -1.0, 2.0, 2.0, 0.1, 1, 0, pr) == BAD_ARG
     tf = lib.gple_mqcl_transform
-    tf.argtypes = [C.c_void_p, C.c_int, C.c_int, dp_, C.c_size_t, C.c_int, C.c_int, C.c_uint, dp_, dp_]
     assert tf(ctx, 3, 3, px, n, 0, 1, 0, pr, pr) == 0
     assert tf(ctx, 2, 3, px, n, 0, 1, 0, pr, pr) == BAD_ARG
     assert tf(ctx, 2, 1, px, n, 0, 3, 0, pr, pr) == BAD_ARG
     assert tf(ctx, 2, 1, px, 4097, 0, 1, 0, pr, pr) == BAD_ARG
     assert tf(ctx, 2, 1, px, n, 0, 1, 0, None, pr) == BAD_ARG
     ob = lib.gple_mqcl_observe
-    ob.argtypes = [C.c_void_p, C.c_int, C.c_int, dp_, dp_, C.c_size_t, C.c_double, C.c_double, C.c_double, C.c_uint, dp_, dp_, dp_, dp_]
     out = np.zeros(8)
     po = out.ctypes.data_as(dp_)
     assert ob(ctx, 2, 1, px, px, n, 2000.0, 0.1, 0.1, 0, pr, None, po, po) == 0

@@ -24,7 +24,6 @@ def _sharded(api, fit, Xs, rank, world, comm, cplx, device=False):
     M = len(Xs)
     ow = 2 if cplx else 1
     fn = api.lib.gple_complex_predict_sharded if cplx else api.lib.gple_real_predict_sharded
-    fn.argtypes = [C.c_void_p, C.c_void_p, _dp, C.c_size_t, C.c_uint, C.c_int, C.c_int, C.c_void_p, _dp, _dp, _dp]
     Xs = np.ascontiguousarray(Xs)
     if device:
         import torch
@@ -43,7 +42,6 @@ def _sharded(api, fit, Xs, rank, world, comm, cplx, device=False):
 
 def test_shard_bounds_match_the_python_partition(gpu):
     lo, hi, per = C.c_size_t(), C.c_size_t(), C.c_size_t()
-    gpu.lib.gple_shard_bounds.argtypes = [C.c_size_t, C.c_int, C.c_int] + [C.POINTER(C.c_size_t)] * 3
     for M in (0, 1, 7, 64, 65537):
         for world in (1, 2, 3, 8):
             for r in range(world):
@@ -88,7 +86,6 @@ def test_sharded_predict_between_threads(gpu, world, cplx, device):
     fake.fake_comm_create.argtypes = [C.c_void_p, C.c_int]
     fake.fake_comm_destroy.argtypes = [C.c_void_p]
     fake.fake_group_destroy.argtypes = [C.c_void_p]
-    gpu.lib.gple_set_allgather_function.argtypes = [C.c_void_p]
     gpu.lib.gple_set_allgather_function(C.cast(fake.fake_allgather, C.c_void_p))
     try:
         M = 1001  # 8 blocks of 128, the last one short: the ranks hold different numbers of points
@@ -147,11 +144,8 @@ X, y, Xs = parity.synthetic_real(64, 300, 3)
 fit = api.real_fit([1.0, 0.7086, 0.7056, 1e-2], X, y, 0)
 dp = C.POINTER(C.c_double)
 fn = api.lib.gple_real_predict_sharded
-fn.argtypes = [C.c_void_p, C.c_void_p, dp, C.c_size_t, C.c_uint, C.c_int, C.c_int, C.c_void_p, dp, dp, dp]
 out = np.empty(300)
 st = fn(api.ctx, fit.handle, np.ascontiguousarray(Xs).ctypes.data_as(dp), 300, 0, 0, 2, C.c_void_p(1), out.ctypes.data_as(dp), None, None)
-api.lib.gple_ctx_last_error.restype = C.c_char_p
-api.lib.gple_ctx_last_error.argtypes = [C.c_void_p]
 msg = api.lib.gple_ctx_last_error(api.ctx)
 print("STATUS", st, msg.decode())
 ''' % ROOT
@@ -178,7 +172,6 @@ def test_weighted_deal_between_threads(gpu, weights, cplx):
     fake.fake_comm_create.argtypes = [C.c_void_p, C.c_int]
     fake.fake_comm_destroy.argtypes = [C.c_void_p]
     fake.fake_group_destroy.argtypes = [C.c_void_p]
-    gpu.lib.gple_set_allgather_function.argtypes = [C.c_void_p]
     gpu.lib.gple_set_allgather_function(C.cast(fake.fake_allgather, C.c_void_p))
     try:
         M = 2000  # 16 blocks, the last one short
@@ -205,7 +198,6 @@ def test_weighted_deal_between_threads(gpu, weights, cplx):
                 comm = fake.fake_comm_create(group, r)
                 mean, var, cut = np.empty(ow * M), np.empty(M), np.empty(ow * M)
                 fn = api.lib.gple_complex_predict_dealt if cplx else api.lib.gple_real_predict_dealt
-                fn.argtypes = [C.c_void_p, C.c_void_p, _dp, C.c_size_t, C.c_uint, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_void_p, _dp, _dp, _dp]
                 st = fn(api.ctx, fit.handle if fit else None, np.ascontiguousarray(Xs).ctypes.data_as(_dp), M, 0, r, world, (C.c_int * world)(*weights), comm,
                         mean.ctypes.data_as(_dp), var.ctypes.data_as(_dp), cut.ctypes.data_as(_dp))
                 assert st == 0, (st, api.lib.gple_ctx_last_error(api.ctx))
@@ -225,7 +217,6 @@ def test_weighted_deal_between_threads(gpu, weights, cplx):
             assert np.array_equal(mean, ref["prediction"]) and np.array_equal(var, ref["variance"]) and np.array_equal(cut, ref["cutoff"])
         # a rank with a share but without the fit is a caller error, not a hang
         fn = gpu.lib.gple_real_predict_dealt
-        fn.argtypes = [C.c_void_p, C.c_void_p, _dp, C.c_size_t, C.c_uint, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_void_p, _dp, _dp, _dp]
         assert fn(gpu.ctx, None, np.ascontiguousarray(Xs).ctypes.data_as(_dp), M, 0, 0, 2, (C.c_int * 2)(1, 1), C.c_void_p(1), None, None, None) == 1
     finally:
         gpu.lib.gple_set_allgather_function(None)

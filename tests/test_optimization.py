@@ -106,7 +106,6 @@ def test_direct_l_known_answers():
         x = np.array(x_fixed if x_fixed is not None else [0.0] * n, dtype=float)
         fv, ne, dp = C.c_double(), C.c_int(), C.POINTER(C.c_double)
         o = c.OptOptions(1e-9, ftol, 1e-15, 0.0, 0.5, maxeval)
-        lib.gple_minimize_direct_l.argtypes = [c.OBJECTIVE_FN, C.c_void_p, C.c_uint, dp, dp, C.POINTER(c.OptOptions), dp, dp, C.POINTER(C.c_int)]
         st = lib.gple_minimize_direct_l(cb, None, n, np.array(lb, float).ctypes.data_as(dp), np.array(ub, float).ctypes.data_as(dp), C.byref(o), x.ctypes.data_as(dp),
                                         C.cast(C.byref(fv), dp), C.byref(ne))
         return st, x, fv.value, ne.value
