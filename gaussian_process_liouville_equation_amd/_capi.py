@@ -146,6 +146,11 @@ class ReconPlane(C.Structure):
     _fields_ = [("x", C.c_double * 4), ("X", C.POINTER(C.c_double)), ("b", C.POINTER(C.c_double)), ("N", C.c_size_t)]
 
 
+class ReconCrossPlane(C.Structure):
+    """gple_recon_cross_plane: the same for the cross-term kernel x = (w_d, w_g, a, c, b)"""
+    _fields_ = [("x", C.c_double * 5), ("X", C.POINTER(C.c_double)), ("b", C.POINTER(C.c_double)), ("N", C.c_size_t)]
+
+
 class PredictScalars(C.Structure):
     _fields_ = [("error", C.c_double), ("error_derivative", C.c_double * 8)]
 
@@ -313,6 +318,8 @@ def _signatures():
         "grid_survey": (st, [CTX, i, i, _dp, _dp, sz, _dp, sz, d, d, d, u, _dp]),
         "grid_select": (st, [CTX, i, _dp, _dp, sz, _dp, sz, i, i, sz, ull, u, ip, _dp, _dp, szp]),
         "grid_reconstruct": (st, [CTX, i, i, _dp, _dp, sz, _dp, sz, d, d, d, C.POINTER(ReconPlane), _dp, u, _dp, _dp]),
+        "nlml_cross_weights": (st, [CTX, _dp, _dp, _dp, sz, u, _dp]),
+        "grid_reconstruct_cross": (st, [CTX, i, i, _dp, _dp, sz, _dp, sz, d, d, d, C.POINTER(ReconCrossPlane), _dp, u, _dp, _dp]),
         # csrc/gple_debug.h: the one debug entry point the binding itself calls
         "debug_last_contraction_kernel": (C.c_char_p, [CTX]),
     }
@@ -651,17 +658,24 @@ class Api:
     # ---- reconstruction of a gridded density with the NLML GP (test/main_evolve.cpp; gple_nlml_weights / gple_grid_*) -------------------------
     SURVEY_FIELDS = ("max", "min", "weight", "argmax", "population", "potential", "kinetic")
 
-    def nlml_weights(self, x, X, y):
-        """gple_nlml_weights: b = K^-1 y of the NOCROSS kernel x = (w_d, w_g, a_x, a_p); numpy in -> numpy out, device tensors in -> device tensor out"""
+    def _weights(self, fn, width, x, X, y):
         x = _f64(x)
-        assert len(x) == 4
+        assert len(x) == width
         if not _on_device(X):
             X, y = _points(X), _f64(y)
         N = int(X.shape[0])
         b = _like(X, N)
         (pX, py, pb), flags = _io(X, y, b)
-        self._check(self.lib.gple_nlml_weights(self.ctx, _ptr(x), pX, py, N, flags, pb))
+        self._check(fn(self.ctx, _ptr(x), pX, py, N, flags, pb))
         return b
+
+    def nlml_weights(self, x, X, y):
+        """gple_nlml_weights: b = K^-1 y of the NOCROSS kernel x = (w_d, w_g, a_x, a_p); numpy in -> numpy out, device tensors in -> device tensor out"""
+        return self._weights(self.lib.gple_nlml_weights, 4, x, X, y)
+
+    def nlml_cross_weights(self, x, X, y):
+        """gple_nlml_cross_weights: the same for the cross-term kernel x = (w_d, w_g, a, c, b)"""
+        return self._weights(self.lib.gple_nlml_cross_weights, 5, x, X, y)
 
     def grid_survey(self, num_pes, model, rho, x, p, mass, dx, dp):
         """gple_grid_survey: (num_pes^2, 8) per real plane q = row * num_pes + col: max, min, sum |v|, row-major index of the first maximum above 0
@@ -684,34 +698,43 @@ class Api:
                                               flags, C.cast(pc, C.POINTER(C.c_int)), pX, py, C.byref(K)))
         return cells, X, y, K.value
 
-    def grid_reconstruct(self, num_pes, model, rho, x, p, mass, dx, dp, planes, scale=None, want_pred=True):
-        """gple_grid_reconstruct: planes = num_pes^2 entries (x (4,), X (N, 2), b (N,)) or None (the plane is predicted as 0), on the side rho lives
-        on; scale: num_pes^2 factors or None.  -> (pred (num_pes^2, nx, np) or None, sums (num_pes^2, 6): sum (c mu - v)^2, population, potential and
-        kinetic energy of c mu on diagonal planes, sum (c mu)^2, sum c mu v)"""
+    def _reconstruct(self, fn, plane_type, width, num_pes, model, rho, x, p, mass, dx, dp, planes, scale, want_pred):
         rho, x, p = _rho(rho, num_pes), _axis(x), _axis(p)
         nq = num_pes * num_pes
         if len(planes) != nq:
             raise ValueError("planes needs num_pes^2 entries")
         pred = _like(rho, (nq, int(x.shape[0]), int(p.shape[0]))) if want_pred else None
         sums = _like(rho, (nq, 6))
-        arr, keep = (ReconPlane * nq)(), []
+        arr, keep = (plane_type * nq)(), []
         for k, pl in enumerate(planes):
             if pl is None:
                 continue
             xk, Xk, bk = pl
+            if len(xk) != width:
+                raise ValueError(f"a plane's kernel needs {width} hyper-parameters")
             if not _on_device(Xk):
                 Xk, bk = _points(Xk), _f64(bk)
             (pX, pb, _), _ = _io(Xk, bk, rho)  # raises unless the plane's arrays live where rho does
             keep.append((Xk, bk))
-            arr[k].x = (C.c_double * 4)(*[float(v) for v in xk])
+            arr[k].x = (C.c_double * width)(*[float(v) for v in xk])
             arr[k].X, arr[k].b, arr[k].N = pX, pb, int(Xk.shape[0])
         sc = None if scale is None else _f64(scale)
         if sc is not None and sc.shape != (nq,):
             raise ValueError("scale needs num_pes^2 entries")
         (pr, px, pp, ppred, ps), flags = _io(rho, x, p, pred, sums)
-        self._check(self.lib.gple_grid_reconstruct(self.ctx, int(num_pes), int(model), pr, px, int(x.shape[0]), pp, int(p.shape[0]), float(mass), float(dx), float(dp),
-                                                   arr, _ptr(sc), flags, ppred, ps))
+        self._check(fn(self.ctx, int(num_pes), int(model), pr, px, int(x.shape[0]), pp, int(p.shape[0]), float(mass), float(dx), float(dp), arr, _ptr(sc), flags,
+                       ppred, ps))
         return pred, sums
+
+    def grid_reconstruct(self, num_pes, model, rho, x, p, mass, dx, dp, planes, scale=None, want_pred=True):
+        """gple_grid_reconstruct: planes = num_pes^2 entries (x (4,), X (N, 2), b (N,)) or None (the plane is predicted as 0), on the side rho lives
+        on; scale: num_pes^2 factors or None.  -> (pred (num_pes^2, nx, np) or None, sums (num_pes^2, 6): sum (c mu - v)^2, population, potential and
+        kinetic energy of c mu on diagonal planes, sum (c mu)^2, sum c mu v)"""
+        return self._reconstruct(self.lib.gple_grid_reconstruct, ReconPlane, 4, num_pes, model, rho, x, p, mass, dx, dp, planes, scale, want_pred)
+
+    def grid_reconstruct_cross(self, num_pes, model, rho, x, p, mass, dx, dp, planes, scale=None, want_pred=True):
+        """gple_grid_reconstruct_cross: the same with the cross-term kernel, x (5,) = (w_d, w_g, a, c, b) and b from nlml_cross_weights"""
+        return self._reconstruct(self.lib.gple_grid_reconstruct_cross, ReconCrossPlane, 5, num_pes, model, rho, x, p, mass, dx, dp, planes, scale, want_pred)
 
     def evolve_n(self, num_pes, fits, model, mass, dt, density, new_points=False):
         """gple_evolve_n: one tick for an N-level system; fits and density in the packing order (0,0), (1,0), (1,1), (2,0), ...;

@@ -10,6 +10,7 @@ namespace
 	bool recon_model_ok(int num_pes, int model) { return (num_pes == 2 || num_pes == 3) && model >= 0 && model <= (num_pes == 3 ? 3 : 2); }
 	bool recon_grid_ok(size_t nx, size_t np) { return nx >= 2 && np >= 2 && nx <= (1u << 16) && np <= (1u << 16); }
 	bool finite4(const double* x) { return std::isfinite(x[0]) && std::isfinite(x[1]) && std::isfinite(x[2]) && std::isfinite(x[3]); }
+	bool finite5(const double* x) { return finite4(x) && std::isfinite(x[4]); }
 	// an int array of the caller by the call's GPLE_IO_DEVICE bit (Staged is for doubles)
 	struct StagedInts
 	{
@@ -30,18 +31,14 @@ namespace
 		}
 		hipError_t back() { return host ? hipMemcpyAsync(host, p, n * sizeof(int), hipMemcpyDeviceToHost, buf.ctx->stream) : hipSuccess; }
 	};
-} // namespace
-
-extern "C"
-{
-	int gple_nlml_weights(gple_ctx* ctx, const double x[4], const double* X, const double* y, size_t N, unsigned flags, double* b)
+	// b = K^-1 y of the kernel x5 = (w_d, w_g, a, c, b) (c = 0: the diagonal kernel), with the give-up protocol of the one-launch factorisation
+	int nlml_weights(gple_ctx* ctx, const double x5[5], const double* X, const double* y, size_t N, unsigned flags, double* b)
 	{
-		if (!ctx || !x || !X || !y || !b || N == 0 || N > static_cast<size_t>(RECON_MAX_N) || !finite4(x)) return GPLE_ERR_BAD_ARG;
+		if (!ctx || !X || !y || !b || N == 0 || N > static_cast<size_t>(RECON_MAX_N)) return GPLE_ERR_BAD_ARG;
 		GPLE_OPEN(ctx);
 		GPLE_CALL(ctx);
 		hipStream_t st = ctx->stream;
 		const bool dev = flags & GPLE_IO_DEVICE;
-		const double x5[5] = {x[0], x[1], x[2], 0.0, x[3]};
 		for (int attempt = 0;; ++attempt)
 		{
 			CholSchemeScope scheme(attempt == 0 ? ctx->chol_scheme : 0); // second attempt: one launch per panel (a give-up of the one-launch scheme)
@@ -59,6 +56,109 @@ extern "C"
 			if (!again) break;
 		}
 		return GPLE_OK;
+	}
+
+	// one plane of either reconstruction entry point: x has 4 values (w_d, w_g, a_x, a_p) or, for the cross-term kernel, 5 (w_d, w_g, a, c, b)
+	struct PlaneIn
+	{
+		const double* x;
+		const double* X;
+		const double* b;
+		size_t N;
+	};
+	// both kernels share the arguments' rules, the staging, the energies, the records and the final sum; the diagonal kernel contracts two
+	// tables, the cross-term kernel generates its operands inside the contraction (gple_recon.hip)
+	int grid_reconstruct(gple_ctx* ctx, int num_pes, int model, const double* rho, const double* x, size_t nx, const double* p, size_t np, double mass,
+		double dx, double dp, const PlaneIn* planes, bool cross, const double* scale, unsigned flags, double* pred, double* sums)
+	{
+		if (!ctx || !recon_model_ok(num_pes, model) || !recon_grid_ok(nx, np) || !rho || !x || !p || !planes || !sums || !(mass > 0.0) || !std::isfinite(mass) ||
+			!std::isfinite(dx) || !std::isfinite(dp))
+			return GPLE_ERR_BAD_ARG;
+		const int nplanes = num_pes * num_pes;
+		for (int q = 0; q < nplanes; ++q)
+		{
+			const PlaneIn& pl = planes[q];
+			if (pl.N > static_cast<size_t>(RECON_MAX_N) || (pl.N && (!pl.X || !pl.b || !(cross ? finite5(pl.x) : finite4(pl.x)))) || (scale && !std::isfinite(scale[q]))) return GPLE_ERR_BAD_ARG;
+		}
+		GPLE_OPEN(ctx);
+		const bool dev = flags & GPLE_IO_DEVICE;
+		const size_t cells = nx * np;
+		GPLE_CALL(ctx);
+		hipStream_t st = ctx->stream;
+		Staged r(ctx, dev), xs(ctx, dev), ps(ctx, dev), po(ctx, dev), so(ctx, dev);
+		std::vector<std::unique_ptr<Staged>> held;
+		Scratch tables(ctx), energy(ctx), records(ctx);
+		GPLE_HIP(ctx, r.in(rho, 2 * nplanes * cells));
+		GPLE_HIP(ctx, xs.in(x, nx));
+		GPLE_HIP(ctx, ps.in(p, np));
+		GPLE_HIP(ctx, po.out(pred, nplanes * cells));
+		GPLE_HIP(ctx, so.out(sums, static_cast<size_t>(GPLE_RECON_SUMS) * nplanes));
+		ReconArgs g{};
+		g.num_pes = num_pes, g.model = model, g.nx = static_cast<int>(nx), g.np = static_cast<int>(np);
+		g.rows_x = static_cast<int>(round_up(nx, 64)), g.rows_p = static_cast<int>(round_up(np, 64));
+		g.rho = r.p, g.x = xs.p, g.p = ps.p, g.pred = po.p, g.sums = so.p, g.mass = mass, g.dxdp = dx * dp;
+		size_t table_doubles = 0;
+		for (int q = 0; q < nplanes; ++q)
+		{
+			ReconPlane& P = g.plane[q];
+			P.N = static_cast<int>(planes[q].N), P.Npad = static_cast<int>(round_up(planes[q].N, 16));
+			if (!cross) table_doubles += static_cast<size_t>(g.rows_x + g.rows_p) * P.Npad;
+		}
+		GPLE_HIP(ctx, tables.get(table_doubles));
+		GPLE_HIP(ctx, energy.get(nx * num_pes));
+		GPLE_HIP(ctx, records.get(recon_record_doubles(num_pes, g.nx, g.np)));
+		g.energy = energy.p, g.records = records.p;
+		double* next = tables.p;
+		for (int q = 0; q < nplanes; ++q)
+		{
+			ReconPlane& P = g.plane[q];
+			if (P.N == 0) continue;
+			const double* px = planes[q].x;
+			P.coef = (scale ? scale[q] : 1.0) * (px[1] * px[1]), P.ax = px[2], P.ap = px[cross ? 4 : 3], P.cross = cross ? px[3] : 0.0;
+			if (!cross)
+			{
+				P.Ax = next, next += static_cast<size_t>(g.rows_x) * P.Npad;
+				P.Ep = next, next += static_cast<size_t>(g.rows_p) * P.Npad;
+			}
+			for (int k = 0; k < 2; ++k)
+			{
+				held.emplace_back(new Staged(ctx, dev));
+				GPLE_HIP(ctx, held.back()->in(k ? planes[q].b : planes[q].X, k ? planes[q].N : 2 * planes[q].N));
+				(k ? P.b : P.X) = held.back()->p;
+			}
+		}
+		timer_start(ctx, GPLE_TIMER_RECON);
+		if (cross)
+		{
+			GPLE_HIP(ctx, launch_recon_energy(st, g));
+			GPLE_HIP(ctx, launch_recon_cross(st, g));
+		}
+		else
+		{
+			GPLE_HIP(ctx, launch_recon_tables(st, g));
+			GPLE_HIP(ctx, launch_recon_contract(st, g));
+		}
+		GPLE_HIP(ctx, launch_recon_final(st, g));
+		timer_stop(ctx, GPLE_TIMER_RECON);
+		GPLE_HIP(ctx, po.back());
+		GPLE_HIP(ctx, so.back());
+		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
+		return GPLE_OK;
+	}
+} // namespace
+
+extern "C"
+{
+	int gple_nlml_weights(gple_ctx* ctx, const double x[4], const double* X, const double* y, size_t N, unsigned flags, double* b)
+	{
+		if (!x || !finite4(x)) return GPLE_ERR_BAD_ARG;
+		const double x5[5] = {x[0], x[1], x[2], 0.0, x[3]};
+		return nlml_weights(ctx, x5, X, y, N, flags, b);
+	}
+	int gple_nlml_cross_weights(gple_ctx* ctx, const double x[5], const double* X, const double* y, size_t N, unsigned flags, double* b)
+	{
+		if (!x || !finite5(x)) return GPLE_ERR_BAD_ARG;
+		return nlml_weights(ctx, x, X, y, N, flags, b);
 	}
 
 	int gple_grid_survey(gple_ctx* ctx, int num_pes, int model, const double* rho, const double* x, size_t nx, const double* p, size_t np, double mass,
@@ -179,67 +279,17 @@ extern "C"
 	int gple_grid_reconstruct(gple_ctx* ctx, int num_pes, int model, const double* rho, const double* x, size_t nx, const double* p, size_t np, double mass,
 		double dx, double dp, const gple_recon_plane* planes, const double* scale, unsigned flags, double* pred, double* sums)
 	{
-		if (!ctx || !recon_model_ok(num_pes, model) || !recon_grid_ok(nx, np) || !rho || !x || !p || !planes || !sums || !(mass > 0.0) || !std::isfinite(mass) ||
-			!std::isfinite(dx) || !std::isfinite(dp))
-			return GPLE_ERR_BAD_ARG;
-		const int nplanes = num_pes * num_pes;
-		for (int q = 0; q < nplanes; ++q)
-		{
-			const gple_recon_plane& pl = planes[q];
-			if (pl.N > static_cast<size_t>(RECON_MAX_N) || (pl.N && (!pl.X || !pl.b || !finite4(pl.x))) || (scale && !std::isfinite(scale[q]))) return GPLE_ERR_BAD_ARG;
-		}
-		GPLE_OPEN(ctx);
-		const bool dev = flags & GPLE_IO_DEVICE;
-		const size_t cells = nx * np;
-		GPLE_CALL(ctx);
-		hipStream_t st = ctx->stream;
-		Staged r(ctx, dev), xs(ctx, dev), ps(ctx, dev), po(ctx, dev), so(ctx, dev);
-		std::vector<std::unique_ptr<Staged>> held;
-		Scratch tables(ctx), energy(ctx), records(ctx);
-		GPLE_HIP(ctx, r.in(rho, 2 * nplanes * cells));
-		GPLE_HIP(ctx, xs.in(x, nx));
-		GPLE_HIP(ctx, ps.in(p, np));
-		GPLE_HIP(ctx, po.out(pred, nplanes * cells));
-		GPLE_HIP(ctx, so.out(sums, static_cast<size_t>(GPLE_RECON_SUMS) * nplanes));
-		ReconArgs g{};
-		g.num_pes = num_pes, g.model = model, g.nx = static_cast<int>(nx), g.np = static_cast<int>(np);
-		g.rows_x = static_cast<int>(round_up(nx, 64)), g.rows_p = static_cast<int>(round_up(np, 64));
-		g.rho = r.p, g.x = xs.p, g.p = ps.p, g.pred = po.p, g.sums = so.p, g.mass = mass, g.dxdp = dx * dp;
-		size_t table_doubles = 0;
-		for (int q = 0; q < nplanes; ++q)
-		{
-			ReconPlane& P = g.plane[q];
-			P.N = static_cast<int>(planes[q].N), P.Npad = static_cast<int>(round_up(planes[q].N, 16));
-			table_doubles += static_cast<size_t>(g.rows_x + g.rows_p) * P.Npad;
-		}
-		GPLE_HIP(ctx, tables.get(table_doubles));
-		GPLE_HIP(ctx, energy.get(nx * num_pes));
-		GPLE_HIP(ctx, records.get(recon_record_doubles(num_pes, g.nx, g.np)));
-		g.energy = energy.p, g.records = records.p;
-		double* next = tables.p;
-		for (int q = 0; q < nplanes; ++q)
-		{
-			ReconPlane& P = g.plane[q];
-			if (P.N == 0) continue;
-			const double* px = planes[q].x;
-			P.coef = (scale ? scale[q] : 1.0) * (px[1] * px[1]), P.ax = px[2], P.ap = px[3];
-			P.Ax = next, next += static_cast<size_t>(g.rows_x) * P.Npad;
-			P.Ep = next, next += static_cast<size_t>(g.rows_p) * P.Npad;
-			for (int k = 0; k < 2; ++k)
-			{
-				held.emplace_back(new Staged(ctx, dev));
-				GPLE_HIP(ctx, held.back()->in(k ? planes[q].b : planes[q].X, k ? planes[q].N : 2 * planes[q].N));
-				(k ? P.b : P.X) = held.back()->p;
-			}
-		}
-		timer_start(ctx, GPLE_TIMER_RECON);
-		GPLE_HIP(ctx, launch_recon_tables(st, g));
-		GPLE_HIP(ctx, launch_recon_contract(st, g));
-		GPLE_HIP(ctx, launch_recon_final(st, g));
-		timer_stop(ctx, GPLE_TIMER_RECON);
-		GPLE_HIP(ctx, po.back());
-		GPLE_HIP(ctx, so.back());
-		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
-		return GPLE_OK;
+		if (!planes || (num_pes != 2 && num_pes != 3)) return GPLE_ERR_BAD_ARG;
+		PlaneIn in[RECON_MAX_PLANES];
+		for (int q = 0; q < num_pes * num_pes; ++q) in[q] = {planes[q].x, planes[q].X, planes[q].b, planes[q].N};
+		return grid_reconstruct(ctx, num_pes, model, rho, x, nx, p, np, mass, dx, dp, in, false, scale, flags, pred, sums);
+	}
+	int gple_grid_reconstruct_cross(gple_ctx* ctx, int num_pes, int model, const double* rho, const double* x, size_t nx, const double* p, size_t np,
+		double mass, double dx, double dp, const gple_recon_cross_plane* planes, const double* scale, unsigned flags, double* pred, double* sums)
+	{
+		if (!planes || (num_pes != 2 && num_pes != 3)) return GPLE_ERR_BAD_ARG;
+		PlaneIn in[RECON_MAX_PLANES];
+		for (int q = 0; q < num_pes * num_pes; ++q) in[q] = {planes[q].x, planes[q].X, planes[q].b, planes[q].N};
+		return grid_reconstruct(ctx, num_pes, model, rho, x, nx, p, np, mass, dx, dp, in, true, scale, flags, pred, sums);
 	}
 }

@@ -304,9 +304,10 @@ namespace gple
 	{
 		const double* X; // 2 N interleaved
 		const double* b; // N
-		double* Ax;      // rows_x x Npad, k contiguous
-		double* Ep;      // rows_p x Npad
-		double coef, ax, ap; // c w_g^2, a_x, a_p
+		double* Ax;      // rows_x x Npad, k contiguous (diagonal kernel only)
+		double* Ep;      // rows_p x Npad (diagonal kernel only)
+		double coef, ax, ap; // c w_g^2, a_x, a_p (cross-term kernel: the diagonal a, b of W = [[a, 0], [c, b]])
+		double cross;        // the cross weight c of W (cross-term kernel only)
 		int N, Npad;
 	};
 	struct ReconArgs
@@ -325,5 +326,10 @@ namespace gple
 	size_t recon_record_doubles(int num_pes, int nx, int np);
 	hipError_t launch_recon_tables(hipStream_t s, const ReconArgs& g);
 	hipError_t launch_recon_contract(hipStream_t s, const ReconArgs& g);
+	// the cross-term kernel: the energies alone, then one contraction that generates its operands per tile around the tile's
+	// centre (no tables: Ax, Ep unused), the same records; RECON_CROSS_LIMIT = L of the range rule, tiles beyond it take the plain path
+	constexpr double RECON_CROSS_LIMIT = 6.0;
+	hipError_t launch_recon_energy(hipStream_t s, const ReconArgs& g);
+	hipError_t launch_recon_cross(hipStream_t s, const ReconArgs& g);
 	hipError_t launch_recon_final(hipStream_t s, const ReconArgs& g);
 } // namespace gple

@@ -4,6 +4,8 @@
 //   recon_tables_kernel / recon_contract_kernel / recon_final_kernel
 //                      predict_phase (gpr.cpp:654-706) on the tensor grid as the product of two tables on the fp64 MFMA, with
 //                      mean_squared_error (gpr.cpp:994-1005) and the from-grid observables of the prediction as its epilogue
+//   recon_cross_kernel the same for the cross-term kernel W = [[a, 0], [c, b]] (gpr.cpp:99-103, 313-321): the bilinear term factorises per tile
+//                      around the tile's centre, so the two operand slabs are generated inside the contraction
 // The state is num_pes^2 real planes (SuperMatrix, test/io.cpp:25-72): plane (r, c) is Re rho_rc for r <= c and Im rho_cr for r > c, all taken
 // from the elements i <= j of the (re, im) interleaved state.
 #include <climits>
@@ -329,6 +331,67 @@ namespace gple
 			for (int i = 0; i < NP; ++i) energy[static_cast<long>(a) * NP + i] = E[i];
 		}
 
+		// The epilogue of a 64 x 64 tile of element (ie, je) held in the MFMA result layout by four waves (2 x 2): the six terms of every cell of
+		// this lane, in the order (fragment row, fragment column, register), reduced over the wave, then over the waves, into the tile's record
+		template <int NP>
+		__device__ __forceinline__ void recon_epilogue(const ReconArgs& g, const d4 (&acc)[2][2][2], int ie, int je, int a0, int b0, double (*red)[2 * RECON_SUMS])
+		{
+#pragma clang fp contract(off)
+			const int t = threadIdx.x, lane = t & 63, w = t >> 6, wm = w >> 1, wn = w & 1;
+			const int fk = lane >> 4, fr = lane & 15;
+			const int nplanes = ie == je ? 1 : 2;
+			const int qs[2] = {ie * NP + je, je * NP + ie};
+			const long cells = static_cast<long>(g.nx) * g.np;
+			const double* __restrict__ el = g.rho + 2 * (static_cast<long>(ie) * NP + je) * cells;
+			double s[2][RECON_SUMS];
+#pragma unroll
+			for (int c = 0; c < 2; ++c)
+#pragma unroll
+				for (int k = 0; k < RECON_SUMS; ++k) s[c][k] = 0.0;
+#pragma unroll
+			for (int i = 0; i < 2; ++i)
+#pragma unroll
+				for (int j = 0; j < 2; ++j)
+#pragma unroll
+					for (int r = 0; r < 4; ++r)
+					{
+						const int a = a0 + wm * 32 + i * 16 + fk + 4 * r, b = b0 + wn * 32 + j * 16 + fr;
+						if (a >= g.nx || b >= g.np) continue;
+						const long cell = static_cast<long>(a) * g.np + b;
+						const d2 z = *reinterpret_cast<const d2*>(el + 2 * cell);
+						const double v[2] = {z.x, z.y};
+#pragma unroll
+						for (int c = 0; c < 2; ++c)
+						{
+							if (c >= nplanes) break;
+							const double mu = acc[c][i][j][r], d = mu - v[c];
+							s[c][0] += d * d, s[c][4] += mu * mu, s[c][5] += mu * v[c];
+							if (g.pred) g.pred[static_cast<long>(qs[c]) * cells + cell] = mu;
+						}
+						if (ie == je)
+						{
+							const double mu = acc[0][i][j][r], pb = g.p[b];
+							s[0][1] += mu, s[0][2] += mu * g.energy[static_cast<long>(a) * NP + ie], s[0][3] += mu * (pb * pb / 2.0 / g.mass);
+						}
+					}
+#pragma unroll
+			for (int c = 0; c < 2; ++c)
+#pragma unroll
+				for (int k = 0; k < RECON_SUMS; ++k)
+				{
+					double val = s[c][k];
+#pragma unroll
+					for (int o = 32; o > 0; o >>= 1) val += __shfl_xor(val, o);
+					if (lane == 0) red[w][c * RECON_SUMS + k] = val;
+				}
+			__syncthreads();
+			if (t < 2 * RECON_SUMS)
+			{
+				const long tile = (static_cast<long>(blockIdx.z) * gridDim.x + blockIdx.x) * gridDim.y + blockIdx.y;
+				g.records[tile * (2 * RECON_SUMS) + t] = ((red[0][t] + red[1][t]) + red[2][t]) + red[3][t];
+			}
+		}
+
 		// Fragment maps of v_mfma_f64_16x16x4_f64 (gple_gemm.hip): first operand X[i = lane & 15][k = lane >> 4], second Y[k = lane >> 4][j = lane & 15],
 		// result D[i = (lane >> 4) + 4 reg][j = lane & 15].  X = Ax (rows x), Y = Ep^T (columns p): a lane's results are 16 consecutive p of one x.
 		// One workgroup = 4 waves (2 x 2) on a 64 x 64 tile of one element i <= j; each wave a 32 x 32 sub-tile in 2 x 2 fragments, for the element's
@@ -405,59 +468,199 @@ namespace gple
 				}
 			}
 
-			// epilogue: the six terms of every cell of this lane, in the order (fragment row, fragment column, register)
-			{
+			recon_epilogue<NP>(g, acc, ie, je, a0, b0, red);
+		}
+
+		// ---- the cross-term kernel on the grid -------------------------------------------------------------------------------------------------
+		// k = w_g^2 exp(-Q / 2), Q = (a dx + c dp)^2 + (b dp)^2 with dx = x_a - X_i, dp = p_b - P_i (W = [[a, 0], [c, b]]).  Around a tile centre
+		// (x_c, p_c) taken from the grid, with u = x_a - x_c, v = p_b - p_c, s_i = x_c - X_i, t_i = p_c - P_i, g_i = a s_i + c t_i:
+		//   -Q / 2 = [-(a u + g_i)^2 / 2 + g_i^2 / 4] + [-(c v + g_i)^2 / 2 + g_i^2 / 4 - (b (v + t_i))^2 / 2] - a c u v
+		// an x operand (a, i), a p operand (b, i) and a factor of the cell.  With A_U = |a| max|u| and C_V = |c| max|v| over the tile at most
+		// L = RECON_CROSS_LIMIT the operand exponents stay below L^2 / 2 and the cell's inside +-L^2; a (tile, plane) beyond L takes the plain
+		// path, one exponential of the summed argument per (cell, point) into the same accumulators.  The per-point values live in LDS, RCH
+		// points at a time: (g_i, g_i^2 / 4, t_i, coef b_i) for the centred form, (X_i, -, P_i, coef b_i) for the plain one; zeros for i >= N.
+		constexpr int RCH = 512;
+		// exp of an exponent that is never above L^2: below -800 the result is 0 either way, and a NaN from inf - inf of a far point's squares is 0 too
+		__device__ __forceinline__ double exp_floor(double e) { return exp(fmax(e, -800.0)); }
+
+		template <int NP>
+		__global__ void __launch_bounds__(256, 2) recon_cross_kernel(const ReconArgs g)
+		{
 #pragma clang fp contract(off)
-				const long cells = static_cast<long>(g.nx) * g.np;
-				const double* __restrict__ el = g.rho + 2 * (static_cast<long>(ie) * NP + je) * cells;
-				double s[2][RECON_SUMS];
+			__shared__ __attribute__((aligned(16))) double As[RBM * RLS], Es[RBN * RLS];
+			__shared__ __attribute__((aligned(16))) double pg[RCH], pq[RCH], pt[RCH], pw[RCH];
+			__shared__ double red[4][2 * RECON_SUMS];
+			__shared__ double span[2]; // max |u|, max |v| over the tile's cells inside the grid
+			const int t = threadIdx.x, lane = t & 63, w = t >> 6, wm = w >> 1, wn = w & 1;
+			const int fk = lane >> 4, fr = lane & 15;
+			const int a0 = blockIdx.x * RBM, b0 = blockIdx.y * RBN;
+			int ie, je;
+			upper_element(NP, blockIdx.z, ie, je);
+			const int nplanes = ie == je ? 1 : 2;
+			const int qs[2] = {ie * NP + je, je * NP + ie};
+			const int ac = min(a0 + RBM / 2, g.nx - 1), bc = min(b0 + RBN / 2, g.np - 1);
+			const double xc = g.x[ac], pc = g.p[bc];
+
+			if (w < 2)
+			{
+				const int r = (w ? b0 : a0) + lane;
+				double d = r < (w ? g.np : g.nx) ? fabs(w ? g.p[r] - pc : g.x[r] - xc) : 0.0;
 #pragma unroll
-				for (int c = 0; c < 2; ++c)
+				for (int o = 32; o > 0; o >>= 1) d = fmax(d, __shfl_xor(d, o));
+				if (lane == 0) span[w] = d;
+			}
+
+			d4 acc[2][2][2]; // [plane][fragment row][fragment column]
 #pragma unroll
-					for (int k = 0; k < RECON_SUMS; ++k) s[c][k] = 0.0;
+			for (int c = 0; c < 2; ++c)
 #pragma unroll
 				for (int i = 0; i < 2; ++i)
 #pragma unroll
-					for (int j = 0; j < 2; ++j)
+					for (int j = 0; j < 2; ++j) acc[c][i][j] = (d4){0.0, 0.0, 0.0, 0.0};
+
+			// staging: this thread generates rows srow and srow + 32 of both slabs at k = scol, scol + 1; rows beyond the grid are exact zeros
+			const int srow = t >> 3, scol = (t & 7) * 2;
+			double us[2], vs[2];
+			bool inx[2], inp[2];
 #pragma unroll
-						for (int r = 0; r < 4; ++r)
+			for (int r = 0; r < 2; ++r)
+			{
+				const int a = a0 + srow + 32 * r, b = b0 + srow + 32 * r;
+				inx[r] = a < g.nx, inp[r] = b < g.np;
+				us[r] = g.x[inx[r] ? a : ac] - xc, vs[r] = g.p[inp[r] ? b : bc] - pc;
+			}
+			// the plain path: the coordinates of this lane's cells in the MFMA result layout
+			double xa[2][4], pb[2];
+#pragma unroll
+			for (int i = 0; i < 2; ++i)
+#pragma unroll
+				for (int r = 0; r < 4; ++r) xa[i][r] = g.x[min(a0 + wm * 32 + i * 16 + fk + 4 * r, g.nx - 1)];
+#pragma unroll
+			for (int j = 0; j < 2; ++j) pb[j] = g.p[min(b0 + wn * 32 + j * 16 + fr, g.np - 1)];
+			__syncthreads(); // span
+
+			bool centred[2] = {false, false};
+#pragma unroll
+			for (int c = 0; c < 2; ++c)
+			{
+				if (c >= nplanes) break;
+				const ReconPlane& P = g.plane[qs[c]];
+				const double wa = P.ax, wc = P.cross, wb = P.ap;
+				centred[c] = fabs(wa) * span[0] <= RECON_CROSS_LIMIT && fabs(wc) * span[1] <= RECON_CROSS_LIMIT;
+				const double au[2] = {wa * us[0], wa * us[1]}, cv[2] = {wc * vs[0], wc * vs[1]};
+				const int npts = P.N > 0 ? P.Npad : 0;
+				for (int i0 = 0; i0 < npts; i0 += RCH)
+				{
+					const int len = min(RCH, npts - i0);
+					__syncthreads(); // the previous chunk's last reads of the point values and of the slabs
+					for (int k = t; k < len; k += 256)
+					{
+						const int i = i0 + k;
+						double gi = 0.0, qi = 0.0, ti = 0.0, wi = 0.0;
+						if (i < P.N)
 						{
-							const int a = a0 + wm * 32 + i * 16 + fk + 4 * r, b = b0 + wn * 32 + j * 16 + fr;
-							if (a >= g.nx || b >= g.np) continue;
-							const long cell = static_cast<long>(a) * g.np + b;
-							const d2 z = *reinterpret_cast<const d2*>(el + 2 * cell);
-							const double v[2] = {z.x, z.y};
-#pragma unroll
-							for (int c = 0; c < 2; ++c)
+							const double Xi = P.X[2 * i], Pi = P.X[2 * i + 1];
+							wi = P.coef * P.b[i];
+							if (centred[c])
 							{
-								if (c >= nplanes) break;
-								const double mu = acc[c][i][j][r], d = mu - v[c];
-								s[c][0] += d * d, s[c][4] += mu * mu, s[c][5] += mu * v[c];
-								if (g.pred) g.pred[static_cast<long>(qs[c]) * cells + cell] = mu;
+								ti = pc - Pi;
+								gi = wa * (xc - Xi) + wc * ti;
+								qi = 0.25 * (gi * gi);
 							}
-							if (ie == je)
+							else gi = Xi, ti = Pi;
+						}
+						pg[k] = gi, pq[k] = qi, pt[k] = ti, pw[k] = wi;
+					}
+					__syncthreads();
+					if (centred[c])
+					{
+						const int nkb = len / RBK;
+						d2 av[2], ev[2];
+						auto generate = [&](int kb) {
+							const int k = kb * RBK + scol;
+							const d2 gk = *reinterpret_cast<const d2*>(&pg[k]), qk = *reinterpret_cast<const d2*>(&pq[k]);
+							const d2 tk = *reinterpret_cast<const d2*>(&pt[k]), wk = *reinterpret_cast<const d2*>(&pw[k]);
+#pragma unroll
+							for (int r = 0; r < 2; ++r)
+#pragma unroll
+								for (int h = 0; h < 2; ++h)
+								{
+									const double mx = au[r] + gk[h], mp = cv[r] + gk[h], d = wb * (vs[r] + tk[h]);
+									const double ex = -0.5 * (mx * mx) + qk[h];
+									const double ep = (-0.5 * (mp * mp) + qk[h]) - 0.5 * (d * d);
+									av[r][h] = inx[r] ? wk[h] * exp_floor(ex) : 0.0;
+									ev[r][h] = (inp[r] && i0 + k + h < P.N) ? exp_floor(ep) : 0.0;
+								}
+						};
+						auto store = [&]() {
+							*reinterpret_cast<d2*>(&As[srow * RLS + scol]) = av[0], *reinterpret_cast<d2*>(&As[(srow + 32) * RLS + scol]) = av[1];
+							*reinterpret_cast<d2*>(&Es[srow * RLS + scol]) = ev[0], *reinterpret_cast<d2*>(&Es[(srow + 32) * RLS + scol]) = ev[1];
+						};
+						generate(0);
+						store();
+						__syncthreads();
+						for (int kb = 0; kb < nkb; ++kb)
+						{
+							if (kb + 1 < nkb) generate(kb + 1);
+#pragma unroll
+							for (int kk = 0; kk < RBK; kk += 4)
 							{
-								const double mu = acc[0][i][j][r], pb = g.p[b];
-								s[0][1] += mu, s[0][2] += mu * g.energy[static_cast<long>(a) * NP + ie], s[0][3] += mu * (pb * pb / 2.0 / g.mass);
+								double af[2], ef[2];
+#pragma unroll
+								for (int i = 0; i < 2; ++i) af[i] = As[(wm * 32 + i * 16 + fr) * RLS + kk + fk];
+#pragma unroll
+								for (int j = 0; j < 2; ++j) ef[j] = Es[(wn * 32 + j * 16 + fr) * RLS + kk + fk];
+#pragma unroll
+								for (int i = 0; i < 2; ++i)
+#pragma unroll
+									for (int j = 0; j < 2; ++j) acc[c][i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[i], ef[j], acc[c][i][j], 0, 0, 0);
+							}
+							__syncthreads();
+							if (kb + 1 < nkb)
+							{
+								store();
+								__syncthreads();
 							}
 						}
-#pragma unroll
-				for (int c = 0; c < 2; ++c)
-#pragma unroll
-					for (int k = 0; k < RECON_SUMS; ++k)
-					{
-						double val = s[c][k];
-#pragma unroll
-						for (int o = 32; o > 0; o >>= 1) val += __shfl_xor(val, o);
-						if (lane == 0) red[w][c * RECON_SUMS + k] = val;
 					}
-				__syncthreads();
-				if (t < 2 * RECON_SUMS)
+					else
+					{
+						const int n = min(len, P.N - i0);
+						for (int k = 0; k < n; ++k)
+						{
+							const double Xi = pg[k], Pi = pt[k], wi = pw[k];
+#pragma unroll
+							for (int j = 0; j < 2; ++j)
+							{
+								const double dp = pb[j] - Pi, cd = wc * dp, bd = wb * dp, bb = bd * bd;
+#pragma unroll
+								for (int i = 0; i < 2; ++i)
+#pragma unroll
+									for (int r = 0; r < 4; ++r)
+									{
+										const double m = wa * (xa[i][r] - Xi) + cd;
+										acc[c][i][j][r] += wi * exp_floor(-0.5 * (m * m + bb));
+									}
+							}
+						}
+					}
+				}
+				// the cell factor exp(-a c u v) of the centred form
+				if (centred[c])
 				{
-					const long tile = (static_cast<long>(blockIdx.z) * gridDim.x + blockIdx.x) * gridDim.y + blockIdx.y;
-					g.records[tile * (2 * RECON_SUMS) + t] = ((red[0][t] + red[1][t]) + red[2][t]) + red[3][t];
+					const double ac2 = wa * wc;
+#pragma unroll
+					for (int j = 0; j < 2; ++j)
+					{
+						const double v = pb[j] - pc;
+#pragma unroll
+						for (int i = 0; i < 2; ++i)
+#pragma unroll
+							for (int r = 0; r < 4; ++r) acc[c][i][j][r] *= exp(-(ac2 * (xa[i][r] - xc) * v));
+					}
 				}
 			}
+			recon_epilogue<NP>(g, acc, ie, je, a0, b0, red);
 		}
 		// sums[6 q + k]: one workgroup adds the tile records of every plane in a fixed order (a strided pass per thread, then a tree)
 		template <int NP>
@@ -537,14 +740,19 @@ namespace gple
 	{
 		return static_cast<size_t>(num_pes * (num_pes + 1) / 2) * ((nx + RBM - 1) / RBM) * ((np + RBN - 1) / RBN) * (2 * RECON_SUMS);
 	}
+	hipError_t launch_recon_energy(hipStream_t s, const ReconArgs& g)
+	{
+		if (g.num_pes == 2) hipLaunchKernelGGL(recon_energy_kernel<2>, dim3((g.nx + 255) / 256), dim3(256), 0, s, g.model, g.x, g.nx, g.energy);
+		else if (g.num_pes == 3) hipLaunchKernelGGL(recon_energy_kernel<3>, dim3((g.nx + 255) / 256), dim3(256), 0, s, g.model, g.x, g.nx, g.energy);
+		else return hipErrorInvalidValue;
+		return hipGetLastError();
+	}
 	hipError_t launch_recon_tables(hipStream_t s, const ReconArgs& g)
 	{
 		int npad = 0;
 		for (int q = 0; q < g.num_pes * g.num_pes; ++q)
 			if (g.plane[q].N > 0) npad = g.plane[q].Npad > npad ? g.plane[q].Npad : npad;
-		if (g.num_pes == 2) hipLaunchKernelGGL(recon_energy_kernel<2>, dim3((g.nx + 255) / 256), dim3(256), 0, s, g.model, g.x, g.nx, g.energy);
-		else if (g.num_pes == 3) hipLaunchKernelGGL(recon_energy_kernel<3>, dim3((g.nx + 255) / 256), dim3(256), 0, s, g.model, g.x, g.nx, g.energy);
-		else return hipErrorInvalidValue;
+		if (hipError_t e = launch_recon_energy(s, g); e != hipSuccess) return e;
 		if (npad > 0)
 		{
 			const long rows = g.rows_x > g.rows_p ? g.rows_x : g.rows_p;
@@ -558,6 +766,14 @@ namespace gple
 		const dim3 grid(g.rows_x / RBM, g.rows_p / RBN, g.num_pes * (g.num_pes + 1) / 2);
 		if (g.num_pes == 2) hipLaunchKernelGGL(recon_contract_kernel<2>, grid, dim3(256), 0, s, g);
 		else if (g.num_pes == 3) hipLaunchKernelGGL(recon_contract_kernel<3>, grid, dim3(256), 0, s, g);
+		else return hipErrorInvalidValue;
+		return hipGetLastError();
+	}
+	hipError_t launch_recon_cross(hipStream_t s, const ReconArgs& g)
+	{
+		const dim3 grid(g.rows_x / RBM, g.rows_p / RBN, g.num_pes * (g.num_pes + 1) / 2);
+		if (g.num_pes == 2) hipLaunchKernelGGL(recon_cross_kernel<2>, grid, dim3(256), 0, s, g);
+		else if (g.num_pes == 3) hipLaunchKernelGGL(recon_cross_kernel<3>, grid, dim3(256), 0, s, g);
 		else return hipErrorInvalidValue;
 		return hipGetLastError();
 	}

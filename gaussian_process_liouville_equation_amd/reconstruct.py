@@ -1,11 +1,13 @@
 """Reconstruction of an exact phase-space density with the NLML GP: the loop body of the reference's test/main_evolve.cpp:56-179 for one
 state, on the library's device entry points (gple_grid_survey, gple_grid_select, gple_nlml, gple_nlml_weights, gple_grid_reconstruct;
-DESIGN.md §13).
+DESIGN.md §13), for either build of the reference's kernel: kernel="nocross", the diagonal ARD weights (w_d, w_g, a_x, a_p), or
+kernel="cross", the default build's lower-triangular weight matrix W = [[a, 0], [c, b]] with (w_d, w_g, a, c, b) (gple_nlml_cross,
+gple_nlml_cross_weights, gple_grid_reconstruct_cross).
 
     set_initial_value()           gpr.cpp:113-195: bounds and start values of the hyper-parameters (w_d, w_g, a_x, a_p) of every plane
     is_small()                    gpr.cpp:197-210 on the survey's max / min
     optimize()                    gpr.cpp:535-643: Nelder-Mead on the NLML value, then one projected-BFGS pass on value + gradient
-    population_from_gpr() ...     gpr.cpp:715-911 (NOCROSS branches), host numpy on b = K^-1 y
+    population_from_gpr() ...     gpr.cpp:715-911 (both branches), host numpy on b = K^-1 y
     obey_conservation()           gpr.cpp:913-992: the factors of the diagonal planes
     reconstruct()                 survey -> is_small -> select -> optimise -> weights -> reconstruct -> obey_conservation -> reconstruct(scale)
     run_mqcl()                    the exact MQCLE run of exact_mqcl.run with a reconstruction at every output time; log.txt, choose.txt, sim.txt
@@ -26,6 +28,13 @@ DIAG_MIN, DIAG_MAX = 1e-8, 1e-5    # gpr.cpp:138-139
 GAUSS_MIN, GAUSS_MAX = 1e-4, 1.0   # gpr.cpp:140-141
 XTOL_ABS, INITIAL_STEP = 1e-10, 0.5  # gpr.cpp:592-596
 DBL_MAX = float(np.finfo(np.float64).max)
+KERNELS = {"nocross": 4, "cross": 5}  # hyper-parameters per plane
+
+
+def _width(kernel):
+    if kernel not in KERNELS:
+        raise ValueError('kernel must be "nocross" or "cross"')
+    return KERNELS[kernel]
 
 
 class State:
@@ -62,9 +71,12 @@ def is_small(survey):
     return (survey[:, 0] < SMALL) & (survey[:, 1] > -SMALL)
 
 
-def set_initial_value(survey, x, p, num_pes):
+def set_initial_value(survey, x, p, num_pes, kernel="nocross"):
     """gpr.cpp:113-195 -> (lower, upper, start), each (num_pes^2, 4) in the order (w_d, w_g, a_x, a_p): sigma_p = p[argmax of plane 0] / 20,
-    sigma_x = 0.5 / sigma_p; the ARD weights start at the inverse widths and are bounded below by the inverse box lengths, unbounded above"""
+    sigma_x = 0.5 / sigma_p; the ARD weights start at the inverse widths and are bounded below by the inverse box lengths, unbounded above.
+    kernel="cross": (num_pes^2, 5) in the order (w_d, w_g, a, c, b), a and b as a_x and a_p, the cross weight c starts at 0 and is unbounded
+    both ways (gpr.cpp:143-145, 176-181: its slot keeps the vectors' initial values)"""
+    cross = _width(kernel) == 5
     arg = int(survey[0, 3])
     if arg < 0:
         raise ValueError("plane (0, 0) has no value above 0: the reference's start values are undefined there (gpr.cpp:119-136)")
@@ -74,6 +86,8 @@ def set_initial_value(survey, x, p, num_pes):
     lower = np.tile([DIAG_MIN, GAUSS_MIN, 1.0 / (x.max() - x.min()), 1.0 / (p.max() - p.min())], (nq, 1))
     upper = np.tile([DIAG_MAX, GAUSS_MAX, DBL_MAX, DBL_MAX], (nq, 1))
     start = np.tile([DIAG_MIN, GAUSS_MAX, 1.0 / sigma_x, 1.0 / sigma_p], (nq, 1))
+    if cross:
+        lower, upper, start = (np.insert(a, 3, v, axis=1) for a, v in ((lower, -DBL_MAX), (upper, DBL_MAX), (start, 0.0)))
     return lower, upper, start
 
 
@@ -85,7 +99,8 @@ def _options(maxeval):
 def optimize(api, X, y, start, lower, upper, maxeval=0):
     """gpr.cpp:535-643 for one plane: the library's Nelder-Mead on the NLML value, then its augmented-Lagrangian search without constraints
     (one projected-BFGS pass) on value + gradient, from the first search's minimiser.  gple_nlml keeps the reference's half gradient on the two
-    kernel weights (gpr.cpp:425, 432): they are doubled here.  -> (hyper-parameters, NLML there, evaluations)"""
+    kernel weights (gpr.cpp:425, 432): they are doubled here.  Five start values run the same on gple_nlml_cross (Api.nlml chooses by length).
+    -> (hyper-parameters, NLML there, evaluations)"""
     count = [0]
 
     def value(xs, want_grad):
@@ -106,20 +121,26 @@ def optimize(api, X, y, start, lower, upper, maxeval=0):
 
 
 def population_from_gpr(hyper, b):
-    """gpr.cpp:715-762, NOCROSS: (2 pi)^Dim w_g^2 / (a_x a_p) sum b, Dim = 1"""
-    return 2.0 * math.pi * hyper[1] ** 2 / (hyper[2] * hyper[3]) * float(np.sum(b))
+    """gpr.cpp:715-762: (2 pi)^Dim w_g^2 / (product of the weight matrix's diagonal) sum b, Dim = 1 — a_x a_p, or a b of the five
+    cross-term parameters (:750)"""
+    return 2.0 * math.pi * hyper[1] ** 2 / (hyper[2] * hyper[-1]) * float(np.sum(b))
 
 
 def kinetic_energy_from_gpr(hyper, X, b, mass):
-    """gpr.cpp:853-911, NOCROSS: the same coefficient times sum (P_i^2 + a_p^-2) b_i / 2 mass"""
-    return 2.0 * math.pi * hyper[1] ** 2 / (hyper[2] * hyper[3]) * float(np.dot(X[:, 1] ** 2 + hyper[3] ** -2, b)) / 2.0 / mass
+    """gpr.cpp:853-911: the same coefficient times sum (P_i^2 + a_p^-2) b_i / 2 mass; with five parameters (W W^T)^-1_pp = 1 / b^2 (:896),
+    the same expression on the last parameter"""
+    return 2.0 * math.pi * hyper[1] ** 2 / (hyper[2] * hyper[-1]) * float(np.dot(X[:, 1] ** 2 + hyper[-1] ** -2, b)) / 2.0 / mass
 
 
 def potential_energy_from_gpr(api, num_pes, model, level, hyper, X, b, step_divisor=16):
     """gpr.cpp:765-841: the integral of E_level(x) rho(x) with rho(x) = w_g^2 sqrt(2 pi) / a_p sum b_i exp(-(a_x (x - X_i))^2 / 2).  The reference
     integrates with Boost's Bulirsch-Stoer after x = (1 - t) / t; here: the trapezoid rule on a uniform grid of step 1 / (step_divisor a_x) — never
     above 1 / step_divisor, so that a kernel much wider than the potential's features does not under-sample the energy — over
-    [min X - 40 / a_x, max X + 40 / a_x], beyond which every term is below exp(-800).  The rule converges geometrically for this integrand."""
+    [min X - 40 / a_x, max X + 40 / a_x], beyond which every term is below exp(-800).  The rule converges geometrically for this integrand.
+    Five parameters (w_d, w_g, a, c, b), gpr.cpp:801-806 as the text reads: it takes Characteristic(0, 1), the zero ABOVE the diagonal of the
+    lower-triangular matrix generate_kernels fills (:313-321), where the cross weight c = Characteristic(1, 0) is meant, so its marginal is
+    w_g^2 sqrt(2 pi) / |b| exp(-(a (x - X_i))^2 / 2) — the expression above with a_p = |b| — and not the kernel's true marginal
+    w_g^2 sqrt(2 pi / (b^2 + c^2)) exp(-a^2 b^2 (x - X_i)^2 / (2 (b^2 + c^2))).  Kept as the reference has it."""
     ax = float(hyper[2])
     h = min(1.0 / (step_divisor * ax), 1.0 / step_divisor)
     lo, hi = float(X[:, 0].min()) - 40.0 / ax, float(X[:, 0].max()) + 40.0 / ax
@@ -130,7 +151,8 @@ def potential_energy_from_gpr(api, num_pes, model, level, hyper, X, b, step_divi
     for i0 in range(0, n, 8192):  # bounded memory: 8192 x N exponentials at a time
         d = ax * (xs[i0:i0 + 8192, None] - X[None, :, 0])
         total += float(np.dot(energy[i0:i0 + 8192], np.exp(-0.5 * d * d) @ b))
-    return hyper[1] ** 2 * math.sqrt(2.0 * math.pi) / hyper[3] * total * h
+    ap = hyper[3] if len(hyper) == 4 else abs(hyper[4])  # sqrt(2 pi / b^2)
+    return hyper[1] ** 2 * math.sqrt(2.0 * math.pi) / ap * total * h
 
 
 def obey_conservation(population, energy, small_diag, initial_energy):
@@ -160,14 +182,17 @@ def obey_conservation(population, energy, small_diag, initial_energy):
     return factors, False
 
 
-def reconstruct(api, state, rho, n_points=200, seed=0, maxeval=0, start=None, initial_energy=None, keep_pred=False, log=None):
+def reconstruct(api, state, rho, n_points=200, seed=0, maxeval=0, start=None, initial_energy=None, keep_pred=False, log=None, kernel="nocross"):
     """One pass of main_evolve.cpp:56-179 on the adiabatic state rho ((num_pes, num_pes, nx, np) complex; numpy, or a torch tensor on the
     GPU, which then never leaves it).  start: the previous output time's hyper-parameters (main_evolve.cpp:94), default set_initial_value;
     initial_energy: the conserved energy (main_evolve.cpp:48), default this state's own; maxeval caps each of the two searches (0: the
-    library's defaults).  Returns the record of log.txt and more: nlml, hyper (nq, 4), mse_before / mse_after (nq), factors (nq), singular,
+    library's defaults); kernel: "nocross" (four hyper-parameters per plane) or "cross" (five, the reference's default build).  Returns the
+    record of log.txt and more: nlml, hyper (nq, 4 or 5), mse_before / mse_after (nq), factors (nq), singular,
     is_small (nq), per level exact / grid / gpr population, potential and kinetic energy before and after, features / labels / cells per
     plane, draws, sums_before / sums_after (nq, 6), seconds per phase, and with keep_pred the two predictions (nq, nx, np) on the host."""
     num_pes, model, mass, dx, dp = state.num_pes, state.model, state.mass, state.dx, state.dp
+    width = _width(kernel)
+    nlml_weights, grid_reconstruct = (api.nlml_weights, api.grid_reconstruct) if width == 4 else (api.nlml_cross_weights, api.grid_reconstruct_cross)
     nq = num_pes * num_pes
     x, p = state.grid_like(rho)
     say = log or (lambda *_: None)
@@ -175,8 +200,8 @@ def reconstruct(api, state, rho, n_points=200, seed=0, maxeval=0, start=None, in
     t0 = time.perf_counter()
     survey = _host(api, api.grid_survey(num_pes, model, rho, x, p, mass, dx, dp))
     small = is_small(survey)
-    lower, upper, first = set_initial_value(survey, state.x, state.p, num_pes)
-    hyper = np.array(first if start is None else start, dtype=np.float64).reshape(nq, 4).copy()
+    lower, upper, first = set_initial_value(survey, state.x, state.p, num_pes, kernel)
+    hyper = np.array(first if start is None else start, dtype=np.float64).reshape(nq, width).copy()
     diag = [i * num_pes + i for i in range(num_pes)]
     exact = {"population": survey[diag, 4], "potential": survey[diag, 5], "kinetic": survey[diag, 6]}
     if initial_energy is None:
@@ -200,7 +225,7 @@ def reconstruct(api, state, rho, n_points=200, seed=0, maxeval=0, start=None, in
     clock["optimize"] = time.perf_counter() - t0
 
     t0 = time.perf_counter()
-    weights = [None if small[q] else api.nlml_weights(hyper[q], features[q], labels[q]) for q in range(nq)]
+    weights = [None if small[q] else nlml_weights(hyper[q], features[q], labels[q]) for q in range(nq)]
     on_device = hasattr(rho, "data_ptr")
 
     def planes():
@@ -217,26 +242,28 @@ def reconstruct(api, state, rho, n_points=200, seed=0, maxeval=0, start=None, in
         return out
 
     plane_args = planes()
-    pred_b, sums_b = api.grid_reconstruct(num_pes, model, rho, x, p, mass, dx, dp, plane_args, None, want_pred=keep_pred)
+    pred_b, sums_b = grid_reconstruct(num_pes, model, rho, x, p, mass, dx, dp, plane_args, None, want_pred=keep_pred)
     sums_b = _host(api, sums_b)
 
-    def from_gpr(factor):
+    def from_gpr():
         pop, pot, kin = np.zeros(num_pes), np.zeros(num_pes), np.zeros(num_pes)
         for i, q in enumerate(diag):
             if small[q]:
                 continue
-            b = weights[q] * factor[i]  # K^-1 (c y) = c K^-1 y: the scaled labels' weights (gpr.cpp:952-955, 986-989)
-            pop[i] = population_from_gpr(hyper[q], b)
-            pot[i] = potential_energy_from_gpr(api, num_pes, model, i, hyper[q], features[q], b)
-            kin[i] = kinetic_energy_from_gpr(hyper[q], features[q], b, mass)
+            pop[i] = population_from_gpr(hyper[q], weights[q])
+            pot[i] = potential_energy_from_gpr(api, num_pes, model, i, hyper[q], features[q], weights[q])
+            kin[i] = kinetic_energy_from_gpr(hyper[q], features[q], weights[q], mass)
         return pop, pot, kin
 
-    pop_b, pot_b, kin_b = from_gpr(np.ones(num_pes))
+    pop_b, pot_b, kin_b = from_gpr()
     level_factor, singular = obey_conservation(pop_b, pot_b + kin_b, small[diag], initial_energy)
     factors = np.ones(nq)
     factors[diag] = level_factor
-    pop_a, pot_a, kin_a = from_gpr(level_factor)
-    pred_a, sums_a = api.grid_reconstruct(num_pes, model, rho, x, p, mass, dx, dp, plane_args, factors, want_pred=keep_pred)
+    # The scaled labels' weights are K^-1 (c y) = c K^-1 y (gpr.cpp:952-955, 986-989) and the three numbers are linear in them, so the factor
+    # is applied to the numbers: summing c b_i afresh would round each product, an error of eps sum |b_i|, which a fit with w_d at its lower
+    # bound (a Gram matrix of condition 1e16, weights of 1e6 and more that cancel) lifts above the 1e-10 the two constraints are solved to.
+    pop_a, pot_a, kin_a = level_factor * pop_b, level_factor * pot_b, level_factor * kin_b
+    pred_a, sums_a = grid_reconstruct(num_pes, model, rho, x, p, mass, dx, dp, plane_args, factors, want_pred=keep_pred)
     sums_a = _host(api, sums_a)
     clock["reconstruct"] = time.perf_counter() - t0
 
@@ -254,7 +281,7 @@ def reconstruct(api, state, rho, n_points=200, seed=0, maxeval=0, start=None, in
 
 
 def log_line(t, rec):
-    """One line of log.txt (main_evolve.cpp:135-178): t, NLML sum, the hyper-parameters, per plane MSE without / with the constraints, per level
+    """One line of log.txt (main_evolve.cpp:135-178): t, NLML sum, the hyper-parameters (four or five per plane), per plane MSE without / with the constraints, per level
     exact / grid / parameters population, potential and kinetic energy without and with the constraints"""
     v = [t, rec["nlml"], *rec["hyper"].ravel()]
     for q in range(len(rec["mse_before"])):
@@ -276,13 +303,15 @@ def sim_block(pred):
 
 
 def run_mqcl(api, out_dir=None, model=DAC, num_pes=2, ln_energy=0.0, n_points=200, seed=0, maxeval=0, write_sim=False, max_outputs=None, log=None,
-             **setup_kw):
+             kernel="nocross", **setup_kw):
     """The exact MQCLE run of exact_mqcl.run with the reconstruction of main_evolve.cpp at every output time.  Each output's state is moved to
     the device once and the four reconstruction entry points work on that resident copy.  Writes log.txt, choose.txt and (write_sim) sim.txt
-    in the reference's layouts next to exact_mqcl.run's files (phase.txt is not written: it is what this run replaces).  Returns exact_mqcl.run's
+    in the reference's layouts next to exact_mqcl.run's files (phase.txt is not written: it is what this run replaces).  kernel: "nocross" or
+    "cross", as in reconstruct.  Returns exact_mqcl.run's
     dict with the reconstruction records under "reconstructions"."""
     import torch
     say = log or (lambda *_: None)
+    _width(kernel)
     files, recs, carry = {}, [], {}
     if out_dir is not None:
         os.makedirs(out_dir, exist_ok=True)
@@ -295,7 +324,7 @@ def run_mqcl(api, out_dir=None, model=DAC, num_pes=2, ln_energy=0.0, n_points=20
             carry["state"] = State(api, num_pes, model, s["x"], s["p"], s["mass"])
         dev = torch.from_numpy(np.ascontiguousarray(adia)).cuda()
         rec = reconstruct(api, carry["state"], dev, n_points=n_points, seed=seed + len(recs), maxeval=maxeval, start=carry.get("hyper"),
-                          initial_energy=carry.get("energy"), keep_pred=write_sim, log=log)
+                          initial_energy=carry.get("energy"), keep_pred=write_sim, log=log, kernel=kernel)
         carry["hyper"] = rec["hyper"]
         carry.setdefault("energy", rec["initial_energy"])
         rec["t"] = t

@@ -151,7 +151,7 @@ typedef enum gple_timer {
 	GPLE_TIMER_DERIV_GEMM = 3,     /* the dK * K^-1 MFMA GEMM of a GPLE_CALC_DERIVATIVE fit (kernel.cpp:354); count = its launches */
 	GPLE_TIMER_WIGNER = 4,         /* the MFMA kernel of gple_wigner alone (all T output times of a call); count = its launches */
 	GPLE_TIMER_MQCL = 5,           /* the step kernels of one gple_mqcl_evolve call (all its steps, no set-up); count = its calls */
-	GPLE_TIMER_RECON = 6           /* the device work of one gple_nlml_weights / gple_grid_survey / gple_grid_select / gple_grid_reconstruct call; count = calls */
+	GPLE_TIMER_RECON = 6           /* the device work of one gple_nlml_weights / gple_grid_survey / gple_grid_select / gple_grid_reconstruct call (and of their _cross forms); count = calls */
 } gple_timer;
 int gple_ctx_enable_timing(gple_ctx* ctx, int on);
 /* Synchronises the stream, then: last = milliseconds of the most recent interval; total / count = accumulated since
@@ -471,6 +471,8 @@ int gple_nlml_cross_predict(gple_ctx* ctx, const double x[5], const double* X, c
 /* b = K^-1 y (N values) of the kernel x = (w_d, w_g, a_x, a_p): the KInvLbl of predict_phase and of the three calculate_*_from_gpr
  * (test/gpr.cpp:692, 736, 788, 874) — the Gram, factorisation and solve gple_nlml_predict runs internally.  1 <= N <= 4096. */
 int gple_nlml_weights(gple_ctx* ctx, const double x[4], const double* X, const double* y, size_t N, unsigned flags, double* b);
+/* The same for the cross-term kernel of gple_nlml_cross, x = (w_d, w_g, a, c, b): the weights gple_nlml_cross_predict forms internally. */
+int gple_nlml_cross_weights(gple_ctx* ctx, const double x[5], const double* X, const double* y, size_t N, unsigned flags, double* b);
 /* One pass over the elements i <= j; out[8 q + ...] per plane q: [0] max, [1] min, [2] sum |v| (the `weight` of gpr.cpp:247), [3] row-major
  * index a np + b of the first strict maximum above 0.0 (set_initial_value, gpr.cpp:119-135) as a double, -1 if none; diagonal planes also
  * [4] sum v dx dp, [5] sum_a rowsum_a E_i(x_a) dx dp, [6] sum_b colsum_b p_b^2 / (2 mass) dx dp (calculate_{population, potential_energy,
@@ -509,6 +511,23 @@ typedef struct gple_recon_plane
 #define GPLE_RECON_SUMS 6
 int gple_grid_reconstruct(gple_ctx* ctx, int num_pes, int model, const double* rho, const double* x, size_t nx, const double* p, size_t np, double mass,
 	double dx, double dp, const gple_recon_plane* planes, const double* scale, unsigned flags, double* pred, double* sums);
+/* The same pass for the cross-term kernel of gple_nlml_cross (the reference's default build), x = (w_d, w_g, a, c, b) per plane with the weights
+ * of gple_nlml_cross_weights: mu(x_a, p_b) = sum_i c_q w_g^2 b_i exp(-Q_i / 2), Q_i = (a dx + c dp)^2 + (b dp)^2, dx = x_a - X_i, dp = p_b - P_i.
+ * The bilinear term a c dx dp couples the axes, so no pair of tables exists; per 64 x 64 tile with centre (x_c, p_c) taken from the grid,
+ * u = x_a - x_c, v = p_b - p_c, g_i = a (x_c - X_i) + c (p_c - P_i), it splits into an operand of (a, i), an operand of (b, i) and a factor
+ * exp(-a c u v) of the cell, and the tile is one fp64 MFMA contraction over i whose operands are generated inside the kernel.
+ * A tile of a plane with |a| max|u| or |c| max|v| above 6 (a kernel narrower than about five grid spacings, or strongly sheared) takes one
+ * exponential of the summed argument per (cell, point) instead: every finite x is served.  Arguments, N = 0 planes, scale, pred, sums, flags,
+ * the timer and the bad-argument rules are gple_grid_reconstruct's; two calls on the same input return the same bits, with or without pred. */
+typedef struct gple_recon_cross_plane
+{
+	double x[5];
+	const double* X;
+	const double* b;
+	size_t N;
+} gple_recon_cross_plane;
+int gple_grid_reconstruct_cross(gple_ctx* ctx, int num_pes, int model, const double* rho, const double* x, size_t nx, const double* p, size_t np,
+	double mass, double dx, double dp, const gple_recon_cross_plane* planes, const double* scale, unsigned flags, double* pred, double* sums);
 
 #ifdef __cplusplus
 }

@@ -5,7 +5,13 @@ Gram, factorisation and solve are left out, as gple_nlml_weights' are on the new
 one process.  Prints the markdown table of §13: ms
 with and without the stored prediction, the old route's ms, the ratio, and the new route's share of max(flops / 78.6 TFLOP/s, bytes / 6.3 TB/s).
 
-    python probes/recon_timing.py [--sizes 961,1921,3841] [--points 200,1024] [--reps 5] [--no-old]
+With --cross a second table for the cross-term kernel (gple_grid_reconstruct_cross, x = (w_d, w_g, a, c, b) with c = --shear): its ms with
+and without the stored prediction, the share of its tiles that take the centred (MFMA) form, and its two yardsticks measured in the same
+process, alternated — (a) gple_nlml_cross_predict on the explicit points (GPLE_TIMER_PREDICT alone), the only route the library had for this
+kernel, and (b) gple_grid_reconstruct at the same n and N, the same contraction without exponentials inside it.  --ax replaces a_x = 1 / SX
+in every route (a narrower or wider kernel moves tiles across the range rule |a| max|u| <= 6).
+
+    python probes/recon_timing.py [--sizes 961,1921,3841] [--points 200,1024] [--reps 5] [--no-old] [--cross] [--shear -0.5] [--ax 6.33]
 """
 import argparse
 import ctypes as C
@@ -60,7 +66,14 @@ def main():
     ap.add_argument("--points", default="200,1024")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--no-old", action="store_true")
+    ap.add_argument("--cross", action="store_true")
+    ap.add_argument("--shear", type=float, default=-0.5)
+    ap.add_argument("--ax", type=float, default=HYPER[2])
     a = ap.parse_args()
+    hyper = HYPER.copy()
+    hyper[2] = a.ax
+    hyper5 = np.array([hyper[0], hyper[1], hyper[2], a.shear, hyper[3]])
+    cross_rows = []
     api = pkg.open_api(0)
     api.enable_timing(True)
     lib = api.lib
@@ -81,15 +94,15 @@ def main():
                 cells = np.sort(rng.choice(w.size, size=N, replace=False, p=w / w.sum()))
                 X = np.ascontiguousarray(np.stack([x[cells // n], p[cells % n]], axis=1))
                 y = v.ravel()[cells].copy()
-                b = api.nlml_weights(HYPER, X, y)
+                b = api.nlml_weights(hyper, X, y)
                 host.append((X, y))
-                dev.append((HYPER, torch.from_numpy(X).cuda(), torch.from_numpy(b).cuda()))
+                dev.append((hyper, torch.from_numpy(X).cuda(), torch.from_numpy(b).cuda()))
             t_pred = timed(api, TIMER_RECON, lambda: api.grid_reconstruct(2, 1, dr, dxs, dps, 2000.0, dx, dp, dev, None, want_pred=True), a.reps)
             t_sums = timed(api, TIMER_RECON, lambda: api.grid_reconstruct(2, 1, dr, dxs, dps, 2000.0, dx, dp, dev, None, want_pred=False), a.reps)
 
             def old():
                 for X, y in host:  # the training set is a host argument of gple_nlml_predict; grid points and result stay on the device
-                    api._check(lib.gple_nlml_predict(api.ctx, _capi._ptr(HYPER), _capi._ptr(X), _capi._ptr(y), N, C.cast(grid_pts.data_ptr(), _capi._dp), n * n,
+                    api._check(lib.gple_nlml_predict(api.ctx, _capi._ptr(hyper), _capi._ptr(X), _capi._ptr(y), N, C.cast(grid_pts.data_ptr(), _capi._dp), n * n,
                                                      _capi.IO_DEVICE, C.cast(mean.data_ptr(), _capi._dp)))
             t_old = float("nan") if a.no_old else timed(api, TIMER_PREDICT, old, a.reps)
             npad, rows = 4 * (N + 15) // 16 * 16, (n + 63) // 64 * 64
@@ -98,6 +111,28 @@ def main():
             t_f, t_b = flops / PEAK_FLOPS * 1e3, byts / PEAK_BYTES * 1e3
             print(f"| {n} | {N} | {t_pred:.3f} | {t_sums:.3f} | {t_old:.2f} | {t_old / t_pred:.1f} | {'MFMA' if t_f > t_b else 'HBM'} {max(t_f, t_b):.3f} ms | "
                   f"{max(t_f, t_b) / t_pred:.2f} |", flush=True)
+            if a.cross:
+                cdev = [(hyper5, X, torch.from_numpy(api.nlml_cross_weights(hyper5, hX, hy)).cuda()) for (_, X, _), (hX, hy) in zip(dev, host)]
+                c_pred = timed(api, TIMER_RECON, lambda: api.grid_reconstruct_cross(2, 1, dr, dxs, dps, 2000.0, dx, dp, cdev, None, want_pred=True), a.reps)
+                c_sums = timed(api, TIMER_RECON, lambda: api.grid_reconstruct_cross(2, 1, dr, dxs, dps, 2000.0, dx, dp, cdev, None, want_pred=False), a.reps)
+
+                def explicit():
+                    for X, y in host:
+                        api._check(lib.gple_nlml_cross_predict(api.ctx, _capi._ptr(hyper5), _capi._ptr(X), _capi._ptr(y), N, C.cast(grid_pts.data_ptr(), _capi._dp),
+                                                               n * n, _capi.IO_DEVICE, C.cast(mean.data_ptr(), _capi._dp)))
+                c_old = float("nan") if a.no_old else timed(api, TIMER_PREDICT, explicit, a.reps)
+                b_pred = timed(api, TIMER_RECON, lambda: api.grid_reconstruct(2, 1, dr, dxs, dps, 2000.0, dx, dp, dev, None, want_pred=True), a.reps)
+                tiles = lambda g: [(r0, min(r0 + 64, n), min(r0 + 32, n - 1)) for r0 in range(0, n, 64)]
+                in_x = np.array([abs(hyper5[2]) * np.abs(x[r0:r1] - x[rc]).max() <= 6.0 for r0, r1, rc in tiles(x)])
+                in_p = np.array([abs(hyper5[3]) * np.abs(p[r0:r1] - p[rc]).max() <= 6.0 for r0, r1, rc in tiles(p)])
+                cross_rows.append(f"| {n} | {N} | {c_pred:.3f} | {c_sums:.3f} | {np.outer(in_x, in_p).mean():.2f} | {c_old:.2f} | {c_old / c_pred:.1f} | {b_pred:.3f} | "
+                                  f"{c_pred / b_pred:.2f} |")
+                print("cross " + cross_rows[-1], flush=True)
+    if cross_rows:
+        print(f"\ncross-term kernel, a = {hyper5[2]:.4g}, c = {hyper5[3]:.4g}, b = {hyper5[4]:.4g}")
+        print("| n | N | cross + pred ms | cross ms (sums only) | tiles centred | (a) `gple_nlml_cross_predict` route ms | (a) / cross | (b) `gple_grid_reconstruct` + pred ms | cross / (b) |")
+        print("|---|---|---|---|---|---|---|---|---|")
+        print("\n".join(cross_rows))
     api.close()
 
 
