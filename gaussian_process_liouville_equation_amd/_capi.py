@@ -151,6 +151,20 @@ class ReconCrossPlane(C.Structure):
     _fields_ = [("x", C.c_double * 5), ("X", C.POINTER(C.c_double)), ("b", C.POINTER(C.c_double)), ("N", C.c_size_t)]
 
 
+class NlmlProblem(C.Structure):
+    """gple_nlml_problem: one problem of gple_nlml_batch, x = (w_d, w_g, a_x, a_p, -) or (w_d, w_g, a, c, b)"""
+    _fields_ = [("x", C.c_double * 5), ("X", C.POINTER(C.c_double)), ("y", C.POINTER(C.c_double)), ("N", C.c_size_t)]
+
+
+class NlmlFitPlane(C.Structure):
+    """gple_nlml_fit_plane: training set, start values and box of one plane of gple_nlml_fit_planes"""
+    _fields_ = [("X", C.POINTER(C.c_double)), ("y", C.POINTER(C.c_double)), ("N", C.c_size_t), ("start", C.c_double * 5), ("lb", C.c_double * 5),
+                ("ub", C.c_double * 5)]
+
+
+NLML_BATCH_MAX_N = 256  # GPLE_NLML_BATCH_MAX_N
+
+
 class PredictScalars(C.Structure):
     _fields_ = [("error", C.c_double), ("error_derivative", C.c_double * 8)]
 
@@ -313,6 +327,9 @@ def _signatures():
         "mqcl_transform": (st, [CTX, i, i, _dp, sz, i, i, u, _dp, _dp]),
         "mqcl_evolve": (st, [CTX, i, i, _dp, _dp, sz, d, d, d, d, sz, u, _dp]),
         "mqcl_observe": (st, [CTX, i, i, _dp, _dp, sz, d, d, d, u, _dp, _dp, _dp, _dp]),
+        # many NLML problems in one launch; the search of several planes in lock-step on it
+        "nlml_batch": (st, [CTX, C.POINTER(NlmlProblem), sz, i, u, _dp, _dp, C.POINTER(_dp), ip]),
+        "nlml_fit_planes": (st, [CTX, C.POINTER(NlmlFitPlane), sz, i, opt, _dp, _dp, ip, C.POINTER(_dp)]),
         # reconstruction of a gridded density
         "nlml_weights": (st, [CTX, _dp, _dp, _dp, sz, u, _dp]),
         "grid_survey": (st, [CTX, i, i, _dp, _dp, sz, _dp, sz, d, d, d, u, _dp]),
@@ -836,6 +853,55 @@ class Api:
         grad = np.empty(len(x)) if want_grad else None
         self._check(self._fn("nlml" if len(x) == 4 else "nlml_cross")(*self._c(), _ptr(x), _ptr(X), _ptr(y), len(X), C.byref(val), _ptr(grad)))
         return val.value, grad
+
+    def nlml_batch(self, xs, Xs, ys, want_grad=True, want_weights=False):
+        """gple_nlml_batch: B problems in one launch; xs (B, 4) or (B, 5) hyper-parameters, Xs / ys lists of (N_b, 2) / (N_b,) arrays, or of device
+        tensors (then every result is a device tensor).  -> (values (B,), grads (B, 4 or 5) or None, weights: list of (N_b,) or None, info (B,)
+        int32: 0, or the 1-based column of the first non-positive pivot of a problem whose results are NaN)"""
+        xs = np.atleast_2d(_f64(xs))
+        B, width = xs.shape
+        if width not in (4, 5) or len(Xs) != B or len(ys) != B:
+            raise ValueError("xs must be (B, 4) or (B, 5), with one training set per row")
+        dev = B > 0 and _on_device(Xs[0])
+        if not dev:
+            Xs, ys = [_points(X) for X in Xs], [_f64(y) for y in ys]
+        ref = Xs[0] if dev else None
+        values, info = _like(ref, B), _like(ref, B, np.int32)
+        grads = _like(ref, (B, width)) if want_grad else None
+        weights = [_like(ref, int(X.shape[0])) for X in Xs] if want_weights else None
+        probs = (NlmlProblem * max(1, B))()
+        flags = 0
+        for b in range(B):
+            (pX, py), flags = _io(Xs[b], ys[b])
+            probs[b].x = (C.c_double * 5)(*xs[b], *([0.0] * (5 - width)))
+            probs[b].X, probs[b].y, probs[b].N = pX, py, int(Xs[b].shape[0])
+        wp = None
+        if want_weights:
+            wp = (_dp * max(1, B))(*[_io(w)[0][0] for w in weights])
+        (pv, pg, pi), _ = _io(values, grads, info)
+        self._check(self.lib.gple_nlml_batch(self.ctx, probs, B, int(width == 5), flags, pv, pg, wp, C.cast(pi, C.POINTER(C.c_int))))
+        return values, grads, weights, info
+
+    def nlml_fit_planes(self, planes, cross=False, options=None, want_weights=False):
+        """gple_nlml_fit_planes: planes = list of (X (N, 2), y (N,), start, lower, upper), 4 (cross=False) or 5 values each; options: an OptOptions
+        or None (the library's defaults).  -> (x (P, 4 or 5), f (P,), n_eval (P,) int, weights: list of (N,) or None)"""
+        P, width = len(planes), 5 if cross else 4
+        arr, keep = (NlmlFitPlane * max(1, P))(), []
+        for q, (X, y, start, lower, upper) in enumerate(planes):
+            X, y = _points(X), _f64(y)
+            keep.append((X, y))
+            arr[q].X, arr[q].y, arr[q].N = _ptr(X), _ptr(y), len(X)
+            for name, v in (("start", start), ("lb", lower), ("ub", upper)):
+                v = _f64(v)
+                if v.shape != (width,):
+                    raise ValueError(f"a plane needs {width} start values, lower and upper bounds")
+                setattr(arr[q], name, (C.c_double * 5)(*v, *([0.0] * (5 - width))))
+        x, f, ne = np.empty((P, 5)), np.empty(P), np.zeros(P, dtype=np.int32)
+        weights = [np.empty(len(X)) for X, _ in keep] if want_weights else None
+        wp = (_dp * max(1, P))(*[_ptr(w) for w in weights]) if want_weights else None
+        self._check(self.lib.gple_nlml_fit_planes(self.ctx, arr, P, int(cross), None if options is None else C.byref(options), _ptr(x), _ptr(f),
+                                                  ne.ctypes.data_as(C.POINTER(C.c_int)), wp))
+        return x[:, :width].copy(), f, ne, weights
 
     def nlml_predict(self, x, X, y, Xs):
         x, X, y, Xs = _f64(x), _points(X), _f64(y), _points(Xs)

@@ -4,6 +4,7 @@
 #include <atomic>
 #include <condition_variable>
 #include <cstring>
+#include <functional>
 #include <limits>
 #include <mutex>
 #include <vector>
@@ -266,4 +267,8 @@ namespace gple
 	int nlml_solve(gple_ctx* ctx, const double x[5], const double* X, const double* y, size_t N, Scratch& Xt, Scratch& yd, Scratch& T, Scratch& bvec,
 		Scratch& info, int* n_out, bool dev = false);
 	int nlml_gave_up(gple_ctx* ctx, int attempt, bool* again);
+	// gple_opt.hip: the library's Nelder-Mead with each step's candidates evaluated as one batch (points in, values out)
+	using PointBatchEval = std::function<void(const std::vector<std::vector<double>>&, std::vector<double>&)>;
+	int neldermead_speculative(const PointBatchEval& eval, unsigned n, const double* lb, const double* ub, const gple_opt_options* options, double* x,
+		double* fmin, int* n_eval);
 } // namespace gple

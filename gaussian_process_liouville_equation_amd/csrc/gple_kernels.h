@@ -166,6 +166,29 @@ namespace gple
 	int nlml_predict_ksplit(int M, int N);
 	hipError_t launch_nlml_predict(hipStream_t s, const double* Xs, int M, const double* Xt, int N, const double* b, const double x[5], double* part, double* mean);
 
+	// ---- B independent NLML problems in one launch, one workgroup each (gple_nlml_batch.hip) ---------------------------------
+	constexpr int NLML_BATCH_MAX_N = 256;
+	constexpr unsigned NLML_BATCH_GRAD = 1u; // NlmlBatchProblem::flags: this problem's gradient is wanted
+	struct NlmlBatchProblem
+	{
+		double x[5];     // (w_d, w_g, a, c, b)
+		const double* X; // device, 2 N
+		const double* y; // device, N
+		double* weights; // device, N: b = K^-1 y (nullable)
+		long work;       // this problem's offset into the work pool, nlml_batch_work_doubles(N) doubles
+		int N;
+		unsigned flags;
+	};
+	inline size_t nlml_batch_work_doubles(size_t N)
+	{
+		const size_t n = round_up(N, CHOL_NB);
+		return 2 * n * n; // the Gram that becomes its factor | the inverse factor, transposed
+	}
+	// values (B) | grads (grad_width = 4: (w_d, w_g, a, b), 5: all; per problem, written for NLML_BATCH_GRAD problems) | info (B): 0 or the
+	// 1-based column of the first non-positive pivot, whose problem returns NaN everywhere
+	hipError_t launch_nlml_batch(hipStream_t s, const NlmlBatchProblem* problems, int B, double* work, double* values, double* grads, int grad_width,
+		int* info);
+
 	// ---- step loop around the GP (gple_evolve.hip): Tully models, MQCLE propagation, Metropolis ---------------------------------
 	hipError_t launch_pes(hipStream_t s, const double* x, int M, int model, double* out6);
 	// query-list layout of one tick: off[s] = first point of source element s, qoff[e][s] / qlen[e] = rows of target e's list

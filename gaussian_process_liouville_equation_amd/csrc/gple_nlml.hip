@@ -9,6 +9,7 @@
 // by the entry at :444, off-diagonal entries raw, :448) are restated from the formula comment and the call sites; parity is
 // pinned by the oracle + numpy identities only ("parity unpinned (Shogun)").
 #include "gple_kernels.h"
+#include "gple_nlml_ard.h"
 
 namespace gple
 {
@@ -33,19 +34,6 @@ namespace gple
 				for (int i = 0; i < NT / 64; ++i) tot += red[i];
 			return tot;
 		}
-		// u = W^T (x - y): u0 = a e0 + c e1, u1 = b e1
-		struct ArdW
-		{
-			double a, c, b;
-		};
-		__device__ __forceinline__ double ard(double a0, double a1, double b0, double b1, ArdW w, double* u0 = nullptr, double* u1 = nullptr)
-		{
-			const double e0 = __dsub_rn(a0, b0), e1 = __dsub_rn(a1, b1);
-			const double d0 = __dadd_rn(__dmul_rn(w.a, e0), __dmul_rn(w.c, e1)), d1 = __dmul_rn(w.b, e1);
-			if (u0) *u0 = d0, *u1 = d1;
-			return exp(__ddiv_rn(-__dadd_rn(__dmul_rn(d0, d0), __dmul_rn(d1, d1)), 2.0));
-		}
-
 		// padded training Gram (identity on the padding)
 		__global__ void __launch_bounds__(256) nlml_gram_kernel(const double* __restrict__ Xt, int N, int n, double wd, double wg, ArdW w,
 			double* __restrict__ K)

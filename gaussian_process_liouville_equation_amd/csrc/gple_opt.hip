@@ -426,6 +426,19 @@ namespace
 	}
 } // namespace
 
+namespace gple
+{
+	// Nelder-Mead with every step's candidates — the start simplex, then reflection, expansion and both contractions, or the shrunk vertices —
+	// handed to `eval` as ONE batch (gple_nlml_fit_planes: one launch of the batched NLML evaluator).  The search is nelder_mead itself, which
+	// gple_minimize_neldermead feeds point by point: same decisions, same iterates, same evaluation count.  (declared in gple_capi.h)
+	int neldermead_speculative(const std::function<void(const std::vector<std::vector<double>>&, std::vector<double>&)>& eval, unsigned n,
+		const double* lb, const double* ub, const gple_opt_options* options, double* x, double* fmin, int* n_eval)
+	{
+		if (!eval || !x || !fmin || n == 0) return GPLE_ERR_BAD_ARG;
+		return nelder_mead(eval, n, make_box(n, lb, ub), defaults(options), x, fmin, n_eval);
+	}
+} // namespace gple
+
 extern "C"
 {
 	int gple_minimize_direct_l(gple_objective_fn f, void* data, unsigned n, const double* lb, const double* ub, const gple_opt_options* options, double* x,

@@ -120,6 +120,15 @@ def optimize(api, X, y, start, lower, upper, maxeval=0):
     return xv, value(xv, False)[0], count[0]  # "Best Combination": the value once more at the result (gpr.cpp:633)
 
 
+def optimize_planes(api, sets, starts, lowers, uppers, maxeval=0):
+    """optimize for several planes at once on gple_nlml_fit_planes: sets = [(X, y), ...] with at most _capi.NLML_BATCH_MAX_N points
+    each; the searches run in lock-step inside the library and every round of evaluations is one launch.  Each plane's result is that of the same
+    search on that plane alone.  -> (hyper-parameters (P, 4 or 5), NLML there (P,), evaluations (P,), weights K^-1 y at the result: list of (N,))"""
+    cross = len(starts[0]) == 5
+    planes = [(X, y, start, lower, upper) for (X, y), start, lower, upper in zip(sets, starts, lowers, uppers)]
+    return api.nlml_fit_planes(planes, cross=cross, options=_options(maxeval), want_weights=True)
+
+
 def population_from_gpr(hyper, b):
     """gpr.cpp:715-762: (2 pi)^Dim w_g^2 / (product of the weight matrix's diagonal) sum b, Dim = 1 — a_x a_p, or a b of the five
     cross-term parameters (:750)"""
@@ -182,14 +191,22 @@ def obey_conservation(population, energy, small_diag, initial_energy):
     return factors, False
 
 
-def reconstruct(api, state, rho, n_points=200, seed=0, maxeval=0, start=None, initial_energy=None, keep_pred=False, log=None, kernel="nocross"):
+FITS = ("serial", "batched")
+
+
+def reconstruct(api, state, rho, n_points=200, seed=0, maxeval=0, start=None, initial_energy=None, keep_pred=False, log=None, kernel="nocross",
+                fit="serial"):
     """One pass of main_evolve.cpp:56-179 on the adiabatic state rho ((num_pes, num_pes, nx, np) complex; numpy, or a torch tensor on the
     GPU, which then never leaves it).  start: the previous output time's hyper-parameters (main_evolve.cpp:94), default set_initial_value;
     initial_energy: the conserved energy (main_evolve.cpp:48), default this state's own; maxeval caps each of the two searches (0: the
     library's defaults); kernel: "nocross" (four hyper-parameters per plane) or "cross" (five, the reference's default build).  Returns the
     record of log.txt and more: nlml, hyper (nq, 4 or 5), mse_before / mse_after (nq), factors (nq), singular,
     is_small (nq), per level exact / grid / gpr population, potential and kinetic energy before and after, features / labels / cells per
-    plane, draws, sums_before / sums_after (nq, 6), seconds per phase, and with keep_pred the two predictions (nq, nx, np) on the host."""
+    plane, draws, sums_before / sums_after (nq, 6), seconds per phase, and with keep_pred the two predictions (nq, nx, np) on the host.
+    fit: "serial" searches plane after plane with optimize; "batched" searches all live planes at once with optimize_planes, which also hands over
+    their weights (planes of more than _capi.NLML_BATCH_MAX_N points still go through optimize)."""
+    if fit not in FITS:
+        raise ValueError('fit must be "serial" or "batched"')
     num_pes, model, mass, dx, dp = state.num_pes, state.model, state.mass, state.dx, state.dp
     width = _width(kernel)
     nlml_weights, grid_reconstruct = (api.nlml_weights, api.grid_reconstruct) if width == 4 else (api.nlml_cross_weights, api.grid_reconstruct_cross)
@@ -216,16 +233,22 @@ def reconstruct(api, state, rho, n_points=200, seed=0, maxeval=0, start=None, in
 
     t0 = time.perf_counter()
     nlml, evals = 0.0, 0
-    for q in range(nq):
-        if small[q]:
-            continue  # "0 everywhere": no optimisation, the hyper-parameters stay (gpr.cpp:575-579)
-        hyper[q], value, n = optimize(api, features[q], labels[q], hyper[q], lower[q], upper[q], maxeval)
+    live = [q for q in range(nq) if not small[q]]  # "0 everywhere": no optimisation, the hyper-parameters stay (gpr.cpp:575-579)
+    together = [q for q in live if fit == "batched" and len(features[q]) <= _capi.NLML_BATCH_MAX_N]
+    found = {}
+    if together:
+        hs, values, ns, ws = optimize_planes(api, [(features[q], labels[q]) for q in together], hyper[together], lower[together], upper[together], maxeval)
+        found = {q: (hs[k], float(values[k]), int(ns[k]), ws[k]) for k, q in enumerate(together)}
+    for q in live:
+        if q not in found:
+            found[q] = optimize(api, features[q], labels[q], hyper[q], lower[q], upper[q], maxeval) + (None,)
+        hyper[q], value, n = found[q][:3]
         nlml, evals = nlml + value, evals + n
         say(f"  plane {q}: NLML {value:.6g} at {np.array2string(hyper[q], precision=5)} after {n} evaluations")
     clock["optimize"] = time.perf_counter() - t0
 
     t0 = time.perf_counter()
-    weights = [None if small[q] else nlml_weights(hyper[q], features[q], labels[q]) for q in range(nq)]
+    weights = [None if small[q] else found[q][3] if found[q][3] is not None else nlml_weights(hyper[q], features[q], labels[q]) for q in range(nq)]
     on_device = hasattr(rho, "data_ptr")
 
     def planes():
@@ -303,15 +326,17 @@ def sim_block(pred):
 
 
 def run_mqcl(api, out_dir=None, model=DAC, num_pes=2, ln_energy=0.0, n_points=200, seed=0, maxeval=0, write_sim=False, max_outputs=None, log=None,
-             kernel="nocross", **setup_kw):
+             kernel="nocross", fit="serial", **setup_kw):
     """The exact MQCLE run of exact_mqcl.run with the reconstruction of main_evolve.cpp at every output time.  Each output's state is moved to
     the device once and the four reconstruction entry points work on that resident copy.  Writes log.txt, choose.txt and (write_sim) sim.txt
     in the reference's layouts next to exact_mqcl.run's files (phase.txt is not written: it is what this run replaces).  kernel: "nocross" or
-    "cross", as in reconstruct.  Returns exact_mqcl.run's
+    "cross", and fit: "serial" or "batched", as in reconstruct.  Returns exact_mqcl.run's
     dict with the reconstruction records under "reconstructions"."""
     import torch
     say = log or (lambda *_: None)
     _width(kernel)
+    if fit not in FITS:
+        raise ValueError('fit must be "serial" or "batched"')
     files, recs, carry = {}, [], {}
     if out_dir is not None:
         os.makedirs(out_dir, exist_ok=True)
@@ -324,7 +349,7 @@ def run_mqcl(api, out_dir=None, model=DAC, num_pes=2, ln_energy=0.0, n_points=20
             carry["state"] = State(api, num_pes, model, s["x"], s["p"], s["mass"])
         dev = torch.from_numpy(np.ascontiguousarray(adia)).cuda()
         rec = reconstruct(api, carry["state"], dev, n_points=n_points, seed=seed + len(recs), maxeval=maxeval, start=carry.get("hyper"),
-                          initial_energy=carry.get("energy"), keep_pred=write_sim, log=log, kernel=kernel)
+                          initial_energy=carry.get("energy"), keep_pred=write_sim, log=log, kernel=kernel, fit=fit)
         carry["hyper"] = rec["hyper"]
         carry.setdefault("energy", rec["initial_energy"])
         rec["t"] = t

@@ -461,6 +461,43 @@ int gple_nlml_cross(gple_ctx* ctx, const double x[5], const double* X, const dou
 int gple_nlml_cross_predict(gple_ctx* ctx, const double x[5], const double* X, const double* y, size_t N, const double* Xs,
 	size_t M, unsigned flags, double* mean);
 
+/* ---- many NLML problems in one launch, and the hyper-parameter search of several planes in lock-step on it ----------- */
+/* B independent problems of gple_nlml (cross == 0: x = (w_d, w_g, a_x, a_p), x[4] ignored) or gple_nlml_cross (cross != 0: x = (w_d, w_g, a, c, b)),
+ * one workgroup each, 1 <= N <= GPLE_NLML_BATCH_MAX_N.  values (B); grads (nullable; 4 B or, with cross, 5 B); weights (nullable: B pointers,
+ * entries nullable, N doubles each: b = K^-1 y, what gple_nlml_weights returns); info (nullable, B ints): 0, or the 1-based column of the first
+ * non-positive pivot — that problem's value, gradient and weights are NaN and no other problem is touched.  flags: GPLE_IO_DEVICE — X, y,
+ * values, grads, info and the arrays `weights` points to are device arrays (`problems` and `weights` themselves are host arrays); the call
+ * drains the stream either way.  A problem's results depend on that problem alone: the same bits alone, at any position of a batch of any
+ * size, beside problems of any N, with or without gradient or weights.  B == 0, N == 0, N > GPLE_NLML_BATCH_MAX_N, null: GPLE_ERR_BAD_ARG. */
+typedef struct gple_nlml_problem
+{
+	double x[5];
+	const double* X;
+	const double* y;
+	size_t N;
+} gple_nlml_problem;
+#define GPLE_NLML_BATCH_MAX_N 256
+int gple_nlml_batch(gple_ctx* ctx, const gple_nlml_problem* problems, size_t B, int cross, unsigned flags, double* values, double* grads,
+	double* const* weights, int* info);
+/* optimize of test/gpr.cpp:535-643 for P <= GPLE_NLML_FIT_MAX_PLANES planes at once (host arrays): per plane the library's Nelder-Mead on the NLML
+ * value from `start` inside [lb, ub], then gple_minimize_auglag_eq with m = 0 on value + gradient from its minimiser (the two kernel-weight
+ * gradients doubled: the reference's dK carries w, not 2 w), then the value once more at the result; a non-finite value counts as DBL_MAX, a
+ * non-finite gradient component as 0.  4 (cross == 0) or 5 entries of start / lb / ub / x_out per plane are used; x_out has 5 P slots.  One host
+ * thread per plane runs the search; their evaluation requests meet at a rendezvous and every round is ONE gple_nlml_batch launch (a Nelder-Mead
+ * step asks for its reflection, expansion and both contractions at once); a plane whose search has ended drops out.  Each plane's iterates,
+ * result and count are those of the same search on that plane alone.  n_eval (P): evaluations the searches consumed; weights (nullable: P
+ * pointers, entries nullable): K^-1 y at the result. */
+typedef struct gple_nlml_fit_plane
+{
+	const double* X;
+	const double* y;
+	size_t N;
+	double start[5], lb[5], ub[5];
+} gple_nlml_fit_plane;
+#define GPLE_NLML_FIT_MAX_PLANES 9
+int gple_nlml_fit_planes(gple_ctx* ctx, const gple_nlml_fit_plane* planes, size_t P, int cross, const gple_opt_options* options, double* x_out,
+	double* f_out, int* n_eval, double* const* weights);
+
 /* ---- reconstruction of a gridded density with the NLML GP (test/main_evolve.cpp:56-179, test/gpr.cpp) ------------------- */
 /* The experiment the reference runs on the exact solvers' phase.txt: pick points of every density-matrix element weighted by |rho|, fit the
  * NOCROSS kernel of gple_nlml, predict the element back on the whole grid and compare.  rho is the phase.txt layout of gple_wigner /
