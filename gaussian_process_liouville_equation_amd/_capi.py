@@ -17,6 +17,7 @@ CALC_AVERAGE = 0x2
 CALC_DERIVATIVE = 0x4
 IO_DEVICE = 0x100
 EVOLVE_NEW_POINTS = 0x400  # gple_evolve: new_point_predict instead of a tick
+FORMAT_JOIN = 0x1000  # gple_format_g: no blank before the first number of a line
 PREDICT_FULL = 0x200  # contract every test row (default: far rows whose contraction cannot move the variance are skipped)
 
 # gple_real_array / gple_complex_array
@@ -337,6 +338,9 @@ def _signatures():
         "grid_reconstruct": (st, [CTX, i, i, _dp, _dp, sz, _dp, sz, d, d, d, C.POINTER(ReconPlane), _dp, u, _dp, _dp]),
         "nlml_cross_weights": (st, [CTX, _dp, _dp, _dp, sz, u, _dp]),
         "grid_reconstruct_cross": (st, [CTX, i, i, _dp, _dp, sz, _dp, sz, d, d, d, C.POINTER(ReconCrossPlane), _dp, u, _dp, _dp]),
+        # "%g" text of device-resident doubles
+        "format_g_bound": (sz, [sz, sz, sz]),
+        "format_g": (st, [CTX, _dp, sz, sz, sz, u, vp, sz, szp]),
         # csrc/gple_debug.h: the one debug entry point the binding itself calls
         "debug_last_contraction_kernel": (C.c_char_p, [CTX]),
     }
@@ -443,6 +447,7 @@ class Api:
     def __init__(self, lib, prefix, with_ctx, device=0, stream=None):
         self.lib, self.prefix, self.with_ctx = lib, prefix, with_ctx
         self.ctx = None
+        self.device = int(device)
         self._fits = weakref.WeakSet()  # a context must outlive its fit handles: close() releases them first
         declare(lib, prefix, with_ctx)
         if with_ctx:
@@ -487,7 +492,7 @@ class Api:
 
     def timing(self, which):
         """(last_ms, total_ms, count) of a gple_timer: 0 = fit, 1 = predict call, 2 = fused predict kernel, 3 = derivative GEMM, 4 = Wigner kernel, 5 = MQCLE
-        steps, 6 = the device work of the reconstruction entry points."""
+        steps, 6 = the device work of the reconstruction entry points, 7 = the kernels of format_g."""
         last, total, count = C.c_double(), C.c_double(), C.c_long()
         self._check(self.lib.gple_ctx_get_timing(self.ctx, which, C.byref(last), C.byref(total), C.byref(count)))
         return last.value, total.value, count.value
@@ -619,18 +624,67 @@ class Api:
                                                 len(times), _ptr(basis), 0x800 if from_psi0 else 0, _ptr(out.view(np.float64))))
         return out
 
-    def wigner(self, num_pes, boundary, x_first, dx, p, psi, energies=None, mass=0.0, phase=True, averages=False):
-        """gple_wigner on psi (T, num_pes * n) complex: (P (T, num_pes, num_pes, n, n_p) complex or None, averages (T, 3) = (E, x, p) or None)"""
+    def wigner(self, num_pes, boundary, x_first, dx, p, psi, energies=None, mass=0.0, phase=True, averages=False, device_out=False):
+        """gple_wigner on psi (T, num_pes * n) complex: (P (T, num_pes, num_pes, n, n_p) complex or None, averages (T, 3) = (E, x, p) or None).
+        device_out: P stays on the device (a complex128 tensor on the context's device; the call has completed when it returns) — the inputs go
+        up as tensors and only the averages come back"""
         p = _f64(p)
         psi = _cplx(np.atleast_2d(psi))
         T = psi.shape[0]
         n = psi.shape[1] // num_pes
+        en = None if energies is None else _f64(energies)
+        if device_out and phase:
+            import torch
+            where = torch.device("cuda", self.device)
+            up = lambda a: None if a is None else torch.from_numpy(a).to(where)
+            P = torch.empty((T, num_pes, num_pes, n, len(p)), dtype=torch.complex128, device=where)
+            av = torch.empty((T, 3), dtype=torch.float64, device=where) if averages else None
+            tp, tpsi, ten = up(p), up(psi.view(np.float64)), up(en)
+            torch.cuda.synchronize(where)  # the uploads, before the context's stream reads them
+            (pp, ppsi, pen, pP, pav), flags = _io(tp, tpsi, ten, torch.view_as_real(P), av)
+            self._check(self.lib.gple_wigner(self.ctx, int(num_pes), int(boundary), n, float(x_first), float(dx), pp, len(p), ppsi, T, pen, float(mass), flags, pP, pav))
+            self.synchronize()
+            return P, None if av is None else av.cpu().numpy()
         P = np.empty((T, num_pes, num_pes, n, len(p)), dtype=np.complex128) if phase else None
         av = np.empty((T, 3)) if averages else None
-        en = None if energies is None else _f64(energies)
         self._check(self.lib.gple_wigner(self.ctx, int(num_pes), int(boundary), n, float(x_first), float(dx), _ptr(p), len(p), _ptr(psi.view(np.float64)), T,
                                          _ptr(en), float(mass), 0, None if P is None else _ptr(P.view(np.float64)), _ptr(av)))
         return P, av
+
+    # ---- text output (gple_format_g) ------------------------------------------------------------------------------------------------------------
+    def format_g(self, values, per_line, lines_per_block=0, join=False):
+        """gple_format_g: the "%g" text of `values` — a numpy array or a contiguous device tensor, float64 or complex128 (read as (re, im) pairs) —
+        with a blank before every number (join: not before the first of a line), a newline after every per_line numbers and an empty line after
+        every lines_per_block lines (0: never).  -> a bytes-like object of exactly the text's length"""
+        if _on_device(values):
+            import torch
+            if not values.is_contiguous():
+                raise ValueError("device tensors must be contiguous")
+            if values.dtype == torch.complex128:
+                values = torch.view_as_real(values)
+            if values.dtype != torch.float64 or not values.is_cuda:
+                raise ValueError("values must be a float64 or complex128 tensor on the GPU")
+            count = values.numel()
+        else:
+            values = np.ascontiguousarray(values)
+            values = values.astype(np.complex128, copy=False).view(np.float64) if np.iscomplexobj(values) else _f64(values)
+            count = values.size
+        per_line, lines_per_block = int(per_line), int(lines_per_block)
+        if per_line <= 0 or count % per_line:
+            raise ValueError("the number of values must be a multiple of per_line")
+        bound = self.lib.gple_format_g_bound(count, per_line, lines_per_block)
+        length = C.c_size_t(0)
+        flags = FORMAT_JOIN if join else 0
+        if _on_device(values):
+            import torch
+            text = torch.empty(max(1, bound), dtype=torch.uint8, device=values.device)
+            torch.cuda.synchronize(values.device)  # whatever produced the values, before the context's stream reads them
+            self._check(self.lib.gple_format_g(self.ctx, C.cast(values.data_ptr(), _dp), count, per_line, lines_per_block, flags | IO_DEVICE,
+                                               C.c_void_p(text.data_ptr()), bound, C.byref(length)))
+            return memoryview(text[:length.value].cpu().numpy())
+        text = np.empty(max(1, bound), dtype=np.uint8)
+        self._check(self.lib.gple_format_g(self.ctx, _ptr(values), count, per_line, lines_per_block, flags, C.c_void_p(text.ctypes.data), bound, C.byref(length)))
+        return memoryview(text)[:length.value]
 
     # ---- exact MQCLE dynamics (liouville_equation/ of the reference; gple_mqcl_*) -------------------------------------------------------------
     MQCL_DIABATIC, MQCL_ADIABATIC, MQCL_FORCE = 0, 1, 2

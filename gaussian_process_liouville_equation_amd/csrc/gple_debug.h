@@ -4,7 +4,8 @@
  *   tests/test_host_logic.py                          -> gple_debug_chol_layout (no device call)
  *   tests/test_gpu_gemm.py                            -> gple_debug_gemm
  *   tests/test_gpu_chol_diag.py                       -> gple_debug_side_stream, gple_debug_chol_knobs (the give-up test)
- *   tests/test_gpu_parity.py                          -> gple_debug_predict_knobs */
+ *   tests/test_gpu_parity.py                          -> gple_debug_predict_knobs
+ *   tests/test_gpu_format.py                          -> gple_debug_format_knobs */
 #ifndef GPLE_DEBUG_H
 #define GPLE_DEBUG_H
 #include "../../include/gple.h"
@@ -40,6 +41,10 @@ extern "C"
 	int gple_debug_predict_knobs(gple_ctx* ctx, int rownorm_pipe, int fused_small);
 	/* Name of the kernel the last predict of this context ran its variance contraction on ("" before the first one; bench.py's roofline label). */
 	const char* gple_debug_last_contraction_kernel(gple_ctx* ctx);
+	/* Test knob of gple_format_g on ONE context: slots = 1 — the size pass keeps every item (16 bytes and a length byte per number) and the write
+	 * pass reads them; 0 — the write pass converts again (the default: DESIGN.md §14 has the measurement); negative leaves it alone.  The two must
+	 * agree byte for byte (tests/test_gpu_format.py). */
+	int gple_debug_format_knobs(gple_ctx* ctx, int slots);
 #ifdef __cplusplus
 }
 #endif

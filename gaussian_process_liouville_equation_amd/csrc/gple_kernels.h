@@ -355,4 +355,14 @@ namespace gple
 	hipError_t launch_recon_energy(hipStream_t s, const ReconArgs& g);
 	hipError_t launch_recon_cross(hipStream_t s, const ReconArgs& g);
 	hipError_t launch_recon_final(hipStream_t s, const ReconArgs& g);
+
+	// ---- "%g" text of device doubles (gple_format.hip): every number with its blank, '\n' after per_line numbers, a second '\n'
+	// after lines_per_block lines (0: never); join: no blank before the first number of a line.  table: the powers of five of gple_g6.h on the
+	// device; work: format_work_bytes() bytes, 16-byte aligned; slots: the second pass reads the items the first one kept instead of converting again.
+	// *length: where the device leaves the text's length.  count a multiple of per_line, at most FORMAT_MAX_COUNT
+	constexpr int FORMAT_BLOCK = 1024; // numbers per workgroup
+	constexpr size_t FORMAT_MAX_COUNT = size_t(1) << 36;
+	size_t format_work_bytes(size_t count, bool slots);
+	hipError_t launch_format(hipStream_t s, const double* values, size_t count, size_t per_line, size_t lines_per_block, bool join,
+		const unsigned long long* table, void* work, bool slots, char* text, const unsigned long long** length);
 } // namespace gple

@@ -138,6 +138,13 @@ def phase_block(P):
     return "".join(lines) + "\n"
 
 
+def phase_text(api, P):
+    """phase_block of every output time of P (T, num_pes, num_pes, n, n_p), on either side, converted on the device by gple_format_g: the same
+    bytes in one call (a line per element, an empty line per output time)"""
+    num_pes, n, n_p = int(P.shape[-3]), int(P.shape[-2]), int(P.shape[-1])
+    return api.format_g(P, 2 * n * n_p, num_pes * num_pes)
+
+
 def averages_line(t, E, X, P, pops, phase_avg):
     """One line of averages.txt (main.cpp:245-253): t <E> <x> <p> populations <E> <x> <p> of the Wigner function."""
     return " ".join(fmt(v) for v in [t, E, X, P, *pops, *phase_avg]) + "\n"
@@ -169,8 +176,12 @@ def run(api, model=DAC, num_pes=2, boundary=PERIODIC, ln_energy=0.0, out_dir=Non
         os.makedirs(out_dir, exist_ok=True)
         write_grid(os.path.join(out_dir, "x.txt"), x)
         write_grid(os.path.join(out_dir, "p.txt"), p)
-        for name in ("t.txt", "psi.txt", "averages.txt") + (("phase.txt",) if write_phase == "text" else ()):
+        for name in ("t.txt", "psi.txt", "averages.txt"):
             files[name] = open(os.path.join(out_dir, name), "w")
+        if write_phase == "text":
+            files["phase.txt"] = open(os.path.join(out_dir, "phase.txt"), "wb")
+    # phase.txt on the device: P stays there and only its text crosses; an api without format_g keeps the Python writer
+    device_text = bool(files) and write_phase == "text" and hasattr(api, "format_g")
     records, stop, last_x, old_pop, pops = [], None, s["x0"], np.zeros(num_pes), None
     t_loop = time.perf_counter()
     try:
@@ -178,7 +189,11 @@ def run(api, model=DAC, num_pes=2, boundary=PERIODIC, ln_energy=0.0, out_dir=Non
             times = np.array([k * s["dt"] for k in steps[c0:c0 + chunk]])
             psi_dia = api.dvr_propagate(num_pes, n, eigvec, eigval, psi0, times)
             psi_adia = to_adiabatic(psi_dia, basis)
-            P, wav = api.wigner(num_pes, boundary, x[0], dx, p, psi_adia, energies=energies, mass=mass, phase=write_phase is not None, averages=True)
+            if device_text:
+                P, wav = api.wigner(num_pes, boundary, x[0], dx, p, psi_adia, energies=energies, mass=mass, averages=True, device_out=True)
+            else:
+                P, wav = api.wigner(num_pes, boundary, x[0], dx, p, psi_adia, energies=energies, mass=mass, phase=write_phase is not None, averages=True)
+            written = 0
             for q, t in enumerate(times):
                 pops = populations(psi_adia[q], n, dx, num_pes)
                 E, X, Pm = psi_averages(psi_dia[q], H, D, x, dx, num_pes)
@@ -187,8 +202,9 @@ def run(api, model=DAC, num_pes=2, boundary=PERIODIC, ln_energy=0.0, out_dir=Non
                     files["t.txt"].write(fmt(t) + "\n")
                     files["psi.txt"].write(psi_line(psi_adia[q]))
                     files["averages.txt"].write(averages_line(t, E, X, Pm, pops, wav[q]))
-                    if write_phase == "text":
-                        files["phase.txt"].write(phase_block(P[q]))
+                    written = q + 1
+                    if write_phase == "text" and not device_text:
+                        files["phase.txt"].write(phase_block(P[q]).encode())
                     elif write_phase == "npy":
                         np.save(os.path.join(out_dir, f"phase_{len(records) - 1}.npy"), P[q])
                 if X > 0.0:  # main.cpp:256-287
@@ -201,6 +217,8 @@ def run(api, model=DAC, num_pes=2, boundary=PERIODIC, ln_energy=0.0, out_dir=Non
                     if stop:
                         break
                 last_x, old_pop = X, pops
+            if device_text and written:
+                files["phase.txt"].write(phase_text(api, P[:written]))  # the chunk's output times up to a stop, in one call
             if stop:
                 break
     finally:

@@ -12,7 +12,7 @@ import time
 
 import numpy as np
 
-from .exact import DAC, HBAR, cutoff, fmt, output_time_cutoff, phase_block, write_grid
+from .exact import DAC, HBAR, cutoff, fmt, output_time_cutoff, phase_block, phase_text, write_grid
 
 DIABATIC, ADIABATIC, FORCE = 0, 1, 2  # Representation (general.h)
 
@@ -104,8 +104,11 @@ def run(api, model=DAC, num_pes=2, ln_energy=0.0, out_dir=None, write_phase="tex
         os.makedirs(out_dir, exist_ok=True)
         write_grid(os.path.join(out_dir, "x.txt"), x)
         write_grid(os.path.join(out_dir, "p.txt"), p)
-        for name in ("t.txt", "averages.txt") + (("phase.txt",) if write_phase == "text" else ()):
+        for name in ("t.txt", "averages.txt"):
             files[name] = open(os.path.join(out_dir, name), "w")
+        if write_phase == "text":
+            files["phase.txt"] = open(os.path.join(out_dir, "phase.txt"), "wb")
+    device_text = hasattr(api, "format_g")  # phase.txt converted on the device; an api without it keeps the Python writer
     records = []
 
     def emit(t, adia, av, pops):
@@ -115,7 +118,7 @@ def run(api, model=DAC, num_pes=2, ln_energy=0.0, out_dir=None, write_phase="tex
         files["t.txt"].write(fmt(t) + "\n")
         files["averages.txt"].write(averages_line(t, av, pops))
         if write_phase == "text":
-            files["phase.txt"].write(phase_block(adia))
+            files["phase.txt"].write(phase_text(api, adia[None]) if device_text else phase_block(adia).encode())
         elif write_phase == "npy":
             np.save(os.path.join(out_dir, f"phase_{len(records) - 1}.npy"), adia)
 

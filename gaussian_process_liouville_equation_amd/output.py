@@ -16,6 +16,8 @@ def output_phase(phase, variance, AllKernels, PhaseGrids, api=None):
     the cut-off prediction) in `phase` and one line in `variance`; zeros for an element without a kernel.  The elements are
     predicted by `PredictiveKernel` / `PredictiveComplexKernel` on the device — the grid predict of the north-star path."""
     grid = np.asarray(PhaseGrids, dtype=float)
+    if api is not None and hasattr(api, "format_g") and len(grid):
+        return _output_phase_device(phase, variance, AllKernels, grid, api)
     zero = _fmt(np.zeros(len(grid)))
     for (i, j) in K.element_order(AllKernels.num_pes):
         k = AllKernels(i, j)
@@ -33,6 +35,30 @@ def output_phase(phase, variance, AllKernels, PhaseGrids, api=None):
             variance.write(_fmt(p.get_variance()) + "\n")
     phase.write("\n")
     variance.write("\n")
+
+
+def _output_phase_device(phase, variance, AllKernels, grid, api):
+    """output_phase with the grid lines converted on the device (gple_format_g with GPLE_FORMAT_JOIN): the same lines, one call
+    per file"""
+    M = len(grid)
+    rows, var = [], []
+    for (i, j) in K.element_order(AllKernels.num_pes):
+        k = AllKernels(i, j)
+        if k is None:
+            rows += [np.zeros(M), np.zeros(M)]
+            var.append(np.zeros(M))
+        elif i == j:
+            p = K.PredictiveKernel(grid, k, False)
+            rows += [np.asarray(p.get_cutoff_prediction(), dtype=float).ravel(), np.zeros(M)]
+            var.append(np.asarray(p.get_variance(), dtype=float).ravel())
+        else:
+            p = K.PredictiveComplexKernel(grid, k, False)
+            pred = np.asarray(p.get_cutoff_prediction())
+            rows += [pred.real.ravel(), pred.imag.ravel()]
+            var.append(np.asarray(p.get_variance(), dtype=float).ravel())
+    # an empty line after the element lines: the whole set is one block
+    phase.write(bytes(api.format_g(np.stack(rows), M, len(rows), join=True)).decode("ascii"))
+    variance.write(bytes(api.format_g(np.stack(var), M, len(var), join=True)).decode("ascii"))
 
 
 def output_param(os, Optimizer):

@@ -151,7 +151,8 @@ typedef enum gple_timer {
 	GPLE_TIMER_DERIV_GEMM = 3,     /* the dK * K^-1 MFMA GEMM of a GPLE_CALC_DERIVATIVE fit (kernel.cpp:354); count = its launches */
 	GPLE_TIMER_WIGNER = 4,         /* the MFMA kernel of gple_wigner alone (all T output times of a call); count = its launches */
 	GPLE_TIMER_MQCL = 5,           /* the step kernels of one gple_mqcl_evolve call (all its steps, no set-up); count = its calls */
-	GPLE_TIMER_RECON = 6           /* the device work of one gple_nlml_weights / gple_grid_survey / gple_grid_select / gple_grid_reconstruct call (and of their _cross forms); count = calls */
+	GPLE_TIMER_RECON = 6,          /* the device work of one gple_nlml_weights / gple_grid_survey / gple_grid_select / gple_grid_reconstruct call (and of their _cross forms); count = calls */
+	GPLE_TIMER_FORMAT = 7          /* the three kernels of one gple_format_g call (no staging, no copy of the text); count = calls */
 } gple_timer;
 int gple_ctx_enable_timing(gple_ctx* ctx, int on);
 /* Synchronises the stream, then: last = milliseconds of the most recent interval; total / count = accumulated since
@@ -565,6 +566,24 @@ typedef struct gple_recon_cross_plane
 } gple_recon_cross_plane;
 int gple_grid_reconstruct_cross(gple_ctx* ctx, int num_pes, int model, const double* rho, const double* x, size_t nx, const double* p, size_t np,
 	double mass, double dx, double dp, const gple_recon_cross_plane* planes, const double* scale, unsigned flags, double* pred, double* sums);
+
+/* ---- text output: "%g" of device-resident doubles ------------------------------------------------------------------------
+ * The reference writes its grids through C++ streams of default precision, one number at a time: output_phase_space_distribution
+ * (schrodinger_equation/general.cpp:384-392 and its liouville_equation twin) writes ' ' << re << ' ' << im for every grid point of an element,
+ * a newline per element and an empty line per output time; output_phase (output.cpp:180-232) writes blank-separated lines of the predicted grid.
+ * gple_format_g produces those bytes from `count` doubles: every number as C's "%g" (6 significant digits, correctly rounded for every double,
+ * "-0" for -0.0, "inf" / "-inf", "nan" without a sign), each preceded by one blank; '\n' after every per_line numbers; a second '\n' after every
+ * lines_per_block lines (0: never).  GPLE_FORMAT_JOIN: the first number of a line has no blank in front (the layout of output_phase).
+ * flags: GPLE_IO_DEVICE — values and text are device pointers — and GPLE_FORMAT_JOIN.  With host pointers the numbers are staged through pooled
+ * device memory and only *length bytes come back.  length is a host pointer in either case: the call drains the stream to fill it.  capacity
+ * (bytes at text) must be at least gple_format_g_bound(count, per_line, lines_per_block) = 14 count + the newlines, which a line of
+ * -1.23457e-308 attains; text carries no terminator.  Two calls on the same input give the same bytes (offsets are sums, nothing is atomic).
+ * GPLE_ERR_BAD_ARG with nothing written: per_line == 0, count not a multiple of per_line, count above 2^36, capacity below the bound, a null
+ * length, null values or text with count > 0.  There is no host formatter: the conversion runs on the device only (timer: GPLE_TIMER_FORMAT). */
+#define GPLE_FORMAT_JOIN 0x1000u
+size_t gple_format_g_bound(size_t count, size_t per_line, size_t lines_per_block);
+int gple_format_g(gple_ctx* ctx, const double* values, size_t count, size_t per_line, size_t lines_per_block, unsigned flags, char* text,
+	size_t capacity, size_t* length);
 
 #ifdef __cplusplus
 }
