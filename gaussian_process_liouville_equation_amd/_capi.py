@@ -341,6 +341,8 @@ def _signatures():
         # "%g" text of device-resident doubles
         "format_g_bound": (sz, [sz, sz, sz]),
         "format_g": (st, [CTX, _dp, sz, sz, sz, u, vp, sz, szp]),
+        # and the doubles of such text
+        "parse_g": (st, [CTX, vp, sz, u, _dp, sz, szp, szp, szp]),
         # csrc/gple_debug.h: the one debug entry point the binding itself calls
         "debug_last_contraction_kernel": (C.c_char_p, [CTX]),
     }
@@ -492,7 +494,7 @@ class Api:
 
     def timing(self, which):
         """(last_ms, total_ms, count) of a gple_timer: 0 = fit, 1 = predict call, 2 = fused predict kernel, 3 = derivative GEMM, 4 = Wigner kernel, 5 = MQCLE
-        steps, 6 = the device work of the reconstruction entry points, 7 = the kernels of format_g."""
+        steps, 6 = the device work of the reconstruction entry points, 7 = the kernels of format_g, 8 = the kernels of parse_g."""
         last, total, count = C.c_double(), C.c_double(), C.c_long()
         self._check(self.lib.gple_ctx_get_timing(self.ctx, which, C.byref(last), C.byref(total), C.byref(count)))
         return last.value, total.value, count.value
@@ -685,6 +687,39 @@ class Api:
         text = np.empty(max(1, bound), dtype=np.uint8)
         self._check(self.lib.gple_format_g(self.ctx, _ptr(values), count, per_line, lines_per_block, flags, C.c_void_p(text.ctypes.data), bound, C.byref(length)))
         return memoryview(text)[:length.value]
+
+    # ---- text input (gple_parse_g) -------------------------------------------------------------------------------------------------------------
+    def parse_g(self, text, device_out=False):
+        """gple_parse_g: the doubles of blank-separated decimal text, converted on the device, each correctly rounded.  text: a bytes-like object, a
+        numpy uint8 array or a contiguous uint8 tensor on the GPU (any byte offset).  -> (values, lines): a numpy float64 array — with device_out
+        or a device text a float64 tensor on the GPU — and the number of lines that hold a number.  One call counts, a second one converts.  A
+        malformed token raises ValueError with its byte offset and its bytes."""
+        if not _on_device(text):
+            text = np.ascontiguousarray(text, dtype=np.uint8).ravel() if isinstance(text, np.ndarray) else np.frombuffer(text, dtype=np.uint8)
+            if device_out:
+                import torch
+                text = torch.from_numpy(text if text.flags.writeable else text.copy()).cuda()
+        on_device = _on_device(text)
+        if on_device:
+            import torch
+            if text.dtype != torch.uint8 or not text.is_cuda or text.dim() != 1 or not text.is_contiguous():
+                raise ValueError("a device text must be a contiguous one-dimensional uint8 tensor on the GPU")
+            length, address, flags = text.numel(), text.data_ptr(), IO_DEVICE
+            torch.cuda.synchronize(text.device)  # whatever produced the text, before the context's stream reads it
+        else:
+            length, address, flags = text.size, text.ctypes.data, 0
+        pointer = C.c_void_p(address if length else None)
+        count, lines, bad = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+        self._check(self.lib.gple_parse_g(self.ctx, pointer, length, flags, None, 0, C.byref(count), C.byref(lines), None))
+        values = torch.empty(count.value, dtype=torch.float64, device=text.device) if on_device else np.empty(count.value)
+        if count.value:
+            out = C.cast(values.data_ptr(), _dp) if on_device else _ptr(values)
+            status = self.lib.gple_parse_g(self.ctx, pointer, length, flags, out, count.value, C.byref(count), C.byref(lines), C.byref(bad))
+            if status != GPLE_OK and bad.value != C.c_size_t(-1).value:
+                piece = text[bad.value:bad.value + 65]
+                raise ValueError(f"malformed number at byte {bad.value}: {bytes(piece.cpu().numpy() if on_device else piece).split()[0]!r}")
+            self._check(status)
+        return values, lines.value
 
     # ---- exact MQCLE dynamics (liouville_equation/ of the reference; gple_mqcl_*) -------------------------------------------------------------
     MQCL_DIABATIC, MQCL_ADIABATIC, MQCL_FORCE = 0, 1, 2

@@ -1,5 +1,7 @@
-// gple_capi_format.hip — C-ABI entry points of include/gple.h: the "%g" text of phase.txt / var.txt, converted on the device (gple_format.hip).
+// gple_capi_format.hip — C-ABI entry points of include/gple.h: the "%g" text of phase.txt / var.txt, converted on the device (gple_format.hip), and
+// read back into doubles there (gple_parse.hip).
 #include "gple_capi.h"
+#include "gple_d2.h"
 #include "gple_debug.h"
 #include "gple_g6.h"
 
@@ -83,6 +85,64 @@ extern "C"
 		GPLE_HIP(ctx, hipStreamSynchronize(st));
 		if (!dev) GPLE_HIP(ctx, hipMemcpy(text, out, bytes, hipMemcpyDeviceToHost));
 		*length = bytes;
+		return GPLE_OK;
+	}
+
+	/* replaces the stream extraction of read_density (test/io.cpp:25-72) */
+	int gple_parse_g(gple_ctx* ctx, const char* text, size_t length, unsigned flags, double* values, size_t capacity, size_t* count, size_t* lines,
+		size_t* bad_offset)
+	{
+		if (!ctx || !count || (length && !text) || length > PARSE_MAX_LENGTH || (!values && capacity)) return GPLE_ERR_BAD_ARG;
+		GPLE_OPEN(ctx);
+		if (bad_offset) *bad_offset = static_cast<size_t>(-1);
+		if (length == 0)
+		{
+			*count = 0;
+			if (lines) *lines = 0;
+			return GPLE_OK;
+		}
+		const bool dev = flags & GPLE_IO_DEVICE;
+		GPLE_CALL(ctx);
+		hipStream_t st = ctx->stream;
+		GPLE_HIP(ctx, format_table(ctx));
+		ByteScratch work(ctx), staged_text(ctx);
+		Staged v(ctx, dev);
+		const char* in = text;
+		if (!dev)
+		{
+			GPLE_HIP(ctx, staged_text.get(length));
+			GPLE_HIP(ctx, hipMemcpyAsync(staged_text.p(), text, length, hipMemcpyHostToDevice, st));
+			in = staged_text.p();
+		}
+		GPLE_HIP(ctx, v.out(values, capacity));
+		GPLE_HIP(ctx, work.get(parse_work_bytes(in, length)));
+		const unsigned long long* result_dev = nullptr;
+		timer_start(ctx, GPLE_TIMER_PARSE);
+		GPLE_HIP(ctx, launch_parse(st, in, length, ctx->format_table, work.p(), v.p, capacity, &result_dev));
+		timer_stop(ctx, GPLE_TIMER_PARSE);
+		unsigned long long result[3] = {0, 0, 0};
+		GPLE_HIP(ctx, hipMemcpyAsync(result, result_dev, sizeof(result), hipMemcpyDeviceToHost, st));
+		GPLE_HIP(ctx, hipStreamSynchronize(st));
+		*count = result[0];
+		if (lines) *lines = result[1];
+		if (!values) return GPLE_OK;
+		if (result[0] > capacity)
+		{
+			ctx->last_error = "gple_parse_g: the text holds " + std::to_string(result[0]) + " numbers, capacity is " + std::to_string(capacity);
+			return GPLE_ERR_BAD_ARG;
+		}
+		if (result[2] != ~0ull)
+		{
+			char token[gple_d2::MAX_TOKEN + 1];
+			const size_t n = std::min<size_t>(sizeof(token), length - result[2]);
+			GPLE_HIP(ctx, hipMemcpy(token, in + result[2], n, hipMemcpyDeviceToHost));
+			size_t end = 0;
+			while (end < n && !gple_d2::is_blank(static_cast<unsigned char>(token[end]))) ++end;
+			if (bad_offset) *bad_offset = result[2];
+			ctx->last_error = "gple_parse_g: malformed token '" + std::string(token, end) + (end == sizeof(token) ? "...'" : "'") + " at byte " + std::to_string(result[2]);
+			return GPLE_ERR_BAD_ARG;
+		}
+		if (!dev) GPLE_HIP(ctx, hipMemcpy(values, v.p, result[0] * sizeof(double), hipMemcpyDeviceToHost));
 		return GPLE_OK;
 	}
 

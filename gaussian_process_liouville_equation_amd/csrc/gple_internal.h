@@ -95,7 +95,7 @@ namespace gple
 		double* host_scalars = nullptr;
 		// device counters of the predict path's far-row pruning: [0] blocks contracted, [1] blocks seen (lazily allocated)
 		unsigned long long* prune_stats = nullptr;
-		// gple_format_g: the powers of five of gple_g6.h, uploaded by the context's first call; gple_debug_format_knobs: the write pass reads kept items
+		// gple_format_g, gple_parse_g: the powers of five of gple_g6.h, uploaded by the context's first call; gple_debug_format_knobs: the write pass reads kept items
 		unsigned long long* format_table = nullptr;
 		bool format_slots = false;
 		// tracing (gple_ctx_enable_timing): every timed interval takes an event pair from a free list and joins `pending`
@@ -108,7 +108,7 @@ namespace gple
 		bool timing = false;
 		std::vector<hipEvent_t> ev_free;
 		std::vector<TimedSpan> pending;
-		static constexpr int NTIMERS = 8; // gple_timer
+		static constexpr int NTIMERS = 9; // gple_timer
 		TimedSpan open_span[NTIMERS] = {};
 		double t_last[NTIMERS] = {}, t_total[NTIMERS] = {};
 		long t_count[NTIMERS] = {};

@@ -365,4 +365,14 @@ namespace gple
 	size_t format_work_bytes(size_t count, bool slots);
 	hipError_t launch_format(hipStream_t s, const double* values, size_t count, size_t per_line, size_t lines_per_block, bool join,
 		const unsigned long long* table, void* work, bool slots, char* text, const unsigned long long** length);
+
+	// ---- the doubles of device "%g" text (gple_parse.hip): token i of the text in file order -> values[i] (values null: count only;
+	// more than `capacity` tokens: nothing is written).  table: as above; work: parse_work_bytes() bytes, 16-byte aligned.  *result: where the device
+	// leaves three words — the tokens, the lines that hold one, the byte offset of the first malformed token (all ones: none).  0 < length <=
+	// PARSE_MAX_LENGTH; the text pointer needs no alignment
+	constexpr int PARSE_CHUNK = 4096; // bytes per workgroup
+	constexpr size_t PARSE_MAX_LENGTH = size_t(1) << 40;
+	size_t parse_work_bytes(const void* text, size_t length);
+	hipError_t launch_parse(hipStream_t s, const char* text, size_t length, const unsigned long long* table, void* work, double* values, size_t capacity,
+		const unsigned long long** result);
 } // namespace gple

@@ -11,10 +11,14 @@ gple_nlml_cross_weights, gple_grid_reconstruct_cross).
     obey_conservation()           gpr.cpp:913-992: the factors of the diagonal planes
     reconstruct()                 survey -> is_small -> select -> optimise -> weights -> reconstruct -> obey_conservation -> reconstruct(scale)
     run_mqcl()                    the exact MQCLE run of exact_mqcl.run with a reconstruction at every output time; log.txt, choose.txt, sim.txt
+    read_grid(), phase_blocks()   read_coord (test/io.cpp:11-23) and the output times of a phase.txt, one block of bytes at a time
+    run_files()                   main_evolve.cpp / main_screenshot.cpp on a directory an exact solver wrote: phase.txt read back on the device
+                                  (gple_parse_g)
 
 The state is num_pes^2 real planes (SuperMatrix, test/io.cpp:25-72): plane q = row * num_pes + col is Re rho_ii, Re rho_ij (row < col) or
 Im rho_ij (row > col)."""
 import math
+import mmap
 import os
 import time
 
@@ -154,12 +158,18 @@ def potential_energy_from_gpr(api, num_pes, model, level, hyper, X, b, step_divi
     h = min(1.0 / (step_divisor * ax), 1.0 / step_divisor)
     lo, hi = float(X[:, 0].min()) - 40.0 / ax, float(X[:, 0].max()) + 40.0 / ax
     n = int(math.ceil((hi - lo) / h)) + 1
-    xs = lo + h * np.arange(n)
-    energy = api.pes_adiabatic_n(num_pes, model, xs)[0][:, level]
+    # blocks of 8192 grid points, and of those only the ones within 40 / a_x of a point (one grid point to spare): everywhere else every term is
+    # exp(-800) = 0 exactly, so leaving a block out leaves the sum as it is, bit for bit.  A fit that ends with a huge a_x (a search that
+    # failed: 1e12 has been seen) has 1e13 grid points but only two blocks per point; neither the grid nor the energies are held as a whole.
+    first = np.floor((X[:, 0] - 40.0 / ax - lo) / h).astype(np.int64) - 1
+    last = np.ceil((X[:, 0] + 40.0 / ax - lo) / h).astype(np.int64) + 1
+    blocks = sorted({int(k) for f, l in zip(first, last) for k in range(max(0, int(f)) // 8192, min(n - 1, int(l)) // 8192 + 1)})
     total = 0.0
-    for i0 in range(0, n, 8192):  # bounded memory: 8192 x N exponentials at a time
-        d = ax * (xs[i0:i0 + 8192, None] - X[None, :, 0])
-        total += float(np.dot(energy[i0:i0 + 8192], np.exp(-0.5 * d * d) @ b))
+    for i0 in (8192 * k for k in blocks):  # bounded memory: 8192 x N exponentials at a time
+        xs = lo + h * np.arange(i0, min(n, i0 + 8192))
+        energy = api.pes_adiabatic_n(num_pes, model, xs)[0][:, level]
+        d = ax * (xs[:, None] - X[None, :, 0])
+        total += float(np.dot(energy, np.exp(-0.5 * d * d) @ b))
     ap = hyper[3] if len(hyper) == 4 else abs(hyper[4])  # sqrt(2 pi / b^2)
     return hyper[1] ** 2 * math.sqrt(2.0 * math.pi) / ap * total * h
 
@@ -325,6 +335,27 @@ def sim_block(pred):
     return "".join("".join(" " + fmt(v) for v in plane.ravel()) + "\n" for plane in pred) + "\n"
 
 
+def _open_outputs(out_dir, write_sim):
+    if out_dir is None:
+        return {}
+    os.makedirs(out_dir, exist_ok=True)
+    return {name: open(os.path.join(out_dir, name), "w") for name in ("log.txt", "choose.txt") + (("sim.txt",) if write_sim else ())}
+
+
+def _write_record(files, t, rec, write_sim):
+    if files:
+        files["log.txt"].write(log_line(t, rec))
+        files["choose.txt"].write(choose_block(rec))
+        if write_sim:
+            files["sim.txt"].write(sim_block(rec["pred_after"]))
+    rec.pop("pred_before", None), rec.pop("pred_after", None)
+
+
+def _say_record(say, t, rec):
+    say(f"T = {t:g}: NLML {rec['nlml']:.6g}, MSE {np.array2string(rec['mse_before'], precision=3)} -> {np.array2string(rec['mse_after'], precision=3)}, "
+        + ", ".join(f"{k} {1e3 * v:.1f} ms" for k, v in rec["seconds"].items()))
+
+
 def run_mqcl(api, out_dir=None, model=DAC, num_pes=2, ln_energy=0.0, n_points=200, seed=0, maxeval=0, write_sim=False, max_outputs=None, log=None,
              kernel="nocross", fit="serial", **setup_kw):
     """The exact MQCLE run of exact_mqcl.run with the reconstruction of main_evolve.cpp at every output time.  Each output's state is moved to
@@ -337,11 +368,7 @@ def run_mqcl(api, out_dir=None, model=DAC, num_pes=2, ln_energy=0.0, n_points=20
     _width(kernel)
     if fit not in FITS:
         raise ValueError('fit must be "serial" or "batched"')
-    files, recs, carry = {}, [], {}
-    if out_dir is not None:
-        os.makedirs(out_dir, exist_ok=True)
-        for name in ("log.txt", "choose.txt") + (("sim.txt",) if write_sim else ()):
-            files[name] = open(os.path.join(out_dir, name), "w")
+    files, recs, carry = _open_outputs(out_dir, write_sim), [], {}
 
     def on_output(t, adia):
         if "state" not in carry:
@@ -353,14 +380,8 @@ def run_mqcl(api, out_dir=None, model=DAC, num_pes=2, ln_energy=0.0, n_points=20
         carry["hyper"] = rec["hyper"]
         carry.setdefault("energy", rec["initial_energy"])
         rec["t"] = t
-        say(f"T = {t:g}: NLML {rec['nlml']:.6g}, MSE {np.array2string(rec['mse_before'], precision=3)} -> {np.array2string(rec['mse_after'], precision=3)}, "
-            + ", ".join(f"{k} {1e3 * v:.1f} ms" for k, v in rec["seconds"].items()))
-        if files:
-            files["log.txt"].write(log_line(t, rec))
-            files["choose.txt"].write(choose_block(rec))
-            if write_sim:
-                files["sim.txt"].write(sim_block(rec["pred_after"]))
-        rec.pop("pred_before", None), rec.pop("pred_after", None)
+        _say_record(say, t, rec)
+        _write_record(files, t, rec, write_sim)
         recs.append(rec)
 
     try:
@@ -371,3 +392,102 @@ def run_mqcl(api, out_dir=None, model=DAC, num_pes=2, ln_energy=0.0, n_points=20
             f.close()
     res["reconstructions"] = recs
     return res
+
+
+def read_grid(path):
+    """read_coord (test/io.cpp:11-23): every number of x.txt / p.txt / t.txt, wherever the line breaks are (a few KB: read on the host)"""
+    with open(path, "rb") as f:
+        return np.array([float(token) for token in f.read().split()], dtype=np.float64)
+
+
+def phase_blocks(path, num_pes, nx, np_, outputs=None):
+    """The output times of a phase.txt, in file order: each block's bytes (a bytearray: num_pes^2 lines and the empty line behind them).  The
+    host finds a block's end in the mapped file without converting anything — the next empty line at or behind the least that
+    2 nx np num_pes^2 numbers can take — and reads that block alone: memory is one block, never the file.  outputs: the indices to yield
+    (default: all); the others are stepped over unread, and the search stops behind the last one.  ValueError with the output's index where
+    the file ends inside a block or a block does not have num_pes^2 lines."""
+    nq = num_pes * num_pes
+    least = nq * (2 * 2 * nx * np_ + 1)  # a blank and a digit per number, a newline per line
+    wanted = None if outputs is None else set(outputs)
+    last = None if wanted is None else max(wanted, default=-1)
+    if os.path.getsize(path) == 0:
+        return
+    with open(path, "rb") as f, mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ) as m:
+        at, index = 0, 0
+        while at < len(m) and (last is None or index <= last):
+            end = m.find(b"\n\n", min(len(m), at + least - 1))
+            if end < 0:
+                if m[at:].strip():
+                    raise ValueError(f"phase.txt ends inside output {index}")
+                return  # a few blank bytes behind the last block
+            end += 2
+            if wanted is None or index in wanted:
+                newlines, found = 0, m.find(b"\n", at, end)
+                while found >= 0 and newlines <= nq + 1:
+                    newlines, found = newlines + 1, m.find(b"\n", found + 1, end)
+                if newlines != nq + 1:
+                    raise ValueError(f"output {index} of phase.txt does not have {nq} lines before its empty line")
+                block = bytearray(end - at)
+                f.seek(at)
+                f.readinto(block)
+                yield block
+            at, index = end, index + 1
+
+
+def _parse_host(block):
+    """Api.parse_g's result for an api without it: float() per token, and the lines that hold one"""
+    data = bytes(block)
+    return np.array([float(token) for token in data.split()], dtype=np.float64), sum(1 for line in data.split(b"\n") if line.strip())
+
+
+def run_files(api, in_dir, out_dir=None, model=DAC, num_pes=2, mass=2000.0, n_points=200, seed=0, maxeval=0, outputs=None, write_sim=False,
+              kernel="nocross", fit="serial", log=None):
+    """main_evolve.cpp:16-179 on a directory that exact.run or exact_mqcl.run (write_phase="text") or one of the reference's solvers wrote: reads
+    x.txt, p.txt and t.txt, then for every output time of phase.txt uploads the block's bytes, converts them on the device (Api.parse_g, DESIGN.md
+    §15) and reconstructs the state where it lies — it never visits the host.  Each output starts from the previous one's hyper-parameters
+    (main_evolve.cpp:94), the conserved energy is that of the first output reconstructed (:48) and output `index` draws with seed + index: the
+    carry of run_mqcl.  outputs: the indices into t.txt to reconstruct (default: all; a single one is main_screenshot.cpp); the others are
+    never uploaded, and a selected output starts from the last selected one before it.  Both triangles of the state are converted and, as in
+    reconstruct, only the upper one is used: read_density's averaging with the element below the diagonal is not restated.  An
+    api without parse_g takes the host route, float() per token into a numpy state.  Writes log.txt, choose.txt and (write_sim) sim.txt into
+    out_dir; returns the list of records (each with its "t" and "index").  ValueError naming the output where a block does not hold
+    2 nx np num_pes^2 numbers in num_pes^2 lines, or phase.txt has fewer outputs than asked for."""
+    say = log or (lambda *_: None)
+    _width(kernel)
+    if fit not in FITS:
+        raise ValueError('fit must be "serial" or "batched"')
+    x, p, t = (read_grid(os.path.join(in_dir, name)) for name in ("x.txt", "p.txt", "t.txt"))
+    nx, n_p, nq = len(x), len(p), num_pes * num_pes
+    indices = list(range(len(t))) if outputs is None else sorted({int(i) for i in outputs})
+    if indices and not 0 <= indices[0] <= indices[-1] < len(t):
+        raise ValueError(f"outputs must be indices into t.txt (0 .. {len(t) - 1})")
+    state = State(api, num_pes, model, x, p, mass)
+    on_device = hasattr(api, "parse_g")
+    files, recs, hyper, energy = _open_outputs(out_dir, write_sim), [], None, None
+    try:
+        blocks = phase_blocks(os.path.join(in_dir, "phase.txt"), num_pes, nx, n_p, outputs=indices)
+        for index, block in zip(indices, blocks):
+            t0 = time.perf_counter()
+            values, lines = api.parse_g(block, device_out=True) if on_device else _parse_host(block)
+            if len(values) != 2 * nx * n_p * nq or lines != nq:
+                raise ValueError(f"output {index} of phase.txt holds {len(values)} numbers in {lines} lines, not {2 * nx * n_p * nq} in {nq}")
+            if on_device:
+                import torch
+                rho = torch.view_as_complex(values.view(num_pes, num_pes, nx, n_p, 2))
+            else:
+                rho = values.view(np.complex128).reshape(num_pes, num_pes, nx, n_p)
+            t_read = time.perf_counter() - t0
+            rec = reconstruct(api, state, rho, n_points=n_points, seed=seed + index, maxeval=maxeval, start=hyper, initial_energy=energy,
+                              keep_pred=write_sim, log=log, kernel=kernel, fit=fit)
+            hyper, energy = rec["hyper"], rec["initial_energy"]
+            rec["t"], rec["index"] = float(t[index]), index
+            rec["seconds"] = {"read": t_read, **rec["seconds"]}
+            _say_record(say, t[index], rec)
+            _write_record(files, t[index], rec, write_sim)
+            recs.append(rec)
+    finally:
+        for f in files.values():
+            f.close()
+    if len(recs) != len(indices):
+        raise ValueError(f"phase.txt ends before output {indices[len(recs)]}")
+    return recs

@@ -152,7 +152,8 @@ typedef enum gple_timer {
 	GPLE_TIMER_WIGNER = 4,         /* the MFMA kernel of gple_wigner alone (all T output times of a call); count = its launches */
 	GPLE_TIMER_MQCL = 5,           /* the step kernels of one gple_mqcl_evolve call (all its steps, no set-up); count = its calls */
 	GPLE_TIMER_RECON = 6,          /* the device work of one gple_nlml_weights / gple_grid_survey / gple_grid_select / gple_grid_reconstruct call (and of their _cross forms); count = calls */
-	GPLE_TIMER_FORMAT = 7          /* the three kernels of one gple_format_g call (no staging, no copy of the text); count = calls */
+	GPLE_TIMER_FORMAT = 7,         /* the three kernels of one gple_format_g call (no staging, no copy of the text); count = calls */
+	GPLE_TIMER_PARSE = 8           /* the kernels of one gple_parse_g call (three, or two when it only counts; no staging, no copies); count = calls */
 } gple_timer;
 int gple_ctx_enable_timing(gple_ctx* ctx, int on);
 /* Synchronises the stream, then: last = milliseconds of the most recent interval; total / count = accumulated since
@@ -584,6 +585,25 @@ int gple_grid_reconstruct_cross(gple_ctx* ctx, int num_pes, int model, const dou
 size_t gple_format_g_bound(size_t count, size_t per_line, size_t lines_per_block);
 int gple_format_g(gple_ctx* ctx, const double* values, size_t count, size_t per_line, size_t lines_per_block, unsigned flags, char* text,
 	size_t capacity, size_t* length);
+
+/* ---- text input: the doubles of "%g" text, on the device ---------------------------------------------------------------------
+ * The reference's reconstruction experiment reads phase.txt back with stream extraction, one number at a time (read_density, test/io.cpp:25-72).
+ * gple_parse_g converts `length` bytes of text: tokens are separated by blanks (' ', \t, \n, \v, \f, \r); token i in file order gives values[i],
+ * the correctly rounded double of  [+-] digits [. digits] [(e|E) [+-] digits]  (at least one mantissa digit; "5." and ".5" are valid) or of
+ * inf / infinity / nan in any letter case with an optional sign (nan: the quiet NaN 0x7ff8000000000000 whatever the sign); "-0" is -0.0, an
+ * exponent beyond the range gives inf or 0.  Everything gple_format_g writes reads back as C's strtod reads it.  Malformed: anything else (hex
+ * floats, a lone sign, "1e", letters), a token of more than 64 bytes, a token with more than 19 significant digits between its leading and its
+ * trailing zeros (rejected, not rounded approximately).
+ * flags: GPLE_IO_DEVICE — text and values are device pointers (text needs no alignment); otherwise both are staged through pooled device memory.
+ * count, lines and bad_offset are host pointers and the call drains the stream to fill them; lines and bad_offset may be NULL.  *count: the
+ * tokens of the text; *lines: the lines that hold at least one (a last line needs no '\n').  values == NULL with capacity == 0 only counts (and
+ * does not look inside the tokens).  Two calls give the same bits.
+ * GPLE_ERR_BAD_ARG: a null count, null text with length > 0, null values with capacity > 0, length above 2^40; *count > capacity, with *count set
+ * and nothing written; a malformed token, with *bad_offset the smallest byte offset of one, gple_ctx_last_error naming it and values unspecified.
+ * On success *bad_offset = (size_t)-1; an empty or all-blank text is a success with *count = 0.  There is no host parser: the conversion runs on
+ * the device only (timer: GPLE_TIMER_PARSE). */
+int gple_parse_g(gple_ctx* ctx, const char* text, size_t length, unsigned flags, double* values, size_t capacity, size_t* count, size_t* lines,
+	size_t* bad_offset);
 
 #ifdef __cplusplus
 }
