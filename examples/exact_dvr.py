@@ -1,7 +1,8 @@
 """Exact DVR dynamics of Tully's dual avoided crossing at the defaults of the reference's schrodinger_equation/input.py (mass 2000,
 x0 = -8, box [-15, 15], dx <= 0.1, sigma_p = p0 / 20, about 50 outputs): the six files of schrodinger_equation/main.cpp in an output
 directory and the final stdout line.  Run on a GPU box:
-    python examples/exact_dvr.py [lnE] [out_dir] [text|npy|none] [reflective|periodic]"""
+    python examples/exact_dvr.py [lnE] [out_dir] [text|npy|none] [reflective|periodic|absorbing]
+With `absorbing` the packet leaves the box through an absorbing region on either side (no eigh)."""
 import os
 import sys
 
@@ -14,13 +15,14 @@ from gaussian_process_liouville_equation_amd import exact  # noqa: E402
 ln_e = float(sys.argv[1]) if len(sys.argv) > 1 else 0.0
 out_dir = sys.argv[2] if len(sys.argv) > 2 else "exact_dvr_out"
 write_phase = sys.argv[3] if len(sys.argv) > 3 else "text"
-boundary = exact.REFLECTIVE if len(sys.argv) > 4 and sys.argv[4] == "reflective" else exact.PERIODIC
+boundary = {"reflective": exact.REFLECTIVE, "absorbing": exact.ABSORBING}.get(sys.argv[4] if len(sys.argv) > 4 else "", exact.PERIODIC)
 api = pkg.open_api(0)
 try:
     res = exact.run(api, model=exact.DAC, num_pes=2, boundary=boundary, ln_energy=ln_e, out_dir=out_dir,
                     write_phase=None if write_phase == "none" else write_phase, log=print)
     s = res["setup"]
-    print(f"grid: {s['n_grids']} points, dx = {s['dx']:g}; eigh {res['eigh_seconds']:.2f} s; {len(res['records'])} outputs, "
+    timing = f"propagator {res['propagator_seconds']:.2f} s" if boundary == exact.ABSORBING else f"eigh {res['eigh_seconds']:.2f} s"
+    print(f"grid: {s['n_grids']} points, dx = {s['dx']:g}; {timing}; {len(res['records'])} outputs, "
           f"{1e3 * res['seconds_per_output']:.1f} ms per output step; total {res['total_seconds']:.1f} s")
     print("final populations:", np.array2string(res["records"][-1]["populations"], precision=6))
     print(res["final_line"])

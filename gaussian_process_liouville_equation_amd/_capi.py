@@ -325,6 +325,9 @@ def _signatures():
         "dvr_hamiltonian": (st, [CTX, i, i, i, d, d, sz, d, u, _dp, _dp, _dp]),
         "dvr_propagate": (st, [CTX, i, sz, _dp, _dp, _dp, _dp, sz, _dp, u, _dp]),
         "wigner": (st, [CTX, i, i, sz, d, d, _dp, sz, _dp, sz, _dp, d, u, _dp, _dp]),
+        "dvr_absorber": (st, [CTX, d, d, sz, d, d, d, d, u, _dp]),
+        "dvr_propagator": (st, [CTX, i, sz, _dp, _dp, d, sz, u, _dp]),
+        "dvr_apply": (st, [CTX, i, sz, _dp, _dp, sz, _dp, u, _dp]),
         "mqcl_transform": (st, [CTX, i, i, _dp, sz, i, i, u, _dp, _dp]),
         "mqcl_evolve": (st, [CTX, i, i, _dp, _dp, sz, d, d, d, d, sz, u, _dp]),
         "mqcl_observe": (st, [CTX, i, i, _dp, _dp, sz, d, d, d, u, _dp, _dp, _dp, _dp]),
@@ -494,7 +497,7 @@ class Api:
 
     def timing(self, which):
         """(last_ms, total_ms, count) of a gple_timer: 0 = fit, 1 = predict call, 2 = fused predict kernel, 3 = derivative GEMM, 4 = Wigner kernel, 5 = MQCLE
-        steps, 6 = the device work of the reconstruction entry points, 7 = the kernels of format_g, 8 = the kernels of parse_g."""
+        steps, 6 = the device work of the reconstruction entry points, 7 = the kernels of format_g, 8 = the kernels of parse_g, 9 = the products of dvr_propagator."""
         last, total, count = C.c_double(), C.c_double(), C.c_long()
         self._check(self.lib.gple_ctx_get_timing(self.ctx, which, C.byref(last), C.byref(total), C.byref(count)))
         return last.value, total.value, count.value
@@ -652,6 +655,69 @@ class Api:
         self._check(self.lib.gple_wigner(self.ctx, int(num_pes), int(boundary), n, float(x_first), float(dx), _ptr(p), len(p), _ptr(psi.view(np.float64)), T,
                                          _ptr(en), float(mass), 0, None if P is None else _ptr(P.view(np.float64)), _ptr(av)))
         return P, av
+
+    # ---- the absorbing boundary: absorber, propagator of n_steps RK4 steps, its application (gple_dvr_absorber / _propagator / _apply) --------
+    def dvr_absorber(self, x_first, dx, n_grids, mass, xmin, xmax, length):
+        """gple_dvr_absorber: W (n_grids,) >= 0 of pes.cpp:64-93 on the grid x_first + dx a; exactly 0 for xmin <= x <= xmax"""
+        W = np.empty(int(n_grids))
+        self._check(self.lib.gple_dvr_absorber(self.ctx, float(x_first), float(dx), int(n_grids), float(mass), float(xmin), float(xmax), float(length), 0, _ptr(W)))
+        return W
+
+    def dvr_propagator(self, num_pes, n_grids, H, W, dt, n_steps, device_out=False):
+        """gple_dvr_propagator: U = P4(-(W + i H) dt / hbar)^n_steps, what n_steps classical RK4 steps apply, as a complex128 (dim, dim) array;
+        W (n_grids,) or None.  device_out: U stays on the device, a float64 tensor (2, dim, dim) = (Re, Im) on the context's device (the call has
+        completed when it returns) that dvr_apply accepts as it is"""
+        dim = int(num_pes) * int(n_grids)
+        H = _f64(H)
+        W = None if W is None else _f64(W)
+        if H.shape != (dim, dim) or (W is not None and W.shape != (n_grids,)):
+            raise ValueError("H (dim, dim) and W (n_grids,) with dim = num_pes * n_grids")
+        if device_out:
+            import torch
+            where = torch.device("cuda", self.device)
+            tH = torch.from_numpy(H).to(where)
+            tW = None if W is None else torch.from_numpy(W).to(where)
+            U = torch.empty((2, dim, dim), dtype=torch.float64, device=where)
+            torch.cuda.synchronize(where)  # the uploads, before the context's stream reads them
+            (pH, pW, pU), flags = _io(tH, tW, U)
+            self._check(self.lib.gple_dvr_propagator(self.ctx, int(num_pes), int(n_grids), pH, pW, float(dt), int(n_steps), flags, pU))
+            self.synchronize()
+            return U
+        planes = np.empty((2, dim, dim))
+        self._check(self.lib.gple_dvr_propagator(self.ctx, int(num_pes), int(n_grids), _ptr(H), _ptr(W), float(dt), int(n_steps), 0, _ptr(planes)))
+        return planes[0] + 1j * planes[1]
+
+    def dvr_apply(self, num_pes, n_grids, U, psi0, T, basis=None):
+        """gple_dvr_apply: psi[k] = U^(k + 1) psi0 for k < T -> (T, dim) complex, adiabatic with basis (n, num_pes, num_pes).  U: a complex
+        (dim, dim) array, or the device tensor of dvr_propagator(device_out=True) (psi0 and basis go up, psi comes back)"""
+        dim, T = int(num_pes) * int(n_grids), int(T)
+        psi0 = _cplx(psi0)
+        if _on_device(U):  # the tensor form is what dvr_propagator(device_out=True) returns, nothing else
+            if tuple(U.shape) != (2, dim, dim) or not U.is_cuda or str(U.dtype) != "torch.float64" or not U.is_contiguous():
+                raise ValueError("a tensor U must be the contiguous float64 (2, dim, dim) planes of dvr_propagator(device_out=True) on the GPU")
+        elif tuple(np.shape(U)) not in ((dim, dim), (2, dim, dim)):
+            raise ValueError("U (dim, dim) complex or (2, dim, dim) planes with dim = num_pes * n_grids")
+        if psi0.shape != (dim,):
+            raise ValueError("psi0 (dim,) with dim = num_pes * n_grids")
+        basis = None if basis is None else _f64(basis)
+        out = np.empty((T, dim), dtype=np.complex128)
+        if T == 0:
+            return out
+        if _on_device(U):
+            import torch
+            tv = torch.from_numpy(psi0.view(np.float64)).to(U.device)
+            tb = None if basis is None else torch.from_numpy(basis).to(U.device)
+            tout = torch.empty((T, 2 * dim), dtype=torch.float64, device=U.device)
+            torch.cuda.synchronize(U.device)
+            (pU, pv, pb, po), flags = _io(U, tv, tb, tout)
+            self._check(self.lib.gple_dvr_apply(self.ctx, int(num_pes), int(n_grids), pU, pv, T, pb, flags, po))
+            self.synchronize()
+            return tout.cpu().numpy().view(np.complex128)
+        planes = _f64(U) if np.ndim(U) == 3 else np.stack([np.real(U), np.imag(U)]).astype(np.float64)
+        planes = np.ascontiguousarray(planes)
+        self._check(self.lib.gple_dvr_apply(self.ctx, int(num_pes), int(n_grids), _ptr(planes), _ptr(psi0.view(np.float64)), T, _ptr(basis), 0,
+                                            _ptr(out.view(np.float64))))
+        return out
 
     # ---- text output (gple_format_g) ------------------------------------------------------------------------------------------------------------
     def format_g(self, values, per_line, lines_per_block=0, join=False):

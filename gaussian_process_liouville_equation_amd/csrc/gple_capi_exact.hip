@@ -107,6 +107,79 @@ extern "C"
 		return GPLE_OK;
 	}
 
+	/* ---- the absorbing boundary (gple_dvr_power.hip): the absorber, the propagator of n_steps RK4 steps as a matrix power, its application ---- */
+	int gple_dvr_absorber(gple_ctx* ctx, double x_first, double dx, size_t n_grids, double mass, double xmin, double xmax, double length, unsigned flags,
+		double* W)
+	{
+		if (!ctx || !W || !dvr_grid_ok(n_grids, dx) || !std::isfinite(x_first) || !(mass > 0.0) || !std::isfinite(mass) || !std::isfinite(xmin) ||
+			!std::isfinite(xmax) || !(xmin < xmax) || !(length > 0.0) || !std::isfinite(length))
+			return GPLE_ERR_BAD_ARG;
+		// the pole of W lies one absorber length outside the box: an end point at or beyond it is refused
+		const double x_last = x_first + dx * static_cast<double>(n_grids - 1);
+		if (xmin - x_first >= length || x_last - xmax >= length) return GPLE_ERR_BAD_ARG;
+		GPLE_OPEN(ctx);
+		const bool dev = flags & GPLE_IO_DEVICE;
+		GPLE_CALL(ctx);
+		hipStream_t st = ctx->stream;
+		Staged w(ctx, dev);
+		GPLE_HIP(ctx, w.out(W, n_grids));
+		GPLE_HIP(ctx, launch_dvr_absorber(st, x_first, dx, static_cast<int>(n_grids), mass, xmin, xmax, length, w.p));
+		GPLE_HIP(ctx, w.back());
+		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
+		return GPLE_OK;
+	}
+
+	int gple_dvr_propagator(gple_ctx* ctx, int num_pes, size_t n_grids, const double* H, const double* W, double dt, size_t n_steps, unsigned flags, double* U)
+	{
+		if (!ctx || (num_pes != 2 && num_pes != 3) || !dvr_grid_ok(n_grids, 1.0) || !H || !U || !std::isfinite(dt) || n_steps < 1 || n_steps > (1ul << 30) ||
+			round_up(static_cast<size_t>(num_pes) * n_grids, 64) > static_cast<size_t>(DVR_POWER_MAX_LD))
+			return GPLE_ERR_BAD_ARG;
+		GPLE_OPEN(ctx);
+		const bool dev = flags & GPLE_IO_DEVICE;
+		const int n = static_cast<int>(n_grids);
+		const size_t dim = static_cast<size_t>(num_pes) * n_grids, ld = round_up(dim, 64);
+		GPLE_CALL(ctx);
+		hipStream_t st = ctx->stream;
+		Scratch work(ctx);
+		Staged h(ctx, dev), w(ctx, dev), u(ctx, dev);
+		GPLE_HIP(ctx, work.get(dvr_power_work_doubles(num_pes, n)));
+		GPLE_HIP(ctx, h.in(H, dim * dim));
+		GPLE_HIP(ctx, w.in(W, n_grids));
+		GPLE_HIP(ctx, u.out(U, 2 * dim * dim));
+		const double* R = nullptr;
+		GPLE_HIP(ctx, launch_dvr_power(ctx, st, num_pes, n, h.p, w.p, dt, static_cast<long>(n_steps), work.p, &R));
+		for (size_t plane = 0; plane < 2; ++plane) // the padded planes, without their padding
+			GPLE_HIP(ctx, hipMemcpy2DAsync(u.p + plane * dim * dim, dim * sizeof(double), R + plane * ld * ld, ld * sizeof(double), dim * sizeof(double), dim,
+				hipMemcpyDeviceToDevice, st));
+		GPLE_HIP(ctx, u.back());
+		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
+		return GPLE_OK;
+	}
+
+	int gple_dvr_apply(gple_ctx* ctx, int num_pes, size_t n_grids, const double* U, const double* psi0, size_t T, const double* basis, unsigned flags,
+		double* psi)
+	{
+		if (!ctx || (num_pes != 2 && num_pes != 3) || !dvr_grid_ok(n_grids, 1.0) || T > 4096 || (T && (!U || !psi0 || !psi))) return GPLE_ERR_BAD_ARG;
+		GPLE_OPEN(ctx);
+		if (T == 0) return GPLE_OK;
+		const bool dev = flags & GPLE_IO_DEVICE;
+		const int n = static_cast<int>(n_grids);
+		const size_t dim = static_cast<size_t>(num_pes) * n_grids;
+		GPLE_CALL(ctx);
+		hipStream_t st = ctx->stream;
+		Scratch dia(ctx);
+		Staged u(ctx, dev), v(ctx, dev), b(ctx, dev), o(ctx, dev);
+		GPLE_HIP(ctx, u.in(U, 2 * dim * dim));
+		GPLE_HIP(ctx, v.in(psi0, 2 * dim));
+		GPLE_HIP(ctx, b.in(basis, n_grids * num_pes * num_pes));
+		GPLE_HIP(ctx, o.out(psi, 2 * dim * T));
+		if (b.p) GPLE_HIP(ctx, dia.get(2 * dim * T));
+		GPLE_HIP(ctx, launch_dvr_apply(st, num_pes, n, u.p, v.p, static_cast<int>(T), b.p, dia.p, o.p));
+		GPLE_HIP(ctx, o.back());
+		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
+		return GPLE_OK;
+	}
+
 	/* ---- exact MQCLE dynamics (gple_mqcl.hip; liouville_equation/ of the reference) ------------------------------------------------------ */
 	static bool mqcl_size_ok(int num_pes, int model, size_t n) { return dvr_model_ok(num_pes, model) && n >= 4 && n <= 4096; }
 

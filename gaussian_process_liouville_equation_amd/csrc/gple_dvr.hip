@@ -1,5 +1,5 @@
 // gple_dvr.hip — exact DVR wavepacket dynamics of the model the GP method is judged against (schrodinger_equation/ of the reference,
-// the reflective and periodic boundaries of general.h:86-97; the absorbing one is out of scope: DESIGN.md §11).
+// the reflective and periodic boundaries of general.h:86-97; the absorbing one is gple_dvr_power.hip: DESIGN.md §11).
 //
 //   dvr_hamiltonian_kernel  Hamiltonian_construction (general.cpp:106-200) without the absorbing term: dense real symmetric dim x dim,
 //                           dim = NP n, index m n + a; the diabatic potential on the diagonal a = a' blocks, the kinetic energy

@@ -282,6 +282,16 @@ namespace gple
 	size_t wigner_avg_work_doubles(int num_pes, int T);
 	hipError_t launch_wigner_averages(hipStream_t s, int num_pes, int n, double x_first, double dx, const double* p, int np, const double* energies,
 		double mass, const double* P, int T, double* work, double* averages);
+	// ---- the absorbing boundary (gple_dvr_power.hip): U = P4(A)^s, A = -(W + i H) dt / hbar, as complex symmetric planes of ld x ld, ld = dim rounded up to 64
+	hipError_t launch_dvr_absorber(hipStream_t s, double x_first, double dx, int n, double mass, double xmin, double xmax, double length, double* W);
+	// work layout (doubles): G = Im A (ld x ld) | P4, two power buffers (2 ld x ld each: Re, Im) | Re A (ld, diagonal)
+	constexpr long DVR_POWER_MAX_LD = 65472; // ld <= 65535 = the largest gridDim.y (a column per block row in the set-up kernels); 7 ld^2 doubles of work are 240 GB there
+	size_t dvr_power_work_doubles(int num_pes, int n);
+	// H: dim x dim, W: n values or null; *result: the Re plane of U inside work (Im follows at + ld ld).  GPLE_TIMER_DVR_POWER of ctx spans the products
+	hipError_t launch_dvr_power(Ctx* ctx, hipStream_t s, int num_pes, int n, const double* H, const double* W, double dt, long n_steps, double* work,
+		const double** result);
+	// psi[k] = U^(k + 1) psi0, k < T; U: two dim x dim planes; scratch: T x dim pairs when basis != null (the diabatic states), unused otherwise
+	hipError_t launch_dvr_apply(hipStream_t s, int num_pes, int n, const double* U, const double* psi0, int T, const double* basis, double* scratch, double* psi);
 	// ---- exact MQCLE dynamics (gple_mqcl.hip): num_pes = 2 or 3, 4 <= n <= 4096, rho: num_pes^2 x n x n (re, im) pairs, x major ------------
 	// tables (mqcl_table_doubles): per x C | E | U | lambda | Q phases of one Q(tq), then (spectral) chirp (n), twiddles (M / 2), chirp spectrum (M)
 	int mqcl_fft_length(int n);

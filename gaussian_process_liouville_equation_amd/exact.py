@@ -1,5 +1,6 @@
-"""Exact DVR wavepacket dynamics: the reference's schrodinger_equation/main.cpp for the reflective and periodic boundaries, restated on the
-library's device entry points (gple_dvr_hamiltonian, gple_dvr_propagate, gple_wigner).
+"""Exact DVR wavepacket dynamics: the reference's schrodinger_equation/main.cpp, restated on the library's device entry points
+(gple_dvr_hamiltonian, gple_dvr_propagate, gple_wigner; for the absorbing boundary gple_dvr_absorber, gple_dvr_propagator, gple_dvr_apply;
+DESIGN.md §11).
 
     setup()            main.cpp:41-146 with the defaults of schrodinger_equation/input.py
     initial_adiabatic_psi(), to_diabatic()  general.cpp:70-103 (Gaussian on the lowest adiabatic surface) taken to the diabatic basis (main.cpp:158-161)
@@ -7,7 +8,9 @@ library's device entry points (gple_dvr_hamiltonian, gple_dvr_propagate, gple_wi
                        (general.cpp:443-478), the Wigner transform and its averages (general.cpp:324-411), the stop criteria (main.cpp:256-294)
     writers            x.txt, p.txt, t.txt, psi.txt, phase.txt, averages.txt in the reference's line layout; numbers as %g (output.py)
 
-The Hamiltonian is diagonalised once per run with numpy.linalg.eigh on the host (set-up, not the hot path: DESIGN.md §11).
+The Hamiltonian is diagonalised once per run with numpy.linalg.eigh on the host (set-up, not the hot path: DESIGN.md §11).  The absorbing
+boundary needs no eigh: the propagator of the output_step RK4 steps between two outputs is formed once on the device as a matrix power and
+applied once per output.
 """
 import math
 import os
@@ -16,9 +19,13 @@ import time
 import numpy as np
 
 HBAR = 1.0                 # general.h:35
-CHANGE_LIM = 1e-5  # general.h:46 (PplLim, :45, applies to the absorbing boundary only)
+CHANGE_LIM = 1e-5  # general.h:46
+PPL_LIM = 1e-4     # general.h:45 (the absorbing boundary only)
 SAC, DAC, ECR, TSAC = 0, 1, 2, 3
 REFLECTIVE, PERIODIC = 0, 1
+ABSORBING = 2  # a constant of this driver only (general.h:88-93): the library's H is the reflective one plus gple_dvr_absorber
+ABSORBER_C = math.sqrt(2.0) * 1.8540746773013719  # sqrt(2) K(1 / sqrt(2)) (pes.cpp:61)
+RK4_ABSORBER_LIMIT = 2.0  # dt max W / hbar of the halving rule: [-2.5, 0] x [-0.7, 0.7] lies inside RK4's stability region
 
 
 def cutoff(val):
@@ -39,9 +46,23 @@ def output_time_cutoff(x):
     return 10 * powx
 
 
-def setup(ln_energy=0.0, mass=2000.0, x0=-8.0, xmin=-15.0, xmax=15.0, dx_max=0.1, number_of_output=50, p0=None, sigma_p=None, output_time=None, dx=None):
+def absorbing_potential(x, mass, xmin, xmax, length):
+    """absorbing_potential (pes.cpp:64-93) with x <= xmin on the left-hand branch, on the host: setup() sizes the time step with its maximum;
+    the run takes W itself from gple_dvr_absorber."""
+    x = np.asarray(x, dtype=np.float64)
+    c = ABSORBER_C
+    xi = c * np.where(x <= xmin, x - xmin, x - xmax) / length
+    w = (2.0 * math.pi * HBAR / length) ** 2 * 2.0 / mass * (1.0 / (c - xi) ** 2 + 1.0 / (c + xi) ** 2 - 2.0 / c ** 2)
+    return np.where((x > xmin) & (x < xmax), 0.0, w)
+
+
+def setup(ln_energy=0.0, mass=2000.0, x0=-8.0, xmin=-15.0, xmax=15.0, dx_max=0.1, number_of_output=50, p0=None, sigma_p=None, output_time=None, dx=None,
+          boundary=PERIODIC, dt_max=0.1):
     """The run's constants: input.py's defaults (p0 = sqrt(2 m e^lnE), sigma_p = p0 / 20, output time from the 1-2-5 rounding) then main.cpp:52-146.
-    dx (optional) replaces the grid spacing main.cpp:74 derives (coarse grids for tests and probes)."""
+    dx (optional) replaces the grid spacing main.cpp:74 derives (coarse grids for tests and probes).  boundary=ABSORBING adds the absorbing
+    region on either side (main.cpp:79-95, 108) and the RK4 time step (main.cpp:130-135, dt_max: the input file's dt), halved until
+    dt max W / hbar <= RK4_ABSORBER_LIMIT (the reference bounds the kinetic term only): dt is the step the run takes, dt_rule the reference's,
+    halvings how often it was halved; the step counts are doubled along, so the output times stay."""
     if p0 is None:
         p0 = float(np.sqrt(2.0 * mass * np.exp(ln_energy)))
     if sigma_p is None:
@@ -53,6 +74,8 @@ def setup(ln_energy=0.0, mass=2000.0, x0=-8.0, xmin=-15.0, xmax=15.0, dx_max=0.1
     if dx is None:
         dx = cutoff(min(dx_max, 2 * math.pi * HBAR / p0max / 5.0))   # main.cpp:74
     n_grids = int((xmax - xmin) / dx) + 1                            # main.cpp:76, 95 (no absorbing region)
+    if boundary == ABSORBING:
+        return _setup_absorbing(mass, x0, p0, sigma_p, sigma_x, xmin, xmax, dx, n_grids, output_time, dt_max)
     pmin, pmax = p0 - math.pi * HBAR / dx / 2.0, p0 + math.pi * HBAR / dx / 2.0  # main.cpp:103-104
     i = np.arange(n_grids)
     x = xmin + dx * i                                                # main.cpp:108
@@ -61,6 +84,26 @@ def setup(ln_energy=0.0, mass=2000.0, x0=-8.0, xmin=-15.0, xmax=15.0, dx_max=0.1
     dt = output_time                                                 # main.cpp:130-140 (no absorbing boundary)
     return dict(mass=mass, x0=x0, p0=p0, sigma_p=sigma_p, sigma_x=sigma_x, xmin=xmin, xmax=xmax, dx=dx, n_grids=n_grids, x=x, p=p,
                 total_time=total_time, output_time=output_time, dt=dt, total_step=int(total_time / dt), output_step=int(output_time / dt))
+
+
+def _setup_absorbing(mass, x0, p0, sigma_p, sigma_x, xmin, xmax, dx, interior, output_time, dt_max):
+    length = 2 * math.pi * HBAR / (p0 - 3.0 * sigma_p)               # main.cpp:79-89
+    n_abs = int(length / dx)                                         # main.cpp:93
+    n_grids = interior + 2 * n_abs                                   # main.cpp:95
+    pmin, pmax = p0 - math.pi * HBAR / dx / 2.0, p0 + math.pi * HBAR / dx / 2.0
+    i = np.arange(n_grids)
+    x = xmin + dx * (i - n_abs)                                      # main.cpp:108
+    p = ((n_grids - 1 - i) * pmin + i * pmax) / (n_grids - 1)
+    total_time = (xmax - xmin) / (p0 / mass) * 2.0
+    dt_rule = cutoff(min(dt_max, HBAR / 500.0 / (sigma_p * p0 / mass)))  # main.cpp:134
+    total_step, output_step = int(total_time / dt_rule), int(output_time / dt_rule)  # main.cpp:144-145
+    w_max = float(absorbing_potential(x, mass, xmin, xmax, length).max())
+    dt, halvings = dt_rule, 0
+    while dt * w_max / HBAR > RK4_ABSORBER_LIMIT:
+        dt, halvings, total_step, output_step = dt / 2.0, halvings + 1, 2 * total_step, 2 * output_step
+    return dict(mass=mass, x0=x0, p0=p0, sigma_p=sigma_p, sigma_x=sigma_x, xmin=xmin, xmax=xmax, dx=dx, n_grids=n_grids, x=x, p=p, total_time=total_time,
+                output_time=output_time, dt=dt, total_step=total_step, output_step=output_step, absorbing_length=length, n_absorbing=n_abs, dt_rule=dt_rule,
+                halvings=halvings, w_max=w_max)
 
 
 def initial_adiabatic_psi(x, x0, p0, sigma_x, num_pes):
@@ -152,8 +195,13 @@ def averages_line(t, E, X, P, pops, phase_avg):
 
 def run(api, model=DAC, num_pes=2, boundary=PERIODIC, ln_energy=0.0, out_dir=None, write_phase="text", max_outputs=None, chunk_bytes=1 << 30,
         p_grid=None, log=None, **setup_kw):
-    """The loop of main.cpp:210-298 for a non-absorbing boundary.  write_phase: "text" (phase.txt), "npy" (phase_<k>.npy per output time) or None;
+    """The loop of main.cpp:210-298.  boundary=ABSORBING: no eigh; the propagator of output_step RK4 steps is formed once (gple_dvr_propagator, kept
+    on the device) and applied once per output (gple_dvr_apply); the Wigner transform is the reflective one (general.cpp:363-364), <E> uses the
+    real H, and the stop criteria carry the PplLim clause.  write_phase: "text" (phase.txt), "npy" (phase_<k>.npy per output time) or None;
     out_dir None writes no file.  max_outputs caps the output times.  Returns a dict with the setup, per-output records and the final stdout line."""
+    absorbing = boundary == ABSORBING
+    if absorbing:
+        setup_kw["boundary"], boundary = ABSORBING, REFLECTIVE  # H and the Wigner transform of the reflective boundary (the reference's switches fall through)
     s = setup(ln_energy, **setup_kw)
     n, dx, x, mass = s["n_grids"], s["dx"], s["x"], s["mass"]
     p = s["p"] if p_grid is None else np.asarray(p_grid, dtype=np.float64)
@@ -161,12 +209,21 @@ def run(api, model=DAC, num_pes=2, boundary=PERIODIC, ln_energy=0.0, out_dir=Non
     t0 = time.perf_counter()
     H, energies, basis = api.dvr_hamiltonian(num_pes, model, boundary, x[0], dx, n, mass)
     t_h = time.perf_counter()
-    eigval, eigvec = np.linalg.eigh(H)
-    t_eigh = time.perf_counter() - t_h
-    say(f"dx = {dx:g}, {n} grids from {x[0]:g} to {x[-1]:g}; dt = {s['dt']:g}, {s['total_step']} steps; eigh of {num_pes * n} x {num_pes * n}: {t_eigh:.2f} s")
+    if absorbing:
+        if s["output_step"] < 1:
+            raise ValueError("the output time is shorter than one time step")
+        W = api.dvr_absorber(x[0], dx, n, mass, s["xmin"], s["xmax"], s["absorbing_length"])
+        U = api.dvr_propagator(num_pes, n, H, W, s["dt"], s["output_step"], device_out=True)
+        t_eigh, t_power = 0.0, time.perf_counter() - t_h
+        say(f"dx = {dx:g}, {n} grids from {x[0]:g} to {x[-1]:g}; dt = {s['dt']:g} ({s['halvings']} halvings), {s['total_step']} steps; "
+            f"propagator of {s['output_step']} steps, {num_pes * n} x {num_pes * n}: {t_power:.2f} s")
+    else:
+        eigval, eigvec = np.linalg.eigh(H)
+        t_eigh, t_power = time.perf_counter() - t_h, 0.0
+        say(f"dx = {dx:g}, {n} grids from {x[0]:g} to {x[-1]:g}; dt = {s['dt']:g}, {s['total_step']} steps; eigh of {num_pes * n} x {num_pes * n}: {t_eigh:.2f} s")
     psi0 = to_diabatic(initial_adiabatic_psi(x, s["x0"], s["p0"], s["sigma_x"], num_pes), basis)
     D = derivative_matrix(n, dx)
-    steps = [k for k in range(s["total_step"] + 1) if k % s["output_step"] == 0]
+    steps = list(range(0, s["total_step"] + 1, s["output_step"]))  # iStep % OutputStep == 0 (main.cpp:217); total_step runs to 1e9 after halvings
     if max_outputs is not None:
         steps = steps[:max_outputs]
     per_time = 16 * num_pes * num_pes * n * len(p) + 64 * num_pes * n
@@ -187,7 +244,11 @@ def run(api, model=DAC, num_pes=2, boundary=PERIODIC, ln_energy=0.0, out_dir=Non
     try:
         for c0 in range(0, len(steps), chunk):
             times = np.array([k * s["dt"] for k in steps[c0:c0 + chunk]])
-            psi_dia = api.dvr_propagate(num_pes, n, eigvec, eigval, psi0, times)
+            if absorbing:  # the chunk's states from the last one; the first output is psi0 itself
+                first = psi0[None, :] if c0 == 0 else np.empty((0, len(psi0)), dtype=np.complex128)
+                psi_dia = np.concatenate([first, api.dvr_apply(num_pes, n, U, psi0 if c0 == 0 else psi_dia[-1], len(times) - len(first))])
+            else:
+                psi_dia = api.dvr_propagate(num_pes, n, eigvec, eigval, psi0, times)
             psi_adia = to_adiabatic(psi_dia, basis)
             if device_text:
                 P, wav = api.wigner(num_pes, boundary, x[0], dx, p, psi_adia, energies=energies, mass=mass, averages=True, device_out=True)
@@ -212,6 +273,8 @@ def run(api, model=DAC, num_pes=2, boundary=PERIODIC, ln_energy=0.0, out_dir=Non
                         stop = f"GET OUT OF INTERACTING REGION, STOP EVOLVING AT {t:g}"
                     elif (X - last_x) * s["p0"] < 0:
                         stop = f"DIRECTION REVERSED DUE TO REFLECTION / PBC, STOP EVOLVING AT {t:g}"
+                    elif absorbing and float(np.sum(pops)) < PPL_LIM:
+                        stop = f"ALMOST ALL POPULATION HAVE BEEN ABSORBED, STOP EVOLVING AT {t:g}"
                     elif np.all(np.abs(pops - old_pop) < CHANGE_LIM):
                         stop = f"POPULATION ON EACH PES IS STABLE. STOP EVOLVING AT {t:g}"
                     if stop:
@@ -228,5 +291,5 @@ def run(api, model=DAC, num_pes=2, boundary=PERIODIC, ln_energy=0.0, out_dir=Non
     head = math.log(s["p0"] ** 2 / 2.0 / mass) if model == DAC else s["p0"]  # main.cpp:308-321
     final_line = " ".join(fmt(v) for v in [head, *pops])
     say(stop or "FINISHED ALL OUTPUT TIMES")
-    return dict(setup=s, records=records, stop=stop, final_line=final_line, eigh_seconds=t_eigh, total_seconds=t_end - t0,
+    return dict(setup=s, records=records, stop=stop, final_line=final_line, eigh_seconds=t_eigh, propagator_seconds=t_power, total_seconds=t_end - t0,
                 seconds_per_output=(t_end - t_loop) / max(1, len(records)), stop_time=records[-1]["t"] if records else None)

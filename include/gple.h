@@ -153,7 +153,8 @@ typedef enum gple_timer {
 	GPLE_TIMER_MQCL = 5,           /* the step kernels of one gple_mqcl_evolve call (all its steps, no set-up); count = its calls */
 	GPLE_TIMER_RECON = 6,          /* the device work of one gple_nlml_weights / gple_grid_survey / gple_grid_select / gple_grid_reconstruct call (and of their _cross forms); count = calls */
 	GPLE_TIMER_FORMAT = 7,         /* the three kernels of one gple_format_g call (no staging, no copy of the text); count = calls */
-	GPLE_TIMER_PARSE = 8           /* the kernels of one gple_parse_g call (three, or two when it only counts; no staging, no copies); count = calls */
+	GPLE_TIMER_PARSE = 8,          /* the kernels of one gple_parse_g call (three, or two when it only counts; no staging, no copies); count = calls */
+	GPLE_TIMER_DVR_POWER = 9       /* the products of one gple_dvr_propagator call (Horner form of P4 and the binary power; no set-up, no copies); count = calls */
 } gple_timer;
 int gple_ctx_enable_timing(gple_ctx* ctx, int on);
 /* Synchronises the stream, then: last = milliseconds of the most recent interval; total / count = accumulated since
@@ -373,13 +374,15 @@ int gple_evolve_n(gple_ctx* ctx, int num_pes, const gple_element* elements, int 
 int gple_pes_adiabatic_n(gple_ctx* ctx, int num_pes, int model, const double* x, size_t M, unsigned flags, double* out);
 
 /* ---- exact DVR dynamics (schrodinger_equation/ of the reference) ------------------------------------------------------- */
-/* The reference's exact quantum dynamics of the same models, for the non-absorbing boundaries.  num_pes = 2 or 3, models as gple_evolve_n
- * (TSAC = 3 only at three levels); wavefunctions are num_pes n_grids (re, im) pairs with the index m n_grids + a (general.cpp:126, 137);
+/* The reference's exact quantum dynamics of the same models.  The reflective and periodic boundaries are propagated spectrally
+ * (gple_dvr_propagate); the absorbing boundary by powers of the one-step RK4 propagator (gple_dvr_absorber, gple_dvr_propagator,
+ * gple_dvr_apply below).  num_pes = 2 or 3, models as gple_evolve_n (TSAC = 3 only at three levels); wavefunctions are num_pes n_grids (re, im) pairs with the index m n_grids + a (general.cpp:126, 137);
  * grid x_a = x_first + dx a (main.cpp:108). */
 typedef enum gple_dvr_boundary
 {
 	GPLE_DVR_REFLECTIVE = 0, /* general.h:92; Colbert-Miller kinetic energy, general.cpp:154-175 */
-	GPLE_DVR_PERIODIC = 1    /* general.h:91 (the reference's default); general.cpp:176-198. The absorbing boundary is not provided */
+	GPLE_DVR_PERIODIC = 1    /* general.h:91 (the reference's default); general.cpp:176-198.  The absorbing boundary (general.h:88-93) is no value of this enum: its H is the
+	                          * reflective one (the reference's switch falls through to it) and its absorber comes from gple_dvr_absorber */
 } gple_dvr_boundary;
 /* Hamiltonian_construction (general.cpp:106-200) without the absorbing term: H (dim x dim, dim = num_pes n_grids, real symmetric) holds the
  * diabatic potential on the diagonal grid blocks and the kinetic energy on the diagonal surface blocks, every entry in the reference's
@@ -404,6 +407,29 @@ int gple_dvr_propagate(gple_ctx* ctx, int num_pes, size_t n_grids, const double*
  * and p^2 / 2 mass; two calls on the same input return the same bits.  Only the elements j <= i are summed, P_ji = conj(P_ij). */
 int gple_wigner(gple_ctx* ctx, int num_pes, int boundary, size_t n_grids, double x_first, double dx, const double* p, size_t n_p,
 	const double* psi, size_t T, const double* energies, double mass, unsigned flags, double* phase, double* averages);
+
+/* ---- the absorbing boundary (general.h:88-93): classical RK4 on i hbar dpsi/dt = (H - i W) psi as powers of its one-step propagator ------ */
+/* absorbing_potential (pes.cpp:64-93) on the grid x_a = x_first + dx a: W = 0 for xmin < x < xmax, otherwise
+ *   W = (2 pi hbar / length)^2 2 / mass (1 / (c - xi)^2 + 1 / (c + xi)^2 - 2 / c^2),  c = sqrt(2) K(1 / sqrt(2)),
+ * xi = c (x - xmin) / length for x <= xmin and c (x - xmax) / length for x >= xmax, in the reference's operation order.  (The reference sends
+ * x == xmin down the right-hand branch, where W < 0: a gain.  Here W >= 0 everywhere and W is exactly 0 at both edges.)  W: n_grids values.
+ * GPLE_ERR_BAD_ARG: a non-finite argument, mass <= 0, length <= 0, xmin >= xmax, or a grid that reaches the pole of W
+ * (xmin - x_first >= length or x_last - xmax >= length). */
+int gple_dvr_absorber(gple_ctx* ctx, double x_first, double dx, size_t n_grids, double mass, double xmin, double xmax, double length,
+	unsigned flags, double* W);
+/* The propagator of n_steps classical RK4 steps of length dt (the method general.cpp:233-236 documents) with the constant generator
+ * A = -(W + i H) dt / hbar:  U = P4(A)^n_steps,  P4(z) = 1 + z + z^2 / 2 + z^3 / 6 + z^4 / 24, which is what n_steps RK4 steps apply to psi.
+ * H (dim x dim) as gple_dvr_hamiltonian returns it; W (nullable: 0): one value per grid point, applied on every surface.  P4 is formed in
+ * Horner form, the power by left-to-right binary exponentiation; every complex product is four real products on the fp64 MFMA GEMM
+ * (timer: GPLE_TIMER_DVR_POWER).  U: two dim x dim planes, Re then Im, each exactly symmetric.  1 <= n_steps <= 2^30, dt finite,
+ * dim <= 65472 (GPLE_ERR_BAD_ARG beyond: the work space of 7 planes of dim^2 doubles is 240 GB there). */
+int gple_dvr_propagator(gple_ctx* ctx, int num_pes, size_t n_grids, const double* H, const double* W, double dt, size_t n_steps,
+	unsigned flags, double* U);
+/* psi[k] = U^(k + 1) psi0 for k < T (T <= 4096), one streaming matrix-vector kernel launch per application with a fixed reduction order: two
+ * calls on the same input return the same bits, and so does a call continued from another call's last state.  U as gple_dvr_propagator
+ * returns it; psi0: dim (re, im) pairs; basis (nullable) as in gple_dvr_propagate; psi: T x dim (re, im) pairs. */
+int gple_dvr_apply(gple_ctx* ctx, int num_pes, size_t n_grids, const double* U, const double* psi0, size_t T, const double* basis,
+	unsigned flags, double* psi);
 
 /* ---- exact MQCLE dynamics (liouville_equation/ of the reference) ------------------------------------------------------- */
 /* The mixed quantum-classical Liouville equation on the square (x, p) grid of n points per axis, evolved in the diabatic basis
