@@ -1,8 +1,10 @@
 """Exact DVR dynamics of Tully's dual avoided crossing at the defaults of the reference's schrodinger_equation/input.py (mass 2000,
 x0 = -8, box [-15, 15], dx <= 0.1, sigma_p = p0 / 20, about 50 outputs): the six files of schrodinger_equation/main.cpp in an output
 directory and the final stdout line.  Run on a GPU box:
-    python examples/exact_dvr.py [lnE] [out_dir] [text|npy|none] [reflective|periodic|absorbing]
-With `absorbing` the packet leaves the box through an absorbing region on either side (no eigh)."""
+    python examples/exact_dvr.py [lnE] [out_dir] [text|npy|none] [reflective|periodic|absorbing] [flux]
+With `absorbing` the packet leaves the box through an absorbing region on either side (no eigh).  `absorbing flux` runs until
+all of it has left and accounts for it: absorbed.txt, and a last line with the head of the final line, the absorbed population on the left
+(reflection) and on the right (transmission) per adiabatic surface, and what is left in the box."""
 import os
 import sys
 
@@ -16,15 +18,18 @@ ln_e = float(sys.argv[1]) if len(sys.argv) > 1 else 0.0
 out_dir = sys.argv[2] if len(sys.argv) > 2 else "exact_dvr_out"
 write_phase = sys.argv[3] if len(sys.argv) > 3 else "text"
 boundary = {"reflective": exact.REFLECTIVE, "absorbing": exact.ABSORBING}.get(sys.argv[4] if len(sys.argv) > 4 else "", exact.PERIODIC)
+flux = len(sys.argv) > 5 and sys.argv[5] == "flux"
 api = pkg.open_api(0)
 try:
     res = exact.run(api, model=exact.DAC, num_pes=2, boundary=boundary, ln_energy=ln_e, out_dir=out_dir,
-                    write_phase=None if write_phase == "none" else write_phase, log=print)
+                    write_phase=None if write_phase == "none" else write_phase, log=print, **(dict(flux=True, until_absorbed=True) if flux else {}))
     s = res["setup"]
     timing = f"propagator {res['propagator_seconds']:.2f} s" if boundary == exact.ABSORBING else f"eigh {res['eigh_seconds']:.2f} s"
     print(f"grid: {s['n_grids']} points, dx = {s['dx']:g}; {timing}; {len(res['records'])} outputs, "
           f"{1e3 * res['seconds_per_output']:.1f} ms per output step; total {res['total_seconds']:.1f} s")
     print("final populations:", np.array2string(res["records"][-1]["populations"], precision=6))
     print(res["final_line"])
+    if flux:
+        print(res["scattering_line"])
 finally:
     api.close()

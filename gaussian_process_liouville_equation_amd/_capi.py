@@ -328,6 +328,8 @@ def _signatures():
         "dvr_absorber": (st, [CTX, d, d, sz, d, d, d, d, u, _dp]),
         "dvr_propagator": (st, [CTX, i, sz, _dp, _dp, d, sz, u, _dp]),
         "dvr_apply": (st, [CTX, i, sz, _dp, _dp, sz, _dp, u, _dp]),
+        "dvr_flux": (st, [CTX, i, sz, _dp, _dp, d, sz, _dp, sz, u, _dp, _dp]),
+        "dvr_flux_apply": (st, [CTX, i, sz, _dp, _dp, sz, u, _dp]),
         "mqcl_transform": (st, [CTX, i, i, _dp, sz, i, i, u, _dp, _dp]),
         "mqcl_evolve": (st, [CTX, i, i, _dp, _dp, sz, d, d, d, d, sz, u, _dp]),
         "mqcl_observe": (st, [CTX, i, i, _dp, _dp, sz, d, d, d, u, _dp, _dp, _dp, _dp]),
@@ -497,7 +499,7 @@ class Api:
 
     def timing(self, which):
         """(last_ms, total_ms, count) of a gple_timer: 0 = fit, 1 = predict call, 2 = fused predict kernel, 3 = derivative GEMM, 4 = Wigner kernel, 5 = MQCLE
-        steps, 6 = the device work of the reconstruction entry points, 7 = the kernels of format_g, 8 = the kernels of parse_g, 9 = the products of dvr_propagator."""
+        steps, 6 = the device work of the reconstruction entry points, 7 = the kernels of format_g, 8 = the kernels of parse_g, 9 = the products of dvr_propagator, 10 = the products of dvr_flux."""
         last, total, count = C.c_double(), C.c_double(), C.c_long()
         self._check(self.lib.gple_ctx_get_timing(self.ctx, which, C.byref(last), C.byref(total), C.byref(count)))
         return last.value, total.value, count.value
@@ -717,6 +719,63 @@ class Api:
         planes = np.ascontiguousarray(planes)
         self._check(self.lib.gple_dvr_apply(self.ctx, int(num_pes), int(n_grids), _ptr(planes), _ptr(psi0.view(np.float64)), T, _ptr(basis), 0,
                                             _ptr(out.view(np.float64))))
+        return out
+
+    # ---- what the absorber took: the quadratic forms per channel and their application (gple_dvr_flux / _flux_apply) ---------------------------
+    def dvr_flux(self, num_pes, n_grids, H, W, dt, n_steps, basis, n_left, device_out=False, want_u=True):
+        """gple_dvr_flux: (U, G).  G (2 num_pes, dim, dim) complex Hermitian: Re psi^H G[c] psi is what channel c = side num_pes + k (side 0: the
+        grid points a < n_left; k: the adiabatic state, column k of basis (n, num_pes, num_pes)) absorbs over n_steps RK4 steps from the diabatic
+        psi, unscaled; the channels add up to |psi|^2 - |U psi|^2.  A figure may be slightly negative.  U as dvr_propagator, or
+        None without want_u.  device_out: both stay on the device as float64 tensors, U (2, dim, dim) and G (2 num_pes, 2, dim, dim) = (Re, Im)
+        planes, which dvr_apply and dvr_flux_apply accept as they are"""
+        num_pes, n_grids = int(num_pes), int(n_grids)
+        dim = num_pes * n_grids
+        H, basis = _f64(H), _f64(basis)
+        W = None if W is None else _f64(W)
+        if H.shape != (dim, dim) or (W is not None and W.shape != (n_grids,)) or basis.shape != (n_grids, num_pes, num_pes):
+            raise ValueError("H (dim, dim), W (n_grids,) and basis (n_grids, num_pes, num_pes) with dim = num_pes * n_grids")
+        if device_out:
+            import torch
+            where = torch.device("cuda", self.device)
+            tH, tb = torch.from_numpy(H).to(where), torch.from_numpy(basis).to(where)
+            tW = None if W is None else torch.from_numpy(W).to(where)
+            U = torch.empty((2, dim, dim), dtype=torch.float64, device=where) if want_u else None
+            G = torch.empty((2 * num_pes, 2, dim, dim), dtype=torch.float64, device=where)
+            torch.cuda.synchronize(where)  # the uploads, before the context's stream reads them
+            (pH, pW, pb, pU, pG), flags = _io(tH, tW, tb, U, G)
+            self._check(self.lib.gple_dvr_flux(self.ctx, num_pes, n_grids, pH, pW, float(dt), int(n_steps), pb, int(n_left), flags, pU, pG))
+            self.synchronize()
+            return U, G
+        planes = np.empty((2, dim, dim)) if want_u else None
+        G = np.empty((2 * num_pes, 2, dim, dim))
+        self._check(self.lib.gple_dvr_flux(self.ctx, num_pes, n_grids, _ptr(H), _ptr(W), float(dt), int(n_steps), _ptr(basis), int(n_left), 0, _ptr(planes), _ptr(G)))
+        return (planes[0] + 1j * planes[1] if want_u else None), G[:, 0] + 1j * G[:, 1]
+
+    def dvr_flux_apply(self, num_pes, n_grids, G, psi):
+        """gple_dvr_flux_apply: Re psi_t^H G[c] psi_t for the diabatic states psi (T, dim) or (dim,) -> (T, 2, num_pes), [t, side, surface],
+        unscaled (a population is this times dx).  G: the complex (2 num_pes, dim, dim) array of dvr_flux, or its device tensor"""
+        num_pes, n_grids = int(num_pes), int(n_grids)
+        dim = num_pes * n_grids
+        psi = np.atleast_2d(_cplx(psi))
+        T = psi.shape[0]
+        if psi.shape != (T, dim) or not 1 <= T <= 4096:
+            raise ValueError("psi (T, dim) with dim = num_pes * n_grids and 1 <= T <= 4096")
+        out = np.empty((T, 2, num_pes))
+        if _on_device(G):
+            if tuple(G.shape) != (2 * num_pes, 2, dim, dim) or not G.is_cuda or str(G.dtype) != "torch.float64" or not G.is_contiguous():
+                raise ValueError("a tensor G must be the contiguous float64 (2 num_pes, 2, dim, dim) planes of dvr_flux(device_out=True) on the GPU")
+            import torch
+            tv = torch.from_numpy(psi.view(np.float64)).to(G.device)
+            tout = torch.empty((T, 2 * num_pes), dtype=torch.float64, device=G.device)
+            torch.cuda.synchronize(G.device)
+            (pG, pv, po), flags = _io(G, tv, tout)
+            self._check(self.lib.gple_dvr_flux_apply(self.ctx, num_pes, n_grids, pG, pv, T, flags, po))
+            self.synchronize()
+            return tout.cpu().numpy().reshape(T, 2, num_pes)
+        if tuple(np.shape(G)) != (2 * num_pes, dim, dim):
+            raise ValueError("G (2 num_pes, dim, dim) complex with dim = num_pes * n_grids")
+        planes = np.ascontiguousarray(np.stack([np.real(G), np.imag(G)], axis=1).astype(np.float64))
+        self._check(self.lib.gple_dvr_flux_apply(self.ctx, num_pes, n_grids, _ptr(planes), _ptr(psi.view(np.float64)), T, 0, _ptr(out)))
         return out
 
     # ---- text output (gple_format_g) ------------------------------------------------------------------------------------------------------------

@@ -180,6 +180,63 @@ extern "C"
 		return GPLE_OK;
 	}
 
+	/* ---- what the absorber took (gple_dvr_power.hip): the quadratic forms of the absorbed population per channel, and their application ------ */
+	int gple_dvr_flux(gple_ctx* ctx, int num_pes, size_t n_grids, const double* H, const double* W, double dt, size_t n_steps, const double* basis,
+		size_t n_left, unsigned flags, double* U, double* G)
+	{
+		if (!ctx || (num_pes != 2 && num_pes != 3) || !dvr_grid_ok(n_grids, 1.0) || !H || !G || !basis || n_left > n_grids || !std::isfinite(dt) ||
+			n_steps < 1 || n_steps > (1ul << 30) || round_up(static_cast<size_t>(num_pes) * n_grids, 64) > static_cast<size_t>(DVR_POWER_MAX_LD))
+			return GPLE_ERR_BAD_ARG;
+		GPLE_OPEN(ctx);
+		const bool dev = flags & GPLE_IO_DEVICE;
+		const int n = static_cast<int>(n_grids);
+		const size_t dim = static_cast<size_t>(num_pes) * n_grids, ld = round_up(dim, 64);
+		GPLE_CALL(ctx);
+		hipStream_t st = ctx->stream;
+		Scratch work(ctx), fwork(ctx);
+		Staged h(ctx, dev), w(ctx, dev), b(ctx, dev), u(ctx, dev), g(ctx, dev);
+		// every allocation before the first launch: one that does not fit leaves the outputs untouched
+		GPLE_HIP(ctx, work.get(dvr_power_work_doubles(num_pes, n)));
+		GPLE_HIP(ctx, fwork.get(dvr_flux_work_doubles(num_pes, n)));
+		GPLE_HIP(ctx, u.out(U, 2 * dim * dim));
+		GPLE_HIP(ctx, g.out(G, 4 * num_pes * dim * dim));
+		GPLE_HIP(ctx, h.in(H, dim * dim));
+		GPLE_HIP(ctx, w.in(W, n_grids));
+		GPLE_HIP(ctx, b.in(basis, n_grids * num_pes * num_pes));
+		const DvrFlux flux{b.p, static_cast<int>(n_left), fwork.p};
+		const double* R = nullptr;
+		GPLE_HIP(ctx, launch_dvr_power(ctx, st, num_pes, n, h.p, w.p, dt, static_cast<long>(n_steps), work.p, &R, &flux));
+		for (size_t plane = 0; u.p && plane < 2; ++plane)
+			GPLE_HIP(ctx, hipMemcpy2DAsync(u.p + plane * dim * dim, dim * sizeof(double), R + plane * ld * ld, ld * sizeof(double), dim * sizeof(double), dim,
+				hipMemcpyDeviceToDevice, st));
+		GPLE_HIP(ctx, launch_dvr_flux_export(st, num_pes, n, flux, g.p));
+		GPLE_HIP(ctx, u.back());
+		GPLE_HIP(ctx, g.back());
+		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
+		return GPLE_OK;
+	}
+
+	int gple_dvr_flux_apply(gple_ctx* ctx, int num_pes, size_t n_grids, const double* G, const double* psi, size_t T, unsigned flags, double* absorbed)
+	{
+		if (!ctx || (num_pes != 2 && num_pes != 3) || !dvr_grid_ok(n_grids, 1.0) || T < 1 || T > 4096 || !G || !psi || !absorbed) return GPLE_ERR_BAD_ARG;
+		GPLE_OPEN(ctx);
+		const bool dev = flags & GPLE_IO_DEVICE;
+		const int n = static_cast<int>(n_grids);
+		const size_t dim = static_cast<size_t>(num_pes) * n_grids;
+		GPLE_CALL(ctx);
+		hipStream_t st = ctx->stream;
+		Scratch partial(ctx);
+		Staged g(ctx, dev), v(ctx, dev), o(ctx, dev);
+		GPLE_HIP(ctx, partial.get(dvr_flux_apply_work_doubles(num_pes, n, static_cast<int>(T))));
+		GPLE_HIP(ctx, o.out(absorbed, T * 2 * num_pes));
+		GPLE_HIP(ctx, g.in(G, 4 * num_pes * dim * dim));
+		GPLE_HIP(ctx, v.in(psi, 2 * dim * T));
+		GPLE_HIP(ctx, launch_dvr_flux_apply(st, num_pes, n, g.p, v.p, static_cast<int>(T), partial.p, o.p));
+		GPLE_HIP(ctx, o.back());
+		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
+		return GPLE_OK;
+	}
+
 	/* ---- exact MQCLE dynamics (gple_mqcl.hip; liouville_equation/ of the reference) ------------------------------------------------------ */
 	static bool mqcl_size_ok(int num_pes, int model, size_t n) { return dvr_model_ok(num_pes, model) && n >= 4 && n <= 4096; }
 

@@ -288,8 +288,22 @@ namespace gple
 	constexpr long DVR_POWER_MAX_LD = 65472; // ld <= 65535 = the largest gridDim.y (a column per block row in the set-up kernels); 7 ld^2 doubles of work are 240 GB there
 	size_t dvr_power_work_doubles(int num_pes, int n);
 	// H: dim x dim, W: n values or null; *result: the Re plane of U inside work (Im follows at + ld ld).  GPLE_TIMER_DVR_POWER of ctx spans the products
+	// with flux: the quadratic forms of the absorbed population beside the power, and GPLE_TIMER_DVR_FLUX instead
+	struct DvrFlux
+	{
+		const double* basis; // n x num_pes x num_pes
+		int n_left;          // the grid points a < n_left are side 0
+		double* work;        // dvr_flux_work_doubles: L, D, T (two ld x ld planes each), then the 2 num_pes channels G_c (two planes each), column-major
+	};
+	size_t dvr_flux_work_doubles(int num_pes, int n);
 	hipError_t launch_dvr_power(Ctx* ctx, hipStream_t s, int num_pes, int n, const double* H, const double* W, double dt, long n_steps, double* work,
-		const double** result);
+		const double** result, const DvrFlux* flux = nullptr);
+	// channel c of flux.work without its padding, row-major, into out (2 num_pes channels of two dim x dim planes)
+	hipError_t launch_dvr_flux_export(hipStream_t s, int num_pes, int n, const DvrFlux& flux, double* out);
+	// absorbed[t 2 num_pes + c] = Re psi_t^H G_c psi_t; G as launch_dvr_flux_export writes it; partial: dvr_flux_apply_work_doubles
+	constexpr int DVR_FLUX_CHUNK = 64; // states per pair of launches (the row results of a chunk are DVR_FLUX_CHUNK x 2 num_pes x dim doubles)
+	size_t dvr_flux_apply_work_doubles(int num_pes, int n, int T);
+	hipError_t launch_dvr_flux_apply(hipStream_t s, int num_pes, int n, const double* G, const double* psi, int T, double* partial, double* absorbed);
 	// psi[k] = U^(k + 1) psi0, k < T; U: two dim x dim planes; scratch: T x dim pairs when basis != null (the diabatic states), unused otherwise
 	hipError_t launch_dvr_apply(hipStream_t s, int num_pes, int n, const double* U, const double* psi0, int T, const double* basis, double* scratch, double* psi);
 	// ---- exact MQCLE dynamics (gple_mqcl.hip): num_pes = 2 or 3, 4 <= n <= 4096, rho: num_pes^2 x n x n (re, im) pairs, x major ------------

@@ -1,12 +1,13 @@
 """Exact DVR wavepacket dynamics: the reference's schrodinger_equation/main.cpp, restated on the library's device entry points
-(gple_dvr_hamiltonian, gple_dvr_propagate, gple_wigner; for the absorbing boundary gple_dvr_absorber, gple_dvr_propagator, gple_dvr_apply;
-DESIGN.md §11).
+(gple_dvr_hamiltonian, gple_dvr_propagate, gple_wigner; for the absorbing boundary gple_dvr_absorber, gple_dvr_propagator, gple_dvr_apply,
+and gple_dvr_flux, gple_dvr_flux_apply for what the absorber took).
 
     setup()            main.cpp:41-146 with the defaults of schrodinger_equation/input.py
     initial_adiabatic_psi(), to_diabatic()  general.cpp:70-103 (Gaussian on the lowest adiabatic surface) taken to the diabatic basis (main.cpp:158-161)
     run()              the output loop of main.cpp:210-298: propagate, adiabatic psi, populations (general.cpp:480-495), <E> <x> <p> from psi
                        (general.cpp:443-478), the Wigner transform and its averages (general.cpp:324-411), the stop criteria (main.cpp:256-294)
-    writers            x.txt, p.txt, t.txt, psi.txt, phase.txt, averages.txt in the reference's line layout; numbers as %g (output.py)
+    writers            x.txt, p.txt, t.txt, psi.txt, phase.txt, averages.txt in the reference's line layout; numbers as %g (output.py);
+                       absorbed.txt (flux=True, no file of the reference's): t, the absorbed population per side and surface, what is left
 
 The Hamiltonian is diagonalised once per run with numpy.linalg.eigh on the host (set-up, not the hot path: DESIGN.md §11).  The absorbing
 boundary needs no eigh: the propagator of the output_step RK4 steps between two outputs is formed once on the device as a matrix power and
@@ -194,12 +195,21 @@ def averages_line(t, E, X, P, pops, phase_avg):
 
 
 def run(api, model=DAC, num_pes=2, boundary=PERIODIC, ln_energy=0.0, out_dir=None, write_phase="text", max_outputs=None, chunk_bytes=1 << 30,
-        p_grid=None, log=None, **setup_kw):
+        p_grid=None, log=None, flux=False, until_absorbed=False, **setup_kw):
     """The loop of main.cpp:210-298.  boundary=ABSORBING: no eigh; the propagator of output_step RK4 steps is formed once (gple_dvr_propagator, kept
     on the device) and applied once per output (gple_dvr_apply); the Wigner transform is the reflective one (general.cpp:363-364), <E> uses the
     real H, and the stop criteria carry the PplLim clause.  write_phase: "text" (phase.txt), "npy" (phase_<k>.npy per output time) or None;
-    out_dir None writes no file.  max_outputs caps the output times.  Returns a dict with the setup, per-output records and the final stdout line."""
+    out_dir None writes no file.  max_outputs caps the output times.  Returns a dict with the setup, per-output records and the final stdout line.
+    flux (absorbing boundary only): U comes with the quadratic forms of gple_dvr_flux, one per side of the box (the grid points left and right
+    of its centre) and adiabatic surface; before every application of U the state's figures (gple_dvr_flux_apply, times dx) join a running
+    total, so every record carries `absorbed` (2, num_pes): what has left up to its output time, [left | right][surface], reflection and
+    transmission for a packet that starts on the left.  The figures and the populations left add up to the initial population to rounding;
+    a figure may be slightly negative.  absorbed.txt has a line per output: t, the 2 num_pes figures, the population left; the
+    result gains `absorbed`, `scattering_line` (the final line's head, the figures, the remainder) and `flux_seconds`.
+    until_absorbed (absorbing boundary only): the PplLim clause is the only stop, tested at every output whatever <x> is."""
     absorbing = boundary == ABSORBING
+    if (flux or until_absorbed) and not absorbing:
+        raise ValueError("flux and until_absorbed belong to boundary=ABSORBING")
     if absorbing:
         setup_kw["boundary"], boundary = ABSORBING, REFLECTIVE  # H and the Wigner transform of the reflective boundary (the reference's switches fall through)
     s = setup(ln_energy, **setup_kw)
@@ -213,7 +223,11 @@ def run(api, model=DAC, num_pes=2, boundary=PERIODIC, ln_energy=0.0, out_dir=Non
         if s["output_step"] < 1:
             raise ValueError("the output time is shorter than one time step")
         W = api.dvr_absorber(x[0], dx, n, mass, s["xmin"], s["xmax"], s["absorbing_length"])
-        U = api.dvr_propagator(num_pes, n, H, W, s["dt"], s["output_step"], device_out=True)
+        if flux:
+            n_left = int(np.sum(x < (s["xmin"] + s["xmax"]) / 2.0))
+            U, G = api.dvr_flux(num_pes, n, H, W, s["dt"], s["output_step"], basis, n_left, device_out=True)
+        else:
+            U = api.dvr_propagator(num_pes, n, H, W, s["dt"], s["output_step"], device_out=True)
         t_eigh, t_power = 0.0, time.perf_counter() - t_h
         say(f"dx = {dx:g}, {n} grids from {x[0]:g} to {x[-1]:g}; dt = {s['dt']:g} ({s['halvings']} halvings), {s['total_step']} steps; "
             f"propagator of {s['output_step']} steps, {num_pes * n} x {num_pes * n}: {t_power:.2f} s")
@@ -233,13 +247,14 @@ def run(api, model=DAC, num_pes=2, boundary=PERIODIC, ln_energy=0.0, out_dir=Non
         os.makedirs(out_dir, exist_ok=True)
         write_grid(os.path.join(out_dir, "x.txt"), x)
         write_grid(os.path.join(out_dir, "p.txt"), p)
-        for name in ("t.txt", "psi.txt", "averages.txt"):
+        for name in ("t.txt", "psi.txt", "averages.txt") + (("absorbed.txt",) if flux else ()):
             files[name] = open(os.path.join(out_dir, name), "w")
         if write_phase == "text":
             files["phase.txt"] = open(os.path.join(out_dir, "phase.txt"), "wb")
     # phase.txt on the device: P stays there and only its text crosses; an api without format_g keeps the Python writer
     device_text = bool(files) and write_phase == "text" and hasattr(api, "format_g")
     records, stop, last_x, old_pop, pops = [], None, s["x0"], np.zeros(num_pes), None
+    absorbed = np.zeros((2, num_pes))  # what has left before the current output
     t_loop = time.perf_counter()
     try:
         for c0 in range(0, len(steps), chunk):
@@ -250,6 +265,8 @@ def run(api, model=DAC, num_pes=2, boundary=PERIODIC, ln_energy=0.0, out_dir=Non
             else:
                 psi_dia = api.dvr_propagate(num_pes, n, eigvec, eigval, psi0, times)
             psi_adia = to_adiabatic(psi_dia, basis)
+            if flux:
+                leaving = api.dvr_flux_apply(num_pes, n, G, psi_dia) * dx  # what each state of the chunk loses to the next application of U
             if device_text:
                 P, wav = api.wigner(num_pes, boundary, x[0], dx, p, psi_adia, energies=energies, mass=mass, averages=True, device_out=True)
             else:
@@ -259,6 +276,11 @@ def run(api, model=DAC, num_pes=2, boundary=PERIODIC, ln_energy=0.0, out_dir=Non
                 pops = populations(psi_adia[q], n, dx, num_pes)
                 E, X, Pm = psi_averages(psi_dia[q], H, D, x, dx, num_pes)
                 records.append(dict(t=t, E=E, x=X, p=Pm, populations=pops, phase_averages=wav[q].copy()))
+                if flux:
+                    records[-1]["absorbed"] = absorbed.copy()
+                    if files:
+                        files["absorbed.txt"].write(" ".join(fmt(v) for v in [t, *absorbed.ravel(), float(np.sum(pops))]) + "\n")
+                    absorbed += leaving[q]
                 if files:
                     files["t.txt"].write(fmt(t) + "\n")
                     files["psi.txt"].write(psi_line(psi_adia[q]))
@@ -268,7 +290,11 @@ def run(api, model=DAC, num_pes=2, boundary=PERIODIC, ln_energy=0.0, out_dir=Non
                         files["phase.txt"].write(phase_block(P[q]).encode())
                     elif write_phase == "npy":
                         np.save(os.path.join(out_dir, f"phase_{len(records) - 1}.npy"), P[q])
-                if X > 0.0:  # main.cpp:256-287
+                if until_absorbed:
+                    if float(np.sum(pops)) < PPL_LIM:
+                        stop = f"ALMOST ALL POPULATION HAVE BEEN ABSORBED, STOP EVOLVING AT {t:g}"
+                        break
+                elif X > 0.0:  # main.cpp:256-287
                     if X > -s["x0"]:
                         stop = f"GET OUT OF INTERACTING REGION, STOP EVOLVING AT {t:g}"
                     elif (X - last_x) * s["p0"] < 0:
@@ -291,5 +317,9 @@ def run(api, model=DAC, num_pes=2, boundary=PERIODIC, ln_energy=0.0, out_dir=Non
     head = math.log(s["p0"] ** 2 / 2.0 / mass) if model == DAC else s["p0"]  # main.cpp:308-321
     final_line = " ".join(fmt(v) for v in [head, *pops])
     say(stop or "FINISHED ALL OUTPUT TIMES")
-    return dict(setup=s, records=records, stop=stop, final_line=final_line, eigh_seconds=t_eigh, propagator_seconds=t_power, total_seconds=t_end - t0,
+    extra = {}
+    if flux:
+        taken = records[-1]["absorbed"] if records else np.zeros((2, num_pes))
+        extra = dict(absorbed=taken, scattering_line=" ".join(fmt(v) for v in [head, *taken.ravel(), float(np.sum(pops))]), flux_seconds=t_power)
+    return dict(**extra, setup=s, records=records, stop=stop, final_line=final_line, eigh_seconds=t_eigh, propagator_seconds=t_power, total_seconds=t_end - t0,
                 seconds_per_output=(t_end - t_loop) / max(1, len(records)), stop_time=records[-1]["t"] if records else None)

@@ -154,7 +154,8 @@ typedef enum gple_timer {
 	GPLE_TIMER_RECON = 6,          /* the device work of one gple_nlml_weights / gple_grid_survey / gple_grid_select / gple_grid_reconstruct call (and of their _cross forms); count = calls */
 	GPLE_TIMER_FORMAT = 7,         /* the three kernels of one gple_format_g call (no staging, no copy of the text); count = calls */
 	GPLE_TIMER_PARSE = 8,          /* the kernels of one gple_parse_g call (three, or two when it only counts; no staging, no copies); count = calls */
-	GPLE_TIMER_DVR_POWER = 9       /* the products of one gple_dvr_propagator call (Horner form of P4 and the binary power; no set-up, no copies); count = calls */
+	GPLE_TIMER_DVR_POWER = 9,      /* the products of one gple_dvr_propagator call (Horner form of P4 and the binary power; no set-up, no copies); count = calls */
+	GPLE_TIMER_DVR_FLUX = 10       /* the products of one gple_dvr_flux call (P4, the power, the loss matrix and every sandwich; no set-up, no copies); count = calls */
 } gple_timer;
 int gple_ctx_enable_timing(gple_ctx* ctx, int on);
 /* Synchronises the stream, then: last = milliseconds of the most recent interval; total / count = accumulated since
@@ -430,6 +431,28 @@ int gple_dvr_propagator(gple_ctx* ctx, int num_pes, size_t n_grids, const double
  * returns it; psi0: dim (re, im) pairs; basis (nullable) as in gple_dvr_propagate; psi: T x dim (re, im) pairs. */
 int gple_dvr_apply(gple_ctx* ctx, int num_pes, size_t n_grids, const double* U, const double* psi0, size_t T, const double* basis,
 	unsigned flags, double* psi);
+
+/* Where the absorber took the packet: the absorbed population of n_steps RK4 steps, per side of the box and adiabatic surface, as Hermitian
+ * quadratic forms psi^H G_c psi ("What the absorber took").  With P = P4(A) and R_k = P^k (complex symmetric: P^H = conj(P)):
+ *   L = I - conj(P) P                       the loss of one step, |psi|^2 - |P psi|^2 = psi^H L psi
+ *   Pi_c                                    the projector on channel c = side num_pes + k: the grid points a < n_left (side 0) or a >= n_left
+ *                                           (side 1) times the adiabatic state k there, column k of `basis` as gple_dvr_hamiltonian returns it
+ *   D_c = (Pi_c L + L Pi_c) / 2             sum_c D_c = L to rounding: the channels add up to the norm loss itself
+ *   G_c = sum_{k < n_steps} conj(R_k) D_c R_k
+ * formed beside the power by the same left-to-right recurrence (G_c += conj(R) (G_c R) before a squaring, G_c += conj(R) (D_c R) before a
+ * multiplication by P), every product on the fp64 MFMA GEMM (timer: GPLE_TIMER_DVR_FLUX, which spans the power's products too).  D_c is not
+ * positive semidefinite: a channel's figure may be negative by O((|H| dt)^2) of the loss, and is not clamped.
+ * G: 2 num_pes channels of two dim x dim planes (Re, then Im), row-major, G_c(r, q) at r dim + q; Re exactly symmetric, Im exactly
+ * antisymmetric with an exactly zero diagonal.  U (nullable): the bits of gple_dvr_propagator for the same arguments.  H, W (nullable), dt,
+ * n_steps, dim as gple_dvr_propagator; basis (n_grids x num_pes x num_pes) is required; n_left <= n_grids.  Work space: 13 + 4 num_pes
+ * planes of dim^2 doubles. */
+int gple_dvr_flux(gple_ctx* ctx, int num_pes, size_t n_grids, const double* H, const double* W, double dt, size_t n_steps, const double* basis,
+	size_t n_left, unsigned flags, double* U, double* G);
+/* absorbed[t 2 num_pes + c] = Re psi_t^H G_c psi_t for the T diabatic states psi (T x dim (re, im) pairs, 1 <= T <= 4096), unscaled (a
+ * population is this times dx).  A wave per row of G_c with lane-strided sums in ascending order and a fixed butterfly, the row results summed
+ * in a fixed order by a second kernel; no atomics: a state's figures are the same bits whatever T is and wherever it stands in the call.  A
+ * sweep over G serves four states; the sweeps of a call run back to back, 64 states per pair of launches. */
+int gple_dvr_flux_apply(gple_ctx* ctx, int num_pes, size_t n_grids, const double* G, const double* psi, size_t T, unsigned flags, double* absorbed);
 
 /* ---- exact MQCLE dynamics (liouville_equation/ of the reference) ------------------------------------------------------- */
 /* The mixed quantum-classical Liouville equation on the square (x, p) grid of n points per axis, evolved in the diabatic basis
