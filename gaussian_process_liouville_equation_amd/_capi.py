@@ -330,6 +330,7 @@ def _signatures():
         "dvr_apply": (st, [CTX, i, sz, _dp, _dp, sz, _dp, u, _dp]),
         "dvr_flux": (st, [CTX, i, sz, _dp, _dp, d, sz, _dp, sz, u, _dp, _dp]),
         "dvr_flux_apply": (st, [CTX, i, sz, _dp, _dp, sz, u, _dp]),
+        "dvr_spectrum": (st, [CTX, i, sz, _dp, _dp, d, i, _dp, sz, _dp, _dp, sz, u, _dp, _dp, _dp]),
         "mqcl_transform": (st, [CTX, i, i, _dp, sz, i, i, u, _dp, _dp]),
         "mqcl_evolve": (st, [CTX, i, i, _dp, _dp, sz, d, d, d, d, sz, u, _dp]),
         "mqcl_observe": (st, [CTX, i, i, _dp, _dp, sz, d, d, d, u, _dp, _dp, _dp, _dp]),
@@ -499,7 +500,8 @@ class Api:
 
     def timing(self, which):
         """(last_ms, total_ms, count) of a gple_timer: 0 = fit, 1 = predict call, 2 = fused predict kernel, 3 = derivative GEMM, 4 = Wigner kernel, 5 = MQCLE
-        steps, 6 = the device work of the reconstruction entry points, 7 = the kernels of format_g, 8 = the kernels of parse_g, 9 = the products of dvr_propagator, 10 = the products of dvr_flux."""
+        steps, 6 = the device work of the reconstruction entry points, 7 = the kernels of format_g, 8 = the kernels of parse_g, 9 = the products of dvr_propagator, 10 = the products of dvr_flux,
+        11 = the device work of dvr_spectrum."""
         last, total, count = C.c_double(), C.c_double(), C.c_long()
         self._check(self.lib.gple_ctx_get_timing(self.ctx, which, C.byref(last), C.byref(total), C.byref(count)))
         return last.value, total.value, count.value
@@ -777,6 +779,29 @@ class Api:
         planes = np.ascontiguousarray(np.stack([np.real(G), np.imag(G)], axis=1).astype(np.float64))
         self._check(self.lib.gple_dvr_flux_apply(self.ctx, num_pes, n_grids, _ptr(planes), _ptr(psi.view(np.float64)), T, 0, _ptr(out)))
         return out
+
+    # ---- the spectrum of one absorbing run (gple_dvr_spectrum) -----------------------------------------------------------------------------------
+    def dvr_spectrum(self, num_pes, n_grids, H, W, dt, levels, basis, n_left, psi0, energies, want_psi=False, want_remaining=True):
+        """gple_dvr_spectrum: (density, psi_e, remaining).  density (n_E, 2, num_pes), [energy, side, surface]: what each channel of dvr_flux
+        absorbed per unit of energy at the total energies `energies` (H's own zero) over the first 2^levels RK4 steps from the diabatic psi0,
+        unscaled (times dx dt / (2 pi hbar): a population per unit energy); a figure may be slightly negative.  psi_e (n_E, dim)
+        complex, with want_psi: sum_{k < 2^levels} e^{i E dt k / hbar} P^k psi0; remaining: |P^(2^levels) psi0|^2.  What is not asked for is None"""
+        num_pes, n_grids = int(num_pes), int(n_grids)
+        dim = num_pes * n_grids
+        H, basis, psi0, energies = _f64(H), _f64(basis), _cplx(psi0), np.atleast_1d(_f64(energies))
+        W = None if W is None else _f64(W)
+        if H.shape != (dim, dim) or (W is not None and W.shape != (n_grids,)) or basis.shape != (n_grids, num_pes, num_pes) or psi0.shape != (dim,):
+            raise ValueError("H (dim, dim), W (n_grids,), basis (n_grids, num_pes, num_pes) and psi0 (dim,) with dim = num_pes * n_grids")
+        n_E = energies.size
+        if energies.ndim != 1 or not 1 <= n_E <= 4096:
+            raise ValueError("energies (n_E,) with 1 <= n_E <= 4096")
+        density = np.empty((n_E, 2, num_pes))
+        psi_e = np.empty((n_E, dim), dtype=np.complex128) if want_psi else None
+        remaining = np.empty(1) if want_remaining else None
+        self._check(self.lib.gple_dvr_spectrum(self.ctx, num_pes, n_grids, _ptr(H), _ptr(W), float(dt), int(levels), _ptr(basis), int(n_left),
+                                               _ptr(psi0.view(np.float64)), _ptr(energies), n_E, 0, _ptr(density),
+                                               None if psi_e is None else _ptr(psi_e.view(np.float64)), _ptr(remaining)))
+        return density, psi_e, (float(remaining[0]) if want_remaining else None)
 
     # ---- text output (gple_format_g) ------------------------------------------------------------------------------------------------------------
     def format_g(self, values, per_line, lines_per_block=0, join=False):

@@ -237,6 +237,56 @@ extern "C"
 		return GPLE_OK;
 	}
 
+	/* ---- the spectrum of one absorbing run (gple_dvr_spectrum.hip): the half-Fourier transform of 2^levels steps per energy, and what each channel took */
+	int gple_dvr_spectrum(gple_ctx* ctx, int num_pes, size_t n_grids, const double* H, const double* W, double dt, int levels, const double* basis,
+		size_t n_left, const double* psi0, const double* energies, size_t n_E, unsigned flags, double* density, double* psi_e, double* remaining)
+	{
+		if (!ctx || (num_pes != 2 && num_pes != 3) || !dvr_grid_ok(n_grids, 1.0) || !H || !basis || !psi0 || !energies || !density || n_left > n_grids ||
+			!std::isfinite(dt) || levels < 0 || levels > 30 || n_E < 1 || n_E > 4096 ||
+			round_up(static_cast<size_t>(num_pes) * n_grids, 64) > static_cast<size_t>(DVR_POWER_MAX_LD))
+			return GPLE_ERR_BAD_ARG;
+		GPLE_OPEN(ctx);
+		const bool dev = flags & GPLE_IO_DEVICE;
+		const int n = static_cast<int>(n_grids), C = 2 * num_pes;
+		const size_t dim = static_cast<size_t>(num_pes) * n_grids;
+		GPLE_CALL(ctx);
+		hipStream_t st = ctx->stream;
+		{ // every energy finite: device energies are looked at on the host first (n_E <= 4096 values)
+			std::vector<double> seen;
+			const double* e = energies;
+			if (dev)
+			{
+				seen.resize(n_E);
+				GPLE_HIP(ctx, hipMemcpyAsync(seen.data(), energies, n_E * sizeof(double), hipMemcpyDeviceToHost, st));
+				GPLE_HIP(ctx, hipStreamSynchronize(st));
+				e = seen.data();
+			}
+			for (size_t k = 0; k < n_E; ++k)
+				if (!std::isfinite(e[k])) return GPLE_ERR_BAD_ARG;
+		}
+		Scratch pwork(ctx), work(ctx);
+		Staged h(ctx, dev), w(ctx, dev), b(ctx, dev), v(ctx, dev), en(ctx, dev), d(ctx, dev), pe(ctx, dev), rem(ctx, dev);
+		// every allocation before the first launch: one that does not fit leaves the outputs untouched
+		GPLE_HIP(ctx, pwork.get(dvr_power_work_doubles(num_pes, n)));
+		GPLE_HIP(ctx, work.get(dvr_spectrum_work_doubles(num_pes, n, static_cast<int>(n_E))));
+		GPLE_HIP(ctx, d.out(density, n_E * C));
+		GPLE_HIP(ctx, pe.out(psi_e, n_E * 2 * dim));
+		GPLE_HIP(ctx, rem.out(remaining, 1));
+		GPLE_HIP(ctx, h.in(H, dim * dim));
+		GPLE_HIP(ctx, w.in(W, n_grids));
+		GPLE_HIP(ctx, b.in(basis, n_grids * num_pes * num_pes));
+		GPLE_HIP(ctx, v.in(psi0, 2 * dim));
+		GPLE_HIP(ctx, en.in(energies, n_E));
+		DvrSpectrum g{};
+		g.num_pes = num_pes, g.n = n, g.levels = levels, g.n_left = static_cast<int>(n_left), g.n_E = static_cast<int>(n_E);
+		g.H = h.p, g.W = w.p, g.dt = dt, g.basis = b.p, g.psi0 = v.p, g.energies = en.p, g.power_work = pwork.p, g.work = work.p;
+		g.density = d.p, g.psi_e = pe.p, g.remaining = rem.p;
+		GPLE_HIP(ctx, launch_dvr_spectrum(ctx, st, g));
+		for (Staged* o : {&d, &pe, &rem}) GPLE_HIP(ctx, o->back());
+		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
+		return GPLE_OK;
+	}
+
 	/* ---- exact MQCLE dynamics (gple_mqcl.hip; liouville_equation/ of the reference) ------------------------------------------------------ */
 	static bool mqcl_size_ok(int num_pes, int model, size_t n) { return dvr_model_ok(num_pes, model) && n >= 4 && n <= 4096; }
 

@@ -325,6 +325,8 @@ namespace gple
 		return hipGetLastError();
 	}
 
+	hipError_t launch_dvr_square(hipStream_t s, const double* X, double* Z, long ld) { return complex_product(s, X, X, Z, ld); }
+
 	size_t dvr_power_work_doubles(int num_pes, int n)
 	{
 		const size_t ld = round_up(static_cast<size_t>(num_pes) * n, 64);

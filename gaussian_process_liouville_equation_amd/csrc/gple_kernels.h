@@ -306,6 +306,26 @@ namespace gple
 	hipError_t launch_dvr_flux_apply(hipStream_t s, int num_pes, int n, const double* G, const double* psi, int T, double* partial, double* absorbed);
 	// psi[k] = U^(k + 1) psi0, k < T; U: two dim x dim planes; scratch: T x dim pairs when basis != null (the diabatic states), unused otherwise
 	hipError_t launch_dvr_apply(hipStream_t s, int num_pes, int n, const double* U, const double* psi0, int T, const double* basis, double* scratch, double* psi);
+	// Z = X X for complex symmetric planes of ld x ld (lower tiles and the mirror): one squaring of the power.  Z may not alias X
+	hipError_t launch_dvr_square(hipStream_t s, const double* X, double* Z, long ld);
+	// ---- the spectrum of one absorbing run (gple_dvr_spectrum.hip): Y(E) = sum_{k < 2^levels} e^{i E dt k / hbar} P4^k psi0 per energy, by the power's squarings
+	struct DvrSpectrum
+	{
+		int num_pes, n, levels, n_left, n_E;
+		const double *H, *W;   // as launch_dvr_power (W nullable)
+		double dt;
+		const double* basis;   // n x num_pes x num_pes
+		const double* psi0;    // dim (re, im) pairs
+		const double* energies; // n_E
+		double* power_work;    // dvr_power_work_doubles: P4 stays in it, its two buffers take the squarings
+		double* work;          // dvr_spectrum_work_doubles: X = Y | Pi_c Y (two planes of ld x (1 + 2 num_pes) nep), P X (the same), T (two planes of ld x nep)
+		double* density;       // n_E x 2 num_pes: Re[(Pi_c Y)^H Y - (P Pi_c Y)^H (P Y)]
+		double* psi_e;         // nullable: n_E x dim (re, im) pairs
+		double* remaining;     // nullable: |P4^(2^levels) psi0|^2
+	};
+	size_t dvr_spectrum_work_doubles(int num_pes, int n, int n_E);
+	// every pointer a device pointer.  GPLE_TIMER_DVR_SPECTRUM of ctx spans P4, the squarings, the thin products, the projection and the reduction
+	hipError_t launch_dvr_spectrum(Ctx* ctx, hipStream_t s, const DvrSpectrum& g);
 	// ---- exact MQCLE dynamics (gple_mqcl.hip): num_pes = 2 or 3, 4 <= n <= 4096, rho: num_pes^2 x n x n (re, im) pairs, x major ------------
 	// tables (mqcl_table_doubles): per x C | E | U | lambda | Q phases of one Q(tq), then (spectral) chirp (n), twiddles (M / 2), chirp spectrum (M)
 	int mqcl_fft_length(int n);

@@ -1,6 +1,6 @@
 """Exact DVR wavepacket dynamics: the reference's schrodinger_equation/main.cpp, restated on the library's device entry points
 (gple_dvr_hamiltonian, gple_dvr_propagate, gple_wigner; for the absorbing boundary gple_dvr_absorber, gple_dvr_propagator, gple_dvr_apply,
-and gple_dvr_flux, gple_dvr_flux_apply for what the absorber took).
+and gple_dvr_flux, gple_dvr_flux_apply for what the absorber took, gple_dvr_spectrum for its resolution in energy).
 
     setup()            main.cpp:41-146 with the defaults of schrodinger_equation/input.py
     initial_adiabatic_psi(), to_diabatic()  general.cpp:70-103 (Gaussian on the lowest adiabatic surface) taken to the diabatic basis (main.cpp:158-161)
@@ -8,6 +8,7 @@ and gple_dvr_flux, gple_dvr_flux_apply for what the absorber took; DESIGN.md §1
                        (general.cpp:443-478), the Wigner transform and its averages (general.cpp:324-411), the stop criteria (main.cpp:256-294)
     writers            x.txt, p.txt, t.txt, psi.txt, phase.txt, averages.txt in the reference's line layout; numbers as %g (output.py);
                        absorbed.txt (flux=True, no file of the reference's): t, the absorbed population per side and surface, what is left
+                       spectrum.txt (spectrum=..., no file of the reference's): E, the absorbed population per unit energy per side and surface
 
 The Hamiltonian is diagonalised once per run with numpy.linalg.eigh on the host (set-up, not the hot path: DESIGN.md §11).  The absorbing
 boundary needs no eigh: the propagator of the output_step RK4 steps between two outputs is formed once on the device as a matrix power and
@@ -194,8 +195,27 @@ def averages_line(t, E, X, P, pops, phase_avg):
     return " ".join(fmt(v) for v in [t, E, X, P, *pops, *phase_avg]) + "\n"
 
 
+def spectrum_levels(end_time, dt):
+    """The smallest J with 2^J dt >= end_time: the 2^J steps of the spectrum's transform cover the run."""
+    J = 0
+    while 2 ** J * dt < end_time:
+        J += 1
+    return J
+
+
+def spectrum_energies(s, adiabatic_energies, n_E):
+    """The default energies of run(spectrum=n_E): n_E momenta uniform in p0 +- 3 sigma_p (p0 itself for n_E = 1) as total energies in H's own
+    zero, E = p^2 / 2m + the lowest adiabatic energy at the grid point nearest x0.  adiabatic_energies: (n, num_pes) of gple_dvr_hamiltonian."""
+    n_E = int(n_E)
+    if n_E < 1:
+        raise ValueError("spectrum needs at least one energy")
+    p = np.linspace(s["p0"] - 3.0 * s["sigma_p"], s["p0"] + 3.0 * s["sigma_p"], n_E) if n_E > 1 else np.array([s["p0"]])
+    lowest = float(np.min(np.asarray(adiabatic_energies)[int(np.argmin(np.abs(s["x"] - s["x0"])))]))
+    return p ** 2 / 2.0 / s["mass"] + lowest
+
+
 def run(api, model=DAC, num_pes=2, boundary=PERIODIC, ln_energy=0.0, out_dir=None, write_phase="text", max_outputs=None, chunk_bytes=1 << 30,
-        p_grid=None, log=None, flux=False, until_absorbed=False, **setup_kw):
+        p_grid=None, log=None, flux=False, until_absorbed=False, spectrum=None, **setup_kw):
     """The loop of main.cpp:210-298.  boundary=ABSORBING: no eigh; the propagator of output_step RK4 steps is formed once (gple_dvr_propagator, kept
     on the device) and applied once per output (gple_dvr_apply); the Wigner transform is the reflective one (general.cpp:363-364), <E> uses the
     real H, and the stop criteria carry the PplLim clause.  write_phase: "text" (phase.txt), "npy" (phase_<k>.npy per output time) or None;
@@ -206,10 +226,17 @@ def run(api, model=DAC, num_pes=2, boundary=PERIODIC, ln_energy=0.0, out_dir=Non
     transmission for a packet that starts on the left.  The figures and the populations left add up to the initial population to rounding;
     a figure may be slightly negative.  absorbed.txt has a line per output: t, the 2 num_pes figures, the population left; the
     result gains `absorbed`, `scattering_line` (the final line's head, the figures, the remainder) and `flux_seconds`.
-    until_absorbed (absorbing boundary only): the PplLim clause is the only stop, tested at every output whatever <x> is."""
+    until_absorbed (absorbing boundary only): the PplLim clause is the only stop, tested at every output whatever <x> is.
+    spectrum (absorbing boundary only): a number n_E of energies (spectrum_energies) or an array of total energies in H's own zero.  After the
+    loop one gple_dvr_spectrum call resolves what the absorber took in energy, over 2^J steps from psi0 with J = spectrum_levels(the run's end
+    time, dt): rho_c(E) = dx dt / (2 pi hbar) psi_e^H D_c psi_e, a population per unit energy per side and surface, not clamped.
+    spectrum.txt has a line per energy: E, the 2 num_pes figures; the result gains `spectrum` (n_E, 1 + 2 num_pes: those lines),
+    `spectrum_levels`, `spectrum_remaining` (the population after the 2^J steps) and `spectrum_seconds`."""
     absorbing = boundary == ABSORBING
     if (flux or until_absorbed) and not absorbing:
         raise ValueError("flux and until_absorbed belong to boundary=ABSORBING")
+    if spectrum is not None and (not absorbing or isinstance(spectrum, bool)):
+        raise ValueError("spectrum (a number of energies or an array of them) belongs to boundary=ABSORBING")
     if absorbing:
         setup_kw["boundary"], boundary = ABSORBING, REFLECTIVE  # H and the Wigner transform of the reflective boundary (the reference's switches fall through)
     s = setup(ln_energy, **setup_kw)
@@ -223,8 +250,8 @@ def run(api, model=DAC, num_pes=2, boundary=PERIODIC, ln_energy=0.0, out_dir=Non
         if s["output_step"] < 1:
             raise ValueError("the output time is shorter than one time step")
         W = api.dvr_absorber(x[0], dx, n, mass, s["xmin"], s["xmax"], s["absorbing_length"])
+        n_left = int(np.sum(x < (s["xmin"] + s["xmax"]) / 2.0))
         if flux:
-            n_left = int(np.sum(x < (s["xmin"] + s["xmax"]) / 2.0))
             U, G = api.dvr_flux(num_pes, n, H, W, s["dt"], s["output_step"], basis, n_left, device_out=True)
         else:
             U = api.dvr_propagator(num_pes, n, H, W, s["dt"], s["output_step"], device_out=True)
@@ -321,5 +348,21 @@ def run(api, model=DAC, num_pes=2, boundary=PERIODIC, ln_energy=0.0, out_dir=Non
     if flux:
         taken = records[-1]["absorbed"] if records else np.zeros((2, num_pes))
         extra = dict(absorbed=taken, scattering_line=" ".join(fmt(v) for v in [head, *taken.ravel(), float(np.sum(pops))]), flux_seconds=t_power)
+    if spectrum is not None:
+        t_s = time.perf_counter()
+        E = spectrum_energies(s, energies, spectrum) if isinstance(spectrum, (int, np.integer)) else np.atleast_1d(np.asarray(spectrum, dtype=np.float64))
+        levels = spectrum_levels(records[-1]["t"] if records else 0.0, s["dt"])
+        if levels > 30:
+            raise ValueError("the run is longer than 2^30 time steps")
+        density, _, left = api.dvr_spectrum(num_pes, n, H, W, s["dt"], levels, basis, n_left, psi0, E)
+        rows = np.concatenate([E[:, None], np.asarray(density).reshape(len(E), 2 * num_pes) * (dx * s["dt"] / (2.0 * math.pi * HBAR))], axis=1)
+        if out_dir is not None:
+            with open(os.path.join(out_dir, "spectrum.txt"), "wb") as f:
+                if hasattr(api, "format_g"):
+                    f.write(api.format_g(rows, rows.shape[1], join=True))
+                else:
+                    f.write("".join(" ".join(fmt(v) for v in row) + "\n" for row in rows).encode())
+        extra.update(spectrum=rows, spectrum_levels=levels, spectrum_remaining=left * dx, spectrum_seconds=time.perf_counter() - t_s)
+        say(f"spectrum of {len(E)} energies over 2^{levels} steps: {extra['spectrum_seconds']:.2f} s")
     return dict(**extra, setup=s, records=records, stop=stop, final_line=final_line, eigh_seconds=t_eigh, propagator_seconds=t_power, total_seconds=t_end - t0,
                 seconds_per_output=(t_end - t_loop) / max(1, len(records)), stop_time=records[-1]["t"] if records else None)

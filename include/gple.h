@@ -155,7 +155,8 @@ typedef enum gple_timer {
 	GPLE_TIMER_FORMAT = 7,         /* the three kernels of one gple_format_g call (no staging, no copy of the text); count = calls */
 	GPLE_TIMER_PARSE = 8,          /* the kernels of one gple_parse_g call (three, or two when it only counts; no staging, no copies); count = calls */
 	GPLE_TIMER_DVR_POWER = 9,      /* the products of one gple_dvr_propagator call (Horner form of P4 and the binary power; no set-up, no copies); count = calls */
-	GPLE_TIMER_DVR_FLUX = 10       /* the products of one gple_dvr_flux call (P4, the power, the loss matrix and every sandwich; no set-up, no copies); count = calls */
+	GPLE_TIMER_DVR_FLUX = 10,      /* the products of one gple_dvr_flux call (P4, the power, the loss matrix and every sandwich; no set-up, no copies); count = calls */
+	GPLE_TIMER_DVR_SPECTRUM = 11   /* the device work of one gple_dvr_spectrum call (P4, the squarings, the thin products, the projection and the reduction; no copies); count = calls */
 } gple_timer;
 int gple_ctx_enable_timing(gple_ctx* ctx, int on);
 /* Synchronises the stream, then: last = milliseconds of the most recent interval; total / count = accumulated since
@@ -453,6 +454,23 @@ int gple_dvr_flux(gple_ctx* ctx, int num_pes, size_t n_grids, const double* H, c
  * in a fixed order by a second kernel; no atomics: a state's figures are the same bits whatever T is and wherever it stands in the call.  A
  * sweep over G serves four states; the sweeps of a call run back to back, 64 states per pair of launches. */
 int gple_dvr_flux_apply(gple_ctx* ctx, int num_pes, size_t n_grids, const double* G, const double* psi, size_t T, unsigned flags, double* absorbed);
+
+/* The energy-resolved spectrum of one absorbing run ("The spectrum of one packet"): for every total energy E, with
+ * theta = E dt / hbar and K = 2^levels, the discrete half-Fourier transform of the first K steps
+ *   psi_e(E) = sum_{k < K} e^{i theta k} P^k psi0 = prod_{j < levels} [I + e^{i theta 2^j} P^(2^j)] psi0          P = P4(A) as gple_dvr_propagator forms it
+ * one column per energy, by the power's own squarings: R = P, then per level Y += R (Y o e^{i theta 2^j}) and R = R R (the lower-tile products and
+ * the mirror of the power; the thin products are four real ones on the fp64 MFMA GEMM).  theta 2^j is exact and the phase is the sine and cosine
+ * of that product.  Nothing steps.  What channel c = side num_pes + k (the Pi_c of gple_dvr_flux) absorbed per unit of energy is
+ *   density[e 2 num_pes + c] = psi_e^H D_c psi_e = Re[(Pi_c psi_e)^H psi_e - (P Pi_c psi_e)^H (P psi_e)]
+ * unscaled: times dx dt / (2 pi hbar) it is a population per unit energy.  No D_c is formed; a figure may be slightly negative, as those of
+ * gple_dvr_flux, and is not clamped.  Over the K energies theta_m = 2 pi m / K the mean of density[m][c] is the figure of gple_dvr_flux with
+ * n_steps = K on psi0.  Fixed reduction orders, no atomics: two calls with the same arguments return the same bits.
+ * H, W (nullable), dt, dim as gple_dvr_propagator; 0 <= levels <= 30; basis (required) and n_left <= n_grids as gple_dvr_flux; psi0: dim
+ * (re, im) pairs; energies: n_E finite values, 1 <= n_E <= 4096, in H's own zero of energy.  psi_e (nullable): n_E x dim (re, im) pairs;
+ * remaining (nullable): |P^K psi0|^2, one value.  Timer: GPLE_TIMER_DVR_SPECTRUM.  Work space: the 7 planes of the power and
+ * (8 num_pes + 6) dim n_E' doubles, n_E' = n_E rounded up to 64. */
+int gple_dvr_spectrum(gple_ctx* ctx, int num_pes, size_t n_grids, const double* H, const double* W, double dt, int levels, const double* basis,
+	size_t n_left, const double* psi0, const double* energies, size_t n_E, unsigned flags, double* density, double* psi_e, double* remaining);
 
 /* ---- exact MQCLE dynamics (liouville_equation/ of the reference) ------------------------------------------------------- */
 /* The mixed quantum-classical Liouville equation on the square (x, p) grid of n points per axis, evolved in the diabatic basis
