@@ -220,6 +220,20 @@ def _io(*arrays):
     return [None if a is None else a.ctypes.data_as(_dp) for a in arrays], 0
 
 
+def _dvr_shapes(num_pes, n_grids, H=None, W=None, basis=None, psi0=None):
+    """ValueError unless every array given has the shape of its place in a DVR system of dim = num_pes * n_grids"""
+    dim = num_pes * n_grids
+    for a, shape in ((H, (dim, dim)), (W, (n_grids,)), (basis, (n_grids, num_pes, num_pes)), (psi0, (dim,))):
+        if a is not None and a.shape != shape:
+            raise ValueError("H (dim, dim), W (n_grids,), basis (n_grids, num_pes, num_pes) and psi0 (dim,) with dim = num_pes * n_grids")
+
+
+def _device_planes(t, shape, source):
+    """ValueError unless the tensor t is what `source`(device_out=True) returns: contiguous float64 planes of this shape on the GPU"""
+    if tuple(t.shape) != shape or not t.is_cuda or str(t.dtype) != "torch.float64" or not t.is_contiguous():
+        raise ValueError(f"a tensor must be the contiguous float64 {shape} planes of {source}(device_out=True) on the GPU")
+
+
 def _axis(v):
     """grid values: a device tensor as it is, anything else as a float64 array"""
     return v if _on_device(v) else _f64(v)
@@ -671,11 +685,11 @@ class Api:
         """gple_dvr_propagator: U = P4(-(W + i H) dt / hbar)^n_steps, what n_steps classical RK4 steps apply, as a complex128 (dim, dim) array;
         W (n_grids,) or None.  device_out: U stays on the device, a float64 tensor (2, dim, dim) = (Re, Im) on the context's device (the call has
         completed when it returns) that dvr_apply accepts as it is"""
-        dim = int(num_pes) * int(n_grids)
+        num_pes, n_grids = int(num_pes), int(n_grids)
+        dim = num_pes * n_grids
         H = _f64(H)
         W = None if W is None else _f64(W)
-        if H.shape != (dim, dim) or (W is not None and W.shape != (n_grids,)):
-            raise ValueError("H (dim, dim) and W (n_grids,) with dim = num_pes * n_grids")
+        _dvr_shapes(num_pes, n_grids, H, W)
         if device_out:
             import torch
             where = torch.device("cuda", self.device)
@@ -684,25 +698,24 @@ class Api:
             U = torch.empty((2, dim, dim), dtype=torch.float64, device=where)
             torch.cuda.synchronize(where)  # the uploads, before the context's stream reads them
             (pH, pW, pU), flags = _io(tH, tW, U)
-            self._check(self.lib.gple_dvr_propagator(self.ctx, int(num_pes), int(n_grids), pH, pW, float(dt), int(n_steps), flags, pU))
+            self._check(self.lib.gple_dvr_propagator(self.ctx, num_pes, n_grids, pH, pW, float(dt), int(n_steps), flags, pU))
             self.synchronize()
             return U
         planes = np.empty((2, dim, dim))
-        self._check(self.lib.gple_dvr_propagator(self.ctx, int(num_pes), int(n_grids), _ptr(H), _ptr(W), float(dt), int(n_steps), 0, _ptr(planes)))
+        self._check(self.lib.gple_dvr_propagator(self.ctx, num_pes, n_grids, _ptr(H), _ptr(W), float(dt), int(n_steps), 0, _ptr(planes)))
         return planes[0] + 1j * planes[1]
 
     def dvr_apply(self, num_pes, n_grids, U, psi0, T, basis=None):
         """gple_dvr_apply: psi[k] = U^(k + 1) psi0 for k < T -> (T, dim) complex, adiabatic with basis (n, num_pes, num_pes).  U: a complex
         (dim, dim) array, or the device tensor of dvr_propagator(device_out=True) (psi0 and basis go up, psi comes back)"""
-        dim, T = int(num_pes) * int(n_grids), int(T)
+        num_pes, n_grids, T = int(num_pes), int(n_grids), int(T)
+        dim = num_pes * n_grids
         psi0 = _cplx(psi0)
         if _on_device(U):  # the tensor form is what dvr_propagator(device_out=True) returns, nothing else
-            if tuple(U.shape) != (2, dim, dim) or not U.is_cuda or str(U.dtype) != "torch.float64" or not U.is_contiguous():
-                raise ValueError("a tensor U must be the contiguous float64 (2, dim, dim) planes of dvr_propagator(device_out=True) on the GPU")
+            _device_planes(U, (2, dim, dim), "dvr_propagator")
         elif tuple(np.shape(U)) not in ((dim, dim), (2, dim, dim)):
             raise ValueError("U (dim, dim) complex or (2, dim, dim) planes with dim = num_pes * n_grids")
-        if psi0.shape != (dim,):
-            raise ValueError("psi0 (dim,) with dim = num_pes * n_grids")
+        _dvr_shapes(num_pes, n_grids, psi0=psi0)
         basis = None if basis is None else _f64(basis)
         out = np.empty((T, dim), dtype=np.complex128)
         if T == 0:
@@ -714,12 +727,12 @@ class Api:
             tout = torch.empty((T, 2 * dim), dtype=torch.float64, device=U.device)
             torch.cuda.synchronize(U.device)
             (pU, pv, pb, po), flags = _io(U, tv, tb, tout)
-            self._check(self.lib.gple_dvr_apply(self.ctx, int(num_pes), int(n_grids), pU, pv, T, pb, flags, po))
+            self._check(self.lib.gple_dvr_apply(self.ctx, num_pes, n_grids, pU, pv, T, pb, flags, po))
             self.synchronize()
             return tout.cpu().numpy().view(np.complex128)
         planes = _f64(U) if np.ndim(U) == 3 else np.stack([np.real(U), np.imag(U)]).astype(np.float64)
         planes = np.ascontiguousarray(planes)
-        self._check(self.lib.gple_dvr_apply(self.ctx, int(num_pes), int(n_grids), _ptr(planes), _ptr(psi0.view(np.float64)), T, _ptr(basis), 0,
+        self._check(self.lib.gple_dvr_apply(self.ctx, num_pes, n_grids, _ptr(planes), _ptr(psi0.view(np.float64)), T, _ptr(basis), 0,
                                             _ptr(out.view(np.float64))))
         return out
 
@@ -734,8 +747,7 @@ class Api:
         dim = num_pes * n_grids
         H, basis = _f64(H), _f64(basis)
         W = None if W is None else _f64(W)
-        if H.shape != (dim, dim) or (W is not None and W.shape != (n_grids,)) or basis.shape != (n_grids, num_pes, num_pes):
-            raise ValueError("H (dim, dim), W (n_grids,) and basis (n_grids, num_pes, num_pes) with dim = num_pes * n_grids")
+        _dvr_shapes(num_pes, n_grids, H, W, basis)
         if device_out:
             import torch
             where = torch.device("cuda", self.device)
@@ -764,8 +776,7 @@ class Api:
             raise ValueError("psi (T, dim) with dim = num_pes * n_grids and 1 <= T <= 4096")
         out = np.empty((T, 2, num_pes))
         if _on_device(G):
-            if tuple(G.shape) != (2 * num_pes, 2, dim, dim) or not G.is_cuda or str(G.dtype) != "torch.float64" or not G.is_contiguous():
-                raise ValueError("a tensor G must be the contiguous float64 (2 num_pes, 2, dim, dim) planes of dvr_flux(device_out=True) on the GPU")
+            _device_planes(G, (2 * num_pes, 2, dim, dim), "dvr_flux")
             import torch
             tv = torch.from_numpy(psi.view(np.float64)).to(G.device)
             tout = torch.empty((T, 2 * num_pes), dtype=torch.float64, device=G.device)
@@ -790,8 +801,7 @@ class Api:
         dim = num_pes * n_grids
         H, basis, psi0, energies = _f64(H), _f64(basis), _cplx(psi0), np.atleast_1d(_f64(energies))
         W = None if W is None else _f64(W)
-        if H.shape != (dim, dim) or (W is not None and W.shape != (n_grids,)) or basis.shape != (n_grids, num_pes, num_pes) or psi0.shape != (dim,):
-            raise ValueError("H (dim, dim), W (n_grids,), basis (n_grids, num_pes, num_pes) and psi0 (dim,) with dim = num_pes * n_grids")
+        _dvr_shapes(num_pes, n_grids, H, W, basis, psi0)
         n_E = energies.size
         if energies.ndim != 1 or not 1 <= n_E <= 4096:
             raise ValueError("energies (n_E,) with 1 <= n_E <= 4096")

@@ -108,6 +108,12 @@ extern "C"
 	}
 
 	/* ---- the absorbing boundary (gple_dvr_power.hip): the absorber, the propagator of n_steps RK4 steps as a matrix power, its application ---- */
+	// what gple_dvr_propagator, gple_dvr_flux and gple_dvr_spectrum (n_steps = 2^levels) ask of a system and a step count before the power is formed
+	static bool dvr_power_args_ok(int num_pes, size_t n_grids, double dt, size_t n_steps)
+	{
+		return (num_pes == 2 || num_pes == 3) && dvr_grid_ok(n_grids, 1.0) && std::isfinite(dt) && n_steps >= 1 && n_steps <= (1ul << 30) &&
+			round_up(static_cast<size_t>(num_pes) * n_grids, 64) <= static_cast<size_t>(DVR_POWER_MAX_LD);
+	}
 	int gple_dvr_absorber(gple_ctx* ctx, double x_first, double dx, size_t n_grids, double mass, double xmin, double xmax, double length, unsigned flags,
 		double* W)
 	{
@@ -129,31 +135,44 @@ extern "C"
 		return GPLE_OK;
 	}
 
-	int gple_dvr_propagator(gple_ctx* ctx, int num_pes, size_t n_grids, const double* H, const double* W, double dt, size_t n_steps, unsigned flags, double* U)
+	// the propagator of gple_dvr_propagator and, with G, the quadratic forms of gple_dvr_flux beside it (basis, n_left: theirs); U nullable with G
+	static int dvr_power_call(gple_ctx* ctx, int num_pes, size_t n_grids, const double* H, const double* W, double dt, size_t n_steps, const double* basis,
+		size_t n_left, unsigned flags, double* U, double* G)
 	{
-		if (!ctx || (num_pes != 2 && num_pes != 3) || !dvr_grid_ok(n_grids, 1.0) || !H || !U || !std::isfinite(dt) || n_steps < 1 || n_steps > (1ul << 30) ||
-			round_up(static_cast<size_t>(num_pes) * n_grids, 64) > static_cast<size_t>(DVR_POWER_MAX_LD))
-			return GPLE_ERR_BAD_ARG;
 		GPLE_OPEN(ctx);
 		const bool dev = flags & GPLE_IO_DEVICE;
 		const int n = static_cast<int>(n_grids);
 		const size_t dim = static_cast<size_t>(num_pes) * n_grids, ld = round_up(dim, 64);
 		GPLE_CALL(ctx);
 		hipStream_t st = ctx->stream;
-		Scratch work(ctx);
-		Staged h(ctx, dev), w(ctx, dev), u(ctx, dev);
+		Scratch work(ctx), fwork(ctx);
+		Staged h(ctx, dev), w(ctx, dev), b(ctx, dev), u(ctx, dev), g(ctx, dev);
+		// every allocation before the first launch: one that does not fit leaves the outputs untouched
 		GPLE_HIP(ctx, work.get(dvr_power_work_doubles(num_pes, n)));
+		if (G) GPLE_HIP(ctx, fwork.get(dvr_flux_work_doubles(num_pes, n)));
+		GPLE_HIP(ctx, u.out(U, 2 * dim * dim));
+		GPLE_HIP(ctx, g.out(G, 4 * num_pes * dim * dim));
 		GPLE_HIP(ctx, h.in(H, dim * dim));
 		GPLE_HIP(ctx, w.in(W, n_grids));
-		GPLE_HIP(ctx, u.out(U, 2 * dim * dim));
-		const double* R = nullptr;
-		GPLE_HIP(ctx, launch_dvr_power(ctx, st, num_pes, n, h.p, w.p, dt, static_cast<long>(n_steps), work.p, &R));
-		for (size_t plane = 0; plane < 2; ++plane) // the padded planes, without their padding
-			GPLE_HIP(ctx, hipMemcpy2DAsync(u.p + plane * dim * dim, dim * sizeof(double), R + plane * ld * ld, ld * sizeof(double), dim * sizeof(double), dim,
+		GPLE_HIP(ctx, b.in(basis, n_grids * num_pes * num_pes));
+		const DvrFlux flux{b.p, static_cast<int>(n_left), fwork.p};
+		DvrPlanes R;
+		GPLE_HIP(ctx, launch_dvr_power(ctx, st, num_pes, n, h.p, w.p, dt, static_cast<long>(n_steps), work.p, &R, G ? &flux : nullptr));
+		const double* const padded[2] = {R.re, R.im}; // the padded planes, without their padding
+		for (size_t plane = 0; u.p && plane < 2; ++plane)
+			GPLE_HIP(ctx, hipMemcpy2DAsync(u.p + plane * dim * dim, dim * sizeof(double), padded[plane], ld * sizeof(double), dim * sizeof(double), dim,
 				hipMemcpyDeviceToDevice, st));
+		if (G) GPLE_HIP(ctx, launch_dvr_flux_export(st, num_pes, n, flux, g.p));
 		GPLE_HIP(ctx, u.back());
+		GPLE_HIP(ctx, g.back());
 		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
 		return GPLE_OK;
+	}
+
+	int gple_dvr_propagator(gple_ctx* ctx, int num_pes, size_t n_grids, const double* H, const double* W, double dt, size_t n_steps, unsigned flags, double* U)
+	{
+		if (!ctx || !dvr_power_args_ok(num_pes, n_grids, dt, n_steps) || !H || !U) return GPLE_ERR_BAD_ARG;
+		return dvr_power_call(ctx, num_pes, n_grids, H, W, dt, n_steps, nullptr, 0, flags, U, nullptr);
 	}
 
 	int gple_dvr_apply(gple_ctx* ctx, int num_pes, size_t n_grids, const double* U, const double* psi0, size_t T, const double* basis, unsigned flags,
@@ -180,40 +199,12 @@ extern "C"
 		return GPLE_OK;
 	}
 
-	/* ---- what the absorber took (gple_dvr_power.hip): the quadratic forms of the absorbed population per channel, and their application ------ */
+	/* ---- what the absorber took (gple_dvr_flux.hip): the quadratic forms of the absorbed population per channel, and their application ------ */
 	int gple_dvr_flux(gple_ctx* ctx, int num_pes, size_t n_grids, const double* H, const double* W, double dt, size_t n_steps, const double* basis,
 		size_t n_left, unsigned flags, double* U, double* G)
 	{
-		if (!ctx || (num_pes != 2 && num_pes != 3) || !dvr_grid_ok(n_grids, 1.0) || !H || !G || !basis || n_left > n_grids || !std::isfinite(dt) ||
-			n_steps < 1 || n_steps > (1ul << 30) || round_up(static_cast<size_t>(num_pes) * n_grids, 64) > static_cast<size_t>(DVR_POWER_MAX_LD))
-			return GPLE_ERR_BAD_ARG;
-		GPLE_OPEN(ctx);
-		const bool dev = flags & GPLE_IO_DEVICE;
-		const int n = static_cast<int>(n_grids);
-		const size_t dim = static_cast<size_t>(num_pes) * n_grids, ld = round_up(dim, 64);
-		GPLE_CALL(ctx);
-		hipStream_t st = ctx->stream;
-		Scratch work(ctx), fwork(ctx);
-		Staged h(ctx, dev), w(ctx, dev), b(ctx, dev), u(ctx, dev), g(ctx, dev);
-		// every allocation before the first launch: one that does not fit leaves the outputs untouched
-		GPLE_HIP(ctx, work.get(dvr_power_work_doubles(num_pes, n)));
-		GPLE_HIP(ctx, fwork.get(dvr_flux_work_doubles(num_pes, n)));
-		GPLE_HIP(ctx, u.out(U, 2 * dim * dim));
-		GPLE_HIP(ctx, g.out(G, 4 * num_pes * dim * dim));
-		GPLE_HIP(ctx, h.in(H, dim * dim));
-		GPLE_HIP(ctx, w.in(W, n_grids));
-		GPLE_HIP(ctx, b.in(basis, n_grids * num_pes * num_pes));
-		const DvrFlux flux{b.p, static_cast<int>(n_left), fwork.p};
-		const double* R = nullptr;
-		GPLE_HIP(ctx, launch_dvr_power(ctx, st, num_pes, n, h.p, w.p, dt, static_cast<long>(n_steps), work.p, &R, &flux));
-		for (size_t plane = 0; u.p && plane < 2; ++plane)
-			GPLE_HIP(ctx, hipMemcpy2DAsync(u.p + plane * dim * dim, dim * sizeof(double), R + plane * ld * ld, ld * sizeof(double), dim * sizeof(double), dim,
-				hipMemcpyDeviceToDevice, st));
-		GPLE_HIP(ctx, launch_dvr_flux_export(st, num_pes, n, flux, g.p));
-		GPLE_HIP(ctx, u.back());
-		GPLE_HIP(ctx, g.back());
-		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
-		return GPLE_OK;
+		if (!ctx || !dvr_power_args_ok(num_pes, n_grids, dt, n_steps) || !H || !G || !basis || n_left > n_grids) return GPLE_ERR_BAD_ARG;
+		return dvr_power_call(ctx, num_pes, n_grids, H, W, dt, n_steps, basis, n_left, flags, U, G);
 	}
 
 	int gple_dvr_flux_apply(gple_ctx* ctx, int num_pes, size_t n_grids, const double* G, const double* psi, size_t T, unsigned flags, double* absorbed)
@@ -241,9 +232,8 @@ extern "C"
 	int gple_dvr_spectrum(gple_ctx* ctx, int num_pes, size_t n_grids, const double* H, const double* W, double dt, int levels, const double* basis,
 		size_t n_left, const double* psi0, const double* energies, size_t n_E, unsigned flags, double* density, double* psi_e, double* remaining)
 	{
-		if (!ctx || (num_pes != 2 && num_pes != 3) || !dvr_grid_ok(n_grids, 1.0) || !H || !basis || !psi0 || !energies || !density || n_left > n_grids ||
-			!std::isfinite(dt) || levels < 0 || levels > 30 || n_E < 1 || n_E > 4096 ||
-			round_up(static_cast<size_t>(num_pes) * n_grids, 64) > static_cast<size_t>(DVR_POWER_MAX_LD))
+		if (!ctx || levels < 0 || levels > 30 || !dvr_power_args_ok(num_pes, n_grids, dt, size_t(1) << levels) || !H || !basis || !psi0 || !energies ||
+			!density || n_left > n_grids || n_E < 1 || n_E > 4096)
 			return GPLE_ERR_BAD_ARG;
 		GPLE_OPEN(ctx);
 		const bool dev = flags & GPLE_IO_DEVICE;

@@ -1,5 +1,6 @@
 // gple_dvr.hip — exact DVR wavepacket dynamics of the model the GP method is judged against (schrodinger_equation/ of the reference,
 // the reflective and periodic boundaries of general.h:86-97; the absorbing one is gple_dvr_power.hip: DESIGN.md §11).
+// The constants, the grid and the fixed reductions that the DVR files share are in gple_dvr_device.h.
 //
 //   dvr_hamiltonian_kernel  Hamiltonian_construction (general.cpp:106-200) without the absorbing term: dense real symmetric dim x dim,
 //                           dim = NP n, index m n + a; the diabatic potential on the diagonal a = a' blocks, the kinetic energy
@@ -16,6 +17,7 @@
 //   wigner_avg_*            the averages of general.cpp:393-410 in a fixed reduction order.
 #include <cstdio>
 
+#include "gple_dvr_device.h"
 #include "gple_kernels.h"
 #include "gple_pes_n.h"
 
@@ -24,17 +26,8 @@ namespace gple
 	namespace
 	{
 		typedef double d4 __attribute__((ext_vector_type(4)));
-		typedef double d2 __attribute__((ext_vector_type(2)));
-		constexpr double PI_D = 3.141592653589793116; // acos(-1.0) (general.h:34)
-		constexpr double HBAR_D = 1.0;                 // general.h:35
+		using namespace dvr;
 
-		// x grid of the reference (main.cpp:108 without absorbing region): x_first + dx * a, rounded twice (never contracted to an fma, so that a
-		// host computing x_first + dx * a gets the same bits)
-		__device__ __forceinline__ double grid_x(double x_first, double dx, long a)
-		{
-#pragma clang fp contract(off)
-			return x_first + dx * static_cast<double>(a);
-		}
 		__device__ __forceinline__ double pow_minus_one(long n) { return n % 2 == 0 ? 1.0 : -1.0; } // general.cpp:38-41
 
 		// one thread per entry (r, c) of the row-major dim x dim matrix (symmetric, so column-major reads the same)

@@ -4,41 +4,25 @@
 //   dvr_absorber_kernel     absorbing_potential (pes.cpp:64-93) on the grid, x <= xmin on the left-hand branch (W >= 0 everywhere).
 //   dvr_generator_kernel    A = -(W + i H) dt / hbar: Re A is diagonal (a vector), Im A = G an ld x ld plane, ld = dim rounded up to 64, zero padded.
 //   dvr_horner_*            P4(A) = I + A (I + A/2 (I + A/3 (I + A/4))): a product with A/k is a row scaling by Re A / k (with the identity added,
-//                           dvr_horner_scale_kernel) plus two real GEMMs with G (alpha = -+ 1/k, beta = 1).
-//   complex_product         Z = X Y on (Re, Im) planes as four real products through launch_gemm (alpha = +-1, accumulated into Z); every matrix here
-//                           is a polynomial in the complex symmetric A, so only the lower tiles are computed and dvr_mirror_kernel copies the lower
-//                           triangle over the upper one: every intermediate, and U, is exactly symmetric.
-//   launch_dvr_power        R = P4; for every lower bit of s from the top: R = R R, and R = R P4 if the bit is set.
+//                           dvr_horner_scale_kernel) plus two real GEMMs with G (alpha = -+ 1/k, beta = 1).  launch_dvr_p4 is the generator and these.
+//   dvr_complex_product     Z = beta Z + X Y or conj(X) Y on (Re, Im) planes as four real products through launch_gemm (alpha = +-1, accumulated into
+//                           Z), on the lower tiles or on all: the one complex product of the power, the flux (gple_dvr_flux.hip) and the spectrum
+//                           (gple_dvr_spectrum.hip).  Every matrix of the power is a polynomial in the complex symmetric A, so launch_dvr_square and the
+//                           walk compute only the lower tiles and dvr_mirror_kernel copies the lower triangle over the upper one: every
+//                           intermediate, and U, is exactly symmetric.
+//   launch_dvr_power        R = P4; for every lower bit of s from the top: R = R R, and R = R P4 if the bit is set (walk); the flux recurrence of
+//                           gple_dvr_flux.hip rides along at three places of the walk.
 //   dvr_apply_kernel        psi <- U psi: a wave per row, both planes read once, lane-strided partial sums and a fixed butterfly: the same bits on
 //                           every repeat.  One launch per application; no flags, no atomics.
-// What the absorber took (gple_dvr_flux): per channel c = (side of the box, adiabatic surface) the Hermitian G_c with
-// psi^H G_c psi = the population channel c absorbs over s steps, by the power's own recurrence.
-//   dvr_loss_kernel         L = I - conj(P) P from the Hermitian product conj(P) P (the loss of one step).
-//   dvr_channel_kernel      D_c = (Pi_c L + L Pi_c) / 2: Pi_c is num_pes x num_pes per grid point, a mix of num_pes rows and num_pes columns.
-//   sandwich                G_c += conj(R) (X R): T = X R on full tiles (four real products), conj(R) T on the lower tiles (four more),
-//                           then the Hermitian form of dvr_mirror_kernel (upper Re copied, upper Im negated, Im diagonal exactly 0).
-//   dvr_flux_export_kernel  the padded column-major G_c as the caller's row-major planes (G(r, q) = conj G(q, r): contiguous both sides).
-//   dvr_flux_rows_kernel    psi_r^* (G_c psi)_r for four states at a time, a wave per row, the reduction of dvr_apply_kernel;
-//   dvr_flux_sum_kernel     the rows summed per (state, channel) in a fixed order.  No atomics, no flags.
-#include <algorithm>
-
+#include "gple_dvr_device.h"
 #include "gple_kernels.h"
 
 namespace gple
 {
 	namespace
 	{
-		typedef double d2 __attribute__((ext_vector_type(2)));
-		constexpr double PI_D = 3.141592653589793116; // acos(-1.0) (general.h:34)
-		constexpr double HBAR_D = 1.0;                 // general.h:35
+		using namespace dvr;
 		constexpr double ABS_C = 0x1.4f9f94f9f50b1p+1; // sqrt(2) * comp_ellint_1(1 / sqrt(2)) as pes.cpp:61 evaluates it (2.62205755429212)
-
-		// the grid of gple_dvr.hip: x_first + dx * a, rounded twice
-		__device__ __forceinline__ double grid_x(double x_first, double dx, long a)
-		{
-#pragma clang fp contract(off)
-			return x_first + dx * static_cast<double>(a);
-		}
 
 		__global__ void __launch_bounds__(256) dvr_absorber_kernel(double x_first, double dx, int n, double mass, double xmin, double xmax, double length,
 			double* __restrict__ W)
@@ -115,33 +99,15 @@ namespace gple
 			}
 		}
 
-		// C (+)= alpha X Y on column-major ld x ld planes, the lower tiles only
-		hipError_t real_product(hipStream_t s, const double* X, const double* Y, double* C, long ld, double alpha, double beta, bool lower = true)
+		// C = beta C + alpha X Y on column-major planes: X ld x ld, Y and C ld x cols (leading dimension ld); lower: the lower tiles only
+		hipError_t real_product(hipStream_t s, const double* X, const double* Y, double* C, long ld, long cols, double alpha, double beta, bool lower)
 		{
 			GemmDesc g{};
 			g.A = X, g.lda = ld, g.a_kmajor = false; // A(m, k) = X(m, k) at m + k ld
 			g.B = Y, g.ldb = ld, g.b_kmajor = true;  // B(n, k) = Y(k, n) at k + n ld
 			g.C = C, g.ldc = ld, g.c_trans = false;
-			g.M = g.N = g.K = static_cast<int>(ld), g.batch = 1, g.alpha = alpha, g.beta = beta, g.krange = K_FULL, g.lower_only = lower;
-			return launch_gemm(s, g, gemm_pick_tile(ld, ld, 1, lower));
-		}
-		hipError_t mirror(hipStream_t s, double* Zr, double* Zi, long ld, bool hermitian = false)
-		{
-			const dim3 grid(static_cast<unsigned>(ld / 32), static_cast<unsigned>(ld / 32), 2);
-			if (hermitian) hipLaunchKernelGGL(dvr_mirror_kernel<true>, grid, dim3(256), 0, s, Zr, Zi, ld);
-			else hipLaunchKernelGGL(dvr_mirror_kernel<false>, grid, dim3(256), 0, s, Zr, Zi, ld);
-			return hipGetLastError();
-		}
-		// Z = X Y: Re Z = Xr Yr - Xi Yi, Im Z = Xr Yi + Xi Yr (four products: the three-multiplication form costs accuracy); Z may alias neither
-		hipError_t complex_product(hipStream_t s, const double* X, const double* Y, double* Z, long ld)
-		{
-			const long pl = ld * ld;
-			hipError_t err;
-			if ((err = real_product(s, X, Y, Z, ld, 1.0, 0.0)) != hipSuccess) return err;
-			if ((err = real_product(s, X + pl, Y + pl, Z, ld, -1.0, 1.0)) != hipSuccess) return err;
-			if ((err = real_product(s, X, Y + pl, Z + pl, ld, 1.0, 0.0)) != hipSuccess) return err;
-			if ((err = real_product(s, X + pl, Y, Z + pl, ld, 1.0, 1.0)) != hipSuccess) return err;
-			return mirror(s, Z, Z + pl, ld);
+			g.M = g.K = static_cast<int>(ld), g.N = static_cast<int>(cols), g.batch = 1, g.alpha = alpha, g.beta = beta, g.krange = K_FULL, g.lower_only = lower;
+			return launch_gemm(s, g, gemm_pick_tile(ld, cols, 1, lower));
 		}
 
 		// out[row] = sum_c U(row, c) in[c]: a wave per row, lane l sums the columns l, l + 64, ... in ascending order, then a fixed butterfly
@@ -161,12 +127,7 @@ namespace gple
 				re += a * v.x - b * v.y;
 				im += a * v.y + b * v.x;
 			}
-#pragma unroll
-			for (int off = 32; off > 0; off >>= 1)
-			{
-				re += __shfl_xor(re, off, 64);
-				im += __shfl_xor(im, off, 64);
-			}
+			wave_sum(re, im);
 			if (lane == 0) *reinterpret_cast<d2*>(out + 2 * static_cast<long>(row)) = (d2){re, im};
 		}
 
@@ -192,130 +153,72 @@ namespace gple
 			}
 		}
 
-		// ---- what the absorber took ----------------------------------------------------------------------------------------------------------
-		// Z = conj(P) P (its lower tiles) -> L = I - Z, zero beyond dim (Z is zero there: P is zero padded); the Hermitian mirror follows
-		__global__ void __launch_bounds__(256) dvr_loss_kernel(double* __restrict__ Lr, double* __restrict__ Li, int dim, long ld)
+		// dim and ld of a system, if the set-up kernels can take it (a column per blockIdx.y)
+		bool power_dims(int num_pes, int n, int* dim, long* ld)
 		{
-			const long r = blockIdx.x * 256L + threadIdx.x, c = blockIdx.y;
-			if (r >= ld) return;
-			Lr[r + c * ld] = ((r == c && r < dim) ? 1.0 : 0.0) - Lr[r + c * ld];
-			Li[r + c * ld] = -Li[r + c * ld];
+			*dim = num_pes * n;
+			*ld = static_cast<long>(round_up(*dim, 64));
+			return (num_pes == 2 || num_pes == 3) && *ld <= DVR_POWER_MAX_LD;
 		}
 
-		// D_c = (Pi_c L + L Pi_c) / 2 for the channel (side, k), Pi_c[(m, a), (m', a)] = [a on side] basis(a; m, k) basis(a; m', k):
-		//   (Pi_c L)(r, c) = [a on side] b(a; m, k) sum_j b(a; j, k) L((j, a), c),   (L Pi_c)(r, c) = [a' on side] sum_j L(r, (j, a')) b(a'; j, k) b(a'; m', k)
-		// for r = (m, a), c = (m', a'); zero beyond dim
-		template <int NP>
-		__global__ void __launch_bounds__(256) dvr_channel_kernel(const double* __restrict__ Lr, const double* __restrict__ Li, const double* __restrict__ basis,
-			int n, int n_left, int side, int k, long ld, double* __restrict__ Dr, double* __restrict__ Di)
+		hipError_t generator(hipStream_t s, int dim, int n, long ld, const double* H, const double* W, double dt, const DvrPowerWork& w)
 		{
-#pragma clang fp contract(off)
-			const long r = blockIdx.x * 256L + threadIdx.x, c = blockIdx.y;
-			if (r >= ld) return;
-			double re = 0.0, im = 0.0;
-			if (r < static_cast<long>(NP) * n && c < static_cast<long>(NP) * n)
+			hipLaunchKernelGGL(dvr_generator_kernel, dvr_plane_grid(ld), dim3(256), 0, s, H, W, dim, n, ld, dt, w.G, w.d);
+			return hipGetLastError();
+		}
+		// Q1 = I + A/4 -> buf[0]; Q2 = I + A/3 Q1 -> buf[1]; Q3 = I + A/2 Q2 -> buf[0]; P4 = I + A Q3 -> P
+		hipError_t horner(hipStream_t s, int dim, long ld, const DvrPowerWork& w)
+		{
+			const dim3 grid = dvr_plane_grid(ld), block(256);
+			hipError_t err;
+			hipLaunchKernelGGL(dvr_horner_first_kernel, grid, block, 0, s, w.G, w.d, dim, ld, w.buf[0].re, w.buf[0].im);
+			if ((err = hipGetLastError()) != hipSuccess) return err;
+			DvrPlanes Q = w.buf[0];
+			const DvrPlanes target[3] = {w.buf[1], w.buf[0], w.P};
+			for (int step = 0; step < 3; ++step)
 			{
-				const int m = static_cast<int>(r / n), a = static_cast<int>(r % n), mp = static_cast<int>(c / n), ap = static_cast<int>(c % n);
-				if ((a < n_left) == (side == 0))
-				{
-					const double* b = basis + static_cast<long>(a) * NP * NP;
-#pragma unroll
-					for (int j = 0; j < NP; ++j)
-					{
-						const double w = b[m * NP + k] * b[j * NP + k];
-						const long at = (static_cast<long>(j) * n + a) + c * ld;
-						re += w * Lr[at], im += w * Li[at];
-					}
-				}
-				if ((ap < n_left) == (side == 0))
-				{
-					const double* b = basis + static_cast<long>(ap) * NP * NP;
-#pragma unroll
-					for (int j = 0; j < NP; ++j)
-					{
-						const double w = b[mp * NP + k] * b[j * NP + k];
-						const long at = r + (static_cast<long>(j) * n + ap) * ld;
-						re += w * Lr[at], im += w * Li[at];
-					}
-				}
-				re *= 0.5, im *= 0.5;
+				const double k = 3.0 - step;
+				const DvrPlanes N = target[step];
+				hipLaunchKernelGGL(dvr_horner_scale_kernel, grid, block, 0, s, Q.re, Q.im, w.d, k, dim, ld, N.re, N.im);
+				if ((err = hipGetLastError()) != hipSuccess) return err;
+				// (i G / k) (Qr + i Qi) = -(G Qi) / k + i (G Qr) / k
+				if ((err = real_product(s, w.G, Q.im, N.re, ld, ld, -1.0 / k, 1.0, true)) != hipSuccess) return err;
+				if ((err = real_product(s, w.G, Q.re, N.im, ld, ld, 1.0 / k, 1.0, true)) != hipSuccess) return err;
+				if ((err = launch_dvr_mirror(s, N, ld, false)) != hipSuccess) return err;
+				Q = N;
 			}
-			Dr[r + c * ld] = re;
-			Di[r + c * ld] = im;
+			return hipSuccess;
 		}
 
-		// out(r, q) at r dim + q from the column-major padded plane: G(r, q) = conj G(q, r) reads along column r.  blockIdx.y = r, blockIdx.z = plane
-		__global__ void __launch_bounds__(256) dvr_flux_export_kernel(const double* __restrict__ Gr, const double* __restrict__ Gi, int dim, long ld,
-			double* __restrict__ out)
+		// Z = X Y for complex symmetric X and Y that commute: the lower tiles, then the mirror
+		hipError_t symmetric_product(hipStream_t s, DvrPlanes X, DvrPlanes Y, DvrPlanes Z, long ld)
 		{
-			const long q = blockIdx.x * 256L + threadIdx.x, r = blockIdx.y;
-			if (q >= dim) return;
-			if (blockIdx.z == 0) out[r * dim + q] = Gr[q + r * ld];
-			else out[static_cast<long>(dim) * dim + r * dim + q] = q == r ? 0.0 : -Gi[q + r * ld];
+			const hipError_t err = dvr_complex_product(s, X, Y, Z, ld, ld, 0.0, false, true);
+			return err != hipSuccess ? err : launch_dvr_mirror(s, Z, ld, false);
 		}
 
-		// partial[(t C + c) dim + row] = Re conj(psi_t[row]) (G_c psi_t)[row] for the states t < T of one pass (T <= DVR_FLUX_CHUNK), four states per
-		// sweep of the row; a sweep past the last state repeats it and writes nothing, so a state's operations do not depend on T or on its place
-		constexpr int FLUX_GROUP = 4;
-		__global__ void __launch_bounds__(256) dvr_flux_rows_kernel(const double* __restrict__ G, int dim, const double* __restrict__ psi, int T,
-			double* __restrict__ partial)
+		// left-to-right binary power: R = P; per lower bit of n_steps from the top R = R R, and R = R P where the bit is set.  The dvr_flux_* calls
+		// are the flux recurrence beside it (f.flux null: none, they do nothing).  *R follows the walk, also where it stops at an error
+		hipError_t walk(const DvrFluxRun& f, const DvrPowerWork& w, long n_steps, DvrPlanes* R)
 		{
-#pragma clang fp contract(off)
-			const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6), c = blockIdx.y, C = gridDim.y;
-			if (row >= dim) return;
-			const long pl = static_cast<long>(dim) * dim;
-			const double* __restrict__ gr = G + 2 * c * pl + static_cast<long>(row) * dim;
-			const double* __restrict__ gi = gr + pl;
-			for (int t0 = 0; t0 < T; t0 += FLUX_GROUP)
+			int top = 0;
+			while ((n_steps >> (top + 1)) != 0) ++top;
+			int next = 0;
+			hipError_t err;
+			if ((err = dvr_flux_first_step(f, w.P)) != hipSuccess) return err;
+			for (int bit = top - 1; bit >= 0; --bit)
 			{
-				const double* v[FLUX_GROUP];
-				double re[FLUX_GROUP], im[FLUX_GROUP];
-#pragma unroll
-				for (int g = 0; g < FLUX_GROUP; ++g) v[g] = psi + 2L * dim * min(t0 + g, T - 1), re[g] = im[g] = 0.0;
-				for (int q = lane; q < dim; q += 64)
+				if ((err = dvr_flux_before_square(f, *R)) != hipSuccess) return err;
+				if ((err = symmetric_product(f.s, *R, *R, w.buf[next], f.ld)) != hipSuccess) return err;
+				*R = w.buf[next], next ^= 1;
+				if ((n_steps >> bit) & 1)
 				{
-					const double a = gr[q], b = gi[q];
-#pragma unroll
-					for (int g = 0; g < FLUX_GROUP; ++g)
-					{
-						const d2 u = *reinterpret_cast<const d2*>(v[g] + 2L * q);
-						re[g] += a * u.x - b * u.y;
-						im[g] += a * u.y + b * u.x;
-					}
-				}
-#pragma unroll
-				for (int g = 0; g < FLUX_GROUP; ++g)
-				{
-#pragma unroll
-					for (int off = 32; off > 0; off >>= 1)
-					{
-						re[g] += __shfl_xor(re[g], off, 64);
-						im[g] += __shfl_xor(im[g], off, 64);
-					}
-					if (lane == 0 && t0 + g < T)
-					{
-						const d2 w = *reinterpret_cast<const d2*>(v[g] + 2L * row);
-						partial[(static_cast<long>(t0 + g) * C + c) * dim + row] = w.x * re[g] + w.y * im[g];
-					}
+					if ((err = dvr_flux_before_multiply(f, *R)) != hipSuccess) return err;
+					if ((err = symmetric_product(f.s, *R, w.P, w.buf[next], f.ld)) != hipSuccess) return err;
+					*R = w.buf[next], next ^= 1;
 				}
 			}
-		}
-		// absorbed[b] = sum_row partial[b dim + row]: thread i sums the rows i, i + 256, ... in ascending order, then a fixed tree
-		__global__ void __launch_bounds__(256) dvr_flux_sum_kernel(const double* __restrict__ partial, int dim, double* __restrict__ absorbed)
-		{
-#pragma clang fp contract(off)
-			__shared__ double sums[256];
-			const double* p = partial + static_cast<long>(blockIdx.x) * dim;
-			double acc = 0.0;
-			for (int r = threadIdx.x; r < dim; r += 256) acc += p[r];
-			sums[threadIdx.x] = acc;
-			__syncthreads();
-			for (int half = 128; half > 0; half >>= 1)
-			{
-				if (static_cast<int>(threadIdx.x) < half) sums[threadIdx.x] += sums[threadIdx.x + half];
-				__syncthreads();
-			}
-			if (threadIdx.x == 0) absorbed[blockIdx.x] = sums[0];
+			return hipSuccess;
 		}
 	} // namespace
 
@@ -325,145 +228,64 @@ namespace gple
 		return hipGetLastError();
 	}
 
-	hipError_t launch_dvr_square(hipStream_t s, const double* X, double* Z, long ld) { return complex_product(s, X, X, Z, ld); }
-
-	size_t dvr_power_work_doubles(int num_pes, int n)
+	hipError_t dvr_complex_product(hipStream_t s, DvrPlanes X, DvrPlanes Y, DvrPlanes Z, long ld, long cols, double beta, bool conj_x, bool lower)
 	{
-		const size_t ld = round_up(static_cast<size_t>(num_pes) * n, 64);
-		return 7 * ld * ld + ld;
-	}
-	hipError_t launch_dvr_power(Ctx* ctx, hipStream_t s, int num_pes, int n, const double* H, const double* W, double dt, long n_steps, double* work,
-		const double** result, const DvrFlux* flux)
-	{
-		if ((num_pes != 2 && num_pes != 3) || n_steps < 1) return hipErrorInvalidValue;
-		const int dim = num_pes * n;
-		const long ld = static_cast<long>(round_up(dim, 64)), pl = ld * ld;
-		if (ld > DVR_POWER_MAX_LD) return hipErrorInvalidValue; // the set-up kernels take a column per blockIdx.y
-		double* G = work;
-		double* P = G + pl;
-		double* buf[2] = {P + 2 * pl, P + 4 * pl};
-		double* d = P + 6 * pl;
-		const dim3 grid(static_cast<unsigned>((ld + 255) / 256), static_cast<unsigned>(ld)), block(256);
+		const double sign = conj_x ? -1.0 : 1.0; // Re Z = Xr Yr -+ Xi Yi, Im Z = Xr Yi +- Xi Yr
 		hipError_t err;
-		hipLaunchKernelGGL(dvr_generator_kernel, grid, block, 0, s, H, W, dim, n, ld, dt, G, d);
-		if ((err = hipGetLastError()) != hipSuccess) return err;
-		const double* R = P;
-		// what the absorber took: G_c += conj(Rm) (X Rm), T = X Rm on full tiles, the Hermitian product on the lower ones
-		const int channels = 2 * num_pes;
-		double* const fL = flux ? flux->work : nullptr;
-		double* const fD = flux ? fL + 2 * pl : nullptr;
-		double* const fT = flux ? fL + 4 * pl : nullptr;
-		double* const fG = flux ? fL + 6 * pl : nullptr;
-		auto hermitian_product = [&](const double* X, const double* Y, double* Z, double beta) -> hipError_t { // Z = beta Z + conj(X) Y, X symmetric
-			if ((err = real_product(s, X, Y, Z, ld, 1.0, beta)) != hipSuccess) return err;
-			if ((err = real_product(s, X + pl, Y + pl, Z, ld, 1.0, 1.0)) != hipSuccess) return err;
-			if ((err = real_product(s, X, Y + pl, Z + pl, ld, 1.0, beta)) != hipSuccess) return err;
-			return real_product(s, X + pl, Y, Z + pl, ld, -1.0, 1.0);
-		};
-		auto sandwich = [&](const double* X, const double* Rm, double* Gc) -> hipError_t {
-			if ((err = real_product(s, X, Rm, fT, ld, 1.0, 0.0, false)) != hipSuccess) return err;
-			if ((err = real_product(s, X + pl, Rm + pl, fT, ld, -1.0, 1.0, false)) != hipSuccess) return err;
-			if ((err = real_product(s, X, Rm + pl, fT + pl, ld, 1.0, 0.0, false)) != hipSuccess) return err;
-			if ((err = real_product(s, X + pl, Rm, fT + pl, ld, 1.0, 1.0, false)) != hipSuccess) return err;
-			if ((err = hermitian_product(Rm, fT, Gc, 1.0)) != hipSuccess) return err;
-			return mirror(s, Gc, Gc + pl, ld, true);
-		};
-		auto channel = [&](int c, double* D) -> hipError_t { // D_c into D
-			if (num_pes == 2) hipLaunchKernelGGL(dvr_channel_kernel<2>, grid, block, 0, s, fL, fL + pl, flux->basis, n, flux->n_left, c / 2, c % 2, ld, D, D + pl);
-			else hipLaunchKernelGGL(dvr_channel_kernel<3>, grid, block, 0, s, fL, fL + pl, flux->basis, n, flux->n_left, c / 3, c % 3, ld, D, D + pl);
-			if ((err = hipGetLastError()) != hipSuccess) return err;
-			return mirror(s, D, D + pl, ld, true);
-		};
-		auto products = [&]() -> hipError_t {
-		// Horner: Q1 = I + A/4 -> buf[0]; Q2 = I + A/3 Q1 -> buf[1]; Q3 = I + A/2 Q2 -> buf[0]; P4 = I + A Q3 -> P
-		hipLaunchKernelGGL(dvr_horner_first_kernel, grid, block, 0, s, G, d, dim, ld, buf[0], buf[0] + pl);
-		if ((err = hipGetLastError()) != hipSuccess) return err;
-		const double* Q = buf[0];
-		double* const target[3] = {buf[1], buf[0], P};
-		for (int step = 0; step < 3; ++step)
-		{
-			const double k = 3.0 - step;
-			double* N = target[step];
-			hipLaunchKernelGGL(dvr_horner_scale_kernel, grid, block, 0, s, Q, Q + pl, d, k, dim, ld, N, N + pl);
-			if ((err = hipGetLastError()) != hipSuccess) return err;
-			// (i G / k) (Qr + i Qi) = -(G Qi) / k + i (G Qr) / k
-			if ((err = real_product(s, G, Q + pl, N, ld, -1.0 / k, 1.0)) != hipSuccess) return err;
-			if ((err = real_product(s, G, Q, N + pl, ld, 1.0 / k, 1.0)) != hipSuccess) return err;
-			if ((err = mirror(s, N, N + pl, ld)) != hipSuccess) return err;
-			Q = N;
-		}
-		// left-to-right binary power: R = P; per lower bit from the top R = R R, and R = R P where the bit is set
-		int top = 0;
-		while ((n_steps >> (top + 1)) != 0) ++top;
-		int next = 0;
-		if (flux) // L = I - conj(P) P, G_c = D_c: one step
-		{
-			if ((err = hermitian_product(P, P, fL, 0.0)) != hipSuccess) return err;
-			hipLaunchKernelGGL(dvr_loss_kernel, grid, block, 0, s, fL, fL + pl, dim, ld);
-			if ((err = hipGetLastError()) != hipSuccess) return err;
-			if ((err = mirror(s, fL, fL + pl, ld, true)) != hipSuccess) return err;
-			for (int c = 0; c < channels; ++c)
-				if ((err = channel(c, fG + 2 * c * pl)) != hipSuccess) return err;
-		}
-		for (int bit = top - 1; bit >= 0; --bit)
-		{
-			for (int c = 0; flux && c < channels; ++c) // the steps m .. 2m - 1 are the first m seen through R = P^m
-				if ((err = sandwich(fG + 2 * c * pl, R, fG + 2 * c * pl)) != hipSuccess) return err;
-			if ((err = complex_product(s, R, R, buf[next], ld)) != hipSuccess) return err;
-			R = buf[next], next ^= 1;
-			if ((n_steps >> bit) & 1)
-			{
-				for (int c = 0; flux && c < channels; ++c) // one more step after R
-				{
-					if ((err = channel(c, fD)) != hipSuccess) return err;
-					if ((err = sandwich(fD, R, fG + 2 * c * pl)) != hipSuccess) return err;
-				}
-				if ((err = complex_product(s, R, P, buf[next], ld)) != hipSuccess) return err;
-				R = buf[next], next ^= 1;
-			}
-		}
-		return hipSuccess;
-		};
-		const int timer = flux ? GPLE_TIMER_DVR_FLUX : GPLE_TIMER_DVR_POWER;
-		if (ctx) timer_start(ctx, timer);
-		err = products();
-		if (ctx) timer_stop(ctx, timer); // on the error path too: no span stays open
-		*result = R;
-		return err;
+		if ((err = real_product(s, X.re, Y.re, Z.re, ld, cols, 1.0, beta, lower)) != hipSuccess) return err;
+		if ((err = real_product(s, X.im, Y.im, Z.re, ld, cols, -sign, 1.0, lower)) != hipSuccess) return err;
+		if ((err = real_product(s, X.re, Y.im, Z.im, ld, cols, 1.0, beta, lower)) != hipSuccess) return err;
+		return real_product(s, X.im, Y.re, Z.im, ld, cols, sign, 1.0, lower);
+	}
+	hipError_t launch_dvr_mirror(hipStream_t s, DvrPlanes Z, long ld, bool hermitian)
+	{
+		const dim3 grid(static_cast<unsigned>(ld / 32), static_cast<unsigned>(ld / 32), 2);
+		if (hermitian) hipLaunchKernelGGL(dvr_mirror_kernel<true>, grid, dim3(256), 0, s, Z.re, Z.im, ld);
+		else hipLaunchKernelGGL(dvr_mirror_kernel<false>, grid, dim3(256), 0, s, Z.re, Z.im, ld);
+		return hipGetLastError();
+	}
+	hipError_t launch_dvr_square(hipStream_t s, DvrPlanes X, DvrPlanes Z, long ld) { return symmetric_product(s, X, X, Z, ld); }
+
+	DvrPowerWork dvr_power_layout(double* work, long ld)
+	{
+		const size_t plane = static_cast<size_t>(ld) * ld;
+		DvrCarve c{work};
+		DvrPowerWork w{};
+		w.G = c.take(plane);
+		w.P = c.planes(plane);
+		w.buf[0] = c.planes(plane);
+		w.buf[1] = c.planes(plane);
+		w.d = c.take(ld);
+		w.doubles = c.used;
+		return w;
+	}
+	size_t dvr_power_work_doubles(int num_pes, int n) { return dvr_power_layout(nullptr, static_cast<long>(round_up(static_cast<size_t>(num_pes) * n, 64))).doubles; }
+
+	hipError_t launch_dvr_p4(hipStream_t s, int num_pes, int n, const double* H, const double* W, double dt, const DvrPowerWork& w)
+	{
+		int dim;
+		long ld;
+		if (!power_dims(num_pes, n, &dim, &ld)) return hipErrorInvalidValue;
+		const hipError_t err = generator(s, dim, n, ld, H, W, dt, w);
+		return err != hipSuccess ? err : horner(s, dim, ld, w);
 	}
 
-	size_t dvr_flux_work_doubles(int num_pes, int n)
+	hipError_t launch_dvr_power(Ctx* ctx, hipStream_t s, int num_pes, int n, const double* H, const double* W, double dt, long n_steps, double* work,
+		DvrPlanes* result, const DvrFlux* flux)
 	{
-		const size_t ld = round_up(static_cast<size_t>(num_pes) * n, 64);
-		return (6 + 4 * static_cast<size_t>(num_pes)) * ld * ld;
-	}
-	hipError_t launch_dvr_flux_export(hipStream_t s, int num_pes, int n, const DvrFlux& flux, double* out)
-	{
-		const int dim = num_pes * n;
-		const long ld = static_cast<long>(round_up(dim, 64)), pl = ld * ld;
-		const dim3 grid((dim + 255) / 256, dim, 2);
-		for (int c = 0; c < 2 * num_pes; ++c)
-		{
-			const double* Gc = flux.work + (6 + 2 * c) * pl;
-			hipLaunchKernelGGL(dvr_flux_export_kernel, grid, dim3(256), 0, s, Gc, Gc + pl, dim, ld, out + 2L * c * dim * dim);
-		}
-		return hipGetLastError();
-	}
-	size_t dvr_flux_apply_work_doubles(int num_pes, int n, int T)
-	{
-		return static_cast<size_t>(std::min(T, DVR_FLUX_CHUNK)) * 2 * num_pes * num_pes * n;
-	}
-	hipError_t launch_dvr_flux_apply(hipStream_t s, int num_pes, int n, const double* G, const double* psi, int T, double* partial, double* absorbed)
-	{
-		if (num_pes != 2 && num_pes != 3) return hipErrorInvalidValue;
-		const int dim = num_pes * n, C = 2 * num_pes;
-		for (int t0 = 0; t0 < T; t0 += DVR_FLUX_CHUNK) // the launches of a stream are ordered, so the chunks share `partial`
-		{
-			const int count = std::min(DVR_FLUX_CHUNK, T - t0);
-			hipLaunchKernelGGL(dvr_flux_rows_kernel, dim3((dim + 3) / 4, C), dim3(256), 0, s, G, dim, psi + 2L * dim * t0, count, partial);
-			hipLaunchKernelGGL(dvr_flux_sum_kernel, dim3(count * C), dim3(256), 0, s, partial, dim, absorbed + static_cast<long>(t0) * C);
-		}
-		return hipGetLastError();
+		int dim;
+		long ld;
+		if (!power_dims(num_pes, n, &dim, &ld) || n_steps < 1) return hipErrorInvalidValue;
+		const DvrPowerWork w = dvr_power_layout(work, ld);
+		hipError_t err = generator(s, dim, n, ld, H, W, dt, w); // before the timer's span: it times the products
+		if (err != hipSuccess) return err;
+		const DvrFluxRun f{s, num_pes, n, ld, flux, flux ? dvr_flux_layout(flux->work, ld, num_pes) : DvrFluxWork{}};
+		const int timer = flux ? GPLE_TIMER_DVR_FLUX : GPLE_TIMER_DVR_POWER;
+		*result = w.P;
+		if (ctx) timer_start(ctx, timer);
+		if ((err = horner(s, dim, ld, w)) == hipSuccess) err = walk(f, w, n_steps, result);
+		if (ctx) timer_stop(ctx, timer); // on the error path too: no span stays open
+		return err;
 	}
 
 	hipError_t launch_dvr_apply(hipStream_t s, int num_pes, int n, const double* U, const double* psi0, int T, const double* basis, double* scratch, double* psi)

@@ -7,20 +7,21 @@
 //                                64; zero beyond dim and beyond n_E); WIDE = false: psi0 in column 0 of 64 (what is left: P^K psi0 as one thin product)
 //   dvr_spectrum_phase_kernel    T = Y o e^{i theta 2^j}: theta 2^j is exact (a scaling by a power of two), the phase is sincos of that product,
 //                                never a squared z; padding written as exact zeros
-//   thin_product                 Y += R T (and P X): four real products through launch_gemm on full tiles, beta = 1 (0 for P X)
+//   dvr_complex_product          Y += R T, P^K psi0 and P X: the power's four real products on full tiles and fewer columns, beta = 1 (0 for the
+//                                last two); T's planes lie ld nep apart, those of Y and P X a whole X plane
 //   dvr_spectrum_project_kernel  Q_c = Pi_c Y for every channel c = (side, adiabatic surface) at once: block diagonal in x, a mix of num_pes rows with
 //                                `basis`, the operation order of dvr_channel_kernel's mix
 //   dvr_spectrum_reduce_kernel   a_c(E) = Re[Q_c^H Y - (P Q_c)^H (P Y)] per (energy, channel): thread-strided sums in ascending order and a fixed
 //                                tree; no floating-point atomics, no flags between workgroups.  The same kernel sums |P^K psi0|^2
 //   dvr_spectrum_export_kernel   the columns of Y as the caller's n_E x dim (re, im) pairs
+#include "gple_dvr_device.h"
 #include "gple_kernels.h"
 
 namespace gple
 {
 	namespace
 	{
-		typedef double d2 __attribute__((ext_vector_type(2)));
-		constexpr double HBAR_D = 1.0; // general.h:35
+		using namespace dvr;
 
 		// Y(r, e) = psi0[r] for r < dim, e < n_E (WIDE) or e == 0 (!WIDE); zero elsewhere.  blockIdx.y = e < columns
 		template <bool WIDE>
@@ -69,17 +70,7 @@ namespace gple
 			if (r < static_cast<long>(NP) * n && e < n_E)
 			{
 				const int m = static_cast<int>(r / n), a = static_cast<int>(r % n);
-				if ((a < n_left) == (side == 0))
-				{
-					const double* b = basis + static_cast<long>(a) * NP * NP;
-#pragma unroll
-					for (int j = 0; j < NP; ++j)
-					{
-						const double w = b[m * NP + k] * b[j * NP + k];
-						const long at = (static_cast<long>(j) * n + a) + e * ld;
-						re += w * Xr[at], im += w * Xi[at];
-					}
-				}
+				if ((a < n_left) == (side == 0)) projector_mix<NP>(basis + static_cast<long>(a) * NP * NP, m, k, Xr, Xi, a + e * ld, n, re, im);
 			}
 			const long to = r + ((1 + c) * nep + e) * ld;
 			Xr[to] = re;
@@ -93,7 +84,6 @@ namespace gple
 			int C, double* __restrict__ out)
 		{
 #pragma clang fp contract(off)
-			__shared__ double sums[256];
 			const long e = blockIdx.x / C, c = blockIdx.x % C, plane = ld * (1 + C) * nep;
 			const long y = e * ld, q = DIFF ? ((1 + c) * nep + e) * ld : y;
 			double acc = 0.0;
@@ -103,14 +93,8 @@ namespace gple
 				if (DIFF) term -= PX[q + r] * PX[y + r] + PX[plane + q + r] * PX[plane + y + r];
 				acc += term;
 			}
-			sums[threadIdx.x] = acc;
-			__syncthreads();
-			for (int half = 128; half > 0; half >>= 1)
-			{
-				if (static_cast<int>(threadIdx.x) < half) sums[threadIdx.x] += sums[threadIdx.x + half];
-				__syncthreads();
-			}
-			if (threadIdx.x == 0) out[blockIdx.x] = sums[0];
+			const double sum = block_sum_256(acc);
+			if (threadIdx.x == 0) out[blockIdx.x] = sum;
 		}
 
 		// psi_e[e][r] = (Yr, Yi)(r, e); blockIdx.y = e < n_E
@@ -122,103 +106,72 @@ namespace gple
 			*reinterpret_cast<d2*>(out + 2 * (e * dim + r)) = (d2){Yr[r + e * ld], Yi[r + e * ld]};
 		}
 
-		// C (+)= alpha R B: R ld x ld, B and C ld x cols (column-major, leading dimension ld), every tile
-		hipError_t thin_real(hipStream_t s, const double* R, const double* B, double* C, long ld, long cols, double alpha, double beta)
+		hipError_t run(hipStream_t s, const DvrSpectrum& g)
 		{
-			GemmDesc g{};
-			g.A = R, g.lda = ld, g.a_kmajor = false; // A(m, k) = R(m, k) at m + k ld
-			g.B = B, g.ldb = ld, g.b_kmajor = true;  // B(n, k) = B(k, n) at k + n ld
-			g.C = C, g.ldc = ld, g.c_trans = false;
-			g.M = g.K = static_cast<int>(ld), g.N = static_cast<int>(cols), g.batch = 1, g.alpha = alpha, g.beta = beta, g.krange = K_FULL, g.lower_only = false;
-			return launch_gemm(s, g, gemm_pick_tile(ld, cols, 1, false));
-		}
-		// Z = beta Z + R B on (Re, Im) planes of ld x cols (plane stride `plane`), the order of the power's complex_product
-		hipError_t thin_product(hipStream_t s, const double* R, const double* B, double* Z, long ld, long cols, long plane, double beta)
-		{
-			const long pl = ld * ld;
+			const int dim = g.num_pes * g.n, C = 2 * g.num_pes;
+			const long ld = static_cast<long>(round_up(dim, 64));
+			const DvrPowerWork pw = dvr_power_layout(g.power_work, ld); // P4 stays in pw.P, the squarings take pw.buf in turn
+			const long nep = static_cast<long>(round_up(g.n_E, 64)), cols = (1 + C) * nep;
+			DvrCarve work{g.work};
+			const DvrPlanes X = work.planes(ld * cols);  // Y | Q_0 .. Q_{C-1}: ld x cols per plane
+			const DvrPlanes PX = work.planes(ld * cols); // P X, the same layout
+			const DvrPlanes T = work.planes(ld * nep);   // ld x nep per plane
+			const unsigned rows = static_cast<unsigned>((ld + 255) / 256);
+			const dim3 block(256), wide(rows, static_cast<unsigned>(nep));
 			hipError_t err;
-			if ((err = thin_real(s, R, B, Z, ld, cols, 1.0, beta)) != hipSuccess) return err;
-			if ((err = thin_real(s, R + pl, B + plane, Z, ld, cols, -1.0, 1.0)) != hipSuccess) return err;
-			if ((err = thin_real(s, R, B + plane, Z + plane, ld, cols, 1.0, beta)) != hipSuccess) return err;
-			return thin_real(s, R + pl, B, Z + plane, ld, cols, 1.0, 1.0);
+			if ((err = launch_dvr_p4(s, g.num_pes, g.n, g.H, g.W, g.dt, pw)) != hipSuccess) return err;
+			hipLaunchKernelGGL(dvr_spectrum_start_kernel<true>, wide, block, 0, s, g.psi0, dim, ld, g.n_E, X.re, X.im);
+			if ((err = hipGetLastError()) != hipSuccess) return err;
+			DvrPlanes R = pw.P;
+			int next = 0;
+			auto square = [&]() -> hipError_t { // R = R R
+				const DvrPlanes Z = pw.buf[next];
+				next ^= 1;
+				const hipError_t e = launch_dvr_square(s, R, Z, ld);
+				R = Z;
+				return e;
+			};
+			double scale = 1.0;
+			for (int j = 0; j < g.levels; ++j, scale *= 2.0)
+			{
+				if (j > 0 && (err = square()) != hipSuccess) return err;
+				hipLaunchKernelGGL(dvr_spectrum_phase_kernel, wide, block, 0, s, X.re, X.im, g.energies, g.dt, scale, dim, ld, g.n_E, T.re, T.im);
+				if ((err = hipGetLastError()) != hipSuccess) return err;
+				if ((err = dvr_complex_product(s, R, T, X, ld, nep, 1.0, false, false)) != hipSuccess) return err; // Y += R T
+			}
+			if (g.remaining) // |P^K psi0|^2: the last squaring, one product of 64 columns, the reduction's sum
+			{
+				if (g.levels > 0 && (err = square()) != hipSuccess) return err;
+				hipLaunchKernelGGL(dvr_spectrum_start_kernel<false>, dim3(rows, 64), block, 0, s, g.psi0, dim, ld, 1, T.re, T.im);
+				if ((err = hipGetLastError()) != hipSuccess) return err;
+				if ((err = dvr_complex_product(s, R, T, PX, ld, 64, 0.0, false, false)) != hipSuccess) return err;
+				hipLaunchKernelGGL(dvr_spectrum_reduce_kernel<false>, dim3(1), block, 0, s, PX.re, PX.re, dim, ld, nep, C, g.remaining);
+				if ((err = hipGetLastError()) != hipSuccess) return err;
+			}
+			const dim3 pgrid(rows, static_cast<unsigned>(nep), static_cast<unsigned>(C));
+			const auto project = g.num_pes == 2 ? dvr_spectrum_project_kernel<2> : dvr_spectrum_project_kernel<3>;
+			hipLaunchKernelGGL(project, pgrid, block, 0, s, X.re, X.im, g.basis, g.n, g.n_left, ld, g.n_E, nep);
+			if ((err = hipGetLastError()) != hipSuccess) return err;
+			if ((err = dvr_complex_product(s, pw.P, X, PX, ld, cols, 0.0, false, false)) != hipSuccess) return err;
+			hipLaunchKernelGGL(dvr_spectrum_reduce_kernel<true>, dim3(static_cast<unsigned>(g.n_E * C)), block, 0, s, X.re, PX.re, dim, ld, nep, C, g.density);
+			if ((err = hipGetLastError()) != hipSuccess) return err;
+			if (g.psi_e)
+				hipLaunchKernelGGL(dvr_spectrum_export_kernel, dim3((dim + 255) / 256, static_cast<unsigned>(g.n_E)), block, 0, s, X.re, X.im, dim, ld, g.psi_e);
+			return hipGetLastError();
 		}
 	} // namespace
 
 	size_t dvr_spectrum_work_doubles(int num_pes, int n, int n_E)
 	{
 		const size_t ld = round_up(static_cast<size_t>(num_pes) * n, 64), nep = round_up(static_cast<size_t>(n_E), 64);
-		return (4 * (1 + 2 * static_cast<size_t>(num_pes)) + 2) * ld * nep;
+		return (4 * (1 + 2 * static_cast<size_t>(num_pes)) + 2) * ld * nep; // X and P X (two planes of ld x (1 + 2 num_pes) nep each), T (two of ld x nep)
 	}
 
 	hipError_t launch_dvr_spectrum(Ctx* ctx, hipStream_t s, const DvrSpectrum& g)
 	{
 		if ((g.num_pes != 2 && g.num_pes != 3) || g.levels < 0 || g.levels > 30 || g.n_E < 1) return hipErrorInvalidValue;
-		const int dim = g.num_pes * g.n, C = 2 * g.num_pes;
-		const long ld = static_cast<long>(round_up(dim, 64)), pl = ld * ld, nep = static_cast<long>(round_up(g.n_E, 64));
-		const long cols = (1 + C) * nep, plane = ld * cols;
-		double* const X = g.work;           // Y | Q_0 .. Q_{C-1}: Re plane, then Im plane
-		double* const PX = X + 2 * plane;   // P X, the same layout
-		double* const T = PX + 2 * plane;   // ld x nep, Re then Im
-		const unsigned rows = static_cast<unsigned>((ld + 255) / 256);
-		const dim3 block(256);
-		hipError_t err;
-		auto run = [&]() -> hipError_t {
-			const double* P = nullptr;
-			if ((err = launch_dvr_power(nullptr, s, g.num_pes, g.n, g.H, g.W, g.dt, 1, g.power_work, &P)) != hipSuccess) return err;
-			double* const buf[2] = {const_cast<double*>(P) + 2 * pl, const_cast<double*>(P) + 4 * pl}; // the power's two buffers: P itself stays
-			hipLaunchKernelGGL(dvr_spectrum_start_kernel<true>, dim3(rows, static_cast<unsigned>(nep)), block, 0, s, g.psi0, dim, ld, g.n_E, X, X + plane);
-			if ((err = hipGetLastError()) != hipSuccess) return err;
-			const double* R = P;
-			int next = 0;
-			double scale = 1.0;
-			for (int j = 0; j < g.levels; ++j, scale *= 2.0)
-			{
-				if (j > 0)
-				{
-					if ((err = launch_dvr_square(s, R, buf[next], ld)) != hipSuccess) return err;
-					R = buf[next], next ^= 1;
-				}
-				hipLaunchKernelGGL(dvr_spectrum_phase_kernel, dim3(rows, static_cast<unsigned>(nep)), block, 0, s, X, X + plane, g.energies, g.dt, scale, dim, ld,
-					g.n_E, T, T + ld * nep);
-				if ((err = hipGetLastError()) != hipSuccess) return err;
-				// Y += R T: T's planes lie ld nep apart, Y's `plane`
-				if ((err = thin_real(s, R, T, X, ld, nep, 1.0, 1.0)) != hipSuccess) return err;
-				if ((err = thin_real(s, R + pl, T + ld * nep, X, ld, nep, -1.0, 1.0)) != hipSuccess) return err;
-				if ((err = thin_real(s, R, T + ld * nep, X + plane, ld, nep, 1.0, 1.0)) != hipSuccess) return err;
-				if ((err = thin_real(s, R + pl, T, X + plane, ld, nep, 1.0, 1.0)) != hipSuccess) return err;
-			}
-			if (g.remaining) // |P^K psi0|^2: the last squaring, one product of 64 columns, the reduction's sum
-			{
-				if (g.levels > 0)
-				{
-					if ((err = launch_dvr_square(s, R, buf[next], ld)) != hipSuccess) return err;
-					R = buf[next], next ^= 1;
-				}
-				hipLaunchKernelGGL(dvr_spectrum_start_kernel<false>, dim3(rows, 64), block, 0, s, g.psi0, dim, ld, 1, T, T + ld * nep);
-				if ((err = hipGetLastError()) != hipSuccess) return err;
-				if ((err = thin_real(s, R, T, PX, ld, 64, 1.0, 0.0)) != hipSuccess) return err;
-				if ((err = thin_real(s, R + pl, T + ld * nep, PX, ld, 64, -1.0, 1.0)) != hipSuccess) return err;
-				if ((err = thin_real(s, R, T + ld * nep, PX + plane, ld, 64, 1.0, 0.0)) != hipSuccess) return err;
-				if ((err = thin_real(s, R + pl, T, PX + plane, ld, 64, 1.0, 1.0)) != hipSuccess) return err;
-				hipLaunchKernelGGL(dvr_spectrum_reduce_kernel<false>, dim3(1), block, 0, s, PX, PX, dim, ld, nep, C, g.remaining);
-				if ((err = hipGetLastError()) != hipSuccess) return err;
-			}
-			const dim3 pgrid(rows, static_cast<unsigned>(nep), static_cast<unsigned>(C));
-			if (g.num_pes == 2) hipLaunchKernelGGL(dvr_spectrum_project_kernel<2>, pgrid, block, 0, s, X, X + plane, g.basis, g.n, g.n_left, ld, g.n_E, nep);
-			else hipLaunchKernelGGL(dvr_spectrum_project_kernel<3>, pgrid, block, 0, s, X, X + plane, g.basis, g.n, g.n_left, ld, g.n_E, nep);
-			if ((err = hipGetLastError()) != hipSuccess) return err;
-			if ((err = thin_product(s, P, X, PX, ld, cols, plane, 0.0)) != hipSuccess) return err;
-			hipLaunchKernelGGL(dvr_spectrum_reduce_kernel<true>, dim3(static_cast<unsigned>(g.n_E * C)), block, 0, s, X, PX, dim, ld, nep, C, g.density);
-			if ((err = hipGetLastError()) != hipSuccess) return err;
-			if (g.psi_e)
-			{
-				hipLaunchKernelGGL(dvr_spectrum_export_kernel, dim3((dim + 255) / 256, static_cast<unsigned>(g.n_E)), block, 0, s, X, X + plane, dim, ld, g.psi_e);
-				if ((err = hipGetLastError()) != hipSuccess) return err;
-			}
-			return hipSuccess;
-		};
 		if (ctx) timer_start(ctx, GPLE_TIMER_DVR_SPECTRUM);
-		err = run();
+		const hipError_t err = run(s, g);
 		if (ctx) timer_stop(ctx, GPLE_TIMER_DVR_SPECTRUM); // on the error path too: no span stays open
 		return err;
 	}

@@ -284,40 +284,92 @@ namespace gple
 		double mass, const double* P, int T, double* work, double* averages);
 	// ---- the absorbing boundary (gple_dvr_power.hip): U = P4(A)^s, A = -(W + i H) dt / hbar, as complex symmetric planes of ld x ld, ld = dim rounded up to 64
 	hipError_t launch_dvr_absorber(hipStream_t s, double x_first, double dx, int n, double mass, double xmin, double xmax, double length, double* W);
-	// work layout (doubles): G = Im A (ld x ld) | P4, two power buffers (2 ld x ld each: Re, Im) | Re A (ld, diagonal)
+	// a complex matrix as its (Re, Im) planes, column-major with the leading dimension ld; the planes lie wherever the owner of the memory put them
+	struct DvrPlanes
+	{
+		double *re = nullptr, *im = nullptr;
+	};
+	// successive pieces of a work buffer, in the order they are taken; with base == nullptr only their total is counted (the dvr_*_work_doubles)
+	struct DvrCarve
+	{
+		double* base;
+		size_t used = 0;
+		double* take(size_t doubles) { used += doubles; return base ? base + (used - doubles) : nullptr; }
+		DvrPlanes planes(size_t plane) { return {take(plane), take(plane)}; } // a braced list is evaluated left to right
+	};
+	// Z = beta Z + X Y, or conj(X) Y with conj_x: X ld x ld, Y and Z ld x cols.  Four real products through launch_gemm, always in the order
+	// Xr Yr, Xi Yi (into Re Z), Xr Yi, Xi Yr (into Im Z); the three-multiplication form costs accuracy.  lower: only the lower tiles of Z (cols == ld;
+	// the caller mirrors, launch_dvr_mirror).  Z may alias neither operand
+	hipError_t dvr_complex_product(hipStream_t s, DvrPlanes X, DvrPlanes Y, DvrPlanes Z, long ld, long cols, double beta, bool conj_x, bool lower);
+	// the lower triangle of Z over the upper one, Z(r, c) <- Z(c, r); hermitian: conj Z(c, r), and the diagonal of Im Z exactly 0
+	hipError_t launch_dvr_mirror(hipStream_t s, DvrPlanes Z, long ld, bool hermitian);
+	// Z = X X for a complex symmetric X (lower tiles and the mirror): one squaring of the power
+	hipError_t launch_dvr_square(hipStream_t s, DvrPlanes X, DvrPlanes Z, long ld);
+	// the grid of the kernels that take a thread per row and a block row per column of an ld x ld plane
+	inline dim3 dvr_plane_grid(long ld) { return dim3(static_cast<unsigned>((ld + 255) / 256), static_cast<unsigned>(ld)); }
 	constexpr long DVR_POWER_MAX_LD = 65472; // ld <= 65535 = the largest gridDim.y (a column per block row in the set-up kernels); 7 ld^2 doubles of work are 240 GB there
+	// the work of the power: dvr_power_layout carves it, dvr_power_work_doubles is the end of the same carving
+	struct DvrPowerWork
+	{
+		double* G;        // Im A, ld x ld
+		DvrPlanes P;      // P4(A)
+		DvrPlanes buf[2]; // the Horner factors, then the squarings and multiplications of the walk in turn
+		double* d;        // Re A, a diagonal of ld values
+		size_t doubles;
+	};
+	DvrPowerWork dvr_power_layout(double* work, long ld);
 	size_t dvr_power_work_doubles(int num_pes, int n);
-	// H: dim x dim, W: n values or null; *result: the Re plane of U inside work (Im follows at + ld ld).  GPLE_TIMER_DVR_POWER of ctx spans the products
-	// with flux: the quadratic forms of the absorbed population beside the power, and GPLE_TIMER_DVR_FLUX instead
+	// P4(A) into w.P (H: dim x dim, W: n values or null), by the generator kernel and three Horner steps that use both buffers of w
+	hipError_t launch_dvr_p4(hipStream_t s, int num_pes, int n, const double* H, const double* W, double dt, const DvrPowerWork& w);
+	// with flux: the quadratic forms of the absorbed population beside the power (gple_dvr_flux.hip)
 	struct DvrFlux
 	{
 		const double* basis; // n x num_pes x num_pes
 		int n_left;          // the grid points a < n_left are side 0
-		double* work;        // dvr_flux_work_doubles: L, D, T (two ld x ld planes each), then the 2 num_pes channels G_c (two planes each), column-major
+		double* work;        // dvr_flux_work_doubles
 	};
-	size_t dvr_flux_work_doubles(int num_pes, int n);
+	// *result: U, planes inside work.  GPLE_TIMER_DVR_POWER of ctx spans the products (the Horner steps and the walk); with flux GPLE_TIMER_DVR_FLUX instead
 	hipError_t launch_dvr_power(Ctx* ctx, hipStream_t s, int num_pes, int n, const double* H, const double* W, double dt, long n_steps, double* work,
-		const double** result, const DvrFlux* flux = nullptr);
+		DvrPlanes* result, const DvrFlux* flux = nullptr);
+	// psi[k] = U^(k + 1) psi0, k < T; U: two dim x dim planes; scratch: T x dim pairs when basis != null (the diabatic states), unused otherwise
+	hipError_t launch_dvr_apply(hipStream_t s, int num_pes, int n, const double* U, const double* psi0, int T, const double* basis, double* scratch, double* psi);
+	// ---- what the absorber took (gple_dvr_flux.hip): per channel c = (side, surface) the Hermitian G_c, by the recurrence of the power's walk
+	struct DvrFluxWork
+	{
+		DvrPlanes L, D, T; // the loss of one step, one channel's D_c, the inner product of a sandwich
+		DvrPlanes G_c[6];  // the 2 num_pes channels
+		size_t doubles;
+	};
+	DvrFluxWork dvr_flux_layout(double* work, long ld, int num_pes);
+	size_t dvr_flux_work_doubles(int num_pes, int n);
+	// the flux recurrence beside one walk of launch_dvr_power, which calls the three steps below; with flux == nullptr (the plain power) they do nothing
+	struct DvrFluxRun
+	{
+		hipStream_t s;
+		int num_pes, n;
+		long ld;
+		const DvrFlux* flux;
+		DvrFluxWork w; // flux->work carved
+	};
+	hipError_t dvr_flux_first_step(const DvrFluxRun& f, DvrPlanes P);      // L = I - conj(P) P and G_c = D_c: one step
+	hipError_t dvr_flux_before_square(const DvrFluxRun& f, DvrPlanes R);   // G_c += conj(R) G_c R: the steps m .. 2m - 1 are the first m seen through R = P^m
+	hipError_t dvr_flux_before_multiply(const DvrFluxRun& f, DvrPlanes R); // G_c += conj(R) D_c R: one more step after R
 	// channel c of flux.work without its padding, row-major, into out (2 num_pes channels of two dim x dim planes)
 	hipError_t launch_dvr_flux_export(hipStream_t s, int num_pes, int n, const DvrFlux& flux, double* out);
 	// absorbed[t 2 num_pes + c] = Re psi_t^H G_c psi_t; G as launch_dvr_flux_export writes it; partial: dvr_flux_apply_work_doubles
 	constexpr int DVR_FLUX_CHUNK = 64; // states per pair of launches (the row results of a chunk are DVR_FLUX_CHUNK x 2 num_pes x dim doubles)
 	size_t dvr_flux_apply_work_doubles(int num_pes, int n, int T);
 	hipError_t launch_dvr_flux_apply(hipStream_t s, int num_pes, int n, const double* G, const double* psi, int T, double* partial, double* absorbed);
-	// psi[k] = U^(k + 1) psi0, k < T; U: two dim x dim planes; scratch: T x dim pairs when basis != null (the diabatic states), unused otherwise
-	hipError_t launch_dvr_apply(hipStream_t s, int num_pes, int n, const double* U, const double* psi0, int T, const double* basis, double* scratch, double* psi);
-	// Z = X X for complex symmetric planes of ld x ld (lower tiles and the mirror): one squaring of the power.  Z may not alias X
-	hipError_t launch_dvr_square(hipStream_t s, const double* X, double* Z, long ld);
 	// ---- the spectrum of one absorbing run (gple_dvr_spectrum.hip): Y(E) = sum_{k < 2^levels} e^{i E dt k / hbar} P4^k psi0 per energy, by the power's squarings
 	struct DvrSpectrum
 	{
 		int num_pes, n, levels, n_left, n_E;
-		const double *H, *W;   // as launch_dvr_power (W nullable)
+		const double *H, *W;   // as launch_dvr_p4 (W nullable)
 		double dt;
 		const double* basis;   // n x num_pes x num_pes
 		const double* psi0;    // dim (re, im) pairs
 		const double* energies; // n_E
-		double* power_work;    // dvr_power_work_doubles: P4 stays in it, its two buffers take the squarings
+		double* power_work;    // dvr_power_work_doubles: P4 stays in its P, its buf[0] and buf[1] take the squarings
 		double* work;          // dvr_spectrum_work_doubles: X = Y | Pi_c Y (two planes of ld x (1 + 2 num_pes) nep), P X (the same), T (two planes of ld x nep)
 		double* density;       // n_E x 2 num_pes: Re[(Pi_c Y)^H Y - (P Pi_c Y)^H (P Y)]
 		double* psi_e;         // nullable: n_E x dim (re, im) pairs

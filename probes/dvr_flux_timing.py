@@ -1,4 +1,4 @@
-"""Timing of the absorbed-population bookkeeping of the exact DVR dynamics (gple_dvr_flux / gple_dvr_flux_apply, csrc/gple_dvr_power.hip;
+"""Timing of the absorbed-population bookkeeping of the exact DVR dynamics (gple_dvr_flux / gple_dvr_flux_apply, csrc/gple_dvr_flux.hip;
 DESIGN.md §11) at the ln E = 0 defaults of schrodinger_equation/input.py (n = 1935, dim 3870, output_step = 1280).  One JSON line per figure:
   flux      GPLE_TIMER_DVR_FLUX of one gple_dvr_flux call (median of --reps after a warm-up), the whole call, and by count the real-GEMM
             flops of the power (lower tiles) and of the sandwiches (four products on full tiles, four on lower tiles each), with the rate

@@ -1,4 +1,4 @@
-"""GPU: what the absorber took (gple_dvr_flux, gple_dvr_flux_apply; csrc/gple_dvr_power.hip) against the numpy restatement and
+"""GPU: what the absorber took (gple_dvr_flux, gple_dvr_flux_apply; csrc/gple_dvr_flux.hip) against the numpy restatement and
 its long-double oracle (tests/dvr_flux_numpy.py), and the driver exact.run(flux=True, until_absorbed=True) against a numpy run of its loop.
 Every test here needs the two entry points: none passes without them.  Measured ratios error / tolerance are printed before each assertion."""
 import ctypes as C
