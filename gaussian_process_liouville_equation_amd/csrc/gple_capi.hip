@@ -1684,4 +1684,42 @@ extern "C"
 		GPLE_HIP(ctx, hipMemcpy(C, c.p, nc * 8, hipMemcpyDeviceToHost));
 		return GPLE_OK;
 	}
+
+	/* gple_debug.h: the same product the way the fits call it — every operand a window of a larger buffer (origin offset, leading dimension beyond
+	 * the extent, batch stride; 0 repeats an operand).  The three whole buffers go to the device, one launch runs, the whole C buffer comes back,
+	 * so the caller sees what was written outside the windows as well.  Every window is checked against its buffer here: nothing is launched
+	 * that would leave one. */
+	int gple_debug_gemm_strided(gple_ctx* ctx, const double* A, long countA, long offA, long lda, long strideA, int a_kmajor, const double* B, long countB,
+		long offB, long ldb, long strideB, int b_kmajor, double* C, long countC, long offC, long ldc, long strideC, int c_trans, int batch, int M, int N, int K,
+		double alpha, double beta, int krange, int lower_only, int tile)
+	{
+		if (!ctx || !A || !B || !C || M <= 0 || N <= 0 || K <= 0 || batch <= 0) return GPLE_ERR_BAD_ARG;
+		// rows x cols window, `fast` contiguous: the last element of the last item must lie inside the buffer; the kernels load 16- and 32-byte vectors
+		auto inside = [batch](long count, long off, long ld, long stride, long fast, long slow) {
+			if (off < 0 || stride < 0 || ld < fast || count <= 0 || off % 4 || ld % 4 || stride % 4) return false;
+			return off + (batch - 1) * stride + (slow - 1) * ld + fast <= count;
+		};
+		if (!inside(countA, offA, lda, strideA, a_kmajor ? K : M, a_kmajor ? M : K) || !inside(countB, offB, ldb, strideB, b_kmajor ? K : N, b_kmajor ? N : K) ||
+			!inside(countC, offC, ldc, strideC, c_trans ? N : M, c_trans ? M : N))
+			return GPLE_ERR_BAD_ARG;
+		if (batch > 1 && strideC < (c_trans ? M : N) * ldc) return GPLE_ERR_BAD_ARG; // items of C must not overlap
+		GPLE_OPEN(ctx);
+		GPLE_CALL(ctx);
+		hipStream_t st = ctx->stream;
+		Scratch a(ctx), b(ctx), c(ctx);
+		GPLE_HIP(ctx, a.get(countA));
+		GPLE_HIP(ctx, b.get(countB));
+		GPLE_HIP(ctx, c.get(countC));
+		GPLE_HIP(ctx, copy_in(st, a.p, A, countA, false));
+		GPLE_HIP(ctx, copy_in(st, b.p, B, countB, false));
+		GPLE_HIP(ctx, copy_in(st, c.p, C, countC, false));
+		GemmDesc g{};
+		g.A = a.p + offA, g.lda = lda, g.strideA = strideA, g.B = b.p + offB, g.ldb = ldb, g.strideB = strideB, g.C = c.p + offC, g.ldc = ldc, g.strideC = strideC;
+		g.M = M, g.N = N, g.K = K, g.batch = batch, g.alpha = alpha, g.beta = beta, g.krange = krange, g.lower_only = lower_only;
+		g.a_kmajor = a_kmajor != 0, g.b_kmajor = b_kmajor != 0, g.c_trans = c_trans != 0;
+		GPLE_HIP(ctx, launch_gemm(st, g, tile ? tile : gemm_pick_tile(M, N, 1, krange != K_FULL || lower_only))); // (the tile of ONE product, as the fits pick it)
+		GPLE_HIP(ctx, hipStreamSynchronize(st));
+		GPLE_HIP(ctx, hipMemcpy(C, c.p, static_cast<size_t>(countC) * 8, hipMemcpyDeviceToHost));
+		return GPLE_OK;
+	}
 }

@@ -2,7 +2,7 @@
  * internal kernel family on host operands so that tests and probes can check it in isolation.
  *   tests/test_gpu_chol_diag.py, probes/step_probe.py -> gple_debug_potrf_step
  *   tests/test_host_logic.py                          -> gple_debug_chol_layout (no device call)
- *   tests/test_gpu_gemm.py                            -> gple_debug_gemm
+ *   tests/test_gpu_gemm.py                            -> gple_debug_gemm, gple_debug_gemm_strided
  *   tests/test_gpu_chol_diag.py                       -> gple_debug_side_stream, gple_debug_chol_knobs (the give-up test)
  *   tests/test_gpu_parity.py                          -> gple_debug_predict_knobs
  *   tests/test_gpu_format.py                          -> gple_debug_format_knobs */
@@ -22,6 +22,14 @@ extern "C"
 	 * in gple_internal.h; tile = 32 | 64 | 128 | 0 (the library's own choice). */
 	int gple_debug_gemm(gple_ctx* ctx, const double* A, long lda, int a_kmajor, const double* B, long ldb, int b_kmajor, double* C, long ldc,
 		int c_trans, int M, int N, int K, double alpha, double beta, int krange, int lower_only, int tile);
+	/* The same product on windows of larger buffers, as the fits call the family: per operand the whole host buffer with its element count, the
+	 * element offset of the window's origin, the leading dimension and the batch stride (0 repeats the operand for every item).  The three buffers
+	 * are copied in whole, one launch of `batch` items runs, the whole C buffer is copied back — what lies outside the written windows included.
+	 * Offsets, leading dimensions and strides are multiples of 4 doubles (the kernels load 32-byte vectors); a window that leaves its buffer, or
+	 * items of C that overlap, are GPLE_ERR_BAD_ARG and nothing is launched. */
+	int gple_debug_gemm_strided(gple_ctx* ctx, const double* A, long countA, long offA, long lda, long strideA, int a_kmajor, const double* B, long countB,
+		long offB, long ldb, long strideB, int b_kmajor, double* C, long countC, long offC, long ldc, long strideC, int c_trans, int batch, int M, int N, int K,
+		double alpha, double beta, int krange, int lower_only, int tile);
 	/* The side stream the context's fits run their block-row inverse on (created by the first fit with n >= 1024): how many candidate streams
 	 * were tried until one ran beside the main stream, and whether the chosen one did (0: none did, or no fit has needed one yet). */
 	int gple_debug_side_stream(gple_ctx* ctx, int* attempts, int* overlaps);

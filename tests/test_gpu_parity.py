@@ -735,7 +735,7 @@ from gaussian_process_liouville_equation_amd import _capi as c
 from tests.test_gpu_configs import config_inputs, THETA_R, THETA_C
 api = pkg.open_api(0)
 out = []
-for N in (100, 256, 300, 700):
+for N in (100, 256, 300, 700, 1000, 1024):
     for cplx in (False, True):
         X, y, _, _ = config_inputs(N, 8, 11, cplx=cplx)
         fit = (api.complex_fit if cplx else api.real_fit)(THETA_C if cplx else THETA_R, X, y, 7)

@@ -18,6 +18,20 @@ def test_complex_fixture(oracle, name, tol):
     parity.check_complex_case(oracle, load_golden(name), deriv=True, tol=tol)
 
 
+def test_deriv_large_complex_fixture_is_what_the_oracle_computes(oracle):
+    """tests/golden/deriv_large_complex_513.npz (oracle/gen_deriv_large.py) stores the oracle's complex derivative fit at N = 513 because
+    the literal complex oracle is too slow for a GPU test: regenerated here, every stored member must match to 1e-12 of its largest
+    entry, so the fixture cannot drift away from the oracle.  Takes about 15-20 s on 8 threads (one O(35 N^3) complex fit)."""
+    from oracle import gen_deriv_large as gen
+    stored = dict(np.load(gen.fixture_path(513)))
+    fresh = gen.complex_reference(oracle, 513)
+    assert sorted(stored) == sorted(fresh)
+    assert stored["dv"].shape == (8, 513) and stored["v"].shape == (513,) and np.iscomplexobj(stored["dv"])
+    for k in sorted(fresh):
+        assert np.all(np.isfinite(stored[k])), k
+        assert parity.rel(stored[k], fresh[k]) <= 1e-12, (k, parity.rel(stored[k], fresh[k]))
+
+
 def test_loocv_identity_bruteforce(oracle):
     """Error = sum (v_i / W_ii)^2 equals the squared leave-one-out residuals computed by N refits."""
     X, y, _ = parity.synthetic_real(24, 4, 5)
