@@ -363,8 +363,9 @@ def _signatures():
         "format_g": (st, [CTX, _dp, sz, sz, sz, u, vp, sz, szp]),
         # and the doubles of such text
         "parse_g": (st, [CTX, vp, sz, u, _dp, sz, szp, szp, szp]),
-        # csrc/gple_debug.h: the one debug entry point the binding itself calls
+        # csrc/gple_debug.h: the debug entry points the binding itself calls
         "debug_last_contraction_kernel": (C.c_char_p, [CTX]),
+        "debug_fit_factor": (st, [vp, vp, _dp, sz, ip, ip, ip]),
     }
 
 
@@ -410,6 +411,17 @@ class _Fit:
             self.release()
         except Exception:
             pass
+
+    def debug_factor(self):
+        """gple_debug_fit_factor (csrc/gple_debug.h): (T, n_split, N) with T[n, k] the padded n_total x n_total inverse Cholesky factor as the
+        predict kernels read it — the 64 x 64 blocks above the diagonal are unwritten memory (NaN under GPLE_POISON_T=1)"""
+        which = (None, self.handle) if self.kind == "complex" else (self.handle, None)
+        nt, ns, N = C.c_int(), C.c_int(), C.c_int()
+        fn = self.api.lib.gple_debug_fit_factor
+        self.api._check(fn(*which, None, 0, C.byref(nt), C.byref(ns), C.byref(N)))
+        buf = np.empty(nt.value * nt.value)
+        self.api._check(fn(*which, _ptr(buf), buf.size, C.byref(nt), C.byref(ns), C.byref(N)))
+        return buf.reshape(nt.value, nt.value).T, ns.value, N.value  # (the buffer is column-major: T(n, k) at [n + k n_total])
 
     def get(self, which):
         N = self.N

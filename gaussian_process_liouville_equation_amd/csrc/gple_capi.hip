@@ -1585,6 +1585,24 @@ extern "C"
 		if (recoveries) *recoveries = ctx->dag_recoveries;
 		return GPLE_OK;
 	}
+	// gple_debug.h: the fit's inverse Cholesky factor as the predict kernels read it (validated first, like every getter)
+	int gple_debug_fit_factor(const gple_real_fit* real, const gple_complex_fit* cplx, double* T, size_t capacity, int* n_total, int* n_split, int* N)
+	{
+		if ((real != nullptr) == (cplx != nullptr)) return GPLE_ERR_BAD_ARG; // exactly one of the two
+		FitCommon* f = real ? static_cast<FitCommon*>(const_cast<gple_real_fit*>(real)) : static_cast<FitCommon*>(const_cast<gple_complex_fit*>(cplx));
+		gple_ctx* ctx = f->ctx;
+		GPLE_CALL(ctx);
+		const size_t nt = static_cast<size_t>(f->n_total);
+		if (n_total) *n_total = f->n_total;
+		if (n_split) *n_split = f->Np;
+		if (N) *N = f->N;
+		if (!T && capacity == 0) return GPLE_OK; // a question about the sizes only
+		if (!T || capacity < nt * nt) return GPLE_ERR_BAD_ARG;
+		if (!f->validated.load()) GPLE_TRY(validate_fit(ctx, f)); // (a getter drains the stream anyway)
+		GPLE_HIP(ctx, hipMemcpyAsync(T, f->T, nt * nt * 8, hipMemcpyDeviceToHost, ctx->stream));
+		GPLE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+		return settle_fit(ctx, f);
+	}
 	const char* gple_debug_last_contraction_kernel(gple_ctx* ctx) { return ctx ? ctx->last_contraction : ""; }
 	int gple_debug_predict_knobs(gple_ctx* ctx, int rownorm_pipe, int fused_small)
 	{

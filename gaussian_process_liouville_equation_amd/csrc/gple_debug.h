@@ -5,7 +5,8 @@
  *   tests/test_gpu_gemm.py                            -> gple_debug_gemm, gple_debug_gemm_strided
  *   tests/test_gpu_chol_diag.py                       -> gple_debug_side_stream, gple_debug_chol_knobs (the give-up test)
  *   tests/test_gpu_parity.py                          -> gple_debug_predict_knobs
- *   tests/test_gpu_format.py                          -> gple_debug_format_knobs */
+ *   tests/test_gpu_format.py                          -> gple_debug_format_knobs
+ *   tests/test_gpu_predict_rows.py                    -> gple_debug_fit_factor */
 #ifndef GPLE_DEBUG_H
 #define GPLE_DEBUG_H
 #include "../../include/gple.h"
@@ -47,6 +48,17 @@ extern "C"
 	 * of a unit as one pipeline).  fused_small: real fits with N <= 256 — 0 = K* generation, contraction and sums as separate kernels,
 	 * 1 = predict_fused256_kernel.  Either pair must agree bit for bit (tests/test_gpu_parity.py). */
 	int gple_debug_predict_knobs(gple_ctx* ctx, int rownorm_pipe, int fused_small);
+	/* The inverse Cholesky factor T = chol(K)^-1 of a fit, copied to the host exactly as the predict kernels read it: the whole
+	 * n_total x n_total buffer with ldt = n_total, padding included.  Exactly one of `real` and `cplx` is set (as in gple_element); both or
+	 * neither is GPLE_ERR_BAD_ARG.  Element order: T(n, k) — row n of the factor, the index the contraction's result rows sit on,
+	 * column k, the index of K*(row, k) — lies at T[n + k * n_total]: column-major, n fastest.  T(n, k) = 0 for k > n inside the diagonal
+	 * 64 x 64 blocks; the 64 x 64 blocks above the diagonal are never written and never read (whatever the memory held, NaN patterns under
+	 * GPLE_POISON_T=1).  The complex fit is the real system of [Re; Im]: n_total = 2 n_split, index n_split + i is the imaginary part of point i.
+	 * Rows and columns N .. n_split - 1 of either half are padding, where T is the identity.  n_total, n_split (= n_total for a real fit's one
+	 * half) and N (each nullable) are always reported; T = NULL with capacity = 0 asks for them alone.  capacity: doubles T has room for — fewer
+	 * than n_total^2 is GPLE_ERR_BAD_ARG and nothing is copied.  Like the other getters the call validates the fit first, so a give-up of the
+	 * one-launch factorisation is recovered before the copy.  tests/test_gpu_predict_rows.py */
+	int gple_debug_fit_factor(const gple_real_fit* real, const gple_complex_fit* cplx, double* T, size_t capacity, int* n_total, int* n_split, int* N);
 	/* Name of the kernel the last predict of this context ran its variance contraction on ("" before the first one; bench.py's roofline label). */
 	const char* gple_debug_last_contraction_kernel(gple_ctx* ctx);
 	/* Test knob of gple_format_g on ONE context: slots = 1 — the size pass keeps every item (16 bytes and a length byte per number) and the write
