@@ -18,6 +18,7 @@ CALC_DERIVATIVE = 0x4
 IO_DEVICE = 0x100
 EVOLVE_NEW_POINTS = 0x400  # gple_evolve: new_point_predict instead of a tick
 FORMAT_JOIN = 0x1000  # gple_format_g: no blank before the first number of a line
+PES_USER = 16  # GPLE_PES_USER: first id of a user potential (gple_pes_define)
 PREDICT_FULL = 0x200  # contract every test row (default: far rows whose contraction cannot move the variance are skipped)
 
 # gple_real_array / gple_complex_array
@@ -328,6 +329,9 @@ def _signatures():
         "evolve": (st, [CTX, el, i, d, d, pts, u]),
         "evolve_n": (st, [CTX, i, el, i, d, d, pts, u]),
         "pes_adiabatic_n": (st, [CTX, i, i, _dp, sz, u, _dp]),
+        "pes_define": (st, [CTX, i, d, d, sz, _dp, _dp, u, ip]),
+        "pes_undefine": (st, [CTX, i]),
+        "pes_diabatic_n": (st, [CTX, i, i, _dp, sz, u, _dp, _dp]),
         "markov_chain": (st, [CTX, el, sz, d, ull, _dp, sz, _dp]),
         "markov_chain_trace": (st, [CTX, el, sz, d, ull, _dp, sz, _dp, _dp]),
         # the NLML GP of test/gpr.cpp
@@ -631,6 +635,29 @@ class Api:
                 NAC[:, k, l], NAC[:, l, k] = out[:, num_pes + ne + e], -out[:, num_pes + ne + e]
                 e += 1
         return E, F, NAC
+
+    # ---- user potentials (gple_pes_define; pes.py tabulates a function) ------------------------------------------------------------------
+    def pes_define(self, num_pes, x_first, dx, V, dV):
+        """gple_pes_define: register the table V, dV (n, num_pes, num_pes) of the diabatic matrix and its x derivative at x_first + dx k (numpy
+        arrays, or contiguous float64 device tensors) -> the model id (>= PES_USER) every N-level entry point of this context accepts"""
+        V, dV = (a if _on_device(a) else _f64(a) for a in (V, dV))
+        if tuple(V.shape) != tuple(dV.shape) or len(V.shape) != 3 or tuple(V.shape[1:]) != (num_pes, num_pes):
+            raise ValueError("V and dV must have shape (n, num_pes, num_pes)")
+        (pv, pd), flags = _io(V, dV)
+        model = C.c_int(-1)
+        self._check(self.lib.gple_pes_define(self.ctx, int(num_pes), float(x_first), float(dx), int(V.shape[0]), pv, pd, flags, C.byref(model)))
+        return model.value
+
+    def pes_undefine(self, model):
+        """gple_pes_undefine: free a user model (its id may be handed out again)"""
+        self._check(self.lib.gple_pes_undefine(self.ctx, int(model)))
+
+    def pes_diabatic_n(self, num_pes, model, x):
+        """gple_pes_diabatic_n: (V (M, N, N), F = -dV/dx (M, N, N)) of any model, built-in or user, at positions x"""
+        x = _f64(x)
+        V, F = np.empty((len(x), num_pes, num_pes)), np.empty((len(x), num_pes, num_pes))
+        self._check(self.lib.gple_pes_diabatic_n(self.ctx, int(num_pes), int(model), _ptr(x), len(x), 0, _ptr(V), _ptr(F)))
+        return V, F
 
     # ---- exact DVR dynamics (schrodinger_equation/ of the reference; gple_dvr_* / gple_wigner) ----------------------------------------------
     DVR_REFLECTIVE, DVR_PERIODIC = 0, 1

@@ -30,6 +30,19 @@ struct gple_ctx: gple::Ctx
 	// the stream and the struct itself go when the last handle created from it is released.
 	std::atomic<int> refs{1};
 	std::atomic<bool> closed{false};
+	// The user potentials of gple_pes_define: slot k holds the model GPLE_PES_USER + k.  The table is device memory of its own (not pooled),
+	// freed by gple_pes_undefine after draining the stream, or with the context.  pes_mu guards the slots; a call copies its descriptor
+	// out under it (pes_resolve) once to validate its arguments and again after it has taken the call lock, and enqueues with that copy:
+	// gple_pes_undefine holds the call lock and drains the stream before it frees, so the table outlives every kernel enqueued on it.
+	struct PesSlot
+	{
+		double* table = nullptr; // nullptr: free
+		int num_pes = 0, n = 0;
+		double x_first = 0.0, dx = 1.0;
+	};
+	static constexpr int PES_SLOTS = 16;
+	PesSlot pes[PES_SLOTS];
+	std::mutex pes_mu;
 
 	double* acquire(size_t bytes, hipError_t* err)
 	{
@@ -67,6 +80,8 @@ inline void ctx_drop(gple_ctx* ctx)
 	(void)hipSetDevice(ctx->device);
 	(void)hipStreamSynchronize(ctx->stream);
 	for (auto& e : ctx->pool) (void)hipFree(e.p);
+	for (auto& slot : ctx->pes)
+		if (slot.table) (void)hipFree(slot.table);
 	if (ctx->host_scalars) (void)hipHostFree(ctx->host_scalars);
 	if (ctx->prune_stats) (void)hipFree(ctx->prune_stats);
 	if (ctx->format_table) (void)hipFree(ctx->format_table);
@@ -92,6 +107,24 @@ inline void ctx_drop(gple_ctx* ctx)
 #define GPLE_CALL(ctx)                                             \
 	std::lock_guard<std::mutex> gple_call_lk_((ctx)->call_mu); \
 	GPLE_HIP((ctx), hipSetDevice((ctx)->device))
+
+// The potential of a num_pes-level call: a built-in id by the rule the N-level entry points share (models 0-2, TSAC = 3 at three levels only),
+// or a user id defined on this context with the same num_pes.  false: the call returns GPLE_ERR_BAD_ARG
+inline bool pes_resolve(gple_ctx* ctx, int num_pes, int model, gple::PesModel* out)
+{
+	if (num_pes != 2 && num_pes != 3) return false;
+	if (model >= 0 && model <= (num_pes == 3 ? 3 : 2))
+	{
+		*out = gple::PesModel(model);
+		return true;
+	}
+	if (model < GPLE_PES_USER || model >= GPLE_PES_USER + gple_ctx::PES_SLOTS) return false;
+	std::lock_guard<std::mutex> lk(ctx->pes_mu);
+	const gple_ctx::PesSlot& slot = ctx->pes[model - GPLE_PES_USER];
+	if (!slot.table || slot.num_pes != num_pes) return false;
+	out->id = model, out->n = slot.n, out->table = slot.table, out->x_first = slot.x_first, out->dx = slot.dx;
+	return true;
+}
 
 namespace gple
 {

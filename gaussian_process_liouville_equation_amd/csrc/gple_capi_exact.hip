@@ -7,13 +7,13 @@
 extern "C"
 {
 	/* ---- exact DVR dynamics (gple_dvr.hip; schrodinger_equation/general.cpp of the reference) ---------------------------------------------- */
-	static bool dvr_model_ok(int num_pes, int model) { return (num_pes == 2 || num_pes == 3) && model >= 0 && model <= (num_pes == 3 ? 3 : 2); }
 	static bool dvr_grid_ok(size_t n_grids, double dx) { return n_grids >= 2 && n_grids <= (1u << 16) && dx > 0.0 && std::isfinite(dx); }
 
 	int gple_dvr_hamiltonian(gple_ctx* ctx, int num_pes, int model, int boundary, double x_first, double dx, size_t n_grids, double mass, unsigned flags,
 		double* H, double* energies, double* basis)
 	{
-		if (!ctx || !dvr_model_ok(num_pes, model) || (boundary != GPLE_DVR_REFLECTIVE && boundary != GPLE_DVR_PERIODIC) || !dvr_grid_ok(n_grids, dx) ||
+		PesModel pes;
+		if (!ctx || !pes_resolve(ctx, num_pes, model, &pes) || (boundary != GPLE_DVR_REFLECTIVE && boundary != GPLE_DVR_PERIODIC) || !dvr_grid_ok(n_grids, dx) ||
 			!std::isfinite(x_first) || !(mass > 0.0))
 			return GPLE_ERR_BAD_ARG;
 		GPLE_OPEN(ctx);
@@ -21,17 +21,18 @@ extern "C"
 		const int n = static_cast<int>(n_grids);
 		const size_t dim = static_cast<size_t>(num_pes) * n_grids;
 		GPLE_CALL(ctx);
+		if (!pes_resolve(ctx, num_pes, model, &pes)) return GPLE_ERR_BAD_ARG; // under the call lock, which gple_pes_undefine takes: the table outlives the enqueue
 		hipStream_t st = ctx->stream;
 		Staged h(ctx, dev), e(ctx, dev), b(ctx, dev);
 		Scratch sw(ctx);
 		GPLE_HIP(ctx, h.out(H, dim * dim));
 		GPLE_HIP(ctx, e.out(energies, n_grids * num_pes));
 		GPLE_HIP(ctx, b.out(basis, n_grids * num_pes * num_pes));
-		if (h.p) GPLE_HIP(ctx, launch_dvr_hamiltonian(st, num_pes, model, boundary, x_first, dx, n, mass, h.p));
+		if (h.p) GPLE_HIP(ctx, launch_dvr_hamiltonian(st, num_pes, pes, boundary, x_first, dx, n, mass, h.p));
 		if (e.p || b.p)
 		{
 			GPLE_HIP(ctx, sw.get(dvr_states_work_doubles(num_pes, n)));
-			GPLE_HIP(ctx, launch_dvr_states(st, num_pes, model, x_first, dx, n, e.p, b.p, sw.p));
+			GPLE_HIP(ctx, launch_dvr_states(st, num_pes, pes, x_first, dx, n, e.p, b.p, sw.p));
 		}
 		for (Staged* o : {&h, &e, &b}) GPLE_HIP(ctx, o->back());
 		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
@@ -278,10 +279,10 @@ extern "C"
 	}
 
 	/* ---- exact MQCLE dynamics (gple_mqcl.hip; liouville_equation/ of the reference) ------------------------------------------------------ */
-	static bool mqcl_size_ok(int num_pes, int model, size_t n) { return dvr_model_ok(num_pes, model) && n >= 4 && n <= 4096; }
+	static bool mqcl_size_ok(gple_ctx* ctx, int num_pes, int model, size_t n, PesModel* pes) { return pes_resolve(ctx, num_pes, model, pes) && n >= 4 && n <= 4096; }
 
 	// the per-x tables of gple_mqcl.hip from host or device x (tq: the time of one Q step, spectral: the FFT tables too)
-	static int mqcl_tables(gple_ctx* ctx, hipStream_t st, int num_pes, int model, const double* x, int n, double tq, bool spectral, Staged& xs,
+	static int mqcl_tables(gple_ctx* ctx, hipStream_t st, int num_pes, const PesModel& model, const double* x, int n, double tq, bool spectral, Staged& xs,
 		Scratch& tables)
 	{
 		GPLE_HIP(ctx, xs.in(x, n));
@@ -293,16 +294,18 @@ extern "C"
 	int gple_mqcl_transform(gple_ctx* ctx, int num_pes, int model, const double* x, size_t n_grids, int from, int to, unsigned flags, const double* rho_in,
 		double* rho_out)
 	{
-		if (!ctx || !mqcl_size_ok(num_pes, model, n_grids) || from < 0 || from > 2 || to < 0 || to > 2 || !x || !rho_in || !rho_out) return GPLE_ERR_BAD_ARG;
+		PesModel pes;
+		if (!ctx || !mqcl_size_ok(ctx, num_pes, model, n_grids, &pes) || from < 0 || from > 2 || to < 0 || to > 2 || !x || !rho_in || !rho_out) return GPLE_ERR_BAD_ARG;
 		GPLE_OPEN(ctx);
 		const bool dev = flags & GPLE_IO_DEVICE;
 		const int n = static_cast<int>(n_grids);
 		const size_t doubles = 2 * static_cast<size_t>(num_pes) * num_pes * n_grids * n_grids;
 		GPLE_CALL(ctx);
+		if (!pes_resolve(ctx, num_pes, model, &pes)) return GPLE_ERR_BAD_ARG; // under the call lock, which gple_pes_undefine takes: the table outlives the enqueue
 		hipStream_t st = ctx->stream;
 		Staged xs(ctx, dev), ri(ctx, dev), ro(ctx, dev);
 		Scratch tables(ctx);
-		GPLE_TRY(mqcl_tables(ctx, st, num_pes, model, x, n, 0.0, false, xs, tables));
+		GPLE_TRY(mqcl_tables(ctx, st, num_pes, pes, x, n, 0.0, false, xs, tables));
 		GPLE_HIP(ctx, ri.in(rho_in, doubles));
 		GPLE_HIP(ctx, ro.out(rho_out, doubles));
 		GPLE_HIP(ctx, launch_mqcl_transform(st, num_pes, n, from, to, tables.p, ri.p, ro.p));
@@ -314,7 +317,8 @@ extern "C"
 	int gple_mqcl_evolve(gple_ctx* ctx, int num_pes, int model, const double* x, const double* p, size_t n_grids, double mass, double length_x,
 		double length_p, double dt, size_t n_steps, unsigned flags, double* rho)
 	{
-		if (!ctx || !mqcl_size_ok(num_pes, model, n_grids) || !x || !p || !rho || !(mass > 0.0) || !std::isfinite(mass) || !(length_x > 0.0) ||
+		PesModel pes;
+		if (!ctx || !mqcl_size_ok(ctx, num_pes, model, n_grids, &pes) || !x || !p || !rho || !(mass > 0.0) || !std::isfinite(mass) || !(length_x > 0.0) ||
 			!std::isfinite(length_x) || !(length_p > 0.0) || !std::isfinite(length_p) || !std::isfinite(dt) || n_steps > (1ul << 40))
 			return GPLE_ERR_BAD_ARG;
 		GPLE_OPEN(ctx);
@@ -323,10 +327,11 @@ extern "C"
 		const int n = static_cast<int>(n_grids);
 		const size_t plane = n_grids * n_grids, doubles = 2 * static_cast<size_t>(num_pes) * num_pes * plane;
 		GPLE_CALL(ctx);
+		if (!pes_resolve(ctx, num_pes, model, &pes)) return GPLE_ERR_BAD_ARG; // under the call lock, which gple_pes_undefine takes: the table outlives the enqueue
 		hipStream_t st = ctx->stream;
 		Staged xs(ctx, dev), pp(ctx, dev), r(ctx, dev);
 		Scratch tables(ctx), tr(ctx);
-		GPLE_TRY(mqcl_tables(ctx, st, num_pes, model, x, n, dt / 2.0, true, xs, tables));
+		GPLE_TRY(mqcl_tables(ctx, st, num_pes, pes, x, n, dt / 2.0, true, xs, tables));
 		GPLE_HIP(ctx, tr.get(2 * plane * (num_pes * (num_pes + 1) / 2)));
 		GPLE_HIP(ctx, pp.in(p, n_grids));
 		GPLE_HIP(ctx, r.inout(rho, doubles));
@@ -345,7 +350,8 @@ extern "C"
 	int gple_mqcl_observe(gple_ctx* ctx, int num_pes, int model, const double* x, const double* p, size_t n_grids, double mass, double dx, double dp,
 		unsigned flags, const double* rho_dia, double* rho_adia, double* averages, double* populations)
 	{
-		if (!ctx || !mqcl_size_ok(num_pes, model, n_grids) || !x || !p || !rho_dia || !averages || !populations || !(mass > 0.0) || !std::isfinite(mass) ||
+		PesModel pes;
+		if (!ctx || !mqcl_size_ok(ctx, num_pes, model, n_grids, &pes) || !x || !p || !rho_dia || !averages || !populations || !(mass > 0.0) || !std::isfinite(mass) ||
 			!std::isfinite(dx) || !std::isfinite(dp))
 			return GPLE_ERR_BAD_ARG;
 		GPLE_OPEN(ctx);
@@ -353,10 +359,11 @@ extern "C"
 		const int n = static_cast<int>(n_grids);
 		const size_t doubles = 2 * static_cast<size_t>(num_pes) * num_pes * n_grids * n_grids;
 		GPLE_CALL(ctx);
+		if (!pes_resolve(ctx, num_pes, model, &pes)) return GPLE_ERR_BAD_ARG; // under the call lock, which gple_pes_undefine takes: the table outlives the enqueue
 		hipStream_t st = ctx->stream;
 		Staged xs(ctx, dev), pp(ctx, dev), r(ctx, dev), a(ctx, dev);
 		Scratch tables(ctx), work(ctx), outd(ctx);
-		GPLE_TRY(mqcl_tables(ctx, st, num_pes, model, x, n, 0.0, false, xs, tables));
+		GPLE_TRY(mqcl_tables(ctx, st, num_pes, pes, x, n, 0.0, false, xs, tables));
 		GPLE_HIP(ctx, pp.in(p, n_grids));
 		GPLE_HIP(ctx, r.in(rho_dia, doubles));
 		GPLE_HIP(ctx, a.out(rho_adia, doubles));

@@ -7,7 +7,6 @@
 
 namespace
 {
-	bool recon_model_ok(int num_pes, int model) { return (num_pes == 2 || num_pes == 3) && model >= 0 && model <= (num_pes == 3 ? 3 : 2); }
 	bool recon_grid_ok(size_t nx, size_t np) { return nx >= 2 && np >= 2 && nx <= (1u << 16) && np <= (1u << 16); }
 	bool finite4(const double* x) { return std::isfinite(x[0]) && std::isfinite(x[1]) && std::isfinite(x[2]) && std::isfinite(x[3]); }
 	bool finite5(const double* x) { return finite4(x) && std::isfinite(x[4]); }
@@ -71,7 +70,8 @@ namespace
 	int grid_reconstruct(gple_ctx* ctx, int num_pes, int model, const double* rho, const double* x, size_t nx, const double* p, size_t np, double mass,
 		double dx, double dp, const PlaneIn* planes, bool cross, const double* scale, unsigned flags, double* pred, double* sums)
 	{
-		if (!ctx || !recon_model_ok(num_pes, model) || !recon_grid_ok(nx, np) || !rho || !x || !p || !planes || !sums || !(mass > 0.0) || !std::isfinite(mass) ||
+		PesModel pes;
+		if (!ctx || !pes_resolve(ctx, num_pes, model, &pes) || !recon_grid_ok(nx, np) || !rho || !x || !p || !planes || !sums || !(mass > 0.0) || !std::isfinite(mass) ||
 			!std::isfinite(dx) || !std::isfinite(dp))
 			return GPLE_ERR_BAD_ARG;
 		const int nplanes = num_pes * num_pes;
@@ -84,6 +84,7 @@ namespace
 		const bool dev = flags & GPLE_IO_DEVICE;
 		const size_t cells = nx * np;
 		GPLE_CALL(ctx);
+		if (!pes_resolve(ctx, num_pes, model, &pes)) return GPLE_ERR_BAD_ARG; // under the call lock, which gple_pes_undefine takes: the table outlives the enqueue
 		hipStream_t st = ctx->stream;
 		Staged r(ctx, dev), xs(ctx, dev), ps(ctx, dev), po(ctx, dev), so(ctx, dev);
 		std::vector<std::unique_ptr<Staged>> held;
@@ -94,7 +95,7 @@ namespace
 		GPLE_HIP(ctx, po.out(pred, nplanes * cells));
 		GPLE_HIP(ctx, so.out(sums, static_cast<size_t>(GPLE_RECON_SUMS) * nplanes));
 		ReconArgs g{};
-		g.num_pes = num_pes, g.model = model, g.nx = static_cast<int>(nx), g.np = static_cast<int>(np);
+		g.num_pes = num_pes, g.model = pes, g.nx = static_cast<int>(nx), g.np = static_cast<int>(np);
 		g.rows_x = static_cast<int>(round_up(nx, 64)), g.rows_p = static_cast<int>(round_up(np, 64));
 		g.rho = r.p, g.x = xs.p, g.p = ps.p, g.pred = po.p, g.sums = so.p, g.mass = mass, g.dxdp = dx * dp;
 		size_t table_doubles = 0;
@@ -164,13 +165,15 @@ extern "C"
 	int gple_grid_survey(gple_ctx* ctx, int num_pes, int model, const double* rho, const double* x, size_t nx, const double* p, size_t np, double mass,
 		double dx, double dp, unsigned flags, double* out)
 	{
-		if (!ctx || !recon_model_ok(num_pes, model) || !recon_grid_ok(nx, np) || !rho || !x || !p || !out || !(mass > 0.0) || !std::isfinite(mass) ||
+		PesModel pes;
+		if (!ctx || !pes_resolve(ctx, num_pes, model, &pes) || !recon_grid_ok(nx, np) || !rho || !x || !p || !out || !(mass > 0.0) || !std::isfinite(mass) ||
 			!std::isfinite(dx) || !std::isfinite(dp))
 			return GPLE_ERR_BAD_ARG;
 		GPLE_OPEN(ctx);
 		const bool dev = flags & GPLE_IO_DEVICE;
 		const size_t planes = static_cast<size_t>(num_pes) * num_pes;
 		GPLE_CALL(ctx);
+		if (!pes_resolve(ctx, num_pes, model, &pes)) return GPLE_ERR_BAD_ARG; // under the call lock, which gple_pes_undefine takes: the table outlives the enqueue
 		hipStream_t st = ctx->stream;
 		Staged r(ctx, dev), xs(ctx, dev), ps(ctx, dev), o(ctx, dev);
 		Scratch work(ctx);
@@ -180,7 +183,7 @@ extern "C"
 		GPLE_HIP(ctx, o.out(out, GPLE_SURVEY_STRIDE * planes));
 		GPLE_HIP(ctx, work.get(recon_survey_work_doubles(num_pes)));
 		timer_start(ctx, GPLE_TIMER_RECON);
-		GPLE_HIP(ctx, launch_recon_survey(st, num_pes, model, r.p, xs.p, static_cast<int>(nx), ps.p, static_cast<int>(np), mass, dx * dp, work.p, o.p));
+		GPLE_HIP(ctx, launch_recon_survey(st, num_pes, pes, r.p, xs.p, static_cast<int>(nx), ps.p, static_cast<int>(np), mass, dx * dp, work.p, o.p));
 		timer_stop(ctx, GPLE_TIMER_RECON);
 		GPLE_HIP(ctx, o.back());
 		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));

@@ -99,25 +99,114 @@ extern "C"
 	 * packing order (0,0), (1,0), (1,1), (2,0), (2,1), (2,2) */
 	int gple_pes_adiabatic_n(gple_ctx* ctx, int num_pes, int model, const double* x, size_t M, unsigned flags, double* out)
 	{
-		if (!ctx || (num_pes != 2 && num_pes != 3) || model < 0 || model > (num_pes == 3 ? 3 : 2) || (M && (!x || !out)) || M > (1u << 28)) return GPLE_ERR_BAD_ARG;
+		PesModel pes;
+		if (!ctx || !pes_resolve(ctx, num_pes, model, &pes) || (M && (!x || !out)) || M > (1u << 28)) return GPLE_ERR_BAD_ARG;
 		GPLE_OPEN(ctx);
 		if (M == 0) return GPLE_OK;
 		const bool dev = flags & GPLE_IO_DEVICE;
 		const size_t width = static_cast<size_t>(num_pes) + 2 * static_cast<size_t>(num_pes * (num_pes + 1) / 2);
 		GPLE_CALL(ctx);
+		if (!pes_resolve(ctx, num_pes, model, &pes)) return GPLE_ERR_BAD_ARG; // under the call lock, which gple_pes_undefine takes: the table outlives the enqueue
 		Staged xd(ctx, dev), od(ctx, dev);
 		GPLE_HIP(ctx, xd.in(x, M));
 		GPLE_HIP(ctx, od.out(out, width * M));
-		GPLE_HIP(ctx, launch_pes_n(ctx->stream, num_pes, xd.p, static_cast<int>(M), model, od.p));
+		GPLE_HIP(ctx, launch_pes_n(ctx->stream, num_pes, xd.p, static_cast<int>(M), pes, od.p));
 		GPLE_HIP(ctx, od.back());
+		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+		return GPLE_OK;
+	}
+
+	/* ---- user potentials: a table of V and dV/dx on a uniform grid, registered on the context under an id >= GPLE_PES_USER ---- */
+	int gple_pes_define(gple_ctx* ctx, int num_pes, double x_first, double dx, size_t n, const double* V, const double* dV, unsigned flags, int* model)
+	{
+		if (!ctx || (num_pes != 2 && num_pes != 3) || n < 2 || n > (size_t(1) << 20) || !std::isfinite(dx) || !(dx > 0.0) || !std::isfinite(x_first) || !V ||
+			!dV || !model)
+			return GPLE_ERR_BAD_ARG;
+		GPLE_OPEN(ctx);
+		GPLE_CALL(ctx);
+		{
+			std::lock_guard<std::mutex> lk(ctx->pes_mu);
+			bool room = false;
+			for (const auto& slot : ctx->pes) room = room || !slot.table;
+			if (!room) return GPLE_ERR_BAD_ARG;
+		}
+		const bool dev = flags & GPLE_IO_DEVICE;
+		const size_t entries = n * static_cast<size_t>(num_pes * num_pes);
+		hipStream_t st = ctx->stream;
+		Staged vs(ctx, dev), ds(ctx, dev);
+		Scratch bad(ctx);
+		GPLE_HIP(ctx, vs.in(V, entries));
+		GPLE_HIP(ctx, ds.in(dV, entries));
+		GPLE_HIP(ctx, bad.get(1));
+		GPLE_HIP(ctx, hipMemsetAsync(bad.p, 0, sizeof(double), st));
+		double* table = nullptr;
+		GPLE_HIP(ctx, hipMalloc(&table, PES_TABLE_PLANES * entries * sizeof(double)));
+		int found = 0;
+		hipError_t e = launch_pes_table_build(st, num_pes, vs.p, ds.p, n, dx, table, reinterpret_cast<int*>(bad.p));
+		if (e == hipSuccess) e = hipMemcpyAsync(&found, bad.p, sizeof(int), hipMemcpyDeviceToHost, st);
+		if (e == hipSuccess) e = hipStreamSynchronize(st);
+		if (e != hipSuccess || found)
+		{
+			(void)hipFree(table);
+			if (e != hipSuccess) GPLE_HIP(ctx, e);
+			return GPLE_ERR_BAD_ARG; // a non-finite entry or an asymmetric matrix
+		}
+		std::lock_guard<std::mutex> lk(ctx->pes_mu);
+		for (int k = 0; k < gple_ctx::PES_SLOTS; ++k)
+		{
+			gple_ctx::PesSlot& slot = ctx->pes[k];
+			if (slot.table) continue;
+			slot.table = table, slot.num_pes = num_pes, slot.n = static_cast<int>(n), slot.x_first = x_first, slot.dx = dx;
+			*model = GPLE_PES_USER + k;
+			return GPLE_OK;
+		}
+		(void)hipFree(table); // (unreachable: defines hold the call lock, and only they fill slots)
+		return GPLE_ERR_BAD_ARG;
+	}
+
+	int gple_pes_undefine(gple_ctx* ctx, int model)
+	{
+		if (!ctx || model < GPLE_PES_USER || model >= GPLE_PES_USER + gple_ctx::PES_SLOTS) return GPLE_ERR_BAD_ARG;
+		GPLE_OPEN(ctx);
+		GPLE_CALL(ctx);
+		double* table = nullptr;
+		{
+			std::lock_guard<std::mutex> lk(ctx->pes_mu);
+			gple_ctx::PesSlot& slot = ctx->pes[model - GPLE_PES_USER];
+			if (!slot.table) return GPLE_ERR_BAD_ARG;
+			table = slot.table;
+			slot = gple_ctx::PesSlot();
+		}
+		GPLE_HIP(ctx, hipStreamSynchronize(ctx->stream)); // enqueued kernels may still read the table
+		GPLE_HIP(ctx, hipFree(table));
+		return GPLE_OK;
+	}
+
+	int gple_pes_diabatic_n(gple_ctx* ctx, int num_pes, int model, const double* x, size_t M, unsigned flags, double* V, double* F)
+	{
+		PesModel pes;
+		if (!ctx || !pes_resolve(ctx, num_pes, model, &pes) || (M && (!x || !V || !F)) || M > (1u << 28)) return GPLE_ERR_BAD_ARG;
+		GPLE_OPEN(ctx);
+		if (M == 0) return GPLE_OK;
+		const bool dev = flags & GPLE_IO_DEVICE;
+		const size_t width = static_cast<size_t>(num_pes * num_pes);
+		GPLE_CALL(ctx);
+		if (!pes_resolve(ctx, num_pes, model, &pes)) return GPLE_ERR_BAD_ARG; // under the call lock, which gple_pes_undefine takes: the table outlives the enqueue
+		Staged xd(ctx, dev), vd(ctx, dev), fd(ctx, dev);
+		GPLE_HIP(ctx, xd.in(x, M));
+		GPLE_HIP(ctx, vd.out(V, width * M));
+		GPLE_HIP(ctx, fd.out(F, width * M));
+		GPLE_HIP(ctx, launch_pes_diabatic_n(ctx->stream, num_pes, xd.p, static_cast<int>(M), pes, vd.p, fd.p));
+		GPLE_HIP(ctx, vd.back());
+		GPLE_HIP(ctx, fd.back());
 		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(ctx->stream));
 		return GPLE_OK;
 	}
 
 	int gple_evolve_n(gple_ctx* ctx, int num_pes, const gple_element* elements, int pes_model, double mass, double dt, gple_points* density, unsigned flags)
 	{
-		if (!ctx || !elements || !density || (num_pes != 2 && num_pes != 3) || pes_model < 0 || pes_model > (num_pes == 3 ? 3 : 2) || !(mass > 0.0))
-			return GPLE_ERR_BAD_ARG;
+		PesModel pes;
+		if (!ctx || !elements || !density || !pes_resolve(ctx, num_pes, pes_model, &pes) || !(mass > 0.0)) return GPLE_ERR_BAD_ARG;
 		GPLE_OPEN(ctx);
 		const int NE = num_pes * (num_pes + 1) / 2;
 		int n[6] = {0, 0, 0, 0, 0, 0}, off[6];
@@ -144,6 +233,7 @@ extern "C"
 		double* qp[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 		{
 			GPLE_CALL(ctx);
+			if (!pes_resolve(ctx, num_pes, pes_model, &pes)) return GPLE_ERR_BAD_ARG; // under the call lock, which gple_pes_undefine takes: the table outlives the enqueue
 			GPLE_HIP(ctx, r_old.get(2 * total));
 			GPLE_HIP(ctx, rho_old.get(2 * total));
 			GPLE_HIP(ctx, r_new.get(2 * total));
@@ -157,7 +247,7 @@ extern "C"
 				GPLE_HIP(ctx, copy_in(st, r_old.p + 2 * off[e], density[e].r, 2 * density[e].n, dev));
 				GPLE_HIP(ctx, copy_in(st, rho_old.p + 2 * off[e], density[e].rho, 2 * density[e].n, dev));
 			}
-			GPLE_HIP(ctx, launch_evolve_prepare_n(st, num_pes, r_old.p, n, mass, dt, pes_model, r_new.p, qp, new_points));
+			GPLE_HIP(ctx, launch_evolve_prepare_n(st, num_pes, r_old.p, n, mass, dt, pes, r_new.p, qp, new_points));
 		}
 		// one batched predict per density-matrix element over everything that was back-propagated into it
 		const double* pred[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -168,7 +258,8 @@ extern "C"
 			pred[e] = pr[e]->p;
 		}
 		GPLE_CALL(ctx);
-		GPLE_HIP(ctx, launch_evolve_combine_n(st, num_pes, r_new.p, rho_old.p, n, mass, dt, pes_model, pred, rho_new.p, new_points));
+		if (!pes_resolve(ctx, num_pes, pes_model, &pes)) return GPLE_ERR_BAD_ARG; // under the call lock, which gple_pes_undefine takes: the table outlives the enqueue
+		GPLE_HIP(ctx, launch_evolve_combine_n(st, num_pes, r_new.p, rho_old.p, n, mass, dt, pes, pred, rho_new.p, new_points));
 		for (int e = 0; e < NE; ++e)
 		{
 			GPLE_HIP(ctx, copy_out(st, density[e].r, r_new.p + 2 * off[e], 2 * density[e].n, dev));

@@ -31,8 +31,8 @@ namespace gple
 		__device__ __forceinline__ double pow_minus_one(long n) { return n % 2 == 0 ? 1.0 : -1.0; } // general.cpp:38-41
 
 		// one thread per entry (r, c) of the row-major dim x dim matrix (symmetric, so column-major reads the same)
-		template <int NP>
-		__global__ void __launch_bounds__(256) dvr_hamiltonian_kernel(int model, int boundary, double x_first, double dx, int n, double mass, double* __restrict__ H)
+		template <int NP, typename PES>
+		__global__ void __launch_bounds__(256) dvr_hamiltonian_kernel(PES model, int boundary, double x_first, double dx, int n, double mass, double* __restrict__ H)
 		{
 #pragma clang fp contract(off)
 			const long dim = static_cast<long>(NP) * n;
@@ -81,8 +81,8 @@ namespace gple
 		}
 
 		// basis[(a NP + row) NP + col] = C(row, col), columns = adiabatic states
-		template <int NP>
-		__global__ void __launch_bounds__(128) dvr_states_kernel(int model, double x_first, double dx, int n, double* __restrict__ basis)
+		template <int NP, typename PES>
+		__global__ void __launch_bounds__(128) dvr_states_kernel(PES model, double x_first, double dx, int n, double* __restrict__ basis)
 		{
 			const int a = blockIdx.x * 128 + threadIdx.x;
 			if (a >= n) return;
@@ -403,18 +403,18 @@ namespace gple
 		}
 	} // namespace
 
-	hipError_t launch_dvr_hamiltonian(hipStream_t s, int num_pes, int model, int boundary, double x_first, double dx, int n, double mass, double* H)
+	hipError_t launch_dvr_hamiltonian(hipStream_t s, int num_pes, PesModel model, int boundary, double x_first, double dx, int n, double mass, double* H)
 	{
 		const long dim = static_cast<long>(num_pes) * n;
 		const dim3 grid(static_cast<unsigned>((dim + 255) / 256), static_cast<unsigned>(dim));
-		if (num_pes == 2) hipLaunchKernelGGL(dvr_hamiltonian_kernel<2>, grid, dim3(256), 0, s, model, boundary, x_first, dx, n, mass, H);
-		else if (num_pes == 3) hipLaunchKernelGGL(dvr_hamiltonian_kernel<3>, grid, dim3(256), 0, s, model, boundary, x_first, dx, n, mass, H);
+		if (num_pes == 2) with_model(model, [&](auto m) { hipLaunchKernelGGL((dvr_hamiltonian_kernel<2, decltype(m)>), grid, dim3(256), 0, s, m, boundary, x_first, dx, n, mass, H); });
+		else if (num_pes == 3) with_model(model, [&](auto m) { hipLaunchKernelGGL((dvr_hamiltonian_kernel<3, decltype(m)>), grid, dim3(256), 0, s, m, boundary, x_first, dx, n, mass, H); });
 		else return hipErrorInvalidValue;
 		return hipGetLastError();
 	}
 	size_t dvr_states_work_doubles(int num_pes, int n) { return static_cast<size_t>(n) * (1 + num_pes + num_pes * (num_pes + 1)); }
 	// energies: the adiabatic energies of gple_pes_adiabatic_n's own kernel at the grid points (the same bits); basis from the same device functions
-	hipError_t launch_dvr_states(hipStream_t s, int num_pes, int model, double x_first, double dx, int n, double* energies, double* basis, double* work)
+	hipError_t launch_dvr_states(hipStream_t s, int num_pes, PesModel model, double x_first, double dx, int n, double* energies, double* basis, double* work)
 	{
 		if (num_pes != 2 && num_pes != 3) return hipErrorInvalidValue;
 		if (energies)
@@ -429,8 +429,8 @@ namespace gple
 		if (basis)
 		{
 			const dim3 grid((n + 127) / 128);
-			if (num_pes == 2) hipLaunchKernelGGL(dvr_states_kernel<2>, grid, dim3(128), 0, s, model, x_first, dx, n, basis);
-			else hipLaunchKernelGGL(dvr_states_kernel<3>, grid, dim3(128), 0, s, model, x_first, dx, n, basis);
+			if (num_pes == 2) with_model(model, [&](auto m) { hipLaunchKernelGGL((dvr_states_kernel<2, decltype(m)>), grid, dim3(128), 0, s, m, x_first, dx, n, basis); });
+			else with_model(model, [&](auto m) { hipLaunchKernelGGL((dvr_states_kernel<3, decltype(m)>), grid, dim3(128), 0, s, m, x_first, dx, n, basis); });
 		}
 		return hipGetLastError();
 	}

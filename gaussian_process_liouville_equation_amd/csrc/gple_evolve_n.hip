@@ -30,8 +30,8 @@ namespace gple
 		};
 
 		// pes.cpp:73-155 for NP levels
-		template <int NP>
-		__device__ __forceinline__ void adiabatic_n(double x, int model, AdiaN<NP>& out)
+		template <int NP, typename PES>
+		__device__ __forceinline__ void adiabatic_n(double x, const PES& model, AdiaN<NP>& out)
 		{
 			Mat<NP> V, Fd, C;
 			diabatic_n<NP>(x, model, V, Fd);
@@ -138,8 +138,8 @@ namespace gple
 			matmul<NP>(O, Rim, T), matmul<NP>(T, Ot, Rim);
 		}
 
-		template <int NP>
-		__device__ __forceinline__ void adiabatic_evolve_n(double& x, double& p, double mass, double dt, double drc, int row, int col, int model)
+		template <int NP, typename PES>
+		__device__ __forceinline__ void adiabatic_evolve_n(double& x, double& p, double mass, double dt, double drc, int row, int col, const PES& model)
 		{
 			x += drc * dt / 2.0 * (p / mass);
 			AdiaN<NP> a;
@@ -183,8 +183,8 @@ namespace gple
 			Mat<NP> W;
 			AdiaN<NP> at2;
 		};
-		template <int NP>
-		__device__ __forceinline__ void back_n(double x0, double p0, double mass, double dt, int row, int col, int model, BackN<NP>& g)
+		template <int NP, typename PES>
+		__device__ __forceinline__ void back_n(double x0, double p0, double mass, double dt, int row, int col, const PES& model, BackN<NP>& g)
 		{
 			g.x2 = x0, g.p1 = p0;
 			adiabatic_evolve_n<NP>(g.x2, g.p1, mass, dt / 2.0, -1.0, row, col, model);
@@ -201,8 +201,8 @@ namespace gple
 		}
 
 		// One thread per sample point: forward propagation (two half steps), the NE x NE back-propagated points into the query lists
-		template <int NP>
-		__global__ void __launch_bounds__(128) evolve_prepare_n_kernel(const double* __restrict__ r, LayoutN<NP> L, double mass, double dt, int model,
+		template <int NP, typename PES>
+		__global__ void __launch_bounds__(128) evolve_prepare_n_kernel(const double* __restrict__ r, LayoutN<NP> L, double mass, double dt, PES model,
 			double* __restrict__ r_new, PtrsN q)
 		{
 			constexpr int NE = NP * (NP + 1) / 2;
@@ -241,9 +241,9 @@ namespace gple
 
 		// One thread per sample point: the predicted densities at its back-propagated points -> the density at its new position.
 		// pred[e]: plain doubles for a diagonal element, (re, im) pairs for an off-diagonal one, nullptr for an element without a kernel
-		template <int NP>
+		template <int NP, typename PES>
 		__global__ void __launch_bounds__(128) evolve_combine_n_kernel(const double* __restrict__ r_new, const double* __restrict__ rho_old, LayoutN<NP> L,
-			double mass, double dt, int model, PtrsN pred, double* __restrict__ rho_new)
+			double mass, double dt, PES model, PtrsN pred, double* __restrict__ rho_new)
 		{
 			constexpr int NE = NP * (NP + 1) / 2;
 			const int t = blockIdx.x * 128 + threadIdx.x;
@@ -346,8 +346,8 @@ namespace gple
 		}
 
 		// adiabatic quantities at M positions: out[(NP + 2 NE) i + ...] = E (NP), F lower-packed (NE), NAC lower-packed (NE: NAC(j, k), j >= k)
-		template <int NP>
-		__global__ void __launch_bounds__(128) pes_n_kernel(const double* __restrict__ x, int M, int model, double* __restrict__ out)
+		template <int NP, typename PES>
+		__global__ void __launch_bounds__(128) pes_n_kernel(const double* __restrict__ x, int M, PES model, double* __restrict__ out)
 		{
 			constexpr int NE = NP * (NP + 1) / 2, W = NP + 2 * NE;
 			const int i = blockIdx.x * 128 + threadIdx.x;
@@ -362,6 +362,38 @@ namespace gple
 			for (int k = 0; k < NP; ++k)
 #pragma unroll
 				for (int l = 0; l <= k; ++l, ++e) o[NP + e] = a.F.a[k][l], o[NP + NE + e] = a.NAC.a[k][l];
+		}
+
+		// the diabatic matrix and force at M positions: V[NP^2 i + NP r + c], F likewise
+		template <int NP, typename PES>
+		__global__ void __launch_bounds__(128) pes_diabatic_n_kernel(const double* __restrict__ x, int M, PES model, double* __restrict__ V, double* __restrict__ F)
+		{
+			const int i = blockIdx.x * 128 + threadIdx.x;
+			if (i >= M) return;
+			Mat<NP> v, f;
+			diabatic_n<NP>(x[i], model, v, f);
+			const long o = static_cast<long>(NP * NP) * i;
+#pragma unroll
+			for (int r = 0; r < NP; ++r)
+#pragma unroll
+				for (int c = 0; c < NP; ++c) V[o + NP * r + c] = v.a[r][c], F[o + NP * r + c] = f.a[r][c];
+		}
+
+		// One thread per entry of a user model's table: node k of dst = V_k | V'_k | dx V'_k; *bad is set where an entry (dx V' included) is not
+		// finite or differs from its transpose
+		__global__ void __launch_bounds__(256) pes_table_build_kernel(int np, const double* __restrict__ V, const double* __restrict__ dV, long entries, double dx,
+			double* __restrict__ dst, int* __restrict__ bad)
+		{
+			const long t = static_cast<long>(blockIdx.x) * 256 + threadIdx.x;
+			if (t >= entries) return;
+			const int S = np * np;
+			const long k = t / S;
+			const int e = static_cast<int>(t - k * S), r = e / np, c = e - r * np;
+			const long mirror = k * S + c * np + r;
+			const double v = V[t], d = dV[t], m = dx * d;
+			if (!isfinite(v) || !isfinite(d) || !isfinite(m) || V[mirror] != v || dV[mirror] != d) *bad = 1;
+			double* node = dst + k * (PES_TABLE_PLANES * S);
+			node[e] = v, node[S + e] = d, node[2 * S + e] = m;
 		}
 
 		template <int NP>
@@ -380,12 +412,27 @@ namespace gple
 		}
 	} // namespace
 
-	hipError_t launch_pes_n(hipStream_t s, int num_pes, const double* x, int M, int model, double* out)
+	hipError_t launch_pes_n(hipStream_t s, int num_pes, const double* x, int M, PesModel model, double* out)
 	{
 		if (M == 0) return hipSuccess;
-		if (num_pes == 2) hipLaunchKernelGGL(pes_n_kernel<2>, dim3((M + 127) / 128), dim3(128), 0, s, x, M, model, out);
-		else if (num_pes == 3) hipLaunchKernelGGL(pes_n_kernel<3>, dim3((M + 127) / 128), dim3(128), 0, s, x, M, model, out);
+		if (num_pes == 2) with_model(model, [&](auto m) { hipLaunchKernelGGL((pes_n_kernel<2, decltype(m)>), dim3((M + 127) / 128), dim3(128), 0, s, x, M, m, out); });
+		else if (num_pes == 3) with_model(model, [&](auto m) { hipLaunchKernelGGL((pes_n_kernel<3, decltype(m)>), dim3((M + 127) / 128), dim3(128), 0, s, x, M, m, out); });
 		else return hipErrorInvalidValue;
+		return hipGetLastError();
+	}
+	hipError_t launch_pes_diabatic_n(hipStream_t s, int num_pes, const double* x, int M, PesModel model, double* V, double* F)
+	{
+		if (M == 0) return hipSuccess;
+		if (num_pes == 2) with_model(model, [&](auto m) { hipLaunchKernelGGL((pes_diabatic_n_kernel<2, decltype(m)>), dim3((M + 127) / 128), dim3(128), 0, s, x, M, m, V, F); });
+		else if (num_pes == 3) with_model(model, [&](auto m) { hipLaunchKernelGGL((pes_diabatic_n_kernel<3, decltype(m)>), dim3((M + 127) / 128), dim3(128), 0, s, x, M, m, V, F); });
+		else return hipErrorInvalidValue;
+		return hipGetLastError();
+	}
+	hipError_t launch_pes_table_build(hipStream_t s, int num_pes, const double* V, const double* dV, size_t n, double dx, double* dst, int* bad)
+	{
+		const long entries = static_cast<long>(n) * num_pes * num_pes;
+		if (entries == 0) return hipSuccess;
+		hipLaunchKernelGGL(pes_table_build_kernel, dim3(static_cast<unsigned>((entries + 255) / 256)), dim3(256), 0, s, num_pes, V, dV, entries, dx, dst, bad);
 		return hipGetLastError();
 	}
 	void evolve_layout_n(int num_pes, const int* n, long* qlen)
@@ -395,7 +442,7 @@ namespace gple
 		for (int s = 0; s < NE; ++s) total += static_cast<long>(NE) * n[s];
 		for (int e = 0; e < NE; ++e) qlen[e] = total; // every element is asked at every branch of every point
 	}
-	hipError_t launch_evolve_prepare_n(hipStream_t s, int num_pes, const double* r, const int* n, double mass, double dt, int model, double* r_new,
+	hipError_t launch_evolve_prepare_n(hipStream_t s, int num_pes, const double* r, const int* n, double mass, double dt, PesModel model, double* r_new,
 		double* const* q, int new_points)
 	{
 		long qlen[6];
@@ -406,19 +453,19 @@ namespace gple
 			LayoutN<2> L;
 			fill_layout<2>(n, new_points, L, qlen);
 			const int total = L.off[2] + L.n[2];
-			if (total) hipLaunchKernelGGL(evolve_prepare_n_kernel<2>, dim3((total + 127) / 128), dim3(128), 0, s, r, L, mass, dt, model, r_new, q_dev);
+			if (total) with_model(model, [&](auto m) { hipLaunchKernelGGL((evolve_prepare_n_kernel<2, decltype(m)>), dim3((total + 127) / 128), dim3(128), 0, s, r, L, mass, dt, m, r_new, q_dev); });
 		}
 		else if (num_pes == 3)
 		{
 			LayoutN<3> L;
 			fill_layout<3>(n, new_points, L, qlen);
 			const int total = L.off[5] + L.n[5];
-			if (total) hipLaunchKernelGGL(evolve_prepare_n_kernel<3>, dim3((total + 127) / 128), dim3(128), 0, s, r, L, mass, dt, model, r_new, q_dev);
+			if (total) with_model(model, [&](auto m) { hipLaunchKernelGGL((evolve_prepare_n_kernel<3, decltype(m)>), dim3((total + 127) / 128), dim3(128), 0, s, r, L, mass, dt, m, r_new, q_dev); });
 		}
 		else return hipErrorInvalidValue;
 		return hipGetLastError();
 	}
-	hipError_t launch_evolve_combine_n(hipStream_t s, int num_pes, const double* r_new, const double* rho_old, const int* n, double mass, double dt, int model,
+	hipError_t launch_evolve_combine_n(hipStream_t s, int num_pes, const double* r_new, const double* rho_old, const int* n, double mass, double dt, PesModel model,
 		const double* const* pred, double* rho_new, int new_points)
 	{
 		long qlen[6];
@@ -429,14 +476,14 @@ namespace gple
 			LayoutN<2> L;
 			fill_layout<2>(n, new_points, L, qlen);
 			const int total = L.off[2] + L.n[2];
-			if (total) hipLaunchKernelGGL(evolve_combine_n_kernel<2>, dim3((total + 127) / 128), dim3(128), 0, s, r_new, rho_old, L, mass, dt, model, pred_dev, rho_new);
+			if (total) with_model(model, [&](auto m) { hipLaunchKernelGGL((evolve_combine_n_kernel<2, decltype(m)>), dim3((total + 127) / 128), dim3(128), 0, s, r_new, rho_old, L, mass, dt, m, pred_dev, rho_new); });
 		}
 		else if (num_pes == 3)
 		{
 			LayoutN<3> L;
 			fill_layout<3>(n, new_points, L, qlen);
 			const int total = L.off[5] + L.n[5];
-			if (total) hipLaunchKernelGGL(evolve_combine_n_kernel<3>, dim3((total + 127) / 128), dim3(128), 0, s, r_new, rho_old, L, mass, dt, model, pred_dev, rho_new);
+			if (total) with_model(model, [&](auto m) { hipLaunchKernelGGL((evolve_combine_n_kernel<3, decltype(m)>), dim3((total + 127) / 128), dim3(128), 0, s, r_new, rho_old, L, mass, dt, m, pred_dev, rho_new); });
 		}
 		else return hipErrorInvalidValue;
 		return hipGetLastError();

@@ -255,20 +255,36 @@ namespace gple
 	// complex finish: rows [0,M) real part, rows [m_split, m_split+M) imaginary part
 	hipError_t launch_predict_finish_complex(hipStream_t s, const double* q, const double* mu, int M, int m_split, double self,
 		const double* s_dev, const double* labels, double* mean, double* var, double* cut, double* err_out);
+	// ---- the potential a kernel evaluates (gple_pes_n.h): a built-in id (table == nullptr), or a user model of the context's registry with its
+	// table in device memory: per node V | V' | dx V' (PES_TABLE_PLANES planes of num_pes^2 doubles, row-major), nodes at x_first + dx k, k < n.
+	// Passed by value into the kernels; a built-in id converts implicitly, so the launchers below take either
+	constexpr int PES_TABLE_PLANES = 3;
+	struct PesModel
+	{
+		int id, n;
+		const double* table;
+		double x_first, dx;
+		__host__ __device__ PesModel(int builtin = 0): id(builtin), n(0), table(nullptr), x_first(0.0), dx(1.0) {}
+	};
+	// V and F = -V' of the model at M positions, num_pes^2 doubles each per position (gple_pes_diabatic_n)
+	hipError_t launch_pes_diabatic_n(hipStream_t s, int num_pes, const double* x, int M, PesModel model, double* V, double* F);
+	// dst (n nodes of the layout above) from V and dV (n x num_pes^2 each); *bad (an int, zeroed by the caller) becomes non-zero when an entry
+	// is not finite or a matrix not exactly symmetric
+	hipError_t launch_pes_table_build(hipStream_t s, int num_pes, const double* V, const double* dV, size_t n, double dx, double* dst, int* bad);
 	// ---- N-level step loop (gple_evolve_n.hip): NumPES = 2 or 3, elements in the packing order (0,0), (1,0), (1,1), (2,0), ... ----
 	// adiabatic quantities: out[(NP + 2 NE) i + ...] = E (NP) | F lower-packed (NE) | NAC lower-packed (NE)
-	hipError_t launch_pes_n(hipStream_t s, int num_pes, const double* x, int M, int model, double* out);
+	hipError_t launch_pes_n(hipStream_t s, int num_pes, const double* x, int M, PesModel model, double* out);
 	// rows of every element's query list: NE branches of every point of every element
 	void evolve_layout_n(int num_pes, const int* n, long* qlen);
-	hipError_t launch_evolve_prepare_n(hipStream_t s, int num_pes, const double* r, const int* n, double mass, double dt, int model, double* r_new,
+	hipError_t launch_evolve_prepare_n(hipStream_t s, int num_pes, const double* r, const int* n, double mass, double dt, PesModel model, double* r_new,
 		double* const* q, int new_points);
-	hipError_t launch_evolve_combine_n(hipStream_t s, int num_pes, const double* r_new, const double* rho_old, const int* n, double mass, double dt, int model,
+	hipError_t launch_evolve_combine_n(hipStream_t s, int num_pes, const double* r_new, const double* rho_old, const int* n, double mass, double dt, PesModel model,
 		const double* const* pred, double* rho_new, int new_points);
 	// ---- exact DVR dynamics (gple_dvr.hip): num_pes = 2 or 3, dim = num_pes n, boundary = gple_dvr_boundary ---------------------------
 	// H: dim x dim (symmetric); energies: n x num_pes; basis: n x num_pes x num_pes (columns = adiabatic states); either may be null
-	hipError_t launch_dvr_hamiltonian(hipStream_t s, int num_pes, int model, int boundary, double x_first, double dx, int n, double mass, double* H);
+	hipError_t launch_dvr_hamiltonian(hipStream_t s, int num_pes, PesModel model, int boundary, double x_first, double dx, int n, double mass, double* H);
 	size_t dvr_states_work_doubles(int num_pes, int n);
-	hipError_t launch_dvr_states(hipStream_t s, int num_pes, int model, double x_first, double dx, int n, double* energies, double* basis, double* work);
+	hipError_t launch_dvr_states(hipStream_t s, int num_pes, PesModel model, double x_first, double dx, int n, double* energies, double* basis, double* work);
 	// work layout (doubles, ld = dim rounded up to 64): C (ld x ld, row-major, zero padded) | Z, Y (ld x round_up(2T, 64) each) | input (ld x 64:
 	// v = psi0 or c0 (dim (re, im) pairs) split into columns re, im) | c0 (ld x 64).  psi: T x dim (re, im) pairs, adiabatic when basis != null
 	size_t dvr_propagate_work_doubles(int num_pes, int n, int T);
@@ -382,7 +398,7 @@ namespace gple
 	// tables (mqcl_table_doubles): per x C | E | U | lambda | Q phases of one Q(tq), then (spectral) chirp (n), twiddles (M / 2), chirp spectrum (M)
 	int mqcl_fft_length(int n);
 	size_t mqcl_table_doubles(int num_pes, int n);
-	hipError_t launch_mqcl_tables(hipStream_t s, int num_pes, int model, const double* x, int n, double tq, bool spectral, double* tables);
+	hipError_t launch_mqcl_tables(hipStream_t s, int num_pes, PesModel model, const double* x, int n, double tq, bool spectral, double* tables);
 	struct MqclEvolveArgs
 	{
 		int num_pes, n, M;
@@ -406,7 +422,7 @@ namespace gple
 	constexpr int RECON_MAX_PLANES = 9, RECON_MAX_N = 4096, RECON_SUMS = 6;
 	constexpr int RECON_SCAN_CHUNK = 4096; // cells per workgroup of the selection's running sum
 	size_t recon_survey_work_doubles(int num_pes);
-	hipError_t launch_recon_survey(hipStream_t s, int num_pes, int model, const double* rho, const double* x, int nx, const double* p, int np, double mass,
+	hipError_t launch_recon_survey(hipStream_t s, int num_pes, PesModel model, const double* rho, const double* x, int nx, const double* p, int np, double mass,
 		double dxdp, double* work, double* out);
 	// selection: running sum of |v| of plane q (within[c]: inclusive within its chunk; offsets[k]: sum of the chunks before k, offsets[nchunks] = W;
 	// counts[nchunks]: cells of non-zero weight), the draws [k0, k0 + nk) with first-occurrence marking in mark (cells ints, INT_MAX = never drawn),
@@ -440,7 +456,8 @@ namespace gple
 		double* records;
 		double* sums;
 		double mass, dxdp;
-		int num_pes, model, nx, np, rows_x, rows_p;
+		PesModel model;
+		int num_pes, nx, np, rows_x, rows_p;
 	};
 	size_t recon_record_doubles(int num_pes, int nx, int np);
 	hipError_t launch_recon_tables(hipStream_t s, const ReconArgs& g);

@@ -123,8 +123,8 @@ namespace gple
 			}
 		}
 
-		template <int NP>
-		__global__ void __launch_bounds__(128) mqcl_pes_kernel(int model, const double* __restrict__ x, int n, double tq, double* __restrict__ table)
+		template <int NP, typename PES>
+		__global__ void __launch_bounds__(128) mqcl_pes_kernel(PES model, const double* __restrict__ x, int n, double tq, double* __restrict__ table)
 		{
 #pragma clang fp contract(off)
 			const int i = blockIdx.x * 128 + threadIdx.x;
@@ -590,14 +590,14 @@ namespace gple
 		const size_t M = static_cast<size_t>(mqcl_fft_length(n));
 		return static_cast<size_t>(pes_stride(num_pes)) * n + 2 * (static_cast<size_t>(n) + M / 2 + M);
 	}
-	hipError_t launch_mqcl_tables(hipStream_t s, int num_pes, int model, const double* x, int n, double tq, bool spectral, double* tables)
+	hipError_t launch_mqcl_tables(hipStream_t s, int num_pes, PesModel model, const double* x, int n, double tq, bool spectral, double* tables)
 	{
 		const int M = mqcl_fft_length(n);
 		double* chirp = tables + static_cast<size_t>(pes_stride(num_pes)) * n;
 		double* tw = chirp + 2 * static_cast<size_t>(n);
 		double* bhat = tw + M;
-		if (num_pes == 2) hipLaunchKernelGGL(mqcl_pes_kernel<2>, dim3((n + 127) / 128), dim3(128), 0, s, model, x, n, tq, tables);
-		else hipLaunchKernelGGL(mqcl_pes_kernel<3>, dim3((n + 127) / 128), dim3(128), 0, s, model, x, n, tq, tables);
+		if (num_pes == 2) with_model(model, [&](auto m) { hipLaunchKernelGGL((mqcl_pes_kernel<2, decltype(m)>), dim3((n + 127) / 128), dim3(128), 0, s, m, x, n, tq, tables); });
+		else with_model(model, [&](auto m) { hipLaunchKernelGGL((mqcl_pes_kernel<3, decltype(m)>), dim3((n + 127) / 128), dim3(128), 0, s, m, x, n, tq, tables); });
 		if (!spectral) return hipGetLastError();
 		hipLaunchKernelGGL(mqcl_chirp_kernel, dim3((std::max(n, M / 2) + 255) / 256), dim3(256), 0, s, n, M, reinterpret_cast<double2*>(chirp),
 			reinterpret_cast<double2*>(tw));

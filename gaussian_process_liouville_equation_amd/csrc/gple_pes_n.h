@@ -2,8 +2,15 @@
 // the exact DVR dynamics (gple_dvr.hip): pes.cpp's diabatic_potential for models 0-2 (at three levels plus the uncoupled third diabat at
 // V = 0), the three-level TSAC model of this library (model 3), a cyclic Jacobi eigen-solver and the library's sign convention of the
 // adiabatic states (ascending energy, last non-zero component of every eigenvector positive; pes.cpp:73-96 at two levels).
+//
+// A user model (id >= GPLE_PES_USER) is a table on a uniform grid, evaluated by table_diabatic_n: a cubic Hermite interpolant of the
+// diabatic matrix from its values and derivatives at the nodes, continued linearly beyond both ends.  The functions here
+// and the kernels that call them take the model as a type M: int for a built-in id, PesModel (gple_kernels.h) for a table.  Two instantiations,
+// because one that carried both cost the step loop's kernels registers and scratch; with_model picks at the launch.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include "gple_kernels.h"
 
 namespace gple
 {
@@ -13,6 +20,62 @@ namespace gple
 		double a[NP][NP];
 	};
 	__device__ __forceinline__ double sgn_n(double v) { return static_cast<double>((v > 0.0) - (v < 0.0)); }
+
+	// The tabulated model at x: s = (x - x_first) / dx, node k = clamp(floor(s), 0, n - 2), t = s - k, and per entry with m = dx V' and
+	// D = V_{k+1} - V_k:  c2 = 3 D - (2 m_k + m_{k+1}), c3 = (m_k + m_{k+1}) - 2 D,  V = V_k + t (m_k + t (c2 + t c3)),
+	// V' = (m_k + t (2 c2 + 3 t c3)) / dx, F = -V'; for s < 0 and s > n - 1 the tangent at the end node.  At t = 0 the value is the node's
+	// bits.  The node index is clamped as a double, so no x (NaN and infinities included) reads outside the table.
+	template <int NP>
+	__device__ __forceinline__ void table_diabatic_n(double x, const PesModel& pes, Mat<NP>& V, Mat<NP>& F)
+	{
+		constexpr int S = NP * NP, NODE = PES_TABLE_PLANES * S;
+		const double s = (x - pes.x_first) / pes.dx;
+		const double last = static_cast<double>(pes.n - 1);
+		if (s < 0.0 || s > last)
+		{
+			const int k = s < 0.0 ? 0 : pes.n - 1;
+			const double* node = pes.table + static_cast<long>(NODE) * k;
+			const double h = x - (pes.x_first + pes.dx * static_cast<double>(k));
+#pragma unroll
+			for (int i = 0; i < NP; ++i)
+#pragma unroll
+				for (int j = 0; j <= i; ++j)
+				{
+					const double v0 = node[NP * i + j], d0 = node[S + NP * i + j];
+					V.a[i][j] = V.a[j][i] = v0 + d0 * h;
+					F.a[i][j] = F.a[j][i] = -d0;
+				}
+			return;
+		}
+		const double kf = fmin(fmax(floor(s), 0.0), last - 1.0);
+		const double t = s - kf;
+		const double* n0 = pes.table + static_cast<long>(NODE) * static_cast<long>(kf);
+		const double* n1 = n0 + NODE;
+#pragma unroll
+		for (int i = 0; i < NP; ++i)
+#pragma unroll
+			for (int j = 0; j <= i; ++j)
+			{
+				const double v0 = n0[NP * i + j], v1 = n1[NP * i + j], m0 = n0[2 * S + NP * i + j], m1 = n1[2 * S + NP * i + j];
+				const double delta = v1 - v0;
+				const double c2 = 3.0 * delta - (2.0 * m0 + m1), c3 = (m0 + m1) - 2.0 * delta;
+				V.a[i][j] = V.a[j][i] = v0 + t * (m0 + t * (c2 + t * c3));
+				F.a[i][j] = F.a[j][i] = -((m0 + t * (2.0 * c2 + 3.0 * t * c3)) / pes.dx);
+			}
+	}
+
+	template <int NP>
+	__device__ __forceinline__ void diabatic_n(double x, const PesModel& pes, Mat<NP>& V, Mat<NP>& F)
+	{
+		table_diabatic_n<NP>(x, pes, V, F);
+	}
+	// f(model.id) for a built-in model, f(model) for a table: the launchers instantiate their kernel for the type f receives
+	template <typename Fn>
+	void with_model(const PesModel& model, Fn&& f)
+	{
+		if (model.table) f(model);
+		else f(model.id);
+	}
 
 	template <int NP>
 	__device__ __forceinline__ void diabatic_n(double x, int model, Mat<NP>& V, Mat<NP>& F)
@@ -126,8 +189,8 @@ namespace gple
 	}
 	// E (ascending) and the adiabatic states C (columns) of the diabatic potential at x, with the sign convention above; Fd receives the
 	// diabatic force (the caller may ignore it)
-	template <int NP>
-	__device__ __forceinline__ void adiabatic_states_n(double x, int model, double (&E)[NP], Mat<NP>& C, Mat<NP>& Fd)
+	template <int NP, typename PES>
+	__device__ __forceinline__ void adiabatic_states_n(double x, const PES& model, double (&E)[NP], Mat<NP>& C, Mat<NP>& Fd)
 	{
 		Mat<NP> V;
 		diabatic_n<NP>(x, model, V, Fd);

@@ -72,8 +72,8 @@ namespace gple
 		}
 
 		// work[(q SB + blk) 7 + ...] = max, min, sum |v|, first index of max, sum v, sum v E_i(x_a), sum v p_b^2 / 2m  over the rows of block blk
-		template <int NP>
-		__global__ void __launch_bounds__(256) recon_survey_kernel(int model, const double* __restrict__ rho, const double* __restrict__ x, int nx,
+		template <int NP, typename PES>
+		__global__ void __launch_bounds__(256) recon_survey_kernel(PES model, const double* __restrict__ rho, const double* __restrict__ x, int nx,
 			const double* __restrict__ p, int np, double mass, double* __restrict__ work)
 		{
 #pragma clang fp contract(off)
@@ -319,8 +319,8 @@ namespace gple
 			}
 			(which ? P.Ep : P.Ax)[idx] = val;
 		}
-		template <int NP>
-		__global__ void __launch_bounds__(256) recon_energy_kernel(int model, const double* __restrict__ x, int nx, double* __restrict__ energy)
+		template <int NP, typename PES>
+		__global__ void __launch_bounds__(256) recon_energy_kernel(PES model, const double* __restrict__ x, int nx, double* __restrict__ energy)
 		{
 			const int a = blockIdx.x * 256 + threadIdx.x;
 			if (a >= nx) return;
@@ -699,12 +699,12 @@ namespace gple
 	} // namespace
 
 	size_t recon_survey_work_doubles(int num_pes) { return static_cast<size_t>(num_pes) * num_pes * RECON_SURVEY_BLOCKS * RECON_SURVEY_VALUES; }
-	hipError_t launch_recon_survey(hipStream_t s, int num_pes, int model, const double* rho, const double* x, int nx, const double* p, int np, double mass,
+	hipError_t launch_recon_survey(hipStream_t s, int num_pes, PesModel model, const double* rho, const double* x, int nx, const double* p, int np, double mass,
 		double dxdp, double* work, double* out)
 	{
 		const dim3 grid(RECON_SURVEY_BLOCKS, num_pes * (num_pes + 1) / 2);
-		if (num_pes == 2) hipLaunchKernelGGL(recon_survey_kernel<2>, grid, dim3(256), 0, s, model, rho, x, nx, p, np, mass, work);
-		else if (num_pes == 3) hipLaunchKernelGGL(recon_survey_kernel<3>, grid, dim3(256), 0, s, model, rho, x, nx, p, np, mass, work);
+		if (num_pes == 2) with_model(model, [&](auto m) { hipLaunchKernelGGL((recon_survey_kernel<2, decltype(m)>), grid, dim3(256), 0, s, m, rho, x, nx, p, np, mass, work); });
+		else if (num_pes == 3) with_model(model, [&](auto m) { hipLaunchKernelGGL((recon_survey_kernel<3, decltype(m)>), grid, dim3(256), 0, s, m, rho, x, nx, p, np, mass, work); });
 		else return hipErrorInvalidValue;
 		hipLaunchKernelGGL(recon_survey_final_kernel, dim3(1), dim3(64), 0, s, num_pes * num_pes, work, dxdp, out);
 		return hipGetLastError();
@@ -742,8 +742,8 @@ namespace gple
 	}
 	hipError_t launch_recon_energy(hipStream_t s, const ReconArgs& g)
 	{
-		if (g.num_pes == 2) hipLaunchKernelGGL(recon_energy_kernel<2>, dim3((g.nx + 255) / 256), dim3(256), 0, s, g.model, g.x, g.nx, g.energy);
-		else if (g.num_pes == 3) hipLaunchKernelGGL(recon_energy_kernel<3>, dim3((g.nx + 255) / 256), dim3(256), 0, s, g.model, g.x, g.nx, g.energy);
+		if (g.num_pes == 2) with_model(g.model, [&](auto m) { hipLaunchKernelGGL((recon_energy_kernel<2, decltype(m)>), dim3((g.nx + 255) / 256), dim3(256), 0, s, m, g.x, g.nx, g.energy); });
+		else if (g.num_pes == 3) with_model(g.model, [&](auto m) { hipLaunchKernelGGL((recon_energy_kernel<3, decltype(m)>), dim3((g.nx + 255) / 256), dim3(256), 0, s, m, g.x, g.nx, g.energy); });
 		else return hipErrorInvalidValue;
 		return hipGetLastError();
 	}

@@ -134,6 +134,11 @@ def tully_potential(api, model):
     return lambda x, iPES: api.pes_adiabatic(model, x)[:, iPES]
 
 
+def model_potential(api, num_pes, model):
+    """the same for any model of num_pes levels, user potentials (Api.pes_define) included, through gple_pes_adiabatic_n"""
+    return lambda x, iPES: api.pes_adiabatic_n(num_pes, model, x)[0][:, iPES]
+
+
 def output_average(os, AllKernels, density, mass, PurityFactor, potential=None):
     """output.cpp:24-118: one line per output tick of ave.txt — per surface (population, <x>, <p>, NaN) from the kernels'
     analytic integrals and (population, <x>, <p>, <E>) from the Monte-Carlo points; the same summed over surfaces; the purity

@@ -23,6 +23,7 @@ from . import kernels as K
 
 SAC, DAC, ECR = 0, 1, 2  # pes.h:27-32; TestModel defaults to DAC (pes.h:38-41)
 TSAC = 3  # three-state avoided crossings: this library's three-level model (num_pes = 3 only; include/gple.h, gple_evolve_n)
+PES_USER = 16  # GPLE_PES_USER: ids from here on are user potentials (Api.pes_define), which only the N-level entry points evaluate
 _ORDER = [(0, 0), (1, 0), (1, 1)]
 
 
@@ -48,11 +49,19 @@ def _points(density, num_pes=2):
     return {e: (density.get(e) if density.get(e) is not None else empty) for e in element_order(num_pes)}
 
 
+def _n_level(all_kernels, model):
+    """the N-level entry points: beyond two levels (the reference asserts there, evolve.cpp:367-371), and for a user potential at two —
+    gple_evolve uses the closed forms of Tully's models, gple_evolve_n reproduces it to rounding"""
+    return all_kernels.num_pes != 2 or model >= PES_USER
+
+
 def evolve(density, mass, dt, all_kernels, model=DAC, api=None):
     """evolve.cpp:377-423: every selected point of every element one time step further, with its density rebuilt by
     back-propagation against the current fit.  density: {(iPES, jPES): (r (n, 2), rho (n,) complex)}; returns the same."""
     if all_kernels.num_pes != 2:  # beyond the reference (evolve.cpp:367-371 asserts): the N-level back-propagation of gple_evolve_n (DESIGN.md §10)
         return _api(all_kernels, api).evolve_n(all_kernels.num_pes, _fits(all_kernels), model, float(np.ravel(mass)[0]), dt, density)
+    if _n_level(all_kernels, model):  # a user potential at two levels: the same entry point, with the elements the two-level call would get
+        return _api(all_kernels, api).evolve_n(2, _fits(all_kernels), model, float(np.ravel(mass)[0]), dt, _points(density))
     return _api(all_kernels, api).evolve(_fits(all_kernels), model, float(np.ravel(mass)[0]), dt, _points(density))
 
 
@@ -187,7 +196,7 @@ def new_point_predict(r, iPES, jPES, mass, dt, all_kernels, model=DAC, api=None)
     dens = _points({}, all_kernels.num_pes)
     dens[(iPES, jPES)] = (r, np.zeros(len(r), dtype=complex))
     a = _api(all_kernels, api)
-    if all_kernels.num_pes != 2:  # the N-level back-propagation (gple_evolve_n)
+    if _n_level(all_kernels, model):  # the N-level back-propagation (gple_evolve_n)
         return a.evolve_n(all_kernels.num_pes, _fits(all_kernels), model, float(np.ravel(mass)[0]), dt, dens, new_points=True)[(iPES, jPES)][1]
     return a.evolve(_fits(all_kernels), model, float(np.ravel(mass)[0]), dt, dens, new_points=True)[(iPES, jPES)][1]
 

@@ -368,12 +368,44 @@ int gple_evolve(gple_ctx* ctx, const gple_element elements[3], int pes_model, do
  * pes_model 0-2: pes.cpp's diabatic_potential as it compiles for num_pes levels (Tully's two surfaces; at three levels plus the uncoupled
  * third diabat at V = 0 that the unfilled matrix entries give); 3 (num_pes = 3 only): a three-state avoided-crossing model of this library,
  * V00 = A tanh(B x), V11 = 0, V22 = -A tanh(B x), V01 = V12 = C sech(D x) with A = 0.02, B = 0.8, C = 0.005, D = 0.5 — the reference has no
- * genuinely three-level model.  Adiabatic states: ascending energy, last non-zero component of every eigenvector positive. */
+ * genuinely three-level model; an id >= GPLE_PES_USER: a user model of gple_pes_define (below) with the same num_pes — at two levels this is the
+ * entry point that ticks on a user model, gple_evolve has none.  Adiabatic states: ascending energy, last non-zero component of every
+ * eigenvector positive. */
 int gple_evolve_n(gple_ctx* ctx, int num_pes, const gple_element* elements, int pes_model, double mass, double dt, gple_points* density,
 	unsigned flags);
 /* adiabatic_potential / adiabatic_force / adiabatic_coupling (pes.cpp:98-155) for num_pes levels at M positions:
  * out[(num_pes + 2 NE) i + ...] = E (num_pes, ascending) | F lower-packed (NE) | NAC lower-packed (NE; NAC(j, k) = F(j, k) / (E_j - E_k), j > k). */
 int gple_pes_adiabatic_n(gple_ctx* ctx, int num_pes, int model, const double* x, size_t M, unsigned flags, double* out);
+
+/* ---- user potentials ------------------------------------------------------------------------------------------------- */
+/* A user model is a table of the symmetric diabatic matrix V(x_k) and its derivative V'(x_k) = dV/dx on the uniform grid x_k = x_first + dx k,
+ * k < n, registered on a context under an id >= GPLE_PES_USER (at most 16 per context).  It is evaluated as a cubic Hermite interpolant, per
+ * entry and in exactly this order (IEEE subtraction and division for s; m_k = dx V'_k is formed once, when the model is defined):
+ *     s = (x - x_first) / dx,  k = clamp(floor(s), 0, n - 2),  t = s - k,  D = V_{k+1} - V_k,
+ *     c2 = 3 D - (2 m_k + m_{k+1}),  c3 = (m_k + m_{k+1}) - 2 D,
+ *     V(x) = V_k + t (m_k + t (c2 + t c3)),  V'(x) = (m_k + t (2 c2 + 3 t c3)) / dx,  F = -V'
+ * so that at a node (t = 0) the value is the node's own bits.  Outside the table the potential continues linearly (C^1): for s < 0,
+ * V = V_0 + V'_0 (x - x_first), V' = V'_0, and for s > n - 1 the same from the last node.  With nodes taken from a smooth function the error is
+ * at most dx^4 / 384 max|V''''| for the value and sqrt(3) / 216 dx^3 max|V''''| for the derivative.
+ * A user id is accepted, on the context it was defined on and with the num_pes it was defined with (GPLE_ERR_BAD_ARG otherwise), by
+ * gple_pes_adiabatic_n, gple_pes_diabatic_n, gple_evolve_n, gple_dvr_hamiltonian, gple_mqcl_transform / _evolve / _observe, gple_grid_survey and
+ * gple_grid_reconstruct / _cross.  The two-level entry points gple_pes_adiabatic and gple_evolve keep refusing it: they use the reference's closed
+ * forms and operation order, of which a table has none; gple_evolve_n at num_pes = 2 reproduces gple_evolve to rounding and takes their place.
+ * Where two surfaces of a user model touch (E_j = E_k) with F_jk != 0 the non-adiabatic coupling is infinite, as its formula says: not guarded.
+ *
+ * gple_pes_define: V and dV are n x num_pes x num_pes, row-major per node; host pointers, or device pointers with GPLE_IO_DEVICE (the same
+ * bits either way).  *model receives the id.  GPLE_ERR_BAD_ARG with nothing registered: num_pes not 2 or 3, n < 2 or n > 2^20, dx not finite
+ * or not positive, x_first not finite, a non-finite entry (dx V' included), V or dV not exactly symmetric, a 17th model on the context.  The
+ * table is copied into device memory the context owns: the caller's arrays are free when the call returns.
+ * gple_pes_undefine: drains the context's stream, then frees the table; the id's slot is reused by a later definition.  gple_ctx_destroy frees
+ * what is still defined.  The entry points look the id up under the context's call lock, which gple_pes_undefine holds too: a model undefined
+ * by another thread is either refused (GPLE_ERR_BAD_ARG) or still alive for everything the call enqueues.  gple_evolve_n takes the lock twice,
+ * around its predicts: undefined in between, it returns GPLE_ERR_BAD_ARG with the densities untouched. */
+#define GPLE_PES_USER 16 /* first id of a user model; at most 16 per context */
+int gple_pes_define(gple_ctx* ctx, int num_pes, double x_first, double dx, size_t n, const double* V, const double* dV, unsigned flags, int* model);
+int gple_pes_undefine(gple_ctx* ctx, int model);
+/* The diabatic matrix and force of any model (built-in ids included) at M positions: V[num_pes^2 i + num_pes r + c] and F = -dV/dx likewise. */
+int gple_pes_diabatic_n(gple_ctx* ctx, int num_pes, int model, const double* x, size_t M, unsigned flags, double* V, double* F);
 
 /* ---- exact DVR dynamics (schrodinger_equation/ of the reference) ------------------------------------------------------- */
 /* The reference's exact quantum dynamics of the same models.  The reflective and periodic boundaries are propagated spectrally
