@@ -18,6 +18,7 @@ CALC_DERIVATIVE = 0x4
 IO_DEVICE = 0x100
 EVOLVE_NEW_POINTS = 0x400  # gple_evolve: new_point_predict instead of a tick
 FORMAT_JOIN = 0x1000  # gple_format_g: no blank before the first number of a line
+HOP_REVERSE = 0x2000  # gple_hop_evolve: a frustrated hop reverses the momentum
 PES_USER = 16  # GPLE_PES_USER: first id of a user potential (gple_pes_define)
 PREDICT_FULL = 0x200  # contract every test row (default: far rows whose contraction cannot move the variance are skipped)
 
@@ -352,6 +353,10 @@ def _signatures():
         "mqcl_transform": (st, [CTX, i, i, _dp, sz, i, i, u, _dp, _dp]),
         "mqcl_evolve": (st, [CTX, i, i, _dp, _dp, sz, d, d, d, d, sz, u, _dp]),
         "mqcl_observe": (st, [CTX, i, i, _dp, _dp, sz, d, d, d, u, _dp, _dp, _dp, _dp]),
+        # fewest-switches surface hopping
+        "hop_sample": (st, [CTX, i, i, sz, sz, ull, d, d, d, d, i, u, _dp, _dp, _dp, ip, ip]),
+        "hop_evolve": (st, [CTX, i, i, sz, sz, ull, d, d, sz, sz, d, d, u, _dp, _dp, _dp, ip, ip]),
+        "hop_observe": (st, [CTX, i, i, sz, d, u, _dp, _dp, _dp, ip, ip, _dp]),
         # many NLML problems in one launch; the search of several planes in lock-step on it
         "nlml_batch": (st, [CTX, C.POINTER(NlmlProblem), sz, i, u, _dp, _dp, C.POINTER(_dp), ip]),
         "nlml_fit_planes": (st, [CTX, C.POINTER(NlmlFitPlane), sz, i, opt, _dp, _dp, ip, C.POINTER(_dp)]),
@@ -531,7 +536,7 @@ class Api:
     def timing(self, which):
         """(last_ms, total_ms, count) of a gple_timer: 0 = fit, 1 = predict call, 2 = fused predict kernel, 3 = derivative GEMM, 4 = Wigner kernel, 5 = MQCLE
         steps, 6 = the device work of the reconstruction entry points, 7 = the kernels of format_g, 8 = the kernels of parse_g, 9 = the products of dvr_propagator, 10 = the products of dvr_flux,
-        11 = the device work of dvr_spectrum."""
+        11 = the device work of dvr_spectrum, 12 = the step kernel of hop_evolve."""
         last, total, count = C.c_double(), C.c_double(), C.c_long()
         self._check(self.lib.gple_ctx_get_timing(self.ctx, which, C.byref(last), C.byref(total), C.byref(count)))
         return last.value, total.value, count.value
@@ -959,6 +964,74 @@ class Api:
         (px, pp, pr, pa, pav, ppo), flags = _io(x, p, rho_dia, adia, av, pops)
         self._check(self.lib.gple_mqcl_observe(self.ctx, int(num_pes), int(model), px, pp, n, float(mass), float(dx), float(dp), flags, pr, pa, pav, ppo))
         return adia, av, pops
+
+    # ---- fewest-switches surface hopping (gple_hop_*; DESIGN.md §17, driven by hopping.py) -----------------------------------------------------
+    # An ensemble is the tuple (x (n,), p (n,) float64, b (n, num_pes) complex128 diabatic amplitudes, surface (n,), status (n,) int32): numpy
+    # arrays, or contiguous tensors on the context's device
+    def _hop_state(self, num_pes, state):
+        x, p, b, surface, status = state
+        if _on_device(x):
+            kinds = ("torch.float64", "torch.float64", "torch.complex128", "torch.int32", "torch.int32")
+            if not all(_on_device(a) and a.is_cuda and a.is_contiguous() and str(a.dtype) == kind for a, kind in zip(state, kinds)):
+                raise ValueError("a device ensemble is contiguous float64 x, p, complex128 b and int32 surface, status tensors on the GPU")
+        else:
+            x, p, b = _f64(x), _f64(p), _cplx(b)
+            surface, status = (np.ascontiguousarray(a, dtype=np.int32) for a in (surface, status))
+        n = int(x.shape[0])
+        if n < 1 or any(tuple(a.shape) != (n,) for a in (x, p, surface, status)) or tuple(b.shape) != (n, num_pes):
+            raise ValueError("an ensemble is x, p, surface, status of shape (n,) and b of shape (n, num_pes), n >= 1")
+        return (x, p, b, surface, status), n
+
+    @staticmethod
+    def _hop_pointers(state):
+        (px, pp, pb), flags = _io(*state[:3])
+        ip = C.POINTER(C.c_int)
+        return [px, pp, pb] + [C.cast(a.data_ptr(), ip) if flags else a.ctypes.data_as(ip) for a in state[3:]], flags
+
+    def hop_sample(self, num_pes, model, n, seed, x0, p0, sigma_x, sigma_p, surface0=0, trajectory_offset=0, device_out=False):
+        """gple_hop_sample: n trajectories drawn from the Gaussian (x0, sigma_x) x (p0, sigma_p) on the adiabatic surface surface0 -> the ensemble
+        (x, p, b, surface, status).  device_out: tensors on the context's device (the call has completed when it returns)"""
+        num_pes, n = int(num_pes), int(n)
+        if n < 1:
+            raise ValueError("an ensemble has at least one trajectory")
+        if device_out:
+            import torch
+            where = torch.device("cuda", self.device)
+            state = (torch.empty(n, dtype=torch.float64, device=where), torch.empty(n, dtype=torch.float64, device=where),
+                     torch.empty((n, num_pes), dtype=torch.complex128, device=where), torch.empty(n, dtype=torch.int32, device=where),
+                     torch.empty(n, dtype=torch.int32, device=where))
+        else:
+            state = (np.empty(n), np.empty(n), np.empty((n, num_pes), dtype=np.complex128), np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32))
+        pointers, flags = self._hop_pointers(state)
+        self._check(self.lib.gple_hop_sample(self.ctx, num_pes, int(model), n, int(trajectory_offset), int(seed), float(x0), float(p0), float(sigma_x),
+                                             float(sigma_p), int(surface0), flags, *pointers))
+        if device_out:
+            self.synchronize()
+        return state
+
+    def hop_evolve(self, num_pes, model, state, seed, mass, dt, first_step, n_steps, x_left, x_right, reverse=False, trajectory_offset=0):
+        """gple_hop_evolve: the steps first_step ... first_step + n_steps - 1 of every running trajectory.  numpy: returns the evolved copy;
+        device tensors: evolves the ensemble in place (asynchronously on the context's stream) and returns it.  reverse: GPLE_HOP_REVERSE"""
+        state, n = self._hop_state(int(num_pes), state)
+        if not _on_device(state[0]):
+            state = tuple(a.copy() for a in state)
+        pointers, flags = self._hop_pointers(state)
+        self._check(self.lib.gple_hop_evolve(self.ctx, int(num_pes), int(model), n, int(trajectory_offset), int(seed), float(mass), float(dt), int(first_step),
+                                             int(n_steps), float(x_left), float(x_right), flags | (HOP_REVERSE if reverse else 0), *pointers))
+        return state
+
+    def hop_observe(self, num_pes, model, state, mass):
+        """gple_hop_observe -> the 4 num_pes + 3 sums as a numpy array: counts [status][surface] (3 num_pes), sum |c_k|^2 (num_pes), sum x, sum p,
+        sum (p^2 / 2 mass + E_surface).  With device tensors only these numbers cross"""
+        state, n = self._hop_state(int(num_pes), state)
+        out = _like(state[0], 4 * int(num_pes) + 3)
+        pointers, flags = self._hop_pointers(state)
+        (po,), _ = _io(out)
+        self._check(self.lib.gple_hop_observe(self.ctx, int(num_pes), int(model), n, float(mass), flags, *pointers, po))
+        if _on_device(out):
+            self.synchronize()
+            return out.cpu().numpy()
+        return out
 
     # ---- reconstruction of a gridded density with the NLML GP (test/main_evolve.cpp; gple_nlml_weights / gple_grid_*) -------------------------
     SURVEY_FIELDS = ("max", "min", "weight", "argmax", "population", "potential", "kinetic")

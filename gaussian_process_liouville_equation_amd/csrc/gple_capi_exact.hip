@@ -384,4 +384,119 @@ extern "C"
 		for (int k = 0; k < num_pes; ++k) populations[k] = h[3 + k];
 		return GPLE_OK;
 	}
+
+	/* ---- fewest-switches surface hopping (gple_hop.hip) --------------------------------------------------------------------- */
+	static bool hop_size_ok(gple_ctx* ctx, int num_pes, int model, size_t n, size_t offset, PesModel* pes)
+	{
+		constexpr size_t LIMIT = size_t(1) << 32; // the trajectory index is one word of the counter
+		return pes_resolve(ctx, num_pes, model, pes) && n >= 1 && n <= LIMIT && offset <= LIMIT - n;
+	}
+	static bool hop_positive(double v) { return std::isfinite(v) && v > 0.0; }
+	// the surface / status array of a hop call as the kernels see it (Staged, for ints): a device array in place, a host array through pooled memory
+	struct StagedInts
+	{
+		Scratch buf;
+		const bool dev;
+		int* p = nullptr;
+		int* host = nullptr; // back() copies p here
+		size_t n = 0;
+		StagedInts(gple_ctx* c, bool device): buf(c), dev(device) {}
+		// read: the kernels read the caller's values; written: the caller receives the kernels'
+		hipError_t stage(const int* a, size_t count, bool read, bool written)
+		{
+			p = const_cast<int*>(a);
+			if (dev) return hipSuccess;
+			hipError_t e = buf.get((count + 1) / 2);
+			if (e != hipSuccess) return e;
+			p = reinterpret_cast<int*>(buf.p);
+			if (written) host = const_cast<int*>(a), n = count;
+			return read ? hipMemcpyAsync(p, a, count * sizeof(int), hipMemcpyHostToDevice, buf.ctx->stream) : hipSuccess;
+		}
+		hipError_t back() { return host ? hipMemcpyAsync(host, p, n * sizeof(int), hipMemcpyDeviceToHost, buf.ctx->stream) : hipSuccess; }
+	};
+
+	int gple_hop_sample(gple_ctx* ctx, int num_pes, int model, size_t n, size_t trajectory_offset, unsigned long long seed, double x0, double p0,
+		double sigma_x, double sigma_p, int surface0, unsigned flags, double* x, double* p, double* b, int* surface, int* status)
+	{
+		PesModel pes;
+		if (!ctx || !hop_size_ok(ctx, num_pes, model, n, trajectory_offset, &pes) || !hop_positive(sigma_x) || !hop_positive(sigma_p) || surface0 < 0 ||
+			surface0 >= num_pes || !x || !p || !b || !surface || !status)
+			return GPLE_ERR_BAD_ARG;
+		GPLE_OPEN(ctx);
+		const bool dev = flags & GPLE_IO_DEVICE;
+		GPLE_CALL(ctx);
+		if (!pes_resolve(ctx, num_pes, model, &pes)) return GPLE_ERR_BAD_ARG; // under the call lock, which gple_pes_undefine takes: the table outlives the enqueue
+		hipStream_t st = ctx->stream;
+		Staged xs(ctx, dev), ps(ctx, dev), bs(ctx, dev);
+		StagedInts su(ctx, dev), ss(ctx, dev);
+		GPLE_HIP(ctx, xs.out(x, n));
+		GPLE_HIP(ctx, ps.out(p, n));
+		GPLE_HIP(ctx, bs.out(b, 2 * n * num_pes));
+		GPLE_HIP(ctx, su.stage(surface, n, false, true));
+		GPLE_HIP(ctx, ss.stage(status, n, false, true));
+		const HopEnsemble e{num_pes, static_cast<long>(n), trajectory_offset, seed, xs.p, ps.p, bs.p, su.p, ss.p};
+		GPLE_HIP(ctx, launch_hop_sample(st, e, pes, x0, p0, sigma_x, sigma_p, surface0));
+		for (Staged* o : {&xs, &ps, &bs}) GPLE_HIP(ctx, o->back());
+		for (StagedInts* o : {&su, &ss}) GPLE_HIP(ctx, o->back());
+		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
+		return GPLE_OK;
+	}
+
+	int gple_hop_evolve(gple_ctx* ctx, int num_pes, int model, size_t n, size_t trajectory_offset, unsigned long long seed, double mass, double dt,
+		size_t first_step, size_t n_steps, double x_left, double x_right, unsigned flags, double* x, double* p, double* b, int* surface, int* status)
+	{
+		PesModel pes;
+		if (!ctx || !hop_size_ok(ctx, num_pes, model, n, trajectory_offset, &pes) || !hop_positive(mass) || !hop_positive(dt) || !std::isfinite(x_left) ||
+			!std::isfinite(x_right) || !(x_left < x_right) || n_steps > (1ul << 40) || !x || !p || !b || !surface || !status)
+			return GPLE_ERR_BAD_ARG;
+		GPLE_OPEN(ctx);
+		if (n_steps == 0) return GPLE_OK;
+		const bool dev = flags & GPLE_IO_DEVICE;
+		GPLE_CALL(ctx);
+		if (!pes_resolve(ctx, num_pes, model, &pes)) return GPLE_ERR_BAD_ARG; // under the call lock, which gple_pes_undefine takes: the table outlives the enqueue
+		hipStream_t st = ctx->stream;
+		Staged xs(ctx, dev), ps(ctx, dev), bs(ctx, dev);
+		StagedInts su(ctx, dev), ss(ctx, dev);
+		GPLE_HIP(ctx, xs.inout(x, n));
+		GPLE_HIP(ctx, ps.inout(p, n));
+		GPLE_HIP(ctx, bs.inout(b, 2 * n * num_pes));
+		GPLE_HIP(ctx, su.stage(surface, n, true, true));
+		GPLE_HIP(ctx, ss.stage(status, n, true, true));
+		const HopEnsemble e{num_pes, static_cast<long>(n), trajectory_offset, seed, xs.p, ps.p, bs.p, su.p, ss.p};
+		timer_start(ctx, GPLE_TIMER_HOP);
+		const hipError_t launched = launch_hop_evolve(st, e, pes, mass, dt, first_step, static_cast<long>(n_steps), x_left, x_right, (flags & GPLE_HOP_REVERSE) != 0);
+		timer_stop(ctx, GPLE_TIMER_HOP); // on the error path too: no span stays open
+		GPLE_HIP(ctx, launched);
+		for (Staged* o : {&xs, &ps, &bs}) GPLE_HIP(ctx, o->back());
+		for (StagedInts* o : {&su, &ss}) GPLE_HIP(ctx, o->back());
+		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
+		return GPLE_OK;
+	}
+
+	int gple_hop_observe(gple_ctx* ctx, int num_pes, int model, size_t n, double mass, unsigned flags, const double* x, const double* p, const double* b,
+		const int* surface, const int* status, double* out)
+	{
+		PesModel pes;
+		if (!ctx || !hop_size_ok(ctx, num_pes, model, n, 0, &pes) || !hop_positive(mass) || !x || !p || !b || !surface || !status || !out) return GPLE_ERR_BAD_ARG;
+		GPLE_OPEN(ctx);
+		const bool dev = flags & GPLE_IO_DEVICE;
+		GPLE_CALL(ctx);
+		if (!pes_resolve(ctx, num_pes, model, &pes)) return GPLE_ERR_BAD_ARG; // under the call lock, which gple_pes_undefine takes: the table outlives the enqueue
+		hipStream_t st = ctx->stream;
+		Staged xs(ctx, dev), ps(ctx, dev), bs(ctx, dev), o(ctx, dev);
+		StagedInts su(ctx, dev), ss(ctx, dev);
+		Scratch work(ctx);
+		GPLE_HIP(ctx, work.get(hop_observe_work_doubles(num_pes, static_cast<long>(n))));
+		GPLE_HIP(ctx, o.out(out, 4 * num_pes + 3));
+		GPLE_HIP(ctx, xs.in(x, n));
+		GPLE_HIP(ctx, ps.in(p, n));
+		GPLE_HIP(ctx, bs.in(b, 2 * n * num_pes));
+		GPLE_HIP(ctx, su.stage(surface, n, true, false));
+		GPLE_HIP(ctx, ss.stage(status, n, true, false));
+		const HopEnsemble e{num_pes, static_cast<long>(n), 0, 0, xs.p, ps.p, bs.p, su.p, ss.p};
+		GPLE_HIP(ctx, launch_hop_observe(st, e, pes, mass, work.p, o.p));
+		GPLE_HIP(ctx, o.back());
+		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
+		return GPLE_OK;
+	}
 }

@@ -1,0 +1,320 @@
+// gple_hop.hip — fewest-switches surface hopping (Tully, J. Chem. Phys. 93, 1061 (1990)) for an ensemble of independent trajectories on the
+// N-level potentials of gple_pes_n.h, built-in or tabulated (numpy restatement: tests/hop_numpy.py).  The reference has no
+// trajectory code: this is the method its three models were made to test.
+//
+// One thread per trajectory; x, p, the diabatic amplitudes b, the active surface a and everything derived from them stay in registers for all
+// the steps of a launch.  No LDS, no atomics, no device globals.  One step of length dt for a running trajectory (V, Fd = -V', E, C: the
+// diabatic matrix and force, the adiabatic energies and states; F = C^T Fd C, symmetrised as in gple_evolve_n.hip):
+//     1  p += F_aa(x) dt / 2,  x_new = x + p / m dt
+//     2  b <- W exp(-i lambda dt / hbar) W^T b,  (lambda, W) the Jacobi eigen-system of (V(x) + V(x_new)) / 2: exactly unitary, no coupling needed
+//     3  E, C, F at x_new,  p += F_aa(x_new) dt / 2
+//     4  c = C^T b;  g_k = max(0, 2 dt (p / m) d_ak Re(conj(c_a) c_k) / |c_a|^2),  d_ak = F_ak / (E_a - E_k)  (0 where F_ak is exactly 0, or |c_a|^2 is)
+//     5  xi = unit53 of the words (0, 1) of Philox4x32-10, counter (trajectory, step low, 0, step high), key (seed low, seed high);
+//        hop to the first k != a (ascending) with xi < g_1 + ... + g_k
+//     6  r = p^2 + 2 m (E_a - E_k):  r >= 0: p = sgn(p) sqrt(r), a = k;  r < 0: frustrated, nothing changes (reverse: p = -p)
+//     7  x < x_left: status 1, x > x_right: status 2; a finished trajectory is never touched again
+// Everything is invariant under flipping a column of C, so the sign convention of the adiabatic states (which flips along x) needs no tracking.
+// The states at x_new are the states at x of the next step: they are formed at one place of the loop only, so that a launch which starts at x
+// forms them with the same instructions as the launch that arrived there (evolve(a) then evolve(b) = evolve(a + b), bit for bit).
+#include "gple_kernels.h"
+#include "gple_pes_n.h"
+#include "gple_philox.h"
+
+namespace gple
+{
+	namespace
+	{
+		constexpr int HOP_BLOCK = 256, HOP_WAVE = 64;
+		constexpr double HBAR_HOP = 1.0;
+
+		// v[a] for a run-time a: a chain of selects, since a run-time index would put the array into scratch
+		template <int NP>
+		__device__ __forceinline__ double pick(const double (&v)[NP], int a)
+		{
+			static_assert(NP == 2 || NP == 3);
+			const double v0 = v[0], v1 = v[1], v2 = v[NP - 1];
+			return a == 0 ? v0 : NP == 2 || a == 1 ? v1 : v2;
+		}
+
+		template <int NP>
+		struct HopStates
+		{
+			Mat<NP> V, C, F; // diabatic matrix, adiabatic states (columns), adiabatic force matrix
+			double E[NP];
+		};
+		// adiabatic_states_n with V kept, and F = C^T Fd C (pes.cpp:98-155 at N levels, as adiabatic_n of gple_evolve_n.hip forms it)
+		template <int NP, typename M>
+		__device__ __forceinline__ void hop_states(double x, const M& model, HopStates<NP>& s)
+		{
+			Mat<NP> Fd, A, FC;
+			diabatic_n<NP>(x, model, s.V, Fd);
+			A = s.V;
+			jacobi_eig<NP>(A, s.E, s.C);
+			adiabatic_sign_n<NP>(s.C);
+#pragma unroll
+			for (int i = 0; i < NP; ++i)
+#pragma unroll
+				for (int k = 0; k < NP; ++k)
+				{
+					double acc = 0.0;
+#pragma unroll
+					for (int j = 0; j < NP; ++j) acc += Fd.a[i][j] * s.C.a[j][k];
+					FC.a[i][k] = acc;
+				}
+#pragma unroll
+			for (int k = 0; k < NP; ++k)
+#pragma unroll
+				for (int l = 0; l <= k; ++l)
+				{
+					double a1 = 0.0, a2 = 0.0;
+#pragma unroll
+					for (int i = 0; i < NP; ++i) a1 += s.C.a[i][k] * FC.a[i][l], a2 += s.C.a[i][l] * FC.a[i][k];
+					s.F.a[k][l] = s.F.a[l][k] = 0.5 * (a1 + a2);
+				}
+		}
+
+		// c = C^T b
+		template <int NP>
+		__device__ __forceinline__ void adiabatic_amplitudes(const Mat<NP>& C, const double (&bre)[NP], const double (&bim)[NP], double (&cre)[NP], double (&cim)[NP])
+		{
+#pragma unroll
+			for (int k = 0; k < NP; ++k)
+			{
+				double re = 0.0, im = 0.0;
+#pragma unroll
+				for (int i = 0; i < NP; ++i) re += C.a[i][k] * bre[i], im += C.a[i][k] * bim[i];
+				cre[k] = re, cim[k] = im;
+			}
+		}
+
+		template <int NP, typename M>
+		__global__ void __launch_bounds__(HOP_BLOCK) hop_sample_kernel(HopEnsemble e, M model, double x0, double p0, double sigma_x, double sigma_p, int surface0)
+		{
+			const long i = static_cast<long>(blockIdx.x) * HOP_BLOCK + threadIdx.x;
+			if (i >= e.n) return;
+			const unsigned long long index = e.offset + static_cast<unsigned long long>(i);
+			unsigned c[4] = {static_cast<unsigned>(index), 0u, 1u, 0u};
+			philox4x32(c, static_cast<unsigned>(e.seed), static_cast<unsigned>(e.seed >> 32));
+			const double u0 = unit53(c[0], c[1]), u1 = unit53(c[2], c[3]);
+			const double rho = sqrt(-2.0 * log(1.0 - u0));
+			double sn, cs;
+			sincospi(2.0 * u1, &sn, &cs);
+			const double x = x0 + sigma_x * rho * cs, p = p0 + sigma_p * rho * sn;
+			double E[NP];
+			Mat<NP> C, Fd;
+			adiabatic_states_n<NP>(x, model, E, C, Fd);
+			e.x[i] = x, e.p[i] = p, e.surface[i] = surface0, e.status[i] = 0;
+			double* b = e.b + 2 * NP * i;
+#pragma unroll
+			for (int k = 0; k < NP; ++k)
+			{
+				double row[NP];
+#pragma unroll
+				for (int r = 0; r < NP; ++r) row[r] = C.a[k][r];
+				b[2 * k] = pick<NP>(row, surface0), b[2 * k + 1] = 0.0;
+			}
+		}
+
+		template <int NP, typename M>
+		__global__ void __launch_bounds__(HOP_BLOCK) hop_evolve_kernel(HopEnsemble e, M model, double mass, double dt, unsigned long long first_step, long n_steps,
+			double x_left, double x_right, int reverse)
+		{
+			const long i = static_cast<long>(blockIdx.x) * HOP_BLOCK + threadIdx.x;
+			if (i >= e.n || e.status[i] != 0) return;
+			double x = e.x[i], p = e.p[i], bre[NP], bim[NP];
+			int a = e.surface[i], status = 0;
+			double* const b = e.b + 2 * NP * i;
+#pragma unroll
+			for (int k = 0; k < NP; ++k) bre[k] = b[2 * k], bim[k] = b[2 * k + 1];
+			const unsigned index = static_cast<unsigned>(e.offset + static_cast<unsigned long long>(i));
+			const unsigned key0 = static_cast<unsigned>(e.seed), key1 = static_cast<unsigned>(e.seed >> 32);
+			Mat<NP> Vx; // V(x) and the diagonal of F(x): set by the pass s = -1, which only forms the states at the start point
+			double Fx[NP];
+			for (long s = -1; s < n_steps && status == 0; ++s)
+			{
+				double xn = x;
+				if (s >= 0)
+				{
+					p += pick<NP>(Fx, a) * dt / 2.0;
+					xn = x + p / mass * dt;
+				}
+				HopStates<NP> st;
+				hop_states<NP>(xn, model, st);
+				if (s >= 0)
+				{
+					// 2: the amplitudes through the mid-point matrix, U = W exp(-i lambda dt / hbar) W^T entry by entry
+					Mat<NP> Vm, W;
+					double lam[NP], cs[NP], sn[NP];
+#pragma unroll
+					for (int r = 0; r < NP; ++r)
+#pragma unroll
+						for (int q = 0; q < NP; ++q) Vm.a[r][q] = 0.5 * (Vx.a[r][q] + st.V.a[r][q]);
+					jacobi_eig<NP>(Vm, lam, W);
+#pragma unroll
+					for (int k = 0; k < NP; ++k) sincos(lam[k] * dt / HBAR_HOP, &sn[k], &cs[k]);
+					double nre[NP], nim[NP];
+#pragma unroll
+					for (int r = 0; r < NP; ++r)
+					{
+						double re = 0.0, im = 0.0;
+#pragma unroll
+						for (int q = 0; q < NP; ++q)
+						{
+							double ure = 0.0, uim = 0.0;
+#pragma unroll
+							for (int k = 0; k < NP; ++k)
+							{
+								const double ww = W.a[r][k] * W.a[q][k];
+								ure += ww * cs[k], uim -= ww * sn[k];
+							}
+							re += ure * bre[q] - uim * bim[q], im += ure * bim[q] + uim * bre[q];
+						}
+						nre[r] = re, nim[r] = im;
+					}
+#pragma unroll
+					for (int r = 0; r < NP; ++r) bre[r] = nre[r], bim[r] = nim[r];
+					// 3
+					double Fdiag[NP], Fa[NP];
+#pragma unroll
+					for (int k = 0; k < NP; ++k)
+					{
+						Fdiag[k] = st.F.a[k][k];
+						double column[NP];
+#pragma unroll
+						for (int r = 0; r < NP; ++r) column[r] = st.F.a[r][k];
+						Fa[k] = pick<NP>(column, a);
+					}
+					p += pick<NP>(Fdiag, a) * dt / 2.0;
+					x = xn;
+					// 4, 5
+					double cre[NP], cim[NP];
+					adiabatic_amplitudes<NP>(st.C, bre, bim, cre, cim);
+					const double are = pick<NP>(cre, a), aim = pick<NP>(cim, a), na = are * are + aim * aim, Ea = pick<NP>(st.E, a);
+					const unsigned long long step = first_step + static_cast<unsigned long long>(s);
+					unsigned c[4] = {index, static_cast<unsigned>(step), 0u, static_cast<unsigned>(step >> 32)};
+					philox4x32(c, key0, key1);
+					const double xi = unit53(c[0], c[1]), v = p / mass;
+					double sum = 0.0;
+					int target = -1;
+#pragma unroll
+					for (int k = 0; k < NP; ++k)
+						if (k != a)
+						{
+							double g = 0.0;
+							if (na != 0.0 && Fa[k] != 0.0)
+							{
+								const double d = Fa[k] / (Ea - st.E[k]);
+								g = fmax(0.0, 2.0 * dt * v * d * (are * cre[k] + aim * cim[k]) / na);
+							}
+							sum += g;
+							if (target < 0 && xi < sum) target = k;
+						}
+					// 6
+					if (target >= 0)
+					{
+						const double r = p * p + 2.0 * mass * (Ea - pick<NP>(st.E, target));
+						if (r >= 0.0) p = sgn_n(p) * sqrt(r), a = target;
+						else if (reverse) p = -p;
+					}
+					// 7
+					if (x < x_left) status = 1;
+					else if (x > x_right) status = 2;
+				}
+				Vx = st.V;
+#pragma unroll
+				for (int k = 0; k < NP; ++k) Fx[k] = st.F.a[k][k];
+			}
+			e.x[i] = x, e.p[i] = p, e.surface[i] = a, e.status[i] = status;
+#pragma unroll
+			for (int k = 0; k < NP; ++k) b[2 * k] = bre[k], b[2 * k + 1] = bim[k];
+		}
+
+		// First stage of the sums: the 4 NP + 3 terms of every trajectory, added over each wave by a butterfly of lane exchanges (every lane of a
+		// launched wave takes part; lanes beyond n hold zeros), one row of partial per wave
+		template <int NP, typename M>
+		__global__ void __launch_bounds__(HOP_BLOCK) hop_observe_kernel(HopEnsemble e, M model, double mass, double* __restrict__ partial)
+		{
+			constexpr int WIDTH = 4 * NP + 3;
+			const long i = static_cast<long>(blockIdx.x) * HOP_BLOCK + threadIdx.x;
+			double t[WIDTH];
+#pragma unroll
+			for (int q = 0; q < WIDTH; ++q) t[q] = 0.0;
+			if (i < e.n)
+			{
+				const double x = e.x[i], p = e.p[i];
+				const int a = e.surface[i], status = e.status[i];
+				double bre[NP], bim[NP], cre[NP], cim[NP], E[NP];
+#pragma unroll
+				for (int k = 0; k < NP; ++k) bre[k] = e.b[2 * (NP * i + k)], bim[k] = e.b[2 * (NP * i + k) + 1];
+				Mat<NP> C, Fd;
+				adiabatic_states_n<NP>(x, model, E, C, Fd);
+				adiabatic_amplitudes<NP>(C, bre, bim, cre, cim);
+				const int cell = status >= 0 && status <= 2 && a >= 0 && a < NP ? status * NP + a : -1;
+#pragma unroll
+				for (int q = 0; q < 3 * NP; ++q) t[q] = q == cell ? 1.0 : 0.0;
+#pragma unroll
+				for (int k = 0; k < NP; ++k) t[3 * NP + k] = cre[k] * cre[k] + cim[k] * cim[k];
+				t[4 * NP] = x, t[4 * NP + 1] = p, t[4 * NP + 2] = p * p / 2.0 / mass + pick<NP>(E, a);
+			}
+			const long wave = i / HOP_WAVE;
+			const int lane = threadIdx.x % HOP_WAVE;
+#pragma unroll
+			for (int q = 0; q < WIDTH; ++q)
+			{
+				double v = t[q];
+#pragma unroll
+				for (int m = HOP_WAVE / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m, HOP_WAVE);
+				if (lane == 0) partial[wave * WIDTH + q] = v;
+			}
+		}
+		// Second stage, one wave per column: lane l adds the rows l, l + 64, ... in ascending order, then the same butterfly
+		__global__ void __launch_bounds__(HOP_WAVE) hop_observe_finish_kernel(const double* __restrict__ partial, long rows, int width, double* __restrict__ out)
+		{
+			const int q = blockIdx.x, lane = threadIdx.x;
+			double v = 0.0;
+			for (long r = lane; r < rows; r += HOP_WAVE) v += partial[r * width + q];
+#pragma unroll
+			for (int m = HOP_WAVE / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m, HOP_WAVE);
+			if (lane == 0) out[q] = v;
+		}
+
+		inline unsigned hop_blocks(long n) { return static_cast<unsigned>((n + HOP_BLOCK - 1) / HOP_BLOCK); }
+	} // namespace
+
+	hipError_t launch_hop_sample(hipStream_t s, const HopEnsemble& e, PesModel model, double x0, double p0, double sigma_x, double sigma_p, int surface0)
+	{
+		if (e.n <= 0) return hipSuccess;
+		const dim3 grid(hop_blocks(e.n)), block(HOP_BLOCK);
+		if (e.num_pes == 2) with_model(model, [&](auto m) { hipLaunchKernelGGL((hop_sample_kernel<2, decltype(m)>), grid, block, 0, s, e, m, x0, p0, sigma_x, sigma_p, surface0); });
+		else if (e.num_pes == 3) with_model(model, [&](auto m) { hipLaunchKernelGGL((hop_sample_kernel<3, decltype(m)>), grid, block, 0, s, e, m, x0, p0, sigma_x, sigma_p, surface0); });
+		else return hipErrorInvalidValue;
+		return hipGetLastError();
+	}
+	hipError_t launch_hop_evolve(hipStream_t s, const HopEnsemble& e, PesModel model, double mass, double dt, unsigned long long first_step, long n_steps,
+		double x_left, double x_right, bool reverse)
+	{
+		if (e.n <= 0 || n_steps <= 0) return hipSuccess;
+		const dim3 grid(hop_blocks(e.n)), block(HOP_BLOCK);
+		const int rev = reverse ? 1 : 0;
+		if (e.num_pes == 2)
+			with_model(model, [&](auto m) { hipLaunchKernelGGL((hop_evolve_kernel<2, decltype(m)>), grid, block, 0, s, e, m, mass, dt, first_step, n_steps, x_left, x_right, rev); });
+		else if (e.num_pes == 3)
+			with_model(model, [&](auto m) { hipLaunchKernelGGL((hop_evolve_kernel<3, decltype(m)>), grid, block, 0, s, e, m, mass, dt, first_step, n_steps, x_left, x_right, rev); });
+		else return hipErrorInvalidValue;
+		return hipGetLastError();
+	}
+	size_t hop_observe_work_doubles(int num_pes, long n) { return static_cast<size_t>(hop_blocks(n)) * (HOP_BLOCK / HOP_WAVE) * (4 * num_pes + 3); }
+	hipError_t launch_hop_observe(hipStream_t s, const HopEnsemble& e, PesModel model, double mass, double* work, double* out)
+	{
+		if (e.n <= 0) return hipErrorInvalidValue;
+		const dim3 grid(hop_blocks(e.n)), block(HOP_BLOCK);
+		if (e.num_pes == 2) with_model(model, [&](auto m) { hipLaunchKernelGGL((hop_observe_kernel<2, decltype(m)>), grid, block, 0, s, e, m, mass, work); });
+		else if (e.num_pes == 3) with_model(model, [&](auto m) { hipLaunchKernelGGL((hop_observe_kernel<3, decltype(m)>), grid, block, 0, s, e, m, mass, work); });
+		else return hipErrorInvalidValue;
+		hipError_t err = hipGetLastError();
+		if (err != hipSuccess) return err;
+		const int width = 4 * e.num_pes + 3;
+		hipLaunchKernelGGL(hop_observe_finish_kernel, dim3(width), dim3(HOP_WAVE), 0, s, work, static_cast<long>(grid.x) * (HOP_BLOCK / HOP_WAVE), width, out);
+		return hipGetLastError();
+	}
+} // namespace gple

@@ -417,6 +417,22 @@ namespace gple
 	hipError_t launch_mqcl_observe(hipStream_t s, int num_pes, int n, const double* tables, const double* x, const double* p, double mass, double dxdp,
 		const double* rho, double* adia, double* work, double* out);
 
+	// ---- fewest-switches surface hopping (gple_hop.hip): num_pes = 2 or 3, one thread per trajectory, every pointer a device pointer ----
+	struct HopEnsemble // x, p: n doubles; b: n x num_pes (re, im) pairs; surface, status: n ints; counters use the index offset + i
+	{
+		int num_pes;
+		long n;
+		unsigned long long offset, seed;
+		double *x, *p, *b;
+		int *surface, *status;
+	};
+	hipError_t launch_hop_sample(hipStream_t s, const HopEnsemble& e, PesModel model, double x0, double p0, double sigma_x, double sigma_p, int surface0);
+	hipError_t launch_hop_evolve(hipStream_t s, const HopEnsemble& e, PesModel model, double mass, double dt, unsigned long long first_step, long n_steps,
+		double x_left, double x_right, bool reverse);
+	// out: 4 num_pes + 3 sums (include/gple.h), from one partial row per wave of the first stage in work (hop_observe_work_doubles)
+	size_t hop_observe_work_doubles(int num_pes, long n);
+	hipError_t launch_hop_observe(hipStream_t s, const HopEnsemble& e, PesModel model, double mass, double* work, double* out);
+
 	// ---- reconstruction of a gridded density (gple_recon.hip; test/gpr.cpp): num_pes = 2 or 3, rho: num_pes^2 x nx x np (re, im) ----
 	constexpr int RECON_SURVEY_BLOCKS = 64, RECON_SURVEY_VALUES = 7; // row blocks of the survey, values per plane and block
 	constexpr int RECON_MAX_PLANES = 9, RECON_MAX_N = 4096, RECON_SUMS = 6;

@@ -156,7 +156,8 @@ typedef enum gple_timer {
 	GPLE_TIMER_PARSE = 8,          /* the kernels of one gple_parse_g call (three, or two when it only counts; no staging, no copies); count = calls */
 	GPLE_TIMER_DVR_POWER = 9,      /* the products of one gple_dvr_propagator call (Horner form of P4 and the binary power; no set-up, no copies); count = calls */
 	GPLE_TIMER_DVR_FLUX = 10,      /* the products of one gple_dvr_flux call (P4, the power, the loss matrix and every sandwich; no set-up, no copies); count = calls */
-	GPLE_TIMER_DVR_SPECTRUM = 11   /* the device work of one gple_dvr_spectrum call (P4, the squarings, the thin products, the projection and the reduction; no copies); count = calls */
+	GPLE_TIMER_DVR_SPECTRUM = 11,  /* the device work of one gple_dvr_spectrum call (P4, the squarings, the thin products, the projection and the reduction; no copies); count = calls */
+	GPLE_TIMER_HOP = 12            /* the step kernel of one gple_hop_evolve call (all its steps, no staging); count = calls */
 } gple_timer;
 int gple_ctx_enable_timing(gple_ctx* ctx, int on);
 /* Synchronises the stream, then: last = milliseconds of the most recent interval; total / count = accumulated since
@@ -388,8 +389,8 @@ int gple_pes_adiabatic_n(gple_ctx* ctx, int num_pes, int model, const double* x,
  * V = V_0 + V'_0 (x - x_first), V' = V'_0, and for s > n - 1 the same from the last node.  With nodes taken from a smooth function the error is
  * at most dx^4 / 384 max|V''''| for the value and sqrt(3) / 216 dx^3 max|V''''| for the derivative.
  * A user id is accepted, on the context it was defined on and with the num_pes it was defined with (GPLE_ERR_BAD_ARG otherwise), by
- * gple_pes_adiabatic_n, gple_pes_diabatic_n, gple_evolve_n, gple_dvr_hamiltonian, gple_mqcl_transform / _evolve / _observe, gple_grid_survey and
- * gple_grid_reconstruct / _cross.  The two-level entry points gple_pes_adiabatic and gple_evolve keep refusing it: they use the reference's closed
+ * gple_pes_adiabatic_n, gple_pes_diabatic_n, gple_evolve_n, gple_dvr_hamiltonian, gple_mqcl_transform / _evolve / _observe, gple_hop_sample / _evolve / _observe,
+ * gple_grid_survey and gple_grid_reconstruct / _cross.  The two-level entry points gple_pes_adiabatic and gple_evolve keep refusing it: they use the reference's closed
  * forms and operation order, of which a table has none; gple_evolve_n at num_pes = 2 reproduces gple_evolve to rounding and takes their place.
  * Where two surfaces of a user model touch (E_j = E_k) with F_jk != 0 the non-adiabatic coupling is infinite, as its formula says: not guarded.
  *
@@ -529,6 +530,33 @@ int gple_mqcl_evolve(gple_ctx* ctx, int num_pes, int model, const double* x, con
  * same input return the same bits. */
 int gple_mqcl_observe(gple_ctx* ctx, int num_pes, int model, const double* x, const double* p, size_t n, double mass, double dx, double dp,
 	unsigned flags, const double* rho_dia, double* rho_adia, double* averages, double* populations);
+
+/* ---- fewest-switches surface hopping (Tully, J. Chem. Phys. 93, 1061 (1990); no code of the reference's) ------------------ */
+/* An ensemble of n independent trajectories, one thread each.  A trajectory is x, p, the DIABATIC amplitudes b (num_pes (re, im) pairs), the
+ * active adiabatic surface and a status: 0 running, 1 left through x_left, 2 left through x_right.  num_pes = 2 or 3, models as gple_evolve_n
+ * (user ids included).  Arrays: x, p of n doubles; b of n x num_pes (re, im) pairs, trajectory-major; surface, status of n int.  Host pointers,
+ * or device pointers with GPLE_IO_DEVICE: the same bits either way.  Random numbers: Philox4x32-10 with key (seed low, seed high); the
+ * trajectory index of every counter is the global one, trajectory_offset + i, so a slice of an ensemble evolves to the bits it has inside the
+ * whole.  GPLE_ERR_BAD_ARG: num_pes not 2 or 3, a model gple_evolve_n would refuse, n == 0, trajectory_offset + n > 2^32, a mass, dt, sigma_x
+ * or sigma_p that is not finite and positive, x_left >= x_right (or not finite), surface0 out of range, a null array. */
+#define GPLE_HOP_REVERSE 0x2000u /* gple_hop_evolve: a frustrated hop reverses the momentum (default: it changes nothing) */
+/* Draws the ensemble: (u0, u1) = unit53 of the words (0, 1) and (2, 3) of counter (index, 0, 1, 0), rho = sqrt(-2 log(1 - u0)),
+ * x = x0 + sigma_x rho cospi(2 u1), p = p0 + sigma_p rho sinpi(2 u1); b = column surface0 of the adiabatic states at x, surface = surface0,
+ * status = 0. */
+int gple_hop_sample(gple_ctx* ctx, int num_pes, int model, size_t n, size_t trajectory_offset, unsigned long long seed, double x0, double p0,
+	double sigma_x, double sigma_p, int surface0, unsigned flags, double* x, double* p, double* b, int* surface, int* status);
+/* n_steps steps of length dt in place, numbered first_step, first_step + 1, ...: velocity Verlet on the active surface, the amplitudes by the
+ * exact exponential of the mid-point diabatic matrix, the hop decision from one uniform number of counter (index, step low word, 0, step high
+ * word), the momentum rescaled to conserve p^2 / 2 mass + E (DESIGN.md §17 has the step in full).  A trajectory that leaves (x_left, x_right)
+ * is finished and never touched again.  The call carries nothing hidden: evolve(a) then evolve(b, first_step = a) gives the bits of
+ * evolve(a + b).  n_steps <= 2^40 (0: nothing happens).  Timer: GPLE_TIMER_HOP. */
+int gple_hop_evolve(gple_ctx* ctx, int num_pes, int model, size_t n, size_t trajectory_offset, unsigned long long seed, double mass, double dt,
+	size_t first_step, size_t n_steps, double x_left, double x_right, unsigned flags, double* x, double* p, double* b, int* surface, int* status);
+/* Sums over the ensemble, taken in a fixed tree order (two calls give the same bits).  out, 4 num_pes + 3 doubles: the counts
+ * [status 0 | 1 | 2][surface] (exact integers), sum |c_k|^2 per adiabatic state k (c = C^T b at the trajectory's x), sum x, sum p,
+ * sum (p^2 / 2 mass + E_surface). */
+int gple_hop_observe(gple_ctx* ctx, int num_pes, int model, size_t n, double mass, unsigned flags, const double* x, const double* p, const double* b,
+	const int* surface, const int* status, double* out);
 
 /* generate_markov_chain (mc.cpp:118-165) for n walkers at once on the fitted distribution |cut-off prediction| of `element`:
  * num_steps Metropolis steps with uniform displacements in [-max_displacement, max_displacement) per dimension; r (2n) holds
