@@ -19,6 +19,9 @@ IO_DEVICE = 0x100
 EVOLVE_NEW_POINTS = 0x400  # gple_evolve: new_point_predict instead of a tick
 FORMAT_JOIN = 0x1000  # gple_format_g: no blank before the first number of a line
 HOP_REVERSE = 0x2000  # gple_hop_evolve: a frustrated hop reverses the momentum
+HOP_ACCUMULATE = 0x4000  # gple_hop_bin: add to acc instead of clearing it first
+HOP_BIN_ALL = 0x8000  # gple_hop_bin: finished trajectories are binned too
+TIMER_HOP_BIN = 13  # gple_timer: the bin kernel of one gple_hop_bin call
 PES_USER = 16  # GPLE_PES_USER: first id of a user potential (gple_pes_define)
 PREDICT_FULL = 0x200  # contract every test row (default: far rows whose contraction cannot move the variance are skipped)
 
@@ -272,6 +275,7 @@ CTX, FL = "ctx", "fl"
 def _signatures():
     st, i, u, sz, d, vp, ull, ip = C.c_int, C.c_int, C.c_uint, C.c_size_t, C.c_double, C.c_void_p, C.c_ulonglong, C.POINTER(C.c_int)
     szp, el, pts, opt = C.POINTER(C.c_size_t), C.POINTER(Element), C.POINTER(Points), C.POINTER(OptOptions)
+    llp = C.POINTER(C.c_longlong)
     predict = [CTX, vp, _dp, sz, u, _dp, _dp, _dp, _dp, C.POINTER(PredictScalars)]
     sharded = [CTX, vp, _dp, sz, u, i, i, vp, _dp, _dp, _dp]
     dealt = [CTX, vp, _dp, sz, u, i, i, ip, vp, _dp, _dp, _dp]
@@ -357,6 +361,8 @@ def _signatures():
         "hop_sample": (st, [CTX, i, i, sz, sz, ull, d, d, d, d, i, u, _dp, _dp, _dp, ip, ip]),
         "hop_evolve": (st, [CTX, i, i, sz, sz, ull, d, d, sz, sz, d, d, u, _dp, _dp, _dp, ip, ip]),
         "hop_observe": (st, [CTX, i, i, sz, d, u, _dp, _dp, _dp, ip, ip, _dp]),
+        "hop_bin": (st, [CTX, i, i, sz, d, d, sz, d, d, sz, u, _dp, _dp, _dp, ip, ip, llp]),
+        "hop_density": (st, [CTX, i, sz, sz, d, d, sz, u, llp, _dp]),
         # many NLML problems in one launch; the search of several planes in lock-step on it
         "nlml_batch": (st, [CTX, C.POINTER(NlmlProblem), sz, i, u, _dp, _dp, C.POINTER(_dp), ip]),
         "nlml_fit_planes": (st, [CTX, C.POINTER(NlmlFitPlane), sz, i, opt, _dp, _dp, ip, C.POINTER(_dp)]),
@@ -536,7 +542,7 @@ class Api:
     def timing(self, which):
         """(last_ms, total_ms, count) of a gple_timer: 0 = fit, 1 = predict call, 2 = fused predict kernel, 3 = derivative GEMM, 4 = Wigner kernel, 5 = MQCLE
         steps, 6 = the device work of the reconstruction entry points, 7 = the kernels of format_g, 8 = the kernels of parse_g, 9 = the products of dvr_propagator, 10 = the products of dvr_flux,
-        11 = the device work of dvr_spectrum, 12 = the step kernel of hop_evolve."""
+        11 = the device work of dvr_spectrum, 12 = the step kernel of hop_evolve, 13 = the bin kernel of hop_bin."""
         last, total, count = C.c_double(), C.c_double(), C.c_long()
         self._check(self.lib.gple_ctx_get_timing(self.ctx, which, C.byref(last), C.byref(total), C.byref(count)))
         return last.value, total.value, count.value
@@ -1032,6 +1038,62 @@ class Api:
             self.synchronize()
             return out.cpu().numpy()
         return out
+
+    @staticmethod
+    def _hop_grid(num_pes, grid):
+        """the 6-tuple (x_first, dx, n_x, p_first, dp, n_p) of hop_bin with its types, and the length of its accumulator"""
+        x_first, dx, n_x, p_first, dp, n_p = grid
+        grid = (float(x_first), float(dx), int(n_x), float(p_first), float(dp), int(n_p))
+        if grid[2] < 1 or grid[5] < 1:
+            raise ValueError("a grid has at least one point per axis")
+        return grid, (num_pes + num_pes * (num_pes - 1)) * grid[2] * grid[5] + 2
+
+    @staticmethod
+    def _hop_acc(acc, words):
+        """acc of hop_bin / hop_density as (array or tensor, pointer, flags): int64 of `words` entries, numpy or contiguous on the GPU"""
+        llp = C.POINTER(C.c_longlong)
+        if _on_device(acc):
+            if not acc.is_cuda or not acc.is_contiguous() or str(acc.dtype) != "torch.int64" or tuple(acc.shape) != (words,):
+                raise ValueError(f"a device accumulator is a contiguous int64 tensor of {words} entries on the GPU")
+            return acc, C.cast(acc.data_ptr(), llp), IO_DEVICE
+        acc = np.ascontiguousarray(acc, dtype=np.int64)
+        if acc.shape != (words,):
+            raise ValueError(f"an accumulator has {words} entries")
+        return acc, acc.ctypes.data_as(llp), 0
+
+    def hop_bin(self, num_pes, model, state, grid, acc=None, bin_all=False):
+        """gple_hop_bin: the ensemble added into the integer accumulator of grid = (x_first, dx, n_x, p_first, dp, n_p) -> acc, int64 of
+        (num_pes + num_pes (num_pes - 1)) n_x n_p + 2 entries: the count planes per active surface, the (re, im) planes of 2^32 c_a conj(c_b)
+        per pair a < b, then [binned, outside].  numpy arrays for a numpy ensemble, a tensor on the GPU for a device one.  acc=None starts from
+        zero; a given acc is added to (GPLE_HOP_ACCUMULATE): numpy returns the sum as a copy, a tensor is added to in place (asynchronously on
+        the context's stream) and returned.  bin_all: GPLE_HOP_BIN_ALL, finished trajectories too"""
+        num_pes = int(num_pes)
+        state, n = self._hop_state(num_pes, state)
+        grid, words = self._hop_grid(num_pes, grid)
+        flags = HOP_BIN_ALL if bin_all else 0
+        if acc is None:
+            acc = _like(state[0], words, np.int64)
+        else:
+            flags |= HOP_ACCUMULATE
+            if _on_device(acc) != _on_device(state[0]):
+                raise ValueError("the accumulator lives on the side the ensemble is on")
+            if not _on_device(acc):
+                acc = np.array(acc, dtype=np.int64)
+        acc, pa, _ = self._hop_acc(acc, words)
+        pointers, io = self._hop_pointers(state)
+        self._check(self.lib.gple_hop_bin(self.ctx, num_pes, int(model), n, *grid, flags | io, *pointers, pa))
+        return acc
+
+    def hop_density(self, num_pes, grid, acc, n_norm):
+        """gple_hop_density: the accumulator of hop_bin as the adiabatic density (num_pes, num_pes, n_x, n_p) complex, the phase.txt layout, on the
+        side acc is on (a tensor: asynchronously on the context's stream); n_norm: the size of the whole ensemble"""
+        num_pes = int(num_pes)
+        grid, words = self._hop_grid(num_pes, grid)
+        acc, pa, flags = self._hop_acc(acc, words)
+        rho = _like(acc, (num_pes, num_pes, grid[2], grid[5]), np.complex128)
+        (pr,), _ = _io(rho)
+        self._check(self.lib.gple_hop_density(self.ctx, num_pes, grid[2], grid[5], grid[1], grid[4], int(n_norm), flags, pa, pr))
+        return rho
 
     # ---- reconstruction of a gridded density with the NLML GP (test/main_evolve.cpp; gple_nlml_weights / gple_grid_*) -------------------------
     SURVEY_FIELDS = ("max", "min", "weight", "argmax", "population", "potential", "kinetic")

@@ -499,4 +499,78 @@ extern "C"
 		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
 		return GPLE_OK;
 	}
+
+	// n_x n_p <= GPLE_HOP_MAX_CELLS, without overflow
+	static bool hop_cells_ok(size_t n_x, size_t n_p) { return n_x >= 1 && n_p >= 1 && n_x <= GPLE_HOP_MAX_CELLS && n_p <= GPLE_HOP_MAX_CELLS / n_x; }
+
+	int gple_hop_bin(gple_ctx* ctx, int num_pes, int model, size_t n, double x_first, double dx, size_t n_x, double p_first, double dp, size_t n_p,
+		unsigned flags, const double* x, const double* p, const double* b, const int* surface, const int* status, long long* acc)
+	{
+		PesModel pes;
+		if (!ctx || !hop_size_ok(ctx, num_pes, model, n, 0, &pes) || !hop_cells_ok(n_x, n_p) || !hop_positive(dx) || !hop_positive(dp) ||
+			!std::isfinite(x_first) || !std::isfinite(p_first) || !x || !p || !b || !surface || !status || !acc)
+			return GPLE_ERR_BAD_ARG;
+		GPLE_OPEN(ctx);
+		const bool dev = flags & GPLE_IO_DEVICE, keep = flags & GPLE_HOP_ACCUMULATE;
+		const size_t words = static_cast<size_t>(hop_bin_planes(num_pes)) * n_x * n_p + 2;
+		GPLE_CALL(ctx);
+		if (!pes_resolve(ctx, num_pes, model, &pes)) return GPLE_ERR_BAD_ARG; // under the call lock, which gple_pes_undefine takes: the table outlives the enqueue
+		hipStream_t st = ctx->stream;
+		Staged xs(ctx, dev), ps(ctx, dev), bs(ctx, dev);
+		StagedInts su(ctx, dev), ss(ctx, dev);
+		Scratch sums(ctx); // a host acc: the integers in pooled memory (8 bytes each, as a double)
+		long long* a = acc;
+		if (!dev)
+		{
+			GPLE_HIP(ctx, sums.get(words));
+			a = reinterpret_cast<long long*>(sums.p);
+		}
+		GPLE_HIP(ctx, xs.in(x, n));
+		GPLE_HIP(ctx, ps.in(p, n));
+		GPLE_HIP(ctx, bs.in(b, 2 * n * num_pes));
+		GPLE_HIP(ctx, su.stage(surface, n, true, false));
+		GPLE_HIP(ctx, ss.stage(status, n, true, false));
+		if (!keep) GPLE_HIP(ctx, hipMemsetAsync(a, 0, words * sizeof(long long), st));
+		else if (!dev) GPLE_HIP(ctx, hipMemcpyAsync(a, acc, words * sizeof(long long), hipMemcpyHostToDevice, st));
+		const HopEnsemble e{num_pes, static_cast<long>(n), 0, 0, xs.p, ps.p, bs.p, su.p, ss.p};
+		const HopGrid g{x_first, dx, p_first, dp, static_cast<long>(n_x), static_cast<long>(n_p)};
+		timer_start(ctx, GPLE_TIMER_HOP_BIN);
+		const hipError_t launched = launch_hop_bin(st, e, pes, g, (flags & GPLE_HOP_BIN_ALL) != 0, a);
+		timer_stop(ctx, GPLE_TIMER_HOP_BIN); // on the error path too: no span stays open
+		GPLE_HIP(ctx, launched);
+		if (!dev)
+		{
+			GPLE_HIP(ctx, hipMemcpyAsync(acc, a, words * sizeof(long long), hipMemcpyDeviceToHost, st));
+			GPLE_HIP(ctx, hipStreamSynchronize(st));
+		}
+		return GPLE_OK;
+	}
+
+	int gple_hop_density(gple_ctx* ctx, int num_pes, size_t n_x, size_t n_p, double dx, double dp, size_t n_norm, unsigned flags, const long long* acc,
+		double* rho)
+	{
+		const double w = static_cast<double>(n_norm) * dx * dp; // left to right
+		if (!ctx || (num_pes != 2 && num_pes != 3) || !hop_cells_ok(n_x, n_p) || !hop_positive(dx) || !hop_positive(dp) || n_norm == 0 || !hop_positive(w) ||
+			!acc || !rho)
+			return GPLE_ERR_BAD_ARG;
+		GPLE_OPEN(ctx);
+		const bool dev = flags & GPLE_IO_DEVICE;
+		const size_t cells = n_x * n_p, words = static_cast<size_t>(hop_bin_planes(num_pes)) * cells + 2;
+		GPLE_CALL(ctx);
+		hipStream_t st = ctx->stream;
+		Staged r(ctx, dev);
+		Scratch sums(ctx);
+		const long long* a = acc;
+		GPLE_HIP(ctx, r.out(rho, 2 * static_cast<size_t>(num_pes) * num_pes * cells));
+		if (!dev)
+		{
+			GPLE_HIP(ctx, sums.get(words));
+			GPLE_HIP(ctx, hipMemcpyAsync(sums.p, acc, words * sizeof(long long), hipMemcpyHostToDevice, st));
+			a = reinterpret_cast<const long long*>(sums.p);
+		}
+		GPLE_HIP(ctx, launch_hop_density(st, num_pes, static_cast<long>(cells), w, a, r.p));
+		GPLE_HIP(ctx, r.back());
+		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
+		return GPLE_OK;
+	}
 }

@@ -3,7 +3,7 @@
 // trajectory code: this is the method its three models were made to test.
 //
 // One thread per trajectory; x, p, the diabatic amplitudes b, the active surface a and everything derived from them stay in registers for all
-// the steps of a launch.  No LDS, no atomics, no device globals.  One step of length dt for a running trajectory (V, Fd = -V', E, C: the
+// the steps of a launch.  No LDS, no device globals, and no atomics but the integer ones of hop_bin_kernel below.  One step of length dt for a running trajectory (V, Fd = -V', E, C: the
 // diabatic matrix and force, the adiabatic energies and states; F = C^T Fd C, symmetrised as in gple_evolve_n.hip):
 //     1  p += F_aa(x) dt / 2,  x_new = x + p / m dt
 //     2  b <- W exp(-i lambda dt / hbar) W^T b,  (lambda, W) the Jacobi eigen-system of (V(x) + V(x_new)) / 2: exactly unitary, no coupling needed
@@ -278,6 +278,87 @@ namespace gple
 			if (lane == 0) out[q] = v;
 		}
 
+		// The ensemble's adiabatic density on a grid ("The ensemble in phase space"), first as integers: one thread per trajectory
+		// adds 1 to the count plane of its active surface and rint(2^32 c_a conj(c_b)) (re, then im) to the two planes of every pair a < b, at the
+		// cell of its nearest grid point, by no-return 64-bit integer atomics at agent scope.  Integer addition is associative: acc has the same
+		// bits whatever order the adds arrive in.  A signed term is added as its two's complement.  The two tallies are counted over the wave by a
+		// ballot first: one atomic per wave and tally
+		template <int NP, typename M>
+		__global__ void __launch_bounds__(HOP_BLOCK) hop_bin_kernel(HopEnsemble e, M model, HopGrid g, int bin_all, unsigned long long* __restrict__ acc)
+		{
+			const long i = static_cast<long>(blockIdx.x) * HOP_BLOCK + threadIdx.x;
+			const long cells = g.n_x * g.n_p;
+			bool binned = false, outside = false;
+			if (i < e.n)
+			{
+				const int a = e.surface[i], status = e.status[i];
+				if (status >= 0 && status <= 2 && a >= 0 && a < NP && (status == 0 || bin_all))
+				{
+					const double x = e.x[i], p = e.p[i];
+					// in double before the conversion, and written so that a NaN or a huge value is outside
+					const double fx = floor((x - g.x_first) / g.dx + 0.5), fp = floor((p - g.p_first) / g.dp + 0.5);
+					binned = fx >= 0.0 && fx < static_cast<double>(g.n_x) && fp >= 0.0 && fp < static_cast<double>(g.n_p);
+					outside = !binned;
+					if (binned)
+					{
+						const long cell = static_cast<long>(fx) * g.n_p + static_cast<long>(fp);
+						double bre[NP], bim[NP], cre[NP], cim[NP], E[NP];
+#pragma unroll
+						for (int k = 0; k < NP; ++k) bre[k] = e.b[2 * (NP * i + k)], bim[k] = e.b[2 * (NP * i + k) + 1];
+						Mat<NP> C, Fd;
+						adiabatic_states_n<NP>(x, model, E, C, Fd);
+						adiabatic_amplitudes<NP>(C, bre, bim, cre, cim);
+						atomicAdd(acc + a * cells + cell, 1ull);
+						unsigned long long* plane = acc + NP * cells + cell;
+#pragma unroll
+						for (int k = 0; k < NP; ++k)
+#pragma unroll
+							for (int l = k + 1; l < NP; ++l)
+							{
+								const double re = cre[k] * cre[l] + cim[k] * cim[l], im = cim[k] * cre[l] - cre[k] * cim[l];
+								atomicAdd(plane, static_cast<unsigned long long>(static_cast<long long>(rint(4294967296.0 * re))));
+								atomicAdd(plane + cells, static_cast<unsigned long long>(static_cast<long long>(rint(4294967296.0 * im))));
+								plane += 2 * cells;
+							}
+					}
+				}
+			}
+			const unsigned long long in = __ballot(binned), out = __ballot(outside);
+			if (threadIdx.x % HOP_WAVE == 0)
+			{
+				unsigned long long* tally = acc + hop_bin_planes(NP) * cells;
+				if (in) atomicAdd(tally, static_cast<unsigned long long>(__popcll(in)));
+				if (out) atomicAdd(tally + 1, static_cast<unsigned long long>(__popcll(out)));
+			}
+		}
+		// One thread per cell: the num_pes^2 planes of the phase.txt layout from the integers.  The lower triangle is formed from the negated
+		// sum (exactly the conjugate, and +0 where the sum is 0)
+		template <int NP>
+		__global__ void __launch_bounds__(HOP_BLOCK) hop_density_kernel(long cells, double w, const long long* __restrict__ acc, double* __restrict__ rho)
+		{
+			const long cell = static_cast<long>(blockIdx.x) * HOP_BLOCK + threadIdx.x;
+			if (cell >= cells) return;
+			constexpr double SCALE = 1.0 / 4294967296.0;
+#pragma unroll
+			for (int a = 0; a < NP; ++a)
+			{
+				double* d = rho + 2 * ((a * NP + a) * cells + cell);
+				d[0] = static_cast<double>(acc[a * cells + cell]) / w, d[1] = 0.0;
+			}
+			const long long* plane = acc + NP * cells + cell;
+#pragma unroll
+			for (int a = 0; a < NP; ++a)
+#pragma unroll
+				for (int b = a + 1; b < NP; ++b)
+				{
+					const long long re = plane[0], im = plane[cells];
+					double *up = rho + 2 * ((a * NP + b) * cells + cell), *lo = rho + 2 * ((b * NP + a) * cells + cell);
+					up[0] = lo[0] = static_cast<double>(re) * SCALE / w;
+					up[1] = static_cast<double>(im) * SCALE / w, lo[1] = static_cast<double>(-im) * SCALE / w;
+					plane += 2 * cells;
+				}
+		}
+
 		inline unsigned hop_blocks(long n) { return static_cast<unsigned>((n + HOP_BLOCK - 1) / HOP_BLOCK); }
 	} // namespace
 
@@ -315,6 +396,26 @@ namespace gple
 		if (err != hipSuccess) return err;
 		const int width = 4 * e.num_pes + 3;
 		hipLaunchKernelGGL(hop_observe_finish_kernel, dim3(width), dim3(HOP_WAVE), 0, s, work, static_cast<long>(grid.x) * (HOP_BLOCK / HOP_WAVE), width, out);
+		return hipGetLastError();
+	}
+	hipError_t launch_hop_bin(hipStream_t s, const HopEnsemble& e, PesModel model, const HopGrid& g, bool bin_all, long long* acc)
+	{
+		if (e.n <= 0 || g.n_x <= 0 || g.n_p <= 0) return hipErrorInvalidValue;
+		const dim3 grid(hop_blocks(e.n)), block(HOP_BLOCK);
+		unsigned long long* const words = reinterpret_cast<unsigned long long*>(acc);
+		const int all = bin_all ? 1 : 0;
+		if (e.num_pes == 2) with_model(model, [&](auto m) { hipLaunchKernelGGL((hop_bin_kernel<2, decltype(m)>), grid, block, 0, s, e, m, g, all, words); });
+		else if (e.num_pes == 3) with_model(model, [&](auto m) { hipLaunchKernelGGL((hop_bin_kernel<3, decltype(m)>), grid, block, 0, s, e, m, g, all, words); });
+		else return hipErrorInvalidValue;
+		return hipGetLastError();
+	}
+	hipError_t launch_hop_density(hipStream_t s, int num_pes, long cells, double w, const long long* acc, double* rho)
+	{
+		if (cells <= 0) return hipErrorInvalidValue;
+		const dim3 grid(hop_blocks(cells)), block(HOP_BLOCK);
+		if (num_pes == 2) hipLaunchKernelGGL(hop_density_kernel<2>, grid, block, 0, s, cells, w, acc, rho);
+		else if (num_pes == 3) hipLaunchKernelGGL(hop_density_kernel<3>, grid, block, 0, s, cells, w, acc, rho);
+		else return hipErrorInvalidValue;
 		return hipGetLastError();
 	}
 } // namespace gple

@@ -432,6 +432,18 @@ namespace gple
 	// out: 4 num_pes + 3 sums (include/gple.h), from one partial row per wave of the first stage in work (hop_observe_work_doubles)
 	size_t hop_observe_work_doubles(int num_pes, long n);
 	hipError_t launch_hop_observe(hipStream_t s, const HopEnsemble& e, PesModel model, double mass, double* work, double* out);
+	// the uniform grid of gple_hop_bin: a point belongs to its nearest grid point, floor((x - x_first) / dx + 0.5) and the same for p
+	struct HopGrid
+	{
+		double x_first, dx, p_first, dp;
+		long n_x, n_p;
+	};
+	// planes of n_x n_p integers in acc, before its two tallies [binned, outside]: num_pes counts, then (re, im) per pair a < b
+	constexpr int hop_bin_planes(int num_pes) { return num_pes + num_pes * (num_pes - 1); }
+	// adds the selected trajectories (status 0, or every valid status with bin_all) to acc by 64-bit integer atomics: any order, the same bits
+	hipError_t launch_hop_bin(hipStream_t s, const HopEnsemble& e, PesModel model, const HopGrid& g, bool bin_all, long long* acc);
+	// rho (num_pes^2 planes of n_x n_p (re, im) pairs) from acc: counts / w, coherence sums 2^-32 / w
+	hipError_t launch_hop_density(hipStream_t s, int num_pes, long cells, double w, const long long* acc, double* rho);
 
 	// ---- reconstruction of a gridded density (gple_recon.hip; test/gpr.cpp): num_pes = 2 or 3, rho: num_pes^2 x nx x np (re, im) ----
 	constexpr int RECON_SURVEY_BLOCKS = 64, RECON_SURVEY_VALUES = 7; // row blocks of the survey, values per plane and block

@@ -3,8 +3,10 @@ and gple_hop_observe: the trajectory baseline of the same model
 run.  The reference has no trajectory code; the run's constants are those of exact.setup(boundary=ABSORBING), so its scattering line lines up
 column for column with exact.run(flux=True)'s.
 
-    unpack()   the sums of gple_hop_observe as counts, populations and means
-    run()      sample, then per output time one hop_evolve of output_step steps and one hop_observe; t.txt and averages.txt
+    unpack()          the sums of gple_hop_observe as counts, populations and means
+    phase_grid_of()   the phase-space grid of a run, from its size
+    run()             sample, then per output time one hop_evolve of output_step steps and one hop_observe; t.txt and averages.txt.  With a
+                      phase_grid also one gple_hop_bin and gple_hop_density: x.txt, p.txt and phase.txt, the adiabatic density of the ensemble
 """
 import os
 import time
@@ -32,14 +34,44 @@ def averages_line(t, rec, n_traj):
     return " ".join(exact.fmt(v) for v in [t, rec["E"], rec["x"], rec["p"], *(rec["counts"].sum(axis=0) / n_traj), *rec["populations"]]) + "\n"
 
 
+GRID_KEYS = ("x_first", "dx", "n_x", "p_first", "dp", "n_p")
+
+
+def phase_grid_of(api, num_pes, model, s, phase_grid):
+    """The grid (x_first, dx, n_x, p_first, dp, n_p) of hop_bin for the setup s.  (n_x, n_p): x_i = xmin + i dx over [xmin, xmax] and p_j over
+    [-p_max, p_max] with p_max = sqrt((p0 + 6 sigma_p)^2 + 2 m (E_max - E_min)), E the adiabatic energies on that x grid: a bound, since a
+    trajectory conserves p^2 / 2m + E_a and the sample's |p| exceeds p0 + 6 sigma_p with probability below 1e-8.  A dict gives n_x and n_p and
+    overrides any of the other four numbers."""
+    given = dict(phase_grid) if isinstance(phase_grid, dict) else dict(zip(("n_x", "n_p"), phase_grid))
+    if set(given) - set(GRID_KEYS) or "n_x" not in given or "n_p" not in given:
+        raise ValueError("phase_grid is (n_x, n_p), or a dict with n_x, n_p and any of x_first, dx, p_first, dp")
+    n_x, n_p = int(given["n_x"]), int(given["n_p"])
+    if n_x < 1 or n_p < 1 or (n_x < 2 and "dx" not in given) or (n_p < 2 and "dp" not in given):
+        raise ValueError("an axis of one point needs its spacing")
+    x_first = float(given.get("x_first", s["xmin"]))
+    dx = float(given["dx"]) if "dx" in given else (s["xmax"] - s["xmin"]) / (n_x - 1)
+    if "p_first" in given and "dp" in given:
+        p_first, dp = float(given["p_first"]), float(given["dp"])
+    else:
+        E = np.asarray(api.pes_adiabatic_n(num_pes, model, x_first + dx * np.arange(n_x))[0], dtype=np.float64)
+        p_max = float(np.sqrt((abs(s["p0"]) + 6.0 * s["sigma_p"]) ** 2 + 2.0 * s["mass"] * (E.max() - E.min())))
+        p_first = float(given.get("p_first", -p_max))
+        dp = float(given["dp"]) if "dp" in given else (p_max - p_first) / (n_p - 1)
+    return (x_first, dx, n_x, p_first, dp, n_p)
+
+
 def run(api, model=DAC, num_pes=2, ln_energy=0.0, n_traj=10000, seed=0, out_dir=None, reverse_frustrated=False, dt=None, surface0=0, max_outputs=None,
-        log=None, **setup_kw):
+        log=None, phase_grid=None, **setup_kw):
     """n_traj trajectories from the packet of exact.setup(ln_energy, boundary=ABSORBING, **setup_kw) (x0, sigma_x, p0, sigma_p, mass) on the adiabatic
     surface surface0, evolved with the time step dt (default: the setup's dt_rule, the reference's own rule) between x_left = xmin and
     x_right = xmax; a trajectory that leaves is finished and counted by side and active surface.  The ensemble stays on the device: every
     output time costs one hop_evolve of output_step = int(output_time / dt) steps and one hop_observe, whose 4 num_pes + 3 sums are all that
     crosses.  The run stops when no trajectory is running, or at total_time.  out_dir: t.txt (a time per line) and averages.txt (averages_line);
     None writes no file.  reverse_frustrated: GPLE_HOP_REVERSE.  max_outputs caps the output times (the one at t = 0 included).
+    phase_grid (phase_grid_of; None: nothing below happens): every output time also costs one hop_bin of the running trajectories, whose record
+    gains binned, outside and binned_counts (per active surface), and with out_dir one hop_density, appended to phase.txt as exact.run writes
+    it (the text made on the device where the api has format_g); x.txt and p.txt are written once.  The directory is then what
+    reconstruct.run_files reads.
     Returns the setup, the records (t and unpack() per output time), stop, and scattering_line: the head of exact.run's final line, the
     fractions that left [left | right][surface], and the fraction still running."""
     setup_kw["boundary"] = exact.ABSORBING
@@ -52,15 +84,31 @@ def run(api, model=DAC, num_pes=2, ln_energy=0.0, n_traj=10000, seed=0, out_dir=
     say = log or (lambda *_: None)
     t0 = time.perf_counter()
     state = api.hop_sample(num_pes, model, n_traj, seed, s["x0"], s["p0"], s["sigma_x"], s["sigma_p"], surface0, device_out=True)
+    grid = None if phase_grid is None else phase_grid_of(api, num_pes, model, s, phase_grid)
     files = {}
     if out_dir is not None:
         os.makedirs(out_dir, exist_ok=True)
         files = {name: open(os.path.join(out_dir, name), "w") for name in ("t.txt", "averages.txt")}
+        if grid is not None:
+            exact.write_grid(os.path.join(out_dir, "x.txt"), grid[0] + grid[1] * np.arange(grid[2]))
+            exact.write_grid(os.path.join(out_dir, "p.txt"), grid[3] + grid[4] * np.arange(grid[5]))
+            files["phase.txt"] = open(os.path.join(out_dir, "phase.txt"), "wb")
     records, stop, step = [], None, 0
     try:
         while True:
             rec = unpack(api.hop_observe(num_pes, model, state, s["mass"]), num_pes, n_traj)
             rec["t"] = step * dt
+            if grid is not None:
+                acc = api.hop_bin(num_pes, model, state, grid)
+                if files:
+                    rho = api.hop_density(num_pes, grid, acc, n_traj)
+                    files["phase.txt"].write(exact.phase_text(api, rho[None]) if hasattr(api, "format_g") else exact.phase_block(rho).encode())
+                if hasattr(acc, "is_cuda"):
+                    api.synchronize()  # the context's stream has written acc: now the framework's may read it
+                few = (acc[:num_pes * grid[2] * grid[5]].reshape(num_pes, -1).sum(1), acc[-2:])  # the only numbers of acc that cross
+                if hasattr(acc, "is_cuda"):
+                    few = tuple(v.cpu().numpy() for v in few)
+                rec["binned_counts"], (rec["binned"], rec["outside"]) = few[0], (int(v) for v in few[1])
             records.append(rec)
             if files:
                 files["t.txt"].write(exact.fmt(rec["t"]) + "\n")

@@ -157,7 +157,8 @@ typedef enum gple_timer {
 	GPLE_TIMER_DVR_POWER = 9,      /* the products of one gple_dvr_propagator call (Horner form of P4 and the binary power; no set-up, no copies); count = calls */
 	GPLE_TIMER_DVR_FLUX = 10,      /* the products of one gple_dvr_flux call (P4, the power, the loss matrix and every sandwich; no set-up, no copies); count = calls */
 	GPLE_TIMER_DVR_SPECTRUM = 11,  /* the device work of one gple_dvr_spectrum call (P4, the squarings, the thin products, the projection and the reduction; no copies); count = calls */
-	GPLE_TIMER_HOP = 12            /* the step kernel of one gple_hop_evolve call (all its steps, no staging); count = calls */
+	GPLE_TIMER_HOP = 12,           /* the step kernel of one gple_hop_evolve call (all its steps, no staging); count = calls */
+	GPLE_TIMER_HOP_BIN = 13        /* the bin kernel of one gple_hop_bin call (no staging, no clear); count = calls */
 } gple_timer;
 int gple_ctx_enable_timing(gple_ctx* ctx, int on);
 /* Synchronises the stream, then: last = milliseconds of the most recent interval; total / count = accumulated since
@@ -389,7 +390,7 @@ int gple_pes_adiabatic_n(gple_ctx* ctx, int num_pes, int model, const double* x,
  * V = V_0 + V'_0 (x - x_first), V' = V'_0, and for s > n - 1 the same from the last node.  With nodes taken from a smooth function the error is
  * at most dx^4 / 384 max|V''''| for the value and sqrt(3) / 216 dx^3 max|V''''| for the derivative.
  * A user id is accepted, on the context it was defined on and with the num_pes it was defined with (GPLE_ERR_BAD_ARG otherwise), by
- * gple_pes_adiabatic_n, gple_pes_diabatic_n, gple_evolve_n, gple_dvr_hamiltonian, gple_mqcl_transform / _evolve / _observe, gple_hop_sample / _evolve / _observe,
+ * gple_pes_adiabatic_n, gple_pes_diabatic_n, gple_evolve_n, gple_dvr_hamiltonian, gple_mqcl_transform / _evolve / _observe, gple_hop_sample / _evolve / _observe / _bin,
  * gple_grid_survey and gple_grid_reconstruct / _cross.  The two-level entry points gple_pes_adiabatic and gple_evolve keep refusing it: they use the reference's closed
  * forms and operation order, of which a table has none; gple_evolve_n at num_pes = 2 reproduces gple_evolve to rounding and takes their place.
  * Where two surfaces of a user model touch (E_j = E_k) with F_jk != 0 the non-adiabatic coupling is infinite, as its formula says: not guarded.
@@ -557,6 +558,36 @@ int gple_hop_evolve(gple_ctx* ctx, int num_pes, int model, size_t n, size_t traj
  * sum (p^2 / 2 mass + E_surface). */
 int gple_hop_observe(gple_ctx* ctx, int num_pes, int model, size_t n, double mass, unsigned flags, const double* x, const double* p, const double* b,
 	const int* surface, const int* status, double* out);
+/* The ensemble's adiabatic density matrix on a uniform phase-space grid ("The ensemble in phase space"), in two calls: the
+ * trajectories are added into an integer accumulator (gple_hop_bin), which gple_hop_density turns into the phase.txt layout.  Populations come
+ * from the active surface and coherences from the amplitudes (Landry, Falk and Subotnik, J. Chem. Phys. 139, 211101 (2013)): with c = C^T b at
+ * the trajectory's x, as gple_hop_observe forms it,
+ *     rho_aa(cell) = #{i in cell: surface_i = a} / (n_norm dx dp),   rho_ab(cell) = sum_{i in cell} c_a conj(c_b) / (n_norm dx dp)  (a < b),
+ * rho_ba = conj(rho_ab), Im rho_aa = 0 exactly.  Grid: x_k = x_first + dx k, k < n_x, and p_j = p_first + dp j, j < n_p; a point belongs to its
+ * nearest grid point, k = floor((x - x_first) / dx + 0.5) (one IEEE subtraction, division, addition and floor, compared with 0 and n_x in
+ * double: a NaN or a huge value is outside) and the same for p.
+ * acc: num_pes + num_pes (num_pes - 1) planes of n_x n_p integers (x major, p fastest), then the two tallies [binned, outside].  The first
+ * num_pes planes count the trajectories per active surface; then, per pair a < b in row-major order, two planes hold the sums of
+ * rint(2^32 Re c_a conj(c_b)) and rint(2^32 Im c_a conj(c_b)).  Why integers: integer addition is associative, so acc has the same bits on
+ * every call, whatever order the atomic adds arrive in, and a slice added to its complement with GPLE_HOP_ACCUMULATE gives the bits of the
+ * whole.  Why 2^32: |c_a conj(c_b)| <= 1/2 for a unit vector, a term is at most 2^31 in magnitude, and the 64-bit sum cannot overflow before
+ * 2^32 trajectories (the index space of an ensemble) share one cell with the same extreme term; the rounding of a term is at most 2^-33, nine
+ * orders of magnitude below the 1 / sqrt(count) noise of the estimator.
+ * gple_hop_bin: only running trajectories (status 0) are binned, or the finished ones too with GPLE_HOP_BIN_ALL.  A selected trajectory off
+ * the grid adds one to `outside` and nothing else; one whose surface or status is out of range is skipped, as gple_hop_observe skips it.  The
+ * call clears acc first, or adds to what is there with GPLE_HOP_ACCUMULATE.  Timer: GPLE_TIMER_HOP_BIN.
+ * gple_hop_density: w = (double)n_norm dx dp, left to right; a count becomes (double)count / w and a coherence sum (double)sum 2^-32 / w
+ * (conversions to nearest); the lower planes are formed from the negated sums.  rho: num_pes^2 planes of n_x x n_p (re, im) pairs, the
+ * rho_adia of gple_mqcl_observe.  With n_norm the size of the whole ensemble, sum_a sum_cells rho_aa dx dp is the fraction binned.
+ * GPLE_ERR_BAD_ARG, with nothing written: num_pes not 2 or 3, a model the other hop calls refuse, n == 0 or n > 2^32 (bin), n_norm == 0
+ * (density), n_x or n_p zero, n_x n_p > GPLE_HOP_MAX_CELLS, dx or dp (or w) not finite and positive, x_first or p_first not finite, a null array. */
+#define GPLE_HOP_ACCUMULATE 0x4000u /* gple_hop_bin: add to acc (default: acc is cleared first) */
+#define GPLE_HOP_BIN_ALL 0x8000u    /* gple_hop_bin: finished trajectories are binned too (default: status 0 only) */
+#define GPLE_HOP_MAX_CELLS 268435456ul /* 2^28 cells: 9 planes of (re, im) pairs are 36 GiB, and every index fits the kernels' long with room */
+int gple_hop_bin(gple_ctx* ctx, int num_pes, int model, size_t n, double x_first, double dx, size_t n_x, double p_first, double dp, size_t n_p,
+	unsigned flags, const double* x, const double* p, const double* b, const int* surface, const int* status, long long* acc);
+int gple_hop_density(gple_ctx* ctx, int num_pes, size_t n_x, size_t n_p, double dx, double dp, size_t n_norm, unsigned flags, const long long* acc,
+	double* rho);
 
 /* generate_markov_chain (mc.cpp:118-165) for n walkers at once on the fitted distribution |cut-off prediction| of `element`:
  * num_steps Metropolis steps with uniform displacements in [-max_displacement, max_displacement) per dimension; r (2n) holds
