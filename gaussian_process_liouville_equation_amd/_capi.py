@@ -22,6 +22,8 @@ HOP_REVERSE = 0x2000  # gple_hop_evolve: a frustrated hop reverses the momentum
 HOP_ACCUMULATE = 0x4000  # gple_hop_bin: add to acc instead of clearing it first
 HOP_BIN_ALL = 0x8000  # gple_hop_bin: finished trajectories are binned too
 TIMER_HOP_BIN = 13  # gple_timer: the bin kernel of one gple_hop_bin call
+TIMER_HOP_GROUPS = 14  # gple_timer: the step kernel of one gple_hop_evolve_groups call
+HOP_MAX_GROUPS = 65536  # GPLE_HOP_MAX_GROUPS
 PES_USER = 16  # GPLE_PES_USER: first id of a user potential (gple_pes_define)
 PREDICT_FULL = 0x200  # contract every test row (default: far rows whose contraction cannot move the variance are skipped)
 
@@ -363,6 +365,9 @@ def _signatures():
         "hop_observe": (st, [CTX, i, i, sz, d, u, _dp, _dp, _dp, ip, ip, _dp]),
         "hop_bin": (st, [CTX, i, i, sz, d, d, sz, d, d, sz, u, _dp, _dp, _dp, ip, ip, llp]),
         "hop_density": (st, [CTX, i, sz, sz, d, d, sz, u, llp, _dp]),
+        "hop_sample_groups": (st, [CTX, i, i, sz, sz, sz, ull, _dp, i, u, _dp, _dp, _dp, ip, ip]),
+        "hop_evolve_groups": (st, [CTX, i, i, sz, sz, sz, ull, d, _dp, sz, sz, d, d, u, _dp, _dp, _dp, ip, ip, ip]),
+        "hop_observe_groups": (st, [CTX, i, i, sz, sz, d, u, _dp, _dp, _dp, ip, ip, _dp]),
         # many NLML problems in one launch; the search of several planes in lock-step on it
         "nlml_batch": (st, [CTX, C.POINTER(NlmlProblem), sz, i, u, _dp, _dp, C.POINTER(_dp), ip]),
         "nlml_fit_planes": (st, [CTX, C.POINTER(NlmlFitPlane), sz, i, opt, _dp, _dp, ip, C.POINTER(_dp)]),
@@ -542,7 +547,8 @@ class Api:
     def timing(self, which):
         """(last_ms, total_ms, count) of a gple_timer: 0 = fit, 1 = predict call, 2 = fused predict kernel, 3 = derivative GEMM, 4 = Wigner kernel, 5 = MQCLE
         steps, 6 = the device work of the reconstruction entry points, 7 = the kernels of format_g, 8 = the kernels of parse_g, 9 = the products of dvr_propagator, 10 = the products of dvr_flux,
-        11 = the device work of dvr_spectrum, 12 = the step kernel of hop_evolve, 13 = the bin kernel of hop_bin."""
+        11 = the device work of dvr_spectrum, 12 = the step kernel of hop_evolve, 13 = the bin kernel of hop_bin,
+        14 = the step kernel of hop_evolve_groups."""
         last, total, count = C.c_double(), C.c_double(), C.c_long()
         self._check(self.lib.gple_ctx_get_timing(self.ctx, which, C.byref(last), C.byref(total), C.byref(count)))
         return last.value, total.value, count.value
@@ -1094,6 +1100,83 @@ class Api:
         (pr,), _ = _io(rho)
         self._check(self.lib.gple_hop_density(self.ctx, num_pes, grid[2], grid[5], grid[1], grid[4], int(n_norm), flags, pa, pr))
         return rho
+
+    # ---- grouped ensembles (gple_hop_*_groups; DESIGN.md §17, "A curve in one launch", driven by hopping.scan) --------------------------------
+    # The same five arrays with n = n_groups n_per_group trajectories, trajectory i in group i / n_per_group; packets (n_groups, 4) rows
+    # (x0, p0, sigma_x, sigma_p) and dt (n_groups,) are small numpy tables
+    @staticmethod
+    def _hop_groups(n, n_per_group):
+        n_per_group = int(n_per_group)
+        if n_per_group < 1 or n % n_per_group:
+            raise ValueError("a grouped ensemble holds a whole number of groups of n_per_group >= 1 trajectories")
+        return n // n_per_group, n_per_group
+
+    def hop_sample_groups(self, num_pes, model, n_per_group, seed, packets, surface0=0, trajectory_offset=0, device_out=False):
+        """gple_hop_sample_groups: n_per_group trajectories per row (x0, p0, sigma_x, sigma_p) of packets -> the ensemble (x, p, b, surface,
+        status) of len(packets) n_per_group trajectories.  A sigma may be 0: the coordinate is then the centre exactly.  device_out: tensors on
+        the context's device (the call has completed when it returns)"""
+        num_pes, n_per_group, packets = int(num_pes), int(n_per_group), _f64(packets)
+        if packets.ndim != 2 or packets.shape[1] != 4 or packets.shape[0] < 1 or n_per_group < 1:
+            raise ValueError("packets is (n_groups, 4) with n_groups >= 1, and a group has at least one trajectory")
+        n_groups = packets.shape[0]
+        n = n_groups * n_per_group
+        if device_out:
+            import torch
+            where = torch.device("cuda", self.device)
+            state = (torch.empty(n, dtype=torch.float64, device=where), torch.empty(n, dtype=torch.float64, device=where),
+                     torch.empty((n, num_pes), dtype=torch.complex128, device=where), torch.empty(n, dtype=torch.int32, device=where),
+                     torch.empty(n, dtype=torch.int32, device=where))
+        else:
+            state = (np.empty(n), np.empty(n), np.empty((n, num_pes), dtype=np.complex128), np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32))
+        pointers, flags = self._hop_pointers(state)
+        self._check(self.lib.gple_hop_sample_groups(self.ctx, num_pes, int(model), n_groups, n_per_group, int(trajectory_offset), int(seed), _ptr(packets),
+                                                    int(surface0), flags, *pointers))
+        if device_out:
+            self.synchronize()
+        return state
+
+    def hop_evolve_groups(self, num_pes, model, state, n_per_group, seed, mass, dt, first_step, n_steps, x_left, x_right, reverse=False, trajectory_offset=0,
+                          hops=None):
+        """gple_hop_evolve_groups: the steps first_step ... first_step + n_steps - 1 of every running trajectory, group g with the time step
+        dt[g].  numpy: returns the evolved copy; device tensors: evolves the ensemble in place (asynchronously on the context's stream) and
+        returns it.  hops (None, or int32 (n, 2) on the side the ensemble is on): the hops taken and the frustrated hops of the call are added
+        to it; the return value is then (state, hops), a numpy hops being a copy.  reverse: GPLE_HOP_REVERSE"""
+        state, n = self._hop_state(int(num_pes), state)
+        n_groups, n_per_group = self._hop_groups(n, n_per_group)
+        dt = _f64(dt)
+        if dt.shape != (n_groups,):
+            raise ValueError("dt has one time step per group")
+        dev = _on_device(state[0])
+        if not dev:
+            state = tuple(a.copy() for a in state)
+        pointers, flags = self._hop_pointers(state)
+        ip, ph = C.POINTER(C.c_int), None
+        if hops is not None:
+            if _on_device(hops) != dev:
+                raise ValueError("hops lives on the side the ensemble is on")
+            if dev:
+                if not hops.is_cuda or not hops.is_contiguous() or str(hops.dtype) != "torch.int32" or tuple(hops.shape) != (n, 2):
+                    raise ValueError("device hops is a contiguous int32 tensor of shape (n, 2) on the GPU")
+                ph = C.cast(hops.data_ptr(), ip)
+            else:
+                hops = np.array(hops, dtype=np.int32, order="C")
+                if hops.shape != (n, 2):
+                    raise ValueError("hops has shape (n, 2)")
+                ph = hops.ctypes.data_as(ip)
+        self._check(self.lib.gple_hop_evolve_groups(self.ctx, int(num_pes), int(model), n_groups, n_per_group, int(trajectory_offset), int(seed), float(mass),
+                                                    _ptr(dt), int(first_step), int(n_steps), float(x_left), float(x_right),
+                                                    flags | (HOP_REVERSE if reverse else 0), *pointers, ph))
+        return state if hops is None else (state, hops)
+
+    def hop_observe_groups(self, num_pes, model, state, n_per_group, mass):
+        """gple_hop_observe_groups -> (n_groups, 4 num_pes + 3) numpy array, row g the sums of hop_observe over group g (the same bits).  With
+        device tensors only these rows cross"""
+        state, n = self._hop_state(int(num_pes), state)
+        n_groups, n_per_group = self._hop_groups(n, n_per_group)
+        out = np.empty((n_groups, 4 * int(num_pes) + 3))
+        pointers, flags = self._hop_pointers(state)
+        self._check(self.lib.gple_hop_observe_groups(self.ctx, int(num_pes), int(model), n_groups, n_per_group, float(mass), flags, *pointers, _ptr(out)))
+        return out
 
     # ---- reconstruction of a gridded density with the NLML GP (test/main_evolve.cpp; gple_nlml_weights / gple_grid_*) -------------------------
     SURVEY_FIELDS = ("max", "min", "weight", "argmax", "population", "potential", "kinetic")

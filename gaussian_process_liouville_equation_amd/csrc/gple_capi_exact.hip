@@ -573,4 +573,125 @@ extern "C"
 		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
 		return GPLE_OK;
 	}
+
+	/* ---- grouped ensembles ("A curve in one launch") ------------------------------------------------------------------------ */
+	// n = n_groups n_per_group without overflow, within the index space together with the offset
+	static bool hop_groups_ok(gple_ctx* ctx, int num_pes, int model, size_t n_groups, size_t n_per_group, size_t offset, PesModel* pes, size_t* n)
+	{
+		if (n_groups == 0 || n_per_group == 0 || n_groups > GPLE_HOP_MAX_GROUPS || n_per_group > (size_t(1) << 32) / n_groups) return false;
+		*n = n_groups * n_per_group;
+		return hop_size_ok(ctx, num_pes, model, *n, offset, pes);
+	}
+	// a host table of a grouped call in pooled device memory.  The table is the caller's pageable memory whatever the flags say: the copy is
+	// waited for, so that the caller may free it when the call returns
+	static hipError_t hop_table(Scratch& t, const double* host, size_t count)
+	{
+		hipError_t e = t.get(count);
+		if (e != hipSuccess) return e;
+		e = hipMemcpyAsync(t.p, host, count * sizeof(double), hipMemcpyHostToDevice, t.ctx->stream);
+		return e == hipSuccess ? hipStreamSynchronize(t.ctx->stream) : e;
+	}
+
+	int gple_hop_sample_groups(gple_ctx* ctx, int num_pes, int model, size_t n_groups, size_t n_per_group, size_t trajectory_offset, unsigned long long seed,
+		const double* packets, int surface0, unsigned flags, double* x, double* p, double* b, int* surface, int* status)
+	{
+		PesModel pes;
+		size_t n = 0;
+		if (!ctx || !hop_groups_ok(ctx, num_pes, model, n_groups, n_per_group, trajectory_offset, &pes, &n) || !packets || surface0 < 0 || surface0 >= num_pes ||
+			!x || !p || !b || !surface || !status)
+			return GPLE_ERR_BAD_ARG;
+		for (size_t g = 0; g < n_groups; ++g)
+		{
+			const double* row = packets + 4 * g;
+			if (!std::isfinite(row[0]) || !std::isfinite(row[1]) || !std::isfinite(row[2]) || !std::isfinite(row[3]) || row[2] < 0.0 || row[3] < 0.0) return GPLE_ERR_BAD_ARG;
+		}
+		GPLE_OPEN(ctx);
+		const bool dev = flags & GPLE_IO_DEVICE;
+		GPLE_CALL(ctx);
+		if (!pes_resolve(ctx, num_pes, model, &pes)) return GPLE_ERR_BAD_ARG; // under the call lock, which gple_pes_undefine takes: the table outlives the enqueue
+		hipStream_t st = ctx->stream;
+		Staged xs(ctx, dev), ps(ctx, dev), bs(ctx, dev);
+		StagedInts su(ctx, dev), ss(ctx, dev);
+		Scratch table(ctx);
+		GPLE_HIP(ctx, hop_table(table, packets, 4 * n_groups));
+		GPLE_HIP(ctx, xs.out(x, n));
+		GPLE_HIP(ctx, ps.out(p, n));
+		GPLE_HIP(ctx, bs.out(b, 2 * n * num_pes));
+		GPLE_HIP(ctx, su.stage(surface, n, false, true));
+		GPLE_HIP(ctx, ss.stage(status, n, false, true));
+		const HopEnsemble e{num_pes, static_cast<long>(n), trajectory_offset, seed, xs.p, ps.p, bs.p, su.p, ss.p};
+		GPLE_HIP(ctx, launch_hop_sample_groups(st, e, pes, static_cast<long>(n_per_group), table.p, surface0));
+		for (Staged* o : {&xs, &ps, &bs}) GPLE_HIP(ctx, o->back());
+		for (StagedInts* o : {&su, &ss}) GPLE_HIP(ctx, o->back());
+		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
+		return GPLE_OK;
+	}
+
+	int gple_hop_evolve_groups(gple_ctx* ctx, int num_pes, int model, size_t n_groups, size_t n_per_group, size_t trajectory_offset, unsigned long long seed,
+		double mass, const double* dt, size_t first_step, size_t n_steps, double x_left, double x_right, unsigned flags, double* x, double* p, double* b,
+		int* surface, int* status, int* hops)
+	{
+		PesModel pes;
+		size_t n = 0;
+		if (!ctx || !hop_groups_ok(ctx, num_pes, model, n_groups, n_per_group, trajectory_offset, &pes, &n) || !hop_positive(mass) || !dt || !std::isfinite(x_left) ||
+			!std::isfinite(x_right) || !(x_left < x_right) || n_steps > (1ul << 40) || !x || !p || !b || !surface || !status)
+			return GPLE_ERR_BAD_ARG;
+		for (size_t g = 0; g < n_groups; ++g)
+			if (!hop_positive(dt[g])) return GPLE_ERR_BAD_ARG;
+		GPLE_OPEN(ctx);
+		if (n_steps == 0) return GPLE_OK;
+		const bool dev = flags & GPLE_IO_DEVICE;
+		GPLE_CALL(ctx);
+		if (!pes_resolve(ctx, num_pes, model, &pes)) return GPLE_ERR_BAD_ARG; // under the call lock, which gple_pes_undefine takes: the table outlives the enqueue
+		hipStream_t st = ctx->stream;
+		Staged xs(ctx, dev), ps(ctx, dev), bs(ctx, dev);
+		StagedInts su(ctx, dev), ss(ctx, dev), hs(ctx, dev);
+		Scratch table(ctx);
+		GPLE_HIP(ctx, hop_table(table, dt, n_groups));
+		GPLE_HIP(ctx, xs.inout(x, n));
+		GPLE_HIP(ctx, ps.inout(p, n));
+		GPLE_HIP(ctx, bs.inout(b, 2 * n * num_pes));
+		GPLE_HIP(ctx, su.stage(surface, n, true, true));
+		GPLE_HIP(ctx, ss.stage(status, n, true, true));
+		if (hops) GPLE_HIP(ctx, hs.stage(hops, 2 * n, true, true));
+		const HopEnsemble e{num_pes, static_cast<long>(n), trajectory_offset, seed, xs.p, ps.p, bs.p, su.p, ss.p};
+		timer_start(ctx, GPLE_TIMER_HOP_GROUPS);
+		const hipError_t launched = launch_hop_evolve_groups(st, e, pes, static_cast<long>(n_per_group), mass, table.p, first_step, static_cast<long>(n_steps), x_left, x_right,
+			(flags & GPLE_HOP_REVERSE) != 0, hs.p);
+		timer_stop(ctx, GPLE_TIMER_HOP_GROUPS); // on the error path too: no span stays open
+		GPLE_HIP(ctx, launched);
+		for (Staged* o : {&xs, &ps, &bs}) GPLE_HIP(ctx, o->back());
+		for (StagedInts* o : {&su, &ss, &hs}) GPLE_HIP(ctx, o->back());
+		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
+		return GPLE_OK;
+	}
+
+	int gple_hop_observe_groups(gple_ctx* ctx, int num_pes, int model, size_t n_groups, size_t n_per_group, double mass, unsigned flags, const double* x,
+		const double* p, const double* b, const int* surface, const int* status, double* out)
+	{
+		PesModel pes;
+		size_t n = 0;
+		if (!ctx || !hop_groups_ok(ctx, num_pes, model, n_groups, n_per_group, 0, &pes, &n) || !hop_positive(mass) || !x || !p || !b || !surface || !status || !out)
+			return GPLE_ERR_BAD_ARG;
+		GPLE_OPEN(ctx);
+		const bool dev = flags & GPLE_IO_DEVICE;
+		GPLE_CALL(ctx);
+		if (!pes_resolve(ctx, num_pes, model, &pes)) return GPLE_ERR_BAD_ARG; // under the call lock, which gple_pes_undefine takes: the table outlives the enqueue
+		hipStream_t st = ctx->stream;
+		Staged xs(ctx, dev), ps(ctx, dev), bs(ctx, dev), o(ctx, false); // out is a host array whatever the flags say
+		StagedInts su(ctx, dev), ss(ctx, dev);
+		Scratch work(ctx);
+		GPLE_HIP(ctx, work.get(hop_observe_groups_work_doubles(num_pes, static_cast<long>(n_groups), static_cast<long>(n_per_group))));
+		GPLE_HIP(ctx, o.out(out, n_groups * (4 * num_pes + 3)));
+		GPLE_HIP(ctx, xs.in(x, n));
+		GPLE_HIP(ctx, ps.in(p, n));
+		GPLE_HIP(ctx, bs.in(b, 2 * n * num_pes));
+		GPLE_HIP(ctx, su.stage(surface, n, true, false));
+		GPLE_HIP(ctx, ss.stage(status, n, true, false));
+		const HopEnsemble e{num_pes, static_cast<long>(n), 0, 0, xs.p, ps.p, bs.p, su.p, ss.p};
+		GPLE_HIP(ctx, launch_hop_observe_groups(st, e, pes, static_cast<long>(n_groups), static_cast<long>(n_per_group), mass, work.p, o.p));
+		GPLE_HIP(ctx, o.back());
+		GPLE_HIP(ctx, hipStreamSynchronize(st));
+		return GPLE_OK;
+	}
 }

@@ -16,6 +16,9 @@
 // Everything is invariant under flipping a column of C, so the sign convention of the adiabatic states (which flips along x) needs no tracking.
 // The states at x_new are the states at x of the next step: they are formed at one place of the loop only, so that a launch which starts at x
 // forms them with the same instructions as the launch that arrived there (evolve(a) then evolve(b) = evolve(a + b), bit for bit).
+// Grouped ensembles ("A curve in one launch"): trajectory i of n_groups n_per_group belongs to group i / n_per_group, which has
+// a packet and a time step of its own.  The plain and the grouped kernels call the same device functions per trajectory (hop_sample_one,
+// hop_evolve_one, hop_observe_terms), so the state of a group is, bit for bit, what the plain call gives for that slice.
 #include "gple_kernels.h"
 #include "gple_pes_n.h"
 #include "gple_philox.h"
@@ -87,11 +90,10 @@ namespace gple
 			}
 		}
 
-		template <int NP, typename M>
-		__global__ void __launch_bounds__(HOP_BLOCK) hop_sample_kernel(HopEnsemble e, M model, double x0, double p0, double sigma_x, double sigma_p, int surface0)
+		// One trajectory of the sample.  ZERO (the grouped call): a sigma of exactly 0 leaves the centre exactly, by a select and not by 0 * rho
+		template <int NP, typename M, bool ZERO>
+		__device__ __forceinline__ void hop_sample_one(const HopEnsemble& e, const M& model, long i, double x0, double p0, double sigma_x, double sigma_p, int surface0)
 		{
-			const long i = static_cast<long>(blockIdx.x) * HOP_BLOCK + threadIdx.x;
-			if (i >= e.n) return;
 			const unsigned long long index = e.offset + static_cast<unsigned long long>(i);
 			unsigned c[4] = {static_cast<unsigned>(index), 0u, 1u, 0u};
 			philox4x32(c, static_cast<unsigned>(e.seed), static_cast<unsigned>(e.seed >> 32));
@@ -99,7 +101,8 @@ namespace gple
 			const double rho = sqrt(-2.0 * log(1.0 - u0));
 			double sn, cs;
 			sincospi(2.0 * u1, &sn, &cs);
-			const double x = x0 + sigma_x * rho * cs, p = p0 + sigma_p * rho * sn;
+			double x = x0 + sigma_x * rho * cs, p = p0 + sigma_p * rho * sn;
+			if constexpr (ZERO) x = sigma_x == 0.0 ? x0 : x, p = sigma_p == 0.0 ? p0 : p;
 			double E[NP];
 			Mat<NP> C, Fd;
 			adiabatic_states_n<NP>(x, model, E, C, Fd);
@@ -114,14 +117,32 @@ namespace gple
 				b[2 * k] = pick<NP>(row, surface0), b[2 * k + 1] = 0.0;
 			}
 		}
-
 		template <int NP, typename M>
-		__global__ void __launch_bounds__(HOP_BLOCK) hop_evolve_kernel(HopEnsemble e, M model, double mass, double dt, unsigned long long first_step, long n_steps,
-			double x_left, double x_right, int reverse)
+		__global__ void __launch_bounds__(HOP_BLOCK) hop_sample_kernel(HopEnsemble e, M model, double x0, double p0, double sigma_x, double sigma_p, int surface0)
 		{
 			const long i = static_cast<long>(blockIdx.x) * HOP_BLOCK + threadIdx.x;
-			if (i >= e.n || e.status[i] != 0) return;
+			if (i >= e.n) return;
+			hop_sample_one<NP, M, false>(e, model, i, x0, p0, sigma_x, sigma_p, surface0);
+		}
+		// The grouped sample ("A curve in one launch"): trajectory i belongs to group i / n_per_group and draws from that group's row
+		// (x0, p0, sigma_x, sigma_p) of packets
+		template <int NP, typename M>
+		__global__ void __launch_bounds__(HOP_BLOCK) hop_sample_groups_kernel(HopEnsemble e, M model, long n_per_group, const double* __restrict__ packets, int surface0)
+		{
+			const long i = static_cast<long>(blockIdx.x) * HOP_BLOCK + threadIdx.x;
+			if (i >= e.n) return;
+			const double* const row = packets + 4 * (i / n_per_group);
+			hop_sample_one<NP, M, true>(e, model, i, row[0], row[1], row[2], row[3], surface0);
+		}
+
+		// All the steps of a launch for the running trajectory i.  COUNT (the grouped call): step 6's two outcomes are counted in registers and
+		// added to hops[2 i], hops[2 i + 1] at the end, where hops is not null
+		template <int NP, typename M, bool COUNT>
+		__device__ __forceinline__ void hop_evolve_one(const HopEnsemble& e, const M& model, long i, double mass, double dt, unsigned long long first_step, long n_steps,
+			double x_left, double x_right, int reverse, int* hops)
+		{
 			double x = e.x[i], p = e.p[i], bre[NP], bim[NP];
+			int taken = 0, frustrated = 0;
 			int a = e.surface[i], status = 0;
 			double* const b = e.b + 2 * NP * i;
 #pragma unroll
@@ -215,6 +236,7 @@ namespace gple
 						const double r = p * p + 2.0 * mass * (Ea - pick<NP>(st.E, target));
 						if (r >= 0.0) p = sgn_n(p) * sqrt(r), a = target;
 						else if (reverse) p = -p;
+						if constexpr (COUNT) taken += r >= 0.0 ? 1 : 0, frustrated += r >= 0.0 ? 0 : 1;
 					}
 					// 7
 					if (x < x_left) status = 1;
@@ -227,10 +249,71 @@ namespace gple
 			e.x[i] = x, e.p[i] = p, e.surface[i] = a, e.status[i] = status;
 #pragma unroll
 			for (int k = 0; k < NP; ++k) b[2 * k] = bre[k], b[2 * k + 1] = bim[k];
+			if constexpr (COUNT)
+				if (hops) hops[2 * i] += taken, hops[2 * i + 1] += frustrated;
+		}
+		template <int NP, typename M>
+		__global__ void __launch_bounds__(HOP_BLOCK) hop_evolve_kernel(HopEnsemble e, M model, double mass, double dt, unsigned long long first_step, long n_steps,
+			double x_left, double x_right, int reverse)
+		{
+			const long i = static_cast<long>(blockIdx.x) * HOP_BLOCK + threadIdx.x;
+			if (i >= e.n || e.status[i] != 0) return;
+			hop_evolve_one<NP, M, false>(e, model, i, mass, dt, first_step, n_steps, x_left, x_right, reverse, nullptr);
+		}
+		// The grouped step: the same trajectory code with the time step of the trajectory's group, dt[i / n_per_group], one load
+		template <int NP, typename M>
+		__global__ void __launch_bounds__(HOP_BLOCK) hop_evolve_groups_kernel(HopEnsemble e, M model, long n_per_group, double mass, const double* __restrict__ dt,
+			unsigned long long first_step, long n_steps, double x_left, double x_right, int reverse, int* hops)
+		{
+			const long i = static_cast<long>(blockIdx.x) * HOP_BLOCK + threadIdx.x;
+			if (i >= e.n || e.status[i] != 0) return;
+			hop_evolve_one<NP, M, true>(e, model, i, mass, dt[i / n_per_group], first_step, n_steps, x_left, x_right, reverse, hops);
 		}
 
-		// First stage of the sums: the 4 NP + 3 terms of every trajectory, added over each wave by a butterfly of lane exchanges (every lane of a
-		// launched wave takes part; lanes beyond n hold zeros), one row of partial per wave
+		// The 4 NP + 3 terms of trajectory i (include/gple.h, gple_hop_observe)
+		template <int NP, typename M>
+		__device__ __forceinline__ void hop_observe_terms(const HopEnsemble& e, const M& model, double mass, long i, double (&t)[4 * NP + 3])
+		{
+			const double x = e.x[i], p = e.p[i];
+			const int a = e.surface[i], status = e.status[i];
+			double bre[NP], bim[NP], cre[NP], cim[NP], E[NP];
+#pragma unroll
+			for (int k = 0; k < NP; ++k) bre[k] = e.b[2 * (NP * i + k)], bim[k] = e.b[2 * (NP * i + k) + 1];
+			Mat<NP> C, Fd;
+			adiabatic_states_n<NP>(x, model, E, C, Fd);
+			adiabatic_amplitudes<NP>(C, bre, bim, cre, cim);
+			const int cell = status >= 0 && status <= 2 && a >= 0 && a < NP ? status * NP + a : -1;
+#pragma unroll
+			for (int q = 0; q < 3 * NP; ++q) t[q] = q == cell ? 1.0 : 0.0;
+#pragma unroll
+			for (int k = 0; k < NP; ++k) t[3 * NP + k] = cre[k] * cre[k] + cim[k] * cim[k];
+			t[4 * NP] = x, t[4 * NP + 1] = p, t[4 * NP + 2] = p * p / 2.0 / mass + pick<NP>(E, a);
+		}
+		// every term added over the wave by a butterfly of lane exchanges (every lane of a launched wave takes part); lane 0 writes the row
+		template <int WIDTH>
+		__device__ __forceinline__ void hop_wave_sums(const double (&t)[WIDTH], double* __restrict__ row)
+		{
+			const int lane = threadIdx.x % HOP_WAVE;
+#pragma unroll
+			for (int q = 0; q < WIDTH; ++q)
+			{
+				double v = t[q];
+#pragma unroll
+				for (int m = HOP_WAVE / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m, HOP_WAVE);
+				if (lane == 0) row[q] = v;
+			}
+		}
+		// column q of `rows` partial rows: lane l adds the rows l, l + 64, ... in ascending order, then the same butterfly
+		__device__ __forceinline__ double hop_column_sum(const double* __restrict__ partial, long rows, int width, int q, int lane)
+		{
+			double v = 0.0;
+			for (long r = lane; r < rows; r += HOP_WAVE) v += partial[r * width + q];
+#pragma unroll
+			for (int m = HOP_WAVE / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m, HOP_WAVE);
+			return v;
+		}
+
+		// First stage of the sums: the 4 NP + 3 terms of every trajectory, added over each wave (lanes beyond n hold zeros), one row of partial per wave
 		template <int NP, typename M>
 		__global__ void __launch_bounds__(HOP_BLOCK) hop_observe_kernel(HopEnsemble e, M model, double mass, double* __restrict__ partial)
 		{
@@ -239,43 +322,36 @@ namespace gple
 			double t[WIDTH];
 #pragma unroll
 			for (int q = 0; q < WIDTH; ++q) t[q] = 0.0;
-			if (i < e.n)
-			{
-				const double x = e.x[i], p = e.p[i];
-				const int a = e.surface[i], status = e.status[i];
-				double bre[NP], bim[NP], cre[NP], cim[NP], E[NP];
-#pragma unroll
-				for (int k = 0; k < NP; ++k) bre[k] = e.b[2 * (NP * i + k)], bim[k] = e.b[2 * (NP * i + k) + 1];
-				Mat<NP> C, Fd;
-				adiabatic_states_n<NP>(x, model, E, C, Fd);
-				adiabatic_amplitudes<NP>(C, bre, bim, cre, cim);
-				const int cell = status >= 0 && status <= 2 && a >= 0 && a < NP ? status * NP + a : -1;
-#pragma unroll
-				for (int q = 0; q < 3 * NP; ++q) t[q] = q == cell ? 1.0 : 0.0;
-#pragma unroll
-				for (int k = 0; k < NP; ++k) t[3 * NP + k] = cre[k] * cre[k] + cim[k] * cim[k];
-				t[4 * NP] = x, t[4 * NP + 1] = p, t[4 * NP + 2] = p * p / 2.0 / mass + pick<NP>(E, a);
-			}
-			const long wave = i / HOP_WAVE;
-			const int lane = threadIdx.x % HOP_WAVE;
-#pragma unroll
-			for (int q = 0; q < WIDTH; ++q)
-			{
-				double v = t[q];
-#pragma unroll
-				for (int m = HOP_WAVE / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m, HOP_WAVE);
-				if (lane == 0) partial[wave * WIDTH + q] = v;
-			}
+			if (i < e.n) hop_observe_terms<NP>(e, model, mass, i, t);
+			hop_wave_sums<WIDTH>(t, partial + (i / HOP_WAVE) * WIDTH);
 		}
-		// Second stage, one wave per column: lane l adds the rows l, l + 64, ... in ascending order, then the same butterfly
+		// Second stage, one wave per column
 		__global__ void __launch_bounds__(HOP_WAVE) hop_observe_finish_kernel(const double* __restrict__ partial, long rows, int width, double* __restrict__ out)
 		{
-			const int q = blockIdx.x, lane = threadIdx.x;
-			double v = 0.0;
-			for (long r = lane; r < rows; r += HOP_WAVE) v += partial[r * width + q];
+			const double v = hop_column_sum(partial, rows, width, blockIdx.x, threadIdx.x);
+			if (threadIdx.x == 0) out[blockIdx.x] = v;
+		}
+		// The grouped sums: every group has blocks_per_group workgroups of its own, so its trajectory j sits in the wave and lane it has in a plain
+		// launch over the group alone, and its rows_per_group = 4 blocks_per_group partial rows are the rows of that launch: the same tree, the same bits
+		template <int NP, typename M>
+		__global__ void __launch_bounds__(HOP_BLOCK) hop_observe_groups_kernel(HopEnsemble e, M model, long n_per_group, unsigned blocks_per_group, double mass,
+			double* __restrict__ partial)
+		{
+			constexpr int WIDTH = 4 * NP + 3;
+			const long group = blockIdx.x / blocks_per_group;
+			const long j = static_cast<long>(blockIdx.x % blocks_per_group) * HOP_BLOCK + threadIdx.x;
+			double t[WIDTH];
 #pragma unroll
-			for (int m = HOP_WAVE / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m, HOP_WAVE);
-			if (lane == 0) out[q] = v;
+			for (int q = 0; q < WIDTH; ++q) t[q] = 0.0;
+			if (j < n_per_group) hop_observe_terms<NP>(e, model, mass, group * n_per_group + j, t);
+			hop_wave_sums<WIDTH>(t, partial + (group * blocks_per_group * (HOP_BLOCK / HOP_WAVE) + j / HOP_WAVE) * WIDTH);
+		}
+		// one wave per group and column: block g width + q
+		__global__ void __launch_bounds__(HOP_WAVE) hop_observe_finish_groups_kernel(const double* __restrict__ partial, long rows_per_group, int width, double* __restrict__ out)
+		{
+			const long group = blockIdx.x / width;
+			const double v = hop_column_sum(partial + group * rows_per_group * width, rows_per_group, width, blockIdx.x % width, threadIdx.x);
+			if (threadIdx.x == 0) out[blockIdx.x] = v;
 		}
 
 		// The ensemble's adiabatic density on a grid ("The ensemble in phase space"), first as integers: one thread per trajectory
@@ -382,6 +458,53 @@ namespace gple
 		else if (e.num_pes == 3)
 			with_model(model, [&](auto m) { hipLaunchKernelGGL((hop_evolve_kernel<3, decltype(m)>), grid, block, 0, s, e, m, mass, dt, first_step, n_steps, x_left, x_right, rev); });
 		else return hipErrorInvalidValue;
+		return hipGetLastError();
+	}
+	hipError_t launch_hop_sample_groups(hipStream_t s, const HopEnsemble& e, PesModel model, long n_per_group, const double* packets, int surface0)
+	{
+		if (e.n <= 0 || n_per_group <= 0) return hipErrorInvalidValue;
+		const dim3 grid(hop_blocks(e.n)), block(HOP_BLOCK);
+		if (e.num_pes == 2) with_model(model, [&](auto m) { hipLaunchKernelGGL((hop_sample_groups_kernel<2, decltype(m)>), grid, block, 0, s, e, m, n_per_group, packets, surface0); });
+		else if (e.num_pes == 3) with_model(model, [&](auto m) { hipLaunchKernelGGL((hop_sample_groups_kernel<3, decltype(m)>), grid, block, 0, s, e, m, n_per_group, packets, surface0); });
+		else return hipErrorInvalidValue;
+		return hipGetLastError();
+	}
+	hipError_t launch_hop_evolve_groups(hipStream_t s, const HopEnsemble& e, PesModel model, long n_per_group, double mass, const double* dt, unsigned long long first_step,
+		long n_steps, double x_left, double x_right, bool reverse, int* hops)
+	{
+		if (e.n <= 0 || n_per_group <= 0) return hipErrorInvalidValue;
+		if (n_steps <= 0) return hipSuccess;
+		const dim3 grid(hop_blocks(e.n)), block(HOP_BLOCK);
+		const int rev = reverse ? 1 : 0;
+		if (e.num_pes == 2)
+			with_model(model, [&](auto m) {
+				hipLaunchKernelGGL((hop_evolve_groups_kernel<2, decltype(m)>), grid, block, 0, s, e, m, n_per_group, mass, dt, first_step, n_steps, x_left, x_right, rev, hops);
+			});
+		else if (e.num_pes == 3)
+			with_model(model, [&](auto m) {
+				hipLaunchKernelGGL((hop_evolve_groups_kernel<3, decltype(m)>), grid, block, 0, s, e, m, n_per_group, mass, dt, first_step, n_steps, x_left, x_right, rev, hops);
+			});
+		else return hipErrorInvalidValue;
+		return hipGetLastError();
+	}
+	size_t hop_observe_groups_work_doubles(int num_pes, long n_groups, long n_per_group)
+	{
+		return static_cast<size_t>(n_groups) * hop_blocks(n_per_group) * (HOP_BLOCK / HOP_WAVE) * (4 * num_pes + 3);
+	}
+	hipError_t launch_hop_observe_groups(hipStream_t s, const HopEnsemble& e, PesModel model, long n_groups, long n_per_group, double mass, double* work, double* out)
+	{
+		if (n_groups <= 0 || n_per_group <= 0 || e.n != n_groups * n_per_group) return hipErrorInvalidValue;
+		const unsigned per_group = hop_blocks(n_per_group);
+		if (static_cast<unsigned long long>(n_groups) * per_group > 0x7FFFFFFFull) return hipErrorInvalidValue;
+		const dim3 grid(static_cast<unsigned>(n_groups * per_group)), block(HOP_BLOCK);
+		if (e.num_pes == 2) with_model(model, [&](auto m) { hipLaunchKernelGGL((hop_observe_groups_kernel<2, decltype(m)>), grid, block, 0, s, e, m, n_per_group, per_group, mass, work); });
+		else if (e.num_pes == 3) with_model(model, [&](auto m) { hipLaunchKernelGGL((hop_observe_groups_kernel<3, decltype(m)>), grid, block, 0, s, e, m, n_per_group, per_group, mass, work); });
+		else return hipErrorInvalidValue;
+		hipError_t err = hipGetLastError();
+		if (err != hipSuccess) return err;
+		const int width = 4 * e.num_pes + 3;
+		hipLaunchKernelGGL(hop_observe_finish_groups_kernel, dim3(static_cast<unsigned>(n_groups * width)), dim3(HOP_WAVE), 0, s, work,
+			static_cast<long>(per_group) * (HOP_BLOCK / HOP_WAVE), width, out);
 		return hipGetLastError();
 	}
 	size_t hop_observe_work_doubles(int num_pes, long n) { return static_cast<size_t>(hop_blocks(n)) * (HOP_BLOCK / HOP_WAVE) * (4 * num_pes + 3); }

@@ -432,6 +432,15 @@ namespace gple
 	// out: 4 num_pes + 3 sums (include/gple.h), from one partial row per wave of the first stage in work (hop_observe_work_doubles)
 	size_t hop_observe_work_doubles(int num_pes, long n);
 	hipError_t launch_hop_observe(hipStream_t s, const HopEnsemble& e, PesModel model, double mass, double* work, double* out);
+	// Grouped ensembles ("A curve in one launch"): e.n = n_groups n_per_group, trajectory i belongs to group i / n_per_group.
+	// packets: n_groups rows (x0, p0, sigma_x, sigma_p), a sigma of exactly 0 gives the centre exactly; dt: n_groups time steps; hops (nullable):
+	// n x 2 ints, the hops taken and the frustrated hops of the call are added
+	hipError_t launch_hop_sample_groups(hipStream_t s, const HopEnsemble& e, PesModel model, long n_per_group, const double* packets, int surface0);
+	hipError_t launch_hop_evolve_groups(hipStream_t s, const HopEnsemble& e, PesModel model, long n_per_group, double mass, const double* dt, unsigned long long first_step,
+		long n_steps, double x_left, double x_right, bool reverse, int* hops);
+	// out: n_groups rows of 4 num_pes + 3 sums, row g with the bits of launch_hop_observe on the group alone; every group has workgroups of its own
+	size_t hop_observe_groups_work_doubles(int num_pes, long n_groups, long n_per_group);
+	hipError_t launch_hop_observe_groups(hipStream_t s, const HopEnsemble& e, PesModel model, long n_groups, long n_per_group, double mass, double* work, double* out);
 	// the uniform grid of gple_hop_bin: a point belongs to its nearest grid point, floor((x - x_first) / dx + 0.5) and the same for p
 	struct HopGrid
 	{

@@ -7,6 +7,8 @@ column for column with exact.run(flux=True)'s.
     phase_grid_of()   the phase-space grid of a run, from its size
     run()             sample, then per output time one hop_evolve of output_step steps and one hop_observe; t.txt and averages.txt.  With a
                       phase_grid also one gple_hop_bin and gple_hop_density: x.txt, p.txt and phase.txt, the adiabatic density of the ensemble
+    scan()            the branching probabilities at many momenta from one grouped ensemble (gple_hop_sample_groups / _evolve_groups /
+                      _observe_groups): a group per momentum with its own packet and time step; scan.txt
 """
 import os
 import time
@@ -131,3 +133,104 @@ def run(api, model=DAC, num_pes=2, ln_energy=0.0, n_traj=10000, seed=0, out_dir=
     line = " ".join(exact.fmt(v) for v in [head, *scattered, counts[RUNNING].sum() / n_traj])
     return dict(setup=s, dt=dt, output_step=output_step, total_step=total_step, n_traj=n_traj, records=records, stop=stop, state=state,
                 scattered=scattered.reshape(2, num_pes), scattering_line=line, stop_time=records[-1]["t"], steps=step, total_seconds=t_end - t0)
+
+
+def scan_line(values):
+    """One line of scan.txt: the head, the fractions [left | right][surface], the fraction running, their standard errors, hops and frustrated
+    hops per trajectory, the drift of the mean energy"""
+    return " ".join(exact.fmt(v) for v in values) + "\n"
+
+
+def _per_group(setup_kw, n_groups):
+    """setup_kw for every group: a list, tuple or array of n_groups values is one value per group, anything else is shared"""
+    per = [dict() for _ in range(n_groups)]
+    for key, value in setup_kw.items():
+        many = isinstance(value, (list, tuple, np.ndarray))
+        if many and len(value) != n_groups:
+            raise ValueError(f"{key} has {len(value)} values for {n_groups} groups")
+        for g in range(n_groups):
+            per[g][key] = value[g] if many else value
+    return per
+
+
+def scan(api, model=DAC, num_pes=2, ln_energies=None, momenta=None, n_per_group=10000, seed=0, fixed=True, surface0=0, dt=None, chunk_steps=4096,
+         max_steps=None, reverse_frustrated=False, out_dir=None, log=None, **setup_kw):
+    """The branching probabilities as a function of the incoming momentum, Tully's plot, from ONE ensemble of len(ln_energies) (or len(momenta))
+    groups of n_per_group trajectories.  Group g takes its constants from exact.setup(ln_energies[g], boundary=ABSORBING, **setup_kw) (momenta:
+    p0 = momenta[g] instead): x0, p0, mass, the bounds xmin and xmax, its time step dt_rule unless dt (a number, or one per group) overrides
+    it, and total_step = int(total_time / dt).  A list, tuple or array in setup_kw is one value per group.  mass, xmin and xmax must not differ
+    between groups (ValueError).  fixed=True is Tully's convention, sigma_x = sigma_p = 0: every trajectory of a point starts at x0 with
+    exactly p0, which is also what an energy-resolved exact curve (exact.run(spectrum=...)) is to be compared with; fixed=False draws from the
+    setup's packet.  The ensemble stays on the device: one hop_sample_groups, then hop_evolve_groups in launches of chunk_steps steps (which
+    bounds the length of one launch; the result does not depend on it, bit for bit), each followed by one hop_observe_groups, whose n_groups
+    rows are all that crosses.  It stops when no trajectory of any group runs, else at max_steps (default: the largest total_step).
+    Returns per group (arrays with n_groups rows): head (ln E for DAC, else p0, as run()), scattered (n_groups, 2, num_pes) the fractions
+    [left | right][surface], running, stderr (n_groups, 2 num_pes + 1) = sqrt(f (1 - f) / n_per_group) of those fractions in scan.txt's order,
+    hops and frustrated per trajectory, energy_drift = (sum E_end - sum E_start) / n_per_group, and lines (scan_line, what scan.txt holds with
+    out_dir); also setups, dt, steps, stop, state, hop_counts (the (n, 2) counters) and rows (the last hop_observe_groups)."""
+    if (ln_energies is None) == (momenta is None):
+        raise ValueError("give ln_energies or momenta, one of them")
+    given = np.atleast_1d(np.asarray(ln_energies if momenta is None else momenta, dtype=np.float64))
+    num_pes, n_groups, n_per_group, chunk_steps = int(num_pes), len(given), int(n_per_group), int(chunk_steps)
+    if given.ndim != 1 or n_groups < 1 or n_per_group < 1 or chunk_steps < 1:
+        raise ValueError("a scan has at least one group, one trajectory per group and one step per launch")
+    setup_kw["boundary"] = exact.ABSORBING
+    setups = []
+    for v, kw in zip(given, _per_group(setup_kw, n_groups)):
+        if momenta is not None:
+            kw["p0"] = float(v)
+        setups.append(exact.setup(float(v) if momenta is None else 0.0, **kw))
+    s0 = setups[0]
+    for key in ("mass", "xmin", "xmax"):
+        if any(s[key] != s0[key] for s in setups):
+            raise ValueError(f"the groups of a scan share one {key}")
+    dts = np.array([s["dt_rule"] for s in setups]) if dt is None else np.broadcast_to(np.asarray(dt, dtype=np.float64), (n_groups,)).copy()
+    total_step = [int(s["total_time"] / t) for s, t in zip(setups, dts)]
+    max_steps = max(total_step) if max_steps is None else int(max_steps)
+    packets = np.array([[s["x0"], s["p0"], 0.0 if fixed else s["sigma_x"], 0.0 if fixed else s["sigma_p"]] for s in setups])
+    say = log or (lambda *_: None)
+    t0 = time.perf_counter()
+    state = api.hop_sample_groups(num_pes, model, n_per_group, seed, packets, surface0, device_out=True)
+    on_device = hasattr(state[0], "is_cuda")
+    if on_device:
+        import torch
+        counts = torch.zeros((n_groups * n_per_group, 2), dtype=torch.int32, device=state[0].device)
+        torch.cuda.synchronize(state[0].device)  # the framework's stream has cleared the counters: now the context's may add to them
+    else:
+        counts = np.zeros((n_groups * n_per_group, 2), dtype=np.int32)
+    width, step, stop = 4 * num_pes + 3, 0, None
+    first = rows = np.asarray(api.hop_observe_groups(num_pes, model, state, n_per_group, s0["mass"]), dtype=np.float64).reshape(n_groups, width)
+    while True:
+        if rows[:, :num_pes].sum() == 0:
+            stop = f"NO TRAJECTORY IS RUNNING, STOP EVOLVING AT STEP {step}"
+            break
+        if step >= max_steps:
+            break
+        n_steps = min(chunk_steps, max_steps - step)
+        state, counts = api.hop_evolve_groups(num_pes, model, state, n_per_group, seed, s0["mass"], dts, step, n_steps, s0["xmin"], s0["xmax"],
+                                              reverse=reverse_frustrated, hops=counts)
+        step += n_steps
+        rows = np.asarray(api.hop_observe_groups(num_pes, model, state, n_per_group, s0["mass"]), dtype=np.float64).reshape(n_groups, width)
+    if on_device:
+        api.synchronize()  # the context's stream has written the counters: now the framework's may read them
+        per_group = counts.reshape(n_groups, n_per_group, 2).sum(dim=1, dtype=torch.int64).cpu().numpy()
+    else:
+        per_group = counts.reshape(n_groups, n_per_group, 2).sum(axis=1, dtype=np.int64)
+    t_end = time.perf_counter()
+    say(stop or f"STOPPED AT {max_steps} STEPS")
+    counts_by = rows[:, :3 * num_pes].reshape(n_groups, 3, num_pes)
+    scattered = counts_by[:, 1:, :] / n_per_group
+    running = counts_by[:, RUNNING, :].sum(axis=1) / n_per_group
+    fractions = np.concatenate([scattered.reshape(n_groups, 2 * num_pes), running[:, None]], axis=1)
+    stderr = np.sqrt(fractions * (1.0 - fractions) / n_per_group)
+    head = np.array([np.log(s["p0"] ** 2 / 2.0 / s["mass"]) if model == DAC else s["p0"] for s in setups])
+    hops, frustrated = per_group[:, 0] / n_per_group, per_group[:, 1] / n_per_group
+    drift = (rows[:, width - 1] - first[:, width - 1]) / n_per_group
+    lines = [scan_line([head[g], *fractions[g], *stderr[g], hops[g], frustrated[g], drift[g]]) for g in range(n_groups)]
+    if out_dir is not None:
+        os.makedirs(out_dir, exist_ok=True)
+        with open(os.path.join(out_dir, "scan.txt"), "w") as f:
+            f.write("".join(lines))
+    return dict(setups=setups, dt=dts, n_per_group=n_per_group, total_step=total_step, max_steps=max_steps, steps=step, stop=stop, state=state,
+                hop_counts=counts, rows=rows, head=head, scattered=scattered, running=running, stderr=stderr, hops=hops, frustrated=frustrated,
+                energy_drift=drift, lines=lines, total_seconds=t_end - t0)

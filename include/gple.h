@@ -158,7 +158,8 @@ typedef enum gple_timer {
 	GPLE_TIMER_DVR_FLUX = 10,      /* the products of one gple_dvr_flux call (P4, the power, the loss matrix and every sandwich; no set-up, no copies); count = calls */
 	GPLE_TIMER_DVR_SPECTRUM = 11,  /* the device work of one gple_dvr_spectrum call (P4, the squarings, the thin products, the projection and the reduction; no copies); count = calls */
 	GPLE_TIMER_HOP = 12,           /* the step kernel of one gple_hop_evolve call (all its steps, no staging); count = calls */
-	GPLE_TIMER_HOP_BIN = 13        /* the bin kernel of one gple_hop_bin call (no staging, no clear); count = calls */
+	GPLE_TIMER_HOP_BIN = 13,       /* the bin kernel of one gple_hop_bin call (no staging, no clear); count = calls */
+	GPLE_TIMER_HOP_GROUPS = 14     /* the step kernel of one gple_hop_evolve_groups call (all its steps, no staging); count = calls */
 } gple_timer;
 int gple_ctx_enable_timing(gple_ctx* ctx, int on);
 /* Synchronises the stream, then: last = milliseconds of the most recent interval; total / count = accumulated since
@@ -390,7 +391,7 @@ int gple_pes_adiabatic_n(gple_ctx* ctx, int num_pes, int model, const double* x,
  * V = V_0 + V'_0 (x - x_first), V' = V'_0, and for s > n - 1 the same from the last node.  With nodes taken from a smooth function the error is
  * at most dx^4 / 384 max|V''''| for the value and sqrt(3) / 216 dx^3 max|V''''| for the derivative.
  * A user id is accepted, on the context it was defined on and with the num_pes it was defined with (GPLE_ERR_BAD_ARG otherwise), by
- * gple_pes_adiabatic_n, gple_pes_diabatic_n, gple_evolve_n, gple_dvr_hamiltonian, gple_mqcl_transform / _evolve / _observe, gple_hop_sample / _evolve / _observe / _bin,
+ * gple_pes_adiabatic_n, gple_pes_diabatic_n, gple_evolve_n, gple_dvr_hamiltonian, gple_mqcl_transform / _evolve / _observe, gple_hop_sample / _evolve / _observe / _bin (and the _groups forms),
  * gple_grid_survey and gple_grid_reconstruct / _cross.  The two-level entry points gple_pes_adiabatic and gple_evolve keep refusing it: they use the reference's closed
  * forms and operation order, of which a table has none; gple_evolve_n at num_pes = 2 reproduces gple_evolve to rounding and takes their place.
  * Where two surfaces of a user model touch (E_j = E_k) with F_jk != 0 the non-adiabatic coupling is infinite, as its formula says: not guarded.
@@ -588,6 +589,31 @@ int gple_hop_bin(gple_ctx* ctx, int num_pes, int model, size_t n, double x_first
 	unsigned flags, const double* x, const double* p, const double* b, const int* surface, const int* status, long long* acc);
 int gple_hop_density(gple_ctx* ctx, int num_pes, size_t n_x, size_t n_p, double dx, double dp, size_t n_norm, unsigned flags, const long long* acc,
 	double* rho);
+/* Grouped ensembles ("A curve in one launch"): n = n_groups n_per_group trajectories in the same five arrays, trajectory i in
+ * group i / n_per_group, its counter index trajectory_offset + i as above: a slice made of whole groups keeps the bits it has inside the
+ * whole.  Every group has a packet and a time step of its own, so the branching probabilities at n_groups momenta take three launches.
+ * packets (n_groups rows x0, p0, sigma_x, sigma_p) and dt (n_groups) are host tables whatever flags says: the call copies them, and they are
+ * free again when it returns.  The five arrays and hops follow GPLE_IO_DEVICE; out is a host array.
+ * gple_hop_sample_groups: gple_hop_sample's counters and formulas with the group's packet.  A sigma may be 0 here (Tully's convention, every
+ * trajectory of a point at x0 with exactly p0): the coordinate is then the centre exactly, by a select.  With both sigmas positive a trajectory
+ * has the bits gple_hop_sample gives for the same global index and packet.
+ * gple_hop_evolve_groups: gple_hop_evolve's step with dt[group]; the state of group g afterwards is, bit for bit, what gple_hop_evolve gives
+ * for that slice with trajectory_offset + g n_per_group and dt[g], and evolve(a) then evolve(b, first_step = a) gives the bits of evolve(a + b).
+ * hops (nullable, n x 2 ints): the hops taken and the frustrated hops (step 6's two outcomes) of every trajectory over the steps of the call
+ * are ADDED to what is there.  Timer: GPLE_TIMER_HOP_GROUPS.
+ * gple_hop_observe_groups: out is n_groups rows of 4 num_pes + 3 sums; row g has the bits of gple_hop_observe on that slice (every group has
+ * workgroups of its own and the same fixed tree; no atomics).
+ * GPLE_ERR_BAD_ARG, with nothing written: everything the plain calls refuse; n_groups == 0, n_per_group == 0, n_groups > GPLE_HOP_MAX_GROUPS;
+ * n_groups n_per_group overflowing, or exceeding 2^32 together with trajectory_offset; a dt[g] that is not finite and positive; a packet entry
+ * that is not finite, or a negative sigma; a null table. */
+#define GPLE_HOP_MAX_GROUPS 65536ul
+int gple_hop_sample_groups(gple_ctx* ctx, int num_pes, int model, size_t n_groups, size_t n_per_group, size_t trajectory_offset, unsigned long long seed,
+	const double* packets, int surface0, unsigned flags, double* x, double* p, double* b, int* surface, int* status);
+int gple_hop_evolve_groups(gple_ctx* ctx, int num_pes, int model, size_t n_groups, size_t n_per_group, size_t trajectory_offset, unsigned long long seed,
+	double mass, const double* dt, size_t first_step, size_t n_steps, double x_left, double x_right, unsigned flags, double* x, double* p, double* b,
+	int* surface, int* status, int* hops);
+int gple_hop_observe_groups(gple_ctx* ctx, int num_pes, int model, size_t n_groups, size_t n_per_group, double mass, unsigned flags, const double* x,
+	const double* p, const double* b, const int* surface, const int* status, double* out);
 
 /* generate_markov_chain (mc.cpp:118-165) for n walkers at once on the fitted distribution |cut-off prediction| of `element`:
  * num_steps Metropolis steps with uniform displacements in [-max_displacement, max_displacement) per dimension; r (2n) holds
