@@ -24,6 +24,9 @@ HOP_BIN_ALL = 0x8000  # gple_hop_bin: finished trajectories are binned too
 TIMER_HOP_BIN = 13  # gple_timer: the bin kernel of one gple_hop_bin call
 TIMER_HOP_GROUPS = 14  # gple_timer: the step kernel of one gple_hop_evolve_groups call
 HOP_MAX_GROUPS = 65536  # GPLE_HOP_MAX_GROUPS
+# GPLE_HOP_DC_*: the decoherence correction of gple_hop_evolve_dc / gple_hop_evolve_groups_dc (step 6a), and the names Api.hop_evolve takes for them
+HOP_DC_NONE, HOP_DC_EDC, HOP_DC_COLLAPSE_HOP, HOP_DC_COLLAPSE_ATTEMPT = range(4)
+HOP_DC_NAMES = {"none": HOP_DC_NONE, "edc": HOP_DC_EDC, "collapse_hop": HOP_DC_COLLAPSE_HOP, "collapse_attempt": HOP_DC_COLLAPSE_ATTEMPT}
 PES_USER = 16  # GPLE_PES_USER: first id of a user potential (gple_pes_define)
 PREDICT_FULL = 0x200  # contract every test row (default: far rows whose contraction cannot move the variance are skipped)
 
@@ -368,6 +371,8 @@ def _signatures():
         "hop_sample_groups": (st, [CTX, i, i, sz, sz, sz, ull, _dp, i, u, _dp, _dp, _dp, ip, ip]),
         "hop_evolve_groups": (st, [CTX, i, i, sz, sz, sz, ull, d, _dp, sz, sz, d, d, u, _dp, _dp, _dp, ip, ip, ip]),
         "hop_observe_groups": (st, [CTX, i, i, sz, sz, d, u, _dp, _dp, _dp, ip, ip, _dp]),
+        "hop_evolve_dc": (st, [CTX, i, i, sz, sz, ull, d, d, sz, sz, d, d, i, d, u, _dp, _dp, _dp, ip, ip]),
+        "hop_evolve_groups_dc": (st, [CTX, i, i, sz, sz, sz, ull, d, _dp, sz, sz, d, d, i, d, u, _dp, _dp, _dp, ip, ip, ip]),
         # many NLML problems in one launch; the search of several planes in lock-step on it
         "nlml_batch": (st, [CTX, C.POINTER(NlmlProblem), sz, i, u, _dp, _dp, C.POINTER(_dp), ip]),
         "nlml_fit_planes": (st, [CTX, C.POINTER(NlmlFitPlane), sz, i, opt, _dp, _dp, ip, C.POINTER(_dp)]),
@@ -548,7 +553,7 @@ class Api:
         """(last_ms, total_ms, count) of a gple_timer: 0 = fit, 1 = predict call, 2 = fused predict kernel, 3 = derivative GEMM, 4 = Wigner kernel, 5 = MQCLE
         steps, 6 = the device work of the reconstruction entry points, 7 = the kernels of format_g, 8 = the kernels of parse_g, 9 = the products of dvr_propagator, 10 = the products of dvr_flux,
         11 = the device work of dvr_spectrum, 12 = the step kernel of hop_evolve, 13 = the bin kernel of hop_bin,
-        14 = the step kernel of hop_evolve_groups."""
+        14 = the step kernel of hop_evolve_groups (12 and 14 also with a decoherence correction)."""
         last, total, count = C.c_double(), C.c_double(), C.c_long()
         self._check(self.lib.gple_ctx_get_timing(self.ctx, which, C.byref(last), C.byref(total), C.byref(count)))
         return last.value, total.value, count.value
@@ -1021,15 +1026,32 @@ class Api:
             self.synchronize()
         return state
 
-    def hop_evolve(self, num_pes, model, state, seed, mass, dt, first_step, n_steps, x_left, x_right, reverse=False, trajectory_offset=0):
+    @staticmethod
+    def _hop_decoherence(decoherence):
+        """the GPLE_HOP_DC_* of a name of HOP_DC_NAMES or of an integer"""
+        if isinstance(decoherence, str):
+            if decoherence not in HOP_DC_NAMES:
+                raise ValueError(f"decoherence is None, an integer or one of {sorted(HOP_DC_NAMES)}")
+            return HOP_DC_NAMES[decoherence]
+        return int(decoherence)
+
+    def hop_evolve(self, num_pes, model, state, seed, mass, dt, first_step, n_steps, x_left, x_right, reverse=False, trajectory_offset=0, decoherence=None,
+                   edc_c=0.1):
         """gple_hop_evolve: the steps first_step ... first_step + n_steps - 1 of every running trajectory.  numpy: returns the evolved copy;
-        device tensors: evolves the ensemble in place (asynchronously on the context's stream) and returns it.  reverse: GPLE_HOP_REVERSE"""
+        device tensors: evolves the ensemble in place (asynchronously on the context's stream) and returns it.  reverse: GPLE_HOP_REVERSE.
+        decoherence: None is gple_hop_evolve itself; "edc", "collapse_hop", "collapse_attempt" ("none", or a GPLE_HOP_DC_* integer) go through
+        gple_hop_evolve_dc, the step with the decoherence correction 6a, edc_c (Hartree) being the constant of mode "edc" alone"""
         state, n = self._hop_state(int(num_pes), state)
         if not _on_device(state[0]):
             state = tuple(a.copy() for a in state)
         pointers, flags = self._hop_pointers(state)
-        self._check(self.lib.gple_hop_evolve(self.ctx, int(num_pes), int(model), n, int(trajectory_offset), int(seed), float(mass), float(dt), int(first_step),
-                                             int(n_steps), float(x_left), float(x_right), flags | (HOP_REVERSE if reverse else 0), *pointers))
+        head = (self.ctx, int(num_pes), int(model), n, int(trajectory_offset), int(seed), float(mass), float(dt), int(first_step), int(n_steps), float(x_left),
+                float(x_right))
+        flags |= HOP_REVERSE if reverse else 0
+        if decoherence is None:
+            self._check(self.lib.gple_hop_evolve(*head, flags, *pointers))
+        else:
+            self._check(self.lib.gple_hop_evolve_dc(*head, self._hop_decoherence(decoherence), float(edc_c), flags, *pointers))
         return state
 
     def hop_observe(self, num_pes, model, state, mass):
@@ -1136,11 +1158,12 @@ class Api:
         return state
 
     def hop_evolve_groups(self, num_pes, model, state, n_per_group, seed, mass, dt, first_step, n_steps, x_left, x_right, reverse=False, trajectory_offset=0,
-                          hops=None):
+                          hops=None, decoherence=None, edc_c=0.1):
         """gple_hop_evolve_groups: the steps first_step ... first_step + n_steps - 1 of every running trajectory, group g with the time step
         dt[g].  numpy: returns the evolved copy; device tensors: evolves the ensemble in place (asynchronously on the context's stream) and
         returns it.  hops (None, or int32 (n, 2) on the side the ensemble is on): the hops taken and the frustrated hops of the call are added
-        to it; the return value is then (state, hops), a numpy hops being a copy.  reverse: GPLE_HOP_REVERSE"""
+        to it; the return value is then (state, hops), a numpy hops being a copy.  reverse: GPLE_HOP_REVERSE.  decoherence, edc_c: as hop_evolve
+        (None is gple_hop_evolve_groups itself, anything else goes through gple_hop_evolve_groups_dc)"""
         state, n = self._hop_state(int(num_pes), state)
         n_groups, n_per_group = self._hop_groups(n, n_per_group)
         dt = _f64(dt)
@@ -1163,9 +1186,13 @@ class Api:
                 if hops.shape != (n, 2):
                     raise ValueError("hops has shape (n, 2)")
                 ph = hops.ctypes.data_as(ip)
-        self._check(self.lib.gple_hop_evolve_groups(self.ctx, int(num_pes), int(model), n_groups, n_per_group, int(trajectory_offset), int(seed), float(mass),
-                                                    _ptr(dt), int(first_step), int(n_steps), float(x_left), float(x_right),
-                                                    flags | (HOP_REVERSE if reverse else 0), *pointers, ph))
+        head = (self.ctx, int(num_pes), int(model), n_groups, n_per_group, int(trajectory_offset), int(seed), float(mass), _ptr(dt), int(first_step), int(n_steps),
+                float(x_left), float(x_right))
+        flags |= HOP_REVERSE if reverse else 0
+        if decoherence is None:
+            self._check(self.lib.gple_hop_evolve_groups(*head, flags, *pointers, ph))
+        else:
+            self._check(self.lib.gple_hop_evolve_groups_dc(*head, self._hop_decoherence(decoherence), float(edc_c), flags, *pointers, ph))
         return state if hops is None else (state, hops)
 
     def hop_observe_groups(self, num_pes, model, state, n_per_group, mass):

@@ -442,12 +442,21 @@ extern "C"
 		return GPLE_OK;
 	}
 
-	int gple_hop_evolve(gple_ctx* ctx, int num_pes, int model, size_t n, size_t trajectory_offset, unsigned long long seed, double mass, double dt,
-		size_t first_step, size_t n_steps, double x_left, double x_right, unsigned flags, double* x, double* p, double* b, int* surface, int* status)
+	// decoherence is a GPLE_HOP_DC_*, and in mode EDC edc_c is finite and not negative (it is read in that mode only)
+	static bool hop_decoherence_ok(int decoherence, double edc_c)
+	{
+		if (decoherence < GPLE_HOP_DC_NONE || decoherence > GPLE_HOP_DC_COLLAPSE_ATTEMPT) return false;
+		return decoherence != GPLE_HOP_DC_EDC || (std::isfinite(edc_c) && edc_c >= 0.0);
+	}
+
+	int gple_hop_evolve_dc(gple_ctx* ctx, int num_pes, int model, size_t n, size_t trajectory_offset, unsigned long long seed, double mass, double dt,
+		size_t first_step, size_t n_steps, double x_left, double x_right, int decoherence, double edc_c, unsigned flags, double* x, double* p, double* b,
+		int* surface, int* status)
 	{
 		PesModel pes;
 		if (!ctx || !hop_size_ok(ctx, num_pes, model, n, trajectory_offset, &pes) || !hop_positive(mass) || !hop_positive(dt) || !std::isfinite(x_left) ||
-			!std::isfinite(x_right) || !(x_left < x_right) || n_steps > (1ul << 40) || !x || !p || !b || !surface || !status)
+			!std::isfinite(x_right) || !(x_left < x_right) || n_steps > (1ul << 40) || !x || !p || !b || !surface || !status ||
+			!hop_decoherence_ok(decoherence, edc_c))
 			return GPLE_ERR_BAD_ARG;
 		GPLE_OPEN(ctx);
 		if (n_steps == 0) return GPLE_OK;
@@ -464,13 +473,20 @@ extern "C"
 		GPLE_HIP(ctx, ss.stage(status, n, true, true));
 		const HopEnsemble e{num_pes, static_cast<long>(n), trajectory_offset, seed, xs.p, ps.p, bs.p, su.p, ss.p};
 		timer_start(ctx, GPLE_TIMER_HOP);
-		const hipError_t launched = launch_hop_evolve(st, e, pes, mass, dt, first_step, static_cast<long>(n_steps), x_left, x_right, (flags & GPLE_HOP_REVERSE) != 0);
+		const hipError_t launched = launch_hop_evolve_dc(st, e, pes, mass, dt, first_step, static_cast<long>(n_steps), x_left, x_right,
+			(flags & GPLE_HOP_REVERSE) != 0, decoherence, edc_c); // GPLE_HOP_DC_NONE: the kernels gple_hop_evolve always launched
 		timer_stop(ctx, GPLE_TIMER_HOP); // on the error path too: no span stays open
 		GPLE_HIP(ctx, launched);
 		for (Staged* o : {&xs, &ps, &bs}) GPLE_HIP(ctx, o->back());
 		for (StagedInts* o : {&su, &ss}) GPLE_HIP(ctx, o->back());
 		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
 		return GPLE_OK;
+	}
+	int gple_hop_evolve(gple_ctx* ctx, int num_pes, int model, size_t n, size_t trajectory_offset, unsigned long long seed, double mass, double dt,
+		size_t first_step, size_t n_steps, double x_left, double x_right, unsigned flags, double* x, double* p, double* b, int* surface, int* status)
+	{
+		return gple_hop_evolve_dc(ctx, num_pes, model, n, trajectory_offset, seed, mass, dt, first_step, n_steps, x_left, x_right, GPLE_HOP_DC_NONE, 0.0, flags, x, p,
+			b, surface, status);
 	}
 
 	int gple_hop_observe(gple_ctx* ctx, int num_pes, int model, size_t n, double mass, unsigned flags, const double* x, const double* p, const double* b,
@@ -627,14 +643,15 @@ extern "C"
 		return GPLE_OK;
 	}
 
-	int gple_hop_evolve_groups(gple_ctx* ctx, int num_pes, int model, size_t n_groups, size_t n_per_group, size_t trajectory_offset, unsigned long long seed,
-		double mass, const double* dt, size_t first_step, size_t n_steps, double x_left, double x_right, unsigned flags, double* x, double* p, double* b,
-		int* surface, int* status, int* hops)
+	int gple_hop_evolve_groups_dc(gple_ctx* ctx, int num_pes, int model, size_t n_groups, size_t n_per_group, size_t trajectory_offset,
+		unsigned long long seed, double mass, const double* dt, size_t first_step, size_t n_steps, double x_left, double x_right, int decoherence,
+		double edc_c, unsigned flags, double* x, double* p, double* b, int* surface, int* status, int* hops)
 	{
 		PesModel pes;
 		size_t n = 0;
 		if (!ctx || !hop_groups_ok(ctx, num_pes, model, n_groups, n_per_group, trajectory_offset, &pes, &n) || !hop_positive(mass) || !dt || !std::isfinite(x_left) ||
-			!std::isfinite(x_right) || !(x_left < x_right) || n_steps > (1ul << 40) || !x || !p || !b || !surface || !status)
+			!std::isfinite(x_right) || !(x_left < x_right) || n_steps > (1ul << 40) || !x || !p || !b || !surface || !status ||
+			!hop_decoherence_ok(decoherence, edc_c))
 			return GPLE_ERR_BAD_ARG;
 		for (size_t g = 0; g < n_groups; ++g)
 			if (!hop_positive(dt[g])) return GPLE_ERR_BAD_ARG;
@@ -656,14 +673,21 @@ extern "C"
 		if (hops) GPLE_HIP(ctx, hs.stage(hops, 2 * n, true, true));
 		const HopEnsemble e{num_pes, static_cast<long>(n), trajectory_offset, seed, xs.p, ps.p, bs.p, su.p, ss.p};
 		timer_start(ctx, GPLE_TIMER_HOP_GROUPS);
-		const hipError_t launched = launch_hop_evolve_groups(st, e, pes, static_cast<long>(n_per_group), mass, table.p, first_step, static_cast<long>(n_steps), x_left, x_right,
-			(flags & GPLE_HOP_REVERSE) != 0, hs.p);
+		const hipError_t launched = launch_hop_evolve_groups_dc(st, e, pes, static_cast<long>(n_per_group), mass, table.p, first_step, static_cast<long>(n_steps), x_left,
+			x_right, (flags & GPLE_HOP_REVERSE) != 0, hs.p, decoherence, edc_c); // GPLE_HOP_DC_NONE: the kernels gple_hop_evolve_groups always launched
 		timer_stop(ctx, GPLE_TIMER_HOP_GROUPS); // on the error path too: no span stays open
 		GPLE_HIP(ctx, launched);
 		for (Staged* o : {&xs, &ps, &bs}) GPLE_HIP(ctx, o->back());
 		for (StagedInts* o : {&su, &ss, &hs}) GPLE_HIP(ctx, o->back());
 		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
 		return GPLE_OK;
+	}
+	int gple_hop_evolve_groups(gple_ctx* ctx, int num_pes, int model, size_t n_groups, size_t n_per_group, size_t trajectory_offset, unsigned long long seed,
+		double mass, const double* dt, size_t first_step, size_t n_steps, double x_left, double x_right, unsigned flags, double* x, double* p, double* b,
+		int* surface, int* status, int* hops)
+	{
+		return gple_hop_evolve_groups_dc(ctx, num_pes, model, n_groups, n_per_group, trajectory_offset, seed, mass, dt, first_step, n_steps, x_left, x_right,
+			GPLE_HOP_DC_NONE, 0.0, flags, x, p, b, surface, status, hops);
 	}
 
 	int gple_hop_observe_groups(gple_ctx* ctx, int num_pes, int model, size_t n_groups, size_t n_per_group, double mass, unsigned flags, const double* x,

@@ -12,6 +12,11 @@
 //     5  xi = unit53 of the words (0, 1) of Philox4x32-10, counter (trajectory, step low, 0, step high), key (seed low, seed high);
 //        hop to the first k != a (ascending) with xi < g_1 + ... + g_k
 //     6  r = p^2 + 2 m (E_a - E_k):  r >= 0: p = sgn(p) sqrt(r), a = k;  r < 0: frustrated, nothing changes (reverse: p = -p)
+//     6a (the instantiations with DC only; DESIGN.md §17, "Decoherence corrections") with a and p as step 6 left them, where |c_a|^2 != 0:
+//        EDC: w = 1 if edc_c == 0 else Ekin / (Ekin + edc_c), Ekin = p^2 / 2 m;  k != a: f_k = exp(-dt |E_k - E_a| w / hbar), c_k <- f_k c_k;
+//             c_a <- c_a sqrt(1 + sum_{k != a} |c_k|^2 (1 - f_k^2) / |c_a|^2)  (the old c_k: the norm the vector has is kept, no cancellation)
+//        COLLAPSE_HOP after a hop taken, COLLAPSE_ATTEMPT after every hop wanted: c_a <- c_a / |c_a|, every other c_k <- 0
+//        then b <- C c (the phase of c_a kept: invariant under the flip of a column of C)
 //     7  x < x_left: status 1, x > x_right: status 2; a finished trajectory is never touched again
 // Everything is invariant under flipping a column of C, so the sign convention of the adiabatic states (which flips along x) needs no tracking.
 // The states at x_new are the states at x of the next step: they are formed at one place of the loop only, so that a launch which starts at x
@@ -136,10 +141,11 @@ namespace gple
 		}
 
 		// All the steps of a launch for the running trajectory i.  COUNT (the grouped call): step 6's two outcomes are counted in registers and
-		// added to hops[2 i], hops[2 i + 1] at the end, where hops is not null
-		template <int NP, typename M, bool COUNT>
+		// added to hops[2 i], hops[2 i + 1] at the end, where hops is not null.  DC: step 6a, mode (a GPLE_HOP_DC_* other than NONE) being
+		// uniform over the launch; without DC neither mode nor edc_c is read, and the code is what it was before 6a existed
+		template <int NP, typename M, bool COUNT, bool DC>
 		__device__ __forceinline__ void hop_evolve_one(const HopEnsemble& e, const M& model, long i, double mass, double dt, unsigned long long first_step, long n_steps,
-			double x_left, double x_right, int reverse, int* hops)
+			double x_left, double x_right, int reverse, int* hops, int mode, double edc_c)
 		{
 			double x = e.x[i], p = e.p[i], bre[NP], bim[NP];
 			int taken = 0, frustrated = 0;
@@ -238,6 +244,48 @@ namespace gple
 						else if (reverse) p = -p;
 						if constexpr (COUNT) taken += r >= 0.0 ? 1 : 0, frustrated += r >= 0.0 ? 0 : 1;
 					}
+					// 6a
+					if constexpr (DC)
+					{
+						const double nre = pick<NP>(cre, a), nim = pick<NP>(cim, a), nn = nre * nre + nim * nim; // c_a of the surface step 6 left
+						bool changed = false;
+						if (nn != 0.0)
+						{
+							if (mode == GPLE_HOP_DC_EDC)
+							{
+								const double kinetic = p * p / 2.0 / mass, w = edc_c == 0.0 ? 1.0 : kinetic / (kinetic + edc_c), En = pick<NP>(st.E, a);
+								double lost = 0.0;
+#pragma unroll
+								for (int k = 0; k < NP; ++k)
+									if (k != a)
+									{
+										const double f = exp(-dt * fabs(st.E[k] - En) * w / HBAR_HOP);
+										lost += (cre[k] * cre[k] + cim[k] * cim[k]) * (1.0 - f * f);
+										cre[k] = f * cre[k], cim[k] = f * cim[k];
+									}
+								const double grow = sqrt(1.0 + lost / nn);
+#pragma unroll
+								for (int k = 0; k < NP; ++k) cre[k] = k == a ? cre[k] * grow : cre[k], cim[k] = k == a ? cim[k] * grow : cim[k];
+								changed = true;
+							}
+							else if (target >= 0 && (mode == GPLE_HOP_DC_COLLAPSE_ATTEMPT || a == target)) // a == target: the hop was taken (target was not a before)
+							{
+								const double length = sqrt(nn);
+#pragma unroll
+								for (int k = 0; k < NP; ++k) cre[k] = k == a ? cre[k] / length : 0.0, cim[k] = k == a ? cim[k] / length : 0.0;
+								changed = true;
+							}
+						}
+						if (changed)
+#pragma unroll
+							for (int r = 0; r < NP; ++r)
+							{
+								double re = 0.0, im = 0.0;
+#pragma unroll
+								for (int k = 0; k < NP; ++k) re += st.C.a[r][k] * cre[k], im += st.C.a[r][k] * cim[k];
+								bre[r] = re, bim[r] = im;
+							}
+					}
 					// 7
 					if (x < x_left) status = 1;
 					else if (x > x_right) status = 2;
@@ -258,7 +306,7 @@ namespace gple
 		{
 			const long i = static_cast<long>(blockIdx.x) * HOP_BLOCK + threadIdx.x;
 			if (i >= e.n || e.status[i] != 0) return;
-			hop_evolve_one<NP, M, false>(e, model, i, mass, dt, first_step, n_steps, x_left, x_right, reverse, nullptr);
+			hop_evolve_one<NP, M, false, false>(e, model, i, mass, dt, first_step, n_steps, x_left, x_right, reverse, nullptr, 0, 0.0);
 		}
 		// The grouped step: the same trajectory code with the time step of the trajectory's group, dt[i / n_per_group], one load
 		template <int NP, typename M>
@@ -267,7 +315,24 @@ namespace gple
 		{
 			const long i = static_cast<long>(blockIdx.x) * HOP_BLOCK + threadIdx.x;
 			if (i >= e.n || e.status[i] != 0) return;
-			hop_evolve_one<NP, M, true>(e, model, i, mass, dt[i / n_per_group], first_step, n_steps, x_left, x_right, reverse, hops);
+			hop_evolve_one<NP, M, true, false>(e, model, i, mass, dt[i / n_per_group], first_step, n_steps, x_left, x_right, reverse, hops, 0, 0.0);
+		}
+		// The two step kernels with step 6a: the mode is a kernel argument, the same for every lane
+		template <int NP, typename M>
+		__global__ void __launch_bounds__(HOP_BLOCK) hop_evolve_dc_kernel(HopEnsemble e, M model, double mass, double dt, unsigned long long first_step, long n_steps,
+			double x_left, double x_right, int reverse, int mode, double edc_c)
+		{
+			const long i = static_cast<long>(blockIdx.x) * HOP_BLOCK + threadIdx.x;
+			if (i >= e.n || e.status[i] != 0) return;
+			hop_evolve_one<NP, M, false, true>(e, model, i, mass, dt, first_step, n_steps, x_left, x_right, reverse, nullptr, mode, edc_c);
+		}
+		template <int NP, typename M>
+		__global__ void __launch_bounds__(HOP_BLOCK) hop_evolve_groups_dc_kernel(HopEnsemble e, M model, long n_per_group, double mass, const double* __restrict__ dt,
+			unsigned long long first_step, long n_steps, double x_left, double x_right, int reverse, int* hops, int mode, double edc_c)
+		{
+			const long i = static_cast<long>(blockIdx.x) * HOP_BLOCK + threadIdx.x;
+			if (i >= e.n || e.status[i] != 0) return;
+			hop_evolve_one<NP, M, true, true>(e, model, i, mass, dt[i / n_per_group], first_step, n_steps, x_left, x_right, reverse, hops, mode, edc_c);
 		}
 
 		// The 4 NP + 3 terms of trajectory i (include/gple.h, gple_hop_observe)
@@ -483,6 +548,47 @@ namespace gple
 		else if (e.num_pes == 3)
 			with_model(model, [&](auto m) {
 				hipLaunchKernelGGL((hop_evolve_groups_kernel<3, decltype(m)>), grid, block, 0, s, e, m, n_per_group, mass, dt, first_step, n_steps, x_left, x_right, rev, hops);
+			});
+		else return hipErrorInvalidValue;
+		return hipGetLastError();
+	}
+	hipError_t launch_hop_evolve_dc(hipStream_t s, const HopEnsemble& e, PesModel model, double mass, double dt, unsigned long long first_step, long n_steps,
+		double x_left, double x_right, bool reverse, int decoherence, double edc_c)
+	{
+		if (decoherence == GPLE_HOP_DC_NONE) return launch_hop_evolve(s, e, model, mass, dt, first_step, n_steps, x_left, x_right, reverse);
+		if (decoherence < GPLE_HOP_DC_NONE || decoherence > GPLE_HOP_DC_COLLAPSE_ATTEMPT) return hipErrorInvalidValue;
+		if (e.n <= 0 || n_steps <= 0) return hipSuccess;
+		const dim3 grid(hop_blocks(e.n)), block(HOP_BLOCK);
+		const int rev = reverse ? 1 : 0;
+		if (e.num_pes == 2)
+			with_model(model, [&](auto m) {
+				hipLaunchKernelGGL((hop_evolve_dc_kernel<2, decltype(m)>), grid, block, 0, s, e, m, mass, dt, first_step, n_steps, x_left, x_right, rev, decoherence, edc_c);
+			});
+		else if (e.num_pes == 3)
+			with_model(model, [&](auto m) {
+				hipLaunchKernelGGL((hop_evolve_dc_kernel<3, decltype(m)>), grid, block, 0, s, e, m, mass, dt, first_step, n_steps, x_left, x_right, rev, decoherence, edc_c);
+			});
+		else return hipErrorInvalidValue;
+		return hipGetLastError();
+	}
+	hipError_t launch_hop_evolve_groups_dc(hipStream_t s, const HopEnsemble& e, PesModel model, long n_per_group, double mass, const double* dt,
+		unsigned long long first_step, long n_steps, double x_left, double x_right, bool reverse, int* hops, int decoherence, double edc_c)
+	{
+		if (decoherence == GPLE_HOP_DC_NONE) return launch_hop_evolve_groups(s, e, model, n_per_group, mass, dt, first_step, n_steps, x_left, x_right, reverse, hops);
+		if (decoherence < GPLE_HOP_DC_NONE || decoherence > GPLE_HOP_DC_COLLAPSE_ATTEMPT) return hipErrorInvalidValue;
+		if (e.n <= 0 || n_per_group <= 0) return hipErrorInvalidValue;
+		if (n_steps <= 0) return hipSuccess;
+		const dim3 grid(hop_blocks(e.n)), block(HOP_BLOCK);
+		const int rev = reverse ? 1 : 0;
+		if (e.num_pes == 2)
+			with_model(model, [&](auto m) {
+				hipLaunchKernelGGL((hop_evolve_groups_dc_kernel<2, decltype(m)>), grid, block, 0, s, e, m, n_per_group, mass, dt, first_step, n_steps, x_left, x_right, rev,
+					hops, decoherence, edc_c);
+			});
+		else if (e.num_pes == 3)
+			with_model(model, [&](auto m) {
+				hipLaunchKernelGGL((hop_evolve_groups_dc_kernel<3, decltype(m)>), grid, block, 0, s, e, m, n_per_group, mass, dt, first_step, n_steps, x_left, x_right, rev,
+					hops, decoherence, edc_c);
 			});
 		else return hipErrorInvalidValue;
 		return hipGetLastError();

@@ -438,6 +438,13 @@ namespace gple
 	hipError_t launch_hop_sample_groups(hipStream_t s, const HopEnsemble& e, PesModel model, long n_per_group, const double* packets, int surface0);
 	hipError_t launch_hop_evolve_groups(hipStream_t s, const HopEnsemble& e, PesModel model, long n_per_group, double mass, const double* dt, unsigned long long first_step,
 		long n_steps, double x_left, double x_right, bool reverse, int* hops);
+	// The step with a decoherence correction ("Decoherence corrections"): decoherence is a GPLE_HOP_DC_* of include/gple.h;
+	// 0 launches the kernels of the two calls above, 1 ... 3 the instantiations with step 6a, which read the mode (wave-uniform) at run time;
+	// edc_c is read in mode 1 only
+	hipError_t launch_hop_evolve_dc(hipStream_t s, const HopEnsemble& e, PesModel model, double mass, double dt, unsigned long long first_step, long n_steps,
+		double x_left, double x_right, bool reverse, int decoherence, double edc_c);
+	hipError_t launch_hop_evolve_groups_dc(hipStream_t s, const HopEnsemble& e, PesModel model, long n_per_group, double mass, const double* dt,
+		unsigned long long first_step, long n_steps, double x_left, double x_right, bool reverse, int* hops, int decoherence, double edc_c);
 	// out: n_groups rows of 4 num_pes + 3 sums, row g with the bits of launch_hop_observe on the group alone; every group has workgroups of its own
 	size_t hop_observe_groups_work_doubles(int num_pes, long n_groups, long n_per_group);
 	hipError_t launch_hop_observe_groups(hipStream_t s, const HopEnsemble& e, PesModel model, long n_groups, long n_per_group, double mass, double* work, double* out);

@@ -9,6 +9,8 @@ column for column with exact.run(flux=True)'s.
                       phase_grid also one gple_hop_bin and gple_hop_density: x.txt, p.txt and phase.txt, the adiabatic density of the ensemble
     scan()            the branching probabilities at many momenta from one grouped ensemble (gple_hop_sample_groups / _evolve_groups /
                       _observe_groups): a group per momentum with its own packet and time step; scan.txt
+run() and scan() take decoherence = None (Tully's algorithm as it stands), "edc", "collapse_hop" or "collapse_attempt" and edc_c: the decoherence
+correction of every step (gple_hop_evolve_dc / gple_hop_evolve_groups_dc; DESIGN.md §17, "Decoherence corrections").  The files are the same.
 """
 import os
 import time
@@ -63,7 +65,7 @@ def phase_grid_of(api, num_pes, model, s, phase_grid):
 
 
 def run(api, model=DAC, num_pes=2, ln_energy=0.0, n_traj=10000, seed=0, out_dir=None, reverse_frustrated=False, dt=None, surface0=0, max_outputs=None,
-        log=None, phase_grid=None, **setup_kw):
+        log=None, phase_grid=None, decoherence=None, edc_c=0.1, **setup_kw):
     """n_traj trajectories from the packet of exact.setup(ln_energy, boundary=ABSORBING, **setup_kw) (x0, sigma_x, p0, sigma_p, mass) on the adiabatic
     surface surface0, evolved with the time step dt (default: the setup's dt_rule, the reference's own rule) between x_left = xmin and
     x_right = xmax; a trajectory that leaves is finished and counted by side and active surface.  The ensemble stays on the device: every
@@ -74,6 +76,8 @@ def run(api, model=DAC, num_pes=2, ln_energy=0.0, n_traj=10000, seed=0, out_dir=
     gains binned, outside and binned_counts (per active surface), and with out_dir one hop_density, appended to phase.txt as exact.run writes
     it (the text made on the device where the api has format_g); x.txt and p.txt are written once.  The directory is then what
     reconstruct.run_files reads.
+    decoherence (None, "edc", "collapse_hop", "collapse_attempt") and edc_c: the decoherence correction of every step; with None the api is
+    called without these keywords, otherwise both are forwarded to every hop_evolve.  The result carries both.
     Returns the setup, the records (t and unpack() per output time), stop, and scattering_line: the head of exact.run's final line, the
     fractions that left [left | right][surface], and the fraction still running."""
     setup_kw["boundary"] = exact.ABSORBING
@@ -83,6 +87,7 @@ def run(api, model=DAC, num_pes=2, ln_energy=0.0, n_traj=10000, seed=0, out_dir=
     output_step, total_step = int(s["output_time"] / dt), int(s["total_time"] / dt)
     if output_step < 1:
         raise ValueError("the output time is shorter than one time step")
+    correction = {} if decoherence is None else dict(decoherence=decoherence, edc_c=edc_c)
     say = log or (lambda *_: None)
     t0 = time.perf_counter()
     state = api.hop_sample(num_pes, model, n_traj, seed, s["x0"], s["p0"], s["sigma_x"], s["sigma_p"], surface0, device_out=True)
@@ -120,7 +125,8 @@ def run(api, model=DAC, num_pes=2, ln_energy=0.0, n_traj=10000, seed=0, out_dir=
                 break
             if step + output_step > total_step or (max_outputs is not None and len(records) >= max_outputs):
                 break
-            state = api.hop_evolve(num_pes, model, state, seed, s["mass"], dt, step, output_step, s["xmin"], s["xmax"], reverse=reverse_frustrated)
+            state = api.hop_evolve(num_pes, model, state, seed, s["mass"], dt, step, output_step, s["xmin"], s["xmax"], reverse=reverse_frustrated,
+                                   **correction)
             step += output_step
     finally:
         for f in files.values():
@@ -132,7 +138,8 @@ def run(api, model=DAC, num_pes=2, ln_energy=0.0, n_traj=10000, seed=0, out_dir=
     scattered = np.concatenate([counts[LEFT], counts[RIGHT]]) / n_traj
     line = " ".join(exact.fmt(v) for v in [head, *scattered, counts[RUNNING].sum() / n_traj])
     return dict(setup=s, dt=dt, output_step=output_step, total_step=total_step, n_traj=n_traj, records=records, stop=stop, state=state,
-                scattered=scattered.reshape(2, num_pes), scattering_line=line, stop_time=records[-1]["t"], steps=step, total_seconds=t_end - t0)
+                scattered=scattered.reshape(2, num_pes), scattering_line=line, stop_time=records[-1]["t"], steps=step, total_seconds=t_end - t0,
+                decoherence=decoherence, edc_c=edc_c)
 
 
 def scan_line(values):
@@ -154,7 +161,7 @@ def _per_group(setup_kw, n_groups):
 
 
 def scan(api, model=DAC, num_pes=2, ln_energies=None, momenta=None, n_per_group=10000, seed=0, fixed=True, surface0=0, dt=None, chunk_steps=4096,
-         max_steps=None, reverse_frustrated=False, out_dir=None, log=None, **setup_kw):
+         max_steps=None, reverse_frustrated=False, out_dir=None, log=None, decoherence=None, edc_c=0.1, **setup_kw):
     """The branching probabilities as a function of the incoming momentum, Tully's plot, from ONE ensemble of len(ln_energies) (or len(momenta))
     groups of n_per_group trajectories.  Group g takes its constants from exact.setup(ln_energies[g], boundary=ABSORBING, **setup_kw) (momenta:
     p0 = momenta[g] instead): x0, p0, mass, the bounds xmin and xmax, its time step dt_rule unless dt (a number, or one per group) overrides
@@ -164,10 +171,11 @@ def scan(api, model=DAC, num_pes=2, ln_energies=None, momenta=None, n_per_group=
     setup's packet.  The ensemble stays on the device: one hop_sample_groups, then hop_evolve_groups in launches of chunk_steps steps (which
     bounds the length of one launch; the result does not depend on it, bit for bit), each followed by one hop_observe_groups, whose n_groups
     rows are all that crosses.  It stops when no trajectory of any group runs, else at max_steps (default: the largest total_step).
+    decoherence and edc_c: as run(); with None hop_evolve_groups is called without these keywords, otherwise both are forwarded to every call.
     Returns per group (arrays with n_groups rows): head (ln E for DAC, else p0, as run()), scattered (n_groups, 2, num_pes) the fractions
     [left | right][surface], running, stderr (n_groups, 2 num_pes + 1) = sqrt(f (1 - f) / n_per_group) of those fractions in scan.txt's order,
     hops and frustrated per trajectory, energy_drift = (sum E_end - sum E_start) / n_per_group, and lines (scan_line, what scan.txt holds with
-    out_dir); also setups, dt, steps, stop, state, hop_counts (the (n, 2) counters) and rows (the last hop_observe_groups)."""
+    out_dir); also setups, dt, steps, stop, state, hop_counts (the (n, 2) counters), rows (the last hop_observe_groups), decoherence and edc_c."""
     if (ln_energies is None) == (momenta is None):
         raise ValueError("give ln_energies or momenta, one of them")
     given = np.atleast_1d(np.asarray(ln_energies if momenta is None else momenta, dtype=np.float64))
@@ -188,6 +196,7 @@ def scan(api, model=DAC, num_pes=2, ln_energies=None, momenta=None, n_per_group=
     total_step = [int(s["total_time"] / t) for s, t in zip(setups, dts)]
     max_steps = max(total_step) if max_steps is None else int(max_steps)
     packets = np.array([[s["x0"], s["p0"], 0.0 if fixed else s["sigma_x"], 0.0 if fixed else s["sigma_p"]] for s in setups])
+    correction = {} if decoherence is None else dict(decoherence=decoherence, edc_c=edc_c)
     say = log or (lambda *_: None)
     t0 = time.perf_counter()
     state = api.hop_sample_groups(num_pes, model, n_per_group, seed, packets, surface0, device_out=True)
@@ -208,7 +217,7 @@ def scan(api, model=DAC, num_pes=2, ln_energies=None, momenta=None, n_per_group=
             break
         n_steps = min(chunk_steps, max_steps - step)
         state, counts = api.hop_evolve_groups(num_pes, model, state, n_per_group, seed, s0["mass"], dts, step, n_steps, s0["xmin"], s0["xmax"],
-                                              reverse=reverse_frustrated, hops=counts)
+                                              reverse=reverse_frustrated, hops=counts, **correction)
         step += n_steps
         rows = np.asarray(api.hop_observe_groups(num_pes, model, state, n_per_group, s0["mass"]), dtype=np.float64).reshape(n_groups, width)
     if on_device:
@@ -233,4 +242,4 @@ def scan(api, model=DAC, num_pes=2, ln_energies=None, momenta=None, n_per_group=
             f.write("".join(lines))
     return dict(setups=setups, dt=dts, n_per_group=n_per_group, total_step=total_step, max_steps=max_steps, steps=step, stop=stop, state=state,
                 hop_counts=counts, rows=rows, head=head, scattered=scattered, running=running, stderr=stderr, hops=hops, frustrated=frustrated,
-                energy_drift=drift, lines=lines, total_seconds=t_end - t0)
+                energy_drift=drift, lines=lines, total_seconds=t_end - t0, decoherence=decoherence, edc_c=edc_c)

@@ -157,9 +157,9 @@ typedef enum gple_timer {
 	GPLE_TIMER_DVR_POWER = 9,      /* the products of one gple_dvr_propagator call (Horner form of P4 and the binary power; no set-up, no copies); count = calls */
 	GPLE_TIMER_DVR_FLUX = 10,      /* the products of one gple_dvr_flux call (P4, the power, the loss matrix and every sandwich; no set-up, no copies); count = calls */
 	GPLE_TIMER_DVR_SPECTRUM = 11,  /* the device work of one gple_dvr_spectrum call (P4, the squarings, the thin products, the projection and the reduction; no copies); count = calls */
-	GPLE_TIMER_HOP = 12,           /* the step kernel of one gple_hop_evolve call (all its steps, no staging); count = calls */
+	GPLE_TIMER_HOP = 12,           /* the step kernel of one gple_hop_evolve or gple_hop_evolve_dc call (all its steps, no staging); count = calls */
 	GPLE_TIMER_HOP_BIN = 13,       /* the bin kernel of one gple_hop_bin call (no staging, no clear); count = calls */
-	GPLE_TIMER_HOP_GROUPS = 14     /* the step kernel of one gple_hop_evolve_groups call (all its steps, no staging); count = calls */
+	GPLE_TIMER_HOP_GROUPS = 14     /* the step kernel of one gple_hop_evolve_groups or _groups_dc call (all its steps, no staging); count = calls */
 } gple_timer;
 int gple_ctx_enable_timing(gple_ctx* ctx, int on);
 /* Synchronises the stream, then: last = milliseconds of the most recent interval; total / count = accumulated since
@@ -614,6 +614,33 @@ int gple_hop_evolve_groups(gple_ctx* ctx, int num_pes, int model, size_t n_group
 	int* surface, int* status, int* hops);
 int gple_hop_observe_groups(gple_ctx* ctx, int num_pes, int model, size_t n_groups, size_t n_per_group, double mass, unsigned flags, const double* x,
 	const double* p, const double* b, const int* surface, const int* status, double* out);
+/* Decoherence corrections ("Decoherence corrections").  Plain fewest-switches hopping never damps the amplitudes of the surfaces
+ * a trajectory is not on (overcoherence).  gple_hop_evolve_dc and gple_hop_evolve_groups_dc are gple_hop_evolve and gple_hop_evolve_groups with
+ * a step 6a between the hop (step 6) and the bounds (step 7), selected by `decoherence`.  6a acts on c = C^T b of step 4 with the active
+ * surface a and the momentum p as step 6 left them:
+ *   GPLE_HOP_DC_NONE              nothing: the kernels and the bits of the calls without _dc.
+ *   GPLE_HOP_DC_EDC               the energy-based correction of Granucci and Persico, J. Chem. Phys. 126, 134114 (2007) (Zhu and Truhlar's
+ *                                 decay of mixing): E_kin = p^2 / 2 mass, w = 1 if edc_c == 0, else E_kin / (E_kin + edc_c); for every k != a
+ *                                 f_k = exp(-dt |E_k - E_a| w / hbar), c_k <- f_k c_k; then c_a <- c_a sqrt(1 + L / |c_a|^2) with
+ *                                 L = sum_{k != a} |c_k|^2 (1 - f_k^2) of the old c_k: the norm the vector has is conserved (not pulled to 1),
+ *                                 and the sum has no cancellation.  The papers' value is edc_c = 0.1 Hartree.
+ *   GPLE_HOP_DC_COLLAPSE_HOP      after a hop that was taken (r >= 0): c_a <- c_a / |c_a|, every other c_k <- 0.
+ *   GPLE_HOP_DC_COLLAPSE_ATTEMPT  the same after every wanted hop, taken or frustrated (then onto the unchanged a).
+ * In every mode |c_a|^2 == 0 skips 6a for that step.  Where 6a changed c, b <- C c: the phase of c_a is kept, so the step stays invariant under
+ * the flip of any column of C.  6a precedes step 7: the step on which a trajectory leaves is corrected too.  edc_c is read in mode EDC only.
+ * Everything else (arrays, counters, hops, the call identities, the timers GPLE_TIMER_HOP and GPLE_TIMER_HOP_GROUPS) is that of the calls
+ * without _dc.  GPLE_ERR_BAD_ARG, with nothing written: everything those calls refuse; decoherence outside 0 ... 3; in mode EDC an edc_c that
+ * is negative or not finite. */
+#define GPLE_HOP_DC_NONE 0
+#define GPLE_HOP_DC_EDC 1
+#define GPLE_HOP_DC_COLLAPSE_HOP 2
+#define GPLE_HOP_DC_COLLAPSE_ATTEMPT 3
+int gple_hop_evolve_dc(gple_ctx* ctx, int num_pes, int model, size_t n, size_t trajectory_offset, unsigned long long seed, double mass, double dt,
+	size_t first_step, size_t n_steps, double x_left, double x_right, int decoherence, double edc_c, unsigned flags, double* x, double* p, double* b,
+	int* surface, int* status);
+int gple_hop_evolve_groups_dc(gple_ctx* ctx, int num_pes, int model, size_t n_groups, size_t n_per_group, size_t trajectory_offset,
+	unsigned long long seed, double mass, const double* dt, size_t first_step, size_t n_steps, double x_left, double x_right, int decoherence,
+	double edc_c, unsigned flags, double* x, double* p, double* b, int* surface, int* status, int* hops);
 
 /* generate_markov_chain (mc.cpp:118-165) for n walkers at once on the fitted distribution |cut-off prediction| of `element`:
  * num_steps Metropolis steps with uniform displacements in [-max_displacement, max_displacement) per dimension; r (2n) holds
