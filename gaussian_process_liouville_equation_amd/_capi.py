@@ -23,6 +23,7 @@ HOP_ACCUMULATE = 0x4000  # gple_hop_bin: add to acc instead of clearing it first
 HOP_BIN_ALL = 0x8000  # gple_hop_bin: finished trajectories are binned too
 TIMER_HOP_BIN = 13  # gple_timer: the bin kernel of one gple_hop_bin call
 TIMER_HOP_GROUPS = 14  # gple_timer: the step kernel of one gple_hop_evolve_groups call
+TIMER_HOP_MF = 15  # gple_timer: the step kernel of one gple_hop_evolve_mf or gple_hop_evolve_groups_mf call
 HOP_MAX_GROUPS = 65536  # GPLE_HOP_MAX_GROUPS
 # GPLE_HOP_DC_*: the decoherence correction of gple_hop_evolve_dc / gple_hop_evolve_groups_dc (step 6a), and the names Api.hop_evolve takes for them
 HOP_DC_NONE, HOP_DC_EDC, HOP_DC_COLLAPSE_HOP, HOP_DC_COLLAPSE_ATTEMPT = range(4)
@@ -373,6 +374,11 @@ def _signatures():
         "hop_observe_groups": (st, [CTX, i, i, sz, sz, d, u, _dp, _dp, _dp, ip, ip, _dp]),
         "hop_evolve_dc": (st, [CTX, i, i, sz, sz, ull, d, d, sz, sz, d, d, i, d, u, _dp, _dp, _dp, ip, ip]),
         "hop_evolve_groups_dc": (st, [CTX, i, i, sz, sz, sz, ull, d, _dp, sz, sz, d, d, i, d, u, _dp, _dp, _dp, ip, ip, ip]),
+        # Ehrenfest (mean-field) trajectories
+        "hop_evolve_mf": (st, [CTX, i, i, sz, d, d, sz, d, d, u, _dp, _dp, _dp, ip]),
+        "hop_evolve_groups_mf": (st, [CTX, i, i, sz, sz, d, _dp, sz, d, d, u, _dp, _dp, _dp, ip]),
+        "hop_observe_mf": (st, [CTX, i, i, sz, d, u, _dp, _dp, _dp, ip, _dp]),
+        "hop_observe_groups_mf": (st, [CTX, i, i, sz, sz, d, u, _dp, _dp, _dp, ip, _dp]),
         # many NLML problems in one launch; the search of several planes in lock-step on it
         "nlml_batch": (st, [CTX, C.POINTER(NlmlProblem), sz, i, u, _dp, _dp, C.POINTER(_dp), ip]),
         "nlml_fit_planes": (st, [CTX, C.POINTER(NlmlFitPlane), sz, i, opt, _dp, _dp, ip, C.POINTER(_dp)]),
@@ -553,7 +559,8 @@ class Api:
         """(last_ms, total_ms, count) of a gple_timer: 0 = fit, 1 = predict call, 2 = fused predict kernel, 3 = derivative GEMM, 4 = Wigner kernel, 5 = MQCLE
         steps, 6 = the device work of the reconstruction entry points, 7 = the kernels of format_g, 8 = the kernels of parse_g, 9 = the products of dvr_propagator, 10 = the products of dvr_flux,
         11 = the device work of dvr_spectrum, 12 = the step kernel of hop_evolve, 13 = the bin kernel of hop_bin,
-        14 = the step kernel of hop_evolve_groups (12 and 14 also with a decoherence correction)."""
+        14 = the step kernel of hop_evolve_groups (12 and 14 also with a decoherence correction), 15 = the step kernel of hop_evolve_mf and
+        hop_evolve_groups_mf."""
         last, total, count = C.c_double(), C.c_double(), C.c_long()
         self._check(self.lib.gple_ctx_get_timing(self.ctx, which, C.byref(last), C.byref(total), C.byref(count)))
         return last.value, total.value, count.value
@@ -1203,6 +1210,68 @@ class Api:
         out = np.empty((n_groups, 4 * int(num_pes) + 3))
         pointers, flags = self._hop_pointers(state)
         self._check(self.lib.gple_hop_observe_groups(self.ctx, int(num_pes), int(model), n_groups, n_per_group, float(mass), flags, *pointers, _ptr(out)))
+        return out
+
+    # ---- Ehrenfest (mean-field) trajectories (gple_hop_*_mf; DESIGN.md §17, "Mean-field (Ehrenfest) trajectories") ------------------------------
+    # The ensemble is the 5-tuple hop_sample returns.  A mean-field trajectory has no active surface: `surface` is never passed down and comes
+    # back as the object it was
+    @staticmethod
+    def _hop_mf_pointers(state):
+        """the pointers of x, p, b, status (no surface) and the io flags"""
+        (px, pp, pb), flags = _io(*state[:3])
+        ip = C.POINTER(C.c_int)
+        return [px, pp, pb, C.cast(state[4].data_ptr(), ip) if flags else state[4].ctypes.data_as(ip)], flags
+
+    def _hop_mf_state(self, num_pes, state, copy):
+        """the checked ensemble with the caller's own surface object in it; copy: numpy x, p, b, status are copies (the evolve calls write them)"""
+        checked, n = self._hop_state(int(num_pes), state)
+        x, p, b, _, status = checked
+        if copy and not _on_device(x):
+            x, p, b, status = (np.array(a) for a in (x, p, b, status))
+        return (x, p, b, state[3], status), n
+
+    def hop_evolve_mf(self, num_pes, model, state, mass, dt, n_steps, x_left, x_right):
+        """gple_hop_evolve_mf: n_steps mean-field steps of every running trajectory (the force b^dagger Fd b, no hops, nothing random).  numpy:
+        returns the evolved copy; device tensors: evolves the ensemble in place (asynchronously on the context's stream) and returns it"""
+        state, n = self._hop_mf_state(num_pes, state, True)
+        pointers, flags = self._hop_mf_pointers(state)
+        self._check(self.lib.gple_hop_evolve_mf(self.ctx, int(num_pes), int(model), n, float(mass), float(dt), int(n_steps), float(x_left), float(x_right), flags,
+                                                *pointers))
+        return state
+
+    def hop_evolve_groups_mf(self, num_pes, model, state, n_per_group, mass, dt, n_steps, x_left, x_right):
+        """gple_hop_evolve_groups_mf: hop_evolve_mf with the time step dt[g] for group g; a group's state has the bits hop_evolve_mf gives for
+        that slice.  numpy: returns the evolved copy; device tensors: in place"""
+        state, n = self._hop_mf_state(num_pes, state, True)
+        n_groups, n_per_group = self._hop_groups(n, n_per_group)
+        dt = _f64(dt)
+        if dt.shape != (n_groups,):
+            raise ValueError("dt has one time step per group")
+        pointers, flags = self._hop_mf_pointers(state)
+        self._check(self.lib.gple_hop_evolve_groups_mf(self.ctx, int(num_pes), int(model), n_groups, n_per_group, float(mass), _ptr(dt), int(n_steps),
+                                                       float(x_left), float(x_right), flags, *pointers))
+        return state
+
+    def hop_observe_mf(self, num_pes, model, state, mass):
+        """gple_hop_observe_mf -> the 3 num_pes + 6 sums as a numpy array: weights [status][k] = sum |c_k|^2 over the trajectories of that status
+        (3 num_pes), the counts per status (3), sum x, sum p, sum (p^2 / 2 mass + sum_k |c_k|^2 E_k).  With device tensors only these cross"""
+        state, n = self._hop_mf_state(num_pes, state, False)
+        out = _like(state[0], 3 * int(num_pes) + 6)
+        pointers, flags = self._hop_mf_pointers(state)
+        (po,), _ = _io(out)
+        self._check(self.lib.gple_hop_observe_mf(self.ctx, int(num_pes), int(model), n, float(mass), flags, *pointers, po))
+        if _on_device(out):
+            self.synchronize()
+            return out.cpu().numpy()
+        return out
+
+    def hop_observe_groups_mf(self, num_pes, model, state, n_per_group, mass):
+        """gple_hop_observe_groups_mf -> (n_groups, 3 num_pes + 6) numpy array, row g the sums of hop_observe_mf over group g (the same bits)"""
+        state, n = self._hop_mf_state(num_pes, state, False)
+        n_groups, n_per_group = self._hop_groups(n, n_per_group)
+        out = np.empty((n_groups, 3 * int(num_pes) + 6))
+        pointers, flags = self._hop_mf_pointers(state)
+        self._check(self.lib.gple_hop_observe_groups_mf(self.ctx, int(num_pes), int(model), n_groups, n_per_group, float(mass), flags, *pointers, _ptr(out)))
         return out
 
     # ---- reconstruction of a gridded density with the NLML GP (test/main_evolve.cpp; gple_nlml_weights / gple_grid_*) -------------------------

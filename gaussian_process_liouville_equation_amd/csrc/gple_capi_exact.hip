@@ -718,4 +718,131 @@ extern "C"
 		GPLE_HIP(ctx, hipStreamSynchronize(st));
 		return GPLE_OK;
 	}
+
+	/* ---- Ehrenfest (mean-field) trajectories ("Mean-field (Ehrenfest) trajectories") ------------------------------------------- */
+	// what the two evolve calls share: the checks of gple_hop_evolve that apply without a surface, a seed and an offset
+	static bool hop_mf_evolve_ok(double mass, size_t n_steps, double x_left, double x_right, unsigned flags, const double* x, const double* p, const double* b,
+		const int* status)
+	{
+		return hop_positive(mass) && std::isfinite(x_left) && std::isfinite(x_right) && x_left < x_right && n_steps <= (1ul << 40) && !(flags & GPLE_HOP_REVERSE) &&
+			x && p && b && status;
+	}
+
+	int gple_hop_evolve_mf(gple_ctx* ctx, int num_pes, int model, size_t n, double mass, double dt, size_t n_steps, double x_left, double x_right, unsigned flags,
+		double* x, double* p, double* b, int* status)
+	{
+		PesModel pes;
+		if (!ctx || !hop_size_ok(ctx, num_pes, model, n, 0, &pes) || !hop_positive(dt) || !hop_mf_evolve_ok(mass, n_steps, x_left, x_right, flags, x, p, b, status))
+			return GPLE_ERR_BAD_ARG;
+		GPLE_OPEN(ctx);
+		if (n_steps == 0) return GPLE_OK;
+		const bool dev = flags & GPLE_IO_DEVICE;
+		GPLE_CALL(ctx);
+		if (!pes_resolve(ctx, num_pes, model, &pes)) return GPLE_ERR_BAD_ARG; // under the call lock, which gple_pes_undefine takes: the table outlives the enqueue
+		hipStream_t st = ctx->stream;
+		Staged xs(ctx, dev), ps(ctx, dev), bs(ctx, dev);
+		StagedInts ss(ctx, dev);
+		GPLE_HIP(ctx, xs.inout(x, n));
+		GPLE_HIP(ctx, ps.inout(p, n));
+		GPLE_HIP(ctx, bs.inout(b, 2 * n * num_pes));
+		GPLE_HIP(ctx, ss.stage(status, n, true, true));
+		const HopEnsemble e{num_pes, static_cast<long>(n), 0, 0, xs.p, ps.p, bs.p, nullptr, ss.p};
+		timer_start(ctx, GPLE_TIMER_HOP_MF);
+		const hipError_t launched = launch_hop_evolve_mf(st, e, pes, mass, dt, static_cast<long>(n_steps), x_left, x_right);
+		timer_stop(ctx, GPLE_TIMER_HOP_MF); // on the error path too: no span stays open
+		GPLE_HIP(ctx, launched);
+		for (Staged* o : {&xs, &ps, &bs}) GPLE_HIP(ctx, o->back());
+		GPLE_HIP(ctx, ss.back());
+		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
+		return GPLE_OK;
+	}
+
+	int gple_hop_evolve_groups_mf(gple_ctx* ctx, int num_pes, int model, size_t n_groups, size_t n_per_group, double mass, const double* dt, size_t n_steps,
+		double x_left, double x_right, unsigned flags, double* x, double* p, double* b, int* status)
+	{
+		PesModel pes;
+		size_t n = 0;
+		if (!ctx || !hop_groups_ok(ctx, num_pes, model, n_groups, n_per_group, 0, &pes, &n) || !dt ||
+			!hop_mf_evolve_ok(mass, n_steps, x_left, x_right, flags, x, p, b, status))
+			return GPLE_ERR_BAD_ARG;
+		for (size_t g = 0; g < n_groups; ++g)
+			if (!hop_positive(dt[g])) return GPLE_ERR_BAD_ARG;
+		GPLE_OPEN(ctx);
+		if (n_steps == 0) return GPLE_OK;
+		const bool dev = flags & GPLE_IO_DEVICE;
+		GPLE_CALL(ctx);
+		if (!pes_resolve(ctx, num_pes, model, &pes)) return GPLE_ERR_BAD_ARG; // under the call lock, which gple_pes_undefine takes: the table outlives the enqueue
+		hipStream_t st = ctx->stream;
+		Staged xs(ctx, dev), ps(ctx, dev), bs(ctx, dev);
+		StagedInts ss(ctx, dev);
+		Scratch table(ctx);
+		GPLE_HIP(ctx, hop_table(table, dt, n_groups));
+		GPLE_HIP(ctx, xs.inout(x, n));
+		GPLE_HIP(ctx, ps.inout(p, n));
+		GPLE_HIP(ctx, bs.inout(b, 2 * n * num_pes));
+		GPLE_HIP(ctx, ss.stage(status, n, true, true));
+		const HopEnsemble e{num_pes, static_cast<long>(n), 0, 0, xs.p, ps.p, bs.p, nullptr, ss.p};
+		timer_start(ctx, GPLE_TIMER_HOP_MF);
+		const hipError_t launched = launch_hop_evolve_groups_mf(st, e, pes, static_cast<long>(n_per_group), mass, table.p, static_cast<long>(n_steps), x_left, x_right);
+		timer_stop(ctx, GPLE_TIMER_HOP_MF); // on the error path too: no span stays open
+		GPLE_HIP(ctx, launched);
+		for (Staged* o : {&xs, &ps, &bs}) GPLE_HIP(ctx, o->back());
+		GPLE_HIP(ctx, ss.back());
+		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
+		return GPLE_OK;
+	}
+
+	int gple_hop_observe_mf(gple_ctx* ctx, int num_pes, int model, size_t n, double mass, unsigned flags, const double* x, const double* p, const double* b,
+		const int* status, double* out)
+	{
+		PesModel pes;
+		if (!ctx || !hop_size_ok(ctx, num_pes, model, n, 0, &pes) || !hop_positive(mass) || !x || !p || !b || !status || !out) return GPLE_ERR_BAD_ARG;
+		GPLE_OPEN(ctx);
+		const bool dev = flags & GPLE_IO_DEVICE;
+		GPLE_CALL(ctx);
+		if (!pes_resolve(ctx, num_pes, model, &pes)) return GPLE_ERR_BAD_ARG; // under the call lock, which gple_pes_undefine takes: the table outlives the enqueue
+		hipStream_t st = ctx->stream;
+		Staged xs(ctx, dev), ps(ctx, dev), bs(ctx, dev), o(ctx, dev);
+		StagedInts ss(ctx, dev);
+		Scratch work(ctx);
+		GPLE_HIP(ctx, work.get(hop_observe_mf_work_doubles(num_pes, static_cast<long>(n))));
+		GPLE_HIP(ctx, o.out(out, 3 * num_pes + 6));
+		GPLE_HIP(ctx, xs.in(x, n));
+		GPLE_HIP(ctx, ps.in(p, n));
+		GPLE_HIP(ctx, bs.in(b, 2 * n * num_pes));
+		GPLE_HIP(ctx, ss.stage(status, n, true, false));
+		const HopEnsemble e{num_pes, static_cast<long>(n), 0, 0, xs.p, ps.p, bs.p, nullptr, ss.p};
+		GPLE_HIP(ctx, launch_hop_observe_mf(st, e, pes, mass, work.p, o.p));
+		GPLE_HIP(ctx, o.back());
+		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
+		return GPLE_OK;
+	}
+
+	int gple_hop_observe_groups_mf(gple_ctx* ctx, int num_pes, int model, size_t n_groups, size_t n_per_group, double mass, unsigned flags, const double* x,
+		const double* p, const double* b, const int* status, double* out)
+	{
+		PesModel pes;
+		size_t n = 0;
+		if (!ctx || !hop_groups_ok(ctx, num_pes, model, n_groups, n_per_group, 0, &pes, &n) || !hop_positive(mass) || !x || !p || !b || !status || !out)
+			return GPLE_ERR_BAD_ARG;
+		GPLE_OPEN(ctx);
+		const bool dev = flags & GPLE_IO_DEVICE;
+		GPLE_CALL(ctx);
+		if (!pes_resolve(ctx, num_pes, model, &pes)) return GPLE_ERR_BAD_ARG; // under the call lock, which gple_pes_undefine takes: the table outlives the enqueue
+		hipStream_t st = ctx->stream;
+		Staged xs(ctx, dev), ps(ctx, dev), bs(ctx, dev), o(ctx, false); // out is a host array whatever the flags say
+		StagedInts ss(ctx, dev);
+		Scratch work(ctx);
+		GPLE_HIP(ctx, work.get(hop_observe_groups_mf_work_doubles(num_pes, static_cast<long>(n_groups), static_cast<long>(n_per_group))));
+		GPLE_HIP(ctx, o.out(out, n_groups * (3 * num_pes + 6)));
+		GPLE_HIP(ctx, xs.in(x, n));
+		GPLE_HIP(ctx, ps.in(p, n));
+		GPLE_HIP(ctx, bs.in(b, 2 * n * num_pes));
+		GPLE_HIP(ctx, ss.stage(status, n, true, false));
+		const HopEnsemble e{num_pes, static_cast<long>(n), 0, 0, xs.p, ps.p, bs.p, nullptr, ss.p};
+		GPLE_HIP(ctx, launch_hop_observe_groups_mf(st, e, pes, static_cast<long>(n_groups), static_cast<long>(n_per_group), mass, work.p, o.p));
+		GPLE_HIP(ctx, o.back());
+		GPLE_HIP(ctx, hipStreamSynchronize(st));
+		return GPLE_OK;
+	}
 }

@@ -24,6 +24,19 @@
 // Grouped ensembles ("A curve in one launch"): trajectory i of n_groups n_per_group belongs to group i / n_per_group, which has
 // a packet and a time step of its own.  The plain and the grouped kernels call the same device functions per trajectory (hop_sample_one,
 // hop_evolve_one, hop_observe_terms), so the state of a group is, bit for bit, what the plain call gives for that slice.
+//
+// Ehrenfest (mean-field) trajectories ("Mean-field (Ehrenfest) trajectories"; numpy restatement: tests/hop_mf_numpy.py): the same
+// ensemble without an active surface, a seed, a step counter or an offset.  A trajectory is x, p, b and its status, and moves on the force
+// averaged over b, which in the diabatic representation needs no eigen-system of V(x):
+//     f(x, b) = sum_i |b_i|^2 Fd_ii + 2 sum_{i<j} Fd_ij Re(conj(b_i) b_j)   (i ascending, then the pairs (i, j) ascending, i first)
+// One step of length dt for a running trajectory:
+//     1  p += f(x, b) dt / 2,  x_new = x + p / m dt
+//     2  b <- W exp(-i lambda dt / hbar) W^T b,  (lambda, W) the Jacobi eigen-system of (V(x) + V(x_new)) / 2, entry by entry as step 2 above
+//     3  p += f(x_new, b_new) dt / 2,  x = x_new
+//     4  x < x_left: status 1, x > x_right: status 2; a finished trajectory is never read or written again
+// Time-symmetric (second order) and unitary to rounding; nothing is random.  V and Fd at x_new are those at x of the next step and are formed
+// at one place of the loop, by the same s = -1 pass, so evolve_mf(a) then evolve_mf(b) = evolve_mf(a + b), bit for bit.  The plain and the
+// grouped kernels call hop_evolve_mf_one and hop_observe_mf_terms per trajectory.
 #include "gple_kernels.h"
 #include "gple_pes_n.h"
 #include "gple_philox.h"
@@ -419,6 +432,155 @@ namespace gple
 			if (threadIdx.x == 0) out[blockIdx.x] = v;
 		}
 
+		// ---- Ehrenfest (mean-field) trajectories: the step and the sums stated at the head of this file ------------------------------------------
+		// f(x, b) = b^dagger Fd b, one running sum: the diagonal terms with i ascending, then 2 Fd_ij Re(conj(b_i) b_j) over the pairs i < j ascending
+		template <int NP>
+		__device__ __forceinline__ double mean_field_force(const Mat<NP>& Fd, const double (&bre)[NP], const double (&bim)[NP])
+		{
+			double f = 0.0;
+#pragma unroll
+			for (int i = 0; i < NP; ++i) f += (bre[i] * bre[i] + bim[i] * bim[i]) * Fd.a[i][i];
+#pragma unroll
+			for (int i = 0; i < NP; ++i)
+#pragma unroll
+				for (int j = i + 1; j < NP; ++j) f += 2.0 * Fd.a[i][j] * (bre[i] * bre[j] + bim[i] * bim[j]);
+			return f;
+		}
+		// All the steps of a launch for the running trajectory i.  Step 2 is hop_evolve_one's, line for line: a copy, so that the kernels above
+		// keep the code they had
+		template <int NP, typename M>
+		__device__ __forceinline__ void hop_evolve_mf_one(const HopEnsemble& e, const M& model, long i, double mass, double dt, long n_steps, double x_left, double x_right)
+		{
+			double x = e.x[i], p = e.p[i], bre[NP], bim[NP];
+			int status = 0;
+			double* const b = e.b + 2 * NP * i;
+#pragma unroll
+			for (int k = 0; k < NP; ++k) bre[k] = b[2 * k], bim[k] = b[2 * k + 1];
+			Mat<NP> Vx, Fx; // V(x) and Fd(x): set by the pass s = -1, which only forms them at the start point
+			for (long s = -1; s < n_steps && status == 0; ++s)
+			{
+				double xn = x;
+				if (s >= 0)
+				{
+					p += mean_field_force<NP>(Fx, bre, bim) * dt / 2.0;
+					xn = x + p / mass * dt;
+				}
+				Mat<NP> Vn, Fn;
+				diabatic_n<NP>(xn, model, Vn, Fn);
+				if (s >= 0)
+				{
+					// 2: the amplitudes through the mid-point matrix, U = W exp(-i lambda dt / hbar) W^T entry by entry
+					Mat<NP> Vm, W;
+					double lam[NP], cs[NP], sn[NP];
+#pragma unroll
+					for (int r = 0; r < NP; ++r)
+#pragma unroll
+						for (int q = 0; q < NP; ++q) Vm.a[r][q] = 0.5 * (Vx.a[r][q] + Vn.a[r][q]);
+					jacobi_eig<NP>(Vm, lam, W);
+#pragma unroll
+					for (int k = 0; k < NP; ++k) sincos(lam[k] * dt / HBAR_HOP, &sn[k], &cs[k]);
+					double nre[NP], nim[NP];
+#pragma unroll
+					for (int r = 0; r < NP; ++r)
+					{
+						double re = 0.0, im = 0.0;
+#pragma unroll
+						for (int q = 0; q < NP; ++q)
+						{
+							double ure = 0.0, uim = 0.0;
+#pragma unroll
+							for (int k = 0; k < NP; ++k)
+							{
+								const double ww = W.a[r][k] * W.a[q][k];
+								ure += ww * cs[k], uim -= ww * sn[k];
+							}
+							re += ure * bre[q] - uim * bim[q], im += ure * bim[q] + uim * bre[q];
+						}
+						nre[r] = re, nim[r] = im;
+					}
+#pragma unroll
+					for (int r = 0; r < NP; ++r) bre[r] = nre[r], bim[r] = nim[r];
+					// 3
+					p += mean_field_force<NP>(Fn, bre, bim) * dt / 2.0;
+					x = xn;
+					// 4
+					if (x < x_left) status = 1;
+					else if (x > x_right) status = 2;
+				}
+				Vx = Vn, Fx = Fn;
+			}
+			e.x[i] = x, e.p[i] = p, e.status[i] = status;
+#pragma unroll
+			for (int k = 0; k < NP; ++k) b[2 * k] = bre[k], b[2 * k + 1] = bim[k];
+		}
+		template <int NP, typename M>
+		__global__ void __launch_bounds__(HOP_BLOCK) hop_evolve_mf_kernel(HopEnsemble e, M model, double mass, double dt, long n_steps, double x_left, double x_right)
+		{
+			const long i = static_cast<long>(blockIdx.x) * HOP_BLOCK + threadIdx.x;
+			if (i >= e.n || e.status[i] != 0) return;
+			hop_evolve_mf_one<NP, M>(e, model, i, mass, dt, n_steps, x_left, x_right);
+		}
+		template <int NP, typename M>
+		__global__ void __launch_bounds__(HOP_BLOCK) hop_evolve_groups_mf_kernel(HopEnsemble e, M model, long n_per_group, double mass, const double* __restrict__ dt,
+			long n_steps, double x_left, double x_right)
+		{
+			const long i = static_cast<long>(blockIdx.x) * HOP_BLOCK + threadIdx.x;
+			if (i >= e.n || e.status[i] != 0) return;
+			hop_evolve_mf_one<NP, M>(e, model, i, mass, dt[i / n_per_group], n_steps, x_left, x_right);
+		}
+
+		// The 3 NP + 6 terms of trajectory i (include/gple.h, gple_hop_observe_mf): there is no active surface, so a channel is weighted by
+		// |c_k|^2, c = C^T b at the trajectory's x as hop_observe_terms forms it.  A status out of range adds to no weight and to no count
+		template <int NP, typename M>
+		__device__ __forceinline__ void hop_observe_mf_terms(const HopEnsemble& e, const M& model, double mass, long i, double (&t)[3 * NP + 6])
+		{
+			const double x = e.x[i], p = e.p[i];
+			const int status = e.status[i];
+			double bre[NP], bim[NP], cre[NP], cim[NP], E[NP];
+#pragma unroll
+			for (int k = 0; k < NP; ++k) bre[k] = e.b[2 * (NP * i + k)], bim[k] = e.b[2 * (NP * i + k) + 1];
+			Mat<NP> C, Fd;
+			adiabatic_states_n<NP>(x, model, E, C, Fd);
+			adiabatic_amplitudes<NP>(C, bre, bim, cre, cim);
+			double potential = 0.0;
+#pragma unroll
+			for (int k = 0; k < NP; ++k)
+			{
+				const double w = cre[k] * cre[k] + cim[k] * cim[k];
+				potential += w * E[k];
+#pragma unroll
+				for (int s = 0; s < 3; ++s) t[s * NP + k] = s == status ? w : 0.0;
+			}
+#pragma unroll
+			for (int s = 0; s < 3; ++s) t[3 * NP + s] = s == status ? 1.0 : 0.0;
+			t[3 * NP + 3] = x, t[3 * NP + 4] = p, t[3 * NP + 5] = p * p / 2.0 / mass + potential;
+		}
+		// the two first stages of the sums with these terms: the launch shapes and the tree of hop_observe_kernel and hop_observe_groups_kernel
+		template <int NP, typename M>
+		__global__ void __launch_bounds__(HOP_BLOCK) hop_observe_mf_kernel(HopEnsemble e, M model, double mass, double* __restrict__ partial)
+		{
+			constexpr int WIDTH = 3 * NP + 6;
+			const long i = static_cast<long>(blockIdx.x) * HOP_BLOCK + threadIdx.x;
+			double t[WIDTH];
+#pragma unroll
+			for (int q = 0; q < WIDTH; ++q) t[q] = 0.0;
+			if (i < e.n) hop_observe_mf_terms<NP>(e, model, mass, i, t);
+			hop_wave_sums<WIDTH>(t, partial + (i / HOP_WAVE) * WIDTH);
+		}
+		template <int NP, typename M>
+		__global__ void __launch_bounds__(HOP_BLOCK) hop_observe_groups_mf_kernel(HopEnsemble e, M model, long n_per_group, unsigned blocks_per_group, double mass,
+			double* __restrict__ partial)
+		{
+			constexpr int WIDTH = 3 * NP + 6;
+			const long group = blockIdx.x / blocks_per_group;
+			const long j = static_cast<long>(blockIdx.x % blocks_per_group) * HOP_BLOCK + threadIdx.x;
+			double t[WIDTH];
+#pragma unroll
+			for (int q = 0; q < WIDTH; ++q) t[q] = 0.0;
+			if (j < n_per_group) hop_observe_mf_terms<NP>(e, model, mass, group * n_per_group + j, t);
+			hop_wave_sums<WIDTH>(t, partial + (group * blocks_per_group * (HOP_BLOCK / HOP_WAVE) + j / HOP_WAVE) * WIDTH);
+		}
+
 		// The ensemble's adiabatic density on a grid ("The ensemble in phase space"), first as integers: one thread per trajectory
 		// adds 1 to the count plane of its active surface and rint(2^32 c_a conj(c_b)) (re, then im) to the two planes of every pair a < b, at the
 		// cell of its nearest grid point, by no-return 64-bit integer atomics at agent scope.  Integer addition is associative: acc has the same
@@ -625,6 +787,68 @@ namespace gple
 		if (err != hipSuccess) return err;
 		const int width = 4 * e.num_pes + 3;
 		hipLaunchKernelGGL(hop_observe_finish_kernel, dim3(width), dim3(HOP_WAVE), 0, s, work, static_cast<long>(grid.x) * (HOP_BLOCK / HOP_WAVE), width, out);
+		return hipGetLastError();
+	}
+	hipError_t launch_hop_evolve_mf(hipStream_t s, const HopEnsemble& e, PesModel model, double mass, double dt, long n_steps, double x_left, double x_right)
+	{
+		if (e.n <= 0 || n_steps <= 0) return hipSuccess;
+		const dim3 grid(hop_blocks(e.n)), block(HOP_BLOCK);
+		if (e.num_pes == 2)
+			with_model(model, [&](auto m) { hipLaunchKernelGGL((hop_evolve_mf_kernel<2, decltype(m)>), grid, block, 0, s, e, m, mass, dt, n_steps, x_left, x_right); });
+		else if (e.num_pes == 3)
+			with_model(model, [&](auto m) { hipLaunchKernelGGL((hop_evolve_mf_kernel<3, decltype(m)>), grid, block, 0, s, e, m, mass, dt, n_steps, x_left, x_right); });
+		else return hipErrorInvalidValue;
+		return hipGetLastError();
+	}
+	hipError_t launch_hop_evolve_groups_mf(hipStream_t s, const HopEnsemble& e, PesModel model, long n_per_group, double mass, const double* dt, long n_steps,
+		double x_left, double x_right)
+	{
+		if (e.n <= 0 || n_per_group <= 0) return hipErrorInvalidValue;
+		if (n_steps <= 0) return hipSuccess;
+		const dim3 grid(hop_blocks(e.n)), block(HOP_BLOCK);
+		if (e.num_pes == 2)
+			with_model(model, [&](auto m) {
+				hipLaunchKernelGGL((hop_evolve_groups_mf_kernel<2, decltype(m)>), grid, block, 0, s, e, m, n_per_group, mass, dt, n_steps, x_left, x_right);
+			});
+		else if (e.num_pes == 3)
+			with_model(model, [&](auto m) {
+				hipLaunchKernelGGL((hop_evolve_groups_mf_kernel<3, decltype(m)>), grid, block, 0, s, e, m, n_per_group, mass, dt, n_steps, x_left, x_right);
+			});
+		else return hipErrorInvalidValue;
+		return hipGetLastError();
+	}
+	size_t hop_observe_mf_work_doubles(int num_pes, long n) { return static_cast<size_t>(hop_blocks(n)) * (HOP_BLOCK / HOP_WAVE) * (3 * num_pes + 6); }
+	hipError_t launch_hop_observe_mf(hipStream_t s, const HopEnsemble& e, PesModel model, double mass, double* work, double* out)
+	{
+		if (e.n <= 0) return hipErrorInvalidValue;
+		const dim3 grid(hop_blocks(e.n)), block(HOP_BLOCK);
+		if (e.num_pes == 2) with_model(model, [&](auto m) { hipLaunchKernelGGL((hop_observe_mf_kernel<2, decltype(m)>), grid, block, 0, s, e, m, mass, work); });
+		else if (e.num_pes == 3) with_model(model, [&](auto m) { hipLaunchKernelGGL((hop_observe_mf_kernel<3, decltype(m)>), grid, block, 0, s, e, m, mass, work); });
+		else return hipErrorInvalidValue;
+		hipError_t err = hipGetLastError();
+		if (err != hipSuccess) return err;
+		const int width = 3 * e.num_pes + 6;
+		hipLaunchKernelGGL(hop_observe_finish_kernel, dim3(width), dim3(HOP_WAVE), 0, s, work, static_cast<long>(grid.x) * (HOP_BLOCK / HOP_WAVE), width, out);
+		return hipGetLastError();
+	}
+	size_t hop_observe_groups_mf_work_doubles(int num_pes, long n_groups, long n_per_group)
+	{
+		return static_cast<size_t>(n_groups) * hop_blocks(n_per_group) * (HOP_BLOCK / HOP_WAVE) * (3 * num_pes + 6);
+	}
+	hipError_t launch_hop_observe_groups_mf(hipStream_t s, const HopEnsemble& e, PesModel model, long n_groups, long n_per_group, double mass, double* work, double* out)
+	{
+		if (n_groups <= 0 || n_per_group <= 0 || e.n != n_groups * n_per_group) return hipErrorInvalidValue;
+		const unsigned per_group = hop_blocks(n_per_group);
+		if (static_cast<unsigned long long>(n_groups) * per_group > 0x7FFFFFFFull) return hipErrorInvalidValue;
+		const dim3 grid(static_cast<unsigned>(n_groups * per_group)), block(HOP_BLOCK);
+		if (e.num_pes == 2) with_model(model, [&](auto m) { hipLaunchKernelGGL((hop_observe_groups_mf_kernel<2, decltype(m)>), grid, block, 0, s, e, m, n_per_group, per_group, mass, work); });
+		else if (e.num_pes == 3) with_model(model, [&](auto m) { hipLaunchKernelGGL((hop_observe_groups_mf_kernel<3, decltype(m)>), grid, block, 0, s, e, m, n_per_group, per_group, mass, work); });
+		else return hipErrorInvalidValue;
+		hipError_t err = hipGetLastError();
+		if (err != hipSuccess) return err;
+		const int width = 3 * e.num_pes + 6;
+		hipLaunchKernelGGL(hop_observe_finish_groups_kernel, dim3(static_cast<unsigned>(n_groups * width)), dim3(HOP_WAVE), 0, s, work,
+			static_cast<long>(per_group) * (HOP_BLOCK / HOP_WAVE), width, out);
 		return hipGetLastError();
 	}
 	hipError_t launch_hop_bin(hipStream_t s, const HopEnsemble& e, PesModel model, const HopGrid& g, bool bin_all, long long* acc)

@@ -448,6 +448,16 @@ namespace gple
 	// out: n_groups rows of 4 num_pes + 3 sums, row g with the bits of launch_hop_observe on the group alone; every group has workgroups of its own
 	size_t hop_observe_groups_work_doubles(int num_pes, long n_groups, long n_per_group);
 	hipError_t launch_hop_observe_groups(hipStream_t s, const HopEnsemble& e, PesModel model, long n_groups, long n_per_group, double mass, double* work, double* out);
+	// Ehrenfest (mean-field) trajectories ("Mean-field (Ehrenfest) trajectories"): of the ensemble only x, p, b and status are read or
+	// written (surface may be null; offset and seed are not used).  The force is b^dagger Fd b, the amplitudes move as in launch_hop_evolve
+	hipError_t launch_hop_evolve_mf(hipStream_t s, const HopEnsemble& e, PesModel model, double mass, double dt, long n_steps, double x_left, double x_right);
+	hipError_t launch_hop_evolve_groups_mf(hipStream_t s, const HopEnsemble& e, PesModel model, long n_per_group, double mass, const double* dt, long n_steps,
+		double x_left, double x_right);
+	// out: 3 num_pes + 6 sums (include/gple.h), the tree of launch_hop_observe at that width; the grouped form has n_groups such rows
+	size_t hop_observe_mf_work_doubles(int num_pes, long n);
+	hipError_t launch_hop_observe_mf(hipStream_t s, const HopEnsemble& e, PesModel model, double mass, double* work, double* out);
+	size_t hop_observe_groups_mf_work_doubles(int num_pes, long n_groups, long n_per_group);
+	hipError_t launch_hop_observe_groups_mf(hipStream_t s, const HopEnsemble& e, PesModel model, long n_groups, long n_per_group, double mass, double* work, double* out);
 	// the uniform grid of gple_hop_bin: a point belongs to its nearest grid point, floor((x - x_first) / dx + 0.5) and the same for p
 	struct HopGrid
 	{

@@ -11,6 +11,9 @@ column for column with exact.run(flux=True)'s.
                       _observe_groups): a group per momentum with its own packet and time step; scan.txt
 run() and scan() take decoherence = None (Tully's algorithm as it stands), "edc", "collapse_hop" or "collapse_attempt" and edc_c: the decoherence
 correction of every step (gple_hop_evolve_dc / gple_hop_evolve_groups_dc; DESIGN.md §17, "Decoherence corrections").  The files are the same.
+run() and scan() also take method = "fssh" (the default, everything above) or "ehrenfest": mean-field trajectories from the same sample, the other
+trajectory baseline (gple_hop_evolve_mf / _observe_mf and their _groups forms; DESIGN.md §17, "Mean-field (Ehrenfest) trajectories"), with
+unpack_mf() for their sums: a trajectory carries all its amplitudes and moves on the force averaged over them, without hops or random numbers.
 """
 import os
 import time
@@ -36,6 +39,37 @@ def unpack(sums, num_pes, n_traj):
 def averages_line(t, rec, n_traj):
     """One line of averages.txt: t <E> <x> <p>, the fraction of trajectories on each active surface, the mean |c_k|^2 per adiabatic state"""
     return " ".join(exact.fmt(v) for v in [t, rec["E"], rec["x"], rec["p"], *(rec["counts"].sum(axis=0) / n_traj), *rec["populations"]]) + "\n"
+
+
+METHODS = ("fssh", "ehrenfest")
+
+
+def unpack_mf(sums, num_pes, n_traj):
+    """The 3 num_pes + 6 sums of hop_observe_mf over n_traj trajectories -> weights (3, num_pes) [status][k] = sum |c_k|^2 over the trajectories of
+    that status, n_status (3,) the trajectories per status, populations (num_pes,) = mean |c_k|^2 over all of them, x, p, E = the means of x, p
+    and p^2 / 2m + sum_k |c_k|^2 E_k; counts = weights, so that the scattering line is built by the code that builds it from unpack()"""
+    sums = np.asarray(sums, dtype=np.float64)
+    if sums.shape != (3 * num_pes + 6,):
+        raise ValueError("hop_observe_mf returns 3 num_pes + 6 sums")
+    weights = sums[:3 * num_pes].reshape(3, num_pes).copy()
+    return dict(weights=weights, counts=weights, n_status=sums[3 * num_pes:3 * num_pes + 3].copy(), populations=weights.sum(axis=0) / n_traj,
+                x=sums[3 * num_pes + 3] / n_traj, p=sums[3 * num_pes + 4] / n_traj, E=sums[3 * num_pes + 5] / n_traj)
+
+
+def averages_line_mf(t, rec):
+    """One line of a mean-field averages.txt: t <E> <x> <p>, the mean |c_k|^2 per adiabatic state (there is no active surface to count)"""
+    return " ".join(exact.fmt(v) for v in [t, rec["E"], rec["x"], rec["p"], *rec["populations"]]) + "\n"
+
+
+def _method(method, decoherence, reverse_frustrated, phase_grid=None):
+    """method of run() and scan(), checked against the options that need an active surface -> True for the mean-field one"""
+    if method not in METHODS:
+        raise ValueError(f"method is one of {METHODS}")
+    if method == "fssh":
+        return False
+    if decoherence is not None or reverse_frustrated or phase_grid is not None:
+        raise ValueError("ehrenfest trajectories have no active surface: no decoherence correction, no frustrated hops and (DESIGN.md §17) no phase_grid")
+    return True
 
 
 GRID_KEYS = ("x_first", "dx", "n_x", "p_first", "dp", "n_p")
@@ -65,7 +99,7 @@ def phase_grid_of(api, num_pes, model, s, phase_grid):
 
 
 def run(api, model=DAC, num_pes=2, ln_energy=0.0, n_traj=10000, seed=0, out_dir=None, reverse_frustrated=False, dt=None, surface0=0, max_outputs=None,
-        log=None, phase_grid=None, decoherence=None, edc_c=0.1, **setup_kw):
+        log=None, phase_grid=None, decoherence=None, edc_c=0.1, method="fssh", **setup_kw):
     """n_traj trajectories from the packet of exact.setup(ln_energy, boundary=ABSORBING, **setup_kw) (x0, sigma_x, p0, sigma_p, mass) on the adiabatic
     surface surface0, evolved with the time step dt (default: the setup's dt_rule, the reference's own rule) between x_left = xmin and
     x_right = xmax; a trajectory that leaves is finished and counted by side and active surface.  The ensemble stays on the device: every
@@ -78,8 +112,13 @@ def run(api, model=DAC, num_pes=2, ln_energy=0.0, n_traj=10000, seed=0, out_dir=
     reconstruct.run_files reads.
     decoherence (None, "edc", "collapse_hop", "collapse_attempt") and edc_c: the decoherence correction of every step; with None the api is
     called without these keywords, otherwise both are forwarded to every hop_evolve.  The result carries both.
+    method: "fssh" (the default: everything above, call for call) or "ehrenfest", mean-field trajectories from the same sample: per output time
+    one hop_evolve_mf and one hop_observe_mf, whose record is unpack_mf()'s; the run stops when n_status[0] == 0.  An averages.txt line is then
+    averages_line_mf (no active-surface columns), and the scattering line holds weights[left][k] / n, weights[right][k] / n and n_status[0] / n
+    in the same columns.  decoherence, reverse_frustrated=True or a phase_grid with "ehrenfest" is a ValueError.
     Returns the setup, the records (t and unpack() per output time), stop, and scattering_line: the head of exact.run's final line, the
     fractions that left [left | right][surface], and the fraction still running."""
+    mean_field = _method(method, decoherence, reverse_frustrated, phase_grid)
     setup_kw["boundary"] = exact.ABSORBING
     s = exact.setup(ln_energy, **setup_kw)
     num_pes, n_traj = int(num_pes), int(n_traj)
@@ -103,7 +142,10 @@ def run(api, model=DAC, num_pes=2, ln_energy=0.0, n_traj=10000, seed=0, out_dir=
     records, stop, step = [], None, 0
     try:
         while True:
-            rec = unpack(api.hop_observe(num_pes, model, state, s["mass"]), num_pes, n_traj)
+            if mean_field:
+                rec = unpack_mf(api.hop_observe_mf(num_pes, model, state, s["mass"]), num_pes, n_traj)
+            else:
+                rec = unpack(api.hop_observe(num_pes, model, state, s["mass"]), num_pes, n_traj)
             rec["t"] = step * dt
             if grid is not None:
                 acc = api.hop_bin(num_pes, model, state, grid)
@@ -119,14 +161,17 @@ def run(api, model=DAC, num_pes=2, ln_energy=0.0, n_traj=10000, seed=0, out_dir=
             records.append(rec)
             if files:
                 files["t.txt"].write(exact.fmt(rec["t"]) + "\n")
-                files["averages.txt"].write(averages_line(rec["t"], rec, n_traj))
-            if rec["counts"][RUNNING].sum() == 0:
+                files["averages.txt"].write(averages_line_mf(rec["t"], rec) if mean_field else averages_line(rec["t"], rec, n_traj))
+            if (rec["n_status"][RUNNING] if mean_field else rec["counts"][RUNNING].sum()) == 0:
                 stop = f"NO TRAJECTORY IS RUNNING, STOP EVOLVING AT {rec['t']:g}"
                 break
             if step + output_step > total_step or (max_outputs is not None and len(records) >= max_outputs):
                 break
-            state = api.hop_evolve(num_pes, model, state, seed, s["mass"], dt, step, output_step, s["xmin"], s["xmax"], reverse=reverse_frustrated,
-                                   **correction)
+            if mean_field:
+                state = api.hop_evolve_mf(num_pes, model, state, s["mass"], dt, output_step, s["xmin"], s["xmax"])
+            else:
+                state = api.hop_evolve(num_pes, model, state, seed, s["mass"], dt, step, output_step, s["xmin"], s["xmax"], reverse=reverse_frustrated,
+                                       **correction)
             step += output_step
     finally:
         for f in files.values():
@@ -136,10 +181,11 @@ def run(api, model=DAC, num_pes=2, ln_energy=0.0, n_traj=10000, seed=0, out_dir=
     counts = records[-1]["counts"]
     head = np.log(s["p0"] ** 2 / 2.0 / s["mass"]) if model == DAC else s["p0"]  # as exact.run (main.cpp:308-321)
     scattered = np.concatenate([counts[LEFT], counts[RIGHT]]) / n_traj
-    line = " ".join(exact.fmt(v) for v in [head, *scattered, counts[RUNNING].sum() / n_traj])
+    running = records[-1]["n_status"][RUNNING] if mean_field else counts[RUNNING].sum()
+    line = " ".join(exact.fmt(v) for v in [head, *scattered, running / n_traj])
     return dict(setup=s, dt=dt, output_step=output_step, total_step=total_step, n_traj=n_traj, records=records, stop=stop, state=state,
                 scattered=scattered.reshape(2, num_pes), scattering_line=line, stop_time=records[-1]["t"], steps=step, total_seconds=t_end - t0,
-                decoherence=decoherence, edc_c=edc_c)
+                decoherence=decoherence, edc_c=edc_c, method=method)
 
 
 def scan_line(values):
@@ -161,7 +207,7 @@ def _per_group(setup_kw, n_groups):
 
 
 def scan(api, model=DAC, num_pes=2, ln_energies=None, momenta=None, n_per_group=10000, seed=0, fixed=True, surface0=0, dt=None, chunk_steps=4096,
-         max_steps=None, reverse_frustrated=False, out_dir=None, log=None, decoherence=None, edc_c=0.1, **setup_kw):
+         max_steps=None, reverse_frustrated=False, out_dir=None, log=None, decoherence=None, edc_c=0.1, method="fssh", **setup_kw):
     """The branching probabilities as a function of the incoming momentum, Tully's plot, from ONE ensemble of len(ln_energies) (or len(momenta))
     groups of n_per_group trajectories.  Group g takes its constants from exact.setup(ln_energies[g], boundary=ABSORBING, **setup_kw) (momenta:
     p0 = momenta[g] instead): x0, p0, mass, the bounds xmin and xmax, its time step dt_rule unless dt (a number, or one per group) overrides
@@ -175,7 +221,14 @@ def scan(api, model=DAC, num_pes=2, ln_energies=None, momenta=None, n_per_group=
     Returns per group (arrays with n_groups rows): head (ln E for DAC, else p0, as run()), scattered (n_groups, 2, num_pes) the fractions
     [left | right][surface], running, stderr (n_groups, 2 num_pes + 1) = sqrt(f (1 - f) / n_per_group) of those fractions in scan.txt's order,
     hops and frustrated per trajectory, energy_drift = (sum E_end - sum E_start) / n_per_group, and lines (scan_line, what scan.txt holds with
-    out_dir); also setups, dt, steps, stop, state, hop_counts (the (n, 2) counters), rows (the last hop_observe_groups), decoherence and edc_c."""
+    out_dir); also setups, dt, steps, stop, state, hop_counts (the (n, 2) counters), rows (the last hop_observe_groups), decoherence and edc_c.
+    method: "fssh" (the default: everything above, call for call) or "ehrenfest": the same sample, then hop_evolve_groups_mf and
+    hop_observe_groups_mf.  scan.txt keeps its columns: the fractions are weights[left | right][k] / n_per_group and n_status[0] / n_per_group,
+    hops and frustrated are 0 (hop_counts is None), energy_drift comes from the mean-field energy p^2 / 2m + sum_k |c_k|^2 E_k.  stderr is then
+    an UPPER BOUND: a fraction f is the mean of weights in [0, 1], whose variance is at most f (1 - f).  With fixed=True every trajectory of a
+    group is the same trajectory (nothing is random), so n_per_group = 1 is enough.  decoherence or reverse_frustrated=True with "ehrenfest" is
+    a ValueError."""
+    mean_field = _method(method, decoherence, reverse_frustrated)
     if (ln_energies is None) == (momenta is None):
         raise ValueError("give ln_energies or momenta, one of them")
     given = np.atleast_1d(np.asarray(ln_energies if momenta is None else momenta, dtype=np.float64))
@@ -201,26 +254,34 @@ def scan(api, model=DAC, num_pes=2, ln_energies=None, momenta=None, n_per_group=
     t0 = time.perf_counter()
     state = api.hop_sample_groups(num_pes, model, n_per_group, seed, packets, surface0, device_out=True)
     on_device = hasattr(state[0], "is_cuda")
-    if on_device:
+    if mean_field:
+        counts = None
+    elif on_device:
         import torch
         counts = torch.zeros((n_groups * n_per_group, 2), dtype=torch.int32, device=state[0].device)
         torch.cuda.synchronize(state[0].device)  # the framework's stream has cleared the counters: now the context's may add to them
     else:
         counts = np.zeros((n_groups * n_per_group, 2), dtype=np.int32)
-    width, step, stop = 4 * num_pes + 3, 0, None
-    first = rows = np.asarray(api.hop_observe_groups(num_pes, model, state, n_per_group, s0["mass"]), dtype=np.float64).reshape(n_groups, width)
+    width, step, stop = (3 * num_pes + 6 if mean_field else 4 * num_pes + 3), 0, None
+    observe = api.hop_observe_groups_mf if mean_field else api.hop_observe_groups
+    first = rows = np.asarray(observe(num_pes, model, state, n_per_group, s0["mass"]), dtype=np.float64).reshape(n_groups, width)
     while True:
-        if rows[:, :num_pes].sum() == 0:
+        if (rows[:, 3 * num_pes] if mean_field else rows[:, :num_pes]).sum() == 0:
             stop = f"NO TRAJECTORY IS RUNNING, STOP EVOLVING AT STEP {step}"
             break
         if step >= max_steps:
             break
         n_steps = min(chunk_steps, max_steps - step)
-        state, counts = api.hop_evolve_groups(num_pes, model, state, n_per_group, seed, s0["mass"], dts, step, n_steps, s0["xmin"], s0["xmax"],
-                                              reverse=reverse_frustrated, hops=counts, **correction)
+        if mean_field:
+            state = api.hop_evolve_groups_mf(num_pes, model, state, n_per_group, s0["mass"], dts, n_steps, s0["xmin"], s0["xmax"])
+        else:
+            state, counts = api.hop_evolve_groups(num_pes, model, state, n_per_group, seed, s0["mass"], dts, step, n_steps, s0["xmin"], s0["xmax"],
+                                                  reverse=reverse_frustrated, hops=counts, **correction)
         step += n_steps
-        rows = np.asarray(api.hop_observe_groups(num_pes, model, state, n_per_group, s0["mass"]), dtype=np.float64).reshape(n_groups, width)
-    if on_device:
+        rows = np.asarray(observe(num_pes, model, state, n_per_group, s0["mass"]), dtype=np.float64).reshape(n_groups, width)
+    if mean_field:
+        per_group = np.zeros((n_groups, 2), dtype=np.int64)
+    elif on_device:
         api.synchronize()  # the context's stream has written the counters: now the framework's may read them
         per_group = counts.reshape(n_groups, n_per_group, 2).sum(dim=1, dtype=torch.int64).cpu().numpy()
     else:
@@ -229,7 +290,7 @@ def scan(api, model=DAC, num_pes=2, ln_energies=None, momenta=None, n_per_group=
     say(stop or f"STOPPED AT {max_steps} STEPS")
     counts_by = rows[:, :3 * num_pes].reshape(n_groups, 3, num_pes)
     scattered = counts_by[:, 1:, :] / n_per_group
-    running = counts_by[:, RUNNING, :].sum(axis=1) / n_per_group
+    running = (rows[:, 3 * num_pes] if mean_field else counts_by[:, RUNNING, :].sum(axis=1)) / n_per_group
     fractions = np.concatenate([scattered.reshape(n_groups, 2 * num_pes), running[:, None]], axis=1)
     stderr = np.sqrt(fractions * (1.0 - fractions) / n_per_group)
     head = np.array([np.log(s["p0"] ** 2 / 2.0 / s["mass"]) if model == DAC else s["p0"] for s in setups])
@@ -242,4 +303,4 @@ def scan(api, model=DAC, num_pes=2, ln_energies=None, momenta=None, n_per_group=
             f.write("".join(lines))
     return dict(setups=setups, dt=dts, n_per_group=n_per_group, total_step=total_step, max_steps=max_steps, steps=step, stop=stop, state=state,
                 hop_counts=counts, rows=rows, head=head, scattered=scattered, running=running, stderr=stderr, hops=hops, frustrated=frustrated,
-                energy_drift=drift, lines=lines, total_seconds=t_end - t0, decoherence=decoherence, edc_c=edc_c)
+                energy_drift=drift, lines=lines, total_seconds=t_end - t0, decoherence=decoherence, edc_c=edc_c, method=method)

@@ -159,7 +159,8 @@ typedef enum gple_timer {
 	GPLE_TIMER_DVR_SPECTRUM = 11,  /* the device work of one gple_dvr_spectrum call (P4, the squarings, the thin products, the projection and the reduction; no copies); count = calls */
 	GPLE_TIMER_HOP = 12,           /* the step kernel of one gple_hop_evolve or gple_hop_evolve_dc call (all its steps, no staging); count = calls */
 	GPLE_TIMER_HOP_BIN = 13,       /* the bin kernel of one gple_hop_bin call (no staging, no clear); count = calls */
-	GPLE_TIMER_HOP_GROUPS = 14     /* the step kernel of one gple_hop_evolve_groups or _groups_dc call (all its steps, no staging); count = calls */
+	GPLE_TIMER_HOP_GROUPS = 14,    /* the step kernel of one gple_hop_evolve_groups or _groups_dc call (all its steps, no staging); count = calls */
+	GPLE_TIMER_HOP_MF = 15         /* the step kernel of one gple_hop_evolve_mf or gple_hop_evolve_groups_mf call (all its steps, no staging); count = calls */
 } gple_timer;
 int gple_ctx_enable_timing(gple_ctx* ctx, int on);
 /* Synchronises the stream, then: last = milliseconds of the most recent interval; total / count = accumulated since
@@ -391,7 +392,7 @@ int gple_pes_adiabatic_n(gple_ctx* ctx, int num_pes, int model, const double* x,
  * V = V_0 + V'_0 (x - x_first), V' = V'_0, and for s > n - 1 the same from the last node.  With nodes taken from a smooth function the error is
  * at most dx^4 / 384 max|V''''| for the value and sqrt(3) / 216 dx^3 max|V''''| for the derivative.
  * A user id is accepted, on the context it was defined on and with the num_pes it was defined with (GPLE_ERR_BAD_ARG otherwise), by
- * gple_pes_adiabatic_n, gple_pes_diabatic_n, gple_evolve_n, gple_dvr_hamiltonian, gple_mqcl_transform / _evolve / _observe, gple_hop_sample / _evolve / _observe / _bin (and the _groups forms),
+ * gple_pes_adiabatic_n, gple_pes_diabatic_n, gple_evolve_n, gple_dvr_hamiltonian, gple_mqcl_transform / _evolve / _observe, gple_hop_sample / _evolve / _observe / _bin (and the _groups, _dc and _mf forms),
  * gple_grid_survey and gple_grid_reconstruct / _cross.  The two-level entry points gple_pes_adiabatic and gple_evolve keep refusing it: they use the reference's closed
  * forms and operation order, of which a table has none; gple_evolve_n at num_pes = 2 reproduces gple_evolve to rounding and takes their place.
  * Where two surfaces of a user model touch (E_j = E_k) with F_jk != 0 the non-adiabatic coupling is infinite, as its formula says: not guarded.
@@ -641,6 +642,36 @@ int gple_hop_evolve_dc(gple_ctx* ctx, int num_pes, int model, size_t n, size_t t
 int gple_hop_evolve_groups_dc(gple_ctx* ctx, int num_pes, int model, size_t n_groups, size_t n_per_group, size_t trajectory_offset,
 	unsigned long long seed, double mass, const double* dt, size_t first_step, size_t n_steps, double x_left, double x_right, int decoherence,
 	double edc_c, unsigned flags, double* x, double* p, double* b, int* surface, int* status, int* hops);
+/* Ehrenfest (mean-field) trajectories ("Mean-field (Ehrenfest) trajectories"): the other trajectory baseline.  A trajectory is
+ * x, p, the diabatic amplitudes b and its status; it has no active surface, no seed, no step counter and no trajectory offset, and nothing is
+ * random.  The ensemble is the one gple_hop_sample (_groups) draws (b starts on column surface0 of C(x)); its surface array is not passed.
+ * V, Fd = -V' are the diabatic matrix and force.  The force on a trajectory is the average over its amplitudes,
+ *     f(x, b) = sum_i |b_i|^2 Fd_ii + 2 sum_{i<j} Fd_ij Re(conj(b_i) b_j),
+ * one running sum: the diagonal terms with i ascending, then the pairs (i, j), i < j, ascending.  One step of length dt, running trajectory:
+ *     1  p += f(x, b) dt / 2,  x_new = x + p / mass dt
+ *     2  b <- W exp(-i lambda dt / hbar) W^T b,  (lambda, W) the Jacobi eigen-system of (V(x) + V(x_new)) / 2, formed entry by entry as step 2
+ *        of gple_hop_evolve forms it
+ *     3  p += f(x_new, b_new) dt / 2,  x = x_new
+ *     4  x < x_left: status 1, x > x_right: status 2; a finished trajectory is never read or written again
+ * The step is time-symmetric (second order) and unitary to rounding.  V and Fd at x_new are those at x of the next step, formed at one place of
+ * the loop: evolve_mf(a) then evolve_mf(b) gives the bits of evolve_mf(a + b).  n_steps <= 2^40 (0: nothing happens).
+ * gple_hop_evolve_groups_mf: the same step with dt[group], group = i / n_per_group; the state of group g afterwards is, bit for bit, what
+ * gple_hop_evolve_mf gives for that slice with dt[g].  Timer of both: GPLE_TIMER_HOP_MF.
+ * gple_hop_observe_mf: sums in the fixed tree of gple_hop_observe.  out, 3 num_pes + 6 doubles, with c = C^T b at the trajectory's x:
+ * the weights [status 0 | 1 | 2][k] = sum of |c_k|^2 over the trajectories of that status; the counts per status (exact integers); sum x,
+ * sum p, sum (p^2 / 2 mass + sum_k |c_k|^2 E_k).  A status outside 0 ... 2 adds to no weight and to no count, as gple_hop_observe skips it.
+ * gple_hop_observe_groups_mf: n_groups such rows (out is a host array), row g with the bits of gple_hop_observe_mf on that slice.
+ * Arrays, GPLE_IO_DEVICE and the dt table as the calls above.  GPLE_ERR_BAD_ARG, with nothing written: everything gple_hop_evolve,
+ * gple_hop_evolve_groups, gple_hop_observe and gple_hop_observe_groups refuse that applies here (num_pes, the model, n, the group sizes, mass,
+ * dt or an entry of dt not finite and positive, the bounds, n_steps > 2^40, a null array), and the flag GPLE_HOP_REVERSE. */
+int gple_hop_evolve_mf(gple_ctx* ctx, int num_pes, int model, size_t n, double mass, double dt, size_t n_steps, double x_left, double x_right,
+	unsigned flags, double* x, double* p, double* b, int* status);
+int gple_hop_evolve_groups_mf(gple_ctx* ctx, int num_pes, int model, size_t n_groups, size_t n_per_group, double mass, const double* dt,
+	size_t n_steps, double x_left, double x_right, unsigned flags, double* x, double* p, double* b, int* status);
+int gple_hop_observe_mf(gple_ctx* ctx, int num_pes, int model, size_t n, double mass, unsigned flags, const double* x, const double* p,
+	const double* b, const int* status, double* out);
+int gple_hop_observe_groups_mf(gple_ctx* ctx, int num_pes, int model, size_t n_groups, size_t n_per_group, double mass, unsigned flags,
+	const double* x, const double* p, const double* b, const int* status, double* out);
 
 /* generate_markov_chain (mc.cpp:118-165) for n walkers at once on the fitted distribution |cut-off prediction| of `element`:
  * num_steps Metropolis steps with uniform displacements in [-max_displacement, max_displacement) per dimension; r (2n) holds
