@@ -24,7 +24,13 @@ HOP_BIN_ALL = 0x8000  # gple_hop_bin: finished trajectories are binned too
 TIMER_HOP_BIN = 13  # gple_timer: the bin kernel of one gple_hop_bin call
 TIMER_HOP_GROUPS = 14  # gple_timer: the step kernel of one gple_hop_evolve_groups call
 TIMER_HOP_MF = 15  # gple_timer: the step kernel of one gple_hop_evolve_mf or gple_hop_evolve_groups_mf call
+TIMER_HOP_SQC = 16  # gple_timer: the step kernel of one gple_hop_evolve_sqc or gple_hop_evolve_groups_sqc call
 HOP_MAX_GROUPS = 65536  # GPLE_HOP_MAX_GROUPS
+# GPLE_HOP_WINDOW_*: the windows of the symmetrical quasi-classical trajectories, the names Api.hop_sample_sqc / hop_observe_sqc take for them, and
+# the customary zero-point parameter gamma of each
+HOP_WINDOW_SQUARE, HOP_WINDOW_TRIANGLE = range(2)
+HOP_WINDOW_NAMES = {"square": HOP_WINDOW_SQUARE, "triangle": HOP_WINDOW_TRIANGLE}
+HOP_WINDOW_GAMMA = {HOP_WINDOW_SQUARE: (3.0 ** 0.5 - 1.0) / 2.0, HOP_WINDOW_TRIANGLE: 1.0 / 3.0}
 # GPLE_HOP_DC_*: the decoherence correction of gple_hop_evolve_dc / gple_hop_evolve_groups_dc (step 6a), and the names Api.hop_evolve takes for them
 HOP_DC_NONE, HOP_DC_EDC, HOP_DC_COLLAPSE_HOP, HOP_DC_COLLAPSE_ATTEMPT = range(4)
 HOP_DC_NAMES = {"none": HOP_DC_NONE, "edc": HOP_DC_EDC, "collapse_hop": HOP_DC_COLLAPSE_HOP, "collapse_attempt": HOP_DC_COLLAPSE_ATTEMPT}
@@ -379,6 +385,13 @@ def _signatures():
         "hop_evolve_groups_mf": (st, [CTX, i, i, sz, sz, d, _dp, sz, d, d, u, _dp, _dp, _dp, ip]),
         "hop_observe_mf": (st, [CTX, i, i, sz, d, u, _dp, _dp, _dp, ip, _dp]),
         "hop_observe_groups_mf": (st, [CTX, i, i, sz, sz, d, u, _dp, _dp, _dp, ip, _dp]),
+        # symmetrical quasi-classical trajectories
+        "hop_sample_sqc": (st, [CTX, i, i, sz, sz, ull, d, d, d, d, i, i, d, u, _dp, _dp, _dp, ip, ip]),
+        "hop_sample_groups_sqc": (st, [CTX, i, i, sz, sz, sz, ull, _dp, i, i, d, u, _dp, _dp, _dp, ip, ip]),
+        "hop_evolve_sqc": (st, [CTX, i, i, sz, d, d, sz, d, d, d, u, _dp, _dp, _dp, ip]),
+        "hop_evolve_groups_sqc": (st, [CTX, i, i, sz, sz, d, _dp, sz, d, d, d, u, _dp, _dp, _dp, ip]),
+        "hop_observe_sqc": (st, [CTX, i, i, sz, d, i, d, u, _dp, _dp, _dp, ip, _dp]),
+        "hop_observe_groups_sqc": (st, [CTX, i, i, sz, sz, d, i, d, u, _dp, _dp, _dp, ip, _dp]),
         # many NLML problems in one launch; the search of several planes in lock-step on it
         "nlml_batch": (st, [CTX, C.POINTER(NlmlProblem), sz, i, u, _dp, _dp, C.POINTER(_dp), ip]),
         "nlml_fit_planes": (st, [CTX, C.POINTER(NlmlFitPlane), sz, i, opt, _dp, _dp, ip, C.POINTER(_dp)]),
@@ -560,7 +573,7 @@ class Api:
         steps, 6 = the device work of the reconstruction entry points, 7 = the kernels of format_g, 8 = the kernels of parse_g, 9 = the products of dvr_propagator, 10 = the products of dvr_flux,
         11 = the device work of dvr_spectrum, 12 = the step kernel of hop_evolve, 13 = the bin kernel of hop_bin,
         14 = the step kernel of hop_evolve_groups (12 and 14 also with a decoherence correction), 15 = the step kernel of hop_evolve_mf and
-        hop_evolve_groups_mf."""
+        hop_evolve_groups_mf, 16 = the step kernel of hop_evolve_sqc and hop_evolve_groups_sqc."""
         last, total, count = C.c_double(), C.c_double(), C.c_long()
         self._check(self.lib.gple_ctx_get_timing(self.ctx, which, C.byref(last), C.byref(total), C.byref(count)))
         return last.value, total.value, count.value
@@ -1272,6 +1285,109 @@ class Api:
         out = np.empty((n_groups, 3 * int(num_pes) + 6))
         pointers, flags = self._hop_mf_pointers(state)
         self._check(self.lib.gple_hop_observe_groups_mf(self.ctx, int(num_pes), int(model), n_groups, n_per_group, float(mass), flags, *pointers, _ptr(out)))
+        return out
+
+    # ---- symmetrical quasi-classical trajectories (gple_hop_*_sqc; DESIGN.md §17, "Symmetrical quasi-classical trajectories") ----------------------
+    # The ensemble is the same 5-tuple; b holds the mapping amplitudes, which are not normalised.  The samples write surface (= surface0); the
+    # evolve and observe calls never pass it down, as their _mf siblings
+    @staticmethod
+    def _hop_window(window, gamma):
+        """(GPLE_HOP_WINDOW_*, gamma) of a name of HOP_WINDOW_NAMES or an integer; gamma None: the customary value of that window"""
+        if isinstance(window, str):
+            if window not in HOP_WINDOW_NAMES:
+                raise ValueError(f"window is an integer or one of {sorted(HOP_WINDOW_NAMES)}")
+            window = HOP_WINDOW_NAMES[window]
+        window = int(window)
+        if gamma is None:
+            if window not in HOP_WINDOW_GAMMA:
+                raise ValueError("no customary gamma for this window")
+            gamma = HOP_WINDOW_GAMMA[window]
+        return window, float(gamma)
+
+    def _hop_empty(self, num_pes, n, device_out):
+        if device_out:
+            import torch
+            where = torch.device("cuda", self.device)
+            return (torch.empty(n, dtype=torch.float64, device=where), torch.empty(n, dtype=torch.float64, device=where),
+                    torch.empty((n, num_pes), dtype=torch.complex128, device=where), torch.empty(n, dtype=torch.int32, device=where),
+                    torch.empty(n, dtype=torch.int32, device=where))
+        return (np.empty(n), np.empty(n), np.empty((n, num_pes), dtype=np.complex128), np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32))
+
+    def hop_sample_sqc(self, num_pes, model, n, seed, x0, p0, sigma_x, sigma_p, surface0=0, window="triangle", gamma=None, trajectory_offset=0, device_out=False):
+        """gple_hop_sample_sqc: x and p as hop_sample draws them (the same bits), the mapping amplitudes b on the start window of the adiabatic
+        state surface0 ("square" or "triangle", gamma None: (sqrt(3) - 1) / 2 or 1 / 3) -> the ensemble (x, p, b, surface, status)"""
+        num_pes, n = int(num_pes), int(n)
+        window, gamma = self._hop_window(window, gamma)
+        if n < 1:
+            raise ValueError("an ensemble has at least one trajectory")
+        state = self._hop_empty(num_pes, n, device_out)
+        pointers, flags = self._hop_pointers(state)
+        self._check(self.lib.gple_hop_sample_sqc(self.ctx, num_pes, int(model), n, int(trajectory_offset), int(seed), float(x0), float(p0), float(sigma_x),
+                                                 float(sigma_p), int(surface0), window, gamma, flags, *pointers))
+        if device_out:
+            self.synchronize()
+        return state
+
+    def hop_sample_groups_sqc(self, num_pes, model, n_per_group, seed, packets, surface0=0, window="triangle", gamma=None, trajectory_offset=0, device_out=False):
+        """gple_hop_sample_groups_sqc: hop_sample_sqc per row (x0, p0, sigma_x, sigma_p) of packets, as hop_sample_groups (a sigma may be 0)"""
+        num_pes, n_per_group, packets = int(num_pes), int(n_per_group), _f64(packets)
+        window, gamma = self._hop_window(window, gamma)
+        if packets.ndim != 2 or packets.shape[1] != 4 or packets.shape[0] < 1 or n_per_group < 1:
+            raise ValueError("packets is (n_groups, 4) with n_groups >= 1, and a group has at least one trajectory")
+        n_groups = packets.shape[0]
+        state = self._hop_empty(num_pes, n_groups * n_per_group, device_out)
+        pointers, flags = self._hop_pointers(state)
+        self._check(self.lib.gple_hop_sample_groups_sqc(self.ctx, num_pes, int(model), n_groups, n_per_group, int(trajectory_offset), int(seed), _ptr(packets),
+                                                        int(surface0), window, gamma, flags, *pointers))
+        if device_out:
+            self.synchronize()
+        return state
+
+    def hop_evolve_sqc(self, num_pes, model, state, mass, dt, n_steps, x_left, x_right, gamma):
+        """gple_hop_evolve_sqc: n_steps steps of every running trajectory on the mapping Hamiltonian (the mean-field step with the force
+        b^dagger Fd b - gamma tr Fd).  numpy: returns the evolved copy; device tensors: evolves the ensemble in place and returns it"""
+        state, n = self._hop_mf_state(num_pes, state, True)
+        pointers, flags = self._hop_mf_pointers(state)
+        self._check(self.lib.gple_hop_evolve_sqc(self.ctx, int(num_pes), int(model), n, float(mass), float(dt), int(n_steps), float(x_left), float(x_right),
+                                                 float(gamma), flags, *pointers))
+        return state
+
+    def hop_evolve_groups_sqc(self, num_pes, model, state, n_per_group, mass, dt, n_steps, x_left, x_right, gamma):
+        """gple_hop_evolve_groups_sqc: hop_evolve_sqc with the time step dt[g] for group g; a group's state has the bits hop_evolve_sqc gives for
+        that slice.  numpy: returns the evolved copy; device tensors: in place"""
+        state, n = self._hop_mf_state(num_pes, state, True)
+        n_groups, n_per_group = self._hop_groups(n, n_per_group)
+        dt = _f64(dt)
+        if dt.shape != (n_groups,):
+            raise ValueError("dt has one time step per group")
+        pointers, flags = self._hop_mf_pointers(state)
+        self._check(self.lib.gple_hop_evolve_groups_sqc(self.ctx, int(num_pes), int(model), n_groups, n_per_group, float(mass), _ptr(dt), int(n_steps),
+                                                        float(x_left), float(x_right), float(gamma), flags, *pointers))
+        return state
+
+    def hop_observe_sqc(self, num_pes, model, state, mass, window="triangle", gamma=None):
+        """gple_hop_observe_sqc -> the 4 num_pes + 9 sums as a numpy array (hopping.unpack_sqc names them): the trajectories [status][window k],
+        per status, per status in no window, sum e_k, sum x, sum p, sum H.  With device tensors only these cross"""
+        state, n = self._hop_mf_state(num_pes, state, False)
+        window, gamma = self._hop_window(window, gamma)
+        out = _like(state[0], 4 * int(num_pes) + 9)
+        pointers, flags = self._hop_mf_pointers(state)
+        (po,), _ = _io(out)
+        self._check(self.lib.gple_hop_observe_sqc(self.ctx, int(num_pes), int(model), n, float(mass), window, gamma, flags, *pointers, po))
+        if _on_device(out):
+            self.synchronize()
+            return out.cpu().numpy()
+        return out
+
+    def hop_observe_groups_sqc(self, num_pes, model, state, n_per_group, mass, window="triangle", gamma=None):
+        """gple_hop_observe_groups_sqc -> (n_groups, 4 num_pes + 9) numpy array, row g the sums of hop_observe_sqc over group g (the same bits)"""
+        state, n = self._hop_mf_state(num_pes, state, False)
+        window, gamma = self._hop_window(window, gamma)
+        n_groups, n_per_group = self._hop_groups(n, n_per_group)
+        out = np.empty((n_groups, 4 * int(num_pes) + 9))
+        pointers, flags = self._hop_mf_pointers(state)
+        self._check(self.lib.gple_hop_observe_groups_sqc(self.ctx, int(num_pes), int(model), n_groups, n_per_group, float(mass), window, gamma, flags, *pointers,
+                                                         _ptr(out)))
         return out
 
     # ---- reconstruction of a gridded density with the NLML GP (test/main_evolve.cpp; gple_nlml_weights / gple_grid_*) -------------------------

@@ -845,4 +845,200 @@ extern "C"
 		GPLE_HIP(ctx, hipStreamSynchronize(st));
 		return GPLE_OK;
 	}
+
+	/* ---- symmetrical quasi-classical trajectories ("Symmetrical quasi-classical trajectories") -------------------------------- */
+	// gamma of the step, where no window is named: finite and not negative
+	static bool hop_sqc_gamma_ok(double gamma) { return std::isfinite(gamma) && gamma >= 0.0; }
+	// window is a GPLE_HOP_WINDOW_* and gamma fits it: the square windows are disjoint for 0 < gamma < 1/2 only
+	static bool hop_sqc_window_ok(int window, double gamma)
+	{
+		if (window != GPLE_HOP_WINDOW_SQUARE && window != GPLE_HOP_WINDOW_TRIANGLE) return false;
+		return hop_sqc_gamma_ok(gamma) && (window != GPLE_HOP_WINDOW_SQUARE || (gamma > 0.0 && gamma < 0.5));
+	}
+
+	int gple_hop_sample_sqc(gple_ctx* ctx, int num_pes, int model, size_t n, size_t trajectory_offset, unsigned long long seed, double x0, double p0,
+		double sigma_x, double sigma_p, int surface0, int window, double gamma, unsigned flags, double* x, double* p, double* b, int* surface, int* status)
+	{
+		PesModel pes;
+		if (!ctx || !hop_size_ok(ctx, num_pes, model, n, trajectory_offset, &pes) || !hop_positive(sigma_x) || !hop_positive(sigma_p) || surface0 < 0 ||
+			surface0 >= num_pes || !hop_sqc_window_ok(window, gamma) || (flags & GPLE_HOP_REVERSE) || !x || !p || !b || !surface || !status)
+			return GPLE_ERR_BAD_ARG;
+		GPLE_OPEN(ctx);
+		const bool dev = flags & GPLE_IO_DEVICE;
+		GPLE_CALL(ctx);
+		if (!pes_resolve(ctx, num_pes, model, &pes)) return GPLE_ERR_BAD_ARG; // under the call lock, which gple_pes_undefine takes: the table outlives the enqueue
+		hipStream_t st = ctx->stream;
+		Staged xs(ctx, dev), ps(ctx, dev), bs(ctx, dev);
+		StagedInts su(ctx, dev), ss(ctx, dev);
+		GPLE_HIP(ctx, xs.out(x, n));
+		GPLE_HIP(ctx, ps.out(p, n));
+		GPLE_HIP(ctx, bs.out(b, 2 * n * num_pes));
+		GPLE_HIP(ctx, su.stage(surface, n, false, true));
+		GPLE_HIP(ctx, ss.stage(status, n, false, true));
+		const HopEnsemble e{num_pes, static_cast<long>(n), trajectory_offset, seed, xs.p, ps.p, bs.p, su.p, ss.p};
+		GPLE_HIP(ctx, launch_hop_sample_sqc(st, e, pes, x0, p0, sigma_x, sigma_p, surface0, window, gamma));
+		for (Staged* o : {&xs, &ps, &bs}) GPLE_HIP(ctx, o->back());
+		for (StagedInts* o : {&su, &ss}) GPLE_HIP(ctx, o->back());
+		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
+		return GPLE_OK;
+	}
+
+	int gple_hop_sample_groups_sqc(gple_ctx* ctx, int num_pes, int model, size_t n_groups, size_t n_per_group, size_t trajectory_offset,
+		unsigned long long seed, const double* packets, int surface0, int window, double gamma, unsigned flags, double* x, double* p, double* b,
+		int* surface, int* status)
+	{
+		PesModel pes;
+		size_t n = 0;
+		if (!ctx || !hop_groups_ok(ctx, num_pes, model, n_groups, n_per_group, trajectory_offset, &pes, &n) || !packets || surface0 < 0 || surface0 >= num_pes ||
+			!hop_sqc_window_ok(window, gamma) || (flags & GPLE_HOP_REVERSE) || !x || !p || !b || !surface || !status)
+			return GPLE_ERR_BAD_ARG;
+		for (size_t g = 0; g < n_groups; ++g)
+		{
+			const double* row = packets + 4 * g;
+			if (!std::isfinite(row[0]) || !std::isfinite(row[1]) || !std::isfinite(row[2]) || !std::isfinite(row[3]) || row[2] < 0.0 || row[3] < 0.0) return GPLE_ERR_BAD_ARG;
+		}
+		GPLE_OPEN(ctx);
+		const bool dev = flags & GPLE_IO_DEVICE;
+		GPLE_CALL(ctx);
+		if (!pes_resolve(ctx, num_pes, model, &pes)) return GPLE_ERR_BAD_ARG; // under the call lock, which gple_pes_undefine takes: the table outlives the enqueue
+		hipStream_t st = ctx->stream;
+		Staged xs(ctx, dev), ps(ctx, dev), bs(ctx, dev);
+		StagedInts su(ctx, dev), ss(ctx, dev);
+		Scratch table(ctx);
+		GPLE_HIP(ctx, hop_table(table, packets, 4 * n_groups));
+		GPLE_HIP(ctx, xs.out(x, n));
+		GPLE_HIP(ctx, ps.out(p, n));
+		GPLE_HIP(ctx, bs.out(b, 2 * n * num_pes));
+		GPLE_HIP(ctx, su.stage(surface, n, false, true));
+		GPLE_HIP(ctx, ss.stage(status, n, false, true));
+		const HopEnsemble e{num_pes, static_cast<long>(n), trajectory_offset, seed, xs.p, ps.p, bs.p, su.p, ss.p};
+		GPLE_HIP(ctx, launch_hop_sample_groups_sqc(st, e, pes, static_cast<long>(n_per_group), table.p, surface0, window, gamma));
+		for (Staged* o : {&xs, &ps, &bs}) GPLE_HIP(ctx, o->back());
+		for (StagedInts* o : {&su, &ss}) GPLE_HIP(ctx, o->back());
+		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
+		return GPLE_OK;
+	}
+
+	int gple_hop_evolve_sqc(gple_ctx* ctx, int num_pes, int model, size_t n, double mass, double dt, size_t n_steps, double x_left, double x_right, double gamma,
+		unsigned flags, double* x, double* p, double* b, int* status)
+	{
+		PesModel pes;
+		if (!ctx || !hop_size_ok(ctx, num_pes, model, n, 0, &pes) || !hop_positive(dt) || !hop_mf_evolve_ok(mass, n_steps, x_left, x_right, flags, x, p, b, status) ||
+			!hop_sqc_gamma_ok(gamma))
+			return GPLE_ERR_BAD_ARG;
+		GPLE_OPEN(ctx);
+		if (n_steps == 0) return GPLE_OK;
+		const bool dev = flags & GPLE_IO_DEVICE;
+		GPLE_CALL(ctx);
+		if (!pes_resolve(ctx, num_pes, model, &pes)) return GPLE_ERR_BAD_ARG; // under the call lock, which gple_pes_undefine takes: the table outlives the enqueue
+		hipStream_t st = ctx->stream;
+		Staged xs(ctx, dev), ps(ctx, dev), bs(ctx, dev);
+		StagedInts ss(ctx, dev);
+		GPLE_HIP(ctx, xs.inout(x, n));
+		GPLE_HIP(ctx, ps.inout(p, n));
+		GPLE_HIP(ctx, bs.inout(b, 2 * n * num_pes));
+		GPLE_HIP(ctx, ss.stage(status, n, true, true));
+		const HopEnsemble e{num_pes, static_cast<long>(n), 0, 0, xs.p, ps.p, bs.p, nullptr, ss.p};
+		timer_start(ctx, GPLE_TIMER_HOP_SQC);
+		const hipError_t launched = launch_hop_evolve_sqc(st, e, pes, mass, dt, static_cast<long>(n_steps), x_left, x_right, gamma);
+		timer_stop(ctx, GPLE_TIMER_HOP_SQC); // on the error path too: no span stays open
+		GPLE_HIP(ctx, launched);
+		for (Staged* o : {&xs, &ps, &bs}) GPLE_HIP(ctx, o->back());
+		GPLE_HIP(ctx, ss.back());
+		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
+		return GPLE_OK;
+	}
+
+	int gple_hop_evolve_groups_sqc(gple_ctx* ctx, int num_pes, int model, size_t n_groups, size_t n_per_group, double mass, const double* dt, size_t n_steps,
+		double x_left, double x_right, double gamma, unsigned flags, double* x, double* p, double* b, int* status)
+	{
+		PesModel pes;
+		size_t n = 0;
+		if (!ctx || !hop_groups_ok(ctx, num_pes, model, n_groups, n_per_group, 0, &pes, &n) || !dt ||
+			!hop_mf_evolve_ok(mass, n_steps, x_left, x_right, flags, x, p, b, status) || !hop_sqc_gamma_ok(gamma))
+			return GPLE_ERR_BAD_ARG;
+		for (size_t g = 0; g < n_groups; ++g)
+			if (!hop_positive(dt[g])) return GPLE_ERR_BAD_ARG;
+		GPLE_OPEN(ctx);
+		if (n_steps == 0) return GPLE_OK;
+		const bool dev = flags & GPLE_IO_DEVICE;
+		GPLE_CALL(ctx);
+		if (!pes_resolve(ctx, num_pes, model, &pes)) return GPLE_ERR_BAD_ARG; // under the call lock, which gple_pes_undefine takes: the table outlives the enqueue
+		hipStream_t st = ctx->stream;
+		Staged xs(ctx, dev), ps(ctx, dev), bs(ctx, dev);
+		StagedInts ss(ctx, dev);
+		Scratch table(ctx);
+		GPLE_HIP(ctx, hop_table(table, dt, n_groups));
+		GPLE_HIP(ctx, xs.inout(x, n));
+		GPLE_HIP(ctx, ps.inout(p, n));
+		GPLE_HIP(ctx, bs.inout(b, 2 * n * num_pes));
+		GPLE_HIP(ctx, ss.stage(status, n, true, true));
+		const HopEnsemble e{num_pes, static_cast<long>(n), 0, 0, xs.p, ps.p, bs.p, nullptr, ss.p};
+		timer_start(ctx, GPLE_TIMER_HOP_SQC);
+		const hipError_t launched =
+			launch_hop_evolve_groups_sqc(st, e, pes, static_cast<long>(n_per_group), mass, table.p, static_cast<long>(n_steps), x_left, x_right, gamma);
+		timer_stop(ctx, GPLE_TIMER_HOP_SQC); // on the error path too: no span stays open
+		GPLE_HIP(ctx, launched);
+		for (Staged* o : {&xs, &ps, &bs}) GPLE_HIP(ctx, o->back());
+		GPLE_HIP(ctx, ss.back());
+		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
+		return GPLE_OK;
+	}
+
+	int gple_hop_observe_sqc(gple_ctx* ctx, int num_pes, int model, size_t n, double mass, int window, double gamma, unsigned flags, const double* x,
+		const double* p, const double* b, const int* status, double* out)
+	{
+		PesModel pes;
+		if (!ctx || !hop_size_ok(ctx, num_pes, model, n, 0, &pes) || !hop_positive(mass) || !hop_sqc_window_ok(window, gamma) || (flags & GPLE_HOP_REVERSE) || !x || !p ||
+			!b || !status || !out)
+			return GPLE_ERR_BAD_ARG;
+		GPLE_OPEN(ctx);
+		const bool dev = flags & GPLE_IO_DEVICE;
+		GPLE_CALL(ctx);
+		if (!pes_resolve(ctx, num_pes, model, &pes)) return GPLE_ERR_BAD_ARG; // under the call lock, which gple_pes_undefine takes: the table outlives the enqueue
+		hipStream_t st = ctx->stream;
+		Staged xs(ctx, dev), ps(ctx, dev), bs(ctx, dev), o(ctx, dev);
+		StagedInts ss(ctx, dev);
+		Scratch work(ctx);
+		GPLE_HIP(ctx, work.get(hop_observe_sqc_work_doubles(num_pes, static_cast<long>(n))));
+		GPLE_HIP(ctx, o.out(out, 4 * num_pes + 9));
+		GPLE_HIP(ctx, xs.in(x, n));
+		GPLE_HIP(ctx, ps.in(p, n));
+		GPLE_HIP(ctx, bs.in(b, 2 * n * num_pes));
+		GPLE_HIP(ctx, ss.stage(status, n, true, false));
+		const HopEnsemble e{num_pes, static_cast<long>(n), 0, 0, xs.p, ps.p, bs.p, nullptr, ss.p};
+		GPLE_HIP(ctx, launch_hop_observe_sqc(st, e, pes, mass, window, gamma, work.p, o.p));
+		GPLE_HIP(ctx, o.back());
+		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
+		return GPLE_OK;
+	}
+
+	int gple_hop_observe_groups_sqc(gple_ctx* ctx, int num_pes, int model, size_t n_groups, size_t n_per_group, double mass, int window, double gamma,
+		unsigned flags, const double* x, const double* p, const double* b, const int* status, double* out)
+	{
+		PesModel pes;
+		size_t n = 0;
+		if (!ctx || !hop_groups_ok(ctx, num_pes, model, n_groups, n_per_group, 0, &pes, &n) || !hop_positive(mass) || !hop_sqc_window_ok(window, gamma) ||
+			(flags & GPLE_HOP_REVERSE) || !x || !p || !b || !status || !out)
+			return GPLE_ERR_BAD_ARG;
+		GPLE_OPEN(ctx);
+		const bool dev = flags & GPLE_IO_DEVICE;
+		GPLE_CALL(ctx);
+		if (!pes_resolve(ctx, num_pes, model, &pes)) return GPLE_ERR_BAD_ARG; // under the call lock, which gple_pes_undefine takes: the table outlives the enqueue
+		hipStream_t st = ctx->stream;
+		Staged xs(ctx, dev), ps(ctx, dev), bs(ctx, dev), o(ctx, false); // out is a host array whatever the flags say
+		StagedInts ss(ctx, dev);
+		Scratch work(ctx);
+		GPLE_HIP(ctx, work.get(hop_observe_groups_sqc_work_doubles(num_pes, static_cast<long>(n_groups), static_cast<long>(n_per_group))));
+		GPLE_HIP(ctx, o.out(out, n_groups * (4 * num_pes + 9)));
+		GPLE_HIP(ctx, xs.in(x, n));
+		GPLE_HIP(ctx, ps.in(p, n));
+		GPLE_HIP(ctx, bs.in(b, 2 * n * num_pes));
+		GPLE_HIP(ctx, ss.stage(status, n, true, false));
+		const HopEnsemble e{num_pes, static_cast<long>(n), 0, 0, xs.p, ps.p, bs.p, nullptr, ss.p};
+		GPLE_HIP(ctx, launch_hop_observe_groups_sqc(st, e, pes, static_cast<long>(n_groups), static_cast<long>(n_per_group), mass, window, gamma, work.p, o.p));
+		GPLE_HIP(ctx, o.back());
+		GPLE_HIP(ctx, hipStreamSynchronize(st));
+		return GPLE_OK;
+	}
 }

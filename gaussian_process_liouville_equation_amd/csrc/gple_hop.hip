@@ -37,6 +37,20 @@
 // Time-symmetric (second order) and unitary to rounding; nothing is random.  V and Fd at x_new are those at x of the next step and are formed
 // at one place of the loop, by the same s = -1 pass, so evolve_mf(a) then evolve_mf(b) = evolve_mf(a + b), bit for bit.  The plain and the
 // grouped kernels call hop_evolve_mf_one and hop_observe_mf_terms per trajectory.
+//
+// Symmetrical quasi-classical (SQC) trajectories ("Symmetrical quasi-classical trajectories"; numpy restatement:
+// tests/hop_sqc_numpy.py): the Meyer-Miller-Stock-Thoss mapping Hamiltonian with the windows of Cotton and Miller.  b is not normalised:
+// with c = C^T b, e_k = |c_k|^2 and the action n_k = e_k - gamma, H = p^2 / 2m + b^dagger V b - gamma tr V, and the force is
+//     f(x, b) = [the mean-field running sum above] - gamma (Fd_00 + ... + Fd_{NP-1,NP-1})   (the trace left to right, the product, then the difference)
+// The step is the mean-field step with this f: i db/dt = V b, no eigen-system of V(x), nothing random, the same s = -1 pass.  The sample draws
+// x and p by the lines of hop_sample_one (counter (index, 0, 1, 0)) and, for level k, (u_k, v_k) = unit53 of the words (0, 1) and (2, 3) of the
+// counter (index, k, 2, 0);  c_k = sqrt(e_k) (cospi(2 v_k) + i sinpi(2 v_k)), b = C(x) c, with occ = surface0 and F = NP
+//     square   (window 0):  e_k = delta_{k,occ} + 2 gamma u_k
+//     triangle (window 1):  t = (1 - u_occ)^(1/F) (sqrt, cbrt),  e_occ = 2 - t,  e_j = u_j t  (j != occ)
+// The sums bin e into the final windows: a trajectory belongs to the first k ascending with
+//     square:    1 <= e_k <= 1 + 2 gamma  and  e_j <= 2 gamma  for all j != k
+//     triangle:  e_k >= 1  and  e_k + e_j <= 2  for all j != k
+// else to none.  The plain and the grouped kernels call hop_sample_sqc_one, hop_evolve_sqc_one and hop_observe_sqc_terms per trajectory.
 #include "gple_kernels.h"
 #include "gple_pes_n.h"
 #include "gple_philox.h"
@@ -581,6 +595,236 @@ namespace gple
 			hop_wave_sums<WIDTH>(t, partial + (group * blocks_per_group * (HOP_BLOCK / HOP_WAVE) + j / HOP_WAVE) * WIDTH);
 		}
 
+		// ---- Symmetrical quasi-classical trajectories: the sample, the step and the sums stated at the head of this file ------------------------------
+		// One trajectory of the sample.  x and p by hop_sample_one's lines (the same bits); then the energies e on the start window and the angles
+		template <int NP, typename M, bool ZERO>
+		__device__ __forceinline__ void hop_sample_sqc_one(const HopEnsemble& e, const M& model, long i, double x0, double p0, double sigma_x, double sigma_p, int surface0,
+			int window, double gamma)
+		{
+			const unsigned long long index = e.offset + static_cast<unsigned long long>(i);
+			const unsigned key0 = static_cast<unsigned>(e.seed), key1 = static_cast<unsigned>(e.seed >> 32);
+			unsigned c[4] = {static_cast<unsigned>(index), 0u, 1u, 0u};
+			philox4x32(c, key0, key1);
+			const double u0 = unit53(c[0], c[1]), u1 = unit53(c[2], c[3]);
+			const double rho = sqrt(-2.0 * log(1.0 - u0));
+			double sn, cs;
+			sincospi(2.0 * u1, &sn, &cs);
+			double x = x0 + sigma_x * rho * cs, p = p0 + sigma_p * rho * sn;
+			if constexpr (ZERO) x = sigma_x == 0.0 ? x0 : x, p = sigma_p == 0.0 ? p0 : p;
+			double E[NP];
+			Mat<NP> C, Fd;
+			adiabatic_states_n<NP>(x, model, E, C, Fd);
+			double u[NP], v[NP];
+#pragma unroll
+			for (int k = 0; k < NP; ++k)
+			{
+				unsigned w[4] = {static_cast<unsigned>(index), static_cast<unsigned>(k), 2u, 0u};
+				philox4x32(w, key0, key1);
+				u[k] = unit53(w[0], w[1]), v[k] = unit53(w[2], w[3]);
+			}
+			const double root = 1.0 - pick<NP>(u, surface0), t = NP == 2 ? sqrt(root) : cbrt(root);
+			double cre[NP], cim[NP];
+#pragma unroll
+			for (int k = 0; k < NP; ++k)
+			{
+				const bool occupied = k == surface0;
+				const double square = (occupied ? 1.0 : 0.0) + 2.0 * gamma * u[k], triangle = occupied ? 2.0 - t : u[k] * t;
+				const double length = sqrt(window == GPLE_HOP_WINDOW_SQUARE ? square : triangle);
+				sincospi(2.0 * v[k], &sn, &cs);
+				cre[k] = length * cs, cim[k] = length * sn;
+			}
+			e.x[i] = x, e.p[i] = p, e.surface[i] = surface0, e.status[i] = 0;
+			double* b = e.b + 2 * NP * i;
+#pragma unroll
+			for (int r = 0; r < NP; ++r)
+			{
+				double re = 0.0, im = 0.0;
+#pragma unroll
+				for (int k = 0; k < NP; ++k) re += C.a[r][k] * cre[k], im += C.a[r][k] * cim[k];
+				b[2 * r] = re, b[2 * r + 1] = im;
+			}
+		}
+		template <int NP, typename M>
+		__global__ void __launch_bounds__(HOP_BLOCK) hop_sample_sqc_kernel(HopEnsemble e, M model, double x0, double p0, double sigma_x, double sigma_p, int surface0,
+			int window, double gamma)
+		{
+			const long i = static_cast<long>(blockIdx.x) * HOP_BLOCK + threadIdx.x;
+			if (i >= e.n) return;
+			hop_sample_sqc_one<NP, M, false>(e, model, i, x0, p0, sigma_x, sigma_p, surface0, window, gamma);
+		}
+		template <int NP, typename M>
+		__global__ void __launch_bounds__(HOP_BLOCK) hop_sample_groups_sqc_kernel(HopEnsemble e, M model, long n_per_group, const double* __restrict__ packets, int surface0,
+			int window, double gamma)
+		{
+			const long i = static_cast<long>(blockIdx.x) * HOP_BLOCK + threadIdx.x;
+			if (i >= e.n) return;
+			const double* const row = packets + 4 * (i / n_per_group);
+			hop_sample_sqc_one<NP, M, true>(e, model, i, row[0], row[1], row[2], row[3], surface0, window, gamma);
+		}
+
+		// f(x, b) = b^dagger Fd b - gamma tr Fd: the mean-field running sum, the trace left to right, the product, then the difference
+		template <int NP>
+		__device__ __forceinline__ double sqc_force(const Mat<NP>& Fd, const double (&bre)[NP], const double (&bim)[NP], double gamma)
+		{
+			double trace = Fd.a[0][0];
+#pragma unroll
+			for (int i = 1; i < NP; ++i) trace += Fd.a[i][i];
+			return mean_field_force<NP>(Fd, bre, bim) - gamma * trace;
+		}
+		// All the steps of a launch for the running trajectory i: hop_evolve_mf_one's lines with sqc_force (a copy, so that the kernels above keep
+		// the code they had)
+		template <int NP, typename M>
+		__device__ __forceinline__ void hop_evolve_sqc_one(const HopEnsemble& e, const M& model, long i, double mass, double dt, long n_steps, double x_left, double x_right,
+			double gamma)
+		{
+			double x = e.x[i], p = e.p[i], bre[NP], bim[NP];
+			int status = 0;
+			double* const b = e.b + 2 * NP * i;
+#pragma unroll
+			for (int k = 0; k < NP; ++k) bre[k] = b[2 * k], bim[k] = b[2 * k + 1];
+			Mat<NP> Vx, Fx; // V(x) and Fd(x): set by the pass s = -1, which only forms them at the start point
+			for (long s = -1; s < n_steps && status == 0; ++s)
+			{
+				double xn = x;
+				if (s >= 0)
+				{
+					p += sqc_force<NP>(Fx, bre, bim, gamma) * dt / 2.0;
+					xn = x + p / mass * dt;
+				}
+				Mat<NP> Vn, Fn;
+				diabatic_n<NP>(xn, model, Vn, Fn);
+				if (s >= 0)
+				{
+					// 2: the amplitudes through the mid-point matrix, U = W exp(-i lambda dt / hbar) W^T entry by entry
+					Mat<NP> Vm, W;
+					double lam[NP], cs[NP], sn[NP];
+#pragma unroll
+					for (int r = 0; r < NP; ++r)
+#pragma unroll
+						for (int q = 0; q < NP; ++q) Vm.a[r][q] = 0.5 * (Vx.a[r][q] + Vn.a[r][q]);
+					jacobi_eig<NP>(Vm, lam, W);
+#pragma unroll
+					for (int k = 0; k < NP; ++k) sincos(lam[k] * dt / HBAR_HOP, &sn[k], &cs[k]);
+					double nre[NP], nim[NP];
+#pragma unroll
+					for (int r = 0; r < NP; ++r)
+					{
+						double re = 0.0, im = 0.0;
+#pragma unroll
+						for (int q = 0; q < NP; ++q)
+						{
+							double ure = 0.0, uim = 0.0;
+#pragma unroll
+							for (int k = 0; k < NP; ++k)
+							{
+								const double ww = W.a[r][k] * W.a[q][k];
+								ure += ww * cs[k], uim -= ww * sn[k];
+							}
+							re += ure * bre[q] - uim * bim[q], im += ure * bim[q] + uim * bre[q];
+						}
+						nre[r] = re, nim[r] = im;
+					}
+#pragma unroll
+					for (int r = 0; r < NP; ++r) bre[r] = nre[r], bim[r] = nim[r];
+					// 3
+					p += sqc_force<NP>(Fn, bre, bim, gamma) * dt / 2.0;
+					x = xn;
+					// 4
+					if (x < x_left) status = 1;
+					else if (x > x_right) status = 2;
+				}
+				Vx = Vn, Fx = Fn;
+			}
+			e.x[i] = x, e.p[i] = p, e.status[i] = status;
+#pragma unroll
+			for (int k = 0; k < NP; ++k) b[2 * k] = bre[k], b[2 * k + 1] = bim[k];
+		}
+		template <int NP, typename M>
+		__global__ void __launch_bounds__(HOP_BLOCK) hop_evolve_sqc_kernel(HopEnsemble e, M model, double mass, double dt, long n_steps, double x_left, double x_right,
+			double gamma)
+		{
+			const long i = static_cast<long>(blockIdx.x) * HOP_BLOCK + threadIdx.x;
+			if (i >= e.n || e.status[i] != 0) return;
+			hop_evolve_sqc_one<NP, M>(e, model, i, mass, dt, n_steps, x_left, x_right, gamma);
+		}
+		template <int NP, typename M>
+		__global__ void __launch_bounds__(HOP_BLOCK) hop_evolve_groups_sqc_kernel(HopEnsemble e, M model, long n_per_group, double mass, const double* __restrict__ dt,
+			long n_steps, double x_left, double x_right, double gamma)
+		{
+			const long i = static_cast<long>(blockIdx.x) * HOP_BLOCK + threadIdx.x;
+			if (i >= e.n || e.status[i] != 0) return;
+			hop_evolve_sqc_one<NP, M>(e, model, i, mass, dt[i / n_per_group], n_steps, x_left, x_right, gamma);
+		}
+
+		// The 4 NP + 9 terms of trajectory i (include/gple.h, gple_hop_observe_sqc): c = C^T b at the trajectory's x as hop_observe_terms forms
+		// it, e_k = |c_k|^2, and the first window (k ascending) that holds e, else none.  A status out of range adds nowhere
+		template <int NP, typename M>
+		__device__ __forceinline__ void hop_observe_sqc_terms(const HopEnsemble& e, const M& model, double mass, int window, double gamma, long i, double (&t)[4 * NP + 9])
+		{
+			const double x = e.x[i], p = e.p[i];
+			const int status = e.status[i];
+			double bre[NP], bim[NP], cre[NP], cim[NP], E[NP], w[NP];
+#pragma unroll
+			for (int k = 0; k < NP; ++k) bre[k] = e.b[2 * (NP * i + k)], bim[k] = e.b[2 * (NP * i + k) + 1];
+			Mat<NP> C, Fd;
+			adiabatic_states_n<NP>(x, model, E, C, Fd);
+			adiabatic_amplitudes<NP>(C, bre, bim, cre, cim);
+			double potential = 0.0;
+#pragma unroll
+			for (int k = 0; k < NP; ++k)
+			{
+				w[k] = cre[k] * cre[k] + cim[k] * cim[k];
+				potential += (w[k] - gamma) * E[k];
+			}
+			int found = -1;
+#pragma unroll
+			for (int k = NP - 1; k >= 0; --k) // descending, so that the least k that holds is what stays
+			{
+				bool square = w[k] >= 1.0 && w[k] <= 1.0 + 2.0 * gamma, triangle = w[k] >= 1.0;
+#pragma unroll
+				for (int j = 0; j < NP; ++j)
+					if (j != k) square = square && w[j] <= 2.0 * gamma, triangle = triangle && w[k] + w[j] <= 2.0;
+				if (window == GPLE_HOP_WINDOW_SQUARE ? square : triangle) found = k;
+			}
+			const bool counted = status >= 0 && status <= 2;
+#pragma unroll
+			for (int s = 0; s < 3; ++s)
+			{
+#pragma unroll
+				for (int k = 0; k < NP; ++k) t[s * NP + k] = s == status && k == found ? 1.0 : 0.0;
+				t[3 * NP + s] = s == status ? 1.0 : 0.0;
+				t[3 * NP + 3 + s] = s == status && found < 0 ? 1.0 : 0.0;
+			}
+#pragma unroll
+			for (int k = 0; k < NP; ++k) t[3 * NP + 6 + k] = counted ? w[k] : 0.0;
+			t[4 * NP + 6] = counted ? x : 0.0, t[4 * NP + 7] = counted ? p : 0.0, t[4 * NP + 8] = counted ? p * p / 2.0 / mass + potential : 0.0;
+		}
+		// the two first stages of the sums with these terms: the launch shapes and the tree of hop_observe_kernel and hop_observe_groups_kernel
+		template <int NP, typename M>
+		__global__ void __launch_bounds__(HOP_BLOCK) hop_observe_sqc_kernel(HopEnsemble e, M model, double mass, int window, double gamma, double* __restrict__ partial)
+		{
+			constexpr int WIDTH = 4 * NP + 9;
+			const long i = static_cast<long>(blockIdx.x) * HOP_BLOCK + threadIdx.x;
+			double t[WIDTH];
+#pragma unroll
+			for (int q = 0; q < WIDTH; ++q) t[q] = 0.0;
+			if (i < e.n) hop_observe_sqc_terms<NP>(e, model, mass, window, gamma, i, t);
+			hop_wave_sums<WIDTH>(t, partial + (i / HOP_WAVE) * WIDTH);
+		}
+		template <int NP, typename M>
+		__global__ void __launch_bounds__(HOP_BLOCK) hop_observe_groups_sqc_kernel(HopEnsemble e, M model, long n_per_group, unsigned blocks_per_group, double mass, int window,
+			double gamma, double* __restrict__ partial)
+		{
+			constexpr int WIDTH = 4 * NP + 9;
+			const long group = blockIdx.x / blocks_per_group;
+			const long j = static_cast<long>(blockIdx.x % blocks_per_group) * HOP_BLOCK + threadIdx.x;
+			double t[WIDTH];
+#pragma unroll
+			for (int q = 0; q < WIDTH; ++q) t[q] = 0.0;
+			if (j < n_per_group) hop_observe_sqc_terms<NP>(e, model, mass, window, gamma, group * n_per_group + j, t);
+			hop_wave_sums<WIDTH>(t, partial + (group * blocks_per_group * (HOP_BLOCK / HOP_WAVE) + j / HOP_WAVE) * WIDTH);
+		}
+
 		// The ensemble's adiabatic density on a grid ("The ensemble in phase space"), first as integers: one thread per trajectory
 		// adds 1 to the count plane of its active surface and rint(2^32 c_a conj(c_b)) (re, then im) to the two planes of every pair a < b, at the
 		// cell of its nearest grid point, by no-return 64-bit integer atomics at agent scope.  Integer addition is associative: acc has the same
@@ -847,6 +1091,107 @@ namespace gple
 		hipError_t err = hipGetLastError();
 		if (err != hipSuccess) return err;
 		const int width = 3 * e.num_pes + 6;
+		hipLaunchKernelGGL(hop_observe_finish_groups_kernel, dim3(static_cast<unsigned>(n_groups * width)), dim3(HOP_WAVE), 0, s, work,
+			static_cast<long>(per_group) * (HOP_BLOCK / HOP_WAVE), width, out);
+		return hipGetLastError();
+	}
+	hipError_t launch_hop_sample_sqc(hipStream_t s, const HopEnsemble& e, PesModel model, double x0, double p0, double sigma_x, double sigma_p, int surface0, int window,
+		double gamma)
+	{
+		if (e.n <= 0) return hipSuccess;
+		const dim3 grid(hop_blocks(e.n)), block(HOP_BLOCK);
+		if (e.num_pes == 2)
+			with_model(model, [&](auto m) {
+				hipLaunchKernelGGL((hop_sample_sqc_kernel<2, decltype(m)>), grid, block, 0, s, e, m, x0, p0, sigma_x, sigma_p, surface0, window, gamma);
+			});
+		else if (e.num_pes == 3)
+			with_model(model, [&](auto m) {
+				hipLaunchKernelGGL((hop_sample_sqc_kernel<3, decltype(m)>), grid, block, 0, s, e, m, x0, p0, sigma_x, sigma_p, surface0, window, gamma);
+			});
+		else return hipErrorInvalidValue;
+		return hipGetLastError();
+	}
+	hipError_t launch_hop_sample_groups_sqc(hipStream_t s, const HopEnsemble& e, PesModel model, long n_per_group, const double* packets, int surface0, int window,
+		double gamma)
+	{
+		if (e.n <= 0 || n_per_group <= 0) return hipErrorInvalidValue;
+		const dim3 grid(hop_blocks(e.n)), block(HOP_BLOCK);
+		if (e.num_pes == 2)
+			with_model(model, [&](auto m) {
+				hipLaunchKernelGGL((hop_sample_groups_sqc_kernel<2, decltype(m)>), grid, block, 0, s, e, m, n_per_group, packets, surface0, window, gamma);
+			});
+		else if (e.num_pes == 3)
+			with_model(model, [&](auto m) {
+				hipLaunchKernelGGL((hop_sample_groups_sqc_kernel<3, decltype(m)>), grid, block, 0, s, e, m, n_per_group, packets, surface0, window, gamma);
+			});
+		else return hipErrorInvalidValue;
+		return hipGetLastError();
+	}
+	hipError_t launch_hop_evolve_sqc(hipStream_t s, const HopEnsemble& e, PesModel model, double mass, double dt, long n_steps, double x_left, double x_right, double gamma)
+	{
+		if (e.n <= 0 || n_steps <= 0) return hipSuccess;
+		const dim3 grid(hop_blocks(e.n)), block(HOP_BLOCK);
+		if (e.num_pes == 2)
+			with_model(model, [&](auto m) { hipLaunchKernelGGL((hop_evolve_sqc_kernel<2, decltype(m)>), grid, block, 0, s, e, m, mass, dt, n_steps, x_left, x_right, gamma); });
+		else if (e.num_pes == 3)
+			with_model(model, [&](auto m) { hipLaunchKernelGGL((hop_evolve_sqc_kernel<3, decltype(m)>), grid, block, 0, s, e, m, mass, dt, n_steps, x_left, x_right, gamma); });
+		else return hipErrorInvalidValue;
+		return hipGetLastError();
+	}
+	hipError_t launch_hop_evolve_groups_sqc(hipStream_t s, const HopEnsemble& e, PesModel model, long n_per_group, double mass, const double* dt, long n_steps,
+		double x_left, double x_right, double gamma)
+	{
+		if (e.n <= 0 || n_per_group <= 0) return hipErrorInvalidValue;
+		if (n_steps <= 0) return hipSuccess;
+		const dim3 grid(hop_blocks(e.n)), block(HOP_BLOCK);
+		if (e.num_pes == 2)
+			with_model(model, [&](auto m) {
+				hipLaunchKernelGGL((hop_evolve_groups_sqc_kernel<2, decltype(m)>), grid, block, 0, s, e, m, n_per_group, mass, dt, n_steps, x_left, x_right, gamma);
+			});
+		else if (e.num_pes == 3)
+			with_model(model, [&](auto m) {
+				hipLaunchKernelGGL((hop_evolve_groups_sqc_kernel<3, decltype(m)>), grid, block, 0, s, e, m, n_per_group, mass, dt, n_steps, x_left, x_right, gamma);
+			});
+		else return hipErrorInvalidValue;
+		return hipGetLastError();
+	}
+	size_t hop_observe_sqc_work_doubles(int num_pes, long n) { return static_cast<size_t>(hop_blocks(n)) * (HOP_BLOCK / HOP_WAVE) * (4 * num_pes + 9); }
+	hipError_t launch_hop_observe_sqc(hipStream_t s, const HopEnsemble& e, PesModel model, double mass, int window, double gamma, double* work, double* out)
+	{
+		if (e.n <= 0) return hipErrorInvalidValue;
+		const dim3 grid(hop_blocks(e.n)), block(HOP_BLOCK);
+		if (e.num_pes == 2) with_model(model, [&](auto m) { hipLaunchKernelGGL((hop_observe_sqc_kernel<2, decltype(m)>), grid, block, 0, s, e, m, mass, window, gamma, work); });
+		else if (e.num_pes == 3) with_model(model, [&](auto m) { hipLaunchKernelGGL((hop_observe_sqc_kernel<3, decltype(m)>), grid, block, 0, s, e, m, mass, window, gamma, work); });
+		else return hipErrorInvalidValue;
+		hipError_t err = hipGetLastError();
+		if (err != hipSuccess) return err;
+		const int width = 4 * e.num_pes + 9;
+		hipLaunchKernelGGL(hop_observe_finish_kernel, dim3(width), dim3(HOP_WAVE), 0, s, work, static_cast<long>(grid.x) * (HOP_BLOCK / HOP_WAVE), width, out);
+		return hipGetLastError();
+	}
+	size_t hop_observe_groups_sqc_work_doubles(int num_pes, long n_groups, long n_per_group)
+	{
+		return static_cast<size_t>(n_groups) * hop_blocks(n_per_group) * (HOP_BLOCK / HOP_WAVE) * (4 * num_pes + 9);
+	}
+	hipError_t launch_hop_observe_groups_sqc(hipStream_t s, const HopEnsemble& e, PesModel model, long n_groups, long n_per_group, double mass, int window, double gamma,
+		double* work, double* out)
+	{
+		if (n_groups <= 0 || n_per_group <= 0 || e.n != n_groups * n_per_group) return hipErrorInvalidValue;
+		const unsigned per_group = hop_blocks(n_per_group);
+		if (static_cast<unsigned long long>(n_groups) * per_group > 0x7FFFFFFFull) return hipErrorInvalidValue;
+		const dim3 grid(static_cast<unsigned>(n_groups * per_group)), block(HOP_BLOCK);
+		if (e.num_pes == 2)
+			with_model(model, [&](auto m) {
+				hipLaunchKernelGGL((hop_observe_groups_sqc_kernel<2, decltype(m)>), grid, block, 0, s, e, m, n_per_group, per_group, mass, window, gamma, work);
+			});
+		else if (e.num_pes == 3)
+			with_model(model, [&](auto m) {
+				hipLaunchKernelGGL((hop_observe_groups_sqc_kernel<3, decltype(m)>), grid, block, 0, s, e, m, n_per_group, per_group, mass, window, gamma, work);
+			});
+		else return hipErrorInvalidValue;
+		hipError_t err = hipGetLastError();
+		if (err != hipSuccess) return err;
+		const int width = 4 * e.num_pes + 9;
 		hipLaunchKernelGGL(hop_observe_finish_groups_kernel, dim3(static_cast<unsigned>(n_groups * width)), dim3(HOP_WAVE), 0, s, work,
 			static_cast<long>(per_group) * (HOP_BLOCK / HOP_WAVE), width, out);
 		return hipGetLastError();

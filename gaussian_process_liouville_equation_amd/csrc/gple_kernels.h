@@ -458,6 +458,22 @@ namespace gple
 	hipError_t launch_hop_observe_mf(hipStream_t s, const HopEnsemble& e, PesModel model, double mass, double* work, double* out);
 	size_t hop_observe_groups_mf_work_doubles(int num_pes, long n_groups, long n_per_group);
 	hipError_t launch_hop_observe_groups_mf(hipStream_t s, const HopEnsemble& e, PesModel model, long n_groups, long n_per_group, double mass, double* work, double* out);
+	// Symmetrical quasi-classical trajectories ("Symmetrical quasi-classical trajectories"): window is a GPLE_HOP_WINDOW_* of
+	// include/gple.h, gamma the zero-point parameter.  The samples write all five arrays (surface = surface0); the step and the sums read and
+	// write x, p, b and status only (surface may be null), the step being the mean-field one with the force b^dagger Fd b - gamma tr Fd
+	hipError_t launch_hop_sample_sqc(hipStream_t s, const HopEnsemble& e, PesModel model, double x0, double p0, double sigma_x, double sigma_p, int surface0, int window,
+		double gamma);
+	hipError_t launch_hop_sample_groups_sqc(hipStream_t s, const HopEnsemble& e, PesModel model, long n_per_group, const double* packets, int surface0, int window,
+		double gamma);
+	hipError_t launch_hop_evolve_sqc(hipStream_t s, const HopEnsemble& e, PesModel model, double mass, double dt, long n_steps, double x_left, double x_right, double gamma);
+	hipError_t launch_hop_evolve_groups_sqc(hipStream_t s, const HopEnsemble& e, PesModel model, long n_per_group, double mass, const double* dt, long n_steps,
+		double x_left, double x_right, double gamma);
+	// out: 4 num_pes + 9 sums (include/gple.h), the tree of launch_hop_observe at that width; the grouped form has n_groups such rows
+	size_t hop_observe_sqc_work_doubles(int num_pes, long n);
+	hipError_t launch_hop_observe_sqc(hipStream_t s, const HopEnsemble& e, PesModel model, double mass, int window, double gamma, double* work, double* out);
+	size_t hop_observe_groups_sqc_work_doubles(int num_pes, long n_groups, long n_per_group);
+	hipError_t launch_hop_observe_groups_sqc(hipStream_t s, const HopEnsemble& e, PesModel model, long n_groups, long n_per_group, double mass, int window, double gamma,
+		double* work, double* out);
 	// the uniform grid of gple_hop_bin: a point belongs to its nearest grid point, floor((x - x_first) / dx + 0.5) and the same for p
 	struct HopGrid
 	{

@@ -14,6 +14,10 @@ correction of every step (gple_hop_evolve_dc / gple_hop_evolve_groups_dc; DESIGN
 run() and scan() also take method = "fssh" (the default, everything above) or "ehrenfest": mean-field trajectories from the same sample, the other
 trajectory baseline (gple_hop_evolve_mf / _observe_mf and their _groups forms; DESIGN.md §17, "Mean-field (Ehrenfest) trajectories"), with
 unpack_mf() for their sums: a trajectory carries all its amplitudes and moves on the force averaged over them, without hops or random numbers.
+method = "sqc" with window = "triangle" (the default) or "square" and gamma (None: 1 / 3 or (sqrt(3) - 1) / 2) is the third baseline: the
+Meyer-Miller-Stock-Thoss mapping Hamiltonian run classically from a sample of actions and angles, populations read off by binning the final
+actions into the symmetrical windows of Cotton and Miller (gple_hop_sample_sqc / _evolve_sqc / _observe_sqc and their _groups forms; DESIGN.md
+§17, "Symmetrical quasi-classical trajectories"), with unpack_sqc() for its sums.  window or gamma with another method is a ValueError.
 """
 import os
 import time
@@ -21,6 +25,7 @@ import time
 import numpy as np
 
 from . import exact
+from ._capi import HOP_WINDOW_GAMMA, HOP_WINDOW_NAMES, HOP_WINDOW_SQUARE
 
 SAC, DAC, ECR, TSAC = exact.SAC, exact.DAC, exact.ECR, exact.TSAC
 RUNNING, LEFT, RIGHT = 0, 1, 2  # the status of a trajectory
@@ -61,15 +66,67 @@ def averages_line_mf(t, rec):
     return " ".join(exact.fmt(v) for v in [t, rec["E"], rec["x"], rec["p"], *rec["populations"]]) + "\n"
 
 
-def _method(method, decoherence, reverse_frustrated, phase_grid=None):
-    """method of run() and scan(), checked against the options that need an active surface -> True for the mean-field one"""
-    if method not in METHODS:
-        raise ValueError(f"method is one of {METHODS}")
+SQC = "sqc"  # the third method: its ensemble comes from a sample of its own (hop_sample_sqc), METHODS are the two that share hop_sample's
+
+
+def _method(method, decoherence, reverse_frustrated, phase_grid=None, window=None, gamma=None):
+    """method of run() and scan(), checked against the options that need an active surface -> True for the mean-field one, SQC for "sqc" """
+    if method not in METHODS + (SQC,):
+        raise ValueError(f"method is one of {METHODS + (SQC,)}")
+    if method != SQC and (window is not None or gamma is not None):
+        raise ValueError('window and gamma belong to method="sqc"')
     if method == "fssh":
         return False
     if decoherence is not None or reverse_frustrated or phase_grid is not None:
-        raise ValueError("ehrenfest trajectories have no active surface: no decoherence correction, no frustrated hops and (DESIGN.md §17) no phase_grid")
-    return True
+        raise ValueError(f"{method} trajectories have no active surface: no decoherence correction, no frustrated hops and (DESIGN.md §17) no phase_grid")
+    return True if method == "ehrenfest" else SQC
+
+
+def sqc_window(window, gamma):
+    """(GPLE_HOP_WINDOW_*, gamma) of run() and scan(): window "triangle" (None) or "square"; gamma None is the window's customary value, 1 / 3 or
+    (sqrt(3) - 1) / 2.  What the library would refuse is a ValueError here, before any call"""
+    name = "triangle" if window is None else window
+    if name not in HOP_WINDOW_NAMES:
+        raise ValueError(f"window is one of {sorted(HOP_WINDOW_NAMES)}")
+    code = HOP_WINDOW_NAMES[name]
+    gamma = HOP_WINDOW_GAMMA[code] if gamma is None else float(gamma)
+    if not np.isfinite(gamma) or gamma < 0.0 or (code == HOP_WINDOW_SQUARE and not 0.0 < gamma < 0.5):
+        raise ValueError("gamma is finite and not negative, and inside (0, 1/2) for the square window")
+    return code, gamma
+
+
+def unpack_sqc(sums, num_pes, n_traj, gamma):
+    """The 4 num_pes + 9 sums of hop_observe_sqc over n_traj trajectories -> counts (3, num_pes) [status][k] the trajectories of that status in
+    the window of state k, n_status (3,) the trajectories per status, none (3,) those of each status in no window (counts.sum(1) + none ==
+    n_status), e (num_pes,) = mean e_k, actions = e - gamma, windowed (num_pes,) the fraction of ALL trajectories in window k, unassigned the
+    fraction in none, x, p, E = the means of x, p and H = p^2 / 2m + sum_k (e_k - gamma) E_k"""
+    sums = np.asarray(sums, dtype=np.float64)
+    N = num_pes
+    if sums.shape != (4 * N + 9,):
+        raise ValueError("hop_observe_sqc returns 4 num_pes + 9 sums")
+    counts = sums[:3 * N].reshape(3, N).copy()
+    e = sums[3 * N + 6:4 * N + 6] / n_traj
+    return dict(counts=counts, n_status=sums[3 * N:3 * N + 3].copy(), none=sums[3 * N + 3:3 * N + 6].copy(), e=e, actions=e - gamma,
+                windowed=counts.sum(axis=0) / n_traj, unassigned=sums[3 * N + 3:3 * N + 6].sum() / n_traj, x=sums[4 * N + 6] / n_traj,
+                p=sums[4 * N + 7] / n_traj, E=sums[4 * N + 8] / n_traj)
+
+
+def averages_line_sqc(t, rec):
+    """One line of an SQC averages.txt: t <E> <x> <p>, the windowed fraction per state over all statuses, the mean action per state, the
+    unassigned fraction"""
+    return " ".join(exact.fmt(v) for v in [t, rec["E"], rec["x"], rec["p"], *rec["windowed"], *rec["actions"], rec["unassigned"]]) + "\n"
+
+
+def sqc_channels(counts, n_status, none):
+    """From the last sums of an ensemble (or, with a leading axis, of every group): the channels (..., 2, num_pes) = counts[side][k] / N_f, N_f
+    the FINISHED AND WINDOWED trajectories (0 where N_f = 0), N_f itself, and the unassigned fraction of the finished ones (0 where none finished)"""
+    counts, n_status, none = (np.asarray(a, dtype=np.float64) for a in (counts, n_status, none))
+    finished = counts[..., 1:, :]
+    n_f = finished.sum(axis=(-2, -1))
+    n_done = n_status[..., 1:].sum(axis=-1)
+    channels = np.divide(finished, n_f[..., None, None], out=np.zeros_like(finished), where=n_f[..., None, None] > 0)
+    lost = np.divide(none[..., 1:].sum(axis=-1), n_done, out=np.zeros_like(n_done), where=n_done > 0)
+    return channels, n_f, lost
 
 
 GRID_KEYS = ("x_first", "dx", "n_x", "p_first", "dp", "n_p")
@@ -99,7 +156,7 @@ def phase_grid_of(api, num_pes, model, s, phase_grid):
 
 
 def run(api, model=DAC, num_pes=2, ln_energy=0.0, n_traj=10000, seed=0, out_dir=None, reverse_frustrated=False, dt=None, surface0=0, max_outputs=None,
-        log=None, phase_grid=None, decoherence=None, edc_c=0.1, method="fssh", **setup_kw):
+        log=None, phase_grid=None, decoherence=None, edc_c=0.1, method="fssh", window=None, gamma=None, **setup_kw):
     """n_traj trajectories from the packet of exact.setup(ln_energy, boundary=ABSORBING, **setup_kw) (x0, sigma_x, p0, sigma_p, mass) on the adiabatic
     surface surface0, evolved with the time step dt (default: the setup's dt_rule, the reference's own rule) between x_left = xmin and
     x_right = xmax; a trajectory that leaves is finished and counted by side and active surface.  The ensemble stays on the device: every
@@ -116,9 +173,13 @@ def run(api, model=DAC, num_pes=2, ln_energy=0.0, n_traj=10000, seed=0, out_dir=
     one hop_evolve_mf and one hop_observe_mf, whose record is unpack_mf()'s; the run stops when n_status[0] == 0.  An averages.txt line is then
     averages_line_mf (no active-surface columns), and the scattering line holds weights[left][k] / n, weights[right][k] / n and n_status[0] / n
     in the same columns.  decoherence, reverse_frustrated=True or a phase_grid with "ehrenfest" is a ValueError.
+    method "sqc" with window ("triangle", the default, or "square") and gamma (None: the window's customary value): _run_sqc below; the same
+    options are a ValueError with it, and so are window or gamma with another method.
     Returns the setup, the records (t and unpack() per output time), stop, and scattering_line: the head of exact.run's final line, the
     fractions that left [left | right][surface], and the fraction still running."""
-    mean_field = _method(method, decoherence, reverse_frustrated, phase_grid)
+    mean_field = _method(method, decoherence, reverse_frustrated, phase_grid, window, gamma)
+    if mean_field == SQC:
+        return _run_sqc(api, model, num_pes, ln_energy, n_traj, seed, out_dir, dt, surface0, max_outputs, log, window, gamma, setup_kw)
     setup_kw["boundary"] = exact.ABSORBING
     s = exact.setup(ln_energy, **setup_kw)
     num_pes, n_traj = int(num_pes), int(n_traj)
@@ -207,7 +268,7 @@ def _per_group(setup_kw, n_groups):
 
 
 def scan(api, model=DAC, num_pes=2, ln_energies=None, momenta=None, n_per_group=10000, seed=0, fixed=True, surface0=0, dt=None, chunk_steps=4096,
-         max_steps=None, reverse_frustrated=False, out_dir=None, log=None, decoherence=None, edc_c=0.1, method="fssh", **setup_kw):
+         max_steps=None, reverse_frustrated=False, out_dir=None, log=None, decoherence=None, edc_c=0.1, method="fssh", window=None, gamma=None, **setup_kw):
     """The branching probabilities as a function of the incoming momentum, Tully's plot, from ONE ensemble of len(ln_energies) (or len(momenta))
     groups of n_per_group trajectories.  Group g takes its constants from exact.setup(ln_energies[g], boundary=ABSORBING, **setup_kw) (momenta:
     p0 = momenta[g] instead): x0, p0, mass, the bounds xmin and xmax, its time step dt_rule unless dt (a number, or one per group) overrides
@@ -227,8 +288,10 @@ def scan(api, model=DAC, num_pes=2, ln_energies=None, momenta=None, n_per_group=
     hops and frustrated are 0 (hop_counts is None), energy_drift comes from the mean-field energy p^2 / 2m + sum_k |c_k|^2 E_k.  stderr is then
     an UPPER BOUND: a fraction f is the mean of weights in [0, 1], whose variance is at most f (1 - f).  With fixed=True every trajectory of a
     group is the same trajectory (nothing is random), so n_per_group = 1 is enough.  decoherence or reverse_frustrated=True with "ehrenfest" is
-    a ValueError."""
-    mean_field = _method(method, decoherence, reverse_frustrated)
+    a ValueError.  method "sqc" with window and gamma as run(): _scan_sqc below, on the groups made here."""
+    mean_field = _method(method, decoherence, reverse_frustrated, None, window, gamma)
+    if mean_field == SQC:
+        window, gamma = sqc_window(window, gamma)
     if (ln_energies is None) == (momenta is None):
         raise ValueError("give ln_energies or momenta, one of them")
     given = np.atleast_1d(np.asarray(ln_energies if momenta is None else momenta, dtype=np.float64))
@@ -251,6 +314,8 @@ def scan(api, model=DAC, num_pes=2, ln_energies=None, momenta=None, n_per_group=
     packets = np.array([[s["x0"], s["p0"], 0.0 if fixed else s["sigma_x"], 0.0 if fixed else s["sigma_p"]] for s in setups])
     correction = {} if decoherence is None else dict(decoherence=decoherence, edc_c=edc_c)
     say = log or (lambda *_: None)
+    if mean_field == SQC:
+        return _scan_sqc(api, model, num_pes, n_per_group, seed, surface0, chunk_steps, max_steps, out_dir, say, window, gamma, setups, dts, total_step, packets)
     t0 = time.perf_counter()
     state = api.hop_sample_groups(num_pes, model, n_per_group, seed, packets, surface0, device_out=True)
     on_device = hasattr(state[0], "is_cuda")
@@ -304,3 +369,98 @@ def scan(api, model=DAC, num_pes=2, ln_energies=None, momenta=None, n_per_group=
     return dict(setups=setups, dt=dts, n_per_group=n_per_group, total_step=total_step, max_steps=max_steps, steps=step, stop=stop, state=state,
                 hop_counts=counts, rows=rows, head=head, scattered=scattered, running=running, stderr=stderr, hops=hops, frustrated=frustrated,
                 energy_drift=drift, lines=lines, total_seconds=t_end - t0, decoherence=decoherence, edc_c=edc_c, method=method)
+
+
+# ---- method="sqc": symmetrical quasi-classical trajectories ("Symmetrical quasi-classical trajectories") ----------------------------
+def _run_sqc(api, model, num_pes, ln_energy, n_traj, seed, out_dir, dt, surface0, max_outputs, log, window, gamma, setup_kw):
+    """run(method="sqc"): the loop of run() on hop_sample_sqc, hop_evolve_sqc and hop_observe_sqc.  One sample; per output time one evolve and
+    one observe, whose record is unpack_sqc()'s; the run stops when n_status[0] == 0.  averages.txt holds averages_line_sqc.  The scattering
+    line keeps run()'s columns with channel (side, k) = counts[side][k] / N_f, N_f the finished and windowed trajectories (all 0 where
+    N_f = 0), then n_status[0] / n, and as a new last column the unassigned fraction of the finished trajectories"""
+    window, gamma = sqc_window(window, gamma)
+    setup_kw["boundary"] = exact.ABSORBING
+    s = exact.setup(ln_energy, **setup_kw)
+    num_pes, n_traj = int(num_pes), int(n_traj)
+    dt = float(s["dt_rule"] if dt is None else dt)
+    output_step, total_step = int(s["output_time"] / dt), int(s["total_time"] / dt)
+    if output_step < 1:
+        raise ValueError("the output time is shorter than one time step")
+    say = log or (lambda *_: None)
+    t0 = time.perf_counter()
+    state = api.hop_sample_sqc(num_pes, model, n_traj, seed, s["x0"], s["p0"], s["sigma_x"], s["sigma_p"], surface0, window, gamma, device_out=True)
+    files = {}
+    if out_dir is not None:
+        os.makedirs(out_dir, exist_ok=True)
+        files = {name: open(os.path.join(out_dir, name), "w") for name in ("t.txt", "averages.txt")}
+    records, stop, step = [], None, 0
+    try:
+        while True:
+            rec = unpack_sqc(api.hop_observe_sqc(num_pes, model, state, s["mass"], window, gamma), num_pes, n_traj, gamma)
+            rec["t"] = step * dt
+            records.append(rec)
+            if files:
+                files["t.txt"].write(exact.fmt(rec["t"]) + "\n")
+                files["averages.txt"].write(averages_line_sqc(rec["t"], rec))
+            if rec["n_status"][RUNNING] == 0:
+                stop = f"NO TRAJECTORY IS RUNNING, STOP EVOLVING AT {rec['t']:g}"
+                break
+            if step + output_step > total_step or (max_outputs is not None and len(records) >= max_outputs):
+                break
+            state = api.hop_evolve_sqc(num_pes, model, state, s["mass"], dt, output_step, s["xmin"], s["xmax"], gamma)
+            step += output_step
+    finally:
+        for f in files.values():
+            f.close()
+    t_end = time.perf_counter()
+    say(stop or "FINISHED ALL OUTPUT TIMES")
+    last = records[-1]
+    channels, n_f, lost = sqc_channels(last["counts"], last["n_status"], last["none"])
+    head = np.log(s["p0"] ** 2 / 2.0 / s["mass"]) if model == DAC else s["p0"]  # as exact.run (main.cpp:308-321)
+    line = " ".join(exact.fmt(v) for v in [head, *channels.reshape(-1), last["n_status"][RUNNING] / n_traj, lost])
+    return dict(setup=s, dt=dt, output_step=output_step, total_step=total_step, n_traj=n_traj, records=records, stop=stop, state=state,
+                scattered=channels, scattering_line=line, stop_time=last["t"], steps=step, total_seconds=t_end - t0, decoherence=None, edc_c=None,
+                method=SQC, window=window, gamma=gamma, n_finished_windowed=float(n_f), unassigned_finished=float(lost))
+
+
+def _scan_sqc(api, model, num_pes, n_per_group, seed, surface0, chunk_steps, max_steps, out_dir, say, window, gamma, setups, dts, total_step, packets):
+    """scan(method="sqc"): the loop of scan() on hop_sample_groups_sqc, hop_evolve_groups_sqc and hop_observe_groups_sqc.  scan.txt keeps its
+    columns: channel (side, k) = counts[side][k] / N_f per group (0 where N_f = 0) with stderr sqrt(f (1 - f) / N_f), running = n_status[0] /
+    n_per_group with stderr over n_per_group, hops and frustrated 0, energy_drift from H; the unassigned fraction of the group's finished
+    trajectories is appended as a new last column"""
+    N, n_groups, s0 = num_pes, len(setups), setups[0]
+    width, step, stop = 4 * N + 9, 0, None
+    t0 = time.perf_counter()
+    state = api.hop_sample_groups_sqc(N, model, n_per_group, seed, packets, surface0, window, gamma, device_out=True)
+    observe = lambda: np.asarray(api.hop_observe_groups_sqc(N, model, state, n_per_group, s0["mass"], window, gamma), dtype=np.float64).reshape(n_groups, width)
+    first = rows = observe()
+    while True:
+        if rows[:, 3 * N].sum() == 0:
+            stop = f"NO TRAJECTORY IS RUNNING, STOP EVOLVING AT STEP {step}"
+            break
+        if step >= max_steps:
+            break
+        n_steps = min(chunk_steps, max_steps - step)
+        state = api.hop_evolve_groups_sqc(N, model, state, n_per_group, s0["mass"], dts, n_steps, s0["xmin"], s0["xmax"], gamma)
+        step += n_steps
+        rows = observe()
+    t_end = time.perf_counter()
+    say(stop or f"STOPPED AT {max_steps} STEPS")
+    scattered, n_f, lost = sqc_channels(rows[:, :3 * N].reshape(n_groups, 3, N), rows[:, 3 * N:3 * N + 3], rows[:, 3 * N + 3:3 * N + 6])
+    running = rows[:, 3 * N] / n_per_group
+    channels = scattered.reshape(n_groups, 2 * N)
+    spread = channels * (1.0 - channels)
+    stderr = np.concatenate([np.sqrt(np.divide(spread, n_f[:, None], out=np.zeros_like(spread), where=n_f[:, None] > 0)),
+                             np.sqrt(running * (1.0 - running) / n_per_group)[:, None]], axis=1)
+    fractions = np.concatenate([channels, running[:, None]], axis=1)
+    head = np.array([np.log(s["p0"] ** 2 / 2.0 / s["mass"]) if model == DAC else s["p0"] for s in setups])
+    hops = frustrated = np.zeros(n_groups)
+    drift = (rows[:, width - 1] - first[:, width - 1]) / n_per_group
+    lines = [scan_line([head[g], *fractions[g], *stderr[g], hops[g], frustrated[g], drift[g], lost[g]]) for g in range(n_groups)]
+    if out_dir is not None:
+        os.makedirs(out_dir, exist_ok=True)
+        with open(os.path.join(out_dir, "scan.txt"), "w") as f:
+            f.write("".join(lines))
+    return dict(setups=setups, dt=dts, n_per_group=n_per_group, total_step=total_step, max_steps=max_steps, steps=step, stop=stop, state=state,
+                hop_counts=None, rows=rows, head=head, scattered=scattered, running=running, stderr=stderr, hops=hops, frustrated=frustrated,
+                energy_drift=drift, lines=lines, total_seconds=t_end - t0, decoherence=None, edc_c=None, method=SQC, window=window, gamma=gamma,
+                n_finished_windowed=n_f, unassigned_finished=lost)

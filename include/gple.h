@@ -160,7 +160,8 @@ typedef enum gple_timer {
 	GPLE_TIMER_HOP = 12,           /* the step kernel of one gple_hop_evolve or gple_hop_evolve_dc call (all its steps, no staging); count = calls */
 	GPLE_TIMER_HOP_BIN = 13,       /* the bin kernel of one gple_hop_bin call (no staging, no clear); count = calls */
 	GPLE_TIMER_HOP_GROUPS = 14,    /* the step kernel of one gple_hop_evolve_groups or _groups_dc call (all its steps, no staging); count = calls */
-	GPLE_TIMER_HOP_MF = 15         /* the step kernel of one gple_hop_evolve_mf or gple_hop_evolve_groups_mf call (all its steps, no staging); count = calls */
+	GPLE_TIMER_HOP_MF = 15,        /* the step kernel of one gple_hop_evolve_mf or gple_hop_evolve_groups_mf call (all its steps, no staging); count = calls */
+	GPLE_TIMER_HOP_SQC = 16        /* the step kernel of one gple_hop_evolve_sqc or gple_hop_evolve_groups_sqc call (all its steps, no staging); count = calls */
 } gple_timer;
 int gple_ctx_enable_timing(gple_ctx* ctx, int on);
 /* Synchronises the stream, then: last = milliseconds of the most recent interval; total / count = accumulated since
@@ -392,7 +393,7 @@ int gple_pes_adiabatic_n(gple_ctx* ctx, int num_pes, int model, const double* x,
  * V = V_0 + V'_0 (x - x_first), V' = V'_0, and for s > n - 1 the same from the last node.  With nodes taken from a smooth function the error is
  * at most dx^4 / 384 max|V''''| for the value and sqrt(3) / 216 dx^3 max|V''''| for the derivative.
  * A user id is accepted, on the context it was defined on and with the num_pes it was defined with (GPLE_ERR_BAD_ARG otherwise), by
- * gple_pes_adiabatic_n, gple_pes_diabatic_n, gple_evolve_n, gple_dvr_hamiltonian, gple_mqcl_transform / _evolve / _observe, gple_hop_sample / _evolve / _observe / _bin (and the _groups, _dc and _mf forms),
+ * gple_pes_adiabatic_n, gple_pes_diabatic_n, gple_evolve_n, gple_dvr_hamiltonian, gple_mqcl_transform / _evolve / _observe, gple_hop_sample / _evolve / _observe / _bin (and the _groups, _dc, _mf and _sqc forms),
  * gple_grid_survey and gple_grid_reconstruct / _cross.  The two-level entry points gple_pes_adiabatic and gple_evolve keep refusing it: they use the reference's closed
  * forms and operation order, of which a table has none; gple_evolve_n at num_pes = 2 reproduces gple_evolve to rounding and takes their place.
  * Where two surfaces of a user model touch (E_j = E_k) with F_jk != 0 the non-adiabatic coupling is infinite, as its formula says: not guarded.
@@ -672,6 +673,57 @@ int gple_hop_observe_mf(gple_ctx* ctx, int num_pes, int model, size_t n, double 
 	const double* b, const int* status, double* out);
 int gple_hop_observe_groups_mf(gple_ctx* ctx, int num_pes, int model, size_t n_groups, size_t n_per_group, double mass, unsigned flags,
 	const double* x, const double* p, const double* b, const int* status, double* out);
+/* Symmetrical quasi-classical (SQC) trajectories ("Symmetrical quasi-classical trajectories"): the Meyer-Miller-Stock-Thoss
+ * mapping Hamiltonian run classically, with the symmetrical windows of Cotton and Miller.  A trajectory is x, p, the diabatic mapping
+ * amplitudes b (num_pes complex numbers, NOT normalised) and its status, in the five arrays of every other ensemble; surface is written by the
+ * sample (= surface0) and neither read nor passed afterwards.  With c = C^T b at the trajectory's x (formed as gple_hop_observe forms it),
+ * e_k = |c_k|^2 and the action n_k = e_k - gamma, gamma being the zero-point parameter:
+ *     H = p^2 / 2 mass + b^dagger V b - gamma tr V = p^2 / 2 mass + sum_k (e_k - gamma) E_k
+ *     f(x, b) = [the running sum of gple_hop_evolve_mf, in its order] - gamma (Fd_00 + ... + Fd_{NP-1,NP-1}):
+ *               the trace is added left to right, the product formed, then subtracted.
+ * The amplitudes obey i db/dt = V b: steps 1 to 4 are those of gple_hop_evolve_mf with this f.  No eigen-system of V(x), nothing random in the
+ * step; evolve(a) then evolve(b) gives the bits of evolve(a + b); sum_k |b_k|^2 is conserved to rounding and is not 1.
+ * Windows, in the adiabatic representation, in terms of e, with F = num_pes and occ = surface0:
+ *   GPLE_HOP_WINDOW_SQUARE    0 < gamma < 1/2 (the windows are disjoint); customary gamma = (sqrt(3) - 1) / 2.
+ *       start:  e_k = delta_{k,occ} + 2 gamma u_k
+ *       final window of state k:  1 <= e_k <= 1 + 2 gamma  and  e_j <= 2 gamma for all j != k
+ *   GPLE_HOP_WINDOW_TRIANGLE  any finite gamma >= 0 (gamma enters H only); customary gamma = 1 / 3.
+ *       start:  t = (1 - u_occ)^(1/F) (sqrt at two levels, cbrt at three),  e_occ = 2 - t,  e_j = u_j t for j != occ:
+ *               the density (2 - e)^(F-1) on [1, 2] for the occupied state, the others uniform on [0, 2 - e_occ]
+ *       final window of state k:  e_k >= 1  and  e_k + e_j <= 2 for all j != k
+ * A trajectory belongs to the first k ascending whose window holds it, else to none.
+ * Random numbers of the sample (Philox4x32-10, key (seed low, seed high), index = trajectory_offset + i): x and p from the counter
+ * (index, 0, 1, 0) by the lines of gple_hop_sample: the same bits for the same index, seed and packet, the sigma == 0 select of the grouped
+ * form included.  Level k draws (u_k, v_k) = unit53 of the words (0, 1) and (2, 3) of the counter (index, k, 2, 0).  Then
+ * c_k = sqrt(e_k) (cospi(2 v_k) + i sinpi(2 v_k)), b = C(x) c, status 0.
+ * gple_hop_sample_groups_sqc: the packets table of gple_hop_sample_groups.  gple_hop_evolve_groups_sqc: dt[group]; a group's state has the
+ * bits of gple_hop_evolve_sqc on that slice.  Timer of both evolve calls: GPLE_TIMER_HOP_SQC.  n_steps <= 2^40 (0: nothing happens).
+ * gple_hop_observe_sqc: sums in the fixed tree of gple_hop_observe.  out, 4 num_pes + 9 doubles:
+ *     [s num_pes + k], s = 0, 1, 2   the trajectories of status s in window k (exact integers)
+ *     [3 num_pes + s]                the trajectories of status s
+ *     [3 num_pes + 3 + s]            the trajectories of status s in no window (windowed + none = the count of the status)
+ *     [3 num_pes + 6 + k]            sum of e_k over the trajectories of status 0 ... 2
+ *     then sum x, sum p, sum (p^2 / 2 mass + sum_k (e_k - gamma) E_k), k ascending, over the same trajectories
+ * A status outside 0 ... 2 adds nowhere.  gple_hop_observe_groups_sqc: n_groups such rows (out is a host array), row g with the bits of
+ * gple_hop_observe_sqc on that slice.  Arrays, GPLE_IO_DEVICE and the tables as the calls above.
+ * GPLE_ERR_BAD_ARG, with nothing written: everything gple_hop_sample (_groups), gple_hop_evolve_mf (_groups_mf) and gple_hop_observe_mf
+ * (_groups_mf) refuse; window not a GPLE_HOP_WINDOW_*; gamma not finite or negative; for the square window gamma outside (0, 1/2); the flag
+ * GPLE_HOP_REVERSE. */
+#define GPLE_HOP_WINDOW_SQUARE 0
+#define GPLE_HOP_WINDOW_TRIANGLE 1
+int gple_hop_sample_sqc(gple_ctx* ctx, int num_pes, int model, size_t n, size_t trajectory_offset, unsigned long long seed, double x0, double p0,
+	double sigma_x, double sigma_p, int surface0, int window, double gamma, unsigned flags, double* x, double* p, double* b, int* surface, int* status);
+int gple_hop_sample_groups_sqc(gple_ctx* ctx, int num_pes, int model, size_t n_groups, size_t n_per_group, size_t trajectory_offset,
+	unsigned long long seed, const double* packets, int surface0, int window, double gamma, unsigned flags, double* x, double* p, double* b,
+	int* surface, int* status);
+int gple_hop_evolve_sqc(gple_ctx* ctx, int num_pes, int model, size_t n, double mass, double dt, size_t n_steps, double x_left, double x_right,
+	double gamma, unsigned flags, double* x, double* p, double* b, int* status);
+int gple_hop_evolve_groups_sqc(gple_ctx* ctx, int num_pes, int model, size_t n_groups, size_t n_per_group, double mass, const double* dt,
+	size_t n_steps, double x_left, double x_right, double gamma, unsigned flags, double* x, double* p, double* b, int* status);
+int gple_hop_observe_sqc(gple_ctx* ctx, int num_pes, int model, size_t n, double mass, int window, double gamma, unsigned flags, const double* x,
+	const double* p, const double* b, const int* status, double* out);
+int gple_hop_observe_groups_sqc(gple_ctx* ctx, int num_pes, int model, size_t n_groups, size_t n_per_group, double mass, int window, double gamma,
+	unsigned flags, const double* x, const double* p, const double* b, const int* status, double* out);
 
 /* generate_markov_chain (mc.cpp:118-165) for n walkers at once on the fitted distribution |cut-off prediction| of `element`:
  * num_steps Metropolis steps with uniform displacements in [-max_displacement, max_displacement) per dimension; r (2n) holds
