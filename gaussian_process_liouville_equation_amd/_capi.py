@@ -25,6 +25,7 @@ TIMER_HOP_BIN = 13  # gple_timer: the bin kernel of one gple_hop_bin call
 TIMER_HOP_GROUPS = 14  # gple_timer: the step kernel of one gple_hop_evolve_groups call
 TIMER_HOP_MF = 15  # gple_timer: the step kernel of one gple_hop_evolve_mf or gple_hop_evolve_groups_mf call
 TIMER_HOP_SQC = 16  # gple_timer: the step kernel of one gple_hop_evolve_sqc or gple_hop_evolve_groups_sqc call
+TIMER_HOP_MASH = 17  # gple_timer: the step kernel of one gple_hop_evolve_mash or gple_hop_evolve_groups_mash call
 HOP_MAX_GROUPS = 65536  # GPLE_HOP_MAX_GROUPS
 # GPLE_HOP_WINDOW_*: the windows of the symmetrical quasi-classical trajectories, the names Api.hop_sample_sqc / hop_observe_sqc take for them, and
 # the customary zero-point parameter gamma of each
@@ -392,6 +393,11 @@ def _signatures():
         "hop_evolve_groups_sqc": (st, [CTX, i, i, sz, sz, d, _dp, sz, d, d, d, u, _dp, _dp, _dp, ip]),
         "hop_observe_sqc": (st, [CTX, i, i, sz, d, i, d, u, _dp, _dp, _dp, ip, _dp]),
         "hop_observe_groups_sqc": (st, [CTX, i, i, sz, sz, d, i, d, u, _dp, _dp, _dp, ip, _dp]),
+        # MASH trajectories
+        "hop_sample_mash": (st, [CTX, i, i, sz, sz, ull, d, d, d, d, i, u, _dp, _dp, _dp, ip, ip]),
+        "hop_sample_groups_mash": (st, [CTX, i, i, sz, sz, sz, ull, _dp, i, u, _dp, _dp, _dp, ip, ip]),
+        "hop_evolve_mash": (st, [CTX, i, i, sz, d, d, sz, d, d, u, _dp, _dp, _dp, ip, ip]),
+        "hop_evolve_groups_mash": (st, [CTX, i, i, sz, sz, d, _dp, sz, d, d, u, _dp, _dp, _dp, ip, ip, ip]),
         # many NLML problems in one launch; the search of several planes in lock-step on it
         "nlml_batch": (st, [CTX, C.POINTER(NlmlProblem), sz, i, u, _dp, _dp, C.POINTER(_dp), ip]),
         "nlml_fit_planes": (st, [CTX, C.POINTER(NlmlFitPlane), sz, i, opt, _dp, _dp, ip, C.POINTER(_dp)]),
@@ -573,7 +579,8 @@ class Api:
         steps, 6 = the device work of the reconstruction entry points, 7 = the kernels of format_g, 8 = the kernels of parse_g, 9 = the products of dvr_propagator, 10 = the products of dvr_flux,
         11 = the device work of dvr_spectrum, 12 = the step kernel of hop_evolve, 13 = the bin kernel of hop_bin,
         14 = the step kernel of hop_evolve_groups (12 and 14 also with a decoherence correction), 15 = the step kernel of hop_evolve_mf and
-        hop_evolve_groups_mf, 16 = the step kernel of hop_evolve_sqc and hop_evolve_groups_sqc."""
+        hop_evolve_groups_mf, 16 = the step kernel of hop_evolve_sqc and hop_evolve_groups_sqc, 17 = the step kernel of hop_evolve_mash and
+        hop_evolve_groups_mash."""
         last, total, count = C.c_double(), C.c_double(), C.c_long()
         self._check(self.lib.gple_ctx_get_timing(self.ctx, which, C.byref(last), C.byref(total), C.byref(count)))
         return last.value, total.value, count.value
@@ -1389,6 +1396,78 @@ class Api:
         self._check(self.lib.gple_hop_observe_groups_sqc(self.ctx, int(num_pes), int(model), n_groups, n_per_group, float(mass), window, gamma, flags, *pointers,
                                                          _ptr(out)))
         return out
+
+    # ---- MASH trajectories (gple_hop_*_mash; DESIGN.md §17, "MASH trajectories") -------------------------------------------------------------------
+    # The ensemble is the same 5-tuple, two levels only.  The samples draw amplitudes of their own; the step needs no seed, step counter or
+    # offset; hop_observe and hop_observe_groups serve the ensemble unchanged
+    def hop_sample_mash(self, num_pes, model, n, seed, x0, p0, sigma_x, sigma_p, surface0=0, trajectory_offset=0, device_out=False):
+        """gple_hop_sample_mash: x and p as hop_sample draws them (the same bits), the amplitudes b with |S_z| drawn from the density 2 s on the
+        side of the adiabatic state surface0 -> the ensemble (x, p, b, surface, status).  num_pes is 2"""
+        num_pes, n = int(num_pes), int(n)
+        if n < 1:
+            raise ValueError("an ensemble has at least one trajectory")
+        state = self._hop_empty(num_pes, n, device_out)
+        pointers, flags = self._hop_pointers(state)
+        self._check(self.lib.gple_hop_sample_mash(self.ctx, num_pes, int(model), n, int(trajectory_offset), int(seed), float(x0), float(p0), float(sigma_x),
+                                                  float(sigma_p), int(surface0), flags, *pointers))
+        if device_out:
+            self.synchronize()
+        return state
+
+    def hop_sample_groups_mash(self, num_pes, model, n_per_group, seed, packets, surface0=0, trajectory_offset=0, device_out=False):
+        """gple_hop_sample_groups_mash: hop_sample_mash per row (x0, p0, sigma_x, sigma_p) of packets, as hop_sample_groups (a sigma may be 0)"""
+        num_pes, n_per_group, packets = int(num_pes), int(n_per_group), _f64(packets)
+        if packets.ndim != 2 or packets.shape[1] != 4 or packets.shape[0] < 1 or n_per_group < 1:
+            raise ValueError("packets is (n_groups, 4) with n_groups >= 1, and a group has at least one trajectory")
+        n_groups = packets.shape[0]
+        state = self._hop_empty(num_pes, n_groups * n_per_group, device_out)
+        pointers, flags = self._hop_pointers(state)
+        self._check(self.lib.gple_hop_sample_groups_mash(self.ctx, num_pes, int(model), n_groups, n_per_group, int(trajectory_offset), int(seed), _ptr(packets),
+                                                         int(surface0), flags, *pointers))
+        if device_out:
+            self.synchronize()
+        return state
+
+    def hop_evolve_mash(self, num_pes, model, state, mass, dt, n_steps, x_left, x_right):
+        """gple_hop_evolve_mash: n_steps MASH steps of every running trajectory (the active surface follows the amplitudes; nothing random).
+        numpy: returns the evolved copy; device tensors: evolves the ensemble in place (asynchronously on the context's stream) and returns it"""
+        state, n = self._hop_state(int(num_pes), state)
+        if not _on_device(state[0]):
+            state = tuple(a.copy() for a in state)
+        pointers, flags = self._hop_pointers(state)
+        self._check(self.lib.gple_hop_evolve_mash(self.ctx, int(num_pes), int(model), n, float(mass), float(dt), int(n_steps), float(x_left), float(x_right), flags,
+                                                  *pointers))
+        return state
+
+    def hop_evolve_groups_mash(self, num_pes, model, state, n_per_group, mass, dt, n_steps, x_left, x_right, hops=None):
+        """gple_hop_evolve_groups_mash: hop_evolve_mash with the time step dt[g] for group g; a group's state has the bits hop_evolve_mash gives
+        for that slice.  hops (None, or int32 (n, 2) on the side the ensemble is on): the hops taken and the frustrated hops of the call are
+        added to it; the return value is then (state, hops), a numpy hops being a copy"""
+        state, n = self._hop_state(int(num_pes), state)
+        n_groups, n_per_group = self._hop_groups(n, n_per_group)
+        dt = _f64(dt)
+        if dt.shape != (n_groups,):
+            raise ValueError("dt has one time step per group")
+        dev = _on_device(state[0])
+        if not dev:
+            state = tuple(a.copy() for a in state)
+        pointers, flags = self._hop_pointers(state)
+        ip, ph = C.POINTER(C.c_int), None
+        if hops is not None:
+            if _on_device(hops) != dev:
+                raise ValueError("hops lives on the side the ensemble is on")
+            if dev:
+                if not hops.is_cuda or not hops.is_contiguous() or str(hops.dtype) != "torch.int32" or tuple(hops.shape) != (n, 2):
+                    raise ValueError("device hops is a contiguous int32 tensor of shape (n, 2) on the GPU")
+                ph = C.cast(hops.data_ptr(), ip)
+            else:
+                hops = np.array(hops, dtype=np.int32, order="C")
+                if hops.shape != (n, 2):
+                    raise ValueError("hops has shape (n, 2)")
+                ph = hops.ctypes.data_as(ip)
+        self._check(self.lib.gple_hop_evolve_groups_mash(self.ctx, int(num_pes), int(model), n_groups, n_per_group, float(mass), _ptr(dt), int(n_steps),
+                                                         float(x_left), float(x_right), flags, *pointers, ph))
+        return state if hops is None else (state, hops)
 
     # ---- reconstruction of a gridded density with the NLML GP (test/main_evolve.cpp; gple_nlml_weights / gple_grid_*) -------------------------
     SURVEY_FIELDS = ("max", "min", "weight", "argmax", "population", "potential", "kinetic")

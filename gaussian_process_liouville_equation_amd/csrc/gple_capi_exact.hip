@@ -1041,4 +1041,142 @@ extern "C"
 		GPLE_HIP(ctx, hipStreamSynchronize(st));
 		return GPLE_OK;
 	}
+
+	/* ---- MASH trajectories ("MASH trajectories") -------------------------------------------------------------------------------- */
+	// what the four calls share beyond the checks of their models: two levels, no GPLE_HOP_REVERSE (MASH always reflects), five arrays
+	static bool hop_mash_ok(int num_pes, unsigned flags, const double* x, const double* p, const double* b, const int* surface, const int* status)
+	{
+		return num_pes == 2 && !(flags & GPLE_HOP_REVERSE) && x && p && b && surface && status;
+	}
+
+	int gple_hop_sample_mash(gple_ctx* ctx, int num_pes, int model, size_t n, size_t trajectory_offset, unsigned long long seed, double x0, double p0,
+		double sigma_x, double sigma_p, int surface0, unsigned flags, double* x, double* p, double* b, int* surface, int* status)
+	{
+		PesModel pes;
+		if (!ctx || !hop_mash_ok(num_pes, flags, x, p, b, surface, status) || !hop_size_ok(ctx, num_pes, model, n, trajectory_offset, &pes) || !hop_positive(sigma_x) ||
+			!hop_positive(sigma_p) || surface0 < 0 || surface0 >= num_pes)
+			return GPLE_ERR_BAD_ARG;
+		GPLE_OPEN(ctx);
+		const bool dev = flags & GPLE_IO_DEVICE;
+		GPLE_CALL(ctx);
+		if (!pes_resolve(ctx, num_pes, model, &pes)) return GPLE_ERR_BAD_ARG; // under the call lock, which gple_pes_undefine takes: the table outlives the enqueue
+		hipStream_t st = ctx->stream;
+		Staged xs(ctx, dev), ps(ctx, dev), bs(ctx, dev);
+		StagedInts su(ctx, dev), ss(ctx, dev);
+		GPLE_HIP(ctx, xs.out(x, n));
+		GPLE_HIP(ctx, ps.out(p, n));
+		GPLE_HIP(ctx, bs.out(b, 2 * n * num_pes));
+		GPLE_HIP(ctx, su.stage(surface, n, false, true));
+		GPLE_HIP(ctx, ss.stage(status, n, false, true));
+		const HopEnsemble e{num_pes, static_cast<long>(n), trajectory_offset, seed, xs.p, ps.p, bs.p, su.p, ss.p};
+		GPLE_HIP(ctx, launch_hop_sample_mash(st, e, pes, x0, p0, sigma_x, sigma_p, surface0));
+		for (Staged* o : {&xs, &ps, &bs}) GPLE_HIP(ctx, o->back());
+		for (StagedInts* o : {&su, &ss}) GPLE_HIP(ctx, o->back());
+		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
+		return GPLE_OK;
+	}
+
+	int gple_hop_sample_groups_mash(gple_ctx* ctx, int num_pes, int model, size_t n_groups, size_t n_per_group, size_t trajectory_offset,
+		unsigned long long seed, const double* packets, int surface0, unsigned flags, double* x, double* p, double* b, int* surface, int* status)
+	{
+		PesModel pes;
+		size_t n = 0;
+		if (!ctx || !hop_mash_ok(num_pes, flags, x, p, b, surface, status) ||
+			!hop_groups_ok(ctx, num_pes, model, n_groups, n_per_group, trajectory_offset, &pes, &n) || !packets || surface0 < 0 || surface0 >= num_pes)
+			return GPLE_ERR_BAD_ARG;
+		for (size_t g = 0; g < n_groups; ++g)
+		{
+			const double* row = packets + 4 * g;
+			if (!std::isfinite(row[0]) || !std::isfinite(row[1]) || !std::isfinite(row[2]) || !std::isfinite(row[3]) || row[2] < 0.0 || row[3] < 0.0) return GPLE_ERR_BAD_ARG;
+		}
+		GPLE_OPEN(ctx);
+		const bool dev = flags & GPLE_IO_DEVICE;
+		GPLE_CALL(ctx);
+		if (!pes_resolve(ctx, num_pes, model, &pes)) return GPLE_ERR_BAD_ARG; // under the call lock, which gple_pes_undefine takes: the table outlives the enqueue
+		hipStream_t st = ctx->stream;
+		Staged xs(ctx, dev), ps(ctx, dev), bs(ctx, dev);
+		StagedInts su(ctx, dev), ss(ctx, dev);
+		Scratch table(ctx);
+		GPLE_HIP(ctx, hop_table(table, packets, 4 * n_groups));
+		GPLE_HIP(ctx, xs.out(x, n));
+		GPLE_HIP(ctx, ps.out(p, n));
+		GPLE_HIP(ctx, bs.out(b, 2 * n * num_pes));
+		GPLE_HIP(ctx, su.stage(surface, n, false, true));
+		GPLE_HIP(ctx, ss.stage(status, n, false, true));
+		const HopEnsemble e{num_pes, static_cast<long>(n), trajectory_offset, seed, xs.p, ps.p, bs.p, su.p, ss.p};
+		GPLE_HIP(ctx, launch_hop_sample_groups_mash(st, e, pes, static_cast<long>(n_per_group), table.p, surface0));
+		for (Staged* o : {&xs, &ps, &bs}) GPLE_HIP(ctx, o->back());
+		for (StagedInts* o : {&su, &ss}) GPLE_HIP(ctx, o->back());
+		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
+		return GPLE_OK;
+	}
+
+	int gple_hop_evolve_mash(gple_ctx* ctx, int num_pes, int model, size_t n, double mass, double dt, size_t n_steps, double x_left, double x_right,
+		unsigned flags, double* x, double* p, double* b, int* surface, int* status)
+	{
+		PesModel pes;
+		if (!ctx || !hop_mash_ok(num_pes, flags, x, p, b, surface, status) || !hop_size_ok(ctx, num_pes, model, n, 0, &pes) || !hop_positive(dt) ||
+			!hop_mf_evolve_ok(mass, n_steps, x_left, x_right, flags, x, p, b, status))
+			return GPLE_ERR_BAD_ARG;
+		GPLE_OPEN(ctx);
+		if (n_steps == 0) return GPLE_OK;
+		const bool dev = flags & GPLE_IO_DEVICE;
+		GPLE_CALL(ctx);
+		if (!pes_resolve(ctx, num_pes, model, &pes)) return GPLE_ERR_BAD_ARG; // under the call lock, which gple_pes_undefine takes: the table outlives the enqueue
+		hipStream_t st = ctx->stream;
+		Staged xs(ctx, dev), ps(ctx, dev), bs(ctx, dev);
+		StagedInts su(ctx, dev), ss(ctx, dev);
+		GPLE_HIP(ctx, xs.inout(x, n));
+		GPLE_HIP(ctx, ps.inout(p, n));
+		GPLE_HIP(ctx, bs.inout(b, 2 * n * num_pes));
+		GPLE_HIP(ctx, su.stage(surface, n, true, true));
+		GPLE_HIP(ctx, ss.stage(status, n, true, true));
+		const HopEnsemble e{num_pes, static_cast<long>(n), 0, 0, xs.p, ps.p, bs.p, su.p, ss.p};
+		timer_start(ctx, GPLE_TIMER_HOP_MASH);
+		const hipError_t launched = launch_hop_evolve_mash(st, e, pes, mass, dt, static_cast<long>(n_steps), x_left, x_right);
+		timer_stop(ctx, GPLE_TIMER_HOP_MASH); // on the error path too: no span stays open
+		GPLE_HIP(ctx, launched);
+		for (Staged* o : {&xs, &ps, &bs}) GPLE_HIP(ctx, o->back());
+		for (StagedInts* o : {&su, &ss}) GPLE_HIP(ctx, o->back());
+		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
+		return GPLE_OK;
+	}
+
+	int gple_hop_evolve_groups_mash(gple_ctx* ctx, int num_pes, int model, size_t n_groups, size_t n_per_group, double mass, const double* dt,
+		size_t n_steps, double x_left, double x_right, unsigned flags, double* x, double* p, double* b, int* surface, int* status, int* hops)
+	{
+		PesModel pes;
+		size_t n = 0;
+		if (!ctx || !hop_mash_ok(num_pes, flags, x, p, b, surface, status) || !hop_groups_ok(ctx, num_pes, model, n_groups, n_per_group, 0, &pes, &n) || !dt ||
+			!hop_mf_evolve_ok(mass, n_steps, x_left, x_right, flags, x, p, b, status))
+			return GPLE_ERR_BAD_ARG;
+		for (size_t g = 0; g < n_groups; ++g)
+			if (!hop_positive(dt[g])) return GPLE_ERR_BAD_ARG;
+		GPLE_OPEN(ctx);
+		if (n_steps == 0) return GPLE_OK;
+		const bool dev = flags & GPLE_IO_DEVICE;
+		GPLE_CALL(ctx);
+		if (!pes_resolve(ctx, num_pes, model, &pes)) return GPLE_ERR_BAD_ARG; // under the call lock, which gple_pes_undefine takes: the table outlives the enqueue
+		hipStream_t st = ctx->stream;
+		Staged xs(ctx, dev), ps(ctx, dev), bs(ctx, dev);
+		StagedInts su(ctx, dev), ss(ctx, dev), hs(ctx, dev);
+		Scratch table(ctx);
+		GPLE_HIP(ctx, hop_table(table, dt, n_groups));
+		GPLE_HIP(ctx, xs.inout(x, n));
+		GPLE_HIP(ctx, ps.inout(p, n));
+		GPLE_HIP(ctx, bs.inout(b, 2 * n * num_pes));
+		GPLE_HIP(ctx, su.stage(surface, n, true, true));
+		GPLE_HIP(ctx, ss.stage(status, n, true, true));
+		if (hops) GPLE_HIP(ctx, hs.stage(hops, 2 * n, true, true));
+		const HopEnsemble e{num_pes, static_cast<long>(n), 0, 0, xs.p, ps.p, bs.p, su.p, ss.p};
+		timer_start(ctx, GPLE_TIMER_HOP_MASH);
+		const hipError_t launched =
+			launch_hop_evolve_groups_mash(st, e, pes, static_cast<long>(n_per_group), mass, table.p, static_cast<long>(n_steps), x_left, x_right, hs.p);
+		timer_stop(ctx, GPLE_TIMER_HOP_MASH); // on the error path too: no span stays open
+		GPLE_HIP(ctx, launched);
+		for (Staged* o : {&xs, &ps, &bs}) GPLE_HIP(ctx, o->back());
+		for (StagedInts* o : {&su, &ss, &hs}) GPLE_HIP(ctx, o->back());
+		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
+		return GPLE_OK;
+	}
 }

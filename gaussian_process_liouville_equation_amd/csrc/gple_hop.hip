@@ -51,6 +51,21 @@
 //     square:    1 <= e_k <= 1 + 2 gamma  and  e_j <= 2 gamma  for all j != k
 //     triangle:  e_k >= 1  and  e_k + e_j <= 2  for all j != k
 // else to none.  The plain and the grouped kernels call hop_sample_sqc_one, hop_evolve_sqc_one and hop_observe_sqc_terms per trajectory.
+//
+// MASH trajectories (Mannouch and Richardson, J. Chem. Phys. 158, 104111 (2023); DESIGN.md §17, "MASH trajectories"; numpy restatement:
+// tests/hop_mash_numpy.py), two levels only: the layout of fewest switches (x, p, b, surface, status), but the active surface is a function of
+// the amplitudes, side(c) = 1 if |c_1|^2 > |c_0|^2 else 0 with c = C^T b, and the step draws no random number.  The sample draws x and p by the
+// lines of hop_sample_one (counter (index, 0, 1, 0)) and (w0, w1) = unit53 of the words (0, 1) and (2, 3) of the counter (index, 0, 3, 0):
+//     s = sqrt(1 - w0)  (density 2 s on (0, 1]: the weight 2 |S_z| drawn, so that populations are counts of the active surface)
+//     a = surface0, o = 1 - a:  c_a = sqrt((1 + s) / 2),  c_o = sqrt((1 - s) / 2) (cospi(2 w1) + i sinpi(2 w1)),  b = C(x) c
+// One step of length dt for a running trajectory: steps 1 to 3 of the fewest-switches step, then
+//     4  c = C^T b, side_new = side(c), at one place of the loop and in every pass (s = -1 too); side_old is the pass before's
+//     5  side_new != side_old and side_new != a:  r = p^2 + 2 m (E_a - E_side_new);  r >= 0: p = sgn(p) sqrt(r), a = side_new (a hop);
+//        r < 0: p = -p, a stays (a frustrated hop: always reflected).  A crossing back to side_new == a changes nothing
+//     6  step 7 above
+// side_old of a launch's first step is formed from the stored b and C(x) by the instructions that formed it at the end of the launch before:
+// evolve_mash(a) then evolve_mash(b) = evolve_mash(a + b), bit for bit.  The plain and the grouped kernels call hop_sample_mash_one and
+// hop_evolve_mash_one per trajectory; the sums are hop_observe_kernel's.
 #include "gple_kernels.h"
 #include "gple_pes_n.h"
 #include "gple_philox.h"
@@ -906,8 +921,214 @@ namespace gple
 				}
 		}
 
+		// ---- MASH trajectories: the sample and the step stated at the head of this file -----------------------------------------------------------
+		// side(c): the adiabatic state with the larger population, 1 if |c_1|^2 > |c_0|^2 else 0 (the sign of the mapping spin's S_z)
+		__device__ __forceinline__ int mash_side(const double (&cre)[2], const double (&cim)[2])
+		{
+			return cre[1] * cre[1] + cim[1] * cim[1] > cre[0] * cre[0] + cim[0] * cim[0] ? 1 : 0;
+		}
+		// One trajectory of the sample.  x and p by hop_sample_one's lines (the same bits); then s = |S_z| with the density 2 s and the angle of
+		// the other amplitude from the counter (index, 0, 3, 0)
+		template <int NP, typename M, bool ZERO>
+		__device__ __forceinline__ void hop_sample_mash_one(const HopEnsemble& e, const M& model, long i, double x0, double p0, double sigma_x, double sigma_p, int surface0)
+		{
+			static_assert(NP == 2, "MASH is a two-level method");
+			const unsigned long long index = e.offset + static_cast<unsigned long long>(i);
+			const unsigned key0 = static_cast<unsigned>(e.seed), key1 = static_cast<unsigned>(e.seed >> 32);
+			unsigned c[4] = {static_cast<unsigned>(index), 0u, 1u, 0u};
+			philox4x32(c, key0, key1);
+			const double u0 = unit53(c[0], c[1]), u1 = unit53(c[2], c[3]);
+			const double rho = sqrt(-2.0 * log(1.0 - u0));
+			double sn, cs;
+			sincospi(2.0 * u1, &sn, &cs);
+			double x = x0 + sigma_x * rho * cs, p = p0 + sigma_p * rho * sn;
+			if constexpr (ZERO) x = sigma_x == 0.0 ? x0 : x, p = sigma_p == 0.0 ? p0 : p;
+			double E[NP];
+			Mat<NP> C, Fd;
+			adiabatic_states_n<NP>(x, model, E, C, Fd);
+			unsigned w[4] = {static_cast<unsigned>(index), 0u, 3u, 0u};
+			philox4x32(w, key0, key1);
+			const double w0 = unit53(w[0], w[1]), w1 = unit53(w[2], w[3]);
+			const double s = sqrt(1.0 - w0), active = sqrt((1.0 + s) / 2.0), other = sqrt((1.0 - s) / 2.0);
+			sincospi(2.0 * w1, &sn, &cs);
+			double cre[NP], cim[NP];
+#pragma unroll
+			for (int k = 0; k < NP; ++k) cre[k] = k == surface0 ? active : other * cs, cim[k] = k == surface0 ? 0.0 : other * sn;
+			e.x[i] = x, e.p[i] = p, e.surface[i] = surface0, e.status[i] = 0;
+			double* b = e.b + 2 * NP * i;
+#pragma unroll
+			for (int r = 0; r < NP; ++r)
+			{
+				double re = 0.0, im = 0.0;
+#pragma unroll
+				for (int k = 0; k < NP; ++k) re += C.a[r][k] * cre[k], im += C.a[r][k] * cim[k];
+				b[2 * r] = re, b[2 * r + 1] = im;
+			}
+		}
+		template <int NP, typename M>
+		__global__ void __launch_bounds__(HOP_BLOCK) hop_sample_mash_kernel(HopEnsemble e, M model, double x0, double p0, double sigma_x, double sigma_p, int surface0)
+		{
+			const long i = static_cast<long>(blockIdx.x) * HOP_BLOCK + threadIdx.x;
+			if (i >= e.n) return;
+			hop_sample_mash_one<NP, M, false>(e, model, i, x0, p0, sigma_x, sigma_p, surface0);
+		}
+		template <int NP, typename M>
+		__global__ void __launch_bounds__(HOP_BLOCK) hop_sample_groups_mash_kernel(HopEnsemble e, M model, long n_per_group, const double* __restrict__ packets, int surface0)
+		{
+			const long i = static_cast<long>(blockIdx.x) * HOP_BLOCK + threadIdx.x;
+			if (i >= e.n) return;
+			const double* const row = packets + 4 * (i / n_per_group);
+			hop_sample_mash_one<NP, M, true>(e, model, i, row[0], row[1], row[2], row[3], surface0);
+		}
+
+		// All the steps of a launch for the running trajectory i.  Steps 1 to 3 and 7 are hop_evolve_one's, line for line: a copy, so that the
+		// kernels above keep the code they had.  COUNT (the grouped call): the two outcomes of a crossing are counted in registers and added to
+		// hops[2 i], hops[2 i + 1] at the end, where hops is not null
+		template <int NP, typename M, bool COUNT>
+		__device__ __forceinline__ void hop_evolve_mash_one(const HopEnsemble& e, const M& model, long i, double mass, double dt, long n_steps, double x_left, double x_right,
+			int* hops)
+		{
+			static_assert(NP == 2, "MASH is a two-level method");
+			double x = e.x[i], p = e.p[i], bre[NP], bim[NP];
+			int taken = 0, frustrated = 0;
+			int a = e.surface[i], status = 0, side = 0;
+			double* const b = e.b + 2 * NP * i;
+#pragma unroll
+			for (int k = 0; k < NP; ++k) bre[k] = b[2 * k], bim[k] = b[2 * k + 1];
+			Mat<NP> Vx; // V(x), the diagonal of F(x) and side(c): set by the pass s = -1, which only forms the states and the side at the start point
+			double Fx[NP];
+			for (long s = -1; s < n_steps && status == 0; ++s)
+			{
+				double xn = x;
+				if (s >= 0)
+				{
+					p += pick<NP>(Fx, a) * dt / 2.0;
+					xn = x + p / mass * dt;
+				}
+				HopStates<NP> st;
+				hop_states<NP>(xn, model, st);
+				if (s >= 0)
+				{
+					// 2: the amplitudes through the mid-point matrix, U = W exp(-i lambda dt / hbar) W^T entry by entry
+					Mat<NP> Vm, W;
+					double lam[NP], cs[NP], sn[NP];
+#pragma unroll
+					for (int r = 0; r < NP; ++r)
+#pragma unroll
+						for (int q = 0; q < NP; ++q) Vm.a[r][q] = 0.5 * (Vx.a[r][q] + st.V.a[r][q]);
+					jacobi_eig<NP>(Vm, lam, W);
+#pragma unroll
+					for (int k = 0; k < NP; ++k) sincos(lam[k] * dt / HBAR_HOP, &sn[k], &cs[k]);
+					double nre[NP], nim[NP];
+#pragma unroll
+					for (int r = 0; r < NP; ++r)
+					{
+						double re = 0.0, im = 0.0;
+#pragma unroll
+						for (int q = 0; q < NP; ++q)
+						{
+							double ure = 0.0, uim = 0.0;
+#pragma unroll
+							for (int k = 0; k < NP; ++k)
+							{
+								const double ww = W.a[r][k] * W.a[q][k];
+								ure += ww * cs[k], uim -= ww * sn[k];
+							}
+							re += ure * bre[q] - uim * bim[q], im += ure * bim[q] + uim * bre[q];
+						}
+						nre[r] = re, nim[r] = im;
+					}
+#pragma unroll
+					for (int r = 0; r < NP; ++r) bre[r] = nre[r], bim[r] = nim[r];
+					// 3
+					double Fdiag[NP];
+#pragma unroll
+					for (int k = 0; k < NP; ++k) Fdiag[k] = st.F.a[k][k];
+					p += pick<NP>(Fdiag, a) * dt / 2.0;
+					x = xn;
+				}
+				// the side of the amplitudes at this point, in every pass: the start of a launch forms it as the end of the launch before did
+				double cre[NP], cim[NP];
+				adiabatic_amplitudes<NP>(st.C, bre, bim, cre, cim);
+				const int side_new = mash_side(cre, cim);
+				if (s >= 0)
+				{
+					// the crossing: the amplitudes changed side, away from the active surface
+					if (side_new != side && side_new != a)
+					{
+						const double r = p * p + 2.0 * mass * (pick<NP>(st.E, a) - pick<NP>(st.E, side_new));
+						if (r >= 0.0) p = sgn_n(p) * sqrt(r), a = side_new;
+						else p = -p;
+						if constexpr (COUNT) taken += r >= 0.0 ? 1 : 0, frustrated += r >= 0.0 ? 0 : 1;
+					}
+					// 7
+					if (x < x_left) status = 1;
+					else if (x > x_right) status = 2;
+				}
+				side = side_new;
+				Vx = st.V;
+#pragma unroll
+				for (int k = 0; k < NP; ++k) Fx[k] = st.F.a[k][k];
+			}
+			e.x[i] = x, e.p[i] = p, e.surface[i] = a, e.status[i] = status;
+#pragma unroll
+			for (int k = 0; k < NP; ++k) b[2 * k] = bre[k], b[2 * k + 1] = bim[k];
+			if constexpr (COUNT)
+				if (hops) hops[2 * i] += taken, hops[2 * i + 1] += frustrated;
+		}
+		template <int NP, typename M>
+		__global__ void __launch_bounds__(HOP_BLOCK) hop_evolve_mash_kernel(HopEnsemble e, M model, double mass, double dt, long n_steps, double x_left, double x_right)
+		{
+			const long i = static_cast<long>(blockIdx.x) * HOP_BLOCK + threadIdx.x;
+			if (i >= e.n || e.status[i] != 0) return;
+			hop_evolve_mash_one<NP, M, false>(e, model, i, mass, dt, n_steps, x_left, x_right, nullptr);
+		}
+		template <int NP, typename M>
+		__global__ void __launch_bounds__(HOP_BLOCK) hop_evolve_groups_mash_kernel(HopEnsemble e, M model, long n_per_group, double mass, const double* __restrict__ dt,
+			long n_steps, double x_left, double x_right, int* hops)
+		{
+			const long i = static_cast<long>(blockIdx.x) * HOP_BLOCK + threadIdx.x;
+			if (i >= e.n || e.status[i] != 0) return;
+			hop_evolve_mash_one<NP, M, true>(e, model, i, mass, dt[i / n_per_group], n_steps, x_left, x_right, hops);
+		}
+
 		inline unsigned hop_blocks(long n) { return static_cast<unsigned>((n + HOP_BLOCK - 1) / HOP_BLOCK); }
 	} // namespace
+
+	hipError_t launch_hop_sample_mash(hipStream_t s, const HopEnsemble& e, PesModel model, double x0, double p0, double sigma_x, double sigma_p, int surface0)
+	{
+		if (e.num_pes != 2) return hipErrorInvalidValue;
+		if (e.n <= 0) return hipSuccess;
+		const dim3 grid(hop_blocks(e.n)), block(HOP_BLOCK);
+		with_model(model, [&](auto m) { hipLaunchKernelGGL((hop_sample_mash_kernel<2, decltype(m)>), grid, block, 0, s, e, m, x0, p0, sigma_x, sigma_p, surface0); });
+		return hipGetLastError();
+	}
+	hipError_t launch_hop_sample_groups_mash(hipStream_t s, const HopEnsemble& e, PesModel model, long n_per_group, const double* packets, int surface0)
+	{
+		if (e.num_pes != 2 || e.n <= 0 || n_per_group <= 0) return hipErrorInvalidValue;
+		const dim3 grid(hop_blocks(e.n)), block(HOP_BLOCK);
+		with_model(model, [&](auto m) { hipLaunchKernelGGL((hop_sample_groups_mash_kernel<2, decltype(m)>), grid, block, 0, s, e, m, n_per_group, packets, surface0); });
+		return hipGetLastError();
+	}
+	hipError_t launch_hop_evolve_mash(hipStream_t s, const HopEnsemble& e, PesModel model, double mass, double dt, long n_steps, double x_left, double x_right)
+	{
+		if (e.num_pes != 2) return hipErrorInvalidValue;
+		if (e.n <= 0 || n_steps <= 0) return hipSuccess;
+		const dim3 grid(hop_blocks(e.n)), block(HOP_BLOCK);
+		with_model(model, [&](auto m) { hipLaunchKernelGGL((hop_evolve_mash_kernel<2, decltype(m)>), grid, block, 0, s, e, m, mass, dt, n_steps, x_left, x_right); });
+		return hipGetLastError();
+	}
+	hipError_t launch_hop_evolve_groups_mash(hipStream_t s, const HopEnsemble& e, PesModel model, long n_per_group, double mass, const double* dt, long n_steps,
+		double x_left, double x_right, int* hops)
+	{
+		if (e.num_pes != 2 || e.n <= 0 || n_per_group <= 0) return hipErrorInvalidValue;
+		if (n_steps <= 0) return hipSuccess;
+		const dim3 grid(hop_blocks(e.n)), block(HOP_BLOCK);
+		with_model(model, [&](auto m) {
+			hipLaunchKernelGGL((hop_evolve_groups_mash_kernel<2, decltype(m)>), grid, block, 0, s, e, m, n_per_group, mass, dt, n_steps, x_left, x_right, hops);
+		});
+		return hipGetLastError();
+	}
 
 	hipError_t launch_hop_sample(hipStream_t s, const HopEnsemble& e, PesModel model, double x0, double p0, double sigma_x, double sigma_p, int surface0)
 	{

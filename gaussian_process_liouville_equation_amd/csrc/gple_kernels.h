@@ -474,6 +474,14 @@ namespace gple
 	size_t hop_observe_groups_sqc_work_doubles(int num_pes, long n_groups, long n_per_group);
 	hipError_t launch_hop_observe_groups_sqc(hipStream_t s, const HopEnsemble& e, PesModel model, long n_groups, long n_per_group, double mass, int window, double gamma,
 		double* work, double* out);
+	// MASH trajectories ("MASH trajectories"): two levels only (any other num_pes is hipErrorInvalidValue).  The ensemble is the
+	// five arrays of launch_hop_sample; the samples draw the amplitudes of their own, the step has no seed, no step counter and no offset, and
+	// counts hops taken and frustrated into hops (nullable) as launch_hop_evolve_groups does.  The sums are launch_hop_observe's
+	hipError_t launch_hop_sample_mash(hipStream_t s, const HopEnsemble& e, PesModel model, double x0, double p0, double sigma_x, double sigma_p, int surface0);
+	hipError_t launch_hop_sample_groups_mash(hipStream_t s, const HopEnsemble& e, PesModel model, long n_per_group, const double* packets, int surface0);
+	hipError_t launch_hop_evolve_mash(hipStream_t s, const HopEnsemble& e, PesModel model, double mass, double dt, long n_steps, double x_left, double x_right);
+	hipError_t launch_hop_evolve_groups_mash(hipStream_t s, const HopEnsemble& e, PesModel model, long n_per_group, double mass, const double* dt, long n_steps,
+		double x_left, double x_right, int* hops);
 	// the uniform grid of gple_hop_bin: a point belongs to its nearest grid point, floor((x - x_first) / dx + 0.5) and the same for p
 	struct HopGrid
 	{

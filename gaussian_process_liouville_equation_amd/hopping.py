@@ -18,6 +18,9 @@ method = "sqc" with window = "triangle" (the default) or "square" and gamma (Non
 Meyer-Miller-Stock-Thoss mapping Hamiltonian run classically from a sample of actions and angles, populations read off by binning the final
 actions into the symmetrical windows of Cotton and Miller (gple_hop_sample_sqc / _evolve_sqc / _observe_sqc and their _groups forms; DESIGN.md
 §17, "Symmetrical quasi-classical trajectories"), with unpack_sqc() for its sums.  window or gamma with another method is a ValueError.
+method = "mash" is the fourth: the mapping approach to surface hopping of Mannouch and Richardson (gple_hop_sample_mash / _evolve_mash and their
+_groups forms; DESIGN.md §17, "MASH trajectories"), two levels only.  It has an active surface, which follows the amplitudes deterministically, so
+the sums, the records and every file are those of "fssh" (gple_hop_observe, unpack(), averages_line, scan_line); all randomness is in its sample.
 """
 import os
 import time
@@ -69,14 +72,24 @@ def averages_line_mf(t, rec):
 SQC = "sqc"  # the third method: its ensemble comes from a sample of its own (hop_sample_sqc), METHODS are the two that share hop_sample's
 
 
-def _method(method, decoherence, reverse_frustrated, phase_grid=None, window=None, gamma=None):
-    """method of run() and scan(), checked against the options that need an active surface -> True for the mean-field one, SQC for "sqc" """
-    if method not in METHODS + (SQC,):
-        raise ValueError(f"method is one of {METHODS + (SQC,)}")
+MASH = "mash"  # the fourth method: a sample and a step of its own, the sums of "fssh"
+
+
+def _method(method, decoherence, reverse_frustrated, phase_grid=None, window=None, gamma=None, num_pes=2):
+    """method of run() and scan(), checked against the options that need an active surface -> True for the mean-field one, SQC for "sqc", MASH
+    for "mash" """
+    if method not in METHODS + (SQC, MASH):
+        raise ValueError(f"method is one of {METHODS + (SQC, MASH)}")
     if method != SQC and (window is not None or gamma is not None):
         raise ValueError('window and gamma belong to method="sqc"')
     if method == "fssh":
         return False
+    if method == MASH:
+        if decoherence is not None or reverse_frustrated or phase_grid is not None:
+            raise ValueError("mash trajectories need no decoherence correction, always reflect a frustrated hop and (DESIGN.md §17) have no phase_grid")
+        if int(num_pes) != 2:
+            raise ValueError("mash is a two-level method: num_pes = 2")
+        return MASH
     if decoherence is not None or reverse_frustrated or phase_grid is not None:
         raise ValueError(f"{method} trajectories have no active surface: no decoherence correction, no frustrated hops and (DESIGN.md §17) no phase_grid")
     return True if method == "ehrenfest" else SQC
@@ -175,11 +188,16 @@ def run(api, model=DAC, num_pes=2, ln_energy=0.0, n_traj=10000, seed=0, out_dir=
     in the same columns.  decoherence, reverse_frustrated=True or a phase_grid with "ehrenfest" is a ValueError.
     method "sqc" with window ("triangle", the default, or "square") and gamma (None: the window's customary value): _run_sqc below; the same
     options are a ValueError with it, and so are window or gamma with another method.
+    method "mash": everything of "fssh" (records, files, the scattering line) with hop_sample_mash for the sample and one hop_evolve_mash per
+    output time, which takes no seed and no step number.  decoherence, reverse_frustrated=True, a phase_grid, window, gamma or num_pes != 2 with
+    it is a ValueError.
     Returns the setup, the records (t and unpack() per output time), stop, and scattering_line: the head of exact.run's final line, the
     fractions that left [left | right][surface], and the fraction still running."""
-    mean_field = _method(method, decoherence, reverse_frustrated, phase_grid, window, gamma)
+    mean_field = _method(method, decoherence, reverse_frustrated, phase_grid, window, gamma, num_pes)
     if mean_field == SQC:
         return _run_sqc(api, model, num_pes, ln_energy, n_traj, seed, out_dir, dt, surface0, max_outputs, log, window, gamma, setup_kw)
+    mash = mean_field == MASH  # the loop of "fssh" with the sample and the step of its own
+    mean_field = mean_field is True
     setup_kw["boundary"] = exact.ABSORBING
     s = exact.setup(ln_energy, **setup_kw)
     num_pes, n_traj = int(num_pes), int(n_traj)
@@ -190,7 +208,8 @@ def run(api, model=DAC, num_pes=2, ln_energy=0.0, n_traj=10000, seed=0, out_dir=
     correction = {} if decoherence is None else dict(decoherence=decoherence, edc_c=edc_c)
     say = log or (lambda *_: None)
     t0 = time.perf_counter()
-    state = api.hop_sample(num_pes, model, n_traj, seed, s["x0"], s["p0"], s["sigma_x"], s["sigma_p"], surface0, device_out=True)
+    sample = api.hop_sample_mash if mash else api.hop_sample
+    state = sample(num_pes, model, n_traj, seed, s["x0"], s["p0"], s["sigma_x"], s["sigma_p"], surface0, device_out=True)
     grid = None if phase_grid is None else phase_grid_of(api, num_pes, model, s, phase_grid)
     files = {}
     if out_dir is not None:
@@ -230,6 +249,8 @@ def run(api, model=DAC, num_pes=2, ln_energy=0.0, n_traj=10000, seed=0, out_dir=
                 break
             if mean_field:
                 state = api.hop_evolve_mf(num_pes, model, state, s["mass"], dt, output_step, s["xmin"], s["xmax"])
+            elif mash:
+                state = api.hop_evolve_mash(num_pes, model, state, s["mass"], dt, output_step, s["xmin"], s["xmax"])
             else:
                 state = api.hop_evolve(num_pes, model, state, seed, s["mass"], dt, step, output_step, s["xmin"], s["xmax"], reverse=reverse_frustrated,
                                        **correction)
@@ -288,10 +309,13 @@ def scan(api, model=DAC, num_pes=2, ln_energies=None, momenta=None, n_per_group=
     hops and frustrated are 0 (hop_counts is None), energy_drift comes from the mean-field energy p^2 / 2m + sum_k |c_k|^2 E_k.  stderr is then
     an UPPER BOUND: a fraction f is the mean of weights in [0, 1], whose variance is at most f (1 - f).  With fixed=True every trajectory of a
     group is the same trajectory (nothing is random), so n_per_group = 1 is enough.  decoherence or reverse_frustrated=True with "ehrenfest" is
-    a ValueError.  method "sqc" with window and gamma as run(): _scan_sqc below, on the groups made here."""
-    mean_field = _method(method, decoherence, reverse_frustrated, None, window, gamma)
+    a ValueError.  method "sqc" with window and gamma as run(): _scan_sqc below, on the groups made here.  method "mash": everything of "fssh"
+    (scan.txt, the counters of hops taken and frustrated) on hop_sample_groups_mash and hop_evolve_groups_mash; the options run() refuses with it
+    are a ValueError here too."""
+    mean_field = _method(method, decoherence, reverse_frustrated, None, window, gamma, num_pes)
     if mean_field == SQC:
         window, gamma = sqc_window(window, gamma)
+    mash = mean_field == MASH  # the loop of "fssh" with the sample and the step of its own
     if (ln_energies is None) == (momenta is None):
         raise ValueError("give ln_energies or momenta, one of them")
     given = np.atleast_1d(np.asarray(ln_energies if momenta is None else momenta, dtype=np.float64))
@@ -316,8 +340,9 @@ def scan(api, model=DAC, num_pes=2, ln_energies=None, momenta=None, n_per_group=
     say = log or (lambda *_: None)
     if mean_field == SQC:
         return _scan_sqc(api, model, num_pes, n_per_group, seed, surface0, chunk_steps, max_steps, out_dir, say, window, gamma, setups, dts, total_step, packets)
+    mean_field = mean_field is True
     t0 = time.perf_counter()
-    state = api.hop_sample_groups(num_pes, model, n_per_group, seed, packets, surface0, device_out=True)
+    state = (api.hop_sample_groups_mash if mash else api.hop_sample_groups)(num_pes, model, n_per_group, seed, packets, surface0, device_out=True)
     on_device = hasattr(state[0], "is_cuda")
     if mean_field:
         counts = None
@@ -339,6 +364,8 @@ def scan(api, model=DAC, num_pes=2, ln_energies=None, momenta=None, n_per_group=
         n_steps = min(chunk_steps, max_steps - step)
         if mean_field:
             state = api.hop_evolve_groups_mf(num_pes, model, state, n_per_group, s0["mass"], dts, n_steps, s0["xmin"], s0["xmax"])
+        elif mash:
+            state, counts = api.hop_evolve_groups_mash(num_pes, model, state, n_per_group, s0["mass"], dts, n_steps, s0["xmin"], s0["xmax"], hops=counts)
         else:
             state, counts = api.hop_evolve_groups(num_pes, model, state, n_per_group, seed, s0["mass"], dts, step, n_steps, s0["xmin"], s0["xmax"],
                                                   reverse=reverse_frustrated, hops=counts, **correction)

@@ -161,7 +161,8 @@ typedef enum gple_timer {
 	GPLE_TIMER_HOP_BIN = 13,       /* the bin kernel of one gple_hop_bin call (no staging, no clear); count = calls */
 	GPLE_TIMER_HOP_GROUPS = 14,    /* the step kernel of one gple_hop_evolve_groups or _groups_dc call (all its steps, no staging); count = calls */
 	GPLE_TIMER_HOP_MF = 15,        /* the step kernel of one gple_hop_evolve_mf or gple_hop_evolve_groups_mf call (all its steps, no staging); count = calls */
-	GPLE_TIMER_HOP_SQC = 16        /* the step kernel of one gple_hop_evolve_sqc or gple_hop_evolve_groups_sqc call (all its steps, no staging); count = calls */
+	GPLE_TIMER_HOP_SQC = 16,       /* the step kernel of one gple_hop_evolve_sqc or gple_hop_evolve_groups_sqc call (all its steps, no staging); count = calls */
+	GPLE_TIMER_HOP_MASH = 17       /* the step kernel of one gple_hop_evolve_mash or gple_hop_evolve_groups_mash call (all its steps, no staging); count = calls */
 } gple_timer;
 int gple_ctx_enable_timing(gple_ctx* ctx, int on);
 /* Synchronises the stream, then: last = milliseconds of the most recent interval; total / count = accumulated since
@@ -393,7 +394,7 @@ int gple_pes_adiabatic_n(gple_ctx* ctx, int num_pes, int model, const double* x,
  * V = V_0 + V'_0 (x - x_first), V' = V'_0, and for s > n - 1 the same from the last node.  With nodes taken from a smooth function the error is
  * at most dx^4 / 384 max|V''''| for the value and sqrt(3) / 216 dx^3 max|V''''| for the derivative.
  * A user id is accepted, on the context it was defined on and with the num_pes it was defined with (GPLE_ERR_BAD_ARG otherwise), by
- * gple_pes_adiabatic_n, gple_pes_diabatic_n, gple_evolve_n, gple_dvr_hamiltonian, gple_mqcl_transform / _evolve / _observe, gple_hop_sample / _evolve / _observe / _bin (and the _groups, _dc, _mf and _sqc forms),
+ * gple_pes_adiabatic_n, gple_pes_diabatic_n, gple_evolve_n, gple_dvr_hamiltonian, gple_mqcl_transform / _evolve / _observe, gple_hop_sample / _evolve / _observe / _bin (and the _groups, _dc, _mf, _sqc and _mash forms),
  * gple_grid_survey and gple_grid_reconstruct / _cross.  The two-level entry points gple_pes_adiabatic and gple_evolve keep refusing it: they use the reference's closed
  * forms and operation order, of which a table has none; gple_evolve_n at num_pes = 2 reproduces gple_evolve to rounding and takes their place.
  * Where two surfaces of a user model touch (E_j = E_k) with F_jk != 0 the non-adiabatic coupling is infinite, as its formula says: not guarded.
@@ -724,6 +725,42 @@ int gple_hop_observe_sqc(gple_ctx* ctx, int num_pes, int model, size_t n, double
 	const double* p, const double* b, const int* status, double* out);
 int gple_hop_observe_groups_sqc(gple_ctx* ctx, int num_pes, int model, size_t n_groups, size_t n_per_group, double mass, int window, double gamma,
 	unsigned flags, const double* x, const double* p, const double* b, const int* status, double* out);
+/* MASH trajectories, the mapping approach to surface hopping (Mannouch and Richardson, J. Chem. Phys. 158, 104111 (2023); DESIGN.md §17, "MASH
+ * trajectories"): a two-level method, num_pes = 2 only.  A trajectory is x, p, the diabatic amplitudes b, its active surface and its status: the
+ * five arrays and the layout of gple_hop_sample, so gple_hop_observe and gple_hop_observe_groups serve it unchanged.  The active surface is a
+ * deterministic function of the amplitudes; with c = C^T b at the trajectory's x (formed as gple_hop_observe forms it)
+ *     side(c) = 1 if |c_1|^2 > |c_0|^2 else 0,  |c_k|^2 = re re + im im      (the sign of the mapping spin's S_z).
+ * The step draws no random number: all randomness sits in the sampled amplitudes.
+ * gple_hop_sample_mash (Philox4x32-10, key (seed low, seed high), index = trajectory_offset + i): x and p from the counter (index, 0, 1, 0) by
+ * the lines of gple_hop_sample: the same bits for the same index, seed and packet, the sigma == 0 select of the grouped form included.  A second
+ * counter (index, 0, 3, 0) gives w0 = unit53 of the words (0, 1) and w1 = unit53 of the words (2, 3);  s = sqrt(1 - w0), in (0, 1] with the
+ * density 2 s: the weight 2 |S_z| of the population-population correlation function, drawn instead of carried, so that populations are plain
+ * counts of the active surface.  With a = surface0 and o = 1 - a:
+ *     c_a = sqrt((1 + s) / 2) (real),  c_o = sqrt((1 - s) / 2) (cospi(2 w1) + i sinpi(2 w1)),  b = C(x) c,  surface = surface0,  status = 0.
+ * gple_hop_sample_groups_mash: the packets table of gple_hop_sample_groups.
+ * gple_hop_evolve_mash, one step of length dt for a running trajectory (a the active surface):
+ *     1 - 3  steps 1 to 3 of gple_hop_evolve: the half kick on F_aa, the drift, the amplitudes through the mid-point matrix, the states at
+ *            x_new, the second half kick
+ *     4  c = C^T b, side_new = side(c): formed at one place, at the start point of a call too; side_old is what the step before formed
+ *     5  side_new != side_old and side_new != a:  r = p^2 + 2 mass (E_a - E_side_new);
+ *        r >= 0: p = sgn(p) sqrt(r), a = side_new (a hop);  r < 0: p = -p, a stays (a frustrated hop; MASH always reflects, there is no flag).
+ *        A crossing back to side_new == a (what follows a reflection) changes nothing
+ *     6  x < x_left: status 1, x > x_right: status 2; a finished trajectory is never touched again
+ * side_old at the start of a call is recomputed from the stored b and C(x): a call carries nothing hidden, evolve_mash(a) then evolve_mash(b)
+ * gives the bits of evolve_mash(a + b).  There is no seed, no first_step and no trajectory_offset.  n_steps <= 2^40 (0: nothing happens).
+ * gple_hop_evolve_groups_mash: dt[group], group = i / n_per_group; a group's state has the bits of gple_hop_evolve_mash on that slice.  hops
+ * (nullable; 2 n ints where the ensemble lives): the hops taken and the frustrated hops of trajectory i during the call are ADDED to
+ * hops[2 i] and hops[2 i + 1].  Timer of both evolve calls: GPLE_TIMER_HOP_MASH.  Arrays, GPLE_IO_DEVICE and the tables as the calls above.
+ * GPLE_ERR_BAD_ARG, with nothing written: everything gple_hop_sample (_groups), gple_hop_evolve_mf (_groups_mf) refuse, a null surface,
+ * num_pes != 2, and the flag GPLE_HOP_REVERSE. */
+int gple_hop_sample_mash(gple_ctx* ctx, int num_pes, int model, size_t n, size_t trajectory_offset, unsigned long long seed, double x0, double p0,
+	double sigma_x, double sigma_p, int surface0, unsigned flags, double* x, double* p, double* b, int* surface, int* status);
+int gple_hop_sample_groups_mash(gple_ctx* ctx, int num_pes, int model, size_t n_groups, size_t n_per_group, size_t trajectory_offset,
+	unsigned long long seed, const double* packets, int surface0, unsigned flags, double* x, double* p, double* b, int* surface, int* status);
+int gple_hop_evolve_mash(gple_ctx* ctx, int num_pes, int model, size_t n, double mass, double dt, size_t n_steps, double x_left, double x_right,
+	unsigned flags, double* x, double* p, double* b, int* surface, int* status);
+int gple_hop_evolve_groups_mash(gple_ctx* ctx, int num_pes, int model, size_t n_groups, size_t n_per_group, double mass, const double* dt,
+	size_t n_steps, double x_left, double x_right, unsigned flags, double* x, double* p, double* b, int* surface, int* status, int* hops);
 
 /* generate_markov_chain (mc.cpp:118-165) for n walkers at once on the fitted distribution |cut-off prediction| of `element`:
  * num_steps Metropolis steps with uniform displacements in [-max_displacement, max_displacement) per dimension; r (2n) holds
