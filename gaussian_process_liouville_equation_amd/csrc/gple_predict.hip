@@ -20,6 +20,9 @@
 // with the same blocking: rownorm2_kernel (round 2: 4 x 4 / 2 x 8 fragments per wave, slabs by LDS-DMA; gple_debug_predict_knobs pipe = 0),
 // rownormp_kernel (round 4, the default: the k-steps of a unit as one pipeline pinned around the barrier), rownorm3_kernel (n <= 512 with few
 // row blocks) and predict_fused256_kernel (round 4: the whole predict of a real fit with N <= 256 in one launch, K* generated inside).
+// rownormp_kernel alone walks the second half of every diagonal 256-block in four DOUBLE steps (32 k-rows per barrier, the second step's live half
+// of the T slab folded into the zero half of the stage) and keeps the stage of every step and the slab pointers free of per-step address
+// arithmetic: in the whole steps every scalar instruction shows in the step time (profiles/diag_steps.md).
 // A workgroup = 8 waves owns 128 test rows and loops over 256-wide N-tiles of T.  The all-zero blocks of T (k > n) are skipped with
 // compile-time block ranges because any branch that merges around the accumulators makes hipcc spill hundreds of VGPRs.  The result rows
 // sit on n and the result columns (lane & 15) on the test row m, so the squared row sums stay lane-local.
@@ -456,17 +459,40 @@ namespace gple
 		// block at n = 4096, 4 of 160 steps' worth at n = 1024); only a unit does.  The tiles of the unit are listed in LDS in the order
 		// (virtual group, tile) they had before; per accumulator the same MFMAs in the same order, the same sums behind them: same bits as
 		// rownorm2_kernel (test_rownorm_variants_agree_bit_for_bit).
+		//
+		// The second half of a diagonal 256-block runs in DOUBLE steps.  Step D of the block (k = n0 + 16 D ...) has only the column blocks jb >= D
+		// live, so a SIMD's MFMA time falls from 4096 cycles at D = 8 to 512 at D = 15 while every step still pays its DMA issues, its scalar stretch,
+		// the wait for a slab requested only one step earlier and the barrier.  From D = 8 on only the columns 128 ... 255 of the T slab are live:
+		// the steps (8, 9), (10, 11), (12, 13), (14, 15) are four steps of 32 k-rows each, with one wait and one barrier per pair.  The B stage keeps
+		// its 16 rows: the live half of step D sits in the columns 128 ... 255 of the stage rows as always, the live half of step D + 1 in the columns
+		// 0 ... 127 that held zeros (the waves with (w & 1) == 0 fetch it in place of the zeros: still 4 B issues per wave); an A stage has 16 more
+		// rows behind the B stages (4 A issues per wave in a double step, 2 elsewhere; the rows of the single steps stay where they were — with all
+		// 32 rows of a stage in one piece the whole steps ran 0.4 % slower, same box).  Per accumulator the MFMAs keep their order — the four groups
+		// of D, then those of D + 1, each with its own compile-time live range — and in the diagonal steps only live fragments are read from LDS.
+		// What a double step cannot hide: the step (14, 15) has 2048 cycles of MFMAs on its busiest SIMD and waits ~3900 for the next tile's first
+		// slab, which can only be requested once the step (12, 13) has left its stage (measured: profiles/diag_steps.md).
+		// The whole steps carry no address arithmetic: a tile has an even number of steps, so the stage of every step is a compile-time constant
+		// (the loop over the whole steps is unrolled by two), the slab pointers move by two 64-bit additions, and the hand-over to the next tile
+		// of the list is compiled into the one step per tile that requests the tile's last slab.  Against per-step stage offsets, a k-row counter
+		// multiplied out and the hand-over test in every step: 0.925 -> 0.957 of the peak at C4r, five same-box pairs (profiles/diag_steps_ab.md).
 		constexpr int TL_MAX = 256; // N-tiles of a factor (n <= 65536)
+		// the first live fragment of column group wni in step D of the diagonal block: jb = wni + wn t >= D  <=>  t >= ceil((D - wni) / wn); 16 / wn: none
+		constexpr int diag_tmin(int D, int wni, int wn) { return D > wni ? (D - wni + wn - 1) / wn : 0; }
+		// the 12 steps of a diagonal block: e < 8 is the single step D = e, e >= 8 the double step (D, D + 1) with D = 2 e - 8
+		constexpr int diag_first(int e) { return e < 8 ? e : 2 * e - 8; }
 		template <int AF, int BF, int WNI>
 		__device__ __forceinline__ void rownormp_unit(const double* __restrict__ Ks, int rows, const double* __restrict__ T, long ldt, double* lds,
 			const int* tl, int ntl, double* __restrict__ q, long qstride, int m0, int wm)
 		{
 			constexpr int KB = 16, WN = 16 / BF, ASr = BM + 16;
 			constexpr int ASL = KB * ASr, BSL = KB * BS;
-			static_assert(BM * KB / 2 / NTHREADS == 2 && BN * KB / 2 / NTHREADS == 4, "six DMA instructions per wave and slab");
+			static_assert(BM * KB / 2 / NTHREADS == 2 && BN * KB / 2 / NTHREADS == 4, "per wave 2 (double step: 4) A and 4 B DMA instructions per slab");
+			// two stages of 16 A rows and 16 B rows where the single steps have always had them, and behind them the 16 further A rows per stage
+			// that only a double step fills
 			double* const As = lds;
 			double* const Bs = lds + 2 * ASL;
-			double* const red = Bs + 2 * BSL;
+			double* const Ax = Bs + 2 * BSL;
+			double* const red = Ax + 2 * ASL;
 			const int t = threadIdx.x, lane = t & 63;
 			const int fk = lane >> 4, fr = lane & 15;
 			const int w = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -476,55 +502,80 @@ namespace gple
 			auto dma = [](const double* base, unsigned voff, unsigned ldst, unsigned poff) {
 				asm volatile("s_add_u32 m0, %1, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %3" ::"v"(voff), "s"(ldst), "s"(poff), "s"(base) : "memory", "scc");
 			};
-			// wave w fills k-rows w and w + 8 of the K* slab and, of the T slab, half (w & 1) of the k-rows (w >> 1) + 4 qq
-			unsigned voff[6], ldst[6];
-			voff[0] = 16u * lane, voff[1] = voff[0] + 64u * static_cast<unsigned>(rows);
-			ldst[0] = lds_addr(As) + 8u * static_cast<unsigned>(w * ASr), ldst[1] = ldst[0] + 8u * (8 * ASr);
+			// wave w fills k-rows w + 8 qq of the K* slab (qq < 2; all four in a double step) and, of the T slab, half (w & 1) of the k-rows (w >> 1) + 4 qq
+			unsigned voffA[4], ldstA[4], voffB[4], ldstB[4];
 #pragma unroll
 			for (int qq = 0; qq < 4; ++qq)
 			{
-				voff[2 + qq] = voff[0] + 32u * static_cast<unsigned>(ldt) * qq;
-				ldst[2 + qq] = lds_addr(Bs) + 8u * static_cast<unsigned>(((w >> 1) + 4 * qq) * BS + 128 * (w & 1));
+				voffA[qq] = 16u * lane + 64u * static_cast<unsigned>(rows) * qq;
+				ldstA[qq] = lds_addr(qq < 2 ? As : Ax) + 8u * static_cast<unsigned>((w + 8 * (qq & 1)) * ASr);
+				voffB[qq] = 16u * lane + 32u * static_cast<unsigned>(ldt) * qq;
+				ldstB[qq] = lds_addr(Bs) + 8u * static_cast<unsigned>(((w >> 1) + 4 * qq) * BS + 128 * (w & 1));
 			}
 			const double* const KsW = Ks + m0 + static_cast<long>(w) * rows;
 			const double* const TW = T + 128 * (w & 1) + static_cast<long>(w >> 1) * ldt;
-			auto entry = [&](int i) { return __builtin_amdgcn_readfirstlane(tl[i]); };
+			// the B slab of a double step: the waves of the left half fetch the columns 128 ... 255 of the SECOND step's 16 k-rows (the left half is zero in both)
+			const long fold = (w & 1) ? 0 : 128 + static_cast<long>(KB) * ldt;
 			auto tile_n0 = [&](int i) { return __builtin_amdgcn_readfirstlane(tl[i]) & 0xffff; };
 			auto tile_vg = [&](int i) { return __builtin_amdgcn_readfirstlane(tl[i]) >> 16; };
-
-			// the slab the next DMA fetches: tile ta (first column n0a), k-rows [ka, ka + 16)
-			int ta = 0, n0a = tile_n0(0) * BN, ka = 0;
-			auto advance = [&](int next_entry) { // next_entry = tl[ta + 1] (-1 behind the last tile)
-				ka += KB;
-				const bool wrap = ka == n0a + BN, has = next_entry >= 0;
-				// behind the last slab of the unit the iterator stays where it is: the two requests past the end re-fetch the last slab (never read)
-				ta = wrap && has ? ta + 1 : ta;
-				ka = wrap ? (has ? 0 : ka - KB) : ka;
-				n0a = wrap && has ? (next_entry & 0xffff) * BN : n0a;
+			// DMA instruction r of a slab with NDMA = 6 (2 A + 4 B: 16 k-rows) or 8 (4 A + 4 B: the 32 k-rows of a double step, pB folded)
+			auto issue = [&](auto ndma_tag, int r, const double* pA, const double* pB, unsigned poA, unsigned poB) {
+				constexpr int NA = decltype(ndma_tag)::value - 4;
+				if (r < NA) dma(pA, voffA[r], ldstA[r], poA);
+				else dma(pB, voffB[r - NA], ldstB[r - NA], poB);
 			};
-			auto stage_all = [&](int buf) {
-				const double* pA = KsW + static_cast<long>(ka) * rows;
-				const double* pB = TW + n0a + static_cast<long>(ka) * ldt;
+
+			// the slab the next DMA fetches, as the wave's two source pointers: tile ta of the list, 16 k-rows — 32 from the middle of the diagonal block on.
+			// Behind a request the pointers move on by the slab's k-rows (two 64-bit additions: every scalar instruction of the whole steps shows in
+			// the step time, see profiles/diag_steps.md); only behind a tile's LAST slab — the double step (14, 15), requested by the tile's step 9 —
+			// they go to the next tile of the list (next_entry = tl[ta + 1]; -1 behind the last tile).  Behind the last slab of the unit they stay on that
+			// slab: the two requests past the end re-fetch 16 of its k-rows each (never read)
+			int ta = 0;
+			const double* pAn = KsW;
+			const double* pBn = TW + tile_n0(0) * BN;
+			const long stepA = static_cast<long>(KB) * rows, stepB = static_cast<long>(KB) * ldt;
+			auto next_tile = [&](int next_entry) {
+				const bool has = next_entry >= 0;
+				ta = has ? ta + 1 : ta;
+				pAn = has ? KsW : pAn;
+				pBn = has ? TW + (next_entry & 0xffff) * BN : pBn;
+			};
+			auto stage_all = [&](int buf) { // the first two slabs of a unit: single steps (a tile has at least the 12 steps of its diagonal block)
 #pragma unroll
-				for (int i = 0; i < 6; ++i) dma(i < 2 ? pA : pB, voff[i], ldst[i], 8u * static_cast<unsigned>(buf * (i < 2 ? ASL : BSL)));
+				for (int r = 0; r < 6; ++r) issue(std::integral_constant<int, 6>{}, r, pAn, pBn, 8u * static_cast<unsigned>(buf * ASL), 8u * static_cast<unsigned>(buf * BSL));
+				pAn += stepA, pBn += stepB;
 			};
 			__syncthreads(); // the stage is free (previous unit)
 			stage_all(0);
-			advance(entry(1));
 			stage_all(1);
-			advance(entry(ta + 1));
 			asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)\n\ts_barrier" ::: "memory"); // slab 0 has landed (the six requests of slab 1 may still be out)
-			int p = 0; // buffer of the current step
 			double cA[AF], cB[BF]; // operands of the next MFMA group
-			auto read_ops = [&](int buf, int kk, double (&af)[AF], double (&bf)[BF]) {
-				const double* __restrict__ pa = As + buf * ASL + wm * (16 * AF) + fr;
-				const double* __restrict__ pb = Bs + buf * BSL + WNI * 16 + fr;
+			// the operands of one MFMA group (4 k-rows from kk on) of the step in stage buf: the fragments j >= TM are live (none: nothing is read);
+			// half = 1: the second 16 k-rows of a double step — the stage's further A rows, the live B columns 128 to the left
+			auto read_ops = [&](auto tm_tag, int buf, int kk, int half, double (&af)[AF], double (&bf)[BF]) {
+				constexpr int TM = decltype(tm_tag)::value;
+				if constexpr (TM < BF)
+				{
+					const double* __restrict__ pa = (half ? Ax : As) + buf * ASL + wm * (16 * AF) + fr;
+					const double* __restrict__ pb = Bs + buf * BSL + WNI * 16 + fr;
 #pragma unroll
-				for (int i = 0; i < AF; ++i) af[i] = pa[(kk + fk) * ASr + i * 16];
+					for (int i = 0; i < AF; ++i) af[i] = pa[(kk + fk) * ASr + i * 16];
 #pragma unroll
-				for (int j = 0; j < BF; ++j) bf[j] = pb[(kk + fk) * BS + j * (16 * WN)];
+					for (int j = TM; j < BF; ++j) bf[j] = pb[(kk + fk) * BS + j * (16 * WN) - 128 * half];
+				}
 			};
-			read_ops(0, 0, cA, cB);
+			auto take = [&](auto tm_tag, const double (&af)[AF], const double (&bf)[BF]) {
+				constexpr int TM = decltype(tm_tag)::value;
+				if constexpr (TM < BF)
+				{
+#pragma unroll
+					for (int i = 0; i < AF; ++i) cA[i] = af[i];
+#pragma unroll
+					for (int j = TM; j < BF; ++j) cB[j] = bf[j];
+				}
+			};
+			constexpr std::integral_constant<int, 0> all_live{};
+			read_ops(all_live, 0, 0, 0, cA, cB);
 			double rsq[AF];
 #pragma unroll
 			for (int i = 0; i < AF; ++i) rsq[i] = 0.0;
@@ -536,41 +587,64 @@ namespace gple
 				for (int i = 0; i < AF; ++i)
 #pragma unroll
 					for (int j = 0; j < BF; ++j) acc[i][j] = (d4){0.0, 0.0, 0.0, 0.0};
-				// one k-step against the column blocks wn + WN t, t >= TMIN
-				auto kstep = [&](auto tmin_tag) {
-					constexpr int TMIN = decltype(tmin_tag)::value;
-					const int next_entry_v = tl[ta + 1]; // consumed in the middle of the step
+				// one step: 16 k-rows against the column blocks wn + WN t, t >= T0, and in a double step (T1 >= 0) 16 more against t >= T1.  TN: the live
+				// range of the first group of the step that follows; NDMA: 6 or 8, the DMA instructions of the slab this step requests (the one after the next)
+				auto kstep = [&](auto p_tag, auto t0_tag, auto t1_tag, auto tn_tag, auto ndma_tag, auto last_tag) {
+					constexpr int p = decltype(p_tag)::value, pn = p ^ 1; // the stage this step reads, the stage of the next step
+					constexpr int T1 = decltype(t1_tag)::value, NDMA = decltype(ndma_tag)::value;
+					constexpr bool DBL = T1 >= 0, LAST = decltype(last_tag)::value; // LAST: this step requests the last slab of its tile
+					int next_entry_v = 0;
+					if constexpr (LAST) next_entry_v = tl[ta + 1]; // consumed in the middle of the step
 					// the slab this step's DMA fetches and where it goes (the buffer this step reads): scalar work, done while the MFMAs behind the last
 					// barrier still run — between a wave's last MFMA of the step and the barrier there is nothing but the barrier
-					const double* pA = KsW + static_cast<long>(ka) * rows;
-					const double* pB = TW + n0a + static_cast<long>(ka) * ldt;
+					const double* pA = pAn;
+					const double* pB = pBn + (NDMA == 8 ? fold : 0);
 					unsigned poA = 8u * static_cast<unsigned>(p * ASL), poB = 8u * static_cast<unsigned>(p * BSL);
 					asm volatile("" : "+s"(pA), "+s"(pB), "+s"(poA), "+s"(poB)); // computed HERE (hipcc sinks them to their use behind the barrier otherwise)
 					double nA[AF], nB[BF];
-#pragma unroll
-					for (int kk = 4; kk < KB; kk += 4)
-					{
-						// Inside the three groups in front of the barrier hipcc schedules (it requests a group's operands two MFMAs before the end of the
-						// group before: 0.923 of the peak at C4r against 0.911 with the requests pinned to the start of the group, 0.918 in its middle —
-						// same box); what is pinned is the barrier's neighbourhood: unpinned, hipcc gathers the reads of ALL groups in front of the barrier
-						// and sinks three groups of MFMAs behind it
-						read_ops(p, kk, nA, nB);
-						if (kk == 8) advance(__builtin_amdgcn_readfirstlane(next_entry_v));
+					auto mfmas = [&](auto tm_tag) {
+						constexpr int TM = decltype(tm_tag)::value;
 #pragma unroll
 						for (int i = 0; i < AF; ++i)
 #pragma unroll
-							for (int j = TMIN; j < BF; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(cB[j], cA[i], acc[i][j], 0, 0, 0);
-						if (kk == 12) __builtin_amdgcn_sched_barrier(0);
+							for (int j = TM; j < BF; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(cB[j], cA[i], acc[i][j], 0, 0, 0);
+					};
 #pragma unroll
-						for (int i = 0; i < AF; ++i) cA[i] = nA[i];
+					for (int kk = 4; kk < KB; kk += 4)
+					{
+						// Inside the groups in front of the barrier hipcc schedules (it requests a group's operands two MFMAs before the end of the
+						// group before: 0.923 of the peak at C4r against 0.911 with the requests pinned to the start of the group, 0.918 in its middle —
+						// same box); what is pinned is the barrier's neighbourhood: unpinned, hipcc gathers the reads of ALL groups in front of the barrier
+						// and sinks three groups of MFMAs behind it
+						read_ops(t0_tag, p, kk, 0, nA, nB);
+						if (kk == 8)
+						{
+							if constexpr (LAST) next_tile(__builtin_amdgcn_readfirstlane(next_entry_v));
+							else pAn += (NDMA == 8 ? 2 : 1) * stepA, pBn += (NDMA == 8 ? 2 : 1) * stepB;
+						}
+						mfmas(t0_tag);
+						if (!DBL && kk == 12) __builtin_amdgcn_sched_barrier(0);
+						take(t0_tag, nA, nB);
+					}
+					if constexpr (DBL)
+					{
+						// the second 16 k-rows: the same accumulators go on with the groups of step D + 1, behind all four groups of step D
 #pragma unroll
-						for (int j = 0; j < BF; ++j) cB[j] = nB[j];
+						for (int kk = 0; kk < KB; kk += 4)
+						{
+							read_ops(t1_tag, p, kk, 1, nA, nB);
+							if (kk == 0) mfmas(t0_tag);
+							else mfmas(t1_tag);
+							if (kk == 12) __builtin_amdgcn_sched_barrier(0);
+							take(t1_tag, nA, nB);
+						}
 					}
 					asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory"); // the next slab has landed; every wave holds its last operands of this one
-					p ^= 1;
 					// behind the barrier: LEAD MFMAs of the step's last group at once (their operands were read in front of the barrier), then the requests
-					// for the next step's first operands, then the six DMA issues of the slab after the next (into the buffer this step read) between
-					// the group's other MFMAs.  LEAD: measured on one box, 4 x 4: 2 leads 0 by 0.6 % at C4r; 2 x 8 (ten operand requests): 0 leads 2 by 0.5 % at C2
+					// for the next step's first operands, then the DMA issues of the slab after the next (into the buffer this step read) between the
+					// group's other MFMAs; a wave with fewer MFMAs than that sends the rest back to back.
+					// LEAD: measured on one box, 4 x 4: 2 leads 0 by 0.6 % at C4r; 2 x 8 (ten operand requests): 0 leads 2 by 0.5 % at C2
+					constexpr int TMIN = DBL ? T1 : decltype(t0_tag)::value; // of the step's last group
 					constexpr int NM = AF * (BF - TMIN), LEAD = AF == 4 ? 2 : 0;
 					int issued = 0;
 #pragma unroll
@@ -581,12 +655,12 @@ namespace gple
 							const int m = i * (BF - TMIN) + (j - TMIN);
 							if (m == LEAD)
 							{
-								read_ops(p, 0, nA, nB);
+								read_ops(tn_tag, pn, 0, 0, nA, nB);
 								__builtin_amdgcn_sched_barrier(0);
 							}
-							if (m >= LEAD && (m - LEAD) % 2 == 0 && issued < 6)
+							if (m >= LEAD && (m - LEAD) % 2 == 0 && issued < NDMA)
 							{
-								dma(issued < 2 ? pA : pB, voff[issued], ldst[issued], issued < 2 ? poA : poB);
+								issue(ndma_tag, issued, pA, pB, poA, poB);
 								++issued;
 							}
 							acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(cB[j], cA[i], acc[i][j], 0, 0, 0);
@@ -595,23 +669,31 @@ namespace gple
 					if constexpr (NM <= LEAD)
 					{
 						__builtin_amdgcn_sched_barrier(0);
-						read_ops(p, 0, nA, nB);
+						read_ops(tn_tag, pn, 0, 0, nA, nB);
 						__builtin_amdgcn_sched_barrier(0);
 					}
 #pragma unroll
-					for (int r = NM > LEAD ? ((NM - LEAD + 1) / 2 < 6 ? (NM - LEAD + 1) / 2 : 6) : 0; r < 6; ++r) dma(r < 2 ? pA : pB, voff[r], ldst[r], r < 2 ? poA : poB);
+					for (int r = NM > LEAD ? ((NM - LEAD + 1) / 2 < NDMA ? (NM - LEAD + 1) / 2 : NDMA) : 0; r < NDMA; ++r) issue(ndma_tag, r, pA, pB, poA, poB);
 					__builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-					for (int i = 0; i < AF; ++i) cA[i] = nA[i];
-#pragma unroll
-					for (int j = 0; j < BF; ++j) cB[j] = nB[j];
+					take(tn_tag, nA, nB);
 				};
 				const int nd = n0 / KB;
-				for (int s = 0; s < nd; ++s) kstep(std::integral_constant<int, 0>{});
-				// diagonal 256-block: step D starts at k = n0 + 16 D, the column blocks jb < D are zero; jb = WNI + WN t >= D  <=>  t >= ceil((D - WNI) / WN)
-				[&]<int... D>(std::integer_sequence<int, D...>) {
-					(kstep(std::integral_constant<int, (D > WNI ? (D - WNI + WN - 1) / WN : 0)>{}), ...);
-				}(std::make_integer_sequence<int, BN / KB>{});
+				// (a tile has an even number of steps, nd a multiple of 16 and the 12 of the diagonal block: the stage of every step is a compile-time constant)
+				for (int s = 0; s < nd; s += 2)
+				{
+					kstep(std::integral_constant<int, 0>{}, all_live, std::integral_constant<int, -1>{}, all_live, std::integral_constant<int, 6>{}, std::false_type{});
+					kstep(std::integral_constant<int, 1>{}, all_live, std::integral_constant<int, -1>{}, all_live, std::integral_constant<int, 6>{}, std::false_type{});
+				}
+				// diagonal 256-block: step D starts at k = n0 + 16 D, the column blocks jb < D are zero.  Twelve steps: D = 0 ... 7, then the pairs (8, 9) ...
+				// (14, 15).  Step e requests the slab of step e + 2: a double one for e = 6 ... 9, the first two of the next tile (whole or step 0: every
+				// fragment live) for e = 10 and 11
+				[&]<int... E>(std::integer_sequence<int, E...>) {
+					(kstep(std::integral_constant<int, (E & 1)>{}, std::integral_constant<int, diag_tmin(diag_first(E), WNI, WN)>{},
+						 std::integral_constant<int, (E < 8 ? -1 : diag_tmin(diag_first(E) + 1, WNI, WN))>{},
+						 std::integral_constant<int, (E == 11 ? 0 : diag_tmin(diag_first(E + 1), WNI, WN))>{},
+						 std::integral_constant<int, (E >= 6 && E <= 9 ? 8 : 6)>{}, std::bool_constant<E == 9>{}),
+						...);
+				}(std::make_integer_sequence<int, 12>{});
 #pragma unroll
 				for (int i = 0; i < AF; ++i)
 #pragma unroll
@@ -648,7 +730,8 @@ namespace gple
 			int n_total, double* __restrict__ q, long qstride, const Prune pr)
 		{
 			constexpr int KB = 16, WN = 16 / BF, ASr = BM + 16;
-			__shared__ __attribute__((aligned(16))) double lds[2 * KB * ASr + 2 * KB * BS + WN * BM];
+			// two stages of 32 A rows and 16 B rows and the partial sums of the column groups: 144 KB (4 x 4) of the CU's 160
+			__shared__ __attribute__((aligned(16))) double lds[4 * KB * ASr + 2 * KB * BS + WN * BM];
 			__shared__ int tl[TL_MAX + 2];
 			__shared__ int s_ntl;
 			const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
