@@ -128,6 +128,23 @@ def evolve(rho, bases, p, mass, length_x, length_p, dt, n_steps, freq=ref_freq):
     return rho
 
 
+# A mass or a momentum box this large takes every R or P phase below the spacing of doubles at 1: that propagator is the identity and the rows
+# or columns it would have coupled evolve on their own, which is what makes a restatement at n = 4096 affordable (Tests)
+DECOUPLE = 1e300
+
+
+def evolve_rows(rho_rows, x_rows, p, model, num_pes, length_x, length_p, dt, n_steps, freq=ref_freq):
+    """mass = DECOUPLE, so R is the identity: the x rows x_rows alone, rho_rows = rho[:, :, I, :] with every p, are the exact restatement of
+    those rows of the full grid"""
+    return evolve(rho_rows, Bases(x_rows, model, num_pes), p, DECOUPLE, length_x, length_p, dt, n_steps, freq)
+
+
+def evolve_columns(rho_cols, bases, p_cols, mass, length_x, dt, n_steps, freq=ref_freq):
+    """length_p = DECOUPLE, so P is the identity: the p columns p_cols alone, rho_cols = rho[:, :, :, J] with every x (bases of the full x grid),
+    are the exact restatement of those columns of the full grid"""
+    return evolve(rho_cols, bases, p_cols, mass, length_x, DECOUPLE, dt, n_steps, freq)
+
+
 def psi_multiplier(theta, n, freq=ref_freq):
     """the hermitised shift as one multiplier on the stored triangle: psi_k = (phi_k + conj(phi_{(n - k) mod n})) / 2"""
     f = freq(n)

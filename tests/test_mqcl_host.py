@@ -119,6 +119,46 @@ def test_restatement_conserves_trace():
     assert abs(tr(out) - tr(rho)) <= 1e-12 * np.abs(rho).sum()
 
 
+def row_sums(r):
+    """sum over p of sum_a Re rho_aa, per x row"""
+    return sum(r[a, a].real.sum(axis=1) for a in range(r.shape[0]))
+
+
+def column_sums(r):
+    """sum over x of sum_a Re rho_aa, per p column"""
+    return sum(r[a, a].real.sum(axis=0) for a in range(r.shape[0]))
+
+
+@pytest.mark.parametrize("axis", ["rows", "columns"])
+@pytest.mark.parametrize("num_pes, model, n", [(2, 1, 37), (3, 3, 40)])
+def test_decoupled_limits_evolve_rows_and_columns_on_their_own(num_pes, model, n, axis):
+    """what tests/test_gpu_mqcl_sizes.py rests on at n up to 4096: with mass = DECOUPLE (length_p = DECOUPLE) R (P) is the identity, a subset of
+    rows (columns) restated alone is the full restatement on that subset, and the sums along the propagated axis are conserved one by one"""
+    x, p, lx = small_grid(n)
+    lp, mass, dt, steps = 40.0, 2000.0, 2.0, 2
+    rho = MN.random_hermitian(num_pes, n, np.random.default_rng(100 * num_pes + n))
+    bases = MN.Bases(x, model, num_pes)
+    idx = np.array([0, 1, 5, 17, n - 2, n - 1])
+    scale = np.abs(rho).max()
+    if axis == "rows":
+        full = MN.evolve(rho, bases, p, MN.DECOUPLE, lx, lp, dt, steps)
+        subset = lambda freq: MN.evolve_rows(rho[:, :, idx, :], x[idx], p, model, num_pes, lx, lp, dt, steps, freq=freq)
+        picked, sums = full[:, :, idx, :], row_sums
+    else:
+        full = MN.evolve(rho, bases, p, mass, lx, MN.DECOUPLE, dt, steps)
+        subset = lambda freq: MN.evolve_columns(rho[:, :, :, idx], bases, p[idx], mass, lx, dt, steps, freq=freq)
+        picked, sums = full[:, :, :, idx], column_sums
+    sub = subset(MN.ref_freq)
+    assert np.abs(sub - picked).max() <= 1e-14 * scale, np.abs(sub - picked).max() / scale
+    s0, s1 = sums(rho), sums(full)
+    assert np.abs(s1 - s0).max() <= 1e-13 * np.abs(s0).max(), np.abs(s1 - s0).max() / np.abs(s0).max()
+    # not a test of the identity: the surviving propagators move the state
+    assert np.abs(full - rho).max() > 1e-2 * scale
+    if n % 2:
+        other = subset(MN.fftfreq)
+        assert np.abs(other - sub).max() > 1e-9 * scale, np.abs(other - sub).max() / scale
+
+
 class NumpyApi:
     """the three gple_mqcl_* calls and pes_adiabatic_n on the restatement: the driver's loop and files without a GPU"""
 
