@@ -384,799 +384,4 @@ extern "C"
 		for (int k = 0; k < num_pes; ++k) populations[k] = h[3 + k];
 		return GPLE_OK;
 	}
-
-	/* ---- fewest-switches surface hopping (gple_hop.hip) --------------------------------------------------------------------- */
-	static bool hop_size_ok(gple_ctx* ctx, int num_pes, int model, size_t n, size_t offset, PesModel* pes)
-	{
-		constexpr size_t LIMIT = size_t(1) << 32; // the trajectory index is one word of the counter
-		return pes_resolve(ctx, num_pes, model, pes) && n >= 1 && n <= LIMIT && offset <= LIMIT - n;
-	}
-	static bool hop_positive(double v) { return std::isfinite(v) && v > 0.0; }
-	// the surface / status array of a hop call as the kernels see it (Staged, for ints): a device array in place, a host array through pooled memory
-	struct StagedInts
-	{
-		Scratch buf;
-		const bool dev;
-		int* p = nullptr;
-		int* host = nullptr; // back() copies p here
-		size_t n = 0;
-		StagedInts(gple_ctx* c, bool device): buf(c), dev(device) {}
-		// read: the kernels read the caller's values; written: the caller receives the kernels'
-		hipError_t stage(const int* a, size_t count, bool read, bool written)
-		{
-			p = const_cast<int*>(a);
-			if (dev) return hipSuccess;
-			hipError_t e = buf.get((count + 1) / 2);
-			if (e != hipSuccess) return e;
-			p = reinterpret_cast<int*>(buf.p);
-			if (written) host = const_cast<int*>(a), n = count;
-			return read ? hipMemcpyAsync(p, a, count * sizeof(int), hipMemcpyHostToDevice, buf.ctx->stream) : hipSuccess;
-		}
-		hipError_t back() { return host ? hipMemcpyAsync(host, p, n * sizeof(int), hipMemcpyDeviceToHost, buf.ctx->stream) : hipSuccess; }
-	};
-
-	int gple_hop_sample(gple_ctx* ctx, int num_pes, int model, size_t n, size_t trajectory_offset, unsigned long long seed, double x0, double p0,
-		double sigma_x, double sigma_p, int surface0, unsigned flags, double* x, double* p, double* b, int* surface, int* status)
-	{
-		PesModel pes;
-		if (!ctx || !hop_size_ok(ctx, num_pes, model, n, trajectory_offset, &pes) || !hop_positive(sigma_x) || !hop_positive(sigma_p) || surface0 < 0 ||
-			surface0 >= num_pes || !x || !p || !b || !surface || !status)
-			return GPLE_ERR_BAD_ARG;
-		GPLE_OPEN(ctx);
-		const bool dev = flags & GPLE_IO_DEVICE;
-		GPLE_CALL(ctx);
-		if (!pes_resolve(ctx, num_pes, model, &pes)) return GPLE_ERR_BAD_ARG; // under the call lock, which gple_pes_undefine takes: the table outlives the enqueue
-		hipStream_t st = ctx->stream;
-		Staged xs(ctx, dev), ps(ctx, dev), bs(ctx, dev);
-		StagedInts su(ctx, dev), ss(ctx, dev);
-		GPLE_HIP(ctx, xs.out(x, n));
-		GPLE_HIP(ctx, ps.out(p, n));
-		GPLE_HIP(ctx, bs.out(b, 2 * n * num_pes));
-		GPLE_HIP(ctx, su.stage(surface, n, false, true));
-		GPLE_HIP(ctx, ss.stage(status, n, false, true));
-		const HopEnsemble e{num_pes, static_cast<long>(n), trajectory_offset, seed, xs.p, ps.p, bs.p, su.p, ss.p};
-		GPLE_HIP(ctx, launch_hop_sample(st, e, pes, x0, p0, sigma_x, sigma_p, surface0));
-		for (Staged* o : {&xs, &ps, &bs}) GPLE_HIP(ctx, o->back());
-		for (StagedInts* o : {&su, &ss}) GPLE_HIP(ctx, o->back());
-		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
-		return GPLE_OK;
-	}
-
-	// decoherence is a GPLE_HOP_DC_*, and in mode EDC edc_c is finite and not negative (it is read in that mode only)
-	static bool hop_decoherence_ok(int decoherence, double edc_c)
-	{
-		if (decoherence < GPLE_HOP_DC_NONE || decoherence > GPLE_HOP_DC_COLLAPSE_ATTEMPT) return false;
-		return decoherence != GPLE_HOP_DC_EDC || (std::isfinite(edc_c) && edc_c >= 0.0);
-	}
-
-	int gple_hop_evolve_dc(gple_ctx* ctx, int num_pes, int model, size_t n, size_t trajectory_offset, unsigned long long seed, double mass, double dt,
-		size_t first_step, size_t n_steps, double x_left, double x_right, int decoherence, double edc_c, unsigned flags, double* x, double* p, double* b,
-		int* surface, int* status)
-	{
-		PesModel pes;
-		if (!ctx || !hop_size_ok(ctx, num_pes, model, n, trajectory_offset, &pes) || !hop_positive(mass) || !hop_positive(dt) || !std::isfinite(x_left) ||
-			!std::isfinite(x_right) || !(x_left < x_right) || n_steps > (1ul << 40) || !x || !p || !b || !surface || !status ||
-			!hop_decoherence_ok(decoherence, edc_c))
-			return GPLE_ERR_BAD_ARG;
-		GPLE_OPEN(ctx);
-		if (n_steps == 0) return GPLE_OK;
-		const bool dev = flags & GPLE_IO_DEVICE;
-		GPLE_CALL(ctx);
-		if (!pes_resolve(ctx, num_pes, model, &pes)) return GPLE_ERR_BAD_ARG; // under the call lock, which gple_pes_undefine takes: the table outlives the enqueue
-		hipStream_t st = ctx->stream;
-		Staged xs(ctx, dev), ps(ctx, dev), bs(ctx, dev);
-		StagedInts su(ctx, dev), ss(ctx, dev);
-		GPLE_HIP(ctx, xs.inout(x, n));
-		GPLE_HIP(ctx, ps.inout(p, n));
-		GPLE_HIP(ctx, bs.inout(b, 2 * n * num_pes));
-		GPLE_HIP(ctx, su.stage(surface, n, true, true));
-		GPLE_HIP(ctx, ss.stage(status, n, true, true));
-		const HopEnsemble e{num_pes, static_cast<long>(n), trajectory_offset, seed, xs.p, ps.p, bs.p, su.p, ss.p};
-		timer_start(ctx, GPLE_TIMER_HOP);
-		const hipError_t launched = launch_hop_evolve_dc(st, e, pes, mass, dt, first_step, static_cast<long>(n_steps), x_left, x_right,
-			(flags & GPLE_HOP_REVERSE) != 0, decoherence, edc_c); // GPLE_HOP_DC_NONE: the kernels gple_hop_evolve always launched
-		timer_stop(ctx, GPLE_TIMER_HOP); // on the error path too: no span stays open
-		GPLE_HIP(ctx, launched);
-		for (Staged* o : {&xs, &ps, &bs}) GPLE_HIP(ctx, o->back());
-		for (StagedInts* o : {&su, &ss}) GPLE_HIP(ctx, o->back());
-		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
-		return GPLE_OK;
-	}
-	int gple_hop_evolve(gple_ctx* ctx, int num_pes, int model, size_t n, size_t trajectory_offset, unsigned long long seed, double mass, double dt,
-		size_t first_step, size_t n_steps, double x_left, double x_right, unsigned flags, double* x, double* p, double* b, int* surface, int* status)
-	{
-		return gple_hop_evolve_dc(ctx, num_pes, model, n, trajectory_offset, seed, mass, dt, first_step, n_steps, x_left, x_right, GPLE_HOP_DC_NONE, 0.0, flags, x, p,
-			b, surface, status);
-	}
-
-	int gple_hop_observe(gple_ctx* ctx, int num_pes, int model, size_t n, double mass, unsigned flags, const double* x, const double* p, const double* b,
-		const int* surface, const int* status, double* out)
-	{
-		PesModel pes;
-		if (!ctx || !hop_size_ok(ctx, num_pes, model, n, 0, &pes) || !hop_positive(mass) || !x || !p || !b || !surface || !status || !out) return GPLE_ERR_BAD_ARG;
-		GPLE_OPEN(ctx);
-		const bool dev = flags & GPLE_IO_DEVICE;
-		GPLE_CALL(ctx);
-		if (!pes_resolve(ctx, num_pes, model, &pes)) return GPLE_ERR_BAD_ARG; // under the call lock, which gple_pes_undefine takes: the table outlives the enqueue
-		hipStream_t st = ctx->stream;
-		Staged xs(ctx, dev), ps(ctx, dev), bs(ctx, dev), o(ctx, dev);
-		StagedInts su(ctx, dev), ss(ctx, dev);
-		Scratch work(ctx);
-		GPLE_HIP(ctx, work.get(hop_observe_work_doubles(num_pes, static_cast<long>(n))));
-		GPLE_HIP(ctx, o.out(out, 4 * num_pes + 3));
-		GPLE_HIP(ctx, xs.in(x, n));
-		GPLE_HIP(ctx, ps.in(p, n));
-		GPLE_HIP(ctx, bs.in(b, 2 * n * num_pes));
-		GPLE_HIP(ctx, su.stage(surface, n, true, false));
-		GPLE_HIP(ctx, ss.stage(status, n, true, false));
-		const HopEnsemble e{num_pes, static_cast<long>(n), 0, 0, xs.p, ps.p, bs.p, su.p, ss.p};
-		GPLE_HIP(ctx, launch_hop_observe(st, e, pes, mass, work.p, o.p));
-		GPLE_HIP(ctx, o.back());
-		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
-		return GPLE_OK;
-	}
-
-	// n_x n_p <= GPLE_HOP_MAX_CELLS, without overflow
-	static bool hop_cells_ok(size_t n_x, size_t n_p) { return n_x >= 1 && n_p >= 1 && n_x <= GPLE_HOP_MAX_CELLS && n_p <= GPLE_HOP_MAX_CELLS / n_x; }
-
-	int gple_hop_bin(gple_ctx* ctx, int num_pes, int model, size_t n, double x_first, double dx, size_t n_x, double p_first, double dp, size_t n_p,
-		unsigned flags, const double* x, const double* p, const double* b, const int* surface, const int* status, long long* acc)
-	{
-		PesModel pes;
-		if (!ctx || !hop_size_ok(ctx, num_pes, model, n, 0, &pes) || !hop_cells_ok(n_x, n_p) || !hop_positive(dx) || !hop_positive(dp) ||
-			!std::isfinite(x_first) || !std::isfinite(p_first) || !x || !p || !b || !surface || !status || !acc)
-			return GPLE_ERR_BAD_ARG;
-		GPLE_OPEN(ctx);
-		const bool dev = flags & GPLE_IO_DEVICE, keep = flags & GPLE_HOP_ACCUMULATE;
-		const size_t words = static_cast<size_t>(hop_bin_planes(num_pes)) * n_x * n_p + 2;
-		GPLE_CALL(ctx);
-		if (!pes_resolve(ctx, num_pes, model, &pes)) return GPLE_ERR_BAD_ARG; // under the call lock, which gple_pes_undefine takes: the table outlives the enqueue
-		hipStream_t st = ctx->stream;
-		Staged xs(ctx, dev), ps(ctx, dev), bs(ctx, dev);
-		StagedInts su(ctx, dev), ss(ctx, dev);
-		Scratch sums(ctx); // a host acc: the integers in pooled memory (8 bytes each, as a double)
-		long long* a = acc;
-		if (!dev)
-		{
-			GPLE_HIP(ctx, sums.get(words));
-			a = reinterpret_cast<long long*>(sums.p);
-		}
-		GPLE_HIP(ctx, xs.in(x, n));
-		GPLE_HIP(ctx, ps.in(p, n));
-		GPLE_HIP(ctx, bs.in(b, 2 * n * num_pes));
-		GPLE_HIP(ctx, su.stage(surface, n, true, false));
-		GPLE_HIP(ctx, ss.stage(status, n, true, false));
-		if (!keep) GPLE_HIP(ctx, hipMemsetAsync(a, 0, words * sizeof(long long), st));
-		else if (!dev) GPLE_HIP(ctx, hipMemcpyAsync(a, acc, words * sizeof(long long), hipMemcpyHostToDevice, st));
-		const HopEnsemble e{num_pes, static_cast<long>(n), 0, 0, xs.p, ps.p, bs.p, su.p, ss.p};
-		const HopGrid g{x_first, dx, p_first, dp, static_cast<long>(n_x), static_cast<long>(n_p)};
-		timer_start(ctx, GPLE_TIMER_HOP_BIN);
-		const hipError_t launched = launch_hop_bin(st, e, pes, g, (flags & GPLE_HOP_BIN_ALL) != 0, a);
-		timer_stop(ctx, GPLE_TIMER_HOP_BIN); // on the error path too: no span stays open
-		GPLE_HIP(ctx, launched);
-		if (!dev)
-		{
-			GPLE_HIP(ctx, hipMemcpyAsync(acc, a, words * sizeof(long long), hipMemcpyDeviceToHost, st));
-			GPLE_HIP(ctx, hipStreamSynchronize(st));
-		}
-		return GPLE_OK;
-	}
-
-	int gple_hop_density(gple_ctx* ctx, int num_pes, size_t n_x, size_t n_p, double dx, double dp, size_t n_norm, unsigned flags, const long long* acc,
-		double* rho)
-	{
-		const double w = static_cast<double>(n_norm) * dx * dp; // left to right
-		if (!ctx || (num_pes != 2 && num_pes != 3) || !hop_cells_ok(n_x, n_p) || !hop_positive(dx) || !hop_positive(dp) || n_norm == 0 || !hop_positive(w) ||
-			!acc || !rho)
-			return GPLE_ERR_BAD_ARG;
-		GPLE_OPEN(ctx);
-		const bool dev = flags & GPLE_IO_DEVICE;
-		const size_t cells = n_x * n_p, words = static_cast<size_t>(hop_bin_planes(num_pes)) * cells + 2;
-		GPLE_CALL(ctx);
-		hipStream_t st = ctx->stream;
-		Staged r(ctx, dev);
-		Scratch sums(ctx);
-		const long long* a = acc;
-		GPLE_HIP(ctx, r.out(rho, 2 * static_cast<size_t>(num_pes) * num_pes * cells));
-		if (!dev)
-		{
-			GPLE_HIP(ctx, sums.get(words));
-			GPLE_HIP(ctx, hipMemcpyAsync(sums.p, acc, words * sizeof(long long), hipMemcpyHostToDevice, st));
-			a = reinterpret_cast<const long long*>(sums.p);
-		}
-		GPLE_HIP(ctx, launch_hop_density(st, num_pes, static_cast<long>(cells), w, a, r.p));
-		GPLE_HIP(ctx, r.back());
-		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
-		return GPLE_OK;
-	}
-
-	/* ---- grouped ensembles ("A curve in one launch") ------------------------------------------------------------------------ */
-	// n = n_groups n_per_group without overflow, within the index space together with the offset
-	static bool hop_groups_ok(gple_ctx* ctx, int num_pes, int model, size_t n_groups, size_t n_per_group, size_t offset, PesModel* pes, size_t* n)
-	{
-		if (n_groups == 0 || n_per_group == 0 || n_groups > GPLE_HOP_MAX_GROUPS || n_per_group > (size_t(1) << 32) / n_groups) return false;
-		*n = n_groups * n_per_group;
-		return hop_size_ok(ctx, num_pes, model, *n, offset, pes);
-	}
-	// a host table of a grouped call in pooled device memory.  The table is the caller's pageable memory whatever the flags say: the copy is
-	// waited for, so that the caller may free it when the call returns
-	static hipError_t hop_table(Scratch& t, const double* host, size_t count)
-	{
-		hipError_t e = t.get(count);
-		if (e != hipSuccess) return e;
-		e = hipMemcpyAsync(t.p, host, count * sizeof(double), hipMemcpyHostToDevice, t.ctx->stream);
-		return e == hipSuccess ? hipStreamSynchronize(t.ctx->stream) : e;
-	}
-
-	int gple_hop_sample_groups(gple_ctx* ctx, int num_pes, int model, size_t n_groups, size_t n_per_group, size_t trajectory_offset, unsigned long long seed,
-		const double* packets, int surface0, unsigned flags, double* x, double* p, double* b, int* surface, int* status)
-	{
-		PesModel pes;
-		size_t n = 0;
-		if (!ctx || !hop_groups_ok(ctx, num_pes, model, n_groups, n_per_group, trajectory_offset, &pes, &n) || !packets || surface0 < 0 || surface0 >= num_pes ||
-			!x || !p || !b || !surface || !status)
-			return GPLE_ERR_BAD_ARG;
-		for (size_t g = 0; g < n_groups; ++g)
-		{
-			const double* row = packets + 4 * g;
-			if (!std::isfinite(row[0]) || !std::isfinite(row[1]) || !std::isfinite(row[2]) || !std::isfinite(row[3]) || row[2] < 0.0 || row[3] < 0.0) return GPLE_ERR_BAD_ARG;
-		}
-		GPLE_OPEN(ctx);
-		const bool dev = flags & GPLE_IO_DEVICE;
-		GPLE_CALL(ctx);
-		if (!pes_resolve(ctx, num_pes, model, &pes)) return GPLE_ERR_BAD_ARG; // under the call lock, which gple_pes_undefine takes: the table outlives the enqueue
-		hipStream_t st = ctx->stream;
-		Staged xs(ctx, dev), ps(ctx, dev), bs(ctx, dev);
-		StagedInts su(ctx, dev), ss(ctx, dev);
-		Scratch table(ctx);
-		GPLE_HIP(ctx, hop_table(table, packets, 4 * n_groups));
-		GPLE_HIP(ctx, xs.out(x, n));
-		GPLE_HIP(ctx, ps.out(p, n));
-		GPLE_HIP(ctx, bs.out(b, 2 * n * num_pes));
-		GPLE_HIP(ctx, su.stage(surface, n, false, true));
-		GPLE_HIP(ctx, ss.stage(status, n, false, true));
-		const HopEnsemble e{num_pes, static_cast<long>(n), trajectory_offset, seed, xs.p, ps.p, bs.p, su.p, ss.p};
-		GPLE_HIP(ctx, launch_hop_sample_groups(st, e, pes, static_cast<long>(n_per_group), table.p, surface0));
-		for (Staged* o : {&xs, &ps, &bs}) GPLE_HIP(ctx, o->back());
-		for (StagedInts* o : {&su, &ss}) GPLE_HIP(ctx, o->back());
-		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
-		return GPLE_OK;
-	}
-
-	int gple_hop_evolve_groups_dc(gple_ctx* ctx, int num_pes, int model, size_t n_groups, size_t n_per_group, size_t trajectory_offset,
-		unsigned long long seed, double mass, const double* dt, size_t first_step, size_t n_steps, double x_left, double x_right, int decoherence,
-		double edc_c, unsigned flags, double* x, double* p, double* b, int* surface, int* status, int* hops)
-	{
-		PesModel pes;
-		size_t n = 0;
-		if (!ctx || !hop_groups_ok(ctx, num_pes, model, n_groups, n_per_group, trajectory_offset, &pes, &n) || !hop_positive(mass) || !dt || !std::isfinite(x_left) ||
-			!std::isfinite(x_right) || !(x_left < x_right) || n_steps > (1ul << 40) || !x || !p || !b || !surface || !status ||
-			!hop_decoherence_ok(decoherence, edc_c))
-			return GPLE_ERR_BAD_ARG;
-		for (size_t g = 0; g < n_groups; ++g)
-			if (!hop_positive(dt[g])) return GPLE_ERR_BAD_ARG;
-		GPLE_OPEN(ctx);
-		if (n_steps == 0) return GPLE_OK;
-		const bool dev = flags & GPLE_IO_DEVICE;
-		GPLE_CALL(ctx);
-		if (!pes_resolve(ctx, num_pes, model, &pes)) return GPLE_ERR_BAD_ARG; // under the call lock, which gple_pes_undefine takes: the table outlives the enqueue
-		hipStream_t st = ctx->stream;
-		Staged xs(ctx, dev), ps(ctx, dev), bs(ctx, dev);
-		StagedInts su(ctx, dev), ss(ctx, dev), hs(ctx, dev);
-		Scratch table(ctx);
-		GPLE_HIP(ctx, hop_table(table, dt, n_groups));
-		GPLE_HIP(ctx, xs.inout(x, n));
-		GPLE_HIP(ctx, ps.inout(p, n));
-		GPLE_HIP(ctx, bs.inout(b, 2 * n * num_pes));
-		GPLE_HIP(ctx, su.stage(surface, n, true, true));
-		GPLE_HIP(ctx, ss.stage(status, n, true, true));
-		if (hops) GPLE_HIP(ctx, hs.stage(hops, 2 * n, true, true));
-		const HopEnsemble e{num_pes, static_cast<long>(n), trajectory_offset, seed, xs.p, ps.p, bs.p, su.p, ss.p};
-		timer_start(ctx, GPLE_TIMER_HOP_GROUPS);
-		const hipError_t launched = launch_hop_evolve_groups_dc(st, e, pes, static_cast<long>(n_per_group), mass, table.p, first_step, static_cast<long>(n_steps), x_left,
-			x_right, (flags & GPLE_HOP_REVERSE) != 0, hs.p, decoherence, edc_c); // GPLE_HOP_DC_NONE: the kernels gple_hop_evolve_groups always launched
-		timer_stop(ctx, GPLE_TIMER_HOP_GROUPS); // on the error path too: no span stays open
-		GPLE_HIP(ctx, launched);
-		for (Staged* o : {&xs, &ps, &bs}) GPLE_HIP(ctx, o->back());
-		for (StagedInts* o : {&su, &ss, &hs}) GPLE_HIP(ctx, o->back());
-		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
-		return GPLE_OK;
-	}
-	int gple_hop_evolve_groups(gple_ctx* ctx, int num_pes, int model, size_t n_groups, size_t n_per_group, size_t trajectory_offset, unsigned long long seed,
-		double mass, const double* dt, size_t first_step, size_t n_steps, double x_left, double x_right, unsigned flags, double* x, double* p, double* b,
-		int* surface, int* status, int* hops)
-	{
-		return gple_hop_evolve_groups_dc(ctx, num_pes, model, n_groups, n_per_group, trajectory_offset, seed, mass, dt, first_step, n_steps, x_left, x_right,
-			GPLE_HOP_DC_NONE, 0.0, flags, x, p, b, surface, status, hops);
-	}
-
-	int gple_hop_observe_groups(gple_ctx* ctx, int num_pes, int model, size_t n_groups, size_t n_per_group, double mass, unsigned flags, const double* x,
-		const double* p, const double* b, const int* surface, const int* status, double* out)
-	{
-		PesModel pes;
-		size_t n = 0;
-		if (!ctx || !hop_groups_ok(ctx, num_pes, model, n_groups, n_per_group, 0, &pes, &n) || !hop_positive(mass) || !x || !p || !b || !surface || !status || !out)
-			return GPLE_ERR_BAD_ARG;
-		GPLE_OPEN(ctx);
-		const bool dev = flags & GPLE_IO_DEVICE;
-		GPLE_CALL(ctx);
-		if (!pes_resolve(ctx, num_pes, model, &pes)) return GPLE_ERR_BAD_ARG; // under the call lock, which gple_pes_undefine takes: the table outlives the enqueue
-		hipStream_t st = ctx->stream;
-		Staged xs(ctx, dev), ps(ctx, dev), bs(ctx, dev), o(ctx, false); // out is a host array whatever the flags say
-		StagedInts su(ctx, dev), ss(ctx, dev);
-		Scratch work(ctx);
-		GPLE_HIP(ctx, work.get(hop_observe_groups_work_doubles(num_pes, static_cast<long>(n_groups), static_cast<long>(n_per_group))));
-		GPLE_HIP(ctx, o.out(out, n_groups * (4 * num_pes + 3)));
-		GPLE_HIP(ctx, xs.in(x, n));
-		GPLE_HIP(ctx, ps.in(p, n));
-		GPLE_HIP(ctx, bs.in(b, 2 * n * num_pes));
-		GPLE_HIP(ctx, su.stage(surface, n, true, false));
-		GPLE_HIP(ctx, ss.stage(status, n, true, false));
-		const HopEnsemble e{num_pes, static_cast<long>(n), 0, 0, xs.p, ps.p, bs.p, su.p, ss.p};
-		GPLE_HIP(ctx, launch_hop_observe_groups(st, e, pes, static_cast<long>(n_groups), static_cast<long>(n_per_group), mass, work.p, o.p));
-		GPLE_HIP(ctx, o.back());
-		GPLE_HIP(ctx, hipStreamSynchronize(st));
-		return GPLE_OK;
-	}
-
-	/* ---- Ehrenfest (mean-field) trajectories ("Mean-field (Ehrenfest) trajectories") ------------------------------------------- */
-	// what the two evolve calls share: the checks of gple_hop_evolve that apply without a surface, a seed and an offset
-	static bool hop_mf_evolve_ok(double mass, size_t n_steps, double x_left, double x_right, unsigned flags, const double* x, const double* p, const double* b,
-		const int* status)
-	{
-		return hop_positive(mass) && std::isfinite(x_left) && std::isfinite(x_right) && x_left < x_right && n_steps <= (1ul << 40) && !(flags & GPLE_HOP_REVERSE) &&
-			x && p && b && status;
-	}
-
-	int gple_hop_evolve_mf(gple_ctx* ctx, int num_pes, int model, size_t n, double mass, double dt, size_t n_steps, double x_left, double x_right, unsigned flags,
-		double* x, double* p, double* b, int* status)
-	{
-		PesModel pes;
-		if (!ctx || !hop_size_ok(ctx, num_pes, model, n, 0, &pes) || !hop_positive(dt) || !hop_mf_evolve_ok(mass, n_steps, x_left, x_right, flags, x, p, b, status))
-			return GPLE_ERR_BAD_ARG;
-		GPLE_OPEN(ctx);
-		if (n_steps == 0) return GPLE_OK;
-		const bool dev = flags & GPLE_IO_DEVICE;
-		GPLE_CALL(ctx);
-		if (!pes_resolve(ctx, num_pes, model, &pes)) return GPLE_ERR_BAD_ARG; // under the call lock, which gple_pes_undefine takes: the table outlives the enqueue
-		hipStream_t st = ctx->stream;
-		Staged xs(ctx, dev), ps(ctx, dev), bs(ctx, dev);
-		StagedInts ss(ctx, dev);
-		GPLE_HIP(ctx, xs.inout(x, n));
-		GPLE_HIP(ctx, ps.inout(p, n));
-		GPLE_HIP(ctx, bs.inout(b, 2 * n * num_pes));
-		GPLE_HIP(ctx, ss.stage(status, n, true, true));
-		const HopEnsemble e{num_pes, static_cast<long>(n), 0, 0, xs.p, ps.p, bs.p, nullptr, ss.p};
-		timer_start(ctx, GPLE_TIMER_HOP_MF);
-		const hipError_t launched = launch_hop_evolve_mf(st, e, pes, mass, dt, static_cast<long>(n_steps), x_left, x_right);
-		timer_stop(ctx, GPLE_TIMER_HOP_MF); // on the error path too: no span stays open
-		GPLE_HIP(ctx, launched);
-		for (Staged* o : {&xs, &ps, &bs}) GPLE_HIP(ctx, o->back());
-		GPLE_HIP(ctx, ss.back());
-		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
-		return GPLE_OK;
-	}
-
-	int gple_hop_evolve_groups_mf(gple_ctx* ctx, int num_pes, int model, size_t n_groups, size_t n_per_group, double mass, const double* dt, size_t n_steps,
-		double x_left, double x_right, unsigned flags, double* x, double* p, double* b, int* status)
-	{
-		PesModel pes;
-		size_t n = 0;
-		if (!ctx || !hop_groups_ok(ctx, num_pes, model, n_groups, n_per_group, 0, &pes, &n) || !dt ||
-			!hop_mf_evolve_ok(mass, n_steps, x_left, x_right, flags, x, p, b, status))
-			return GPLE_ERR_BAD_ARG;
-		for (size_t g = 0; g < n_groups; ++g)
-			if (!hop_positive(dt[g])) return GPLE_ERR_BAD_ARG;
-		GPLE_OPEN(ctx);
-		if (n_steps == 0) return GPLE_OK;
-		const bool dev = flags & GPLE_IO_DEVICE;
-		GPLE_CALL(ctx);
-		if (!pes_resolve(ctx, num_pes, model, &pes)) return GPLE_ERR_BAD_ARG; // under the call lock, which gple_pes_undefine takes: the table outlives the enqueue
-		hipStream_t st = ctx->stream;
-		Staged xs(ctx, dev), ps(ctx, dev), bs(ctx, dev);
-		StagedInts ss(ctx, dev);
-		Scratch table(ctx);
-		GPLE_HIP(ctx, hop_table(table, dt, n_groups));
-		GPLE_HIP(ctx, xs.inout(x, n));
-		GPLE_HIP(ctx, ps.inout(p, n));
-		GPLE_HIP(ctx, bs.inout(b, 2 * n * num_pes));
-		GPLE_HIP(ctx, ss.stage(status, n, true, true));
-		const HopEnsemble e{num_pes, static_cast<long>(n), 0, 0, xs.p, ps.p, bs.p, nullptr, ss.p};
-		timer_start(ctx, GPLE_TIMER_HOP_MF);
-		const hipError_t launched = launch_hop_evolve_groups_mf(st, e, pes, static_cast<long>(n_per_group), mass, table.p, static_cast<long>(n_steps), x_left, x_right);
-		timer_stop(ctx, GPLE_TIMER_HOP_MF); // on the error path too: no span stays open
-		GPLE_HIP(ctx, launched);
-		for (Staged* o : {&xs, &ps, &bs}) GPLE_HIP(ctx, o->back());
-		GPLE_HIP(ctx, ss.back());
-		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
-		return GPLE_OK;
-	}
-
-	int gple_hop_observe_mf(gple_ctx* ctx, int num_pes, int model, size_t n, double mass, unsigned flags, const double* x, const double* p, const double* b,
-		const int* status, double* out)
-	{
-		PesModel pes;
-		if (!ctx || !hop_size_ok(ctx, num_pes, model, n, 0, &pes) || !hop_positive(mass) || !x || !p || !b || !status || !out) return GPLE_ERR_BAD_ARG;
-		GPLE_OPEN(ctx);
-		const bool dev = flags & GPLE_IO_DEVICE;
-		GPLE_CALL(ctx);
-		if (!pes_resolve(ctx, num_pes, model, &pes)) return GPLE_ERR_BAD_ARG; // under the call lock, which gple_pes_undefine takes: the table outlives the enqueue
-		hipStream_t st = ctx->stream;
-		Staged xs(ctx, dev), ps(ctx, dev), bs(ctx, dev), o(ctx, dev);
-		StagedInts ss(ctx, dev);
-		Scratch work(ctx);
-		GPLE_HIP(ctx, work.get(hop_observe_mf_work_doubles(num_pes, static_cast<long>(n))));
-		GPLE_HIP(ctx, o.out(out, 3 * num_pes + 6));
-		GPLE_HIP(ctx, xs.in(x, n));
-		GPLE_HIP(ctx, ps.in(p, n));
-		GPLE_HIP(ctx, bs.in(b, 2 * n * num_pes));
-		GPLE_HIP(ctx, ss.stage(status, n, true, false));
-		const HopEnsemble e{num_pes, static_cast<long>(n), 0, 0, xs.p, ps.p, bs.p, nullptr, ss.p};
-		GPLE_HIP(ctx, launch_hop_observe_mf(st, e, pes, mass, work.p, o.p));
-		GPLE_HIP(ctx, o.back());
-		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
-		return GPLE_OK;
-	}
-
-	int gple_hop_observe_groups_mf(gple_ctx* ctx, int num_pes, int model, size_t n_groups, size_t n_per_group, double mass, unsigned flags, const double* x,
-		const double* p, const double* b, const int* status, double* out)
-	{
-		PesModel pes;
-		size_t n = 0;
-		if (!ctx || !hop_groups_ok(ctx, num_pes, model, n_groups, n_per_group, 0, &pes, &n) || !hop_positive(mass) || !x || !p || !b || !status || !out)
-			return GPLE_ERR_BAD_ARG;
-		GPLE_OPEN(ctx);
-		const bool dev = flags & GPLE_IO_DEVICE;
-		GPLE_CALL(ctx);
-		if (!pes_resolve(ctx, num_pes, model, &pes)) return GPLE_ERR_BAD_ARG; // under the call lock, which gple_pes_undefine takes: the table outlives the enqueue
-		hipStream_t st = ctx->stream;
-		Staged xs(ctx, dev), ps(ctx, dev), bs(ctx, dev), o(ctx, false); // out is a host array whatever the flags say
-		StagedInts ss(ctx, dev);
-		Scratch work(ctx);
-		GPLE_HIP(ctx, work.get(hop_observe_groups_mf_work_doubles(num_pes, static_cast<long>(n_groups), static_cast<long>(n_per_group))));
-		GPLE_HIP(ctx, o.out(out, n_groups * (3 * num_pes + 6)));
-		GPLE_HIP(ctx, xs.in(x, n));
-		GPLE_HIP(ctx, ps.in(p, n));
-		GPLE_HIP(ctx, bs.in(b, 2 * n * num_pes));
-		GPLE_HIP(ctx, ss.stage(status, n, true, false));
-		const HopEnsemble e{num_pes, static_cast<long>(n), 0, 0, xs.p, ps.p, bs.p, nullptr, ss.p};
-		GPLE_HIP(ctx, launch_hop_observe_groups_mf(st, e, pes, static_cast<long>(n_groups), static_cast<long>(n_per_group), mass, work.p, o.p));
-		GPLE_HIP(ctx, o.back());
-		GPLE_HIP(ctx, hipStreamSynchronize(st));
-		return GPLE_OK;
-	}
-
-	/* ---- symmetrical quasi-classical trajectories ("Symmetrical quasi-classical trajectories") -------------------------------- */
-	// gamma of the step, where no window is named: finite and not negative
-	static bool hop_sqc_gamma_ok(double gamma) { return std::isfinite(gamma) && gamma >= 0.0; }
-	// window is a GPLE_HOP_WINDOW_* and gamma fits it: the square windows are disjoint for 0 < gamma < 1/2 only
-	static bool hop_sqc_window_ok(int window, double gamma)
-	{
-		if (window != GPLE_HOP_WINDOW_SQUARE && window != GPLE_HOP_WINDOW_TRIANGLE) return false;
-		return hop_sqc_gamma_ok(gamma) && (window != GPLE_HOP_WINDOW_SQUARE || (gamma > 0.0 && gamma < 0.5));
-	}
-
-	int gple_hop_sample_sqc(gple_ctx* ctx, int num_pes, int model, size_t n, size_t trajectory_offset, unsigned long long seed, double x0, double p0,
-		double sigma_x, double sigma_p, int surface0, int window, double gamma, unsigned flags, double* x, double* p, double* b, int* surface, int* status)
-	{
-		PesModel pes;
-		if (!ctx || !hop_size_ok(ctx, num_pes, model, n, trajectory_offset, &pes) || !hop_positive(sigma_x) || !hop_positive(sigma_p) || surface0 < 0 ||
-			surface0 >= num_pes || !hop_sqc_window_ok(window, gamma) || (flags & GPLE_HOP_REVERSE) || !x || !p || !b || !surface || !status)
-			return GPLE_ERR_BAD_ARG;
-		GPLE_OPEN(ctx);
-		const bool dev = flags & GPLE_IO_DEVICE;
-		GPLE_CALL(ctx);
-		if (!pes_resolve(ctx, num_pes, model, &pes)) return GPLE_ERR_BAD_ARG; // under the call lock, which gple_pes_undefine takes: the table outlives the enqueue
-		hipStream_t st = ctx->stream;
-		Staged xs(ctx, dev), ps(ctx, dev), bs(ctx, dev);
-		StagedInts su(ctx, dev), ss(ctx, dev);
-		GPLE_HIP(ctx, xs.out(x, n));
-		GPLE_HIP(ctx, ps.out(p, n));
-		GPLE_HIP(ctx, bs.out(b, 2 * n * num_pes));
-		GPLE_HIP(ctx, su.stage(surface, n, false, true));
-		GPLE_HIP(ctx, ss.stage(status, n, false, true));
-		const HopEnsemble e{num_pes, static_cast<long>(n), trajectory_offset, seed, xs.p, ps.p, bs.p, su.p, ss.p};
-		GPLE_HIP(ctx, launch_hop_sample_sqc(st, e, pes, x0, p0, sigma_x, sigma_p, surface0, window, gamma));
-		for (Staged* o : {&xs, &ps, &bs}) GPLE_HIP(ctx, o->back());
-		for (StagedInts* o : {&su, &ss}) GPLE_HIP(ctx, o->back());
-		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
-		return GPLE_OK;
-	}
-
-	int gple_hop_sample_groups_sqc(gple_ctx* ctx, int num_pes, int model, size_t n_groups, size_t n_per_group, size_t trajectory_offset,
-		unsigned long long seed, const double* packets, int surface0, int window, double gamma, unsigned flags, double* x, double* p, double* b,
-		int* surface, int* status)
-	{
-		PesModel pes;
-		size_t n = 0;
-		if (!ctx || !hop_groups_ok(ctx, num_pes, model, n_groups, n_per_group, trajectory_offset, &pes, &n) || !packets || surface0 < 0 || surface0 >= num_pes ||
-			!hop_sqc_window_ok(window, gamma) || (flags & GPLE_HOP_REVERSE) || !x || !p || !b || !surface || !status)
-			return GPLE_ERR_BAD_ARG;
-		for (size_t g = 0; g < n_groups; ++g)
-		{
-			const double* row = packets + 4 * g;
-			if (!std::isfinite(row[0]) || !std::isfinite(row[1]) || !std::isfinite(row[2]) || !std::isfinite(row[3]) || row[2] < 0.0 || row[3] < 0.0) return GPLE_ERR_BAD_ARG;
-		}
-		GPLE_OPEN(ctx);
-		const bool dev = flags & GPLE_IO_DEVICE;
-		GPLE_CALL(ctx);
-		if (!pes_resolve(ctx, num_pes, model, &pes)) return GPLE_ERR_BAD_ARG; // under the call lock, which gple_pes_undefine takes: the table outlives the enqueue
-		hipStream_t st = ctx->stream;
-		Staged xs(ctx, dev), ps(ctx, dev), bs(ctx, dev);
-		StagedInts su(ctx, dev), ss(ctx, dev);
-		Scratch table(ctx);
-		GPLE_HIP(ctx, hop_table(table, packets, 4 * n_groups));
-		GPLE_HIP(ctx, xs.out(x, n));
-		GPLE_HIP(ctx, ps.out(p, n));
-		GPLE_HIP(ctx, bs.out(b, 2 * n * num_pes));
-		GPLE_HIP(ctx, su.stage(surface, n, false, true));
-		GPLE_HIP(ctx, ss.stage(status, n, false, true));
-		const HopEnsemble e{num_pes, static_cast<long>(n), trajectory_offset, seed, xs.p, ps.p, bs.p, su.p, ss.p};
-		GPLE_HIP(ctx, launch_hop_sample_groups_sqc(st, e, pes, static_cast<long>(n_per_group), table.p, surface0, window, gamma));
-		for (Staged* o : {&xs, &ps, &bs}) GPLE_HIP(ctx, o->back());
-		for (StagedInts* o : {&su, &ss}) GPLE_HIP(ctx, o->back());
-		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
-		return GPLE_OK;
-	}
-
-	int gple_hop_evolve_sqc(gple_ctx* ctx, int num_pes, int model, size_t n, double mass, double dt, size_t n_steps, double x_left, double x_right, double gamma,
-		unsigned flags, double* x, double* p, double* b, int* status)
-	{
-		PesModel pes;
-		if (!ctx || !hop_size_ok(ctx, num_pes, model, n, 0, &pes) || !hop_positive(dt) || !hop_mf_evolve_ok(mass, n_steps, x_left, x_right, flags, x, p, b, status) ||
-			!hop_sqc_gamma_ok(gamma))
-			return GPLE_ERR_BAD_ARG;
-		GPLE_OPEN(ctx);
-		if (n_steps == 0) return GPLE_OK;
-		const bool dev = flags & GPLE_IO_DEVICE;
-		GPLE_CALL(ctx);
-		if (!pes_resolve(ctx, num_pes, model, &pes)) return GPLE_ERR_BAD_ARG; // under the call lock, which gple_pes_undefine takes: the table outlives the enqueue
-		hipStream_t st = ctx->stream;
-		Staged xs(ctx, dev), ps(ctx, dev), bs(ctx, dev);
-		StagedInts ss(ctx, dev);
-		GPLE_HIP(ctx, xs.inout(x, n));
-		GPLE_HIP(ctx, ps.inout(p, n));
-		GPLE_HIP(ctx, bs.inout(b, 2 * n * num_pes));
-		GPLE_HIP(ctx, ss.stage(status, n, true, true));
-		const HopEnsemble e{num_pes, static_cast<long>(n), 0, 0, xs.p, ps.p, bs.p, nullptr, ss.p};
-		timer_start(ctx, GPLE_TIMER_HOP_SQC);
-		const hipError_t launched = launch_hop_evolve_sqc(st, e, pes, mass, dt, static_cast<long>(n_steps), x_left, x_right, gamma);
-		timer_stop(ctx, GPLE_TIMER_HOP_SQC); // on the error path too: no span stays open
-		GPLE_HIP(ctx, launched);
-		for (Staged* o : {&xs, &ps, &bs}) GPLE_HIP(ctx, o->back());
-		GPLE_HIP(ctx, ss.back());
-		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
-		return GPLE_OK;
-	}
-
-	int gple_hop_evolve_groups_sqc(gple_ctx* ctx, int num_pes, int model, size_t n_groups, size_t n_per_group, double mass, const double* dt, size_t n_steps,
-		double x_left, double x_right, double gamma, unsigned flags, double* x, double* p, double* b, int* status)
-	{
-		PesModel pes;
-		size_t n = 0;
-		if (!ctx || !hop_groups_ok(ctx, num_pes, model, n_groups, n_per_group, 0, &pes, &n) || !dt ||
-			!hop_mf_evolve_ok(mass, n_steps, x_left, x_right, flags, x, p, b, status) || !hop_sqc_gamma_ok(gamma))
-			return GPLE_ERR_BAD_ARG;
-		for (size_t g = 0; g < n_groups; ++g)
-			if (!hop_positive(dt[g])) return GPLE_ERR_BAD_ARG;
-		GPLE_OPEN(ctx);
-		if (n_steps == 0) return GPLE_OK;
-		const bool dev = flags & GPLE_IO_DEVICE;
-		GPLE_CALL(ctx);
-		if (!pes_resolve(ctx, num_pes, model, &pes)) return GPLE_ERR_BAD_ARG; // under the call lock, which gple_pes_undefine takes: the table outlives the enqueue
-		hipStream_t st = ctx->stream;
-		Staged xs(ctx, dev), ps(ctx, dev), bs(ctx, dev);
-		StagedInts ss(ctx, dev);
-		Scratch table(ctx);
-		GPLE_HIP(ctx, hop_table(table, dt, n_groups));
-		GPLE_HIP(ctx, xs.inout(x, n));
-		GPLE_HIP(ctx, ps.inout(p, n));
-		GPLE_HIP(ctx, bs.inout(b, 2 * n * num_pes));
-		GPLE_HIP(ctx, ss.stage(status, n, true, true));
-		const HopEnsemble e{num_pes, static_cast<long>(n), 0, 0, xs.p, ps.p, bs.p, nullptr, ss.p};
-		timer_start(ctx, GPLE_TIMER_HOP_SQC);
-		const hipError_t launched =
-			launch_hop_evolve_groups_sqc(st, e, pes, static_cast<long>(n_per_group), mass, table.p, static_cast<long>(n_steps), x_left, x_right, gamma);
-		timer_stop(ctx, GPLE_TIMER_HOP_SQC); // on the error path too: no span stays open
-		GPLE_HIP(ctx, launched);
-		for (Staged* o : {&xs, &ps, &bs}) GPLE_HIP(ctx, o->back());
-		GPLE_HIP(ctx, ss.back());
-		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
-		return GPLE_OK;
-	}
-
-	int gple_hop_observe_sqc(gple_ctx* ctx, int num_pes, int model, size_t n, double mass, int window, double gamma, unsigned flags, const double* x,
-		const double* p, const double* b, const int* status, double* out)
-	{
-		PesModel pes;
-		if (!ctx || !hop_size_ok(ctx, num_pes, model, n, 0, &pes) || !hop_positive(mass) || !hop_sqc_window_ok(window, gamma) || (flags & GPLE_HOP_REVERSE) || !x || !p ||
-			!b || !status || !out)
-			return GPLE_ERR_BAD_ARG;
-		GPLE_OPEN(ctx);
-		const bool dev = flags & GPLE_IO_DEVICE;
-		GPLE_CALL(ctx);
-		if (!pes_resolve(ctx, num_pes, model, &pes)) return GPLE_ERR_BAD_ARG; // under the call lock, which gple_pes_undefine takes: the table outlives the enqueue
-		hipStream_t st = ctx->stream;
-		Staged xs(ctx, dev), ps(ctx, dev), bs(ctx, dev), o(ctx, dev);
-		StagedInts ss(ctx, dev);
-		Scratch work(ctx);
-		GPLE_HIP(ctx, work.get(hop_observe_sqc_work_doubles(num_pes, static_cast<long>(n))));
-		GPLE_HIP(ctx, o.out(out, 4 * num_pes + 9));
-		GPLE_HIP(ctx, xs.in(x, n));
-		GPLE_HIP(ctx, ps.in(p, n));
-		GPLE_HIP(ctx, bs.in(b, 2 * n * num_pes));
-		GPLE_HIP(ctx, ss.stage(status, n, true, false));
-		const HopEnsemble e{num_pes, static_cast<long>(n), 0, 0, xs.p, ps.p, bs.p, nullptr, ss.p};
-		GPLE_HIP(ctx, launch_hop_observe_sqc(st, e, pes, mass, window, gamma, work.p, o.p));
-		GPLE_HIP(ctx, o.back());
-		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
-		return GPLE_OK;
-	}
-
-	int gple_hop_observe_groups_sqc(gple_ctx* ctx, int num_pes, int model, size_t n_groups, size_t n_per_group, double mass, int window, double gamma,
-		unsigned flags, const double* x, const double* p, const double* b, const int* status, double* out)
-	{
-		PesModel pes;
-		size_t n = 0;
-		if (!ctx || !hop_groups_ok(ctx, num_pes, model, n_groups, n_per_group, 0, &pes, &n) || !hop_positive(mass) || !hop_sqc_window_ok(window, gamma) ||
-			(flags & GPLE_HOP_REVERSE) || !x || !p || !b || !status || !out)
-			return GPLE_ERR_BAD_ARG;
-		GPLE_OPEN(ctx);
-		const bool dev = flags & GPLE_IO_DEVICE;
-		GPLE_CALL(ctx);
-		if (!pes_resolve(ctx, num_pes, model, &pes)) return GPLE_ERR_BAD_ARG; // under the call lock, which gple_pes_undefine takes: the table outlives the enqueue
-		hipStream_t st = ctx->stream;
-		Staged xs(ctx, dev), ps(ctx, dev), bs(ctx, dev), o(ctx, false); // out is a host array whatever the flags say
-		StagedInts ss(ctx, dev);
-		Scratch work(ctx);
-		GPLE_HIP(ctx, work.get(hop_observe_groups_sqc_work_doubles(num_pes, static_cast<long>(n_groups), static_cast<long>(n_per_group))));
-		GPLE_HIP(ctx, o.out(out, n_groups * (4 * num_pes + 9)));
-		GPLE_HIP(ctx, xs.in(x, n));
-		GPLE_HIP(ctx, ps.in(p, n));
-		GPLE_HIP(ctx, bs.in(b, 2 * n * num_pes));
-		GPLE_HIP(ctx, ss.stage(status, n, true, false));
-		const HopEnsemble e{num_pes, static_cast<long>(n), 0, 0, xs.p, ps.p, bs.p, nullptr, ss.p};
-		GPLE_HIP(ctx, launch_hop_observe_groups_sqc(st, e, pes, static_cast<long>(n_groups), static_cast<long>(n_per_group), mass, window, gamma, work.p, o.p));
-		GPLE_HIP(ctx, o.back());
-		GPLE_HIP(ctx, hipStreamSynchronize(st));
-		return GPLE_OK;
-	}
-
-	/* ---- MASH trajectories ("MASH trajectories") -------------------------------------------------------------------------------- */
-	// what the four calls share beyond the checks of their models: two levels, no GPLE_HOP_REVERSE (MASH always reflects), five arrays
-	static bool hop_mash_ok(int num_pes, unsigned flags, const double* x, const double* p, const double* b, const int* surface, const int* status)
-	{
-		return num_pes == 2 && !(flags & GPLE_HOP_REVERSE) && x && p && b && surface && status;
-	}
-
-	int gple_hop_sample_mash(gple_ctx* ctx, int num_pes, int model, size_t n, size_t trajectory_offset, unsigned long long seed, double x0, double p0,
-		double sigma_x, double sigma_p, int surface0, unsigned flags, double* x, double* p, double* b, int* surface, int* status)
-	{
-		PesModel pes;
-		if (!ctx || !hop_mash_ok(num_pes, flags, x, p, b, surface, status) || !hop_size_ok(ctx, num_pes, model, n, trajectory_offset, &pes) || !hop_positive(sigma_x) ||
-			!hop_positive(sigma_p) || surface0 < 0 || surface0 >= num_pes)
-			return GPLE_ERR_BAD_ARG;
-		GPLE_OPEN(ctx);
-		const bool dev = flags & GPLE_IO_DEVICE;
-		GPLE_CALL(ctx);
-		if (!pes_resolve(ctx, num_pes, model, &pes)) return GPLE_ERR_BAD_ARG; // under the call lock, which gple_pes_undefine takes: the table outlives the enqueue
-		hipStream_t st = ctx->stream;
-		Staged xs(ctx, dev), ps(ctx, dev), bs(ctx, dev);
-		StagedInts su(ctx, dev), ss(ctx, dev);
-		GPLE_HIP(ctx, xs.out(x, n));
-		GPLE_HIP(ctx, ps.out(p, n));
-		GPLE_HIP(ctx, bs.out(b, 2 * n * num_pes));
-		GPLE_HIP(ctx, su.stage(surface, n, false, true));
-		GPLE_HIP(ctx, ss.stage(status, n, false, true));
-		const HopEnsemble e{num_pes, static_cast<long>(n), trajectory_offset, seed, xs.p, ps.p, bs.p, su.p, ss.p};
-		GPLE_HIP(ctx, launch_hop_sample_mash(st, e, pes, x0, p0, sigma_x, sigma_p, surface0));
-		for (Staged* o : {&xs, &ps, &bs}) GPLE_HIP(ctx, o->back());
-		for (StagedInts* o : {&su, &ss}) GPLE_HIP(ctx, o->back());
-		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
-		return GPLE_OK;
-	}
-
-	int gple_hop_sample_groups_mash(gple_ctx* ctx, int num_pes, int model, size_t n_groups, size_t n_per_group, size_t trajectory_offset,
-		unsigned long long seed, const double* packets, int surface0, unsigned flags, double* x, double* p, double* b, int* surface, int* status)
-	{
-		PesModel pes;
-		size_t n = 0;
-		if (!ctx || !hop_mash_ok(num_pes, flags, x, p, b, surface, status) ||
-			!hop_groups_ok(ctx, num_pes, model, n_groups, n_per_group, trajectory_offset, &pes, &n) || !packets || surface0 < 0 || surface0 >= num_pes)
-			return GPLE_ERR_BAD_ARG;
-		for (size_t g = 0; g < n_groups; ++g)
-		{
-			const double* row = packets + 4 * g;
-			if (!std::isfinite(row[0]) || !std::isfinite(row[1]) || !std::isfinite(row[2]) || !std::isfinite(row[3]) || row[2] < 0.0 || row[3] < 0.0) return GPLE_ERR_BAD_ARG;
-		}
-		GPLE_OPEN(ctx);
-		const bool dev = flags & GPLE_IO_DEVICE;
-		GPLE_CALL(ctx);
-		if (!pes_resolve(ctx, num_pes, model, &pes)) return GPLE_ERR_BAD_ARG; // under the call lock, which gple_pes_undefine takes: the table outlives the enqueue
-		hipStream_t st = ctx->stream;
-		Staged xs(ctx, dev), ps(ctx, dev), bs(ctx, dev);
-		StagedInts su(ctx, dev), ss(ctx, dev);
-		Scratch table(ctx);
-		GPLE_HIP(ctx, hop_table(table, packets, 4 * n_groups));
-		GPLE_HIP(ctx, xs.out(x, n));
-		GPLE_HIP(ctx, ps.out(p, n));
-		GPLE_HIP(ctx, bs.out(b, 2 * n * num_pes));
-		GPLE_HIP(ctx, su.stage(surface, n, false, true));
-		GPLE_HIP(ctx, ss.stage(status, n, false, true));
-		const HopEnsemble e{num_pes, static_cast<long>(n), trajectory_offset, seed, xs.p, ps.p, bs.p, su.p, ss.p};
-		GPLE_HIP(ctx, launch_hop_sample_groups_mash(st, e, pes, static_cast<long>(n_per_group), table.p, surface0));
-		for (Staged* o : {&xs, &ps, &bs}) GPLE_HIP(ctx, o->back());
-		for (StagedInts* o : {&su, &ss}) GPLE_HIP(ctx, o->back());
-		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
-		return GPLE_OK;
-	}
-
-	int gple_hop_evolve_mash(gple_ctx* ctx, int num_pes, int model, size_t n, double mass, double dt, size_t n_steps, double x_left, double x_right,
-		unsigned flags, double* x, double* p, double* b, int* surface, int* status)
-	{
-		PesModel pes;
-		if (!ctx || !hop_mash_ok(num_pes, flags, x, p, b, surface, status) || !hop_size_ok(ctx, num_pes, model, n, 0, &pes) || !hop_positive(dt) ||
-			!hop_mf_evolve_ok(mass, n_steps, x_left, x_right, flags, x, p, b, status))
-			return GPLE_ERR_BAD_ARG;
-		GPLE_OPEN(ctx);
-		if (n_steps == 0) return GPLE_OK;
-		const bool dev = flags & GPLE_IO_DEVICE;
-		GPLE_CALL(ctx);
-		if (!pes_resolve(ctx, num_pes, model, &pes)) return GPLE_ERR_BAD_ARG; // under the call lock, which gple_pes_undefine takes: the table outlives the enqueue
-		hipStream_t st = ctx->stream;
-		Staged xs(ctx, dev), ps(ctx, dev), bs(ctx, dev);
-		StagedInts su(ctx, dev), ss(ctx, dev);
-		GPLE_HIP(ctx, xs.inout(x, n));
-		GPLE_HIP(ctx, ps.inout(p, n));
-		GPLE_HIP(ctx, bs.inout(b, 2 * n * num_pes));
-		GPLE_HIP(ctx, su.stage(surface, n, true, true));
-		GPLE_HIP(ctx, ss.stage(status, n, true, true));
-		const HopEnsemble e{num_pes, static_cast<long>(n), 0, 0, xs.p, ps.p, bs.p, su.p, ss.p};
-		timer_start(ctx, GPLE_TIMER_HOP_MASH);
-		const hipError_t launched = launch_hop_evolve_mash(st, e, pes, mass, dt, static_cast<long>(n_steps), x_left, x_right);
-		timer_stop(ctx, GPLE_TIMER_HOP_MASH); // on the error path too: no span stays open
-		GPLE_HIP(ctx, launched);
-		for (Staged* o : {&xs, &ps, &bs}) GPLE_HIP(ctx, o->back());
-		for (StagedInts* o : {&su, &ss}) GPLE_HIP(ctx, o->back());
-		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
-		return GPLE_OK;
-	}
-
-	int gple_hop_evolve_groups_mash(gple_ctx* ctx, int num_pes, int model, size_t n_groups, size_t n_per_group, double mass, const double* dt,
-		size_t n_steps, double x_left, double x_right, unsigned flags, double* x, double* p, double* b, int* surface, int* status, int* hops)
-	{
-		PesModel pes;
-		size_t n = 0;
-		if (!ctx || !hop_mash_ok(num_pes, flags, x, p, b, surface, status) || !hop_groups_ok(ctx, num_pes, model, n_groups, n_per_group, 0, &pes, &n) || !dt ||
-			!hop_mf_evolve_ok(mass, n_steps, x_left, x_right, flags, x, p, b, status))
-			return GPLE_ERR_BAD_ARG;
-		for (size_t g = 0; g < n_groups; ++g)
-			if (!hop_positive(dt[g])) return GPLE_ERR_BAD_ARG;
-		GPLE_OPEN(ctx);
-		if (n_steps == 0) return GPLE_OK;
-		const bool dev = flags & GPLE_IO_DEVICE;
-		GPLE_CALL(ctx);
-		if (!pes_resolve(ctx, num_pes, model, &pes)) return GPLE_ERR_BAD_ARG; // under the call lock, which gple_pes_undefine takes: the table outlives the enqueue
-		hipStream_t st = ctx->stream;
-		Staged xs(ctx, dev), ps(ctx, dev), bs(ctx, dev);
-		StagedInts su(ctx, dev), ss(ctx, dev), hs(ctx, dev);
-		Scratch table(ctx);
-		GPLE_HIP(ctx, hop_table(table, dt, n_groups));
-		GPLE_HIP(ctx, xs.inout(x, n));
-		GPLE_HIP(ctx, ps.inout(p, n));
-		GPLE_HIP(ctx, bs.inout(b, 2 * n * num_pes));
-		GPLE_HIP(ctx, su.stage(surface, n, true, true));
-		GPLE_HIP(ctx, ss.stage(status, n, true, true));
-		if (hops) GPLE_HIP(ctx, hs.stage(hops, 2 * n, true, true));
-		const HopEnsemble e{num_pes, static_cast<long>(n), 0, 0, xs.p, ps.p, bs.p, su.p, ss.p};
-		timer_start(ctx, GPLE_TIMER_HOP_MASH);
-		const hipError_t launched =
-			launch_hop_evolve_groups_mash(st, e, pes, static_cast<long>(n_per_group), mass, table.p, static_cast<long>(n_steps), x_left, x_right, hs.p);
-		timer_stop(ctx, GPLE_TIMER_HOP_MASH); // on the error path too: no span stays open
-		GPLE_HIP(ctx, launched);
-		for (Staged* o : {&xs, &ps, &bs}) GPLE_HIP(ctx, o->back());
-		for (StagedInts* o : {&su, &ss, &hs}) GPLE_HIP(ctx, o->back());
-		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
-		return GPLE_OK;
-	}
 }

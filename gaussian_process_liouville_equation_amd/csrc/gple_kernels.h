@@ -417,7 +417,7 @@ namespace gple
 	hipError_t launch_mqcl_observe(hipStream_t s, int num_pes, int n, const double* tables, const double* x, const double* p, double mass, double dxdp,
 		const double* rho, double* adia, double* work, double* out);
 
-	// ---- fewest-switches surface hopping (gple_hop.hip): num_pes = 2 or 3, one thread per trajectory, every pointer a device pointer ----
+	// ---- trajectory ensembles (gple_hop.hip): num_pes = 2 or 3, one thread per trajectory, every pointer a device pointer ----
 	struct HopEnsemble // x, p: n doubles; b: n x num_pes (re, im) pairs; surface, status: n ints; counters use the index offset + i
 	{
 		int num_pes;
@@ -426,37 +426,32 @@ namespace gple
 		double *x, *p, *b;
 		int *surface, *status;
 	};
+	// Fewest switches.  Grouped ensembles ("A curve in one launch"): e.n = n_groups n_per_group, trajectory i belongs to group
+	// i / n_per_group.  packets: n_groups rows (x0, p0, sigma_x, sigma_p), a sigma of exactly 0 gives the centre exactly; dt: n_groups time
+	// steps; hops (nullable): n x 2 ints, the hops taken and the frustrated hops of the call are added.
+	// decoherence ("Decoherence corrections") is a GPLE_HOP_DC_* of include/gple.h: NONE launches the kernels without step 6a,
+	// 1 ... 3 the instantiations with it, which read the mode (wave-uniform) at run time; edc_c is read in mode 1 only
 	hipError_t launch_hop_sample(hipStream_t s, const HopEnsemble& e, PesModel model, double x0, double p0, double sigma_x, double sigma_p, int surface0);
-	hipError_t launch_hop_evolve(hipStream_t s, const HopEnsemble& e, PesModel model, double mass, double dt, unsigned long long first_step, long n_steps,
-		double x_left, double x_right, bool reverse);
-	// out: 4 num_pes + 3 sums (include/gple.h), from one partial row per wave of the first stage in work (hop_observe_work_doubles)
-	size_t hop_observe_work_doubles(int num_pes, long n);
-	hipError_t launch_hop_observe(hipStream_t s, const HopEnsemble& e, PesModel model, double mass, double* work, double* out);
-	// Grouped ensembles ("A curve in one launch"): e.n = n_groups n_per_group, trajectory i belongs to group i / n_per_group.
-	// packets: n_groups rows (x0, p0, sigma_x, sigma_p), a sigma of exactly 0 gives the centre exactly; dt: n_groups time steps; hops (nullable):
-	// n x 2 ints, the hops taken and the frustrated hops of the call are added
 	hipError_t launch_hop_sample_groups(hipStream_t s, const HopEnsemble& e, PesModel model, long n_per_group, const double* packets, int surface0);
+	hipError_t launch_hop_evolve(hipStream_t s, const HopEnsemble& e, PesModel model, double mass, double dt, unsigned long long first_step, long n_steps,
+		double x_left, double x_right, bool reverse, int decoherence = GPLE_HOP_DC_NONE, double edc_c = 0.0);
 	hipError_t launch_hop_evolve_groups(hipStream_t s, const HopEnsemble& e, PesModel model, long n_per_group, double mass, const double* dt, unsigned long long first_step,
-		long n_steps, double x_left, double x_right, bool reverse, int* hops);
-	// The step with a decoherence correction ("Decoherence corrections"): decoherence is a GPLE_HOP_DC_* of include/gple.h;
-	// 0 launches the kernels of the two calls above, 1 ... 3 the instantiations with step 6a, which read the mode (wave-uniform) at run time;
-	// edc_c is read in mode 1 only
-	hipError_t launch_hop_evolve_dc(hipStream_t s, const HopEnsemble& e, PesModel model, double mass, double dt, unsigned long long first_step, long n_steps,
-		double x_left, double x_right, bool reverse, int decoherence, double edc_c);
-	hipError_t launch_hop_evolve_groups_dc(hipStream_t s, const HopEnsemble& e, PesModel model, long n_per_group, double mass, const double* dt,
-		unsigned long long first_step, long n_steps, double x_left, double x_right, bool reverse, int* hops, int decoherence, double edc_c);
-	// out: n_groups rows of 4 num_pes + 3 sums, row g with the bits of launch_hop_observe on the group alone; every group has workgroups of its own
-	size_t hop_observe_groups_work_doubles(int num_pes, long n_groups, long n_per_group);
+		long n_steps, double x_left, double x_right, bool reverse, int* hops, int decoherence = GPLE_HOP_DC_NONE, double edc_c = 0.0);
+	// The sums of include/gple.h, per method hop_observe*_width(num_pes) of them: out is one row of sums, from one partial row per wave of the first
+	// stage in work (hop_observe_work_doubles(width, 1, n)); the grouped forms give n_groups rows, row g with the bits of the plain launch on the
+	// group alone (every group has workgroups of its own), from hop_observe_work_doubles(width, n_groups, n_per_group) of work
+	constexpr int hop_observe_width(int num_pes) { return 4 * num_pes + 3; }
+	constexpr int hop_observe_mf_width(int num_pes) { return 3 * num_pes + 6; }
+	constexpr int hop_observe_sqc_width(int num_pes) { return 4 * num_pes + 9; }
+	size_t hop_observe_work_doubles(int width, long n_groups, long n_per_group);
+	hipError_t launch_hop_observe(hipStream_t s, const HopEnsemble& e, PesModel model, double mass, double* work, double* out);
 	hipError_t launch_hop_observe_groups(hipStream_t s, const HopEnsemble& e, PesModel model, long n_groups, long n_per_group, double mass, double* work, double* out);
 	// Ehrenfest (mean-field) trajectories ("Mean-field (Ehrenfest) trajectories"): of the ensemble only x, p, b and status are read or
 	// written (surface may be null; offset and seed are not used).  The force is b^dagger Fd b, the amplitudes move as in launch_hop_evolve
 	hipError_t launch_hop_evolve_mf(hipStream_t s, const HopEnsemble& e, PesModel model, double mass, double dt, long n_steps, double x_left, double x_right);
 	hipError_t launch_hop_evolve_groups_mf(hipStream_t s, const HopEnsemble& e, PesModel model, long n_per_group, double mass, const double* dt, long n_steps,
 		double x_left, double x_right);
-	// out: 3 num_pes + 6 sums (include/gple.h), the tree of launch_hop_observe at that width; the grouped form has n_groups such rows
-	size_t hop_observe_mf_work_doubles(int num_pes, long n);
 	hipError_t launch_hop_observe_mf(hipStream_t s, const HopEnsemble& e, PesModel model, double mass, double* work, double* out);
-	size_t hop_observe_groups_mf_work_doubles(int num_pes, long n_groups, long n_per_group);
 	hipError_t launch_hop_observe_groups_mf(hipStream_t s, const HopEnsemble& e, PesModel model, long n_groups, long n_per_group, double mass, double* work, double* out);
 	// Symmetrical quasi-classical trajectories ("Symmetrical quasi-classical trajectories"): window is a GPLE_HOP_WINDOW_* of
 	// include/gple.h, gamma the zero-point parameter.  The samples write all five arrays (surface = surface0); the step and the sums read and
@@ -468,10 +463,7 @@ namespace gple
 	hipError_t launch_hop_evolve_sqc(hipStream_t s, const HopEnsemble& e, PesModel model, double mass, double dt, long n_steps, double x_left, double x_right, double gamma);
 	hipError_t launch_hop_evolve_groups_sqc(hipStream_t s, const HopEnsemble& e, PesModel model, long n_per_group, double mass, const double* dt, long n_steps,
 		double x_left, double x_right, double gamma);
-	// out: 4 num_pes + 9 sums (include/gple.h), the tree of launch_hop_observe at that width; the grouped form has n_groups such rows
-	size_t hop_observe_sqc_work_doubles(int num_pes, long n);
 	hipError_t launch_hop_observe_sqc(hipStream_t s, const HopEnsemble& e, PesModel model, double mass, int window, double gamma, double* work, double* out);
-	size_t hop_observe_groups_sqc_work_doubles(int num_pes, long n_groups, long n_per_group);
 	hipError_t launch_hop_observe_groups_sqc(hipStream_t s, const HopEnsemble& e, PesModel model, long n_groups, long n_per_group, double mass, int window, double gamma,
 		double* work, double* out);
 	// MASH trajectories ("MASH trajectories"): two levels only (any other num_pes is hipErrorInvalidValue).  The ensemble is the
