@@ -26,6 +26,7 @@ TIMER_HOP_GROUPS = 14  # gple_timer: the step kernel of one gple_hop_evolve_grou
 TIMER_HOP_MF = 15  # gple_timer: the step kernel of one gple_hop_evolve_mf or gple_hop_evolve_groups_mf call
 TIMER_HOP_SQC = 16  # gple_timer: the step kernel of one gple_hop_evolve_sqc or gple_hop_evolve_groups_sqc call
 TIMER_HOP_MASH = 17  # gple_timer: the step kernel of one gple_hop_evolve_mash or gple_hop_evolve_groups_mash call
+TIMER_HOP_BIN_MF = 18  # gple_timer: the bin kernel of one gple_hop_bin_mf call
 HOP_MAX_GROUPS = 65536  # GPLE_HOP_MAX_GROUPS
 # GPLE_HOP_WINDOW_*: the windows of the symmetrical quasi-classical trajectories, the names Api.hop_sample_sqc / hop_observe_sqc take for them, and
 # the customary zero-point parameter gamma of each
@@ -386,6 +387,8 @@ def _signatures():
         "hop_evolve_groups_mf": (st, [CTX, i, i, sz, sz, d, _dp, sz, d, d, u, _dp, _dp, _dp, ip]),
         "hop_observe_mf": (st, [CTX, i, i, sz, d, u, _dp, _dp, _dp, ip, _dp]),
         "hop_observe_groups_mf": (st, [CTX, i, i, sz, sz, d, u, _dp, _dp, _dp, ip, _dp]),
+        "hop_bin_mf": (st, [CTX, i, i, sz, d, d, sz, d, d, sz, u, _dp, _dp, _dp, ip, llp]),
+        "hop_density_mf": (st, [CTX, i, sz, sz, d, d, sz, u, llp, _dp]),
         # symmetrical quasi-classical trajectories
         "hop_sample_sqc": (st, [CTX, i, i, sz, sz, ull, d, d, d, d, i, i, d, u, _dp, _dp, _dp, ip, ip]),
         "hop_sample_groups_sqc": (st, [CTX, i, i, sz, sz, sz, ull, _dp, i, i, d, u, _dp, _dp, _dp, ip, ip]),
@@ -580,7 +583,7 @@ class Api:
         11 = the device work of dvr_spectrum, 12 = the step kernel of hop_evolve, 13 = the bin kernel of hop_bin,
         14 = the step kernel of hop_evolve_groups (12 and 14 also with a decoherence correction), 15 = the step kernel of hop_evolve_mf and
         hop_evolve_groups_mf, 16 = the step kernel of hop_evolve_sqc and hop_evolve_groups_sqc, 17 = the step kernel of hop_evolve_mash and
-        hop_evolve_groups_mash."""
+        hop_evolve_groups_mash, 18 = the bin kernel of hop_bin_mf."""
         last, total, count = C.c_double(), C.c_double(), C.c_long()
         self._check(self.lib.gple_ctx_get_timing(self.ctx, which, C.byref(last), C.byref(total), C.byref(count)))
         return last.value, total.value, count.value
@@ -1293,6 +1296,40 @@ class Api:
         pointers, flags = self._hop_mf_pointers(state)
         self._check(self.lib.gple_hop_observe_groups_mf(self.ctx, int(num_pes), int(model), n_groups, n_per_group, float(mass), flags, *pointers, _ptr(out)))
         return out
+
+    def hop_bin_mf(self, num_pes, model, state, grid, acc=None, bin_all=False):
+        """gple_hop_bin_mf: hop_bin from the amplitudes alone (the state's surface is ignored and never passed down) -> acc, int64 with the
+        length and the plane order of hop_bin's: the first num_pes planes hold the sums of rint(2^32 |c_a|^2) and no counts, then the (re, im)
+        planes of 2^32 c_a conj(c_b) per pair a < b, then [binned, outside].  acc and bin_all as hop_bin: numpy for a numpy ensemble, a tensor
+        on the GPU for a device one; a given acc is added to (GPLE_HOP_ACCUMULATE), numpy as a copy, a tensor in place.  At most 2^31
+        trajectories per call, and per accumulator"""
+        num_pes = int(num_pes)
+        state, n = self._hop_mf_state(num_pes, state, False)
+        grid, words = self._hop_grid(num_pes, grid)
+        flags = HOP_BIN_ALL if bin_all else 0
+        if acc is None:
+            acc = _like(state[0], words, np.int64)
+        else:
+            flags |= HOP_ACCUMULATE
+            if _on_device(acc) != _on_device(state[0]):
+                raise ValueError("the accumulator lives on the side the ensemble is on")
+            if not _on_device(acc):
+                acc = np.array(acc, dtype=np.int64)
+        acc, pa, _ = self._hop_acc(acc, words)
+        pointers, io = self._hop_mf_pointers(state)
+        self._check(self.lib.gple_hop_bin_mf(self.ctx, num_pes, int(model), n, *grid, flags | io, *pointers, pa))
+        return acc
+
+    def hop_density_mf(self, num_pes, grid, acc, n_norm):
+        """gple_hop_density_mf: the accumulator of hop_bin_mf as the adiabatic density (num_pes, num_pes, n_x, n_p) complex, the phase.txt
+        layout, on the side acc is on (a tensor: asynchronously on the context's stream); n_norm: the size of the whole ensemble"""
+        num_pes = int(num_pes)
+        grid, words = self._hop_grid(num_pes, grid)
+        acc, pa, flags = self._hop_acc(acc, words)
+        rho = _like(acc, (num_pes, num_pes, grid[2], grid[5]), np.complex128)
+        (pr,), _ = _io(rho)
+        self._check(self.lib.gple_hop_density_mf(self.ctx, num_pes, grid[2], grid[5], grid[1], grid[4], int(n_norm), flags, pa, pr))
+        return rho
 
     # ---- symmetrical quasi-classical trajectories (gple_hop_*_sqc; DESIGN.md §17, "Symmetrical quasi-classical trajectories") ----------------------
     # The ensemble is the same 5-tuple; b holds the mapping amplitudes, which are not normalised.  The samples write surface (= surface0); the

@@ -184,6 +184,67 @@ namespace
 	{
 		return num_pes == 2 && !(flags & GPLE_HOP_REVERSE) && x && p && b && surface && status;
 	}
+	// gple_hop_bin and gple_hop_bin_mf around their launch (surface: null for the call without one; n_max: the call's own bound on n): the
+	// checks, the model, a host acc through pooled memory (8 bytes an integer, as a double), the clear or the copy, the timer around the kernel alone
+	using HopBinLaunch = hipError_t (*)(hipStream_t, const HopEnsemble&, PesModel, const HopGrid&, bool, long long*);
+	int hop_bin_call(gple_ctx* ctx, int num_pes, int model, size_t n, size_t n_max, double x_first, double dx, size_t n_x, double p_first, double dp, size_t n_p,
+		unsigned flags, const double* x, const double* p, const double* b, const int* surface, const int* status, long long* acc, int timer, HopBinLaunch launch)
+	{
+		PesModel pes;
+		if (!ctx || !hop_size_ok(ctx, num_pes, model, n, 0, &pes) || n > n_max || !hop_cells_ok(n_x, n_p) || !hop_positive(dx) || !hop_positive(dp) ||
+			!std::isfinite(x_first) || !std::isfinite(p_first) || !x || !p || !b || !status || !acc)
+			return GPLE_ERR_BAD_ARG;
+		GPLE_OPEN(ctx);
+		const bool dev = flags & GPLE_IO_DEVICE, keep = flags & GPLE_HOP_ACCUMULATE;
+		const size_t words = static_cast<size_t>(hop_bin_planes(num_pes)) * n_x * n_p + 2;
+		GPLE_CALL(ctx);
+		hipStream_t stream = ctx->stream;
+		HopStaged st(ctx, flags);
+		GPLE_TRY(st.begin(num_pes, model));
+		Scratch sums(ctx);
+		long long* a = acc;
+		if (!dev)
+		{
+			GPLE_HIP(ctx, sums.get(words));
+			a = reinterpret_cast<long long*>(sums.p);
+		}
+		GPLE_TRY(st.arrays(HopStaged::READ, num_pes, n, 0, 0, x, p, b, surface, status));
+		if (!keep) GPLE_HIP(ctx, hipMemsetAsync(a, 0, words * sizeof(long long), stream));
+		else if (!dev) GPLE_HIP(ctx, hipMemcpyAsync(a, acc, words * sizeof(long long), hipMemcpyHostToDevice, stream));
+		const HopGrid g{x_first, dx, p_first, dp, static_cast<long>(n_x), static_cast<long>(n_p)};
+		GPLE_TRY(hop_timed(ctx, timer, [&] { return launch(stream, st.e, st.pes, g, (flags & GPLE_HOP_BIN_ALL) != 0, a); }));
+		if (!dev) GPLE_HIP(ctx, hipMemcpyAsync(acc, a, words * sizeof(long long), hipMemcpyDeviceToHost, stream));
+		return st.finish();
+	}
+	// gple_hop_density and gple_hop_density_mf around their launch
+	using HopDensityLaunch = hipError_t (*)(hipStream_t, int, long, double, const long long*, double*);
+	int hop_density_call(gple_ctx* ctx, int num_pes, size_t n_x, size_t n_p, double dx, double dp, size_t n_norm, unsigned flags, const long long* acc, double* rho,
+		HopDensityLaunch launch)
+	{
+		const double w = static_cast<double>(n_norm) * dx * dp; // left to right
+		if (!ctx || (num_pes != 2 && num_pes != 3) || !hop_cells_ok(n_x, n_p) || !hop_positive(dx) || !hop_positive(dp) || n_norm == 0 || !hop_positive(w) ||
+			!acc || !rho)
+			return GPLE_ERR_BAD_ARG;
+		GPLE_OPEN(ctx);
+		const bool dev = flags & GPLE_IO_DEVICE;
+		const size_t cells = n_x * n_p, words = static_cast<size_t>(hop_bin_planes(num_pes)) * cells + 2;
+		GPLE_CALL(ctx);
+		hipStream_t st = ctx->stream;
+		Staged r(ctx, dev);
+		Scratch sums(ctx);
+		const long long* a = acc;
+		GPLE_HIP(ctx, r.out(rho, 2 * static_cast<size_t>(num_pes) * num_pes * cells));
+		if (!dev)
+		{
+			GPLE_HIP(ctx, sums.get(words));
+			GPLE_HIP(ctx, hipMemcpyAsync(sums.p, acc, words * sizeof(long long), hipMemcpyHostToDevice, st));
+			a = reinterpret_cast<const long long*>(sums.p);
+		}
+		GPLE_HIP(ctx, launch(st, num_pes, static_cast<long>(cells), w, a, r.p));
+		GPLE_HIP(ctx, r.back());
+		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
+		return GPLE_OK;
+	}
 } // namespace
 
 extern "C"
@@ -246,59 +307,30 @@ extern "C"
 	int gple_hop_bin(gple_ctx* ctx, int num_pes, int model, size_t n, double x_first, double dx, size_t n_x, double p_first, double dp, size_t n_p,
 		unsigned flags, const double* x, const double* p, const double* b, const int* surface, const int* status, long long* acc)
 	{
-		PesModel pes;
-		if (!ctx || !hop_size_ok(ctx, num_pes, model, n, 0, &pes) || !hop_cells_ok(n_x, n_p) || !hop_positive(dx) || !hop_positive(dp) ||
-			!std::isfinite(x_first) || !std::isfinite(p_first) || !x || !p || !b || !surface || !status || !acc)
-			return GPLE_ERR_BAD_ARG;
-		GPLE_OPEN(ctx);
-		const bool dev = flags & GPLE_IO_DEVICE, keep = flags & GPLE_HOP_ACCUMULATE;
-		const size_t words = static_cast<size_t>(hop_bin_planes(num_pes)) * n_x * n_p + 2;
-		GPLE_CALL(ctx);
-		hipStream_t stream = ctx->stream;
-		HopStaged st(ctx, flags);
-		GPLE_TRY(st.begin(num_pes, model));
-		Scratch sums(ctx); // a host acc: the integers in pooled memory (8 bytes each, as a double)
-		long long* a = acc;
-		if (!dev)
-		{
-			GPLE_HIP(ctx, sums.get(words));
-			a = reinterpret_cast<long long*>(sums.p);
-		}
-		GPLE_TRY(st.arrays(HopStaged::READ, num_pes, n, 0, 0, x, p, b, surface, status));
-		if (!keep) GPLE_HIP(ctx, hipMemsetAsync(a, 0, words * sizeof(long long), stream));
-		else if (!dev) GPLE_HIP(ctx, hipMemcpyAsync(a, acc, words * sizeof(long long), hipMemcpyHostToDevice, stream));
-		const HopGrid g{x_first, dx, p_first, dp, static_cast<long>(n_x), static_cast<long>(n_p)};
-		GPLE_TRY(hop_timed(ctx, GPLE_TIMER_HOP_BIN, [&] { return launch_hop_bin(stream, st.e, st.pes, g, (flags & GPLE_HOP_BIN_ALL) != 0, a); }));
-		if (!dev) GPLE_HIP(ctx, hipMemcpyAsync(acc, a, words * sizeof(long long), hipMemcpyDeviceToHost, stream));
-		return st.finish();
+		if (!surface) return GPLE_ERR_BAD_ARG;
+		return hop_bin_call(ctx, num_pes, model, n, size_t(1) << 32, x_first, dx, n_x, p_first, dp, n_p, flags, x, p, b, surface, status, acc, GPLE_TIMER_HOP_BIN,
+			launch_hop_bin);
 	}
 
 	int gple_hop_density(gple_ctx* ctx, int num_pes, size_t n_x, size_t n_p, double dx, double dp, size_t n_norm, unsigned flags, const long long* acc,
 		double* rho)
 	{
-		const double w = static_cast<double>(n_norm) * dx * dp; // left to right
-		if (!ctx || (num_pes != 2 && num_pes != 3) || !hop_cells_ok(n_x, n_p) || !hop_positive(dx) || !hop_positive(dp) || n_norm == 0 || !hop_positive(w) ||
-			!acc || !rho)
-			return GPLE_ERR_BAD_ARG;
-		GPLE_OPEN(ctx);
-		const bool dev = flags & GPLE_IO_DEVICE;
-		const size_t cells = n_x * n_p, words = static_cast<size_t>(hop_bin_planes(num_pes)) * cells + 2;
-		GPLE_CALL(ctx);
-		hipStream_t st = ctx->stream;
-		Staged r(ctx, dev);
-		Scratch sums(ctx);
-		const long long* a = acc;
-		GPLE_HIP(ctx, r.out(rho, 2 * static_cast<size_t>(num_pes) * num_pes * cells));
-		if (!dev)
-		{
-			GPLE_HIP(ctx, sums.get(words));
-			GPLE_HIP(ctx, hipMemcpyAsync(sums.p, acc, words * sizeof(long long), hipMemcpyHostToDevice, st));
-			a = reinterpret_cast<const long long*>(sums.p);
-		}
-		GPLE_HIP(ctx, launch_hop_density(st, num_pes, static_cast<long>(cells), w, a, r.p));
-		GPLE_HIP(ctx, r.back());
-		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
-		return GPLE_OK;
+		return hop_density_call(ctx, num_pes, n_x, n_p, dx, dp, n_norm, flags, acc, rho, launch_hop_density);
+	}
+
+	/* ---- the density from the amplitudes ("The ensemble in phase space, from the amplitudes") ------------------------------- */
+	int gple_hop_bin_mf(gple_ctx* ctx, int num_pes, int model, size_t n, double x_first, double dx, size_t n_x, double p_first, double dp, size_t n_p,
+		unsigned flags, const double* x, const double* p, const double* b, const int* status, long long* acc)
+	{
+		// n <= 2^31: a weight term is at most 2^32 to rounding, and one call must not overflow the signed sum of a cell
+		return hop_bin_call(ctx, num_pes, model, n, size_t(1) << 31, x_first, dx, n_x, p_first, dp, n_p, flags, x, p, b, nullptr, status, acc, GPLE_TIMER_HOP_BIN_MF,
+			launch_hop_bin_mf);
+	}
+
+	int gple_hop_density_mf(gple_ctx* ctx, int num_pes, size_t n_x, size_t n_p, double dx, double dp, size_t n_norm, unsigned flags, const long long* acc,
+		double* rho)
+	{
+		return hop_density_call(ctx, num_pes, n_x, n_p, dx, dp, n_norm, flags, acc, rho, launch_hop_density_mf);
 	}
 
 	/* ---- grouped ensembles ("A curve in one launch") ------------------------------------------------------------------------ */

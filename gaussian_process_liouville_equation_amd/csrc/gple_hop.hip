@@ -3,7 +3,7 @@
 // (SQC) and MASH trajectories.  The reference has no trajectory code: these are the methods its three models were made to test.
 //
 // One thread per trajectory; x, p, the diabatic amplitudes b, the active surface a and everything derived from them stay in registers for all
-// the steps of a launch.  No LDS, no device globals, and no atomics but the integer ones of hop_bin_kernel below.  Every piece that more than
+// the steps of a launch.  No LDS, no device globals, and no atomics but the integer ones of hop_bin_kernel and hop_bin_mf_kernel below.  Every piece that more than
 // one method uses is one device function, stated once here; a method is a sampler, a force and a crossing rule on top of them.
 //
 // The shared pieces (V, Fd = -V', E, C: the diabatic matrix and force, the adiabatic energies and states; F = C^T Fd C, symmetrised as in
@@ -844,9 +844,65 @@ namespace gple
 				if (out) atomicAdd(tally + 1, static_cast<unsigned long long>(__popcll(out)));
 			}
 		}
+		// The density of an ensemble without an active surface, or the second prescription of Landry, Falk and Subotnik for one that has one
+		// ("The ensemble in phase space, from the amplitudes"): hop_bin_kernel with the populations from the amplitudes too.
+		// e.surface is not read (the mean-field calls pass none).  A binned trajectory adds rint(2^32 |c_a|^2) to plane a for every a, so the
+		// first NP planes hold weights in fixed point and no counts, and the coherence terms of hop_bin_kernel to the planes behind them: NP^2
+		// no-return atomics.  A weight is at most 2^32 (to rounding) for a unit vector: 2^31 of them cannot overflow the signed sum of a cell.
+		// The cell, the coherence terms and the tallies are hop_bin_kernel's lines, copied: shared as device functions they left that kernel
+		// its registers but not its instructions, and its bits are pinned
+		template <int NP, typename M>
+		__global__ void __launch_bounds__(HOP_BLOCK) hop_bin_mf_kernel(HopEnsemble e, M model, HopGrid g, int bin_all, unsigned long long* __restrict__ acc)
+		{
+			const long i = static_cast<long>(blockIdx.x) * HOP_BLOCK + threadIdx.x;
+			const long cells = g.n_x * g.n_p;
+			bool binned = false, outside = false;
+			if (i < e.n)
+			{
+				const int status = e.status[i];
+				if (status >= 0 && status <= 2 && (status == 0 || bin_all))
+				{
+					const double x = e.x[i], p = e.p[i];
+					const double fx = floor((x - g.x_first) / g.dx + 0.5), fp = floor((p - g.p_first) / g.dp + 0.5);
+					binned = fx >= 0.0 && fx < static_cast<double>(g.n_x) && fp >= 0.0 && fp < static_cast<double>(g.n_p);
+					outside = !binned;
+					if (binned)
+					{
+						const long cell = static_cast<long>(fx) * g.n_p + static_cast<long>(fp);
+						double cre[NP], cim[NP], E[NP];
+						hop_adiabatic<NP>(e, model, i, x, E, cre, cim);
+#pragma unroll
+						for (int a = 0; a < NP; ++a)
+						{
+							const double w = cre[a] * cre[a] + cim[a] * cim[a];
+							atomicAdd(acc + a * cells + cell, static_cast<unsigned long long>(static_cast<long long>(rint(4294967296.0 * w))));
+						}
+						unsigned long long* plane = acc + NP * cells + cell;
+#pragma unroll
+						for (int k = 0; k < NP; ++k)
+#pragma unroll
+							for (int l = k + 1; l < NP; ++l)
+							{
+								const double re = cre[k] * cre[l] + cim[k] * cim[l], im = cim[k] * cre[l] - cre[k] * cim[l];
+								atomicAdd(plane, static_cast<unsigned long long>(static_cast<long long>(rint(4294967296.0 * re))));
+								atomicAdd(plane + cells, static_cast<unsigned long long>(static_cast<long long>(rint(4294967296.0 * im))));
+								plane += 2 * cells;
+							}
+					}
+				}
+			}
+			const unsigned long long in = __ballot(binned), out = __ballot(outside);
+			if (threadIdx.x % HOP_WAVE == 0)
+			{
+				unsigned long long* tally = acc + hop_bin_planes(NP) * cells;
+				if (in) atomicAdd(tally, static_cast<unsigned long long>(__popcll(in)));
+				if (out) atomicAdd(tally + 1, static_cast<unsigned long long>(__popcll(out)));
+			}
+		}
 		// One thread per cell: the num_pes^2 planes of the phase.txt layout from the integers.  The lower triangle is formed from the negated
-		// sum (exactly the conjugate, and +0 where the sum is 0)
-		template <int NP>
+		// sum (exactly the conjugate, and +0 where the sum is 0).  WEIGHTS: the accumulator of hop_bin_mf_kernel, whose first NP planes are sums
+		// of 2^32 |c_a|^2 and are scaled as the coherence sums are
+		template <int NP, bool WEIGHTS>
 		__global__ void __launch_bounds__(HOP_BLOCK) hop_density_kernel(long cells, double w, const long long* __restrict__ acc, double* __restrict__ rho)
 		{
 			const long cell = static_cast<long>(blockIdx.x) * HOP_BLOCK + threadIdx.x;
@@ -856,7 +912,8 @@ namespace gple
 			for (int a = 0; a < NP; ++a)
 			{
 				double* d = rho + 2 * ((a * NP + a) * cells + cell);
-				d[0] = static_cast<double>(acc[a * cells + cell]) / w, d[1] = 0.0;
+				const double sum = static_cast<double>(acc[a * cells + cell]);
+				d[0] = (WEIGHTS ? sum * SCALE : sum) / w, d[1] = 0.0;
 			}
 			const long long* plane = acc + NP * cells + cell;
 #pragma unroll
@@ -1186,8 +1243,24 @@ namespace gple
 	hipError_t launch_hop_density(hipStream_t s, int num_pes, long cells, double w, const long long* acc, double* rho)
 	{
 		if (cells <= 0) return hipErrorInvalidValue;
-		if (num_pes == 2) hop_launch(s, cells, hop_density_kernel<2>, cells, w, acc, rho);
-		else if (num_pes == 3) hop_launch(s, cells, hop_density_kernel<3>, cells, w, acc, rho);
+		if (num_pes == 2) hop_launch(s, cells, hop_density_kernel<2, false>, cells, w, acc, rho);
+		else if (num_pes == 3) hop_launch(s, cells, hop_density_kernel<3, false>, cells, w, acc, rho);
+		else return hipErrorInvalidValue;
+		return hipGetLastError();
+	}
+
+	hipError_t launch_hop_bin_mf(hipStream_t s, const HopEnsemble& e, PesModel model, const HopGrid& g, bool bin_all, long long* acc)
+	{
+		if (e.n <= 0 || g.n_x <= 0 || g.n_p <= 0) return hipErrorInvalidValue;
+		unsigned long long* const words = reinterpret_cast<unsigned long long*>(acc);
+		const int all = bin_all ? 1 : 0;
+		return hop_dispatch(e, model, [&](auto np, auto m) { hop_launch(s, e.n, hop_bin_mf_kernel<np(), decltype(m)>, e, m, g, all, words); });
+	}
+	hipError_t launch_hop_density_mf(hipStream_t s, int num_pes, long cells, double w, const long long* acc, double* rho)
+	{
+		if (cells <= 0) return hipErrorInvalidValue;
+		if (num_pes == 2) hop_launch(s, cells, hop_density_kernel<2, true>, cells, w, acc, rho);
+		else if (num_pes == 3) hop_launch(s, cells, hop_density_kernel<3, true>, cells, w, acc, rho);
 		else return hipErrorInvalidValue;
 		return hipGetLastError();
 	}

@@ -486,6 +486,10 @@ namespace gple
 	hipError_t launch_hop_bin(hipStream_t s, const HopEnsemble& e, PesModel model, const HopGrid& g, bool bin_all, long long* acc);
 	// rho (num_pes^2 planes of n_x n_p (re, im) pairs) from acc: counts / w, coherence sums 2^-32 / w
 	hipError_t launch_hop_density(hipStream_t s, int num_pes, long cells, double w, const long long* acc, double* rho);
+	// the same two from the amplitudes alone (e.surface is not read): the first num_pes planes of acc are sums of rint(2^32 |c_a|^2), which the
+	// density scales by 2^-32 / w as it scales the coherence sums.  A weight is at most 2^32 to rounding: the caller keeps e.n <= 2^31
+	hipError_t launch_hop_bin_mf(hipStream_t s, const HopEnsemble& e, PesModel model, const HopGrid& g, bool bin_all, long long* acc);
+	hipError_t launch_hop_density_mf(hipStream_t s, int num_pes, long cells, double w, const long long* acc, double* rho);
 
 	// ---- reconstruction of a gridded density (gple_recon.hip; test/gpr.cpp): num_pes = 2 or 3, rho: num_pes^2 x nx x np (re, im) ----
 	constexpr int RECON_SURVEY_BLOCKS = 64, RECON_SURVEY_VALUES = 7; // row blocks of the survey, values per plane and block

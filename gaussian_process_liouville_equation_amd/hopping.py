@@ -7,6 +7,7 @@ column for column with exact.run(flux=True)'s.
     phase_grid_of()   the phase-space grid of a run, from its size
     run()             sample, then per output time one hop_evolve of output_step steps and one hop_observe; t.txt and averages.txt.  With a
                       phase_grid also one gple_hop_bin and gple_hop_density: x.txt, p.txt and phase.txt, the adiabatic density of the ensemble
+                      (phase_density="amplitude": gple_hop_bin_mf and gple_hop_density_mf, which "ehrenfest" runs have too)
     scan()            the branching probabilities at many momenta from one grouped ensemble (gple_hop_sample_groups / _evolve_groups /
                       _observe_groups): a group per momentum with its own packet and time step; scan.txt
 run() and scan() take decoherence = None (Tully's algorithm as it stands), "edc", "collapse_hop" or "collapse_attempt" and edc_c: the decoherence
@@ -75,11 +76,19 @@ SQC = "sqc"  # the third method: its ensemble comes from a sample of its own (ho
 MASH = "mash"  # the fourth method: a sample and a step of its own, the sums of "fssh"
 
 
-def _method(method, decoherence, reverse_frustrated, phase_grid=None, window=None, gamma=None, num_pes=2):
+PHASE_DENSITIES = (None, "mixed", "amplitude")  # run(phase_density=...): None is "mixed"
+
+
+def _method(method, decoherence, reverse_frustrated, phase_grid=None, window=None, gamma=None, num_pes=2, phase_density=None):
     """method of run() and scan(), checked against the options that need an active surface -> True for the mean-field one, SQC for "sqc", MASH
-    for "mash" """
+    for "mash".  phase_density: the prescription of run()'s phase_grid; "amplitude" needs no active surface, so "ehrenfest" may have a
+    phase_grid with it (and with it alone)"""
     if method not in METHODS + (SQC, MASH):
         raise ValueError(f"method is one of {METHODS + (SQC, MASH)}")
+    if phase_density not in PHASE_DENSITIES:
+        raise ValueError('phase_density is None, "mixed" or "amplitude"')
+    if phase_density is not None and phase_grid is None:
+        raise ValueError("phase_density belongs to a phase_grid")
     if method != SQC and (window is not None or gamma is not None):
         raise ValueError('window and gamma belong to method="sqc"')
     if method == "fssh":
@@ -90,8 +99,11 @@ def _method(method, decoherence, reverse_frustrated, phase_grid=None, window=Non
         if int(num_pes) != 2:
             raise ValueError("mash is a two-level method: num_pes = 2")
         return MASH
+    if method == "ehrenfest" and phase_density == "amplitude":
+        phase_grid = None  # the density from the amplitudes needs no active surface
     if decoherence is not None or reverse_frustrated or phase_grid is not None:
-        raise ValueError(f"{method} trajectories have no active surface: no decoherence correction, no frustrated hops and (DESIGN.md §17) no phase_grid")
+        raise ValueError(f"{method} trajectories have no active surface: no decoherence correction, no frustrated hops and (DESIGN.md §17) no phase_grid"
+                         + (' but with phase_density="amplitude"' if method == "ehrenfest" else ""))
     return True if method == "ehrenfest" else SQC
 
 
@@ -169,7 +181,7 @@ def phase_grid_of(api, num_pes, model, s, phase_grid):
 
 
 def run(api, model=DAC, num_pes=2, ln_energy=0.0, n_traj=10000, seed=0, out_dir=None, reverse_frustrated=False, dt=None, surface0=0, max_outputs=None,
-        log=None, phase_grid=None, decoherence=None, edc_c=0.1, method="fssh", window=None, gamma=None, **setup_kw):
+        log=None, phase_grid=None, decoherence=None, edc_c=0.1, method="fssh", window=None, gamma=None, phase_density=None, **setup_kw):
     """n_traj trajectories from the packet of exact.setup(ln_energy, boundary=ABSORBING, **setup_kw) (x0, sigma_x, p0, sigma_p, mass) on the adiabatic
     surface surface0, evolved with the time step dt (default: the setup's dt_rule, the reference's own rule) between x_left = xmin and
     x_right = xmax; a trajectory that leaves is finished and counted by side and active surface.  The ensemble stays on the device: every
@@ -180,12 +192,16 @@ def run(api, model=DAC, num_pes=2, ln_energy=0.0, n_traj=10000, seed=0, out_dir=
     gains binned, outside and binned_counts (per active surface), and with out_dir one hop_density, appended to phase.txt as exact.run writes
     it (the text made on the device where the api has format_g); x.txt and p.txt are written once.  The directory is then what
     reconstruct.run_files reads.
+    phase_density (with a phase_grid only): None or "mixed" is the above, call for call: populations from the active surface, coherences from
+    the amplitudes.  "amplitude" takes both from the amplitudes (hop_bin_mf / hop_density_mf; DESIGN.md §17, "The ensemble in phase space,
+    from the amplitudes"), which is the density of an "ehrenfest" run and the other prescription of an "fssh" one; the files are the same, and
+    a record gains binned, outside and binned_weights, the per-state sums of the weight planes times 2^-32 as floats (no binned_counts).
     decoherence (None, "edc", "collapse_hop", "collapse_attempt") and edc_c: the decoherence correction of every step; with None the api is
     called without these keywords, otherwise both are forwarded to every hop_evolve.  The result carries both.
     method: "fssh" (the default: everything above, call for call) or "ehrenfest", mean-field trajectories from the same sample: per output time
     one hop_evolve_mf and one hop_observe_mf, whose record is unpack_mf()'s; the run stops when n_status[0] == 0.  An averages.txt line is then
     averages_line_mf (no active-surface columns), and the scattering line holds weights[left][k] / n, weights[right][k] / n and n_status[0] / n
-    in the same columns.  decoherence, reverse_frustrated=True or a phase_grid with "ehrenfest" is a ValueError.
+    in the same columns.  decoherence, reverse_frustrated=True or a phase_grid without phase_density="amplitude" is a ValueError with "ehrenfest".
     method "sqc" with window ("triangle", the default, or "square") and gamma (None: the window's customary value): _run_sqc below; the same
     options are a ValueError with it, and so are window or gamma with another method.
     method "mash": everything of "fssh" (records, files, the scattering line) with hop_sample_mash for the sample and one hop_evolve_mash per
@@ -193,7 +209,8 @@ def run(api, model=DAC, num_pes=2, ln_energy=0.0, n_traj=10000, seed=0, out_dir=
     it is a ValueError.
     Returns the setup, the records (t and unpack() per output time), stop, and scattering_line: the head of exact.run's final line, the
     fractions that left [left | right][surface], and the fraction still running."""
-    mean_field = _method(method, decoherence, reverse_frustrated, phase_grid, window, gamma, num_pes)
+    mean_field = _method(method, decoherence, reverse_frustrated, phase_grid, window, gamma, num_pes, phase_density)
+    amplitude = phase_density == "amplitude"
     if mean_field == SQC:
         return _run_sqc(api, model, num_pes, ln_energy, n_traj, seed, out_dir, dt, surface0, max_outputs, log, window, gamma, setup_kw)
     mash = mean_field == MASH  # the loop of "fssh" with the sample and the step of its own
@@ -228,16 +245,20 @@ def run(api, model=DAC, num_pes=2, ln_energy=0.0, n_traj=10000, seed=0, out_dir=
                 rec = unpack(api.hop_observe(num_pes, model, state, s["mass"]), num_pes, n_traj)
             rec["t"] = step * dt
             if grid is not None:
-                acc = api.hop_bin(num_pes, model, state, grid)
+                acc = (api.hop_bin_mf if amplitude else api.hop_bin)(num_pes, model, state, grid)
                 if files:
-                    rho = api.hop_density(num_pes, grid, acc, n_traj)
+                    rho = (api.hop_density_mf if amplitude else api.hop_density)(num_pes, grid, acc, n_traj)
                     files["phase.txt"].write(exact.phase_text(api, rho[None]) if hasattr(api, "format_g") else exact.phase_block(rho).encode())
                 if hasattr(acc, "is_cuda"):
                     api.synchronize()  # the context's stream has written acc: now the framework's may read it
                 few = (acc[:num_pes * grid[2] * grid[5]].reshape(num_pes, -1).sum(1), acc[-2:])  # the only numbers of acc that cross
                 if hasattr(acc, "is_cuda"):
                     few = tuple(v.cpu().numpy() for v in few)
-                rec["binned_counts"], (rec["binned"], rec["outside"]) = few[0], (int(v) for v in few[1])
+                rec["binned"], rec["outside"] = (int(v) for v in few[1])
+                if amplitude:
+                    rec["binned_weights"] = np.asarray(few[0], dtype=np.float64) / 4294967296.0
+                else:
+                    rec["binned_counts"] = few[0]
             records.append(rec)
             if files:
                 files["t.txt"].write(exact.fmt(rec["t"]) + "\n")
@@ -267,7 +288,7 @@ def run(api, model=DAC, num_pes=2, ln_energy=0.0, n_traj=10000, seed=0, out_dir=
     line = " ".join(exact.fmt(v) for v in [head, *scattered, running / n_traj])
     return dict(setup=s, dt=dt, output_step=output_step, total_step=total_step, n_traj=n_traj, records=records, stop=stop, state=state,
                 scattered=scattered.reshape(2, num_pes), scattering_line=line, stop_time=records[-1]["t"], steps=step, total_seconds=t_end - t0,
-                decoherence=decoherence, edc_c=edc_c, method=method)
+                decoherence=decoherence, edc_c=edc_c, method=method, phase_density=phase_density)
 
 
 def scan_line(values):

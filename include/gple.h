@@ -162,7 +162,8 @@ typedef enum gple_timer {
 	GPLE_TIMER_HOP_GROUPS = 14,    /* the step kernel of one gple_hop_evolve_groups or _groups_dc call (all its steps, no staging); count = calls */
 	GPLE_TIMER_HOP_MF = 15,        /* the step kernel of one gple_hop_evolve_mf or gple_hop_evolve_groups_mf call (all its steps, no staging); count = calls */
 	GPLE_TIMER_HOP_SQC = 16,       /* the step kernel of one gple_hop_evolve_sqc or gple_hop_evolve_groups_sqc call (all its steps, no staging); count = calls */
-	GPLE_TIMER_HOP_MASH = 17       /* the step kernel of one gple_hop_evolve_mash or gple_hop_evolve_groups_mash call (all its steps, no staging); count = calls */
+	GPLE_TIMER_HOP_MASH = 17,      /* the step kernel of one gple_hop_evolve_mash or gple_hop_evolve_groups_mash call (all its steps, no staging); count = calls */
+	GPLE_TIMER_HOP_BIN_MF = 18     /* the bin kernel of one gple_hop_bin_mf call (no staging, no clear); count = calls */
 } gple_timer;
 int gple_ctx_enable_timing(gple_ctx* ctx, int on);
 /* Synchronises the stream, then: last = milliseconds of the most recent interval; total / count = accumulated since
@@ -674,6 +675,32 @@ int gple_hop_observe_mf(gple_ctx* ctx, int num_pes, int model, size_t n, double 
 	const double* b, const int* status, double* out);
 int gple_hop_observe_groups_mf(gple_ctx* ctx, int num_pes, int model, size_t n_groups, size_t n_per_group, double mass, unsigned flags,
 	const double* x, const double* p, const double* b, const int* status, double* out);
+/* The ensemble's adiabatic density from the amplitudes alone ("The ensemble in phase space, from the amplitudes"): gple_hop_bin
+ * and gple_hop_density for an ensemble without an active surface.  With c = C^T b at the trajectory's x, as gple_hop_observe_mf forms it,
+ *     rho_ab(cell) = sum_{i in cell} c_a conj(c_b) / (n_norm dx dp)   for every a and b, the diagonal included,
+ * which is the density of a mean-field (Ehrenfest) ensemble, and for a fewest-switches ensemble the second prescription of Landry, Falk and
+ * Subotnik (J. Chem. Phys. 139, 211101 (2013)), populations from the amplitudes, beside the mixed one of gple_hop_bin.  surface is not passed.
+ * gple_hop_bin_mf, operation for operation:
+ *   selection  the one of gple_hop_observe_mf: status 0, or 0 ... 2 with GPLE_HOP_BIN_ALL; a status out of range is skipped (no term, no tally).
+ *   cell       gple_hop_bin's: k = floor((x - x_first) / dx + 0.5), compared with 0 and n_x in double (a NaN or a huge value is outside), the
+ *              same for p; a selected trajectory off the grid adds one to `outside` and nothing else.
+ *   terms      a binned trajectory adds num_pes^2 integers at its cell: rint(2^32 (Re c_a Re c_a + Im c_a Im c_a)) to plane a, for every a;
+ *              and, per pair a < b, rint(2^32 Re c_a conj(c_b)) and rint(2^32 Im c_a conj(c_b)) to the pair's two planes, the very terms of
+ *              gple_hop_bin; then one to `binned`.
+ * acc has the length and the plane order of gple_hop_bin's, (num_pes + num_pes (num_pes - 1)) n_x n_p + 2 integers; only the meaning of the
+ * first num_pes planes differs: they hold sums of 2^32 |c_a|^2 and are no counts.  The integers have the same bits whatever order the adds
+ * arrive in, and a slice added to its complement with GPLE_HOP_ACCUMULATE gives the bits of the whole.  The result is defined for amplitudes
+ * of unit norm to rounding, as gple_hop_bin's is: a weight term is then at most 2^32 (plus rounding), and since n <= 2^31 one call cannot
+ * overflow the signed 64-bit sum of a cell.  Across GPLE_HOP_ACCUMULATE calls that bound (2^31 trajectories in all) is the caller's to keep.
+ * Flags: GPLE_IO_DEVICE, GPLE_HOP_ACCUMULATE, GPLE_HOP_BIN_ALL, as for gple_hop_bin.  Timer: GPLE_TIMER_HOP_BIN_MF.
+ * gple_hop_density_mf: w = (double)n_norm dx dp, left to right; every sum, the diagonal's too, becomes (double)sum 2^-32 / w; Im rho_aa = +0
+ * exactly; the lower planes are formed from the negated sums (+0 where the sum is 0), as gple_hop_density forms them.  With n_norm the size
+ * of the whole ensemble, sum_a sum_cells rho_aa dx dp is the fraction binned, to the rounding of the terms.
+ * GPLE_ERR_BAD_ARG, with nothing written: everything gple_hop_bin and gple_hop_density refuse that applies here; n > 2^31 (bin); a null array. */
+int gple_hop_bin_mf(gple_ctx* ctx, int num_pes, int model, size_t n, double x_first, double dx, size_t n_x, double p_first, double dp, size_t n_p,
+	unsigned flags, const double* x, const double* p, const double* b, const int* status, long long* acc);
+int gple_hop_density_mf(gple_ctx* ctx, int num_pes, size_t n_x, size_t n_p, double dx, double dp, size_t n_norm, unsigned flags, const long long* acc,
+	double* rho);
 /* Symmetrical quasi-classical (SQC) trajectories ("Symmetrical quasi-classical trajectories"): the Meyer-Miller-Stock-Thoss
  * mapping Hamiltonian run classically, with the symmetrical windows of Cotton and Miller.  A trajectory is x, p, the diabatic mapping
  * amplitudes b (num_pes complex numbers, NOT normalised) and its status, in the five arrays of every other ensemble; surface is written by the
