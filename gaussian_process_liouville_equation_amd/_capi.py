@@ -371,6 +371,8 @@ def _signatures():
         "mqcl_transform": (st, [CTX, i, i, _dp, sz, i, i, u, _dp, _dp]),
         "mqcl_evolve": (st, [CTX, i, i, _dp, _dp, sz, d, d, d, d, sz, u, _dp]),
         "mqcl_observe": (st, [CTX, i, i, _dp, _dp, sz, d, d, d, u, _dp, _dp, _dp, _dp]),
+        "mqcl_absorb": (st, [CTX, i, i, _dp, sz, _dp, sz, u, _dp, _dp]),
+        "mqcl_evolve_absorbing": (st, [CTX, i, i, _dp, _dp, sz, d, d, d, d, sz, sz, _dp, sz, u, _dp, _dp]),
         # fewest-switches surface hopping
         "hop_sample": (st, [CTX, i, i, sz, sz, ull, d, d, d, d, i, u, _dp, _dp, _dp, ip, ip]),
         "hop_evolve": (st, [CTX, i, i, sz, sz, ull, d, d, sz, sz, d, d, u, _dp, _dp, _dp, ip, ip]),
@@ -1011,6 +1013,46 @@ class Api:
         (px, pp, pr, pa, pav, ppo), flags = _io(x, p, rho_dia, adia, av, pops)
         self._check(self.lib.gple_mqcl_observe(self.ctx, int(num_pes), int(model), px, pp, n, float(mass), float(dx), float(dp), flags, pr, pa, pav, ppo))
         return adia, av, pops
+
+    def _mqcl_mask(self, num_pes, n, rho, g, absorbed_p):
+        """the state, the half-mask g (n,) and the accumulator (2, num_pes, n) of a masking call, on one side: numpy -> copies of the state and
+        the accumulator (zeros when None), device tensors as they are (the accumulator a new zero tensor when None)"""
+        rho = _rho(rho, num_pes, n)
+        g = _axis(g)
+        if tuple(g.shape) != (n,):
+            raise ValueError("g has one value per grid point")
+        if absorbed_p is None:
+            absorbed_p = _like(rho, (2, num_pes, n))
+            absorbed_p[...] = 0.0
+        elif not _on_device(absorbed_p):
+            absorbed_p = np.array(absorbed_p, dtype=np.float64, order="C")
+        if tuple(absorbed_p.shape) != (2, num_pes, n) or (_on_device(absorbed_p) and str(absorbed_p.dtype) != "torch.float64"):
+            raise ValueError("absorbed_p is float64 of shape (2, num_pes, n)")
+        if not _on_device(rho):
+            rho = rho.copy()
+        return rho, g, absorbed_p
+
+    def mqcl_absorb(self, num_pes, model, x, rho, g, n_left, absorbed_p=None):
+        """gple_mqcl_absorb: rho(x_i, .) <- (1 - g_i) rho(x_i, .) on the diabatic rho (num_pes, num_pes, n, n) complex, and g_i times the adiabatic
+        diagonal added to absorbed_p (2, num_pes, n) [side][surface][j], side 0 the rows i < n_left; absorbed_p None starts from zeros.  numpy:
+        returns the masked copy and the new accumulator; device tensors: both in place (asynchronously) and returned"""
+        x = _axis(x)
+        n = int(x.shape[0])
+        rho, g, absorbed_p = self._mqcl_mask(num_pes, n, rho, g, absorbed_p)
+        (px, pg, pr, pa), flags = _io(x, g, rho, absorbed_p)
+        self._check(self.lib.gple_mqcl_absorb(self.ctx, int(num_pes), int(model), px, n, pg, int(n_left), flags, pr, pa))
+        return rho, absorbed_p
+
+    def mqcl_evolve_absorbing(self, num_pes, model, x, p, rho, mass, length_x, length_p, dt, n_steps, mask_every, g, n_left, absorbed_p=None):
+        """gple_mqcl_evolve_absorbing: n_steps / mask_every blocks of mqcl_absorb(g), mask_every steps of mqcl_evolve, mqcl_absorb(g), enqueued in
+        one call; the bits of those separate calls.  Arrays and results as mqcl_absorb"""
+        x, p = _axis(x), _axis(p)
+        n = int(x.shape[0])
+        rho, g, absorbed_p = self._mqcl_mask(num_pes, n, rho, g, absorbed_p)
+        (px, pp, pg, pr, pa), flags = _io(x, p, g, rho, absorbed_p)
+        self._check(self.lib.gple_mqcl_evolve_absorbing(self.ctx, int(num_pes), int(model), px, pp, n, float(mass), float(length_x), float(length_p), float(dt),
+                                                        int(n_steps), int(mask_every), pg, int(n_left), flags, pr, pa))
+        return rho, absorbed_p
 
     # ---- fewest-switches surface hopping (gple_hop_*; DESIGN.md §17, driven by hopping.py) -----------------------------------------------------
     # An ensemble is the tuple (x (n,), p (n,) float64, b (n, num_pes) complex128 diabatic amplitudes, surface (n,), status (n,) int32): numpy

@@ -347,6 +347,111 @@ extern "C"
 		return GPLE_OK;
 	}
 
+	/* ---- the absorbing boundary of the MQCLE run (gple_mqcl_absorb.hip) ------------------------------------------------------ */
+	// what every mask of a call shares: g on the device, the number of rows with g_i != 0 from the host's copy of g (a device g is copied back
+	// once, which drains the stream) and their ascending list
+	struct MqclMask
+	{
+		Staged g;
+		Scratch rows, slab;
+		int count = 0;
+		MqclMask(gple_ctx* ctx, bool dev): g(ctx, dev), rows(ctx), slab(ctx) {}
+	};
+	static int mqcl_mask_plan(gple_ctx* ctx, hipStream_t st, int num_pes, const double* g, int n, bool dev, MqclMask& m)
+	{
+		GPLE_HIP(ctx, m.g.in(g, n));
+		std::vector<double> copy;
+		if (dev)
+		{
+			copy.resize(n);
+			GPLE_HIP(ctx, hipMemcpyAsync(copy.data(), g, n * sizeof(double), hipMemcpyDeviceToHost, st));
+			GPLE_HIP(ctx, hipStreamSynchronize(st));
+			g = copy.data();
+		}
+		for (int i = 0; i < n; ++i) m.count += g[i] != 0.0;
+		GPLE_HIP(ctx, m.rows.get(mqcl_absorb_rows_doubles(n)));
+		GPLE_HIP(ctx, m.slab.get(mqcl_absorb_slab_doubles(num_pes, n, m.count)));
+		if (m.count) GPLE_HIP(ctx, launch_mqcl_absorb_rows(st, m.g.p, n, reinterpret_cast<int*>(m.rows.p)));
+		return GPLE_OK;
+	}
+	static MqclAbsorbArgs mqcl_mask_args(int num_pes, const PesModel& pes, int n, size_t n_left, const double* x, const MqclMask& m, double* rho, double* absorbed_p)
+	{
+		MqclAbsorbArgs a{};
+		a.num_pes = num_pes, a.n = n, a.n_left = static_cast<int>(n_left), a.count = m.count, a.model = pes, a.x = x, a.g = m.g.p;
+		a.rows = reinterpret_cast<const int*>(m.rows.p), a.slab = m.slab.p, a.rho = rho, a.absorbed_p = absorbed_p;
+		return a;
+	}
+
+	int gple_mqcl_absorb(gple_ctx* ctx, int num_pes, int model, const double* x, size_t n_grids, const double* g, size_t n_left, unsigned flags, double* rho,
+		double* absorbed_p)
+	{
+		PesModel pes;
+		if (!ctx || !mqcl_size_ok(ctx, num_pes, model, n_grids, &pes) || n_left > n_grids || !x || !g || !rho || !absorbed_p) return GPLE_ERR_BAD_ARG;
+		GPLE_OPEN(ctx);
+		const bool dev = flags & GPLE_IO_DEVICE;
+		const int n = static_cast<int>(n_grids);
+		const size_t doubles = 2 * static_cast<size_t>(num_pes) * num_pes * n_grids * n_grids;
+		GPLE_CALL(ctx);
+		if (!pes_resolve(ctx, num_pes, model, &pes)) return GPLE_ERR_BAD_ARG; // under the call lock, which gple_pes_undefine takes: the table outlives the enqueue
+		hipStream_t st = ctx->stream;
+		Staged xs(ctx, dev), r(ctx, dev), acc(ctx, dev);
+		MqclMask mask(ctx, dev);
+		GPLE_TRY(mqcl_mask_plan(ctx, st, num_pes, g, n, dev, mask));
+		GPLE_HIP(ctx, xs.in(x, n_grids));
+		GPLE_HIP(ctx, r.inout(rho, doubles));
+		GPLE_HIP(ctx, acc.inout(absorbed_p, 2 * static_cast<size_t>(num_pes) * n_grids));
+		GPLE_HIP(ctx, launch_mqcl_absorb(st, mqcl_mask_args(num_pes, pes, n, n_left, xs.p, mask, r.p, acc.p)));
+		GPLE_HIP(ctx, r.back());
+		GPLE_HIP(ctx, acc.back());
+		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
+		return GPLE_OK;
+	}
+
+	int gple_mqcl_evolve_absorbing(gple_ctx* ctx, int num_pes, int model, const double* x, const double* p, size_t n_grids, double mass, double length_x,
+		double length_p, double dt, size_t n_steps, size_t mask_every, const double* g, size_t n_left, unsigned flags, double* rho, double* absorbed_p)
+	{
+		PesModel pes;
+		if (!ctx || !mqcl_size_ok(ctx, num_pes, model, n_grids, &pes) || !x || !p || !rho || !(mass > 0.0) || !std::isfinite(mass) || !(length_x > 0.0) ||
+			!std::isfinite(length_x) || !(length_p > 0.0) || !std::isfinite(length_p) || !std::isfinite(dt) || n_steps > (1ul << 40) || mask_every == 0 ||
+			n_steps % mask_every != 0 || n_left > n_grids || !g || !absorbed_p)
+			return GPLE_ERR_BAD_ARG;
+		GPLE_OPEN(ctx);
+		if (n_steps == 0) return GPLE_OK;
+		const bool dev = flags & GPLE_IO_DEVICE;
+		const int n = static_cast<int>(n_grids);
+		const size_t plane = n_grids * n_grids, doubles = 2 * static_cast<size_t>(num_pes) * num_pes * plane;
+		GPLE_CALL(ctx);
+		if (!pes_resolve(ctx, num_pes, model, &pes)) return GPLE_ERR_BAD_ARG; // under the call lock, which gple_pes_undefine takes: the table outlives the enqueue
+		hipStream_t st = ctx->stream;
+		Staged xs(ctx, dev), pp(ctx, dev), r(ctx, dev), acc(ctx, dev);
+		Scratch tables(ctx), tr(ctx);
+		MqclMask mask(ctx, dev);
+		GPLE_TRY(mqcl_mask_plan(ctx, st, num_pes, g, n, dev, mask));
+		GPLE_TRY(mqcl_tables(ctx, st, num_pes, pes, x, n, dt / 2.0, true, xs, tables));
+		GPLE_HIP(ctx, tr.get(2 * plane * (num_pes * (num_pes + 1) / 2)));
+		GPLE_HIP(ctx, pp.in(p, n_grids));
+		GPLE_HIP(ctx, r.inout(rho, doubles));
+		GPLE_HIP(ctx, acc.inout(absorbed_p, 2 * static_cast<size_t>(num_pes) * n_grids));
+		MqclEvolveArgs e{};
+		e.num_pes = num_pes, e.n = n, e.n_steps = static_cast<long>(mask_every), e.rho = r.p, e.transposed = tr.p, e.table = tables.p, e.p = pp.p;
+		e.mass = mass, e.length_x = length_x, e.length_p = length_p, e.dt = dt;
+		const MqclAbsorbArgs a = mqcl_mask_args(num_pes, pes, n, n_left, xs.p, mask, r.p, acc.p);
+		// per block what gple_mqcl_absorb, gple_mqcl_evolve (mask_every steps), gple_mqcl_absorb enqueue, in that order: the same bits
+		timer_start(ctx, GPLE_TIMER_MQCL);
+		for (size_t block = 0; block < n_steps / mask_every; ++block)
+		{
+			GPLE_HIP(ctx, launch_mqcl_absorb(st, a));
+			GPLE_HIP(ctx, launch_mqcl_evolve(st, e));
+			GPLE_HIP(ctx, launch_mqcl_lower(st, num_pes, n, r.p));
+			GPLE_HIP(ctx, launch_mqcl_absorb(st, a));
+		}
+		timer_stop(ctx, GPLE_TIMER_MQCL);
+		GPLE_HIP(ctx, r.back());
+		GPLE_HIP(ctx, acc.back());
+		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
+		return GPLE_OK;
+	}
+
 	int gple_mqcl_observe(gple_ctx* ctx, int num_pes, int model, const double* x, const double* p, size_t n_grids, double mass, double dx, double dp,
 		unsigned flags, const double* rho_dia, double* rho_adia, double* averages, double* populations)
 	{

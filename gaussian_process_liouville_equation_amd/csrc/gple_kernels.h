@@ -416,6 +416,22 @@ namespace gple
 	size_t mqcl_observe_work_doubles(int num_pes, int n);
 	hipError_t launch_mqcl_observe(hipStream_t s, int num_pes, int n, const double* tables, const double* x, const double* p, double mass, double dxdp,
 		const double* rho, double* adia, double* work, double* out);
+	// ---- the absorbing boundary of the MQCLE run (gple_mqcl_absorb.hip): rho <- (1 - g_i) rho on the rows with g_i != 0, what leaves booked ----
+	// rows (mqcl_absorb_rows_doubles): the ascending list of those rows, written by launch_mqcl_absorb_rows; count: their number (the host's)
+	size_t mqcl_absorb_rows_doubles(int n);
+	size_t mqcl_absorb_slab_doubles(int num_pes, int n, int count);
+	hipError_t launch_mqcl_absorb_rows(hipStream_t s, const double* g, int n, int* rows);
+	struct MqclAbsorbArgs
+	{
+		int num_pes, n, n_left, count;
+		PesModel model;
+		const double *x, *g; // n each
+		const int* rows;
+		double* slab;       // mqcl_absorb_slab_doubles: g_i rho^adia_aa(x_i, p_j) as [row][a][j]
+		double* rho;        // num_pes^2 x n x n (re, im) pairs, diabatic, masked in place
+		double* absorbed_p; // 2 x num_pes x n, [side][a][j]: the slab's rows are added to it
+	};
+	hipError_t launch_mqcl_absorb(hipStream_t s, const MqclAbsorbArgs& a);
 
 	// ---- trajectory ensembles (gple_hop.hip): num_pes = 2 or 3, one thread per trajectory, every pointer a device pointer ----
 	struct HopEnsemble // x, p: n doubles; b: n x num_pes (re, im) pairs; surface, status: n ints; counters use the index offset + i

@@ -150,7 +150,7 @@ typedef enum gple_timer {
 	GPLE_TIMER_PREDICT_KERNEL = 2, /* the MFMA row-norm kernel of *_predict alone; count = its launches */
 	GPLE_TIMER_DERIV_GEMM = 3,     /* the dK * K^-1 MFMA GEMM of a GPLE_CALC_DERIVATIVE fit (kernel.cpp:354); count = its launches */
 	GPLE_TIMER_WIGNER = 4,         /* the MFMA kernel of gple_wigner alone (all T output times of a call); count = its launches */
-	GPLE_TIMER_MQCL = 5,           /* the step kernels of one gple_mqcl_evolve call (all its steps, no set-up); count = its calls */
+	GPLE_TIMER_MQCL = 5,           /* the step kernels of one gple_mqcl_evolve call (all its steps, no set-up), or every block and mask of one gple_mqcl_evolve_absorbing call; count = its calls */
 	GPLE_TIMER_RECON = 6,          /* the device work of one gple_nlml_weights / gple_grid_survey / gple_grid_select / gple_grid_reconstruct call (and of their _cross forms); count = calls */
 	GPLE_TIMER_FORMAT = 7,         /* the three kernels of one gple_format_g call (no staging, no copy of the text); count = calls */
 	GPLE_TIMER_PARSE = 8,          /* the kernels of one gple_parse_g call (three, or two when it only counts; no staging, no copies); count = calls */
@@ -536,6 +536,25 @@ int gple_mqcl_evolve(gple_ctx* ctx, int num_pes, int model, const double* x, con
  * same input return the same bits. */
 int gple_mqcl_observe(gple_ctx* ctx, int num_pes, int model, const double* x, const double* p, size_t n, double mass, double dx, double dp,
 	unsigned flags, const double* rho_dia, double* rho_adia, double* averages, double* populations);
+/* The absorbing boundary of the MQCLE run: a complex absorbing potential -i W(x), a multiple of the identity in surface space,
+ * damps every element pointwise at the order of the MQCLE's own truncation, rho(x, p) <- exp(-2 W(x) tau / hbar) rho(x, p), split symmetrically
+ * around a block of tau / dt Trotter steps.  g (n values in [0, 1]) is the half-mask, g_i = 1 - exp(-W(x_i) tau / hbar): gple_mqcl_absorb
+ * replaces every stored double of the rows with g_i != 0 by (1 - g_i) times itself (the difference rounded once per row, the product once
+ * per double: the bits of the host's (1.0 - g) * rho) and leaves the other rows alone.  What it removes is booked where it is removed: the
+ * adiabatic diagonal g_i rho^adia_aa(x_i, p_j), added over the rows i < n_left (side 0) and the others (side 1) in ascending row order and
+ * then ADDED to absorbed_p, 2 num_pes n doubles [side][a][j], unscaled (times dx dp and summed over j: the absorbed population of the channel;
+ * per j: its outgoing momentum distribution).  The caller zeroes absorbed_p once per run.  A figure may be slightly negative, because rho is
+ * no positive density; nothing is clamped.  rho: the diabatic state in the phase.txt layout, in place.  No atomics: two calls on the same input
+ * return the same bits.  A device g is copied to the host once per call (the list of absorbing rows needs its length there).
+ * gple_mqcl_evolve_absorbing runs n_steps / mask_every blocks of absorb(g), mask_every steps of gple_mqcl_evolve, absorb(g) on the context's
+ * stream with no host synchronisation between them; its state and accumulator are the bits of that sequence of separate calls.
+ * GPLE_TIMER_MQCL spans the whole call.
+ * GPLE_ERR_BAD_ARG, with nothing written: num_pes not 2 or 3, a model gple_mqcl_evolve refuses, n outside its range, n_left > n, mask_every
+ * zero or not dividing n_steps, a null array, gple_mqcl_evolve's own cases. */
+int gple_mqcl_absorb(gple_ctx* ctx, int num_pes, int model, const double* x, size_t n, const double* g, size_t n_left, unsigned flags, double* rho,
+	double* absorbed_p);
+int gple_mqcl_evolve_absorbing(gple_ctx* ctx, int num_pes, int model, const double* x, const double* p, size_t n, double mass, double length_x,
+	double length_p, double dt, size_t n_steps, size_t mask_every, const double* g, size_t n_left, unsigned flags, double* rho, double* absorbed_p);
 
 /* ---- fewest-switches surface hopping (Tully, J. Chem. Phys. 93, 1061 (1990); no code of the reference's) ------------------ */
 /* An ensemble of n independent trajectories, one thread each.  A trajectory is x, p, the DIABATIC amplitudes b (num_pes (re, im) pairs), the
