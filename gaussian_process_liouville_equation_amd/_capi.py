@@ -1077,26 +1077,72 @@ class Api:
         ip = C.POINTER(C.c_int)
         return [px, pp, pb] + [C.cast(a.data_ptr(), ip) if flags else a.ctypes.data_as(ip) for a in state[3:]], flags
 
-    def hop_sample(self, num_pes, model, n, seed, x0, p0, sigma_x, sigma_p, surface0=0, trajectory_offset=0, device_out=False):
-        """gple_hop_sample: n trajectories drawn from the Gaussian (x0, sigma_x) x (p0, sigma_p) on the adiabatic surface surface0 -> the ensemble
-        (x, p, b, surface, status).  device_out: tensors on the context's device (the call has completed when it returns)"""
-        num_pes, n = int(num_pes), int(n)
-        if n < 1:
-            raise ValueError("an ensemble has at least one trajectory")
+    # The shared bodies.  Every gple_hop_* function is (ctx, num_pes, <head>, flags, <the ensemble's pointers>, <tail>); `name` is the C name
+    # without its gple_, pointers_of is _hop_pointers, or _hop_mf_pointers for the calls that are never given the surface
+    def _hop_call(self, name, num_pes, head, state, pointers_of, flags=0, tail=()):
+        pointers, io = pointers_of(state)
+        self._check(getattr(self.lib, "gple_" + name)(self.ctx, int(num_pes), *head, flags | io, *pointers, *tail))
+
+    def _hop_own(self, num_pes, state):
+        """_hop_state for a step that writes all five arrays: a numpy ensemble is copied, a device one is evolved in place"""
+        state, n = self._hop_state(int(num_pes), state)
+        return (state if _on_device(state[0]) else tuple(a.copy() for a in state)), n
+
+    def _hop_empty(self, num_pes, n, device_out):
         if device_out:
             import torch
             where = torch.device("cuda", self.device)
-            state = (torch.empty(n, dtype=torch.float64, device=where), torch.empty(n, dtype=torch.float64, device=where),
-                     torch.empty((n, num_pes), dtype=torch.complex128, device=where), torch.empty(n, dtype=torch.int32, device=where),
-                     torch.empty(n, dtype=torch.int32, device=where))
-        else:
-            state = (np.empty(n), np.empty(n), np.empty((n, num_pes), dtype=np.complex128), np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32))
-        pointers, flags = self._hop_pointers(state)
-        self._check(self.lib.gple_hop_sample(self.ctx, num_pes, int(model), n, int(trajectory_offset), int(seed), float(x0), float(p0), float(sigma_x),
-                                             float(sigma_p), int(surface0), flags, *pointers))
+            return (torch.empty(n, dtype=torch.float64, device=where), torch.empty(n, dtype=torch.float64, device=where),
+                    torch.empty((n, num_pes), dtype=torch.complex128, device=where), torch.empty(n, dtype=torch.int32, device=where),
+                    torch.empty(n, dtype=torch.int32, device=where))
+        return (np.empty(n), np.empty(n), np.empty((n, num_pes), dtype=np.complex128), np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32))
+
+    def _hop_draw(self, name, num_pes, n, head, device_out):
+        """a sample: a new ensemble of n trajectories, filled when this returns; head is what stands between num_pes and the flags"""
+        state = self._hop_empty(int(num_pes), n, device_out)
+        self._hop_call(name, num_pes, head, state, self._hop_pointers)
         if device_out:
             self.synchronize()
         return state
+
+    @staticmethod
+    def _hop_packet(model, n, trajectory_offset, seed, x0, p0, sigma_x, sigma_p, surface0):
+        """n and the head of a sample from one packet"""
+        n = int(n)
+        if n < 1:
+            raise ValueError("an ensemble has at least one trajectory")
+        return n, (int(model), n, int(trajectory_offset), int(seed), float(x0), float(p0), float(sigma_x), float(sigma_p), int(surface0))
+
+    @staticmethod
+    def _hop_packets(model, n_per_group, trajectory_offset, seed, packets, surface0):
+        """n and the head of a sample from a table of packets"""
+        n_per_group, packets = int(n_per_group), _f64(packets)
+        if packets.ndim != 2 or packets.shape[1] != 4 or packets.shape[0] < 1 or n_per_group < 1:
+            raise ValueError("packets is (n_groups, 4) with n_groups >= 1, and a group has at least one trajectory")
+        n_groups = packets.shape[0]
+        return n_groups * n_per_group, (int(model), n_groups, n_per_group, int(trajectory_offset), int(seed), _ptr(packets), int(surface0))  # the pointer holds the table
+
+    def _hop_sums(self, name, num_pes, head, state, pointers_of, width):
+        """an observe: the sums on the side the ensemble is on, then on the host"""
+        out = _like(state[0], width)
+        (po,), _ = _io(out)
+        self._hop_call(name, num_pes, head, state, pointers_of, tail=(po,))
+        if _on_device(out):
+            self.synchronize()
+            return out.cpu().numpy()
+        return out
+
+    def _hop_sums_groups(self, name, num_pes, head, state, pointers_of, n_groups, width):
+        """a grouped observe: the library brings the rows to the host itself"""
+        out = np.empty((n_groups, width))
+        self._hop_call(name, num_pes, head, state, pointers_of, tail=(_ptr(out),))
+        return out
+
+    def hop_sample(self, num_pes, model, n, seed, x0, p0, sigma_x, sigma_p, surface0=0, trajectory_offset=0, device_out=False):
+        """gple_hop_sample: n trajectories drawn from the Gaussian (x0, sigma_x) x (p0, sigma_p) on the adiabatic surface surface0 -> the ensemble
+        (x, p, b, surface, status).  device_out: tensors on the context's device (the call has completed when it returns)"""
+        n, head = self._hop_packet(model, n, trajectory_offset, seed, x0, p0, sigma_x, sigma_p, surface0)
+        return self._hop_draw("hop_sample", num_pes, n, head, device_out)
 
     @staticmethod
     def _hop_decoherence(decoherence):
@@ -1113,31 +1159,22 @@ class Api:
         device tensors: evolves the ensemble in place (asynchronously on the context's stream) and returns it.  reverse: GPLE_HOP_REVERSE.
         decoherence: None is gple_hop_evolve itself; "edc", "collapse_hop", "collapse_attempt" ("none", or a GPLE_HOP_DC_* integer) go through
         gple_hop_evolve_dc, the step with the decoherence correction 6a, edc_c (Hartree) being the constant of mode "edc" alone"""
-        state, n = self._hop_state(int(num_pes), state)
-        if not _on_device(state[0]):
-            state = tuple(a.copy() for a in state)
-        pointers, flags = self._hop_pointers(state)
-        head = (self.ctx, int(num_pes), int(model), n, int(trajectory_offset), int(seed), float(mass), float(dt), int(first_step), int(n_steps), float(x_left),
-                float(x_right))
-        flags |= HOP_REVERSE if reverse else 0
-        if decoherence is None:
-            self._check(self.lib.gple_hop_evolve(*head, flags, *pointers))
-        else:
-            self._check(self.lib.gple_hop_evolve_dc(*head, self._hop_decoherence(decoherence), float(edc_c), flags, *pointers))
+        state, n = self._hop_own(num_pes, state)
+        head = (int(model), n, int(trajectory_offset), int(seed), float(mass), float(dt), int(first_step), int(n_steps), float(x_left), float(x_right))
+        self._hop_fssh_step("hop_evolve", num_pes, head, state, reverse, decoherence, edc_c)
         return state
+
+    def _hop_fssh_step(self, name, num_pes, head, state, reverse, decoherence, edc_c, tail=()):
+        """gple_<name>, or with a decoherence gple_<name>_dc, whose head ends in the mode and edc_c"""
+        if decoherence is not None:
+            name, head = name + "_dc", head + (self._hop_decoherence(decoherence), float(edc_c))
+        self._hop_call(name, num_pes, head, state, self._hop_pointers, HOP_REVERSE if reverse else 0, tail)
 
     def hop_observe(self, num_pes, model, state, mass):
         """gple_hop_observe -> the 4 num_pes + 3 sums as a numpy array: counts [status][surface] (3 num_pes), sum |c_k|^2 (num_pes), sum x, sum p,
         sum (p^2 / 2 mass + E_surface).  With device tensors only these numbers cross"""
         state, n = self._hop_state(int(num_pes), state)
-        out = _like(state[0], 4 * int(num_pes) + 3)
-        pointers, flags = self._hop_pointers(state)
-        (po,), _ = _io(out)
-        self._check(self.lib.gple_hop_observe(self.ctx, int(num_pes), int(model), n, float(mass), flags, *pointers, po))
-        if _on_device(out):
-            self.synchronize()
-            return out.cpu().numpy()
-        return out
+        return self._hop_sums("hop_observe", num_pes, (int(model), n, float(mass)), state, self._hop_pointers, 4 * int(num_pes) + 3)
 
     @staticmethod
     def _hop_grid(num_pes, grid):
@@ -1167,8 +1204,10 @@ class Api:
         per pair a < b, then [binned, outside].  numpy arrays for a numpy ensemble, a tensor on the GPU for a device one.  acc=None starts from
         zero; a given acc is added to (GPLE_HOP_ACCUMULATE): numpy returns the sum as a copy, a tensor is added to in place (asynchronously on
         the context's stream) and returned.  bin_all: GPLE_HOP_BIN_ALL, finished trajectories too"""
-        num_pes = int(num_pes)
-        state, n = self._hop_state(num_pes, state)
+        state, n = self._hop_state(int(num_pes), state)
+        return self._hop_bin("hop_bin", int(num_pes), model, state, n, self._hop_pointers, grid, acc, bin_all)
+
+    def _hop_bin(self, name, num_pes, model, state, n, pointers_of, grid, acc, bin_all):
         grid, words = self._hop_grid(num_pes, grid)
         flags = HOP_BIN_ALL if bin_all else 0
         if acc is None:
@@ -1180,19 +1219,20 @@ class Api:
             if not _on_device(acc):
                 acc = np.array(acc, dtype=np.int64)
         acc, pa, _ = self._hop_acc(acc, words)
-        pointers, io = self._hop_pointers(state)
-        self._check(self.lib.gple_hop_bin(self.ctx, num_pes, int(model), n, *grid, flags | io, *pointers, pa))
+        self._hop_call(name, num_pes, (int(model), n, *grid), state, pointers_of, flags, (pa,))
         return acc
 
     def hop_density(self, num_pes, grid, acc, n_norm):
         """gple_hop_density: the accumulator of hop_bin as the adiabatic density (num_pes, num_pes, n_x, n_p) complex, the phase.txt layout, on the
         side acc is on (a tensor: asynchronously on the context's stream); n_norm: the size of the whole ensemble"""
-        num_pes = int(num_pes)
+        return self._hop_density("hop_density", int(num_pes), grid, acc, n_norm)
+
+    def _hop_density(self, name, num_pes, grid, acc, n_norm):
         grid, words = self._hop_grid(num_pes, grid)
         acc, pa, flags = self._hop_acc(acc, words)
         rho = _like(acc, (num_pes, num_pes, grid[2], grid[5]), np.complex128)
         (pr,), _ = _io(rho)
-        self._check(self.lib.gple_hop_density(self.ctx, num_pes, grid[2], grid[5], grid[1], grid[4], int(n_norm), flags, pa, pr))
+        self._check(getattr(self.lib, "gple_" + name)(self.ctx, num_pes, grid[2], grid[5], grid[1], grid[4], int(n_norm), flags, pa, pr))
         return rho
 
     # ---- grouped ensembles (gple_hop_*_groups; DESIGN.md §17, "A curve in one launch", driven by hopping.scan) --------------------------------
@@ -1205,29 +1245,36 @@ class Api:
             raise ValueError("a grouped ensemble holds a whole number of groups of n_per_group >= 1 trajectories")
         return n // n_per_group, n_per_group
 
+    @staticmethod
+    def _hop_dt(dt, n_groups):
+        dt = _f64(dt)
+        if dt.shape != (n_groups,):
+            raise ValueError("dt has one time step per group")
+        return dt
+
+    @staticmethod
+    def _hop_hops(hops, n, dev):
+        """the counters of a grouped step as (hops, pointer): None and a null pointer, a device tensor as it is, or a copy of a numpy array"""
+        ip = C.POINTER(C.c_int)
+        if hops is None:
+            return None, None
+        if _on_device(hops) != dev:
+            raise ValueError("hops lives on the side the ensemble is on")
+        if dev:
+            if not hops.is_cuda or not hops.is_contiguous() or str(hops.dtype) != "torch.int32" or tuple(hops.shape) != (n, 2):
+                raise ValueError("device hops is a contiguous int32 tensor of shape (n, 2) on the GPU")
+            return hops, C.cast(hops.data_ptr(), ip)
+        hops = np.array(hops, dtype=np.int32, order="C")
+        if hops.shape != (n, 2):
+            raise ValueError("hops has shape (n, 2)")
+        return hops, hops.ctypes.data_as(ip)
+
     def hop_sample_groups(self, num_pes, model, n_per_group, seed, packets, surface0=0, trajectory_offset=0, device_out=False):
         """gple_hop_sample_groups: n_per_group trajectories per row (x0, p0, sigma_x, sigma_p) of packets -> the ensemble (x, p, b, surface,
         status) of len(packets) n_per_group trajectories.  A sigma may be 0: the coordinate is then the centre exactly.  device_out: tensors on
         the context's device (the call has completed when it returns)"""
-        num_pes, n_per_group, packets = int(num_pes), int(n_per_group), _f64(packets)
-        if packets.ndim != 2 or packets.shape[1] != 4 or packets.shape[0] < 1 or n_per_group < 1:
-            raise ValueError("packets is (n_groups, 4) with n_groups >= 1, and a group has at least one trajectory")
-        n_groups = packets.shape[0]
-        n = n_groups * n_per_group
-        if device_out:
-            import torch
-            where = torch.device("cuda", self.device)
-            state = (torch.empty(n, dtype=torch.float64, device=where), torch.empty(n, dtype=torch.float64, device=where),
-                     torch.empty((n, num_pes), dtype=torch.complex128, device=where), torch.empty(n, dtype=torch.int32, device=where),
-                     torch.empty(n, dtype=torch.int32, device=where))
-        else:
-            state = (np.empty(n), np.empty(n), np.empty((n, num_pes), dtype=np.complex128), np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32))
-        pointers, flags = self._hop_pointers(state)
-        self._check(self.lib.gple_hop_sample_groups(self.ctx, num_pes, int(model), n_groups, n_per_group, int(trajectory_offset), int(seed), _ptr(packets),
-                                                    int(surface0), flags, *pointers))
-        if device_out:
-            self.synchronize()
-        return state
+        n, head = self._hop_packets(model, n_per_group, trajectory_offset, seed, packets, surface0)
+        return self._hop_draw("hop_sample_groups", num_pes, n, head, device_out)
 
     def hop_evolve_groups(self, num_pes, model, state, n_per_group, seed, mass, dt, first_step, n_steps, x_left, x_right, reverse=False, trajectory_offset=0,
                           hops=None, decoherence=None, edc_c=0.1):
@@ -1236,35 +1283,13 @@ class Api:
         returns it.  hops (None, or int32 (n, 2) on the side the ensemble is on): the hops taken and the frustrated hops of the call are added
         to it; the return value is then (state, hops), a numpy hops being a copy.  reverse: GPLE_HOP_REVERSE.  decoherence, edc_c: as hop_evolve
         (None is gple_hop_evolve_groups itself, anything else goes through gple_hop_evolve_groups_dc)"""
-        state, n = self._hop_state(int(num_pes), state)
+        state, n = self._hop_own(num_pes, state)
         n_groups, n_per_group = self._hop_groups(n, n_per_group)
-        dt = _f64(dt)
-        if dt.shape != (n_groups,):
-            raise ValueError("dt has one time step per group")
-        dev = _on_device(state[0])
-        if not dev:
-            state = tuple(a.copy() for a in state)
-        pointers, flags = self._hop_pointers(state)
-        ip, ph = C.POINTER(C.c_int), None
-        if hops is not None:
-            if _on_device(hops) != dev:
-                raise ValueError("hops lives on the side the ensemble is on")
-            if dev:
-                if not hops.is_cuda or not hops.is_contiguous() or str(hops.dtype) != "torch.int32" or tuple(hops.shape) != (n, 2):
-                    raise ValueError("device hops is a contiguous int32 tensor of shape (n, 2) on the GPU")
-                ph = C.cast(hops.data_ptr(), ip)
-            else:
-                hops = np.array(hops, dtype=np.int32, order="C")
-                if hops.shape != (n, 2):
-                    raise ValueError("hops has shape (n, 2)")
-                ph = hops.ctypes.data_as(ip)
-        head = (self.ctx, int(num_pes), int(model), n_groups, n_per_group, int(trajectory_offset), int(seed), float(mass), _ptr(dt), int(first_step), int(n_steps),
-                float(x_left), float(x_right))
-        flags |= HOP_REVERSE if reverse else 0
-        if decoherence is None:
-            self._check(self.lib.gple_hop_evolve_groups(*head, flags, *pointers, ph))
-        else:
-            self._check(self.lib.gple_hop_evolve_groups_dc(*head, self._hop_decoherence(decoherence), float(edc_c), flags, *pointers, ph))
+        dt = self._hop_dt(dt, n_groups)
+        hops, ph = self._hop_hops(hops, n, _on_device(state[0]))
+        head = (int(model), n_groups, n_per_group, int(trajectory_offset), int(seed), float(mass), _ptr(dt), int(first_step), int(n_steps), float(x_left),
+                float(x_right))
+        self._hop_fssh_step("hop_evolve_groups", num_pes, head, state, reverse, decoherence, edc_c, (ph,))
         return state if hops is None else (state, hops)
 
     def hop_observe_groups(self, num_pes, model, state, n_per_group, mass):
@@ -1272,10 +1297,8 @@ class Api:
         device tensors only these rows cross"""
         state, n = self._hop_state(int(num_pes), state)
         n_groups, n_per_group = self._hop_groups(n, n_per_group)
-        out = np.empty((n_groups, 4 * int(num_pes) + 3))
-        pointers, flags = self._hop_pointers(state)
-        self._check(self.lib.gple_hop_observe_groups(self.ctx, int(num_pes), int(model), n_groups, n_per_group, float(mass), flags, *pointers, _ptr(out)))
-        return out
+        return self._hop_sums_groups("hop_observe_groups", num_pes, (int(model), n_groups, n_per_group, float(mass)), state, self._hop_pointers, n_groups,
+                                     4 * int(num_pes) + 3)
 
     # ---- Ehrenfest (mean-field) trajectories (gple_hop_*_mf; DESIGN.md §17, "Mean-field (Ehrenfest) trajectories") ------------------------------
     # The ensemble is the 5-tuple hop_sample returns.  A mean-field trajectory has no active surface: `surface` is never passed down and comes
@@ -1295,49 +1318,41 @@ class Api:
             x, p, b, status = (np.array(a) for a in (x, p, b, status))
         return (x, p, b, state[3], status), n
 
+    def _hop_step(self, name, num_pes, model, state, n, pointers_of, n_per_group, mass, dt, n_steps, x_left, x_right, extra=()):
+        """the step of the methods that need no seed (_mf, _sqc, _mash): n_per_group None is the plain form, otherwise dt has a time step per
+        group; extra ends the head"""
+        if n_per_group is None:
+            size, dt = (n,), float(dt)
+        else:
+            size = self._hop_groups(n, n_per_group)
+            dt = _ptr(self._hop_dt(dt, size[0]))
+        self._hop_call(name, num_pes, (int(model), *size, float(mass), dt, int(n_steps), float(x_left), float(x_right), *extra), state, pointers_of)
+        return state
+
     def hop_evolve_mf(self, num_pes, model, state, mass, dt, n_steps, x_left, x_right):
         """gple_hop_evolve_mf: n_steps mean-field steps of every running trajectory (the force b^dagger Fd b, no hops, nothing random).  numpy:
         returns the evolved copy; device tensors: evolves the ensemble in place (asynchronously on the context's stream) and returns it"""
         state, n = self._hop_mf_state(num_pes, state, True)
-        pointers, flags = self._hop_mf_pointers(state)
-        self._check(self.lib.gple_hop_evolve_mf(self.ctx, int(num_pes), int(model), n, float(mass), float(dt), int(n_steps), float(x_left), float(x_right), flags,
-                                                *pointers))
-        return state
+        return self._hop_step("hop_evolve_mf", num_pes, model, state, n, self._hop_mf_pointers, None, mass, dt, n_steps, x_left, x_right)
 
     def hop_evolve_groups_mf(self, num_pes, model, state, n_per_group, mass, dt, n_steps, x_left, x_right):
         """gple_hop_evolve_groups_mf: hop_evolve_mf with the time step dt[g] for group g; a group's state has the bits hop_evolve_mf gives for
         that slice.  numpy: returns the evolved copy; device tensors: in place"""
         state, n = self._hop_mf_state(num_pes, state, True)
-        n_groups, n_per_group = self._hop_groups(n, n_per_group)
-        dt = _f64(dt)
-        if dt.shape != (n_groups,):
-            raise ValueError("dt has one time step per group")
-        pointers, flags = self._hop_mf_pointers(state)
-        self._check(self.lib.gple_hop_evolve_groups_mf(self.ctx, int(num_pes), int(model), n_groups, n_per_group, float(mass), _ptr(dt), int(n_steps),
-                                                       float(x_left), float(x_right), flags, *pointers))
-        return state
+        return self._hop_step("hop_evolve_groups_mf", num_pes, model, state, n, self._hop_mf_pointers, n_per_group, mass, dt, n_steps, x_left, x_right)
 
     def hop_observe_mf(self, num_pes, model, state, mass):
         """gple_hop_observe_mf -> the 3 num_pes + 6 sums as a numpy array: weights [status][k] = sum |c_k|^2 over the trajectories of that status
         (3 num_pes), the counts per status (3), sum x, sum p, sum (p^2 / 2 mass + sum_k |c_k|^2 E_k).  With device tensors only these cross"""
         state, n = self._hop_mf_state(num_pes, state, False)
-        out = _like(state[0], 3 * int(num_pes) + 6)
-        pointers, flags = self._hop_mf_pointers(state)
-        (po,), _ = _io(out)
-        self._check(self.lib.gple_hop_observe_mf(self.ctx, int(num_pes), int(model), n, float(mass), flags, *pointers, po))
-        if _on_device(out):
-            self.synchronize()
-            return out.cpu().numpy()
-        return out
+        return self._hop_sums("hop_observe_mf", num_pes, (int(model), n, float(mass)), state, self._hop_mf_pointers, 3 * int(num_pes) + 6)
 
     def hop_observe_groups_mf(self, num_pes, model, state, n_per_group, mass):
         """gple_hop_observe_groups_mf -> (n_groups, 3 num_pes + 6) numpy array, row g the sums of hop_observe_mf over group g (the same bits)"""
         state, n = self._hop_mf_state(num_pes, state, False)
         n_groups, n_per_group = self._hop_groups(n, n_per_group)
-        out = np.empty((n_groups, 3 * int(num_pes) + 6))
-        pointers, flags = self._hop_mf_pointers(state)
-        self._check(self.lib.gple_hop_observe_groups_mf(self.ctx, int(num_pes), int(model), n_groups, n_per_group, float(mass), flags, *pointers, _ptr(out)))
-        return out
+        return self._hop_sums_groups("hop_observe_groups_mf", num_pes, (int(model), n_groups, n_per_group, float(mass)), state, self._hop_mf_pointers, n_groups,
+                                     3 * int(num_pes) + 6)
 
     def hop_bin_mf(self, num_pes, model, state, grid, acc=None, bin_all=False):
         """gple_hop_bin_mf: hop_bin from the amplitudes alone (the state's surface is ignored and never passed down) -> acc, int64 with the
@@ -1345,33 +1360,13 @@ class Api:
         planes of 2^32 c_a conj(c_b) per pair a < b, then [binned, outside].  acc and bin_all as hop_bin: numpy for a numpy ensemble, a tensor
         on the GPU for a device one; a given acc is added to (GPLE_HOP_ACCUMULATE), numpy as a copy, a tensor in place.  At most 2^31
         trajectories per call, and per accumulator"""
-        num_pes = int(num_pes)
         state, n = self._hop_mf_state(num_pes, state, False)
-        grid, words = self._hop_grid(num_pes, grid)
-        flags = HOP_BIN_ALL if bin_all else 0
-        if acc is None:
-            acc = _like(state[0], words, np.int64)
-        else:
-            flags |= HOP_ACCUMULATE
-            if _on_device(acc) != _on_device(state[0]):
-                raise ValueError("the accumulator lives on the side the ensemble is on")
-            if not _on_device(acc):
-                acc = np.array(acc, dtype=np.int64)
-        acc, pa, _ = self._hop_acc(acc, words)
-        pointers, io = self._hop_mf_pointers(state)
-        self._check(self.lib.gple_hop_bin_mf(self.ctx, num_pes, int(model), n, *grid, flags | io, *pointers, pa))
-        return acc
+        return self._hop_bin("hop_bin_mf", int(num_pes), model, state, n, self._hop_mf_pointers, grid, acc, bin_all)
 
     def hop_density_mf(self, num_pes, grid, acc, n_norm):
         """gple_hop_density_mf: the accumulator of hop_bin_mf as the adiabatic density (num_pes, num_pes, n_x, n_p) complex, the phase.txt
         layout, on the side acc is on (a tensor: asynchronously on the context's stream); n_norm: the size of the whole ensemble"""
-        num_pes = int(num_pes)
-        grid, words = self._hop_grid(num_pes, grid)
-        acc, pa, flags = self._hop_acc(acc, words)
-        rho = _like(acc, (num_pes, num_pes, grid[2], grid[5]), np.complex128)
-        (pr,), _ = _io(rho)
-        self._check(self.lib.gple_hop_density_mf(self.ctx, num_pes, grid[2], grid[5], grid[1], grid[4], int(n_norm), flags, pa, pr))
-        return rho
+        return self._hop_density("hop_density_mf", int(num_pes), grid, acc, n_norm)
 
     # ---- symmetrical quasi-classical trajectories (gple_hop_*_sqc; DESIGN.md §17, "Symmetrical quasi-classical trajectories") ----------------------
     # The ensemble is the same 5-tuple; b holds the mapping amplitudes, which are not normalised.  The samples write surface (= surface0); the
@@ -1390,91 +1385,46 @@ class Api:
             gamma = HOP_WINDOW_GAMMA[window]
         return window, float(gamma)
 
-    def _hop_empty(self, num_pes, n, device_out):
-        if device_out:
-            import torch
-            where = torch.device("cuda", self.device)
-            return (torch.empty(n, dtype=torch.float64, device=where), torch.empty(n, dtype=torch.float64, device=where),
-                    torch.empty((n, num_pes), dtype=torch.complex128, device=where), torch.empty(n, dtype=torch.int32, device=where),
-                    torch.empty(n, dtype=torch.int32, device=where))
-        return (np.empty(n), np.empty(n), np.empty((n, num_pes), dtype=np.complex128), np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32))
-
     def hop_sample_sqc(self, num_pes, model, n, seed, x0, p0, sigma_x, sigma_p, surface0=0, window="triangle", gamma=None, trajectory_offset=0, device_out=False):
         """gple_hop_sample_sqc: x and p as hop_sample draws them (the same bits), the mapping amplitudes b on the start window of the adiabatic
         state surface0 ("square" or "triangle", gamma None: (sqrt(3) - 1) / 2 or 1 / 3) -> the ensemble (x, p, b, surface, status)"""
-        num_pes, n = int(num_pes), int(n)
-        window, gamma = self._hop_window(window, gamma)
-        if n < 1:
-            raise ValueError("an ensemble has at least one trajectory")
-        state = self._hop_empty(num_pes, n, device_out)
-        pointers, flags = self._hop_pointers(state)
-        self._check(self.lib.gple_hop_sample_sqc(self.ctx, num_pes, int(model), n, int(trajectory_offset), int(seed), float(x0), float(p0), float(sigma_x),
-                                                 float(sigma_p), int(surface0), window, gamma, flags, *pointers))
-        if device_out:
-            self.synchronize()
-        return state
+        window = self._hop_window(window, gamma)
+        n, head = self._hop_packet(model, n, trajectory_offset, seed, x0, p0, sigma_x, sigma_p, surface0)
+        return self._hop_draw("hop_sample_sqc", num_pes, n, head + window, device_out)
 
     def hop_sample_groups_sqc(self, num_pes, model, n_per_group, seed, packets, surface0=0, window="triangle", gamma=None, trajectory_offset=0, device_out=False):
         """gple_hop_sample_groups_sqc: hop_sample_sqc per row (x0, p0, sigma_x, sigma_p) of packets, as hop_sample_groups (a sigma may be 0)"""
-        num_pes, n_per_group, packets = int(num_pes), int(n_per_group), _f64(packets)
-        window, gamma = self._hop_window(window, gamma)
-        if packets.ndim != 2 or packets.shape[1] != 4 or packets.shape[0] < 1 or n_per_group < 1:
-            raise ValueError("packets is (n_groups, 4) with n_groups >= 1, and a group has at least one trajectory")
-        n_groups = packets.shape[0]
-        state = self._hop_empty(num_pes, n_groups * n_per_group, device_out)
-        pointers, flags = self._hop_pointers(state)
-        self._check(self.lib.gple_hop_sample_groups_sqc(self.ctx, num_pes, int(model), n_groups, n_per_group, int(trajectory_offset), int(seed), _ptr(packets),
-                                                        int(surface0), window, gamma, flags, *pointers))
-        if device_out:
-            self.synchronize()
-        return state
+        window = self._hop_window(window, gamma)
+        n, head = self._hop_packets(model, n_per_group, trajectory_offset, seed, packets, surface0)
+        return self._hop_draw("hop_sample_groups_sqc", num_pes, n, head + window, device_out)
 
     def hop_evolve_sqc(self, num_pes, model, state, mass, dt, n_steps, x_left, x_right, gamma):
         """gple_hop_evolve_sqc: n_steps steps of every running trajectory on the mapping Hamiltonian (the mean-field step with the force
         b^dagger Fd b - gamma tr Fd).  numpy: returns the evolved copy; device tensors: evolves the ensemble in place and returns it"""
         state, n = self._hop_mf_state(num_pes, state, True)
-        pointers, flags = self._hop_mf_pointers(state)
-        self._check(self.lib.gple_hop_evolve_sqc(self.ctx, int(num_pes), int(model), n, float(mass), float(dt), int(n_steps), float(x_left), float(x_right),
-                                                 float(gamma), flags, *pointers))
-        return state
+        return self._hop_step("hop_evolve_sqc", num_pes, model, state, n, self._hop_mf_pointers, None, mass, dt, n_steps, x_left, x_right, (float(gamma),))
 
     def hop_evolve_groups_sqc(self, num_pes, model, state, n_per_group, mass, dt, n_steps, x_left, x_right, gamma):
         """gple_hop_evolve_groups_sqc: hop_evolve_sqc with the time step dt[g] for group g; a group's state has the bits hop_evolve_sqc gives for
         that slice.  numpy: returns the evolved copy; device tensors: in place"""
         state, n = self._hop_mf_state(num_pes, state, True)
-        n_groups, n_per_group = self._hop_groups(n, n_per_group)
-        dt = _f64(dt)
-        if dt.shape != (n_groups,):
-            raise ValueError("dt has one time step per group")
-        pointers, flags = self._hop_mf_pointers(state)
-        self._check(self.lib.gple_hop_evolve_groups_sqc(self.ctx, int(num_pes), int(model), n_groups, n_per_group, float(mass), _ptr(dt), int(n_steps),
-                                                        float(x_left), float(x_right), float(gamma), flags, *pointers))
-        return state
+        return self._hop_step("hop_evolve_groups_sqc", num_pes, model, state, n, self._hop_mf_pointers, n_per_group, mass, dt, n_steps, x_left, x_right,
+                              (float(gamma),))
 
     def hop_observe_sqc(self, num_pes, model, state, mass, window="triangle", gamma=None):
         """gple_hop_observe_sqc -> the 4 num_pes + 9 sums as a numpy array (hopping.unpack_sqc names them): the trajectories [status][window k],
         per status, per status in no window, sum e_k, sum x, sum p, sum H.  With device tensors only these cross"""
         state, n = self._hop_mf_state(num_pes, state, False)
-        window, gamma = self._hop_window(window, gamma)
-        out = _like(state[0], 4 * int(num_pes) + 9)
-        pointers, flags = self._hop_mf_pointers(state)
-        (po,), _ = _io(out)
-        self._check(self.lib.gple_hop_observe_sqc(self.ctx, int(num_pes), int(model), n, float(mass), window, gamma, flags, *pointers, po))
-        if _on_device(out):
-            self.synchronize()
-            return out.cpu().numpy()
-        return out
+        head = (int(model), n, float(mass), *self._hop_window(window, gamma))
+        return self._hop_sums("hop_observe_sqc", num_pes, head, state, self._hop_mf_pointers, 4 * int(num_pes) + 9)
 
     def hop_observe_groups_sqc(self, num_pes, model, state, n_per_group, mass, window="triangle", gamma=None):
         """gple_hop_observe_groups_sqc -> (n_groups, 4 num_pes + 9) numpy array, row g the sums of hop_observe_sqc over group g (the same bits)"""
         state, n = self._hop_mf_state(num_pes, state, False)
-        window, gamma = self._hop_window(window, gamma)
+        window = self._hop_window(window, gamma)
         n_groups, n_per_group = self._hop_groups(n, n_per_group)
-        out = np.empty((n_groups, 4 * int(num_pes) + 9))
-        pointers, flags = self._hop_mf_pointers(state)
-        self._check(self.lib.gple_hop_observe_groups_sqc(self.ctx, int(num_pes), int(model), n_groups, n_per_group, float(mass), window, gamma, flags, *pointers,
-                                                         _ptr(out)))
-        return out
+        return self._hop_sums_groups("hop_observe_groups_sqc", num_pes, (int(model), n_groups, n_per_group, float(mass), *window), state, self._hop_mf_pointers,
+                                     n_groups, 4 * int(num_pes) + 9)
 
     # ---- MASH trajectories (gple_hop_*_mash; DESIGN.md §17, "MASH trajectories") -------------------------------------------------------------------
     # The ensemble is the same 5-tuple, two levels only.  The samples draw amplitudes of their own; the step needs no seed, step counter or
@@ -1482,70 +1432,30 @@ class Api:
     def hop_sample_mash(self, num_pes, model, n, seed, x0, p0, sigma_x, sigma_p, surface0=0, trajectory_offset=0, device_out=False):
         """gple_hop_sample_mash: x and p as hop_sample draws them (the same bits), the amplitudes b with |S_z| drawn from the density 2 s on the
         side of the adiabatic state surface0 -> the ensemble (x, p, b, surface, status).  num_pes is 2"""
-        num_pes, n = int(num_pes), int(n)
-        if n < 1:
-            raise ValueError("an ensemble has at least one trajectory")
-        state = self._hop_empty(num_pes, n, device_out)
-        pointers, flags = self._hop_pointers(state)
-        self._check(self.lib.gple_hop_sample_mash(self.ctx, num_pes, int(model), n, int(trajectory_offset), int(seed), float(x0), float(p0), float(sigma_x),
-                                                  float(sigma_p), int(surface0), flags, *pointers))
-        if device_out:
-            self.synchronize()
-        return state
+        n, head = self._hop_packet(model, n, trajectory_offset, seed, x0, p0, sigma_x, sigma_p, surface0)
+        return self._hop_draw("hop_sample_mash", num_pes, n, head, device_out)
 
     def hop_sample_groups_mash(self, num_pes, model, n_per_group, seed, packets, surface0=0, trajectory_offset=0, device_out=False):
         """gple_hop_sample_groups_mash: hop_sample_mash per row (x0, p0, sigma_x, sigma_p) of packets, as hop_sample_groups (a sigma may be 0)"""
-        num_pes, n_per_group, packets = int(num_pes), int(n_per_group), _f64(packets)
-        if packets.ndim != 2 or packets.shape[1] != 4 or packets.shape[0] < 1 or n_per_group < 1:
-            raise ValueError("packets is (n_groups, 4) with n_groups >= 1, and a group has at least one trajectory")
-        n_groups = packets.shape[0]
-        state = self._hop_empty(num_pes, n_groups * n_per_group, device_out)
-        pointers, flags = self._hop_pointers(state)
-        self._check(self.lib.gple_hop_sample_groups_mash(self.ctx, num_pes, int(model), n_groups, n_per_group, int(trajectory_offset), int(seed), _ptr(packets),
-                                                         int(surface0), flags, *pointers))
-        if device_out:
-            self.synchronize()
-        return state
+        n, head = self._hop_packets(model, n_per_group, trajectory_offset, seed, packets, surface0)
+        return self._hop_draw("hop_sample_groups_mash", num_pes, n, head, device_out)
 
     def hop_evolve_mash(self, num_pes, model, state, mass, dt, n_steps, x_left, x_right):
         """gple_hop_evolve_mash: n_steps MASH steps of every running trajectory (the active surface follows the amplitudes; nothing random).
         numpy: returns the evolved copy; device tensors: evolves the ensemble in place (asynchronously on the context's stream) and returns it"""
-        state, n = self._hop_state(int(num_pes), state)
-        if not _on_device(state[0]):
-            state = tuple(a.copy() for a in state)
-        pointers, flags = self._hop_pointers(state)
-        self._check(self.lib.gple_hop_evolve_mash(self.ctx, int(num_pes), int(model), n, float(mass), float(dt), int(n_steps), float(x_left), float(x_right), flags,
-                                                  *pointers))
-        return state
+        state, n = self._hop_own(num_pes, state)
+        return self._hop_step("hop_evolve_mash", num_pes, model, state, n, self._hop_pointers, None, mass, dt, n_steps, x_left, x_right)
 
     def hop_evolve_groups_mash(self, num_pes, model, state, n_per_group, mass, dt, n_steps, x_left, x_right, hops=None):
         """gple_hop_evolve_groups_mash: hop_evolve_mash with the time step dt[g] for group g; a group's state has the bits hop_evolve_mash gives
         for that slice.  hops (None, or int32 (n, 2) on the side the ensemble is on): the hops taken and the frustrated hops of the call are
         added to it; the return value is then (state, hops), a numpy hops being a copy"""
-        state, n = self._hop_state(int(num_pes), state)
+        state, n = self._hop_own(num_pes, state)
         n_groups, n_per_group = self._hop_groups(n, n_per_group)
-        dt = _f64(dt)
-        if dt.shape != (n_groups,):
-            raise ValueError("dt has one time step per group")
-        dev = _on_device(state[0])
-        if not dev:
-            state = tuple(a.copy() for a in state)
-        pointers, flags = self._hop_pointers(state)
-        ip, ph = C.POINTER(C.c_int), None
-        if hops is not None:
-            if _on_device(hops) != dev:
-                raise ValueError("hops lives on the side the ensemble is on")
-            if dev:
-                if not hops.is_cuda or not hops.is_contiguous() or str(hops.dtype) != "torch.int32" or tuple(hops.shape) != (n, 2):
-                    raise ValueError("device hops is a contiguous int32 tensor of shape (n, 2) on the GPU")
-                ph = C.cast(hops.data_ptr(), ip)
-            else:
-                hops = np.array(hops, dtype=np.int32, order="C")
-                if hops.shape != (n, 2):
-                    raise ValueError("hops has shape (n, 2)")
-                ph = hops.ctypes.data_as(ip)
-        self._check(self.lib.gple_hop_evolve_groups_mash(self.ctx, int(num_pes), int(model), n_groups, n_per_group, float(mass), _ptr(dt), int(n_steps),
-                                                         float(x_left), float(x_right), flags, *pointers, ph))
+        dt = self._hop_dt(dt, n_groups)
+        hops, ph = self._hop_hops(hops, n, _on_device(state[0]))
+        head = (int(model), n_groups, n_per_group, float(mass), _ptr(dt), int(n_steps), float(x_left), float(x_right))
+        self._hop_call("hop_evolve_groups_mash", num_pes, head, state, self._hop_pointers, tail=(ph,))
         return state if hops is None else (state, hops)
 
     # ---- reconstruction of a gridded density with the NLML GP (test/main_evolve.cpp; gple_nlml_weights / gple_grid_*) -------------------------

@@ -12,19 +12,19 @@ column for column with exact.run(flux=True)'s.
                       _observe_groups): a group per momentum with its own packet and time step; scan.txt
 run() and scan() take decoherence = None (Tully's algorithm as it stands), "edc", "collapse_hop" or "collapse_attempt" and edc_c: the decoherence
 correction of every step (gple_hop_evolve_dc / gple_hop_evolve_groups_dc; DESIGN.md §17, "Decoherence corrections").  The files are the same.
-run() and scan() also take method = "fssh" (the default, everything above) or "ehrenfest": mean-field trajectories from the same sample, the other
-trajectory baseline (gple_hop_evolve_mf / _observe_mf and their _groups forms; DESIGN.md §17, "Mean-field (Ehrenfest) trajectories"), with
-unpack_mf() for their sums: a trajectory carries all its amplitudes and moves on the force averaged over them, without hops or random numbers.
-method = "sqc" with window = "triangle" (the default) or "square" and gamma (None: 1 / 3 or (sqrt(3) - 1) / 2) is the third baseline: the
-Meyer-Miller-Stock-Thoss mapping Hamiltonian run classically from a sample of actions and angles, populations read off by binning the final
-actions into the symmetrical windows of Cotton and Miller (gple_hop_sample_sqc / _evolve_sqc / _observe_sqc and their _groups forms; DESIGN.md
-§17, "Symmetrical quasi-classical trajectories"), with unpack_sqc() for its sums.  window or gamma with another method is a ValueError.
-method = "mash" is the fourth: the mapping approach to surface hopping of Mannouch and Richardson (gple_hop_sample_mash / _evolve_mash and their
-_groups forms; DESIGN.md §17, "MASH trajectories"), two levels only.  It has an active surface, which follows the amplitudes deterministically, so
-the sums, the records and every file are those of "fssh" (gple_hop_observe, unpack(), averages_line, scan_line); all randomness is in its sample.
+run() and scan() are one loop each, written against the record of their method in TABLE (a Method: which api calls sample, evolve and observe,
+how the arguments of the step are built, how its sums are read, what it refuses):
+    "fssh"       the default, everything above
+    "ehrenfest"  mean-field trajectories from the same sample: hop_evolve_mf / hop_observe_mf, unpack_mf(); no hops, nothing random
+    "sqc"        the Meyer-Miller-Stock-Thoss mapping Hamiltonian with the windows of Cotton and Miller: window = "triangle" (the default) or
+                 "square" and gamma (None: 1 / 3 or (sqrt(3) - 1) / 2); hop_sample_sqc / hop_evolve_sqc / hop_observe_sqc, unpack_sqc()
+    "mash"       the mapping approach to surface hopping of Mannouch and Richardson, two levels only: hop_sample_mash / hop_evolve_mash, then
+                 the sums, the records and every file of "fssh"
+each with its _groups forms in scan() (DESIGN.md §17 has a section per method).  A new method is one more record.
 """
 import os
 import time
+from typing import Callable, NamedTuple, Optional
 
 import numpy as np
 
@@ -79,34 +79,6 @@ MASH = "mash"  # the fourth method: a sample and a step of its own, the sums of 
 PHASE_DENSITIES = (None, "mixed", "amplitude")  # run(phase_density=...): None is "mixed"
 
 
-def _method(method, decoherence, reverse_frustrated, phase_grid=None, window=None, gamma=None, num_pes=2, phase_density=None):
-    """method of run() and scan(), checked against the options that need an active surface -> True for the mean-field one, SQC for "sqc", MASH
-    for "mash".  phase_density: the prescription of run()'s phase_grid; "amplitude" needs no active surface, so "ehrenfest" may have a
-    phase_grid with it (and with it alone)"""
-    if method not in METHODS + (SQC, MASH):
-        raise ValueError(f"method is one of {METHODS + (SQC, MASH)}")
-    if phase_density not in PHASE_DENSITIES:
-        raise ValueError('phase_density is None, "mixed" or "amplitude"')
-    if phase_density is not None and phase_grid is None:
-        raise ValueError("phase_density belongs to a phase_grid")
-    if method != SQC and (window is not None or gamma is not None):
-        raise ValueError('window and gamma belong to method="sqc"')
-    if method == "fssh":
-        return False
-    if method == MASH:
-        if decoherence is not None or reverse_frustrated or phase_grid is not None:
-            raise ValueError("mash trajectories need no decoherence correction, always reflect a frustrated hop and (DESIGN.md §17) have no phase_grid")
-        if int(num_pes) != 2:
-            raise ValueError("mash is a two-level method: num_pes = 2")
-        return MASH
-    if method == "ehrenfest" and phase_density == "amplitude":
-        phase_grid = None  # the density from the amplitudes needs no active surface
-    if decoherence is not None or reverse_frustrated or phase_grid is not None:
-        raise ValueError(f"{method} trajectories have no active surface: no decoherence correction, no frustrated hops and (DESIGN.md §17) no phase_grid"
-                         + (' but with phase_density="amplitude"' if method == "ehrenfest" else ""))
-    return True if method == "ehrenfest" else SQC
-
-
 def sqc_window(window, gamma):
     """(GPLE_HOP_WINDOW_*, gamma) of run() and scan(): window "triangle" (None) or "square"; gamma None is the window's customary value, 1 / 3 or
     (sqrt(3) - 1) / 2.  What the library would refuse is a ValueError here, before any call"""
@@ -152,6 +124,108 @@ def sqc_channels(counts, n_status, none):
     channels = np.divide(finished, n_f[..., None, None], out=np.zeros_like(finished), where=n_f[..., None, None] > 0)
     lost = np.divide(none[..., 1:].sum(axis=-1), n_done, out=np.zeros_like(n_done), where=n_done > 0)
     return channels, n_f, lost
+
+
+# ---- the methods: one record each, which run() and scan() are written against ---------------------------------------------------------------------
+# tail below is what a windowed method's calls take beside the others' arguments: sqc_window()'s (code, gamma), else ()
+def _seeded_step(seed, reverse, correction, tail, mass, dt, first_step, n_steps, x_left, x_right):
+    return (seed, mass, dt, first_step, n_steps, x_left, x_right), dict(reverse=reverse, **correction)
+
+
+def _plain_step(seed, reverse, correction, tail, mass, dt, first_step, n_steps, x_left, x_right):
+    return (mass, dt, n_steps, x_left, x_right, *tail[1:]), {}  # windowed: gamma last
+
+
+def _on_surface(sums, num_pes):
+    return sums[..., :num_pes].sum(axis=-1)
+
+
+def _of_status(sums, num_pes):
+    return sums[..., 3 * num_pes]
+
+
+def _counted(sums, num_pes, n):
+    """counts[side][surface] / n (with "ehrenfest" the weights): every trajectory is in the sample"""
+    counts = sums[..., :3 * num_pes].reshape(*sums.shape[:-1], 3, num_pes)
+    return counts[..., 1:, :] / n, np.full(sums.shape[:-1], float(n)), ()
+
+
+def _windowed(sums, num_pes, n):
+    """sqc_channels over the finished and windowed trajectories, and as a new last column the unassigned fraction of the finished ones"""
+    N = num_pes
+    channels, n_f, lost = sqc_channels(sums[..., :3 * N].reshape(*sums.shape[:-1], 3, N), sums[..., 3 * N:3 * N + 3], sums[..., 3 * N + 3:3 * N + 6])
+    return channels, n_f, (lost,)
+
+
+def _sqc_result(result, tail, n_f, last):
+    """no correction to report and no phase_density; the window's code, gamma and what sqc_channels counted (numbers from run(), rows from scan())"""
+    own = (float(n_f), float(last[0])) if np.ndim(n_f) == 0 else (n_f, last[0])
+    result = {key: value for key, value in result.items() if key != "phase_density"}
+    return dict(result, decoherence=None, edc_c=None, window=tail[0], gamma=tail[1], n_finished_windowed=own[0], unassigned_finished=own[1])
+
+
+class Method(NamedTuple):
+    """A trajectory method as run() and scan() see it; the defaults are the sums, records and files of "fssh".  sample, evolve, observe: the
+    suffix of the api attribute, hop_<verb><suffix> in run() and hop_<verb>_groups<suffix> in scan(), looked up on the api when it is called"""
+    sample: str = ""
+    evolve: str = ""
+    observe: str = ""
+    step_args: Callable = _plain_step  # (seed, reverse, correction, tail, mass, dt, first_step, n_steps, x_left, x_right) -> after the ensemble [and n_per_group]; keywords
+    width: Callable = lambda num_pes: 4 * num_pes + 3  # the numbers in a row of sums
+    unpack: Callable = unpack          # unpack, unpack_mf or unpack_sqc (which takes gamma too)
+    line: Callable = averages_line     # (t, rec, n_traj) -> the line of averages.txt
+    running: Callable = _on_surface    # (sums (..., width), num_pes) -> the trajectories still running (...)
+    channels: Callable = _counted      # (sums (..., width), num_pes, n) -> scattered (..., 2, num_pes), the size (...) of the sample behind it, further last columns
+    result: Callable = lambda result, tail, n_f, last: result  # the result all methods share -> the method's
+    counters: bool = False             # the grouped step keeps the (n, 2) counters of hops taken and frustrated
+    windowed: bool = False             # takes window and gamma
+    refusal: Optional[str] = None      # the ValueError of a decoherence correction, reverse_frustrated=True or a phase_grid; None: takes them
+    amplitude_grid: bool = False       # takes a phase_grid with phase_density="amplitude" all the same
+    two_level: bool = False
+
+
+_NO_SURFACE = "{} trajectories have no active surface: no decoherence correction, no frustrated hops and (DESIGN.md §17) no phase_grid"
+TABLE = {
+    "fssh": Method(step_args=_seeded_step, counters=True),
+    "ehrenfest": Method(evolve="_mf", observe="_mf", width=lambda num_pes: 3 * num_pes + 6, unpack=unpack_mf, line=lambda t, rec, n_traj: averages_line_mf(t, rec),
+                        running=_of_status, refusal=_NO_SURFACE.format("ehrenfest") + ' but with phase_density="amplitude"', amplitude_grid=True),
+    SQC: Method(sample="_sqc", evolve="_sqc", observe="_sqc", width=lambda num_pes: 4 * num_pes + 9, unpack=unpack_sqc,
+                line=lambda t, rec, n_traj: averages_line_sqc(t, rec), running=_of_status, channels=_windowed, result=_sqc_result, windowed=True,
+                refusal=_NO_SURFACE.format(SQC)),
+    MASH: Method(sample="_mash", evolve="_mash", counters=True, two_level=True,
+                 refusal="mash trajectories need no decoherence correction, always reflect a frustrated hop and (DESIGN.md §17) have no phase_grid"),
+}
+
+
+def _method(method, decoherence, reverse_frustrated, phase_grid=None, window=None, gamma=None, num_pes=2, phase_density=None):
+    """method of run() and scan(), checked against the options it refuses -> its record.  phase_density: the prescription of run()'s phase_grid;
+    "amplitude" needs no active surface, so "ehrenfest" may have a phase_grid with it (and with it alone)"""
+    if method not in TABLE:
+        raise ValueError(f"method is one of {tuple(TABLE)}")
+    if phase_density not in PHASE_DENSITIES:
+        raise ValueError('phase_density is None, "mixed" or "amplitude"')
+    if phase_density is not None and phase_grid is None:
+        raise ValueError("phase_density belongs to a phase_grid")
+    m = TABLE[method]
+    if not m.windowed and (window is not None or gamma is not None):
+        raise ValueError('window and gamma belong to method="sqc"')
+    if m.amplitude_grid and phase_density == "amplitude":
+        phase_grid = None  # the density from the amplitudes needs no active surface
+    if m.refusal is not None and (decoherence is not None or reverse_frustrated or phase_grid is not None):
+        raise ValueError(m.refusal)
+    if m.two_level and int(num_pes) != 2:
+        raise ValueError(f"{method} is a two-level method: num_pes = 2")
+    return m
+
+
+def _call(api, verb, suffix, grouped=False):
+    """the api's hop_<verb>[_groups]<suffix>, looked up now: an api needs the calls of the methods it is asked for, and no others"""
+    return getattr(api, f"hop_{verb}{'_groups' if grouped else ''}{suffix}")
+
+
+def _head(model, s):
+    """the first column of a scattering line, as exact.run (main.cpp:308-321): ln E for DAC, else p0"""
+    return np.log(s["p0"] ** 2 / 2.0 / s["mass"]) if model == DAC else s["p0"]
 
 
 GRID_KEYS = ("x_first", "dx", "n_x", "p_first", "dp", "n_p")
@@ -202,19 +276,19 @@ def run(api, model=DAC, num_pes=2, ln_energy=0.0, n_traj=10000, seed=0, out_dir=
     one hop_evolve_mf and one hop_observe_mf, whose record is unpack_mf()'s; the run stops when n_status[0] == 0.  An averages.txt line is then
     averages_line_mf (no active-surface columns), and the scattering line holds weights[left][k] / n, weights[right][k] / n and n_status[0] / n
     in the same columns.  decoherence, reverse_frustrated=True or a phase_grid without phase_density="amplitude" is a ValueError with "ehrenfest".
-    method "sqc" with window ("triangle", the default, or "square") and gamma (None: the window's customary value): _run_sqc below; the same
-    options are a ValueError with it, and so are window or gamma with another method.
+    method "sqc" with window ("triangle", the default, or "square") and gamma (None: the window's customary value): hop_sample_sqc, then per output
+    time one hop_evolve_sqc and one hop_observe_sqc, whose record is unpack_sqc()'s; averages.txt holds averages_line_sqc.  The scattering line
+    keeps its columns with channel (side, k) = counts[side][k] / N_f, N_f the finished and windowed trajectories (all 0 where N_f = 0), then
+    n_status[0] / n, and as a new last column the unassigned fraction of the finished trajectories.  The same options are a ValueError with it,
+    and so are window or gamma with another method.
     method "mash": everything of "fssh" (records, files, the scattering line) with hop_sample_mash for the sample and one hop_evolve_mash per
     output time, which takes no seed and no step number.  decoherence, reverse_frustrated=True, a phase_grid, window, gamma or num_pes != 2 with
     it is a ValueError.
     Returns the setup, the records (t and unpack() per output time), stop, and scattering_line: the head of exact.run's final line, the
     fractions that left [left | right][surface], and the fraction still running."""
-    mean_field = _method(method, decoherence, reverse_frustrated, phase_grid, window, gamma, num_pes, phase_density)
+    m = _method(method, decoherence, reverse_frustrated, phase_grid, window, gamma, num_pes, phase_density)
+    tail = sqc_window(window, gamma) if m.windowed else ()  # what follows surface0 in the sample and mass in the observe
     amplitude = phase_density == "amplitude"
-    if mean_field == SQC:
-        return _run_sqc(api, model, num_pes, ln_energy, n_traj, seed, out_dir, dt, surface0, max_outputs, log, window, gamma, setup_kw)
-    mash = mean_field == MASH  # the loop of "fssh" with the sample and the step of its own
-    mean_field = mean_field is True
     setup_kw["boundary"] = exact.ABSORBING
     s = exact.setup(ln_energy, **setup_kw)
     num_pes, n_traj = int(num_pes), int(n_traj)
@@ -225,8 +299,7 @@ def run(api, model=DAC, num_pes=2, ln_energy=0.0, n_traj=10000, seed=0, out_dir=
     correction = {} if decoherence is None else dict(decoherence=decoherence, edc_c=edc_c)
     say = log or (lambda *_: None)
     t0 = time.perf_counter()
-    sample = api.hop_sample_mash if mash else api.hop_sample
-    state = sample(num_pes, model, n_traj, seed, s["x0"], s["p0"], s["sigma_x"], s["sigma_p"], surface0, device_out=True)
+    state = _call(api, "sample", m.sample)(num_pes, model, n_traj, seed, s["x0"], s["p0"], s["sigma_x"], s["sigma_p"], surface0, *tail, device_out=True)
     grid = None if phase_grid is None else phase_grid_of(api, num_pes, model, s, phase_grid)
     files = {}
     if out_dir is not None:
@@ -239,10 +312,8 @@ def run(api, model=DAC, num_pes=2, ln_energy=0.0, n_traj=10000, seed=0, out_dir=
     records, stop, step = [], None, 0
     try:
         while True:
-            if mean_field:
-                rec = unpack_mf(api.hop_observe_mf(num_pes, model, state, s["mass"]), num_pes, n_traj)
-            else:
-                rec = unpack(api.hop_observe(num_pes, model, state, s["mass"]), num_pes, n_traj)
+            sums = np.asarray(_call(api, "observe", m.observe)(num_pes, model, state, s["mass"], *tail), dtype=np.float64)
+            rec = m.unpack(sums, num_pes, n_traj, *tail[1:])
             rec["t"] = step * dt
             if grid is not None:
                 acc = (api.hop_bin_mf if amplitude else api.hop_bin)(num_pes, model, state, grid)
@@ -262,33 +333,25 @@ def run(api, model=DAC, num_pes=2, ln_energy=0.0, n_traj=10000, seed=0, out_dir=
             records.append(rec)
             if files:
                 files["t.txt"].write(exact.fmt(rec["t"]) + "\n")
-                files["averages.txt"].write(averages_line_mf(rec["t"], rec) if mean_field else averages_line(rec["t"], rec, n_traj))
-            if (rec["n_status"][RUNNING] if mean_field else rec["counts"][RUNNING].sum()) == 0:
+                files["averages.txt"].write(m.line(rec["t"], rec, n_traj))
+            if m.running(sums, num_pes) == 0:
                 stop = f"NO TRAJECTORY IS RUNNING, STOP EVOLVING AT {rec['t']:g}"
                 break
             if step + output_step > total_step or (max_outputs is not None and len(records) >= max_outputs):
                 break
-            if mean_field:
-                state = api.hop_evolve_mf(num_pes, model, state, s["mass"], dt, output_step, s["xmin"], s["xmax"])
-            elif mash:
-                state = api.hop_evolve_mash(num_pes, model, state, s["mass"], dt, output_step, s["xmin"], s["xmax"])
-            else:
-                state = api.hop_evolve(num_pes, model, state, seed, s["mass"], dt, step, output_step, s["xmin"], s["xmax"], reverse=reverse_frustrated,
-                                       **correction)
+            args, keywords = m.step_args(seed, reverse_frustrated, correction, tail, s["mass"], dt, step, output_step, s["xmin"], s["xmax"])
+            state = _call(api, "evolve", m.evolve)(num_pes, model, state, *args, **keywords)
             step += output_step
     finally:
         for f in files.values():
             f.close()
     t_end = time.perf_counter()
     say(stop or "FINISHED ALL OUTPUT TIMES")
-    counts = records[-1]["counts"]
-    head = np.log(s["p0"] ** 2 / 2.0 / s["mass"]) if model == DAC else s["p0"]  # as exact.run (main.cpp:308-321)
-    scattered = np.concatenate([counts[LEFT], counts[RIGHT]]) / n_traj
-    running = records[-1]["n_status"][RUNNING] if mean_field else counts[RUNNING].sum()
-    line = " ".join(exact.fmt(v) for v in [head, *scattered, running / n_traj])
-    return dict(setup=s, dt=dt, output_step=output_step, total_step=total_step, n_traj=n_traj, records=records, stop=stop, state=state,
-                scattered=scattered.reshape(2, num_pes), scattering_line=line, stop_time=records[-1]["t"], steps=step, total_seconds=t_end - t0,
-                decoherence=decoherence, edc_c=edc_c, method=method, phase_density=phase_density)
+    scattered, n_f, last = m.channels(sums, num_pes, n_traj)
+    line = " ".join(exact.fmt(v) for v in [_head(model, s), *scattered.reshape(-1), m.running(sums, num_pes) / n_traj, *last])
+    return m.result(dict(setup=s, dt=dt, output_step=output_step, total_step=total_step, n_traj=n_traj, records=records, stop=stop, state=state,
+                         scattered=scattered, scattering_line=line, stop_time=records[-1]["t"], steps=step, total_seconds=t_end - t0,
+                         decoherence=decoherence, edc_c=edc_c, method=method, phase_density=phase_density), tail, n_f, last)
 
 
 def scan_line(values):
@@ -330,13 +393,14 @@ def scan(api, model=DAC, num_pes=2, ln_energies=None, momenta=None, n_per_group=
     hops and frustrated are 0 (hop_counts is None), energy_drift comes from the mean-field energy p^2 / 2m + sum_k |c_k|^2 E_k.  stderr is then
     an UPPER BOUND: a fraction f is the mean of weights in [0, 1], whose variance is at most f (1 - f).  With fixed=True every trajectory of a
     group is the same trajectory (nothing is random), so n_per_group = 1 is enough.  decoherence or reverse_frustrated=True with "ehrenfest" is
-    a ValueError.  method "sqc" with window and gamma as run(): _scan_sqc below, on the groups made here.  method "mash": everything of "fssh"
+    a ValueError.  method "sqc" with window and gamma as run(), on hop_sample_groups_sqc, hop_evolve_groups_sqc and hop_observe_groups_sqc: channel
+    (side, k) = counts[side][k] / N_f per group (0 where N_f = 0) with stderr sqrt(f (1 - f) / N_f), running = n_status[0] / n_per_group with stderr
+    over n_per_group, hops and frustrated 0, energy_drift from H, and the unassigned fraction of the group's finished trajectories as a new last
+    column of scan.txt.  method "mash": everything of "fssh"
     (scan.txt, the counters of hops taken and frustrated) on hop_sample_groups_mash and hop_evolve_groups_mash; the options run() refuses with it
     are a ValueError here too."""
-    mean_field = _method(method, decoherence, reverse_frustrated, None, window, gamma, num_pes)
-    if mean_field == SQC:
-        window, gamma = sqc_window(window, gamma)
-    mash = mean_field == MASH  # the loop of "fssh" with the sample and the step of its own
+    m = _method(method, decoherence, reverse_frustrated, None, window, gamma, num_pes)
+    tail = sqc_window(window, gamma) if m.windowed else ()  # what follows surface0 in the sample and mass in the observe
     if (ln_energies is None) == (momenta is None):
         raise ValueError("give ln_energies or momenta, one of them")
     given = np.atleast_1d(np.asarray(ln_energies if momenta is None else momenta, dtype=np.float64))
@@ -359,13 +423,10 @@ def scan(api, model=DAC, num_pes=2, ln_energies=None, momenta=None, n_per_group=
     packets = np.array([[s["x0"], s["p0"], 0.0 if fixed else s["sigma_x"], 0.0 if fixed else s["sigma_p"]] for s in setups])
     correction = {} if decoherence is None else dict(decoherence=decoherence, edc_c=edc_c)
     say = log or (lambda *_: None)
-    if mean_field == SQC:
-        return _scan_sqc(api, model, num_pes, n_per_group, seed, surface0, chunk_steps, max_steps, out_dir, say, window, gamma, setups, dts, total_step, packets)
-    mean_field = mean_field is True
     t0 = time.perf_counter()
-    state = (api.hop_sample_groups_mash if mash else api.hop_sample_groups)(num_pes, model, n_per_group, seed, packets, surface0, device_out=True)
+    state = _call(api, "sample", m.sample, True)(num_pes, model, n_per_group, seed, packets, surface0, *tail, device_out=True)
     on_device = hasattr(state[0], "is_cuda")
-    if mean_field:
+    if not m.counters:
         counts = None
     elif on_device:
         import torch
@@ -373,26 +434,28 @@ def scan(api, model=DAC, num_pes=2, ln_energies=None, momenta=None, n_per_group=
         torch.cuda.synchronize(state[0].device)  # the framework's stream has cleared the counters: now the context's may add to them
     else:
         counts = np.zeros((n_groups * n_per_group, 2), dtype=np.int32)
-    width, step, stop = (3 * num_pes + 6 if mean_field else 4 * num_pes + 3), 0, None
-    observe = api.hop_observe_groups_mf if mean_field else api.hop_observe_groups
-    first = rows = np.asarray(observe(num_pes, model, state, n_per_group, s0["mass"]), dtype=np.float64).reshape(n_groups, width)
+    width, step, stop = m.width(num_pes), 0, None
+
+    def observe():
+        sums = _call(api, "observe", m.observe, True)(num_pes, model, state, n_per_group, s0["mass"], *tail)
+        return np.asarray(sums, dtype=np.float64).reshape(n_groups, width)
+
+    first = rows = observe()
     while True:
-        if (rows[:, 3 * num_pes] if mean_field else rows[:, :num_pes]).sum() == 0:
+        if m.running(rows, num_pes).sum() == 0:
             stop = f"NO TRAJECTORY IS RUNNING, STOP EVOLVING AT STEP {step}"
             break
         if step >= max_steps:
             break
         n_steps = min(chunk_steps, max_steps - step)
-        if mean_field:
-            state = api.hop_evolve_groups_mf(num_pes, model, state, n_per_group, s0["mass"], dts, n_steps, s0["xmin"], s0["xmax"])
-        elif mash:
-            state, counts = api.hop_evolve_groups_mash(num_pes, model, state, n_per_group, s0["mass"], dts, n_steps, s0["xmin"], s0["xmax"], hops=counts)
+        args, keywords = m.step_args(seed, reverse_frustrated, correction, tail, s0["mass"], dts, step, n_steps, s0["xmin"], s0["xmax"])
+        if m.counters:
+            state, counts = _call(api, "evolve", m.evolve, True)(num_pes, model, state, n_per_group, *args, hops=counts, **keywords)
         else:
-            state, counts = api.hop_evolve_groups(num_pes, model, state, n_per_group, seed, s0["mass"], dts, step, n_steps, s0["xmin"], s0["xmax"],
-                                                  reverse=reverse_frustrated, hops=counts, **correction)
+            state = _call(api, "evolve", m.evolve, True)(num_pes, model, state, n_per_group, *args, **keywords)
         step += n_steps
-        rows = np.asarray(observe(num_pes, model, state, n_per_group, s0["mass"]), dtype=np.float64).reshape(n_groups, width)
-    if mean_field:
+        rows = observe()
+    if not m.counters:
         per_group = np.zeros((n_groups, 2), dtype=np.int64)
     elif on_device:
         api.synchronize()  # the context's stream has written the counters: now the framework's may read them
@@ -401,114 +464,21 @@ def scan(api, model=DAC, num_pes=2, ln_energies=None, momenta=None, n_per_group=
         per_group = counts.reshape(n_groups, n_per_group, 2).sum(axis=1, dtype=np.int64)
     t_end = time.perf_counter()
     say(stop or f"STOPPED AT {max_steps} STEPS")
-    counts_by = rows[:, :3 * num_pes].reshape(n_groups, 3, num_pes)
-    scattered = counts_by[:, 1:, :] / n_per_group
-    running = (rows[:, 3 * num_pes] if mean_field else counts_by[:, RUNNING, :].sum(axis=1)) / n_per_group
-    fractions = np.concatenate([scattered.reshape(n_groups, 2 * num_pes), running[:, None]], axis=1)
-    stderr = np.sqrt(fractions * (1.0 - fractions) / n_per_group)
-    head = np.array([np.log(s["p0"] ** 2 / 2.0 / s["mass"]) if model == DAC else s["p0"] for s in setups])
-    hops, frustrated = per_group[:, 0] / n_per_group, per_group[:, 1] / n_per_group
-    drift = (rows[:, width - 1] - first[:, width - 1]) / n_per_group
-    lines = [scan_line([head[g], *fractions[g], *stderr[g], hops[g], frustrated[g], drift[g]]) for g in range(n_groups)]
-    if out_dir is not None:
-        os.makedirs(out_dir, exist_ok=True)
-        with open(os.path.join(out_dir, "scan.txt"), "w") as f:
-            f.write("".join(lines))
-    return dict(setups=setups, dt=dts, n_per_group=n_per_group, total_step=total_step, max_steps=max_steps, steps=step, stop=stop, state=state,
-                hop_counts=counts, rows=rows, head=head, scattered=scattered, running=running, stderr=stderr, hops=hops, frustrated=frustrated,
-                energy_drift=drift, lines=lines, total_seconds=t_end - t0, decoherence=decoherence, edc_c=edc_c, method=method)
-
-
-# ---- method="sqc": symmetrical quasi-classical trajectories ("Symmetrical quasi-classical trajectories") ----------------------------
-def _run_sqc(api, model, num_pes, ln_energy, n_traj, seed, out_dir, dt, surface0, max_outputs, log, window, gamma, setup_kw):
-    """run(method="sqc"): the loop of run() on hop_sample_sqc, hop_evolve_sqc and hop_observe_sqc.  One sample; per output time one evolve and
-    one observe, whose record is unpack_sqc()'s; the run stops when n_status[0] == 0.  averages.txt holds averages_line_sqc.  The scattering
-    line keeps run()'s columns with channel (side, k) = counts[side][k] / N_f, N_f the finished and windowed trajectories (all 0 where
-    N_f = 0), then n_status[0] / n, and as a new last column the unassigned fraction of the finished trajectories"""
-    window, gamma = sqc_window(window, gamma)
-    setup_kw["boundary"] = exact.ABSORBING
-    s = exact.setup(ln_energy, **setup_kw)
-    num_pes, n_traj = int(num_pes), int(n_traj)
-    dt = float(s["dt_rule"] if dt is None else dt)
-    output_step, total_step = int(s["output_time"] / dt), int(s["total_time"] / dt)
-    if output_step < 1:
-        raise ValueError("the output time is shorter than one time step")
-    say = log or (lambda *_: None)
-    t0 = time.perf_counter()
-    state = api.hop_sample_sqc(num_pes, model, n_traj, seed, s["x0"], s["p0"], s["sigma_x"], s["sigma_p"], surface0, window, gamma, device_out=True)
-    files = {}
-    if out_dir is not None:
-        os.makedirs(out_dir, exist_ok=True)
-        files = {name: open(os.path.join(out_dir, name), "w") for name in ("t.txt", "averages.txt")}
-    records, stop, step = [], None, 0
-    try:
-        while True:
-            rec = unpack_sqc(api.hop_observe_sqc(num_pes, model, state, s["mass"], window, gamma), num_pes, n_traj, gamma)
-            rec["t"] = step * dt
-            records.append(rec)
-            if files:
-                files["t.txt"].write(exact.fmt(rec["t"]) + "\n")
-                files["averages.txt"].write(averages_line_sqc(rec["t"], rec))
-            if rec["n_status"][RUNNING] == 0:
-                stop = f"NO TRAJECTORY IS RUNNING, STOP EVOLVING AT {rec['t']:g}"
-                break
-            if step + output_step > total_step or (max_outputs is not None and len(records) >= max_outputs):
-                break
-            state = api.hop_evolve_sqc(num_pes, model, state, s["mass"], dt, output_step, s["xmin"], s["xmax"], gamma)
-            step += output_step
-    finally:
-        for f in files.values():
-            f.close()
-    t_end = time.perf_counter()
-    say(stop or "FINISHED ALL OUTPUT TIMES")
-    last = records[-1]
-    channels, n_f, lost = sqc_channels(last["counts"], last["n_status"], last["none"])
-    head = np.log(s["p0"] ** 2 / 2.0 / s["mass"]) if model == DAC else s["p0"]  # as exact.run (main.cpp:308-321)
-    line = " ".join(exact.fmt(v) for v in [head, *channels.reshape(-1), last["n_status"][RUNNING] / n_traj, lost])
-    return dict(setup=s, dt=dt, output_step=output_step, total_step=total_step, n_traj=n_traj, records=records, stop=stop, state=state,
-                scattered=channels, scattering_line=line, stop_time=last["t"], steps=step, total_seconds=t_end - t0, decoherence=None, edc_c=None,
-                method=SQC, window=window, gamma=gamma, n_finished_windowed=float(n_f), unassigned_finished=float(lost))
-
-
-def _scan_sqc(api, model, num_pes, n_per_group, seed, surface0, chunk_steps, max_steps, out_dir, say, window, gamma, setups, dts, total_step, packets):
-    """scan(method="sqc"): the loop of scan() on hop_sample_groups_sqc, hop_evolve_groups_sqc and hop_observe_groups_sqc.  scan.txt keeps its
-    columns: channel (side, k) = counts[side][k] / N_f per group (0 where N_f = 0) with stderr sqrt(f (1 - f) / N_f), running = n_status[0] /
-    n_per_group with stderr over n_per_group, hops and frustrated 0, energy_drift from H; the unassigned fraction of the group's finished
-    trajectories is appended as a new last column"""
-    N, n_groups, s0 = num_pes, len(setups), setups[0]
-    width, step, stop = 4 * N + 9, 0, None
-    t0 = time.perf_counter()
-    state = api.hop_sample_groups_sqc(N, model, n_per_group, seed, packets, surface0, window, gamma, device_out=True)
-    observe = lambda: np.asarray(api.hop_observe_groups_sqc(N, model, state, n_per_group, s0["mass"], window, gamma), dtype=np.float64).reshape(n_groups, width)
-    first = rows = observe()
-    while True:
-        if rows[:, 3 * N].sum() == 0:
-            stop = f"NO TRAJECTORY IS RUNNING, STOP EVOLVING AT STEP {step}"
-            break
-        if step >= max_steps:
-            break
-        n_steps = min(chunk_steps, max_steps - step)
-        state = api.hop_evolve_groups_sqc(N, model, state, n_per_group, s0["mass"], dts, n_steps, s0["xmin"], s0["xmax"], gamma)
-        step += n_steps
-        rows = observe()
-    t_end = time.perf_counter()
-    say(stop or f"STOPPED AT {max_steps} STEPS")
-    scattered, n_f, lost = sqc_channels(rows[:, :3 * N].reshape(n_groups, 3, N), rows[:, 3 * N:3 * N + 3], rows[:, 3 * N + 3:3 * N + 6])
-    running = rows[:, 3 * N] / n_per_group
-    channels = scattered.reshape(n_groups, 2 * N)
+    scattered, n_f, last = m.channels(rows, num_pes, n_per_group)
+    running = m.running(rows, num_pes) / n_per_group
+    channels = scattered.reshape(n_groups, 2 * num_pes)
     spread = channels * (1.0 - channels)
     stderr = np.concatenate([np.sqrt(np.divide(spread, n_f[:, None], out=np.zeros_like(spread), where=n_f[:, None] > 0)),
                              np.sqrt(running * (1.0 - running) / n_per_group)[:, None]], axis=1)
     fractions = np.concatenate([channels, running[:, None]], axis=1)
-    head = np.array([np.log(s["p0"] ** 2 / 2.0 / s["mass"]) if model == DAC else s["p0"] for s in setups])
-    hops = frustrated = np.zeros(n_groups)
+    head = np.array([_head(model, s) for s in setups])
+    hops, frustrated = per_group[:, 0] / n_per_group, per_group[:, 1] / n_per_group
     drift = (rows[:, width - 1] - first[:, width - 1]) / n_per_group
-    lines = [scan_line([head[g], *fractions[g], *stderr[g], hops[g], frustrated[g], drift[g], lost[g]]) for g in range(n_groups)]
+    lines = [scan_line([head[g], *fractions[g], *stderr[g], hops[g], frustrated[g], drift[g], *(column[g] for column in last)]) for g in range(n_groups)]
     if out_dir is not None:
         os.makedirs(out_dir, exist_ok=True)
         with open(os.path.join(out_dir, "scan.txt"), "w") as f:
             f.write("".join(lines))
-    return dict(setups=setups, dt=dts, n_per_group=n_per_group, total_step=total_step, max_steps=max_steps, steps=step, stop=stop, state=state,
-                hop_counts=None, rows=rows, head=head, scattered=scattered, running=running, stderr=stderr, hops=hops, frustrated=frustrated,
-                energy_drift=drift, lines=lines, total_seconds=t_end - t0, decoherence=None, edc_c=None, method=SQC, window=window, gamma=gamma,
-                n_finished_windowed=n_f, unassigned_finished=lost)
+    return m.result(dict(setups=setups, dt=dts, n_per_group=n_per_group, total_step=total_step, max_steps=max_steps, steps=step, stop=stop, state=state,
+                         hop_counts=counts, rows=rows, head=head, scattered=scattered, running=running, stderr=stderr, hops=hops, frustrated=frustrated,
+                         energy_drift=drift, lines=lines, total_seconds=t_end - t0, decoherence=decoherence, edc_c=edc_c, method=method), tail, n_f, last)
