@@ -27,6 +27,10 @@ TIMER_HOP_MF = 15  # gple_timer: the step kernel of one gple_hop_evolve_mf or gp
 TIMER_HOP_SQC = 16  # gple_timer: the step kernel of one gple_hop_evolve_sqc or gple_hop_evolve_groups_sqc call
 TIMER_HOP_MASH = 17  # gple_timer: the step kernel of one gple_hop_evolve_mash or gple_hop_evolve_groups_mash call
 TIMER_HOP_BIN_MF = 18  # gple_timer: the bin kernel of one gple_hop_bin_mf call
+TIMER_HOP_OUTGOING = 19  # gple_timer: the bin kernel of one gple_hop_outgoing, gple_hop_outgoing_mf or gple_hop_outgoing_sqc call
+# GPLE_HOP_AXIS_*: what gple_hop_outgoing bins by, and the names Api.hop_outgoing takes for them
+HOP_AXIS_MOMENTUM, HOP_AXIS_ENERGY = range(2)
+HOP_AXIS_NAMES = {"momentum": HOP_AXIS_MOMENTUM, "energy": HOP_AXIS_ENERGY}
 HOP_MAX_GROUPS = 65536  # GPLE_HOP_MAX_GROUPS
 # GPLE_HOP_WINDOW_*: the windows of the symmetrical quasi-classical trajectories, the names Api.hop_sample_sqc / hop_observe_sqc take for them, and
 # the customary zero-point parameter gamma of each
@@ -403,6 +407,10 @@ def _signatures():
         "hop_sample_groups_mash": (st, [CTX, i, i, sz, sz, sz, ull, _dp, i, u, _dp, _dp, _dp, ip, ip]),
         "hop_evolve_mash": (st, [CTX, i, i, sz, d, d, sz, d, d, u, _dp, _dp, _dp, ip, ip]),
         "hop_evolve_groups_mash": (st, [CTX, i, i, sz, sz, d, _dp, sz, d, d, u, _dp, _dp, _dp, ip, ip, ip]),
+        # what left the box, per channel
+        "hop_outgoing": (st, [CTX, i, i, sz, d, i, d, d, sz, u, _dp, _dp, _dp, ip, ip, llp]),
+        "hop_outgoing_mf": (st, [CTX, i, i, sz, d, i, d, d, sz, u, _dp, _dp, _dp, ip, llp]),
+        "hop_outgoing_sqc": (st, [CTX, i, i, sz, d, i, d, i, d, d, sz, u, _dp, _dp, _dp, ip, llp]),
         # many NLML problems in one launch; the search of several planes in lock-step on it
         "nlml_batch": (st, [CTX, C.POINTER(NlmlProblem), sz, i, u, _dp, _dp, C.POINTER(_dp), ip]),
         "nlml_fit_planes": (st, [CTX, C.POINTER(NlmlFitPlane), sz, i, opt, _dp, _dp, ip, C.POINTER(_dp)]),
@@ -585,7 +593,7 @@ class Api:
         11 = the device work of dvr_spectrum, 12 = the step kernel of hop_evolve, 13 = the bin kernel of hop_bin,
         14 = the step kernel of hop_evolve_groups (12 and 14 also with a decoherence correction), 15 = the step kernel of hop_evolve_mf and
         hop_evolve_groups_mf, 16 = the step kernel of hop_evolve_sqc and hop_evolve_groups_sqc, 17 = the step kernel of hop_evolve_mash and
-        hop_evolve_groups_mash, 18 = the bin kernel of hop_bin_mf."""
+        hop_evolve_groups_mash, 18 = the bin kernel of hop_bin_mf, 19 = the bin kernel of hop_outgoing, hop_outgoing_mf and hop_outgoing_sqc."""
         last, total, count = C.c_double(), C.c_double(), C.c_long()
         self._check(self.lib.gple_ctx_get_timing(self.ctx, which, C.byref(last), C.byref(total), C.byref(count)))
         return last.value, total.value, count.value
@@ -1425,6 +1433,51 @@ class Api:
         n_groups, n_per_group = self._hop_groups(n, n_per_group)
         return self._hop_sums_groups("hop_observe_groups_sqc", num_pes, (int(model), n_groups, n_per_group, float(mass), *window), state, self._hop_mf_pointers,
                                      n_groups, 4 * int(num_pes) + 9)
+
+    # ---- what left the box (gple_hop_outgoing*; DESIGN.md §17, "What left the box") ------------------------------------------------------------------
+    # grid is (first, step, n_bins) of the momentum or the energy; acc is int64 of 2 num_pes n_bins + 4 entries: the planes [side][level][bin]
+    # of weights times 2^32, then [binned, outside, running, unassigned] (hopping.outgoing_density reads it)
+    def _hop_outgoing(self, name, num_pes, model, state, n, pointers_of, mass, grid, axis, acc, extra=()):
+        first, step, n_bins = grid
+        first, step, n_bins = float(first), float(step), int(n_bins)
+        if n_bins < 1:
+            raise ValueError("a grid has at least one point")
+        if isinstance(axis, str):
+            if axis not in HOP_AXIS_NAMES:
+                raise ValueError(f"axis is an integer or one of {sorted(HOP_AXIS_NAMES)}")
+            axis = HOP_AXIS_NAMES[axis]
+        words, flags = 2 * num_pes * n_bins + 4, 0
+        if acc is None:
+            acc = _like(state[0], words, np.int64)
+        else:
+            flags = HOP_ACCUMULATE
+            if _on_device(acc) != _on_device(state[0]):
+                raise ValueError("the accumulator lives on the side the ensemble is on")
+            if not _on_device(acc):
+                acc = np.array(acc, dtype=np.int64)
+        acc, pa, _ = self._hop_acc(acc, words)
+        self._hop_call(name, num_pes, (int(model), n, float(mass), *extra, int(axis), first, step, n_bins), state, pointers_of, flags, (pa,))
+        return acc
+
+    def hop_outgoing(self, num_pes, model, state, mass, grid, axis="momentum", acc=None):
+        """gple_hop_outgoing: the finished trajectories added to the plane of their channel (side, active surface) at the bin of their momentum
+        (axis "momentum") or of p^2 / 2 mass + E_surface ("energy") on grid = (first, step, n_bins) -> acc.  numpy for a numpy ensemble, a
+        tensor on the GPU for a device one; acc=None starts from zero, a given acc is added to (GPLE_HOP_ACCUMULATE): numpy returns the sum as a
+        copy, a tensor is added to in place (asynchronously on the context's stream) and returned"""
+        state, n = self._hop_state(int(num_pes), state)
+        return self._hop_outgoing("hop_outgoing", int(num_pes), model, state, n, self._hop_pointers, mass, grid, axis, acc)
+
+    def hop_outgoing_mf(self, num_pes, model, state, mass, grid, axis="momentum", acc=None):
+        """gple_hop_outgoing_mf: hop_outgoing from the amplitudes alone: a finished trajectory adds rint(2^32 |c_k|^2) to every level k of its
+        side, and its energy is p^2 / 2 mass + sum_k |c_k|^2 E_k.  The state's surface is never passed down.  At most 2^31 trajectories"""
+        state, n = self._hop_mf_state(num_pes, state, False)
+        return self._hop_outgoing("hop_outgoing_mf", int(num_pes), model, state, n, self._hop_mf_pointers, mass, grid, axis, acc)
+
+    def hop_outgoing_sqc(self, num_pes, model, state, mass, grid, axis="momentum", window="triangle", gamma=None, acc=None):
+        """gple_hop_outgoing_sqc: hop_outgoing with the level the window hop_observe_sqc finds for (window, gamma); a finished trajectory that
+        no window holds is counted in `unassigned`.  The energy is H = p^2 / 2 mass + sum_k (e_k - gamma) E_k"""
+        state, n = self._hop_mf_state(num_pes, state, False)
+        return self._hop_outgoing("hop_outgoing_sqc", int(num_pes), model, state, n, self._hop_mf_pointers, mass, grid, axis, acc, self._hop_window(window, gamma))
 
     # ---- MASH trajectories (gple_hop_*_mash; DESIGN.md §17, "MASH trajectories") -------------------------------------------------------------------
     # The ensemble is the same 5-tuple, two levels only.  The samples draw amplitudes of their own; the step needs no seed, step counter or

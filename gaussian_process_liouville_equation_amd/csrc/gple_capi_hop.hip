@@ -216,6 +216,39 @@ namespace
 		if (!dev) GPLE_HIP(ctx, hipMemcpyAsync(acc, a, words * sizeof(long long), hipMemcpyDeviceToHost, stream));
 		return st.finish();
 	}
+	// gple_hop_outgoing, _mf and _sqc around their launch, as hop_bin_call (surface: null for the two forms without one; ok: what the form's
+	// observe call checks beyond the shared checks: its n_max, window and gamma, the flags it refuses)
+	template <typename Launch>
+	int hop_outgoing_call(gple_ctx* ctx, int num_pes, int model, size_t n, bool ok, double mass, int axis, double first, double step, size_t n_bins, unsigned flags,
+		const double* x, const double* p, const double* b, const int* surface, const int* status, long long* acc, Launch&& launch)
+	{
+		PesModel pes;
+		if (!ctx || !ok || !hop_size_ok(ctx, num_pes, model, n, 0, &pes) || n > (size_t(1) << 31) || !hop_positive(mass) ||
+			(axis != GPLE_HOP_AXIS_MOMENTUM && axis != GPLE_HOP_AXIS_ENERGY) || n_bins == 0 || n_bins > GPLE_HOP_MAX_CELLS / 6 || !hop_positive(step) ||
+			!std::isfinite(first) || !x || !p || !b || !status || !acc)
+			return GPLE_ERR_BAD_ARG;
+		GPLE_OPEN(ctx);
+		const bool dev = flags & GPLE_IO_DEVICE, keep = flags & GPLE_HOP_ACCUMULATE;
+		const size_t words = hop_outgoing_words(num_pes, n_bins);
+		GPLE_CALL(ctx);
+		hipStream_t stream = ctx->stream;
+		HopStaged st(ctx, flags);
+		GPLE_TRY(st.begin(num_pes, model));
+		Scratch sums(ctx);
+		long long* a = acc;
+		if (!dev)
+		{
+			GPLE_HIP(ctx, sums.get(words));
+			a = reinterpret_cast<long long*>(sums.p);
+		}
+		GPLE_TRY(st.arrays(HopStaged::READ, num_pes, n, 0, 0, x, p, b, surface, status));
+		if (!keep) GPLE_HIP(ctx, hipMemsetAsync(a, 0, words * sizeof(long long), stream));
+		else if (!dev) GPLE_HIP(ctx, hipMemcpyAsync(a, acc, words * sizeof(long long), hipMemcpyHostToDevice, stream));
+		const HopAxis g{first, step, static_cast<long>(n_bins), axis == GPLE_HOP_AXIS_ENERGY ? 1 : 0};
+		GPLE_TRY(hop_timed(ctx, GPLE_TIMER_HOP_OUTGOING, [&] { return launch(stream, st.e, st.pes, g, a); }));
+		if (!dev) GPLE_HIP(ctx, hipMemcpyAsync(acc, a, words * sizeof(long long), hipMemcpyDeviceToHost, stream));
+		return st.finish();
+	}
 	// gple_hop_density and gple_hop_density_mf around their launch
 	using HopDensityLaunch = hipError_t (*)(hipStream_t, int, long, double, const long long*, double*);
 	int hop_density_call(gple_ctx* ctx, int num_pes, size_t n_x, size_t n_p, double dx, double dp, size_t n_norm, unsigned flags, const long long* acc, double* rho,
@@ -331,6 +364,30 @@ extern "C"
 		double* rho)
 	{
 		return hop_density_call(ctx, num_pes, n_x, n_p, dx, dp, n_norm, flags, acc, rho, launch_hop_density_mf);
+	}
+
+	/* ---- what left the box, per channel ("What left the box") ----------------------------------------------------------------- */
+	int gple_hop_outgoing(gple_ctx* ctx, int num_pes, int model, size_t n, double mass, int axis, double first, double step, size_t n_bins, unsigned flags,
+		const double* x, const double* p, const double* b, const int* surface, const int* status, long long* acc)
+	{
+		return hop_outgoing_call(ctx, num_pes, model, n, surface != nullptr, mass, axis, first, step, n_bins, flags, x, p, b, surface, status, acc,
+			[&](hipStream_t s, const HopEnsemble& e, const PesModel& pes, const HopAxis& g, long long* a) { return launch_hop_outgoing(s, e, pes, mass, g, a); });
+	}
+
+	int gple_hop_outgoing_mf(gple_ctx* ctx, int num_pes, int model, size_t n, double mass, int axis, double first, double step, size_t n_bins, unsigned flags,
+		const double* x, const double* p, const double* b, const int* status, long long* acc)
+	{
+		return hop_outgoing_call(ctx, num_pes, model, n, true, mass, axis, first, step, n_bins, flags, x, p, b, nullptr, status, acc,
+			[&](hipStream_t s, const HopEnsemble& e, const PesModel& pes, const HopAxis& g, long long* a) { return launch_hop_outgoing_mf(s, e, pes, mass, g, a); });
+	}
+
+	int gple_hop_outgoing_sqc(gple_ctx* ctx, int num_pes, int model, size_t n, double mass, int window, double gamma, int axis, double first, double step,
+		size_t n_bins, unsigned flags, const double* x, const double* p, const double* b, const int* status, long long* acc)
+	{
+		return hop_outgoing_call(ctx, num_pes, model, n, hop_sqc_window_ok(window, gamma) && !(flags & GPLE_HOP_REVERSE), mass, axis, first, step, n_bins, flags, x,
+			p, b, nullptr, status, acc, [&](hipStream_t s, const HopEnsemble& e, const PesModel& pes, const HopAxis& g, long long* a) {
+				return launch_hop_outgoing_sqc(s, e, pes, mass, window, gamma, g, a);
+			});
 	}
 
 	/* ---- grouped ensembles ("A curve in one launch") ------------------------------------------------------------------------ */

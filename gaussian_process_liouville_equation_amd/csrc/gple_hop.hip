@@ -3,7 +3,7 @@
 // (SQC) and MASH trajectories.  The reference has no trajectory code: these are the methods its three models were made to test.
 //
 // One thread per trajectory; x, p, the diabatic amplitudes b, the active surface a and everything derived from them stay in registers for all
-// the steps of a launch.  No LDS, no device globals, and no atomics but the integer ones of hop_bin_kernel and hop_bin_mf_kernel below.  Every piece that more than
+// the steps of a launch.  No LDS, no device globals, and no atomics but the integer ones of hop_bin_kernel, hop_bin_mf_kernel and hop_outgoing_kernel below.  Every piece that more than
 // one method uses is one device function, stated once here; a method is a sampler, a force and a crossing rule on top of them.
 //
 // The shared pieces (V, Fd = -V', E, C: the diabatic matrix and force, the adiabatic energies and states; F = C^T Fd C, symmetrised as in
@@ -929,6 +929,109 @@ namespace gple
 				}
 		}
 
+		// ---- what left the box ------------------------------------------------------------------------------------------------------------------------
+		// The outgoing momentum or energy per channel (side, adiabatic level) of the finished trajectories ("What left the box";
+		// include/gple.h, gple_hop_outgoing).  A form is the Terms policy of a method's sums and what a finished trajectory's terms say of its
+		// channel: channel() returns the level k of a trajectory that sits in one plane (-1: in none) and fills w where WEIGHTED spreads it over
+		// every level.  The terms are fill()'s own, so the weights and the energy are the expressions the sums add.  Every index into t is a
+		// constant after unrolling: nothing goes to scratch
+		// the level k whose count term [status][k], one of the first 3 NP terms of the surface and the window sums, is set; -1: none is
+		template <int NP, int WIDTH>
+		__device__ __forceinline__ int hop_counted_level(const double (&t)[WIDTH], int status)
+		{
+			int found = -1;
+#pragma unroll
+			for (int s = 1; s <= 2; ++s)
+#pragma unroll
+				for (int k = 0; k < NP; ++k) found = s == status && t[s * NP + k] != 0.0 ? k : found;
+			return found;
+		}
+		struct HopOutSurface
+		{
+			using Terms = HopSurfaceTerms;
+			static constexpr bool WEIGHTED = false, TALLY_NONE = false; // a surface out of range is skipped, as the sums skip it
+			Terms terms;
+			template <int NP>
+			__device__ __forceinline__ static int channel(const double (&t)[Terms::width(NP)], int status, double (&)[NP])
+			{
+				return hop_counted_level<NP>(t, status);
+			}
+		};
+		struct HopOutMeanField
+		{
+			using Terms = HopMeanFieldTerms;
+			static constexpr bool WEIGHTED = true, TALLY_NONE = false;
+			Terms terms;
+			template <int NP>
+			__device__ __forceinline__ static int channel(const double (&t)[Terms::width(NP)], int status, double (&w)[NP])
+			{
+#pragma unroll
+				for (int k = 0; k < NP; ++k) w[k] = status == 1 ? t[NP + k] : t[2 * NP + k];
+				return 0;
+			}
+		};
+		struct HopOutSqc
+		{
+			using Terms = HopSqcTerms;
+			static constexpr bool WEIGHTED = false, TALLY_NONE = true; // no window: the tally `unassigned`
+			Terms terms;
+			template <int NP>
+			__device__ __forceinline__ static int channel(const double (&t)[Terms::width(NP)], int status, double (&)[NP])
+			{
+				return hop_counted_level<NP>(t, status);
+			}
+		};
+		// One thread per trajectory.  A finished one (status 1: side 0, status 2: side 1) on the grid adds 2^32 to the plane of its channel, or
+		// rint(2^32 w_k) to every plane of its side, at the bin of its nearest grid point, by the no-return 64-bit integer atomics at agent scope
+		// of hop_bin_kernel: any order, the same bits.  The four tallies are counted over the wave by a ballot first, one atomic per wave and tally
+		template <int NP, typename M, typename Form>
+		__global__ void __launch_bounds__(HOP_BLOCK) hop_outgoing_kernel(HopEnsemble e, M model, Form form, HopAxis g, unsigned long long* __restrict__ acc)
+		{
+			const long i = static_cast<long>(blockIdx.x) * HOP_BLOCK + threadIdx.x;
+			bool binned = false, outside = false, running = false, unassigned = false;
+			if (i < e.n)
+			{
+				const int status = e.status[i];
+				running = status == 0;
+				if (status == 1 || status == 2)
+				{
+					constexpr int WIDTH = Form::Terms::width(NP);
+					double t[WIDTH], w[NP];
+					form.terms.template fill<NP>(e, model, i, t);
+					const int k = Form::template channel<NP>(t, status, w);
+					unassigned = Form::TALLY_NONE && k < 0;
+					if (k >= 0)
+					{
+						const double q = g.energy ? t[WIDTH - 1] : e.p[i];
+						// in double before the conversion, and written so that a NaN or a huge value is outside
+						const double f = floor((q - g.first) / g.step + 0.5);
+						binned = f >= 0.0 && f < static_cast<double>(g.n_bins);
+						outside = !binned;
+						if (binned)
+						{
+							unsigned long long* const side = acc + (status - 1) * NP * g.n_bins + static_cast<long>(f);
+							if constexpr (Form::WEIGHTED)
+							{
+#pragma unroll
+								for (int l = 0; l < NP; ++l)
+									atomicAdd(side + l * g.n_bins, static_cast<unsigned long long>(static_cast<long long>(rint(4294967296.0 * w[l]))));
+							}
+							else atomicAdd(side + k * g.n_bins, 4294967296ull);
+						}
+					}
+				}
+			}
+			const unsigned long long in = __ballot(binned), out = __ballot(outside), on = __ballot(running), none = __ballot(unassigned);
+			if (threadIdx.x % HOP_WAVE == 0)
+			{
+				unsigned long long* tally = acc + 2 * NP * g.n_bins;
+				if (in) atomicAdd(tally, static_cast<unsigned long long>(__popcll(in)));
+				if (out) atomicAdd(tally + 1, static_cast<unsigned long long>(__popcll(out)));
+				if (on) atomicAdd(tally + 2, static_cast<unsigned long long>(__popcll(on)));
+				if (none) atomicAdd(tally + 3, static_cast<unsigned long long>(__popcll(none)));
+			}
+		}
+
 		// ---- MASH ------------------------------------------------------------------------------------------------------------------------------------
 		// side(c): the adiabatic state with the larger population, 1 if |c_1|^2 > |c_0|^2 else 0 (the sign of the mapping spin's S_z)
 		__device__ __forceinline__ int mash_side(const double (&cre)[2], const double (&cim)[2])
@@ -1263,5 +1366,28 @@ namespace gple
 		else if (num_pes == 3) hop_launch(s, cells, hop_density_kernel<3, true>, cells, w, acc, rho);
 		else return hipErrorInvalidValue;
 		return hipGetLastError();
+	}
+
+	namespace
+	{
+		template <typename Form>
+		hipError_t hop_outgoing(hipStream_t s, const HopEnsemble& e, const PesModel& model, const Form& form, const HopAxis& g, long long* acc)
+		{
+			if (e.n <= 0 || g.n_bins <= 0) return hipErrorInvalidValue;
+			unsigned long long* const words = reinterpret_cast<unsigned long long*>(acc);
+			return hop_dispatch(e, model, [&](auto np, auto m) { hop_launch(s, e.n, hop_outgoing_kernel<np(), decltype(m), Form>, e, m, form, g, words); });
+		}
+	} // namespace
+	hipError_t launch_hop_outgoing(hipStream_t s, const HopEnsemble& e, PesModel model, double mass, const HopAxis& g, long long* acc)
+	{
+		return hop_outgoing(s, e, model, HopOutSurface{{mass}}, g, acc);
+	}
+	hipError_t launch_hop_outgoing_mf(hipStream_t s, const HopEnsemble& e, PesModel model, double mass, const HopAxis& g, long long* acc)
+	{
+		return hop_outgoing(s, e, model, HopOutMeanField{{mass}}, g, acc);
+	}
+	hipError_t launch_hop_outgoing_sqc(hipStream_t s, const HopEnsemble& e, PesModel model, double mass, int window, double gamma, const HopAxis& g, long long* acc)
+	{
+		return hop_outgoing(s, e, model, HopOutSqc{{mass, window, gamma}}, g, acc);
 	}
 } // namespace gple

@@ -506,6 +506,21 @@ namespace gple
 	// density scales by 2^-32 / w as it scales the coherence sums.  A weight is at most 2^32 to rounding: the caller keeps e.n <= 2^31
 	hipError_t launch_hop_bin_mf(hipStream_t s, const HopEnsemble& e, PesModel model, const HopGrid& g, bool bin_all, long long* acc);
 	hipError_t launch_hop_density_mf(hipStream_t s, int num_pes, long cells, double w, const long long* acc, double* rho);
+	// the axis of gple_hop_outgoing: q_j = first + step j, j < n_bins, of the momentum or (energy != 0) of the energy term of the method's sums;
+	// a value belongs to its nearest grid point, floor((q - first) / step + 0.5)
+	struct HopAxis
+	{
+		double first, step;
+		long n_bins;
+		int energy;
+	};
+	// integers of acc: 2 num_pes planes [side][level] of n_bins, then the tallies [binned, outside, running, unassigned]
+	constexpr size_t hop_outgoing_words(int num_pes, size_t n_bins) { return 2 * static_cast<size_t>(num_pes) * n_bins + 4; }
+	// adds the finished trajectories to acc by 64-bit integer atomics, in the three forms of the sums (include/gple.h): by the active surface
+	// (e.surface is read), by the amplitudes' weights (e.n <= 2^31 is the caller's to keep), by the window that holds them
+	hipError_t launch_hop_outgoing(hipStream_t s, const HopEnsemble& e, PesModel model, double mass, const HopAxis& g, long long* acc);
+	hipError_t launch_hop_outgoing_mf(hipStream_t s, const HopEnsemble& e, PesModel model, double mass, const HopAxis& g, long long* acc);
+	hipError_t launch_hop_outgoing_sqc(hipStream_t s, const HopEnsemble& e, PesModel model, double mass, int window, double gamma, const HopAxis& g, long long* acc);
 
 	// ---- reconstruction of a gridded density (gple_recon.hip; test/gpr.cpp): num_pes = 2 or 3, rho: num_pes^2 x nx x np (re, im) ----
 	constexpr int RECON_SURVEY_BLOCKS = 64, RECON_SURVEY_VALUES = 7; // row blocks of the survey, values per plane and block

@@ -7,7 +7,9 @@ column for column with exact.run(flux=True)'s.
     phase_grid_of()   the phase-space grid of a run, from its size
     run()             sample, then per output time one hop_evolve of output_step steps and one hop_observe; t.txt and averages.txt.  With a
                       phase_grid also one gple_hop_bin and gple_hop_density: x.txt, p.txt and phase.txt, the adiabatic density of the ensemble
-                      (phase_density="amplitude": gple_hop_bin_mf and gple_hop_density_mf, which "ehrenfest" runs have too)
+                      (phase_density="amplitude": gple_hop_bin_mf and gple_hop_density_mf, which "ehrenfest" runs have too).  With outgoing
+                      also one gple_hop_outgoing (_mf, _sqc) per axis on the final state: outgoing_p.txt and outgoing_e.txt, what left the
+                      box per side and level by momentum and by energy (outgoing_density(), outgoing_grids(), write_outgoing())
     scan()            the branching probabilities at many momenta from one grouped ensemble (gple_hop_sample_groups / _evolve_groups /
                       _observe_groups): a group per momentum with its own packet and time step; scan.txt
 run() and scan() take decoherence = None (Tully's algorithm as it stands), "edc", "collapse_hop" or "collapse_attempt" and edc_c: the decoherence
@@ -254,8 +256,78 @@ def phase_grid_of(api, num_pes, model, s, phase_grid):
     return (x_first, dx, n_x, p_first, dp, n_p)
 
 
+OUTGOING_AXES = ("momentum", "energy")  # run(outgoing=...): the keys, in the order of their calls
+
+
+def outgoing_density(acc, num_pes, n_bins, n_norm, step):
+    """The accumulator of hop_outgoing (numpy, or a tensor on the GPU, of which only its numbers cross) -> the density (2, num_pes, n_bins)
+    float64 [side][level][bin] = (double)sum 2^-32 / (n_norm step), left to right, per unit of the axis and normalised to the n_norm trajectories
+    behind the method's scattering line, and the four tallies [binned, outside, running, unassigned] as Python integers"""
+    acc = np.asarray(acc.cpu().numpy() if hasattr(acc, "is_cuda") else acc, dtype=np.int64)
+    num_pes, n_bins = int(num_pes), int(n_bins)
+    if acc.shape != (2 * num_pes * n_bins + 4,):
+        raise ValueError("hop_outgoing returns 2 num_pes n_bins + 4 integers")
+    w = np.float64(n_norm) * np.float64(step)
+    if not w > 0.0:
+        raise ValueError("n_norm and step are positive")
+    return acc[:-4].reshape(2, num_pes, n_bins).astype(np.float64) * (1.0 / 4294967296.0) / w, tuple(int(v) for v in acc[-4:])
+
+
+def _outgoing_request(outgoing):
+    """run(outgoing=...) checked before any api call -> {axis: a number of bins >= 2, or the triple (first, step, n_bins)} in OUTGOING_AXES' order"""
+    if outgoing is None:
+        return {}
+    if not isinstance(outgoing, dict) or not outgoing or set(outgoing) - set(OUTGOING_AXES):
+        raise ValueError(f"outgoing is a dict with any of the keys {OUTGOING_AXES}")
+    request = {}
+    for axis in OUTGOING_AXES:
+        if axis not in outgoing:
+            continue
+        given = outgoing[axis]
+        if isinstance(given, (tuple, list)) and len(given) == 3:
+            first, step, n_bins = float(given[0]), float(given[1]), given[2]
+            if n_bins != int(n_bins) or int(n_bins) < 1 or not np.isfinite(first) or not np.isfinite(step) or step <= 0.0:
+                raise ValueError("an outgoing grid is (first, step, n_bins): first finite, step finite and positive, n_bins >= 1")
+            request[axis] = (first, step, int(n_bins))
+        elif isinstance(given, (int, np.integer)) and not isinstance(given, bool) and given >= 2:
+            request[axis] = int(given)
+        else:
+            raise ValueError("an outgoing axis is a number of bins (at least 2) or the triple (first, step, n_bins)")
+    return request
+
+
+def outgoing_grids(api, num_pes, model, s, surface0, request):
+    """The grids (first, step, n_bins) of run(outgoing=...) for the setup s; a triple is taken as it is.  A number of bins: for the momentum the
+    p axis of phase_grid_of(api, num_pes, model, s, (257, n_bins)), which bounds every outgoing momentum; for the energy n_bins points from
+    (p0 - 3 sigma_p)^2 / 2m + E0 to (p0 + 3 sigma_p)^2 / 2m + E0, E0 the adiabatic energy of surface0 at x0 (the lower momentum taken as 0
+    where it would be negative): a trajectory keeps the energy it was drawn with"""
+    grids = {}
+    for axis, given in request.items():
+        if isinstance(given, tuple):
+            grids[axis] = given
+        elif axis == OUTGOING_AXES[0]:
+            grids[axis] = phase_grid_of(api, num_pes, model, s, (257, given))[3:]
+        else:
+            E0 = float(np.asarray(api.pes_adiabatic_n(num_pes, model, np.array([s["x0"]]))[0], dtype=np.float64).reshape(-1, num_pes)[0, surface0])
+            low, high = (max(p, 0.0) ** 2 / 2.0 / s["mass"] + E0 for p in (s["p0"] - 3.0 * s["sigma_p"], s["p0"] + 3.0 * s["sigma_p"]))
+            grids[axis] = (low, (high - low) / (given - 1), given)
+    return grids
+
+
+def write_outgoing(out_dir, axis, grid, density):
+    """outgoing_p.txt: a line per (side, level) with the n_bins densities per unit momentum, the layout of exact_mqcl's absorbed_p.txt;
+    outgoing_e.txt: a line per bin with E and the 2 num_pes densities per unit energy, the layout of exact's spectrum.txt"""
+    flat = density.reshape(-1, density.shape[-1])
+    if axis == OUTGOING_AXES[0]:
+        name, rows = "outgoing_p.txt", flat
+    else:
+        name, rows = "outgoing_e.txt", np.column_stack([grid[0] + grid[1] * np.arange(grid[2]), flat.T])
+    with open(os.path.join(out_dir, name), "w") as f:
+        f.write("".join(" ".join(exact.fmt(v) for v in row) + "\n" for row in rows))
+
+
 def run(api, model=DAC, num_pes=2, ln_energy=0.0, n_traj=10000, seed=0, out_dir=None, reverse_frustrated=False, dt=None, surface0=0, max_outputs=None,
-        log=None, phase_grid=None, decoherence=None, edc_c=0.1, method="fssh", window=None, gamma=None, phase_density=None, **setup_kw):
+        log=None, phase_grid=None, decoherence=None, edc_c=0.1, method="fssh", window=None, gamma=None, phase_density=None, outgoing=None, **setup_kw):
     """n_traj trajectories from the packet of exact.setup(ln_energy, boundary=ABSORBING, **setup_kw) (x0, sigma_x, p0, sigma_p, mass) on the adiabatic
     surface surface0, evolved with the time step dt (default: the setup's dt_rule, the reference's own rule) between x_left = xmin and
     x_right = xmax; a trajectory that leaves is finished and counted by side and active surface.  The ensemble stays on the device: every
@@ -284,10 +356,18 @@ def run(api, model=DAC, num_pes=2, ln_energy=0.0, n_traj=10000, seed=0, out_dir=
     method "mash": everything of "fssh" (records, files, the scattering line) with hop_sample_mash for the sample and one hop_evolve_mash per
     output time, which takes no seed and no step number.  decoherence, reverse_frustrated=True, a phase_grid, window, gamma or num_pes != 2 with
     it is a ValueError.
+    outgoing (None: nothing below happens, call for call and key for key): a dict with any of the keys "momentum" and "energy", each a number of
+    bins, at least 2 on either axis since the default grids take their step from their two ends (the grid of outgoing_grids), or a triple
+    (first, step, n_bins), which may have one bin.  After the loop the final state costs one hop_outgoing<suffix> call per
+    axis, the suffix being that of the method's observe call ("What left the box"): what left per side and level, resolved in
+    the outgoing momentum or in the energy the method conserves.  The result gains `outgoing`: per axis grid, density (outgoing_density with
+    n_norm the sample behind the scattering line, so that density step summed over the bins is `scattered` where nothing is outside), acc and
+    tallies; with out_dir also outgoing_p.txt and outgoing_e.txt (write_outgoing).  Anything else in outgoing is a ValueError before any call.
     Returns the setup, the records (t and unpack() per output time), stop, and scattering_line: the head of exact.run's final line, the
     fractions that left [left | right][surface], and the fraction still running."""
     m = _method(method, decoherence, reverse_frustrated, phase_grid, window, gamma, num_pes, phase_density)
     tail = sqc_window(window, gamma) if m.windowed else ()  # what follows surface0 in the sample and mass in the observe
+    request = _outgoing_request(outgoing)
     amplitude = phase_density == "amplitude"
     setup_kw["boundary"] = exact.ABSORBING
     s = exact.setup(ln_energy, **setup_kw)
@@ -345,13 +425,23 @@ def run(api, model=DAC, num_pes=2, ln_energy=0.0, n_traj=10000, seed=0, out_dir=
     finally:
         for f in files.values():
             f.close()
+    scattered, n_f, last = m.channels(sums, num_pes, n_traj)
+    left = {}
+    for axis, grid in outgoing_grids(api, num_pes, model, s, surface0, request).items():
+        acc = _call(api, "outgoing", m.observe)(num_pes, model, state, s["mass"], grid, axis, *tail)
+        if hasattr(acc, "is_cuda"):
+            api.synchronize()  # the context's stream has written acc: now the framework's may read it
+        density, tallies = outgoing_density(acc, num_pes, grid[2], max(float(n_f), 1.0), grid[1])  # an empty sample: every sum is 0
+        left[axis] = dict(grid=grid, density=density, acc=acc, tallies=dict(zip(("binned", "outside", "running", "unassigned"), tallies)))
+        if out_dir is not None:
+            write_outgoing(out_dir, axis, grid, density)
     t_end = time.perf_counter()
     say(stop or "FINISHED ALL OUTPUT TIMES")
-    scattered, n_f, last = m.channels(sums, num_pes, n_traj)
     line = " ".join(exact.fmt(v) for v in [_head(model, s), *scattered.reshape(-1), m.running(sums, num_pes) / n_traj, *last])
-    return m.result(dict(setup=s, dt=dt, output_step=output_step, total_step=total_step, n_traj=n_traj, records=records, stop=stop, state=state,
-                         scattered=scattered, scattering_line=line, stop_time=records[-1]["t"], steps=step, total_seconds=t_end - t0,
-                         decoherence=decoherence, edc_c=edc_c, method=method, phase_density=phase_density), tail, n_f, last)
+    result = m.result(dict(setup=s, dt=dt, output_step=output_step, total_step=total_step, n_traj=n_traj, records=records, stop=stop, state=state,
+                           scattered=scattered, scattering_line=line, stop_time=records[-1]["t"], steps=step, total_seconds=t_end - t0,
+                           decoherence=decoherence, edc_c=edc_c, method=method, phase_density=phase_density), tail, n_f, last)
+    return dict(result, outgoing=left) if request else result
 
 
 def scan_line(values):

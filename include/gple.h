@@ -163,7 +163,8 @@ typedef enum gple_timer {
 	GPLE_TIMER_HOP_MF = 15,        /* the step kernel of one gple_hop_evolve_mf or gple_hop_evolve_groups_mf call (all its steps, no staging); count = calls */
 	GPLE_TIMER_HOP_SQC = 16,       /* the step kernel of one gple_hop_evolve_sqc or gple_hop_evolve_groups_sqc call (all its steps, no staging); count = calls */
 	GPLE_TIMER_HOP_MASH = 17,      /* the step kernel of one gple_hop_evolve_mash or gple_hop_evolve_groups_mash call (all its steps, no staging); count = calls */
-	GPLE_TIMER_HOP_BIN_MF = 18     /* the bin kernel of one gple_hop_bin_mf call (no staging, no clear); count = calls */
+	GPLE_TIMER_HOP_BIN_MF = 18,    /* the bin kernel of one gple_hop_bin_mf call (no staging, no clear); count = calls */
+	GPLE_TIMER_HOP_OUTGOING = 19   /* the bin kernel of one gple_hop_outgoing, _outgoing_mf or _outgoing_sqc call (no staging, no clear); count = calls */
 } gple_timer;
 int gple_ctx_enable_timing(gple_ctx* ctx, int on);
 /* Synchronises the stream, then: last = milliseconds of the most recent interval; total / count = accumulated since
@@ -395,7 +396,7 @@ int gple_pes_adiabatic_n(gple_ctx* ctx, int num_pes, int model, const double* x,
  * V = V_0 + V'_0 (x - x_first), V' = V'_0, and for s > n - 1 the same from the last node.  With nodes taken from a smooth function the error is
  * at most dx^4 / 384 max|V''''| for the value and sqrt(3) / 216 dx^3 max|V''''| for the derivative.
  * A user id is accepted, on the context it was defined on and with the num_pes it was defined with (GPLE_ERR_BAD_ARG otherwise), by
- * gple_pes_adiabatic_n, gple_pes_diabatic_n, gple_evolve_n, gple_dvr_hamiltonian, gple_mqcl_transform / _evolve / _observe, gple_hop_sample / _evolve / _observe / _bin (and the _groups, _dc, _mf, _sqc and _mash forms),
+ * gple_pes_adiabatic_n, gple_pes_diabatic_n, gple_evolve_n, gple_dvr_hamiltonian, gple_mqcl_transform / _evolve / _observe, gple_hop_sample / _evolve / _observe / _bin / _outgoing (and the _groups, _dc, _mf, _sqc and _mash forms),
  * gple_grid_survey and gple_grid_reconstruct / _cross.  The two-level entry points gple_pes_adiabatic and gple_evolve keep refusing it: they use the reference's closed
  * forms and operation order, of which a table has none; gple_evolve_n at num_pes = 2 reproduces gple_evolve to rounding and takes their place.
  * Where two surfaces of a user model touch (E_j = E_k) with F_jk != 0 the non-adiabatic coupling is infinite, as its formula says: not guarded.
@@ -807,6 +808,46 @@ int gple_hop_evolve_mash(gple_ctx* ctx, int num_pes, int model, size_t n, double
 	unsigned flags, double* x, double* p, double* b, int* surface, int* status);
 int gple_hop_evolve_groups_mash(gple_ctx* ctx, int num_pes, int model, size_t n_groups, size_t n_per_group, double mass, const double* dt,
 	size_t n_steps, double x_left, double x_right, unsigned flags, double* x, double* p, double* b, int* surface, int* status, int* hops);
+/* What left the box ("What left the box"): the finished trajectories of an ensemble, binned by their outgoing momentum or by the
+ * energy their method conserves, per channel.  A trajectory with status 1 left on the left and belongs to side 0, one with status 2 left on
+ * the right and belongs to side 1; a channel is (side, adiabatic level k).  A finished trajectory keeps the x, p, b (surface) of its last
+ * step, so the calls read the state as the sums read it.  The three calls follow the three forms of the sums; with c = C^T b at the
+ * trajectory's x and w_k = |c_k|^2, both formed as the form's observe call forms them:
+ *   gple_hop_outgoing      (fewest switches with every decoherence mode, MASH)  weight 1 in channel (side, surface_i);
+ *                          q_E = p p / 2 / mass + E_a, the energy term of gple_hop_observe
+ *   gple_hop_outgoing_mf   (Ehrenfest)  weight w_k in channel (side, k) for every k;
+ *                          q_E = p p / 2 / mass + sum_k w_k E_k, the energy term of gple_hop_observe_mf
+ *   gple_hop_outgoing_sqc  (SQC)  weight 1 in channel (side, k), k the window gple_hop_observe_sqc finds for (window, gamma); none: see below;
+ *                          q_E = p p / 2 / mass + sum_k (w_k - gamma) E_k, the energy term of gple_hop_observe_sqc
+ * each q_E in the expression and the order of that observe call.  axis: GPLE_HOP_AXIS_MOMENTUM, q = p, or GPLE_HOP_AXIS_ENERGY, q = q_E.
+ * The grid is q_j = first + step j, j < n_bins; a value belongs to its nearest grid point, j = floor((q - first) / step + 0.5): one IEEE
+ * subtraction, one division, one addition, one floor, compared with 0 and n_bins in double (a NaN or a huge value is outside), as the cell
+ * of gple_hop_bin.
+ * acc: 2 num_pes planes of n_bins 64-bit integers, [side][k][j], then the tallies [binned, outside, running, unassigned]:
+ * 2 num_pes n_bins + 4 integers.  Per trajectory, the first that applies:
+ *   status 0                                           one to `running`, nothing else
+ *   status not 1 or 2, or (gple_hop_outgoing) a surface outside 0 ... num_pes - 1: skipped, as the sums skip it
+ *   (gple_hop_outgoing_sqc) no window holds it         one to `unassigned`, nothing else
+ *   j outside 0 ... n_bins - 1                         one to `outside`, nothing else
+ *   otherwise                                          (long long)rint(2^32 weight) to [side][k][j] of each of its channels, which is exactly
+ *                                                      2^32 in one plane for the surface and window forms and a term for every k for the
+ *                                                      amplitude form; then one to `binned`
+ * The sums are integers for the reason gple_hop_bin's are: the same bits in every call whatever order the atomic adds arrive in, and a
+ * slice added to its complement with GPLE_HOP_ACCUMULATE gives the bits of the whole.  The call clears acc first, or adds to what is there
+ * with GPLE_HOP_ACCUMULATE.  n <= 2^31 (a weight is at most 2^32 to rounding: one call cannot overflow a signed sum; across accumulating
+ * calls the bound is the caller's to keep) and n_bins <= GPLE_HOP_MAX_CELLS / 6.  Flags: GPLE_IO_DEVICE (acc too), GPLE_HOP_ACCUMULATE.
+ * Timer of all three: GPLE_TIMER_HOP_OUTGOING.
+ * GPLE_ERR_BAD_ARG, with nothing written: whatever the form's observe call refuses (num_pes, the model, n == 0, mass not finite and
+ * positive, a null array, for _sqc the window, gamma and the flag GPLE_HOP_REVERSE); n > 2^31; an axis other than the two; n_bins == 0 or
+ * above its bound; step not finite and positive; first not finite. */
+#define GPLE_HOP_AXIS_MOMENTUM 0
+#define GPLE_HOP_AXIS_ENERGY 1
+int gple_hop_outgoing(gple_ctx* ctx, int num_pes, int model, size_t n, double mass, int axis, double first, double step, size_t n_bins, unsigned flags,
+	const double* x, const double* p, const double* b, const int* surface, const int* status, long long* acc);
+int gple_hop_outgoing_mf(gple_ctx* ctx, int num_pes, int model, size_t n, double mass, int axis, double first, double step, size_t n_bins,
+	unsigned flags, const double* x, const double* p, const double* b, const int* status, long long* acc);
+int gple_hop_outgoing_sqc(gple_ctx* ctx, int num_pes, int model, size_t n, double mass, int window, double gamma, int axis, double first, double step,
+	size_t n_bins, unsigned flags, const double* x, const double* p, const double* b, const int* status, long long* acc);
 
 /* generate_markov_chain (mc.cpp:118-165) for n walkers at once on the fitted distribution |cut-off prediction| of `element`:
  * num_steps Metropolis steps with uniform displacements in [-max_displacement, max_displacement) per dimension; r (2n) holds
