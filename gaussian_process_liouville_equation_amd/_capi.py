@@ -28,6 +28,7 @@ TIMER_HOP_SQC = 16  # gple_timer: the step kernel of one gple_hop_evolve_sqc or 
 TIMER_HOP_MASH = 17  # gple_timer: the step kernel of one gple_hop_evolve_mash or gple_hop_evolve_groups_mash call
 TIMER_HOP_BIN_MF = 18  # gple_timer: the bin kernel of one gple_hop_bin_mf call
 TIMER_HOP_OUTGOING = 19  # gple_timer: the bin kernel of one gple_hop_outgoing, gple_hop_outgoing_mf or gple_hop_outgoing_sqc call
+TIMER_HOP_SMOOTH = 20  # gple_timer: the three kernels of one gple_hop_smooth or gple_hop_smooth_mf call
 # GPLE_HOP_AXIS_*: what gple_hop_outgoing bins by, and the names Api.hop_outgoing takes for them
 HOP_AXIS_MOMENTUM, HOP_AXIS_ENERGY = range(2)
 HOP_AXIS_NAMES = {"momentum": HOP_AXIS_MOMENTUM, "energy": HOP_AXIS_ENERGY}
@@ -411,6 +412,9 @@ def _signatures():
         "hop_outgoing": (st, [CTX, i, i, sz, d, i, d, d, sz, u, _dp, _dp, _dp, ip, ip, llp]),
         "hop_outgoing_mf": (st, [CTX, i, i, sz, d, i, d, d, sz, u, _dp, _dp, _dp, ip, llp]),
         "hop_outgoing_sqc": (st, [CTX, i, i, sz, d, i, d, i, d, d, sz, u, _dp, _dp, _dp, ip, llp]),
+        # the smoothed density
+        "hop_smooth": (st, [CTX, i, i, sz, d, d, sz, d, d, sz, d, d, sz, u, _dp, _dp, _dp, ip, ip, _dp, llp]),
+        "hop_smooth_mf": (st, [CTX, i, i, sz, d, d, sz, d, d, sz, d, d, sz, u, _dp, _dp, _dp, ip, _dp, llp]),
         # many NLML problems in one launch; the search of several planes in lock-step on it
         "nlml_batch": (st, [CTX, C.POINTER(NlmlProblem), sz, i, u, _dp, _dp, C.POINTER(_dp), ip]),
         "nlml_fit_planes": (st, [CTX, C.POINTER(NlmlFitPlane), sz, i, opt, _dp, _dp, ip, C.POINTER(_dp)]),
@@ -593,7 +597,8 @@ class Api:
         11 = the device work of dvr_spectrum, 12 = the step kernel of hop_evolve, 13 = the bin kernel of hop_bin,
         14 = the step kernel of hop_evolve_groups (12 and 14 also with a decoherence correction), 15 = the step kernel of hop_evolve_mf and
         hop_evolve_groups_mf, 16 = the step kernel of hop_evolve_sqc and hop_evolve_groups_sqc, 17 = the step kernel of hop_evolve_mash and
-        hop_evolve_groups_mash, 18 = the bin kernel of hop_bin_mf, 19 = the bin kernel of hop_outgoing, hop_outgoing_mf and hop_outgoing_sqc."""
+        hop_evolve_groups_mash, 18 = the bin kernel of hop_bin_mf, 19 = the bin kernel of hop_outgoing, hop_outgoing_mf and hop_outgoing_sqc,
+        20 = the three kernels of hop_smooth and hop_smooth_mf."""
         last, total, count = C.c_double(), C.c_double(), C.c_long()
         self._check(self.lib.gple_ctx_get_timing(self.ctx, which, C.byref(last), C.byref(total), C.byref(count)))
         return last.value, total.value, count.value
@@ -1375,6 +1380,31 @@ class Api:
         """gple_hop_density_mf: the accumulator of hop_bin_mf as the adiabatic density (num_pes, num_pes, n_x, n_p) complex, the phase.txt
         layout, on the side acc is on (a tensor: asynchronously on the context's stream); n_norm: the size of the whole ensemble"""
         return self._hop_density("hop_density_mf", int(num_pes), grid, acc, n_norm)
+
+    # ---- the smoothed density (gple_hop_smooth, gple_hop_smooth_mf; DESIGN.md §17, "The ensemble in phase space, smoothed") ------------------------
+    def hop_smooth(self, num_pes, model, state, grid, bandwidth, n_norm, bin_all=False):
+        """gple_hop_smooth: the ensemble as a Gaussian kernel density estimate on grid = (x_first, dx, n_x, p_first, dp, n_p) with
+        bandwidth = (h_x, h_p) -> (rho, (used, nonfinite)).  rho is the adiabatic density (num_pes, num_pes, n_x, n_p) complex, the phase.txt
+        layout, on the side the ensemble is on, as hop_density returns it: populations from the active surface, coherences from the amplitudes.
+        The selection is hop_bin's (bin_all: GPLE_HOP_BIN_ALL); n_norm: the size of the whole ensemble.  The tallies are ready when this
+        returns"""
+        state, n = self._hop_state(int(num_pes), state)
+        return self._hop_smooth("hop_smooth", int(num_pes), model, state, n, self._hop_pointers, grid, bandwidth, n_norm, bin_all)
+
+    def hop_smooth_mf(self, num_pes, model, state, grid, bandwidth, n_norm, bin_all=False):
+        """gple_hop_smooth_mf: hop_smooth from the amplitudes alone (the state's surface is ignored and never passed down), as hop_bin_mf and
+        hop_density_mf -> (rho, (used, nonfinite))"""
+        state, n = self._hop_mf_state(num_pes, state, False)
+        return self._hop_smooth("hop_smooth_mf", int(num_pes), model, state, n, self._hop_mf_pointers, grid, bandwidth, n_norm, bin_all)
+
+    def _hop_smooth(self, name, num_pes, model, state, n, pointers_of, grid, bandwidth, n_norm, bin_all):
+        grid, _ = self._hop_grid(num_pes, grid)
+        h_x, h_p = bandwidth
+        rho = _like(state[0], (num_pes, num_pes, grid[2], grid[5]), np.complex128)
+        (pr,), _ = _io(rho)
+        tally = (C.c_longlong * 2)(0, 0)
+        self._hop_call(name, num_pes, (int(model), n, *grid, float(h_x), float(h_p), int(n_norm)), state, pointers_of, HOP_BIN_ALL if bin_all else 0, (pr, tally))
+        return rho, (int(tally[0]), int(tally[1]))
 
     # ---- symmetrical quasi-classical trajectories (gple_hop_*_sqc; DESIGN.md §17, "Symmetrical quasi-classical trajectories") ----------------------
     # The ensemble is the same 5-tuple; b holds the mapping amplitudes, which are not normalised.  The samples write surface (= surface0); the

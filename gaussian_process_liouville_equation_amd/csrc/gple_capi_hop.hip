@@ -3,6 +3,7 @@
 #include <cmath>
 
 #include "gple_capi.h"
+#include "gple_debug.h"
 
 namespace
 {
@@ -278,6 +279,42 @@ namespace
 		if (!dev) GPLE_HIP(ctx, hipStreamSynchronize(st));
 		return GPLE_OK;
 	}
+	// gple_hop_smooth and gple_hop_smooth_mf around their kernels, as hop_bin_call (surface: null for the call without one): the checks, the
+	// model, rho by the call's GPLE_IO_DEVICE bit, the terms, the partial planes and the two tallies in pooled memory, the timer around the three
+	// kernels alone.  tally is the host's whatever the flags say
+	int hop_smooth_call(gple_ctx* ctx, int num_pes, int model, size_t n, double x_first, double dx, size_t n_x, double p_first, double dp, size_t n_p, double h_x,
+		double h_p, size_t n_norm, unsigned flags, const double* x, const double* p, const double* b, const int* surface, const int* status, double* rho,
+		long long* tally, bool mean_field)
+	{
+		PesModel pes;
+		const double scale = 1.0 / (static_cast<double>(n_norm) * 6.283185307179586 * h_x * h_p); // the denominator left to right
+		if (!ctx || !hop_size_ok(ctx, num_pes, model, n, 0, &pes) || n > (size_t(1) << 31) || !hop_cells_ok(n_x, n_p) || !hop_positive(dx) || !hop_positive(dp) ||
+			!std::isfinite(x_first) || !std::isfinite(p_first) || !hop_positive(h_x) || !hop_positive(h_p) || n_norm == 0 || !hop_positive(scale) ||
+			(flags & (GPLE_HOP_ACCUMULATE | GPLE_HOP_REVERSE)) || !x || !p || !b || !status || !rho)
+			return GPLE_ERR_BAD_ARG;
+		GPLE_OPEN(ctx);
+		const bool dev = flags & GPLE_IO_DEVICE;
+		GPLE_CALL(ctx);
+		hipStream_t stream = ctx->stream;
+		HopStaged st(ctx, flags);
+		GPLE_TRY(st.begin(num_pes, model));
+		Staged r(ctx, dev);
+		Scratch work(ctx), counts(ctx);
+		GPLE_HIP(ctx, work.get(hop_smooth_work_doubles(num_pes, static_cast<long>(n), static_cast<long>(n_x), static_cast<long>(n_p))));
+		GPLE_HIP(ctx, counts.get(2));
+		GPLE_HIP(ctx, r.out(rho, 2 * static_cast<size_t>(num_pes) * num_pes * n_x * n_p));
+		GPLE_TRY(st.arrays(HopStaged::READ, num_pes, n, 0, 0, x, p, b, surface, status));
+		unsigned long long* const c = reinterpret_cast<unsigned long long*>(counts.p);
+		GPLE_HIP(ctx, hipMemsetAsync(c, 0, 2 * sizeof(unsigned long long), stream));
+		const HopGrid g{x_first, dx, p_first, dp, static_cast<long>(n_x), static_cast<long>(n_p)};
+		GPLE_TRY(hop_timed(ctx, GPLE_TIMER_HOP_SMOOTH, [&] {
+			const hipError_t terms = launch_hop_smooth_terms(stream, st.e, st.pes, mean_field, (flags & GPLE_HOP_BIN_ALL) != 0, work.p, c);
+			return terms != hipSuccess ? terms : launch_hop_smooth(stream, num_pes, static_cast<long>(n), g, h_x, h_p, scale, work.p, r.p);
+		}));
+		GPLE_HIP(ctx, r.back());
+		if (tally) GPLE_HIP(ctx, hipMemcpyAsync(tally, c, 2 * sizeof(long long), hipMemcpyDeviceToHost, stream));
+		return st.finish(tally != nullptr);
+	}
 } // namespace
 
 extern "C"
@@ -388,6 +425,29 @@ extern "C"
 			p, b, nullptr, status, acc, [&](hipStream_t s, const HopEnsemble& e, const PesModel& pes, const HopAxis& g, long long* a) {
 				return launch_hop_outgoing_sqc(s, e, pes, mass, window, gamma, g, a);
 			});
+	}
+
+	/* ---- the smoothed density ("The ensemble in phase space, smoothed") -------------------------------------------------------- */
+	int gple_hop_smooth(gple_ctx* ctx, int num_pes, int model, size_t n, double x_first, double dx, size_t n_x, double p_first, double dp, size_t n_p, double h_x,
+		double h_p, size_t n_norm, unsigned flags, const double* x, const double* p, const double* b, const int* surface, const int* status, double* rho,
+		long long* tally)
+	{
+		if (!surface) return GPLE_ERR_BAD_ARG;
+		return hop_smooth_call(ctx, num_pes, model, n, x_first, dx, n_x, p_first, dp, n_p, h_x, h_p, n_norm, flags, x, p, b, surface, status, rho, tally, false);
+	}
+
+	int gple_hop_smooth_mf(gple_ctx* ctx, int num_pes, int model, size_t n, double x_first, double dx, size_t n_x, double p_first, double dp, size_t n_p,
+		double h_x, double h_p, size_t n_norm, unsigned flags, const double* x, const double* p, const double* b, const int* status, double* rho, long long* tally)
+	{
+		return hop_smooth_call(ctx, num_pes, model, n, x_first, dx, n_x, p_first, dp, n_p, h_x, h_p, n_norm, flags, x, p, b, nullptr, status, rho, tally, true);
+	}
+
+	int gple_debug_hop_smooth_split(int num_pes, size_t n, size_t n_x, size_t n_p, size_t* chunk, size_t* n_chunks)
+	{
+		if ((num_pes != 2 && num_pes != 3) || n == 0 || n > (size_t(1) << 31) || !hop_cells_ok(n_x, n_p) || !chunk || !n_chunks) return GPLE_ERR_BAD_ARG;
+		const HopSmoothPlan plan = hop_smooth_plan(num_pes, static_cast<long>(n), static_cast<long>(n_x), static_cast<long>(n_p));
+		*chunk = static_cast<size_t>(plan.chunk), *n_chunks = static_cast<size_t>(plan.n_chunks);
+		return GPLE_OK;
 	}
 
 	/* ---- grouped ensembles ("A curve in one launch") ------------------------------------------------------------------------ */

@@ -6,7 +6,8 @@
  *   tests/test_gpu_chol_diag.py                       -> gple_debug_side_stream, gple_debug_chol_knobs (the give-up test)
  *   tests/test_gpu_parity.py                          -> gple_debug_predict_knobs
  *   tests/test_gpu_format.py                          -> gple_debug_format_knobs
- *   tests/test_gpu_predict_rows.py                    -> gple_debug_fit_factor */
+ *   tests/test_gpu_predict_rows.py                    -> gple_debug_fit_factor
+ *   tests/test_gpu_hop_smooth.py                      -> gple_debug_hop_smooth_split (no device call) */
 #ifndef GPLE_DEBUG_H
 #define GPLE_DEBUG_H
 #include "../../include/gple.h"
@@ -65,6 +66,9 @@ extern "C"
 	 * pass reads them; 0 — the write pass converts again (the default: DESIGN.md §14 has the measurement); negative leaves it alone.  The two must
 	 * agree byte for byte (tests/test_gpu_format.py). */
 	int gple_debug_format_knobs(gple_ctx* ctx, int slots);
+	/* The split of the trajectory index of gple_hop_smooth and gple_hop_smooth_mf (host logic only; DESIGN.md §17, "The ensemble in phase space,
+	 * smoothed"): the trajectories of a chunk and the number of chunks, whose partial sums the finish adds in ascending order. */
+	int gple_debug_hop_smooth_split(int num_pes, size_t n, size_t n_x, size_t n_p, size_t* chunk, size_t* n_chunks);
 #ifdef __cplusplus
 }
 #endif

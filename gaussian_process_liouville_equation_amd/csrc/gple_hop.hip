@@ -1390,4 +1390,272 @@ namespace gple
 	{
 		return hop_outgoing(s, e, model, HopOutSqc{{mass, window, gamma}}, g, acc);
 	}
+
+	// ---- the ensemble in phase space, smoothed -------------------------------------------------------------------------------------------------------
+	// The Gaussian sum of gple_hop_smooth and gple_hop_smooth_mf (include/gple.h; DESIGN.md §17, "The ensemble in phase space, smoothed"):
+	// rho_q = s A_q B with A_q[k, i] = u_qi g_x(x_k - x_i) and B[i, j] = g_p(p_j - p_i), a GEMM over the trajectory index whose operands are
+	// generated in LDS and never stored, on v_mfma_f64_16x16x4_f64 as wigner_kernel of gple_dvr.hip.  Three kernels: the terms (one thread per
+	// trajectory), the contraction (a workgroup per 64 x 64 tile, trajectory chunk and plane group) and the finish (one thread per cell)
+	namespace
+	{
+		typedef double sm4 __attribute__((ext_vector_type(4)));
+		constexpr int SMT = 64;       // grid lines of a tile, in x and in p
+		constexpr int SMK = 16;       // trajectories of a k block
+		constexpr int SML = SMT + 8;  // LDS row stride of the g_x and g_p blocks (doubles)
+		constexpr long SM_MIN_CHUNK = 256;              // trajectories: below this a chunk is not worth a workgroup
+		constexpr long SM_WORKGROUPS = 1024;            // the split aims at this many workgroups: four to each of the chip's 256 CUs
+		constexpr long SM_PARTIAL_DOUBLES = 1L << 24;   // the partial tiles of all chunks stay below this (128 MiB), or at one chunk
+		constexpr int hop_smooth_group(int num_pes) { return num_pes == 2 ? 4 : 3; } // planes a workgroup accumulates: 4 of 4, or 3 of 9
+
+		// One thread per trajectory of the padded index space: x_i, p_i and the num_pes^2 weights u_qi of a used trajectory, zeros for every
+		// other one (unselected, skipped, not finite, padding): the contraction needs no mask and never sees a NaN.  Planes: u_a for the
+		// diagonal a, then (re, im) per pair a < b in row-major order.  MF: the diagonal from the amplitudes and no surface, as hop_bin_mf_kernel;
+		// otherwise 1 on the active surface, as hop_bin_kernel.  The two tallies go by ballot, one atomic per wave and tally
+		template <int NP, typename M, bool MF>
+		__global__ void __launch_bounds__(HOP_BLOCK) hop_smooth_terms_kernel(HopEnsemble e, M model, int bin_all, long npad, double* __restrict__ xs,
+			double* __restrict__ ps, double* __restrict__ u, unsigned long long* __restrict__ tally)
+		{
+			const long i = static_cast<long>(blockIdx.x) * HOP_BLOCK + threadIdx.x;
+			bool used = false, nonfinite = false;
+			double x = 0.0, p = 0.0, w[NP * NP];
+#pragma unroll
+			for (int q = 0; q < NP * NP; ++q) w[q] = 0.0;
+			if (i < e.n)
+			{
+				int a = 0;
+				if constexpr (!MF) a = e.surface[i];
+				const int status = e.status[i];
+				if (status >= 0 && status <= 2 && a >= 0 && a < NP && (status == 0 || bin_all))
+				{
+					const double xi = e.x[i], pi = e.p[i];
+					used = isfinite(xi) && isfinite(pi);
+					nonfinite = !used;
+					if (used)
+					{
+						x = xi, p = pi;
+						double cre[NP], cim[NP], E[NP];
+						hop_adiabatic<NP>(e, model, i, xi, E, cre, cim);
+#pragma unroll
+						for (int k = 0; k < NP; ++k) w[k] = MF ? cre[k] * cre[k] + cim[k] * cim[k] : (a == k ? 1.0 : 0.0);
+						int q = NP;
+#pragma unroll
+						for (int k = 0; k < NP; ++k)
+#pragma unroll
+							for (int l = k + 1; l < NP; ++l)
+							{
+								w[q] = cre[k] * cre[l] + cim[k] * cim[l], w[q + 1] = cim[k] * cre[l] - cre[k] * cim[l];
+								q += 2;
+							}
+					}
+				}
+			}
+			if (i < npad)
+			{
+				xs[i] = x, ps[i] = p;
+#pragma unroll
+				for (int q = 0; q < NP * NP; ++q) u[q * npad + i] = w[q];
+			}
+			const unsigned long long in = __ballot(used), bad = __ballot(nonfinite);
+			if (threadIdx.x % HOP_WAVE == 0)
+			{
+				if (in) atomicAdd(tally, static_cast<unsigned long long>(__popcll(in)));
+				if (bad) atomicAdd(tally + 1, static_cast<unsigned long long>(__popcll(bad)));
+			}
+		}
+
+		struct HopSmoothArgs
+		{
+			const double *xs, *ps, *u; // npad each; u: num_pes^2 planes of npad
+			double* partial;           // [chunk][plane][n_x][n_p]
+			double x_first, dx, p_first, dp, h_x, h_p;
+			long n_x, n_p, npad, chunk; // chunk: trajectories of a chunk, a multiple of SMK
+			int tiles_p, planes;
+		};
+
+		// Fragment maps of v_mfma_f64_16x16x4_f64 (gple_gemm.hip): first operand X[i = lane & 15][k = lane >> 4], second Y[k = lane >> 4][j = lane & 15],
+		// result D[i = (lane >> 4) + 4 reg][j = lane & 15].  X = u_q g_x (rows x), Y = g_p (columns p).  One workgroup = 4 waves (2 x 2) on a 64 x 64
+		// tile of PG planes over one trajectory chunk; each wave a 32 x 32 sub-tile in 2 x 2 fragments per plane.  A k block is 16 trajectories:
+		// the 256 threads form its 16 x 64 values of g_x and of g_p (one division and one exp each, shared by the PG planes) into the LDS buffer
+		// the MFMAs do not read, so a block costs one barrier.  Lines beyond the grid are computed (finite, or 0) and never stored
+		template <int PG>
+		__global__ void __launch_bounds__(256, 2) hop_smooth_kernel(const HopSmoothArgs g)
+		{
+			__shared__ double Gx[2][SMK * SML], Gp[2][SMK * SML], U[2][PG * SMK];
+			const int t = threadIdx.x, lane = t & 63, w = t >> 6, wm = w >> 1, wn = w & 1;
+			const long a0 = static_cast<long>(blockIdx.x / g.tiles_p) * SMT, b0 = static_cast<long>(blockIdx.x % g.tiles_p) * SMT;
+			const long c = blockIdx.y;
+			const int q0 = blockIdx.z * PG;
+			const long i_first = c * g.chunk, i_last = i_first + g.chunk < g.npad ? i_first + g.chunk : g.npad;
+			const int nkb = static_cast<int>((i_last - i_first) / SMK);
+
+			double xk, pj;
+			{
+#pragma clang fp contract(off)
+				xk = g.x_first + g.dx * static_cast<double>(a0 + lane);
+				pj = g.p_first + g.dp * static_cast<double>(b0 + lane);
+			}
+			auto generate = [&](int kb, int buf) {
+#pragma clang fp contract(off)
+				const long i0 = i_first + static_cast<long>(kb) * SMK;
+				double xi[4], pi[4];
+#pragma unroll
+				for (int r = 0; r < 4; ++r) xi[r] = g.xs[i0 + w + 4 * r], pi[r] = g.ps[i0 + w + 4 * r];
+				double uv = 0.0;
+				if (t < PG * SMK) uv = g.u[(q0 + t / SMK) * g.npad + i0 + t % SMK];
+#pragma unroll
+				for (int r = 0; r < 4; ++r)
+				{
+					const double tx = (xk - xi[r]) / g.h_x, tp = (pj - pi[r]) / g.h_p;
+					Gx[buf][(w + 4 * r) * SML + lane] = exp(-0.5 * tx * tx);
+					Gp[buf][(w + 4 * r) * SML + lane] = exp(-0.5 * tp * tp);
+				}
+				if (t < PG * SMK) U[buf][t] = uv;
+			};
+
+			sm4 acc[PG][2][2];
+#pragma unroll
+			for (int q = 0; q < PG; ++q)
+#pragma unroll
+				for (int i = 0; i < 2; ++i)
+#pragma unroll
+					for (int j = 0; j < 2; ++j) acc[q][i][j] = (sm4){0.0, 0.0, 0.0, 0.0};
+
+			const int fk = lane >> 4, fr = lane & 15;
+			if (nkb > 0) generate(0, 0);
+			__syncthreads();
+			for (int kb = 0; kb < nkb; ++kb)
+			{
+				const int buf = kb & 1;
+				if (kb + 1 < nkb) generate(kb + 1, buf ^ 1);
+#pragma unroll
+				for (int kk = 0; kk < SMK; kk += 4)
+				{
+					const int kl = kk + fk;
+					double gx[2], gp[2];
+#pragma unroll
+					for (int i = 0; i < 2; ++i) gx[i] = Gx[buf][kl * SML + wm * 32 + i * 16 + fr];
+#pragma unroll
+					for (int j = 0; j < 2; ++j) gp[j] = Gp[buf][kl * SML + wn * 32 + j * 16 + fr];
+#pragma unroll
+					for (int q = 0; q < PG; ++q)
+					{
+						const double uq = U[buf][q * SMK + kl];
+#pragma unroll
+						for (int i = 0; i < 2; ++i)
+						{
+							const double a = uq * gx[i];
+#pragma unroll
+							for (int j = 0; j < 2; ++j) acc[q][i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, gp[j], acc[q][i][j], 0, 0, 0);
+						}
+					}
+				}
+				__syncthreads();
+			}
+
+			const long cells = g.n_x * g.n_p;
+#pragma unroll
+			for (int q = 0; q < PG; ++q)
+			{
+				double* __restrict__ out = g.partial + (c * g.planes + q0 + q) * cells;
+#pragma unroll
+				for (int i = 0; i < 2; ++i)
+#pragma unroll
+					for (int j = 0; j < 2; ++j)
+#pragma unroll
+						for (int r = 0; r < 4; ++r)
+						{
+							const long a = a0 + wm * 32 + i * 16 + fk + 4 * r, b = b0 + wn * 32 + j * 16 + fr;
+							if (a < g.n_x && b < g.n_p) out[a * g.n_p + b] = acc[q][i][j][r];
+						}
+			}
+		}
+
+		// One thread per cell: the chunks' partial sums added in ascending order, times s, in the phase.txt layout.  Im rho_aa is +0, and a
+		// lower plane is formed from the negated sum (exactly the conjugate, and +0 where the sum is 0)
+		template <int NP>
+		__global__ void __launch_bounds__(HOP_BLOCK) hop_smooth_finish_kernel(long cells, long n_chunks, double s, const double* __restrict__ partial,
+			double* __restrict__ rho)
+		{
+			const long cell = static_cast<long>(blockIdx.x) * HOP_BLOCK + threadIdx.x;
+			if (cell >= cells) return;
+			double sum[NP * NP];
+#pragma unroll
+			for (int q = 0; q < NP * NP; ++q) sum[q] = partial[q * cells + cell];
+			for (long c = 1; c < n_chunks; ++c)
+#pragma unroll
+				for (int q = 0; q < NP * NP; ++q) sum[q] += partial[(c * NP * NP + q) * cells + cell];
+#pragma unroll
+			for (int a = 0; a < NP; ++a)
+			{
+				double* d = rho + 2 * ((a * NP + a) * cells + cell);
+				d[0] = s * sum[a], d[1] = 0.0;
+			}
+			int q = NP;
+#pragma unroll
+			for (int a = 0; a < NP; ++a)
+#pragma unroll
+				for (int b = a + 1; b < NP; ++b)
+				{
+					double *up = rho + 2 * ((a * NP + b) * cells + cell), *lo = rho + 2 * ((b * NP + a) * cells + cell);
+					up[0] = lo[0] = s * sum[q];
+					up[1] = s * sum[q + 1], lo[1] = s * (0.0 - sum[q + 1]);
+					q += 2;
+				}
+		}
+	} // namespace
+
+	// The split of the trajectory index: a function of (num_pes, n, n_x, n_p) alone, so that two calls add the same partial sums in the same order
+	HopSmoothPlan hop_smooth_plan(int num_pes, long n, long n_x, long n_p)
+	{
+		HopSmoothPlan plan{};
+		const long planes = static_cast<long>(num_pes) * num_pes, cells = n_x * n_p;
+		plan.groups = static_cast<int>(planes / hop_smooth_group(num_pes));
+		plan.tiles_x = (n_x + SMT - 1) / SMT, plan.tiles_p = (n_p + SMT - 1) / SMT;
+		const long tiles = plan.tiles_x * plan.tiles_p * plan.groups;
+		const long most = std::max(1L, std::min(SM_WORKGROUPS / tiles, SM_PARTIAL_DOUBLES / (planes * cells)));
+		const long even = ((n + most - 1) / most + SMK - 1) / SMK * SMK;
+		plan.chunk = std::max(SM_MIN_CHUNK, even);
+		plan.n_chunks = (n + plan.chunk - 1) / plan.chunk;
+		plan.npad = (n + SMK - 1) / SMK * SMK;
+		return plan;
+	}
+	size_t hop_smooth_work_doubles(int num_pes, long n, long n_x, long n_p)
+	{
+		const HopSmoothPlan plan = hop_smooth_plan(num_pes, n, n_x, n_p);
+		const size_t planes = static_cast<size_t>(num_pes) * num_pes;
+		return (2 + planes) * static_cast<size_t>(plan.npad) + static_cast<size_t>(plan.n_chunks) * planes * static_cast<size_t>(n_x) * static_cast<size_t>(n_p);
+	}
+	hipError_t launch_hop_smooth_terms(hipStream_t s, const HopEnsemble& e, PesModel model, bool mean_field, bool bin_all, double* work, unsigned long long* tally)
+	{
+		if (e.n <= 0) return hipErrorInvalidValue;
+		const long npad = (e.n + SMK - 1) / SMK * SMK;
+		double *xs = work, *ps = work + npad, *u = work + 2 * npad;
+		const int all = bin_all ? 1 : 0;
+		return hop_dispatch(e, model, [&](auto np, auto m) {
+			if (mean_field) hop_launch(s, npad, hop_smooth_terms_kernel<np(), decltype(m), true>, e, m, all, npad, xs, ps, u, tally);
+			else hop_launch(s, npad, hop_smooth_terms_kernel<np(), decltype(m), false>, e, m, all, npad, xs, ps, u, tally);
+		});
+	}
+	hipError_t launch_hop_smooth(hipStream_t s, int num_pes, long n, const HopGrid& g, double h_x, double h_p, double scale, double* work, double* rho)
+	{
+		if ((num_pes != 2 && num_pes != 3) || n <= 0 || g.n_x <= 0 || g.n_p <= 0) return hipErrorInvalidValue;
+		const HopSmoothPlan plan = hop_smooth_plan(num_pes, n, g.n_x, g.n_p);
+		const int planes = num_pes * num_pes;
+		double* const partial = work + (2 + planes) * plan.npad;
+		const HopSmoothArgs a{work, work + plan.npad, work + 2 * plan.npad, partial, g.x_first, g.dx, g.p_first, g.dp, h_x, h_p, g.n_x, g.n_p, plan.npad, plan.chunk,
+			static_cast<int>(plan.tiles_p), planes};
+		const dim3 grid(static_cast<unsigned>(plan.tiles_x * plan.tiles_p), static_cast<unsigned>(plan.n_chunks), static_cast<unsigned>(plan.groups));
+		const long cells = g.n_x * g.n_p;
+		if (num_pes == 2)
+		{
+			hipLaunchKernelGGL(hop_smooth_kernel<hop_smooth_group(2)>, grid, dim3(256), 0, s, a);
+			hop_launch(s, cells, hop_smooth_finish_kernel<2>, cells, plan.n_chunks, scale, partial, rho);
+		}
+		else
+		{
+			hipLaunchKernelGGL(hop_smooth_kernel<hop_smooth_group(3)>, grid, dim3(256), 0, s, a);
+			hop_launch(s, cells, hop_smooth_finish_kernel<3>, cells, plan.n_chunks, scale, partial, rho);
+		}
+		return hipGetLastError();
+	}
 } // namespace gple

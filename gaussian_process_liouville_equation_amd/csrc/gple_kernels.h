@@ -521,6 +521,22 @@ namespace gple
 	hipError_t launch_hop_outgoing(hipStream_t s, const HopEnsemble& e, PesModel model, double mass, const HopAxis& g, long long* acc);
 	hipError_t launch_hop_outgoing_mf(hipStream_t s, const HopEnsemble& e, PesModel model, double mass, const HopAxis& g, long long* acc);
 	hipError_t launch_hop_outgoing_sqc(hipStream_t s, const HopEnsemble& e, PesModel model, double mass, int window, double gamma, const HopAxis& g, long long* acc);
+	// The smoothed density of gple_hop_smooth ("The ensemble in phase space, smoothed").  The split of the trajectory index: chunks
+	// of `chunk` trajectories (a multiple of 16; the last one shorter), n_chunks of them, npad = n rounded up to 16; a function of
+	// (num_pes, n, n_x, n_p) alone.  work: hop_smooth_work_doubles() doubles, the terms (x, p and num_pes^2 weights, npad each) and then the
+	// chunks' partial planes, at most max(2^24, num_pes^2 n_x n_p) doubles of them
+	struct HopSmoothPlan
+	{
+		long npad, chunk, n_chunks, tiles_x, tiles_p;
+		int groups;
+	};
+	HopSmoothPlan hop_smooth_plan(int num_pes, long n, long n_x, long n_p);
+	size_t hop_smooth_work_doubles(int num_pes, long n, long n_x, long n_p);
+	// the terms of every trajectory into work (zeros for the ones that do not contribute) and the tallies [used, nonfinite] added to tally;
+	// mean_field: the diagonal weights from the amplitudes and e.surface not read
+	hipError_t launch_hop_smooth_terms(hipStream_t s, const HopEnsemble& e, PesModel model, bool mean_field, bool bin_all, double* work, unsigned long long* tally);
+	// the contraction and the finish: rho = scale sum_i u_i g_x g_p in the phase.txt layout, from the terms in work
+	hipError_t launch_hop_smooth(hipStream_t s, int num_pes, long n, const HopGrid& g, double h_x, double h_p, double scale, double* work, double* rho);
 
 	// ---- reconstruction of a gridded density (gple_recon.hip; test/gpr.cpp): num_pes = 2 or 3, rho: num_pes^2 x nx x np (re, im) ----
 	constexpr int RECON_SURVEY_BLOCKS = 64, RECON_SURVEY_VALUES = 7; // row blocks of the survey, values per plane and block

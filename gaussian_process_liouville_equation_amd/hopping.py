@@ -7,7 +7,8 @@ column for column with exact.run(flux=True)'s.
     phase_grid_of()   the phase-space grid of a run, from its size
     run()             sample, then per output time one hop_evolve of output_step steps and one hop_observe; t.txt and averages.txt.  With a
                       phase_grid also one gple_hop_bin and gple_hop_density: x.txt, p.txt and phase.txt, the adiabatic density of the ensemble
-                      (phase_density="amplitude": gple_hop_bin_mf and gple_hop_density_mf, which "ehrenfest" runs have too).  With outgoing
+                      (phase_density="amplitude": gple_hop_bin_mf and gple_hop_density_mf, which "ehrenfest" runs have too).  With phase_smooth
+                      the phase.txt block is the Gaussian kernel density estimate of gple_hop_smooth (_mf) instead.  With outgoing
                       also one gple_hop_outgoing (_mf, _sqc) per axis on the final state: outgoing_p.txt and outgoing_e.txt, what left the
                       box per side and level by momentum and by energy (outgoing_density(), outgoing_grids(), write_outgoing())
     scan()            the branching probabilities at many momenta from one grouped ensemble (gple_hop_sample_groups / _evolve_groups /
@@ -314,6 +315,34 @@ def outgoing_grids(api, num_pes, model, s, surface0, request):
     return grids
 
 
+def _smooth_request(phase_smooth, phase_grid):
+    """run(phase_smooth=...) checked before any api call -> None, "scott" or the pair (h_x, h_p) as floats"""
+    if phase_smooth is None:
+        return None
+    if phase_grid is None:
+        raise ValueError("phase_smooth belongs to a phase_grid")
+    if isinstance(phase_smooth, str):
+        if phase_smooth != "scott":
+            raise ValueError('phase_smooth is None, "scott" or a pair (h_x, h_p) of finite positive numbers')
+        return phase_smooth
+    try:
+        h_x, h_p = (float(h) for h in phase_smooth)
+    except (TypeError, ValueError):
+        raise ValueError('phase_smooth is None, "scott" or a pair (h_x, h_p) of finite positive numbers') from None
+    if not (np.isfinite(h_x) and np.isfinite(h_p) and h_x > 0.0 and h_p > 0.0):
+        raise ValueError('phase_smooth is None, "scott" or a pair (h_x, h_p) of finite positive numbers')
+    return (h_x, h_p)
+
+
+def smooth_bandwidth(request, s, n_traj):
+    """The bandwidths (h_x, h_p) of run(phase_smooth=...): a pair as it is; "scott": Scott's rule for a Gaussian kernel in two dimensions,
+    h = sigma n_traj^(-1/6) per axis with the packet's sigma_x and sigma_p"""
+    if request == "scott":
+        factor = float(n_traj) ** (-1.0 / 6.0)
+        return (float(s["sigma_x"]) * factor, float(s["sigma_p"]) * factor)
+    return request
+
+
 def write_outgoing(out_dir, axis, grid, density):
     """outgoing_p.txt: a line per (side, level) with the n_bins densities per unit momentum, the layout of exact_mqcl's absorbed_p.txt;
     outgoing_e.txt: a line per bin with E and the 2 num_pes densities per unit energy, the layout of exact's spectrum.txt"""
@@ -327,7 +356,8 @@ def write_outgoing(out_dir, axis, grid, density):
 
 
 def run(api, model=DAC, num_pes=2, ln_energy=0.0, n_traj=10000, seed=0, out_dir=None, reverse_frustrated=False, dt=None, surface0=0, max_outputs=None,
-        log=None, phase_grid=None, decoherence=None, edc_c=0.1, method="fssh", window=None, gamma=None, phase_density=None, outgoing=None, **setup_kw):
+        log=None, phase_grid=None, decoherence=None, edc_c=0.1, method="fssh", window=None, gamma=None, phase_density=None, outgoing=None, phase_smooth=None,
+        **setup_kw):
     """n_traj trajectories from the packet of exact.setup(ln_energy, boundary=ABSORBING, **setup_kw) (x0, sigma_x, p0, sigma_p, mass) on the adiabatic
     surface surface0, evolved with the time step dt (default: the setup's dt_rule, the reference's own rule) between x_left = xmin and
     x_right = xmax; a trajectory that leaves is finished and counted by side and active surface.  The ensemble stays on the device: every
@@ -363,11 +393,19 @@ def run(api, model=DAC, num_pes=2, ln_energy=0.0, n_traj=10000, seed=0, out_dir=
     the outgoing momentum or in the energy the method conserves.  The result gains `outgoing`: per axis grid, density (outgoing_density with
     n_norm the sample behind the scattering line, so that density step summed over the bins is `scattered` where nothing is outside), acc and
     tallies; with out_dir also outgoing_p.txt and outgoing_e.txt (write_outgoing).  Anything else in outgoing is a ValueError before any call.
+    phase_smooth (with a phase_grid only; None: nothing below happens, call for call and key for key): "scott" (smooth_bandwidth: h = sigma
+    n_traj^(-1/6) per axis) or a pair (h_x, h_p) of finite positive numbers.  Every output time still makes its hop_bin (or hop_bin_mf) call,
+    so binned, outside and binned_counts or binned_weights stay as they are, and also one hop_smooth (phase_density None or "mixed") or
+    hop_smooth_mf ("amplitude"), the Gaussian kernel density estimate of DESIGN.md §17, "The ensemble in phase space, smoothed": its field is
+    the phase.txt block in place of hop_density's, and the record gains smoothed and nonfinite, the call's two tallies.  The result gains
+    phase_smooth, the pair used.  Anything else in phase_smooth, or one without a phase_grid, is a ValueError before any call; a method that
+    refuses a phase_grid refuses this with it.
     Returns the setup, the records (t and unpack() per output time), stop, and scattering_line: the head of exact.run's final line, the
     fractions that left [left | right][surface], and the fraction still running."""
     m = _method(method, decoherence, reverse_frustrated, phase_grid, window, gamma, num_pes, phase_density)
     tail = sqc_window(window, gamma) if m.windowed else ()  # what follows surface0 in the sample and mass in the observe
     request = _outgoing_request(outgoing)
+    smooth = _smooth_request(phase_smooth, phase_grid)
     amplitude = phase_density == "amplitude"
     setup_kw["boundary"] = exact.ABSORBING
     s = exact.setup(ln_energy, **setup_kw)
@@ -381,6 +419,7 @@ def run(api, model=DAC, num_pes=2, ln_energy=0.0, n_traj=10000, seed=0, out_dir=
     t0 = time.perf_counter()
     state = _call(api, "sample", m.sample)(num_pes, model, n_traj, seed, s["x0"], s["p0"], s["sigma_x"], s["sigma_p"], surface0, *tail, device_out=True)
     grid = None if phase_grid is None else phase_grid_of(api, num_pes, model, s, phase_grid)
+    bandwidth = smooth_bandwidth(smooth, s, n_traj)
     files = {}
     if out_dir is not None:
         os.makedirs(out_dir, exist_ok=True)
@@ -397,8 +436,11 @@ def run(api, model=DAC, num_pes=2, ln_energy=0.0, n_traj=10000, seed=0, out_dir=
             rec["t"] = step * dt
             if grid is not None:
                 acc = (api.hop_bin_mf if amplitude else api.hop_bin)(num_pes, model, state, grid)
+                if bandwidth is not None:
+                    rho, (rec["smoothed"], rec["nonfinite"]) = (api.hop_smooth_mf if amplitude else api.hop_smooth)(num_pes, model, state, grid, bandwidth, n_traj)
                 if files:
-                    rho = (api.hop_density_mf if amplitude else api.hop_density)(num_pes, grid, acc, n_traj)
+                    if bandwidth is None:
+                        rho = (api.hop_density_mf if amplitude else api.hop_density)(num_pes, grid, acc, n_traj)
                     files["phase.txt"].write(exact.phase_text(api, rho[None]) if hasattr(api, "format_g") else exact.phase_block(rho).encode())
                 if hasattr(acc, "is_cuda"):
                     api.synchronize()  # the context's stream has written acc: now the framework's may read it
@@ -441,6 +483,8 @@ def run(api, model=DAC, num_pes=2, ln_energy=0.0, n_traj=10000, seed=0, out_dir=
     result = m.result(dict(setup=s, dt=dt, output_step=output_step, total_step=total_step, n_traj=n_traj, records=records, stop=stop, state=state,
                            scattered=scattered, scattering_line=line, stop_time=records[-1]["t"], steps=step, total_seconds=t_end - t0,
                            decoherence=decoherence, edc_c=edc_c, method=method, phase_density=phase_density), tail, n_f, last)
+    if bandwidth is not None:
+        result = dict(result, phase_smooth=bandwidth)
     return dict(result, outgoing=left) if request else result
 
 

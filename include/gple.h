@@ -164,7 +164,8 @@ typedef enum gple_timer {
 	GPLE_TIMER_HOP_SQC = 16,       /* the step kernel of one gple_hop_evolve_sqc or gple_hop_evolve_groups_sqc call (all its steps, no staging); count = calls */
 	GPLE_TIMER_HOP_MASH = 17,      /* the step kernel of one gple_hop_evolve_mash or gple_hop_evolve_groups_mash call (all its steps, no staging); count = calls */
 	GPLE_TIMER_HOP_BIN_MF = 18,    /* the bin kernel of one gple_hop_bin_mf call (no staging, no clear); count = calls */
-	GPLE_TIMER_HOP_OUTGOING = 19   /* the bin kernel of one gple_hop_outgoing, _outgoing_mf or _outgoing_sqc call (no staging, no clear); count = calls */
+	GPLE_TIMER_HOP_OUTGOING = 19,  /* the bin kernel of one gple_hop_outgoing, _outgoing_mf or _outgoing_sqc call (no staging, no clear); count = calls */
+	GPLE_TIMER_HOP_SMOOTH = 20     /* the three kernels of one gple_hop_smooth or gple_hop_smooth_mf call (terms, contraction, finish; no staging); count = calls */
 } gple_timer;
 int gple_ctx_enable_timing(gple_ctx* ctx, int on);
 /* Synchronises the stream, then: last = milliseconds of the most recent interval; total / count = accumulated since
@@ -848,6 +849,40 @@ int gple_hop_outgoing_mf(gple_ctx* ctx, int num_pes, int model, size_t n, double
 	unsigned flags, const double* x, const double* p, const double* b, const int* status, long long* acc);
 int gple_hop_outgoing_sqc(gple_ctx* ctx, int num_pes, int model, size_t n, double mass, int window, double gamma, int axis, double first, double step,
 	size_t n_bins, unsigned flags, const double* x, const double* p, const double* b, const int* status, long long* acc);
+/* The ensemble's adiabatic density matrix as a smooth field ("The ensemble in phase space, smoothed"): a Gaussian kernel density
+ * estimate in x and p, straight from the ensemble to the phase.txt layout with no integer accumulator in between.  gple_hop_smooth is the
+ * smooth form of gple_hop_bin + gple_hop_density (populations from the active surface), gple_hop_smooth_mf that of gple_hop_bin_mf +
+ * gple_hop_density_mf (populations from the amplitudes, no surface array).
+ * Grid: gple_hop_bin's, x_k = x_first + dx k, k < n_x, and p_j = p_first + dp j, j < n_p (one product and one sum each).  Bandwidths: h_x and
+ * h_p, finite and positive.
+ * Selection: that of the bin call.  gple_hop_smooth: status 0, or 0 ... 2 with GPLE_HOP_BIN_ALL; a status or a surface out of range is
+ * skipped.  gple_hop_smooth_mf: the same without a surface.  A selected trajectory whose x or p is not finite adds one to `nonfinite` and
+ * nothing else (the analogue of `outside`); every other selected trajectory adds one to `used` and contributes to every cell.
+ * Terms of a used trajectory, with c = C^T b at its x as the bin calls form it: for a pair a < b
+ *     re = cre_a cre_b + cim_a cim_b,   im = cim_a cre_b - cre_a cim_b;
+ * for the diagonal a, u = 1 where surface == a and 0 elsewhere (gple_hop_smooth), u = cre_a^2 + cim_a^2 (gple_hop_smooth_mf): num_pes^2 real
+ * weights u_q per trajectory.
+ * Field: t_x = (x_k - x_i) / h_x, g_x = exp(-1/2 t_x t_x) (the product as (-0.5 t_x) t_x), the same for p, and
+ *     rho_q(k, j) = s sum_i u_qi g_x g_p,   s = 1 / ((double)n_norm 2 pi h_x h_p), the denominator formed left to right.
+ * rho: num_pes^2 planes of n_x x n_p (re, im) pairs, the layout of gple_hop_density.  Im rho_aa = +0 exactly; a lower plane is the conjugate
+ * of the upper one, formed from the negated sum (+0 where the sum is 0).  tally (nullable, a host array whatever the flags say): two
+ * integers [used, nonfinite].
+ * Normalisation: with n_norm the size of the ensemble, sum_a sum_cells rho_aa dx dp = used / n_norm, up to the part of the Gaussians that
+ * lies off the grid and a quadrature error of 2 exp(-2 pi^2 (h / d)^2) per axis: 1.4e-9 at h = d, 7.9e-6 at h = 0.75 d, at rounding from
+ * h = 1.5 d.  For h_x h_p >= hbar / 2 the field is a Husimi-like, positive picture.
+ * Determinism: the sum is floating point.  The split of the trajectory index over workgroups and the order in which partial sums are added
+ * depend on (n, n_x, n_p, num_pes) alone: two calls give the same bits, and device pointers give the bits of host pointers.  There is no
+ * GPLE_HOP_ACCUMULATE form: a slice plus its complement would not be the whole, bit for bit.
+ * Flags: GPLE_IO_DEVICE (the five arrays and rho), GPLE_HOP_BIN_ALL.  Timer: GPLE_TIMER_HOP_SMOOTH.
+ * GPLE_ERR_BAD_ARG, with nothing written: num_pes not 2 or 3, a model the other hop calls refuse, n == 0, n > 2^31, n_x or n_p zero,
+ * n_x n_p > GPLE_HOP_MAX_CELLS, dx or dp not finite and positive, x_first or p_first not finite, h_x or h_p not finite and positive,
+ * n_norm == 0, an s that is not finite and positive, the flags GPLE_HOP_ACCUMULATE and GPLE_HOP_REVERSE, a null array (tally excepted). */
+int gple_hop_smooth(gple_ctx* ctx, int num_pes, int model, size_t n, double x_first, double dx, size_t n_x, double p_first, double dp, size_t n_p,
+	double h_x, double h_p, size_t n_norm, unsigned flags, const double* x, const double* p, const double* b, const int* surface, const int* status,
+	double* rho, long long* tally);
+int gple_hop_smooth_mf(gple_ctx* ctx, int num_pes, int model, size_t n, double x_first, double dx, size_t n_x, double p_first, double dp, size_t n_p,
+	double h_x, double h_p, size_t n_norm, unsigned flags, const double* x, const double* p, const double* b, const int* status, double* rho,
+	long long* tally);
 
 /* generate_markov_chain (mc.cpp:118-165) for n walkers at once on the fitted distribution |cut-off prediction| of `element`:
  * num_steps Metropolis steps with uniform displacements in [-max_displacement, max_displacement) per dimension; r (2n) holds
