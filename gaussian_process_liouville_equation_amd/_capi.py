@@ -29,6 +29,8 @@ TIMER_HOP_MASH = 17  # gple_timer: the step kernel of one gple_hop_evolve_mash o
 TIMER_HOP_BIN_MF = 18  # gple_timer: the bin kernel of one gple_hop_bin_mf call
 TIMER_HOP_OUTGOING = 19  # gple_timer: the bin kernel of one gple_hop_outgoing, gple_hop_outgoing_mf or gple_hop_outgoing_sqc call
 TIMER_HOP_SMOOTH = 20  # gple_timer: the three kernels of one gple_hop_smooth or gple_hop_smooth_mf call
+TIMER_SCATTER = 21  # gple_timer: the march kernel of one gple_scatter call
+SCATTER_MAX_ENERGIES, SCATTER_MAX_STEPS = 1 << 20, 1 << 24  # the bounds of gple_scatter
 # GPLE_HOP_AXIS_*: what gple_hop_outgoing bins by, and the names Api.hop_outgoing takes for them
 HOP_AXIS_MOMENTUM, HOP_AXIS_ENERGY = range(2)
 HOP_AXIS_NAMES = {"momentum": HOP_AXIS_MOMENTUM, "energy": HOP_AXIS_ENERGY}
@@ -415,6 +417,8 @@ def _signatures():
         # the smoothed density
         "hop_smooth": (st, [CTX, i, i, sz, d, d, sz, d, d, sz, d, d, sz, u, _dp, _dp, _dp, ip, ip, _dp, llp]),
         "hop_smooth_mf": (st, [CTX, i, i, sz, d, d, sz, d, d, sz, d, d, sz, u, _dp, _dp, _dp, ip, _dp, llp]),
+        # exact branching probabilities per energy
+        "scatter": (st, [CTX, i, i, d, d, d, sz, sz, _dp, u, _dp, _dp]),
         # many NLML problems in one launch; the search of several planes in lock-step on it
         "nlml_batch": (st, [CTX, C.POINTER(NlmlProblem), sz, i, u, _dp, _dp, C.POINTER(_dp), ip]),
         "nlml_fit_planes": (st, [CTX, C.POINTER(NlmlFitPlane), sz, i, opt, _dp, _dp, ip, C.POINTER(_dp)]),
@@ -598,7 +602,7 @@ class Api:
         14 = the step kernel of hop_evolve_groups (12 and 14 also with a decoherence correction), 15 = the step kernel of hop_evolve_mf and
         hop_evolve_groups_mf, 16 = the step kernel of hop_evolve_sqc and hop_evolve_groups_sqc, 17 = the step kernel of hop_evolve_mash and
         hop_evolve_groups_mash, 18 = the bin kernel of hop_bin_mf, 19 = the bin kernel of hop_outgoing, hop_outgoing_mf and hop_outgoing_sqc,
-        20 = the three kernels of hop_smooth and hop_smooth_mf."""
+        20 = the three kernels of hop_smooth and hop_smooth_mf, 21 = the march kernel of scatter."""
         last, total, count = C.c_double(), C.c_double(), C.c_long()
         self._check(self.lib.gple_ctx_get_timing(self.ctx, which, C.byref(last), C.byref(total), C.byref(count)))
         return last.value, total.value, count.value
@@ -918,6 +922,32 @@ class Api:
                                                _ptr(psi0.view(np.float64)), _ptr(energies), n_E, 0, _ptr(density),
                                                None if psi_e is None else _ptr(psi_e.view(np.float64)), _ptr(remaining)))
         return density, psi_e, (float(remaining[0]) if want_remaining else None)
+
+    # ---- exact branching probabilities per energy (gple_scatter) ---------------------------------------------------------------------------------
+    def scatter(self, num_pes, model, mass, x_left, x_right, n_steps, energies, want_defect=True):
+        """gple_scatter: (prob, defect) of the coupled-channel Schrodinger equation on `model` at the total energies `energies` (the potential's
+        own zero; a numpy array, or a contiguous float64 tensor on the GPU, which gives device tensors back), by the renormalised Numerov method on
+        x_left + n h, n = 0 ... n_steps, the potential constant beyond both ends.  prob (n_E, num_pes, 2, num_pes),
+        [energy, incoming surface, side (0 reflected, 1 transmitted), final surface]: exactly 0 for a closed final channel, NaN for a closed
+        incoming one.  defect (n_E, num_pes), or None without want_defect: the probability sum of an incoming channel minus one"""
+        num_pes = int(num_pes)
+        if _on_device(energies):
+            if str(energies.dtype) != "torch.float64" or energies.dim() != 1:
+                raise ValueError("energies must be a float64 tensor (n_E,)")
+            import torch
+            torch.cuda.synchronize(energies.device)  # whatever produced the energies, before the context's stream reads them
+        else:
+            energies = np.atleast_1d(_f64(energies))
+        n_E = int(energies.shape[0])
+        if len(energies.shape) != 1 or not 1 <= n_E <= SCATTER_MAX_ENERGIES:
+            raise ValueError(f"energies (n_E,) with 1 <= n_E <= {SCATTER_MAX_ENERGIES}")
+        prob = _like(energies, (n_E, num_pes, 2, num_pes))
+        defect = _like(energies, (n_E, num_pes)) if want_defect else None
+        (pe, pp, pd), flags = _io(energies, prob, defect)
+        self._check(self.lib.gple_scatter(self.ctx, num_pes, int(model), float(mass), float(x_left), float(x_right), int(n_steps), n_E, pe, flags, pp, pd))
+        if flags:
+            self.synchronize()
+        return prob, defect
 
     # ---- text output (gple_format_g) ------------------------------------------------------------------------------------------------------------
     def format_g(self, values, per_line, lines_per_block=0, join=False):

@@ -108,7 +108,7 @@ namespace gple
 		bool timing = false;
 		std::vector<hipEvent_t> ev_free;
 		std::vector<TimedSpan> pending;
-		static constexpr int NTIMERS = 21; // gple_timer: one more than the last GPLE_TIMER_*
+		static constexpr int NTIMERS = 22; // gple_timer: one more than the last GPLE_TIMER_*
 		TimedSpan open_span[NTIMERS] = {};
 		double t_last[NTIMERS] = {}, t_total[NTIMERS] = {};
 		long t_count[NTIMERS] = {};

@@ -538,6 +538,16 @@ namespace gple
 	// the contraction and the finish: rho = scale sum_i u_i g_x g_p in the phase.txt layout, from the terms in work
 	hipError_t launch_hop_smooth(hipStream_t s, int num_pes, long n, const HopGrid& g, double h_x, double h_p, double scale, double* work, double* rho);
 
+	// ---- coupled-channel scattering (gple_scatter.hip): the renormalised Numerov march of gple_scatter, one thread per energy ----
+	// c = (h^2 / 12)(2 m / hbar^2) with h = (x_right - x_left) / n_steps, formed left to right: the factor of T_n = c (V_n - E)
+	double scatter_step_constant(double mass, double x_left, double x_right, long n_steps);
+	// the table of a call: the upper triangle of V_n, row by row, for n = 0 ... n_steps, then the ascending eigenvalues of V_0 and of V_{n_steps}
+	size_t scatter_table_doubles(int num_pes, long n_steps);
+	hipError_t launch_scatter_table(hipStream_t s, int num_pes, PesModel model, double x_left, double x_right, long n_steps, double* table);
+	// prob: n_E x num_pes (incoming) x 2 (reflected, transmitted) x num_pes (final); defect (nullable): n_E x num_pes.  Device pointers
+	hipError_t launch_scatter(hipStream_t s, int num_pes, double c, long n_steps, const double* table, const double* energies, long n_E, double* prob,
+		double* defect);
+
 	// ---- reconstruction of a gridded density (gple_recon.hip; test/gpr.cpp): num_pes = 2 or 3, rho: num_pes^2 x nx x np (re, im) ----
 	constexpr int RECON_SURVEY_BLOCKS = 64, RECON_SURVEY_VALUES = 7; // row blocks of the survey, values per plane and block
 	constexpr int RECON_MAX_PLANES = 9, RECON_MAX_N = 4096, RECON_SUMS = 6;

@@ -165,7 +165,8 @@ typedef enum gple_timer {
 	GPLE_TIMER_HOP_MASH = 17,      /* the step kernel of one gple_hop_evolve_mash or gple_hop_evolve_groups_mash call (all its steps, no staging); count = calls */
 	GPLE_TIMER_HOP_BIN_MF = 18,    /* the bin kernel of one gple_hop_bin_mf call (no staging, no clear); count = calls */
 	GPLE_TIMER_HOP_OUTGOING = 19,  /* the bin kernel of one gple_hop_outgoing, _outgoing_mf or _outgoing_sqc call (no staging, no clear); count = calls */
-	GPLE_TIMER_HOP_SMOOTH = 20     /* the three kernels of one gple_hop_smooth or gple_hop_smooth_mf call (terms, contraction, finish; no staging); count = calls */
+	GPLE_TIMER_HOP_SMOOTH = 20,    /* the three kernels of one gple_hop_smooth or gple_hop_smooth_mf call (terms, contraction, finish; no staging); count = calls */
+	GPLE_TIMER_SCATTER = 21        /* the march kernel of one gple_scatter call (no table of the potential, no staging); count = calls */
 } gple_timer;
 int gple_ctx_enable_timing(gple_ctx* ctx, int on);
 /* Synchronises the stream, then: last = milliseconds of the most recent interval; total / count = accumulated since
@@ -883,6 +884,37 @@ int gple_hop_smooth(gple_ctx* ctx, int num_pes, int model, size_t n, double x_fi
 int gple_hop_smooth_mf(gple_ctx* ctx, int num_pes, int model, size_t n, double x_first, double dx, size_t n_x, double p_first, double dp, size_t n_p,
 	double h_x, double h_p, size_t n_norm, unsigned flags, const double* x, const double* p, const double* b, const int* status, double* rho,
 	long long* tally);
+
+/* ---- exact branching probabilities per energy ----------------------------------------------------------------------------
+ * The time-independent problem under every trajectory curve: for each total energy E the coupled-channel Schrodinger equation
+ *     psi'' = (2 m / hbar^2)(V(x) - E) psi
+ * on the diabatic matrix V of `model` (a built-in id or a user table, as every N-level call), solved by the renormalised Numerov method and read
+ * at the asymptotes.  No packet, no absorber, no clock, no random number; closed channels are handled; fourth order in the grid spacing; unitary
+ * to rounding.
+ * Grid: x_n = x_left + n h, n = 0 ... n_steps, h = (x_right - x_left) / n_steps, V_n = V(x_n).  The potential is taken to be CONSTANT beyond both
+ * ends, V = V_0 for n <= 0 and V = V_{n_steps} for n >= n_steps: that is the problem solved, so the box has to hold everything but the flat
+ * asymptotes (a user table must be flat where the box ends).
+ * Method, with c = (h^2 / 12)(2 m / hbar^2): T_n = c (V_n - E I), U_n = 12 (I - T_n)^-1 - 10 I = (I - T_n)^-1 (2 I + 10 T_n), and for
+ * F_n = (I - T_n) psi_n Numerov's rule F_{n+1} - U_n F_n + F_{n-1} = 0.  Per end, (eps, C) the Jacobi eigen-system of its matrix,
+ * t_j = c (eps_j - E), u_j = 12 / (1 - t_j) - 10, z_j the root of z + 1 / z = u_j that moves or decays to the right: u_j / 2 + i sqrt(1 - u_j^2 / 4)
+ * for |u_j| < 2 (an open channel), else the real root with |z_j| <= 1 (closed); s_j = Im z_j.  z_j^n solves the rule in the constant region
+ * exactly, so the match is exact for the discrete problem and its flux is conserved to rounding; the only method error is the O(h^4) of the rule.
+ * March from the transmitted side: L_{N+1} = C_R diag(1 / z^R) C_R^T; for n = N ... 0: G = L_{n+1}^-1, L_n = U_n - G; for n = N - 1 ... 0:
+ * M <- M G.  At the left, Lambda = C_L^T L_0 C_L, Z = diag(z^L), rho = (Z - Lambda)^-1 (Lambda - Z^-1), tau = C_R^T M C_L (I + rho), and for an
+ * open incoming channel i
+ *     R_{j<-i} = s^L_j |rho_ji|^2 / s^L_i,   T_{j<-i} = s^R_j |tau_ji|^2 / s^L_i,   defect_i = sum_j (R_{j<-i} + T_{j<-i}) - 1.
+ * Channels are the adiabatic surfaces of the ends, ascending.  Incidence is from the left.  A closed final channel j is exactly 0; the column of a
+ * closed incoming channel i is NaN, and so is its defect.  An energy exactly at a threshold (|u_j| = 2) is unspecified: finite or NaN.
+ * energies (n_energies): total energies in the potential's own zero, the convention of gple_dvr_spectrum.
+ * prob: [n_energies][incoming i][side: 0 reflected, 1 transmitted][final j], 2 num_pes^2 doubles per energy.  defect (nullable): [n_energies][i].
+ * One thread per energy; 2 x 2 and 3 x 3 inverses are explicit adjugates.  Two calls give the same bits, and device pointers (GPLE_IO_DEVICE:
+ * energies, prob, defect) give the bits of host pointers.  Timer: GPLE_TIMER_SCATTER (the march alone).
+ * GPLE_ERR_BAD_ARG, with nothing written: num_pes not 2 or 3, a model the other N-level calls refuse, n_energies == 0 or > 2^20, n_steps < 2 or
+ * > 2^24, mass not finite and positive, x_left or x_right not finite or x_left >= x_right, an energy that is not finite (device energies are looked
+ * at on the host first), a null energies or prob, and a grid too coarse for an end channel: c (E_max - eps_min) >= 1/2 with eps_min the lowest
+ * eigenvalue of either end. */
+int gple_scatter(gple_ctx* ctx, int num_pes, int model, double mass, double x_left, double x_right, size_t n_steps, size_t n_energies,
+	const double* energies, unsigned flags, double* prob, double* defect);
 
 /* generate_markov_chain (mc.cpp:118-165) for n walkers at once on the fitted distribution |cut-off prediction| of `element`:
  * num_steps Metropolis steps with uniform displacements in [-max_displacement, max_displacement) per dimension; r (2n) holds
