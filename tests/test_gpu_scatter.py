@@ -7,8 +7,9 @@ straddle the upper threshold inside one wave.  Every entry of prob (all incoming
 D being the largest distance between the float64 and the long double restatement for that case, measured here; NaN columns sit where the
 restatement has them and closed final channels are exactly 0.  An energy is set aside only where the restatement's own |u_j| - 2 is within 1e-9 of
 zero, and none may be.  The closed forms of tests/scatter_cases.py run on the device through tables at dx = 1 / 64 with N = 4000; the bound is
-twice the long double restatement's own distance from the closed form on that table plus the tolerance above.  The ratios measured on the MI355X
-are in DESIGN.md §18."""
+twice the long double restatement's own distance from the closed form on that table plus the tolerance above.  Small grids, in the same pattern:
+the smallest grid accepted (N = 2), 3 and 5, and the grids on which the N + 1 nodes cross a block of the table kernel (255, 256, 257), SAC and
+a DAC table, with n = 1, 64, 65 and 70 energies.  The ratios measured on the MI355X are in DESIGN.md §18."""
 import ctypes as C
 import functools
 
@@ -50,16 +51,19 @@ def closed_table(name):
 
 
 @functools.lru_cache(maxsize=None)
-def reference(name, n):
-    """The case on the restatement, once: float64 and long double, and D"""
+def reference(name, n, box=None, n_steps=N_STEPS, p_max=30.0):
+    """The case on the restatement, once: float64 and long double, and D.  box, n_steps, p_max: another box, grid and largest momentum than
+    the case's own (the small grids)"""
     assert np.finfo(np.longdouble).eps < 1e-18  # or D calibrates nothing
     c = {"tabulated": False, **CASES[name]}
+    if box is not None:
+        c["box"] = box
     pot = HN.table(tabulated(c["model"], c["N"])) if c["tabulated"] else HN.builtin(c["model"], c["N"])
     eps = HN.jacobi(pot(np.array([-c["box"]]))[0])[0][0]
-    p = np.linspace(3.0, 30.0, n)
+    p = np.linspace(3.0, p_max, n)
     energies = p * p / 2.0 / MASS + eps[0]
-    ref = SN.march(pot, c["N"], MASS, -c["box"], c["box"], N_STEPS, energies)
-    wide = SN.march(pot, c["N"], MASS, -c["box"], c["box"], N_STEPS, energies, dtype=np.longdouble)
+    ref = SN.march(pot, c["N"], MASS, -c["box"], c["box"], n_steps, energies)
+    wide = SN.march(pot, c["N"], MASS, -c["box"], c["box"], n_steps, energies, dtype=np.longdouble)
     assert np.array_equal(np.isnan(ref["prob"]), np.isnan(wide["prob"]))
     D = float(np.nanmax(np.abs((ref["prob"] - wide["prob"]).astype(np.float64))))
     closed_final = np.stack([~(np.abs(ref["u_left"]) < 2.0), ~(np.abs(ref["u_right"]) < 2.0)], axis=1)  # (n, side, final surface)
@@ -113,6 +117,40 @@ def test_against_the_restatement(gpu, model_of, name):
             assert len(flips) and (flips // 64 == (flips + 1) // 64).all(), "no threshold inside a wave: the case tests less than it says"
         assert err <= tol, (name, n, err, tol)
         assert open_defect < 1e-11
+
+
+# ---- 1b. small grids: the march reads V_n one step ahead and the table kernel runs (n_steps + 256) / 256 blocks of 256 ------------------------------------------
+# name, box, n_steps, the largest momentum: the smallest grid gple_scatter accepts (2) and 3, an odd small one, and the grids on which
+# n_steps + 1 nodes fill a block but for one, exactly, and with one over.  The largest momentum keeps c (E_max - eps_min) below 1 / 2: a grid
+# without an open discrete channel is refused (BAD_ARG), and the restatement does not refuse
+SMALL_GRIDS = [("sac", 0.25, 2, 9.0), ("sac", 0.25, 3, 14.0), ("sac", 1.0, 5, 6.0), ("sac", 10.0, 255, 30.0), ("sac", 10.0, 256, 30.0), ("sac", 10.0, 257, 30.0),
+               ("table2", 10.0, 255, 30.0), ("table2", 10.0, 256, 30.0)]
+SMALL_SIZES = (1, 64, 65, 70)  # one energy, a full wave, a wave and one lane, a wave and six: exact and ragged last waves of the one-wave workgroups
+
+
+@pytest.mark.parametrize("name, box, n_steps, p_max", SMALL_GRIDS, ids=[f"{name}-{box:g}-{n_steps}" for name, box, n_steps, _ in SMALL_GRIDS])
+def test_small_grids_against_the_restatement(gpu, model_of, name, box, n_steps, p_max):
+    c = reference(name, SMALL_SIZES[0], box, n_steps, p_max)["case"]
+    model = case_model(model_of, c)
+    for n in SMALL_SIZES:
+        ref = reference(name, n, box, n_steps, p_max)
+        prob, defect = gpu.scatter(c["N"], model, MASS, -box, box, n_steps, ref["energies"])
+        again = gpu.scatter(c["N"], model, MASS, -box, box, n_steps, ref["energies"])
+        assert ref["aside"].sum() <= 0  # near_threshold sets nothing aside
+        closed_in = np.isnan(ref["prob"])
+        assert np.array_equal(np.isnan(prob), closed_in) and np.array_equal(np.isnan(defect), np.isnan(ref["defect"]))
+        exact_zero = np.broadcast_to(ref["closed_final"][:, None], prob.shape) & ~closed_in
+        assert (prob[exact_zero] == 0.0).all() and (ref["prob"][exact_zero] == 0.0).all()
+        tol = 64.0 * ref["D"] + 1e-13
+        err = float(np.nanmax(np.abs(prob - ref["prob"])))
+        open_defect = float(np.nanmax(np.abs(defect)))
+        T00 = ref["prob"][:, 0, 1, 0]
+        print(f"scatter small grid {name} box {box:g} N = {n_steps} n = {n}: closed incoming columns {int(np.isnan(ref['defect']).sum())}, closed final entries "
+              f"{int(exact_zero.sum())}, T00 {T00.min():.3g} ... {T00.max():.3g}, D {ref['D']:.3g}, err / tol {err / tol:.3g}, largest |defect| {open_defect:.3g}")
+        assert np.isfinite(T00).all()  # the lowest surface is open at every energy: no case is hollow
+        assert err <= tol, (name, box, n_steps, n, err, tol)
+        assert open_defect < 1e-11
+        assert same_bits(again[0], prob) and same_bits(again[1], defect)  # a repeat
 
 
 # ---- 2. closed forms on the device -------------------------------------------------------------------------------------------------------------------
